@@ -22,13 +22,22 @@ timed region:
 The path has no cross-block data collective; what is exchanged is boundary metadata.  After the clock stops rank 0 concatenates
 the fragments and checks the stream (reference golden at 100 MB / 2^30 bytes, else decompressed by the oracle and compared).
 
-At N=1 the same run also times the other BASELINE.json configs as extra keys of the JSON line (each
+At N=1 a --full run also times the other BASELINE.json configs as extra keys of the JSON line (each
 median of 5 after one warm-up, each checked against its golden / by round trip): `e2e_host_buffer`
 (configs[2] through the host-buffer C ABI: H2D + kernels + D2H), `e2e_js_front` (the same call from Node through
 js/index.js on a Uint8Array — the real boundary), `bzip2_1_compress` (configs[1], device-resident), `bzip2_9_decompress`
 (configs[4], host-buffer ABI), `bwtc_9_compress` (configs[3] at 100 MB, host-buffer ABI, GPU / serial-coder split).
 At N>1 rank 0 times `bzip2_9_decompress` and `bwtc_9_compress` on the whole stream with cjs_opts.n_devices = N (the other
 ranks wait at a host-side barrier): configs[4] and [3] on N GPUs, "replicable stages x N, serial tail x 1".
+
+A plain run (no --full) only sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: the
+headline `value` / `ms_per_step` and the `roofline` below, which both come from the timed steps.  Everything else described
+here (the untimed stage-breakdown step, the checks against the golden / the oracle, `cpu_baseline`, the extra configs) runs
+only with --full.
+
+--dump-outputs DIR writes the .bz2 stream of the last timed step (rank 0's assembled stream at N > 1) as .npy files in float32 /
+float64: `stream_len`, `stream_sample_pos` + `stream_sample` (the whole stream up to DUMP_SAMPLE bytes, else a fixed seeded
+sample of DUMP_SAMPLE positions) and `stream_sha256` (the digest of the whole stream, one byte per element).
 
 One JSON line on stdout (rank 0).  `roofline` = dominant kernel (LSD radix scatter of the suffix sort)
 priced at SURVEY.md §8(d)'s algorithmic bytes (1 B read + out/in B written per input byte) x the
@@ -56,6 +65,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s
 PROFILE_DIR = "r03_final"          # profiles/<dir>/pmc_traffic.json: PMC pass of this command (tools/gpu_round_profile.sh)
+DUMP_SAMPLE = 1 << 22              # stream bytes --dump-outputs stores: 16 MB of float32 bytes + 32 MB of float64 positions at most
 
 
 def log(*a):
@@ -75,7 +85,13 @@ def parse_args():
     ap.add_argument("--strong", action="store_true", help="strong scaling: one 2^30-byte stream split over the ranks")
     ap.add_argument("--strong-mb", type=int, default=0, help="strong scaling on this many 10^6 bytes instead of 2^30")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra configs")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the stage breakdown, the output checks, cpu_baseline and the extra configs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output stream to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -110,6 +126,18 @@ def _golden(name):
 
 def _matches(out, g):
     return bool(g is not None and out.size == g["out_len"] and hashlib.sha256(out.tobytes()).hexdigest() == g["out_sha256"])
+
+
+def dump_outputs(out_dir, stream):
+    """--dump-outputs: the .bz2 stream as .npy files (see the module docstring); the sample positions depend only on its length"""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(stream.size)
+    pos = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    digest = np.frombuffer(hashlib.sha256(stream.tobytes()).digest(), dtype=np.uint8)
+    arrays = {"stream_len": np.array([n], dtype=np.float64), "stream_sample_pos": pos.astype(np.float64),
+              "stream_sample": stream[pos].astype(np.float32), "stream_sha256": digest.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class _Opts(ctypes.Structure):
@@ -350,7 +378,7 @@ def main():
     res = None
     for _ in range(args.steps):
         # inside the timed loop the library only records events (whole call + every full-size launch of the dominant kernel): the
-        # per-stage times need a stream synchronisation per stage and come from one extra, untimed step below
+        # per-stage times need a stream synchronisation per stage and come from one extra, untimed step below (--full only)
         st = pkg.Stats()
         res = step(st)
         agg["dom_ms"] += st.ms_bwt_dominant * st.bwt_dominant_launches
@@ -361,11 +389,23 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    st = pkg.Stats()
-    ctx.set_stage_times(True)
-    step(st)                                             # untimed: stage breakdown (synchronises between the stages)
-    for k in ("ms_total", "ms_rle1", "ms_bwt", "ms_mtf", "ms_huff", "ms_pack"):
-        agg["stage"][k] = getattr(st, k) * args.steps
+    # what the last timed step computed, on the host before anything else runs on the device (only when it is written or checked)
+    need_stream = args.full or args.dump_outputs is not None
+    stream = None
+    if n_gpus == 1:
+        stream_len = res
+        if need_stream:
+            stream = d_out[:res].cpu().numpy()
+    else:
+        (fo, fl, so, sl), metas = res
+        stream_len = int(sl)
+        frag = d_out[fo:fo + fl].cpu().numpy() if need_stream else None
+    if args.full:
+        st = pkg.Stats()
+        ctx.set_stage_times(True)
+        step(st)                                             # untimed: stage breakdown (synchronises between the stages)
+        for k in ("ms_total", "ms_rle1", "ms_bwt", "ms_mtf", "ms_huff", "ms_pack"):
+            agg["stage"][k] = getattr(st, k) * args.steps
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if use_nccl else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -373,13 +413,7 @@ def main():
 
     # ---------------- verification (outside the timed region)
     verify = {}
-    stream = None
-    if n_gpus == 1:
-        out_n = res
-        stream = d_out[:out_n].cpu().numpy()
-    else:
-        (fo, fl, so, sl), metas = res
-        frag = d_out[fo:fo + fl].cpu().numpy()
+    if n_gpus > 1 and need_stream:
         parts = [None] * world
         dist.all_gather_object(parts, (int(so), int(sl), frag.tobytes()), group=host_pg)
         if rank == 0:
@@ -394,7 +428,9 @@ def main():
             stream = np.concatenate(chunks)
             verify["fragments"] = [len(b) for _, _, b in parts]
             verify["blocks"] = int(metas[0].total_blocks)
-    if rank == 0:
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, stream)
+    if rank == 0 and args.full:
         verify["out_len"] = int(stream.size)
         verify["out_sha256"] = hashlib.sha256(stream.tobytes()).hexdigest()
         gname = "golden_big_bzip2_%d_1g.json" % args.level if stream_bytes == 1 << 30 else "golden_big_bzip2_%d_%dm.json" % (args.level, stream_bytes // 1_000_000)
@@ -411,10 +447,10 @@ def main():
             verify["oracle_round_trip"] = bool(rc == 0 and back.size == stream_bytes and np.array_equal(back, data))
             verify["oracle_round_trip_s"] = round(time.perf_counter() - t1, 1)
             assert verify["oracle_round_trip"], "the assembled stream does not decode to the input (oracle rc %d)" % rc
-    out_bytes_total = int(stream.size) if rank == 0 else 0
+    out_bytes_total = stream_len if rank == 0 else 0
 
     cpu_baseline = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         orc = support.Oracle()
         sample = data if stream_bytes <= 200_000_000 else data[:100_000_000]        # bounded: ~10-20 s of CPU work
         t1 = time.perf_counter()
@@ -431,7 +467,7 @@ def main():
 
     # ---------------- the other BASELINE.json configs, timed in the same run (never part of `value`)
     extra = {}
-    if not args.no_extra and args.level == 9 and not args.no_verify:
+    if args.full and not args.no_extra and args.level == 9 and not args.no_verify:
         ctx.close()
         ctx = None
         del d_out, d_in

@@ -118,7 +118,7 @@ def test_bench_starts_its_own_ranks(extra):
     # `python bench.py --gpus 2` with NO launcher: bench.py starts torch.distributed.run itself (before it touches the GPU);
     # gloo for the exchanges, both ranks on GPU 0; the stream is assembled INSIDE the timed region and checked afterwards,
     # and rank 0 times decompress / BWTC over 2 device shares
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline", "--full"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, BENCH_FORCE_DEVICE0="1"), cwd=ROOT, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

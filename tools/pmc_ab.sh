@@ -1,12 +1,14 @@
 #!/bin/bash
 # usage (GPU box): tools/pmc_ab.sh "<kernel substrings, | separated>" "<ENV=val ...>" ... -- FETCH_SIZE and WRITE_SIZE per kernel (summed over one bench step)
+# logs and traces go to $OUT_DIR (default tool_out/); the bench runs use --full (stage step, output checks)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
+out=${OUT_DIR:-tool_out}; mkdir -p $out
 ks=$1; shift
 for e in "$@"; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    rm -rf gpurun_out/pmcab
-    env $e timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d gpurun_out/pmcab -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-extra > gpurun_out/pmcab.log 2>&1 || { tail -5 gpurun_out/pmcab.log; exit 1; }
-    python3 - "$(ls gpurun_out/pmcab/*/*counter_collection.csv)" "$ks" "$e" "$c" <<'PY'
+    rm -rf $out/pmcab
+    env $e timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $out/pmcab -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-extra > $out/pmcab.log 2>&1 || { tail -5 $out/pmcab.log; exit 1; }
+    python3 - "$(ls $out/pmcab/*/*counter_collection.csv)" "$ks" "$e" "$c" <<'PY'
 import csv,sys
 acc={}
 keys=sys.argv[2].split('|')
@@ -20,4 +22,4 @@ for k,v in sorted(acc.items()): print("%-40s %-11s %-34s launches %3d  total %8.
 PY
   done
 done
-rm -rf gpurun_out/pmcab
+rm -rf $out/pmcab
