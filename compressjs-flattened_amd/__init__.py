@@ -81,6 +81,9 @@ def load_library():
     L.cjs_bzip2_compress_device.argtypes = [V, V, S, I, V, S, PS, ctypes.POINTER(Stats)]
     L.cjs_bzip2_compress_device_range.argtypes = [V, V, S, I, ctypes.c_long, ctypes.c_long, V, S, ctypes.POINTER(ctypes.c_uint64),
                                                   V, ctypes.c_long, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(Stats)]
+    L.cjs_bzip2_compress_batch.argtypes = [ctypes.POINTER(u8p), PS, S, I, PP, PS, PS, V]
+    L.cjs_ctx_create_batch.argtypes = [ctypes.POINTER(V), I, S, S, I]
+    L.cjs_bzip2_compress_batch_device.argtypes = [V, V, PS, S, I, V, S, PS, PS]
     L.cjs_bzip2_shard_share_bytes.argtypes = [S, I]
     L.cjs_bzip2_shard_share_bytes.restype = S
     L.cjs_bzip2_shard_tiles.argtypes = [V, V, S, I, I, V]
@@ -125,19 +128,43 @@ def _stream_call(fn, data, *mid):
     return _adopt(out, out_n.value)
 
 
+def _bzip2_level(props):
+    # Q17: typeof props === 'number' -> the level, anything else -> 9 (5.0 is the number 5 in JavaScript)
+    level = props if isinstance(props, (int, float)) and not isinstance(props, bool) else 9
+    if isinstance(level, float) and level == int(level):
+        level = int(level)
+    if level < 1 or level > 9 or not isinstance(level, int):      # (a fractional level is meaningless; the reference does not guard it)
+        raise CjsError(-20, "Invalid block size multiplier")
+    return level
+
+
 class Bzip2:
     """Same surface as the reference's `Bzip2` object for the hot path (returns a uint8 ndarray)."""
 
     @staticmethod
     def compressFile(input, output=None, props=None):
-        # Q17: typeof props === 'number' -> the level, anything else -> 9 (5.0 is the number 5 in JavaScript)
-        level = props if isinstance(props, (int, float)) and not isinstance(props, bool) else 9
-        if isinstance(level, float) and level == int(level):
-            level = int(level)
-        if level < 1 or level > 9 or not isinstance(level, int):      # (a fractional level is meaningless; the reference does not guard it)
-            raise CjsError(-20, "Invalid block size multiplier")
-        res = _stream_call(load_library().cjs_bzip2_compress, input, level)
+        res = _stream_call(load_library().cjs_bzip2_compress, input, _bzip2_level(props))
         return _deliver(res, output)
+
+    @staticmethod
+    def compressFiles(inputs, props=None):
+        """compressFile over a batch: one uint8 ndarray (a .bz2 stream) per input, in input order, all inputs in one pass
+        per stage on the GPU (cjs_bzip2_compress_batch).  The streams are views of one result buffer."""
+        level = _bzip2_level(props)
+        arrs = [_coerce_input(x) for x in inputs]
+        L = load_library()
+        count = len(arrs)
+        ptrs = (u8p * max(count, 1))(*[a.ctypes.data_as(u8p) for a in arrs])
+        lens = (ctypes.c_size_t * max(count, 1))(*[a.size for a in arrs])
+        off = (ctypes.c_size_t * max(count, 1))()
+        ln = (ctypes.c_size_t * max(count, 1))()
+        out = u8p()
+        _check(L.cjs_bzip2_compress_batch(ptrs, lens, count, level, ctypes.byref(out), off, ln, None))
+        if not count:
+            return []
+        total = max(off[k] + ln[k] for k in range(count))
+        buf = _adopt(out, total)
+        return [buf[off[k]: off[k] + ln[k]] for k in range(count)]
 
     @staticmethod
     def decompressFile(input, output=None, multistream=False):
@@ -193,6 +220,29 @@ class DeviceContext:
     def set_stage_times(self, on):
         """stats of later calls: per-stage times (a stream synchronisation per stage) or events only"""
         self.L.cjs_ctx_set_stage_times(self.h, 1 if on else 0)
+
+    @classmethod
+    def batch(cls, device, max_input, max_items, level):
+        """context of the batch path (compress_batch): batches of up to max_input bytes and max_items inputs per pass"""
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.h = ctypes.c_void_p()
+        self.level = level
+        _check(self.L.cjs_ctx_create_batch(ctypes.byref(self.h), device, max_input, max_items, level))
+        return self
+
+    def compress_batch(self, d_in_ptr, in_off, d_out_ptr, out_cap):
+        """input k = d_in[in_off[k] .. in_off[k+1]) (device memory; in_off on the host) -> (out_off, out_len) uint64 arrays:
+        stream k is left at d_out + out_off[k], out_len[k] bytes"""
+        o = np.ascontiguousarray(in_off, dtype=np.uint64)
+        count = max(o.size - 1, 0)
+        off = np.zeros(max(count, 1), dtype=np.uint64)
+        ln = np.zeros(max(count, 1), dtype=np.uint64)
+        PS = ctypes.POINTER(ctypes.c_size_t)
+        keep = o if o.size else np.zeros(1, dtype=np.uint64)
+        _check(self.L.cjs_bzip2_compress_batch_device(self.h, d_in_ptr, keep.ctypes.data_as(PS), count, self.level, d_out_ptr, out_cap,
+                                                      off.ctypes.data_as(PS), ln.ctypes.data_as(PS)))
+        return off[:count], ln[:count]
 
     def close(self):
         if self.h:

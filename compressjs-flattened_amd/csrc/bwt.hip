@@ -22,6 +22,14 @@ namespace cjs {
 
 struct Geom { uint32_t nb, stride, n_last; };
 __device__ __forceinline__ uint32_t blk_len(const Geom& g, uint32_t blk) { return blk == g.nb - 1 ? g.n_last : g.stride; }
+// Blocks of different lengths in slots of one stride (a batch of independent inputs: one block per input, bwt_run_var).
+// Slot positions at or past a block's length are holes: round 1 gives them keys that sort behind the block's suffixes and
+// resolve as singletons there, so no later round sees them.  The kernels take the geometry as a template parameter: the
+// fixed-geometry instantiation (bwt_run) is the code it was before.
+struct VarGeom { uint32_t nb, stride, n_last; const uint32_t* len; };
+__device__ __forceinline__ uint32_t blk_len(const VarGeom& g, uint32_t blk) { return g.len[blk]; }
+template <typename G> struct is_var_geom { static constexpr bool value = false; };
+template <> struct is_var_geom<VarGeom> { static constexpr bool value = true; };
 
 // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2),
 // so workgroup w = 8*j + x works on tile x*ceil(T/8) + j: every XCD walks ONE contiguous range of the
@@ -344,13 +352,20 @@ __global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, con
 // suffix-sort kernels
 // ------------------------------------------------------------------------------------------
 // round 0 keys: (block id, first nsym symbols).  cyclic: bytes wrap; sentinel: 9-bit symbols, 0 = past the end
-__global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__ T, Geom g, int cyclic, int nsym, uint32_t M,
+// VarGeom: one more bit between the block id and the symbols flags a hole; a hole's symbols are its position (unique)
+template <typename G>
+__global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__ T, G g, int cyclic, int nsym, uint32_t M,
                                                      uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
   for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < M; a += (uint64_t)gridDim.x * 256) {
     const uint32_t blk = (uint32_t)(a / g.stride), i = (uint32_t)(a - (uint64_t)blk * g.stride), n = blk_len(g, blk);
     const uint8_t* t = T + (size_t)blk * g.stride;
     uint64_t k = 0;
-    if (cyclic) {
+    if constexpr (is_var_geom<G>::value) {
+      uint32_t x = i;
+      if (i >= n) k = (1ull << (8 * nsym)) | i;
+      else for (int j = 0; j < nsym; j++) { k = (k << 8) | t[x]; if (++x == n) x = 0; }
+      k |= (uint64_t)blk << (8 * nsym + 1);
+    } else if (cyclic) {
       uint32_t x = i;
       for (int j = 0; j < nsym; j++) { k = (k << 8) | t[x]; if (++x == n) x = 0; }
       k |= (uint64_t)blk << (8 * nsym);
@@ -373,7 +388,8 @@ __global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__
 struct HalfMap { uint32_t halves, stride; };      // halves 2: the two sweeps are the launches SWEEP 1 and SWEEP 2 of bwt_apply
 
 // round r>=1 keys: (group ordinal, rank of suffix i+h)
-__global__ __launch_bounds__(256) void bwt_gather_keys(Geom g, int cyclic, uint32_t A, uint32_t h, const uint32_t* __restrict__ R,
+template <typename G>
+__global__ __launch_bounds__(256) void bwt_gather_keys(G g, int cyclic, uint32_t A, uint32_t h, const uint32_t* __restrict__ R,
                                                        const uint32_t* __restrict__ val, const uint32_t* __restrict__ pos,
                                                        const uint32_t* __restrict__ gord, uint64_t* __restrict__ key, uint32_t T) {
   const uint32_t tile = xcd_tile(blockIdx.x, T);
@@ -526,9 +542,9 @@ __device__ __forceinline__ uint64_t class_head_before(const uint64_t* __restrict
 // in front -- sweep 1 stores the ranks of the lower half-blocks and leaves the tile counts that bwt_flags would have made
 // (it finds the one class head it cannot see by search: class_head_before); sweep 2 stores the upper half and, with the
 // scanned counts, everything else.
-template <bool FIRST, bool PACKED, int SWEEP = 0>      // FIRST: round 1 - slot a is sorted position a, and there is no previous grouping
+template <bool FIRST, bool PACKED, int SWEEP = 0, typename G = Geom>      // FIRST: round 1 - slot a is sorted position a, and there is no previous grouping
 __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val,
-                                                 const uint32_t* __restrict__ pos, uint32_t A, Geom g,
+                                                 const uint32_t* __restrict__ pos, uint32_t A, G g,
                                                  uint32_t* tile_cnt, uint32_t T,
                                                  uint32_t* __restrict__ R, uint32_t* __restrict__ SA,
                                                  uint32_t* __restrict__ nval, uint32_t* __restrict__ npos, uint32_t* __restrict__ ngord, HalfMap hm_,
@@ -697,15 +713,16 @@ constexpr uint32_t TS_WIN = 4096, TS_MAXGRP = 1024, TS_NOM = TS_WIN - TS_MAXGRP,
 // fetches its rank and writes its key: the window that owns its group, else the window whose nominal range holds it.  The
 // only group a window cannot see whole is the one that runs into it from the left; whether the window before owns that one
 // (<= TS_MAXGRP members, all inside its 4096 slots) follows from the 1024 ordinals in front of the window.
-struct TsGather { const uint32_t* R; const uint32_t* pos; const uint32_t* gord; uint32_t h; int cyclic; Geom g; };
+template <typename G> struct TsGatherT { const uint32_t* R; const uint32_t* pos; const uint32_t* gord; uint32_t h; int cyclic; G g; };
+using TsGather = TsGatherT<Geom>;
 // slot of step s of a thread: 64 consecutive slots per wave instruction in both layouts (word of a slot = slot >> 6)
 template <bool WMAP> __device__ __forceinline__ uint32_t ts_slot(int s, int tid) {
   return WMAP ? (uint32_t)(tid >> 6) * 1024u + (uint32_t)s * 64u + (uint32_t)(tid & 63) : (uint32_t)s * 256u + (uint32_t)tid;
 }
 // Loads of the fused form (all issued before the first use): ordinals, suffixes and sorted positions of the window, and the
 // position (+1) of the last ordinal in front of the window that differs from the window's first one (this thread's four).
-template <bool WMAP>
-__device__ __forceinline__ uint32_t ts_fused_load(const TsGather& tg, const uint32_t* __restrict__ val, uint64_t wb, uint32_t L,
+template <bool WMAP, typename TG>
+__device__ __forceinline__ uint32_t ts_fused_load(const TG& tg, const uint32_t* __restrict__ val, uint64_t wb, uint32_t L,
                                                   uint32_t (&go)[16], uint32_t (&pv)[16], uint32_t (&pp)[16], uint32_t& gprev) {
   const int tid = threadIdx.x;
 #pragma unroll
@@ -736,7 +753,8 @@ __device__ __forceinline__ uint32_t ts_prev_end(uint64_t wb, uint32_t L, bool at
   return sb + e <= TS_MAXGRP ? e : 0u;
 }
 // rank keys of the slots in `need` (bit s = step s): R[suffix + h] + 1 of the suffix's block, 0 past the end (sentinel form)
-__device__ __forceinline__ void ts_fused_gather(const TsGather& tg, uint32_t need, const uint32_t (&pv)[16], uint32_t (&pp)[16], uint32_t (&rk20)[16]) {
+template <typename TG>
+__device__ __forceinline__ void ts_fused_gather(const TG& tg, uint32_t need, const uint32_t (&pv)[16], uint32_t (&pp)[16], uint32_t (&rk20)[16]) {
   uint32_t past = 0;
 #pragma unroll
   for (int s = 0; s < 16; s++) {
@@ -757,8 +775,9 @@ __device__ __forceinline__ void ts_ce(uint64_t& a, uint64_t& b, bool up) {
   const uint64_t x = sw ? b : a, y = sw ? a : b;
   a = x; b = y;
 }
+template <typename TG>
 __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t A,
-                                                     uint8_t* __restrict__ dflag, TsGather tg, uint32_t Tt) {
+                                                     uint8_t* __restrict__ dflag, TG tg, uint32_t Tt) {
   __shared__ uint64_t sk[TS_WIN];
   __shared__ uint64_t hm[64];                    // head mask of the window
   __shared__ int32_t wlast[64], wnext[64];       // last head before word / first head after word (window slot, -1 / TS_WIN+1 = none)
@@ -933,8 +952,9 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
 // composite (4 passes of 8 bits, wave64 match-any ranking, one LDS staging array) is then a permutation INSIDE every owned
 // group: exactly h slots carry a composite below (h << 20), so the members of the group headed at h land on [h, h + size).
 // The cost does not depend on the group sizes (the counting / bitonic version above degrades with them).
+template <typename TG>
 __global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t A,
-                                                           uint8_t* __restrict__ dflag, TsGather tg, uint32_t Tt) {
+                                                           uint8_t* __restrict__ dflag, TG tg, uint32_t Tt) {
   __shared__ uint64_t se[TS_WIN];                // (composite << 32) | suffix: staging of a pass
   __shared__ uint64_t hm[64];
   __shared__ int32_t wlast[64], wnext[64];
@@ -1125,8 +1145,9 @@ __global__ __launch_bounds__(256) void bwt_defer_scatter(uint32_t D, const uint6
   }
 }
 
+template <typename G>
 __global__ __launch_bounds__(256) void bwt_flush_active(uint32_t A, const uint32_t* __restrict__ val, const uint32_t* __restrict__ pos,
-                                                        uint32_t* __restrict__ SA, Geom g, const uint8_t* __restrict__ Tx, uint8_t* __restrict__ U, int carried) {
+                                                        uint32_t* __restrict__ SA, G g, const uint8_t* __restrict__ Tx, uint8_t* __restrict__ U, int carried) {
   for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < A; a += (uint64_t)gridDim.x * 256) {
     const uint32_t p = pos[a], v = val[a] & PK_POS_MASK;
     if (U && carried) U[p] = (uint8_t)(val[a] >> VAL_PREV_SHIFT);
@@ -1234,7 +1255,8 @@ __global__ __launch_bounds__(256) void bwt_phase2_records(const uint64_t* __rest
 
 // primary index.  cyclic: last row of the group of rotation 0 (equal rotations are ordered by
 // descending start, J/Bzip2_joined_.js:957-968); sentinel: (row of suffix 0)+1
-__global__ __launch_bounds__(256) void bwt_pidx(Geom g, int cyclic, int leftover, const uint32_t* __restrict__ R, uint32_t* __restrict__ pidx) {
+template <typename G>
+__global__ __launch_bounds__(256) void bwt_pidx(G g, int cyclic, int leftover, const uint32_t* __restrict__ R, uint32_t* __restrict__ pidx) {
   __shared__ uint32_t sm[4];
   const uint32_t blk = blockIdx.x, n = blk_len(g, blk);
   const uint32_t* r = R + (size_t)blk * g.stride;
@@ -1360,15 +1382,17 @@ template int radix_pass_segments_public<uint32_t>(hipStream_t, BwtWork&, uint32_
 // Which tile sorter: the LDS radix version costs the same whatever the groups look like (18 ps per suffix), the counting /
 // bitonic version is cheaper once the groups are tiny (round 2 of the bench text, 7.7 suffixes per group: 1.51 vs 1.82 ms;
 // round 3, 3.5 per group: 0.67 vs 0.64 ms; later rounds up to 2x in favour of counting).
-static void launch_tile_sort(hipStream_t s, uint32_t Tt, uint64_t* key, uint32_t* val, uint32_t A, uint8_t* dflag, uint32_t ngroups, const TsGather& tg) {
-  if (ngroups && A / ngroups >= 5) hipLaunchKernelGGL(bwt_tile_sort_radix, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, A, dflag, tg, Tt);
-  else hipLaunchKernelGGL(bwt_tile_sort, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, A, dflag, tg, Tt);
+template <typename TG>
+static void launch_tile_sort(hipStream_t s, uint32_t Tt, uint64_t* key, uint32_t* val, uint32_t A, uint8_t* dflag, uint32_t ngroups, const TG& tg) {
+  if (ngroups && A / ngroups >= 5) hipLaunchKernelGGL(bwt_tile_sort_radix<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, A, dflag, tg, Tt);
+  else hipLaunchKernelGGL(bwt_tile_sort<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, A, dflag, tg, Tt);
 }
 // the tile sorters take the round (small remainders: whole-array radix passes on keys that bwt_gather_keys writes first)
 static bool tile_sorted_round(uint32_t A) { return A >= 2 * TS_WIN; }
 // One sort of a round >= 2: in-LDS tile sort of the small groups + global radix passes for the large ones.
 // Works in place on (key[c], val[c]); only the whole-array fallback flips c.
-static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int bits, LaunchTimes* lt, uint32_t ngroups, const TsGather& tg) {
+template <typename TG>
+static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int bits, LaunchTimes* lt, uint32_t ngroups, const TG& tg) {
   if (!tile_sorted_round(A)) return radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, lt);      // (bwt_gather_keys made the keys)
   const uint32_t Tt = (A + TS_NOM - 1) / TS_NOM, Tg = (A + TS_GT - 1) / TS_GT;
   uint8_t* dflag = w.dflag;
@@ -1403,14 +1427,19 @@ static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int
   return 0;
 }
 
-int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, uint32_t n_last,
-            bool cyclic, uint8_t* d_U, uint32_t* d_pidx, cjs_stats* stats, bool resolve_stats) {
+// G = Geom: every block `stride` long but the last (n_last).  G = VarGeom: block k is g.len[k] <= stride long, every slot of
+// the array is `stride` wide (n_last == stride), and round 1 takes the unsegmented path with the hole bit (bwt_init_keys).
+template <typename G>
+static int bwt_run_impl(hipStream_t s, BwtWork& w, const uint8_t* d_T, const G g, bool cyclic, uint8_t* d_U, uint32_t* d_pidx,
+                        cjs_stats* stats, bool resolve_stats) {
+  constexpr bool VAR = is_var_geom<G>::value;
+  const uint32_t nb = g.nb, stride = g.stride, n_last = g.n_last;
   if (nb == 0) return 0;
+  if (VAR && (!cyclic || n_last != stride)) return CJS_E_INVALID_ARG;
   const uint64_t M64 = (uint64_t)(nb - 1) * stride + n_last;
   if (M64 > w.cap || M64 >= 0xFFFFF000ull) return CJS_E_INVALID_ARG;
   if (stride > (1u << 20) - 2) return CJS_E_INVALID_ARG;          // ranks must fit 20 bits
   const uint32_t M = (uint32_t)M64;
-  const Geom g{nb, stride, n_last};
   const uint32_t max_n = nb > 1 ? stride : n_last;
   const int grid_lin = (int)((M + 255) / 256 < 65535u * 16u ? (M + 255) / 256 : 65535u * 16u);
   LaunchTimes& lt = w.lt; lt.reset(); lt.enabled = stats != nullptr; lt.min_elems = M;      // the roofline is priced on the full-size scatter passes
@@ -1422,8 +1451,8 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
   // was carved for, e.g. many tiny blocks): keys materialised with the block id on top, sorted as one array.
   const int sym_bits = cyclic ? 8 : 9;
   const uint32_t tps = ((nb > 1 ? stride : n_last) + RS_TILE - 1) / RS_TILE;
-  const bool segmented = (uint64_t)nb * tps <= w.hist_tiles && nb <= w.bintot_segs && getenv("CJS_NO_SEGMENTED_SORT") == nullptr;
-  const int blk_bits = bits_for(nb - 1);
+  const bool segmented = !VAR && (uint64_t)nb * tps <= w.hist_tiles && nb <= w.bintot_segs && getenv("CJS_NO_SEGMENTED_SORT") == nullptr;
+  const int blk_bits = bits_for(nb - 1) + (VAR ? 1 : 0);           // (VarGeom: + the hole bit)
   int nsym = segmented ? 7 : (64 - blk_bits) / sym_bits;
   if (nsym > 7) nsym = 7;
   // packed round-1 records (5 bytes + position in one u64, no value array) for cyclic, segmented sorts, as a two-phase sort:
@@ -1435,14 +1464,15 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
   if (packed) nsym = 7;
   const SegGeom sg{nb, stride, n_last, tps};
   const GenSrc gen{d_T, cyclic ? 1 : 0, nsym, packed ? 2 : 0};
-  if (!segmented) hipLaunchKernelGGL(bwt_init_keys, dim3(grid_lin), dim3(256), 0, s, d_T, g, (int)cyclic, nsym, M, w.key[0], w.val[0]);
+  if (VAR && nsym < 3) return CJS_E_INVALID_ARG;                   // a hole's position must fit its symbol bits
+  if (!segmented) hipLaunchKernelGGL(bwt_init_keys<G>, dim3(grid_lin), dim3(256), 0, s, d_T, g, (int)cyclic, nsym, M, w.key[0], w.val[0]);
   uint32_t A = M, h = (uint32_t)nsym, rounds = 0, ngroups = 0;
   w.no_large_groups = false;
   int bits = nsym * sym_bits + (segmented ? 0 : blk_bits);
   // two-sweep scheduling of the round-1 rank scatter (see HalfMap): pays only with the packed records (the second sweep of the
   // 12-byte key + value form re-reads more than the merged stores save: 2.15 vs 1.64 ms)
   const bool sweeps = nb >= 8 && packed;
-  TsGather tg{nullptr, nullptr, nullptr, 0u, 0, g};
+  TsGatherT<G> tg{nullptr, nullptr, nullptr, 0u, 0, g};
   // cyclic form: the regroup kernels write the BWT bytes of the suffixes they resolve themselves; the sentinel form keeps a suffix array
   const uint8_t* dT = cyclic ? d_T : nullptr;
   uint8_t* dU = cyclic ? d_U : nullptr;
@@ -1461,11 +1491,11 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
     const uint32_t T = (A + RS_TILE - 1) / RS_TILE;
     if (rounds == 0 && sweeps) {                                       // two launches, no counting pass (see bwt_apply)
       const HalfMap hm{2u, stride};
-      hipLaunchKernelGGL((bwt_apply<true, true, 1>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      hipLaunchKernelGGL((bwt_apply<true, true, 1, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                          w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
       hipLaunchKernelGGL(bwt_scan_tiles, dim3(1), dim3(1024), 0, s, w.tile_cnt, T, w.counters, w.h_counters);
       CJS_HIP_TRY(hipEventRecord(w.ev_scan, s));
-      hipLaunchKernelGGL((bwt_apply<true, true, 2>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      hipLaunchKernelGGL((bwt_apply<true, true, 2, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                          w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
     } else {
     hipLaunchKernelGGL(bwt_flags, dim3(T), dim3(256), 0, s, w.key[c], A, w.tile_cnt, T, rounds == 0 ? gs1 : 0, w.counters + 4, rounds == 0 ? stride : 0u);
@@ -1474,11 +1504,11 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
     if (rounds == 0) {
       const HalfMap hm{1u, stride};
       const uint32_t grid = xcd_grid(T);
-      if (packed) hipLaunchKernelGGL((bwt_apply<true, true>), dim3(grid), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      if (packed) hipLaunchKernelGGL((bwt_apply<true, true, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                                      w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-      else hipLaunchKernelGGL((bwt_apply<true, false>), dim3(grid), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      else hipLaunchKernelGGL((bwt_apply<true, false, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                               w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-    } else hipLaunchKernelGGL((bwt_apply<false, false>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+    } else hipLaunchKernelGGL((bwt_apply<false, false, 0, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                               w.val[1 - c], w.pos[1 - pc], w.gord, HalfMap{1u, stride}, dT, dU, w.counters + 4, gs1, carried);
     }
     // the host only needs the counters of the tile scan: it waits for THAT kernel and queues the next round behind the regroup
@@ -1492,20 +1522,20 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
     A = A2; ngroups = NG;
     if (A == 0) break;
     if (cyclic && h >= max_n) {     // only groups of equal rotations are left
-      hipLaunchKernelGGL(bwt_flush_active, dim3((A + 255) / 256), dim3(256), 0, s, A, w.val[c], w.pos[pc], w.SA, g, dT, dU, carried);
+      hipLaunchKernelGGL(bwt_flush_active<G>, dim3((A + 255) / 256), dim3(256), 0, s, A, w.val[c], w.pos[pc], w.SA, g, dT, dU, carried);
       break;
     }
     if (rounds > 40) return CJS_E_HIP;    // cannot happen: depth doubles every round
-    if (tile_sorted_round(A)) tg = TsGather{w.R, w.pos[pc], w.gord, h, (int)cyclic, g};       // the tile sorters fetch the ranks themselves
+    if (tile_sorted_round(A)) tg = TsGatherT<G>{w.R, w.pos[pc], w.gord, h, (int)cyclic, g};       // the tile sorters fetch the ranks themselves
     else {
       const uint32_t Tg = (A + RS_TILE - 1) / RS_TILE;
-      hipLaunchKernelGGL(bwt_gather_keys, dim3(xcd_grid(Tg)), dim3(256), 0, s, g, (int)cyclic, A, h, w.R, w.val[c], w.pos[pc], w.gord, w.key[c], Tg);
+      hipLaunchKernelGGL(bwt_gather_keys<G>, dim3(xcd_grid(Tg)), dim3(256), 0, s, g, (int)cyclic, A, h, w.R, w.val[c], w.pos[pc], w.gord, w.key[c], Tg);
     }
     h = h < (1u << 29) ? h * 2 : h;
     bits = 20 + bits_for(NG ? NG - 1 : 0);
   }
-  hipLaunchKernelGGL(bwt_pidx, dim3(nb), dim3(256), 0, s, g, (int)cyclic, (int)(A != 0), w.R, d_pidx);
-  if (!cyclic) {
+  hipLaunchKernelGGL(bwt_pidx<G>, dim3(nb), dim3(256), 0, s, g, (int)cyclic, (int)(A != 0), w.R, d_pidx);
+  if constexpr (!VAR) if (!cyclic) {
     const uint32_t Tn = (M + RS_TILE - 1) / RS_TILE;
     hipLaunchKernelGGL(bwt_emit_sentinel, dim3(xcd_grid(Tn)), dim3(256), 0, s, d_T, g, M, w.SA, w.R, d_U, Tn);
   }
@@ -1516,6 +1546,16 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
     lt.resolve(stats);
   }
   return 0;
+}
+
+int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, uint32_t n_last,
+            bool cyclic, uint8_t* d_U, uint32_t* d_pidx, cjs_stats* stats, bool resolve_stats) {
+  return bwt_run_impl(s, w, d_T, Geom{nb, stride, n_last}, cyclic, d_U, d_pidx, stats, resolve_stats);
+}
+
+int bwt_run_var(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, const uint32_t* d_len,
+                uint8_t* d_U, uint32_t* d_pidx) {
+  return bwt_run_impl(s, w, d_T, VarGeom{nb, stride, stride, d_len}, true, d_U, d_pidx, nullptr, true);
 }
 
 }  // namespace cjs

@@ -161,5 +161,9 @@ struct BwtWork {
 // and writes the BWT bytes to d_U (same layout) and the primary indices to d_pidx[nb].
 int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, uint32_t n_last,
             bool cyclic, uint8_t* d_U, uint32_t* d_pidx, cjs_stats* stats, bool resolve_stats = true);
+// Cyclic form over nb blocks of DIFFERENT lengths (a batch of independent inputs): block k = d_T[k*stride .. +d_len[k]),
+// 1 <= d_len[k] <= stride (device array); BWT bytes to d_U with the same layout.  The slots past a block's length are ignored.
+int bwt_run_var(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, const uint32_t* d_len,
+                uint8_t* d_U, uint32_t* d_pidx);
 
 }  // namespace cjs

@@ -52,4 +52,13 @@ int huff_pack_run(hipStream_t s, HuffWork& w, uint32_t nb_total, uint32_t first,
                   const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
                   uint32_t* d_out32, size_t out_cap_bytes, const PackShard* ps = nullptr);    // scalars[2] = 1 and nothing written if the stream does not fit
 
+// Batches of independent streams (cjs_bzip2_compress_batch*), one per block: framed = header, block j, trailer; else block j's
+// bare bit string from bit 0.  Item j lands at byte d_soff[j] (4-byte aligned, from `base` on, in block order); d_slen[j] = its
+// length in bytes, w.scalars[0] = bytes of all of them (aligned).  The pack run writes them into d_out32, whose range
+// [base, base + scalars[0]) the caller has zeroed.
+int huff_batch_offsets_run(hipStream_t s, HuffWork& w, uint32_t nb, uint64_t base, int framed, uint64_t* d_soff, uint32_t* d_slen);
+int huff_batch_pack_run(hipStream_t s, HuffWork& w, uint32_t nb, int level, int framed, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
+                        const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
+                        const uint64_t* d_soff, uint32_t* d_out32);
+
 }  // namespace cjs

@@ -755,6 +755,62 @@ __global__ void pack_frame(HuffBufs hb, uint32_t nb_range_end, int level, int wr
   *total_bits = bit;
 }
 
+// ------------------------------------------------------------------ batches of independent streams
+// framed: stream j = 'BZh<level>', block j, end-of-stream magic and CRC (= the block's CRC: the fold of one block from 0);
+// else the bare bit string of block j from bit 0 (a block of an input of several blocks, assembled into its stream later).
+// They follow each other at 4-byte-aligned byte offsets from `base`; one workgroup scans their sizes.  sc[0] = total bytes
+// (aligned), sc[2] = 0 (the pack kernels' "output too small" flag: the caller has made room).
+__global__ __launch_bounds__(1024) void huff_batch_offsets(HuffBufs hb, uint32_t nb, uint64_t base, int framed, uint64_t* __restrict__ soff,
+                                                          uint32_t* __restrict__ slen, uint64_t* __restrict__ sc) {
+  __shared__ uint64_t sm[16];
+  uint64_t run = 0;
+  for (uint32_t c0 = 0; c0 < nb; c0 += 1024) {
+    const uint32_t j = c0 + threadIdx.x;
+    const uint64_t bytes = j < nb ? ((framed ? 112u : 0u) + (uint64_t)hb.bitlen[j] + 7u) / 8u : 0u;
+    uint64_t tot;
+    const uint64_t ex = block_excl_sum<1024>((bytes + 3u) & ~(uint64_t)3, sm, tot);
+    if (j < nb) { const uint64_t o = base + run + ex; soff[j] = o; slen[j] = (uint32_t)bytes; hb.bitoff[j] = o * 8u + (framed ? 32u : 0u); }
+    run += tot;
+  }
+  if (threadIdx.x == 0) { sc[0] = run; sc[2] = 0; }
+}
+// header word and trailer of every stream (the pack kernels have written the block behind the header word)
+__global__ __launch_bounds__(256) void huff_batch_frame(HuffBufs hb, uint32_t nb, int level, const uint32_t* __restrict__ block_crc,
+                                                        const uint64_t* __restrict__ soff, uint32_t* __restrict__ out32) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= nb) return;
+  out32[soff[j] >> 2] = __builtin_bswap32(0x425a6830u + (uint32_t)level);      // 'B''Z''h''0'+level (a word of its own)
+  uint64_t bit = hb.bitoff[j] + hb.bitlen[j];
+  const uint64_t vals[2] = {0x177245385090ull, (uint64_t)block_crc[j]};
+  const uint32_t nbs[2] = {48, 32};
+  for (int q = 0; q < 2; q++) {
+    uint32_t left = nbs[q];
+    while (left) {
+      const uint32_t o = (uint32_t)(bit & 31), room = 32 - o, take = left < room ? left : room;
+      const uint32_t chunk = (uint32_t)((vals[q] >> (left - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
+      atomicOr(&out32[bit >> 5], __builtin_bswap32(chunk << (room - take)));
+      left -= take; bit += take;
+    }
+  }
+}
+
+int huff_batch_offsets_run(hipStream_t s, HuffWork& w, uint32_t nb, uint64_t base, int framed, uint64_t* d_soff, uint32_t* d_slen) {
+  if (!nb) return 0;
+  hipLaunchKernelGGL(huff_batch_offsets, dim3(1), dim3(1024), 0, s, w.b, nb, base, framed, d_soff, d_slen, w.scalars);
+  CJS_HIP_TRY(hipGetLastError());
+  return 0;
+}
+int huff_batch_pack_run(hipStream_t s, HuffWork& w, uint32_t nb, int level, int framed, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
+                        const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
+                        const uint64_t* d_soff, uint32_t* d_out32) {
+  if (!nb) return 0;
+  hipLaunchKernelGGL(pack_block, dim3(nb), dim3(1024), 0, s, w.b, 0u, d_A, a_stride, d_npos, d_asz, d_alist, d_block_crc, d_pidx, d_out32, w.scalars + 2);
+  hipLaunchKernelGGL(pack_data, dim3((unsigned)(w.b.tile_stride - 1), nb), dim3(1024), 0, s, w.b, d_A, a_stride, d_npos, d_out32, w.scalars + 2);
+  if (framed) hipLaunchKernelGGL(huff_batch_frame, dim3((nb + 255) / 256), dim3(256), 0, s, w.b, nb, level, d_block_crc, d_soff, d_out32);
+  CJS_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 size_t HuffWork::bytes_needed(size_t max_blocks, uint32_t stride) {
   size_t b = 0;

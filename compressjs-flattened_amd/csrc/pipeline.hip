@@ -5,6 +5,7 @@
 #include "rle1.h"
 #include "mtf.h"
 #include "huff.h"
+#include "ctx.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -19,28 +20,6 @@ using namespace cjs;
 
 namespace cjs { int select_device(const cjs_opts* opts); }
 
-struct cjs_ctx {
-  int device = 0, level = 0;
-  uint32_t cap = 0;
-  size_t max_input = 0, max_blocks = 0, range_blocks = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t side = nullptr;            // block CRCs run here, beside the suffix sort
-  hipStream_t tail = nullptr;            // MTF / Huffman tables of a finished piece run here, beside the suffix sort of the next piece
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_piece[8] = {}, ev_tail = nullptr;
-  Arena arena;
-  Rle1Work rle;
-  BwtWork bwt;
-  MtfWork mtf;
-  HuffWork huff;
-  uint8_t* d_blocks = nullptr;
-  uint8_t* d_U = nullptr;
-  uint32_t* d_pidx = nullptr;
-  uint64_t* h_scalars = nullptr;   // pinned
-  EventTimer timer;
-  // phase state of a multi-GPU job (cjs_bzip2_shard_tiles -> _blocks -> _pack)
-  uint32_t sh_nb = 0, sh_first = 0, sh_cnt = 0, sh_state = 0;
-  bool stage_times = true;         // cjs_ctx_set_stage_times
-};
 
 extern "C" int cjs_ctx_create(cjs_ctx** out, int device, size_t max_input, int level) {
   return cjs_ctx_create_sharded(out, device, max_input, 0, level);
@@ -108,6 +87,7 @@ extern "C" void cjs_ctx_destroy(cjs_ctx* c) {
   if (c->side) (void)hipStreamDestroy(c->side);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->h_scalars) (void)hipHostFree(c->h_scalars);
+  if (c->batch) batch_destroy(c->batch);
   c->bwt.release_host();
   c->rle.release();
   c->arena.destroy();
@@ -687,7 +667,9 @@ extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
+namespace cjs { void batch_trim(); }
 extern "C" void cjs_trim(void) {
+  batch_trim();
   DevPool::trim();
   HostPool::trim();
   int cur = 0;

@@ -40,6 +40,19 @@ int rle1_run(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, uint32
 int rle1_tiles(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, uint32_t t0, uint32_t t1, uint8_t* share, uint32_t tpr);
 int rle1_tables_from_shares(hipStream_t s, Rle1Work& w, uint64_t N, const uint8_t* d_recv, uint32_t tpr);
 int rle1_walk_run(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, uint32_t* nblocks_host, uint32_t* last_len_host = nullptr);
+// Batches of independent inputs (input k = d_in[d_se[2k] .. d_se[2k+1]), d_se on the device):
+//   rle1_batch_len: RLE1 length of every input, d_len2[k] = min(len, cap + 1) << 1 | (last byte absorbed into a run-length byte);
+//   rle1_batch_walk: block boundaries of the inputs d_item[0..count) (RleBlock s / e relative to the input, len), at most
+//     d_tbase[j+1] - d_tbase[j] of them from d_blocks + d_tbase[j], their number to d_nblk[j];
+//   rle1_batch_materialize: RLE1 bytes of blocks d_blk[0..nb) (s / e relative to d_in), block j at d_blocks + j*stride.
+int rle1_batch_len(hipStream_t s, const uint8_t* d_in, const uint64_t* d_se, uint32_t count, uint32_t cap, uint64_t* d_len2);
+int rle1_batch_walk(hipStream_t s, const uint8_t* d_in, const uint64_t* d_se, const uint32_t* d_item, const uint32_t* d_tbase, uint32_t count,
+                    uint32_t cap, RleBlock* d_blocks, uint32_t* d_nblk);
+int rle1_batch_materialize(hipStream_t s, const uint8_t* d_in, const RleBlock* d_blk, uint32_t nb, uint32_t stride, uint8_t* d_blocks);
+// CRC-32 (bzip2 form) of byte ranges [d_blocks[k].s, d_blocks[k].e) of d_data, k < min(count, *d_nblocks); d_seg_crc holds
+// count * max_segs words, max_segs >= (longest range) / 16 KiB + 2
+int crc_ranges(hipStream_t s, const uint8_t* d_data, const RleBlock* d_blocks, const uint32_t* d_nblocks, uint32_t count, uint32_t max_segs,
+               uint32_t* d_seg_crc, uint32_t* d_crc_out);
 int rle1_finish(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, uint32_t first, uint32_t count, uint8_t* d_blocks,
                 hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr);
 

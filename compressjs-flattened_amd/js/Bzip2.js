@@ -36,6 +36,15 @@ Bzip2.compressFile = function (inStream, outStream, props) {
   try { result = common.addon().bzip2Compress(input.bytes, level); } catch (e) { rethrow(e); }
   return common.deliver(result, outStream);
 };
+// Bzip2.compressFile over a batch: one stream per input, in input order, all inputs in one pass per stage on the GPU
+Bzip2.compressFiles = function (inStreams, props) {
+  var level = 9;
+  if (typeof props === 'number') { level = props; }
+  if (level < 1 || level > 9) { throw new Error('Invalid block size multiplier'); }
+  var inputs = [];
+  for (var i = 0; i < inStreams.length; i++) { inputs.push(common.coerceInput(inStreams[i]).bytes); }
+  try { return common.addon().bzip2CompressBatch(inputs, level); } catch (e) { rethrow(e); }
+};
 Bzip2.decompressFile = function (inStream, outStream, multistream) {
   var input = common.coerceInput(inStream);
   var result;

@@ -78,6 +78,14 @@ int cjs_bzip2_compress(const uint8_t *in, size_t n, int level, uint8_t **out, si
 int cjs_bzip2_decompress(const uint8_t *in, size_t n, int multistream, uint8_t **out, size_t *out_n, const cjs_opts *opts);
 int cjs_bwtc_compress(const uint8_t *in, size_t n, int level, uint8_t **out, size_t *out_n, const cjs_opts *opts);
 int cjs_bwtc_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, const cjs_opts *opts);
+/* Bzip2.compressFile over a batch: `count` independent inputs (in[k], n[k] bytes; n[k] may be 0) at one level, one .bz2 stream
+ * per input, stream k byte-identical to cjs_bzip2_compress(in[k], n[k], level).  The library allocates ONE result buffer
+ * (*out, released with cjs_free): stream k is bytes [off[k], off[k] + len[k]) of it (4-byte-aligned offsets; off / len have
+ * `count` entries).  level outside 1..9: CJS_E_BAD_LEVEL before the device is touched; count == 0: success, *out = NULL.
+ * Inputs are uploaded in groups of up to 256 MiB; an input larger than that goes through cjs_bzip2_compress in the same call.
+ * The batch context of each device is kept between calls (cjs_trim gives it back). */
+int cjs_bzip2_compress_batch(const uint8_t *const *in, const size_t *n, size_t count, int level, uint8_t **out, size_t *off,
+                             size_t *len, const cjs_opts *opts);
 /* Bzip2.table (J/Bzip2_joined_.js:1823-1863): fills (bit position, uncompressed size) of up to `cap` blocks,
  * returns the number of blocks or a negative code.  Bzip2.decompressBlock (:1797-1818): the single block
  * whose 48-bit magic starts at bit `bitpos`. */
@@ -104,6 +112,9 @@ const char *cjs_version(void);
  * A context owns the per-GPU workspace (sized for max_input bytes at `level`) and one stream. */
 typedef struct cjs_ctx cjs_ctx;
 int cjs_ctx_create(cjs_ctx **ctx, int device, size_t max_input, int level);
+/* context of the batch path (cjs_bzip2_compress_batch_device): its workspace takes batches of up to max_input bytes in all and
+ * max_items inputs in one pass per stage (larger batches run in several passes).  Only the batch entry point takes it. */
+int cjs_ctx_create_batch(cjs_ctx **ctx, int device, size_t max_input, size_t max_items, int level);
 /* as above, but the per-block workspace (suffix sorter, MTF, Huffman) is sized for at most
  * max_range_blocks blocks per call: for cjs_bzip2_compress_device_range on a replicated stream */
 int cjs_ctx_create_sharded(cjs_ctx **ctx, int device, size_t max_input, long max_range_blocks, int level);
@@ -116,6 +127,13 @@ void cjs_ctx_set_stage_times(cjs_ctx *ctx, int on);
  * Synchronous on return (the context stream has drained). */
 int cjs_bzip2_compress_device(cjs_ctx *ctx, const uint8_t *d_in, size_t n, int level,
                               uint8_t *d_out, size_t out_cap, size_t *out_n, cjs_stats *stats);
+/* Batch form of the above on a cjs_ctx_create_batch context: input k is d_in[in_off[k] .. in_off[k+1]) (in_off: HOST array of
+ * count + 1 ascending offsets).  Stream k is left at d_out + out_off[k], out_len[k] bytes (4-byte-aligned offsets, out_off /
+ * out_len host arrays of `count` entries).  The streams are assembled in the context's staging buffer and reach d_out in one copy
+ * once all sizes are known: when the last stream ends past out_cap (max of out_off[k] + out_len[k]) the call returns
+ * CJS_E_OUTPUT_TOO_SMALL and d_out is left untouched (out_off / out_len still describe the layout).  d_out must be 4-byte aligned.  Synchronous on return. */
+int cjs_bzip2_compress_batch_device(cjs_ctx *ctx, const uint8_t *d_in, const size_t *in_off, size_t count, int level,
+                                    uint8_t *d_out, size_t out_cap, size_t *out_off, size_t *out_len);
 /* Sharded variant for one-process-per-GPU jobs: compress only blocks [first, first+count) of the
  * stream held (replicated) in d_in, writing the block bit-strings from bit 0 of d_out WITHOUT the
  * 'BZh' header / trailer.  Returns the bit length and the per-block CRCs so the ranks can fold the
