@@ -1,6 +1,7 @@
 // api.hip — C ABI of libcjs_hip.so (include/cjs_hip.h): contexts, host-buffer entry points,
 // stage-level entry points.  No CPU fallback: without a HIP device every call fails loudly.
 #include "cjs_internal.h"
+#include "host.h"
 #include "rle1.h"
 #include <stdarg.h>
 #include <stdlib.h>
@@ -19,6 +20,8 @@ void set_detail(const char* fmt, ...) {
   vsnprintf(g_detail, sizeof g_detail, fmt, ap);
   va_end(ap);
 }
+bool env_debug() { static const bool on = getenv("CJS_DEBUG") != nullptr; return on; }
+bool env_no_ctx_cache() { static const bool on = getenv("CJS_NO_CTX_CACHE") != nullptr; return on; }
 }  // namespace cjs
 
 extern "C" {
@@ -94,10 +97,9 @@ void* DevPool::take(size_t bytes) {
 }
 void DevPool::give(void* p) {
   if (!p) return;
-  static const bool no_cache = getenv("CJS_NO_CTX_CACHE") != nullptr;
   std::lock_guard<std::mutex> lock(g_pool_mu);
   for (size_t i = 0; i < g_pool.size(); i++) if (g_pool[i].p == p) {
-    if (no_cache) { (void)hipFree(p); g_pool.erase(g_pool.begin() + (long)i); return; }
+    if (env_no_ctx_cache()) { (void)hipFree(p); g_pool.erase(g_pool.begin() + (long)i); return; }
     g_pool[i].busy = false;
     size_t idle = 0;
     for (auto& b : g_pool) if (!b.busy) idle += b.bytes;
@@ -147,7 +149,8 @@ void* HostPool::take(size_t bytes) {
   }
   void* p = nullptr;
   const size_t cap = bytes + bytes / 16;                 // a later result of about the same size fits too
-  if (hipHostMalloc(&p, cap, hipHostMallocPortable) != hipSuccess || !p)      // (portable: every GPU of a multi-device call copies into it) { (void)hipGetLastError(); return malloc(bytes); }
+  // (portable: every GPU of a multi-device call copies into it)
+  if (hipHostMalloc(&p, cap, hipHostMallocPortable) != hipSuccess || !p) { (void)hipGetLastError(); return malloc(bytes); }
   std::lock_guard<std::mutex> lock(g_host_mu);
   g_host.push_back(HostBuf{p, cap, true});
   return p;
@@ -182,15 +185,22 @@ void HostPool::trim() {
   }
 }
 
+Opts::Opts(const cjs_opts* o) {
+  if (o && o->struct_size >= sizeof(cjs_opts)) { device = o->device; n_devices = o->n_devices; flags = o->flags; stats = o->stats; }
+  if (const char* e = getenv("CJS_DEVICES")) n_devices = (uint32_t)atoi(e);
+}
+
 int select_device(const cjs_opts* opts) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return CJS_E_NO_DEVICE;
-  if (opts && opts->struct_size >= sizeof(cjs_opts) && opts->device >= 0) {
-    if (opts->device >= n) return CJS_E_INVALID_ARG;
-    CJS_HIP_TRY(hipSetDevice(opts->device));
-  }
+  const int dev = Opts(opts).device;
+  if (dev >= n) return CJS_E_INVALID_ARG;
+  if (dev >= 0) CJS_HIP_TRY(hipSetDevice(dev));
   return 0;
 }
+
+static DevCache g_cache[MAX_DEVICES][CACHE_SLOTS];      // per-device context caches (host.h)
+DevCache& dev_cache(int device, int slot) { return g_cache[device][slot]; }
 
 }  // namespace cjs
 
@@ -213,7 +223,7 @@ extern "C" int cjs_stage_bwt(const uint8_t* in, size_t n, int block_len, int cyc
   if (!rc && (!d_T || !d_U || !d_p)) rc = CJS_E_OUT_OF_MEMORY;
   if (!rc && hipStreamCreate(&s) != hipSuccess) rc = CJS_E_HIP;
   if (!rc && hipMemcpyAsync(d_T, in, n, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = bwt_run(s, w, d_T, nb, stride, n_last, cyclic != 0, d_U, d_p, opts && opts->struct_size >= sizeof(cjs_opts) ? opts->stats : nullptr);
+  if (!rc) rc = bwt_run(s, w, d_T, nb, stride, n_last, cyclic != 0, d_U, d_p, Opts(opts).stats);
   if (!rc && hipMemcpyAsync(out, d_U, n, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
   if (!rc && hipMemcpyAsync(pidx, d_p, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
   if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;

@@ -12,17 +12,16 @@
 //   empty inputs: the 14-byte empty stream
 // The streams are assembled in a staging buffer of the context; they reach the caller's buffer only once every size is known.
 #include "ctx.h"
+#include "host.h"
 #include "prims.hpp"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 using namespace cjs;
 
 namespace cjs {
-int select_device(const cjs_opts* opts);
 
 constexpr uint32_t BATCH_MAX_ITEMS = 65535;          // blocks of a sub-batch (grid y of the per-block kernels)
 constexpr size_t BATCH_MAX_ELEMS = (size_t)1 << 29;   // slots of a sub-batch (suffix-sort workspace ~50 B each)
@@ -113,19 +112,6 @@ __global__ __launch_bounds__(256) void batch_asm_frame(const AsmStream* __restri
   }
 }
 
-int grow(uint8_t*& buf, size_t& cap_, hipStream_t s, size_t need) {
-  if (need <= cap_) return 0;
-  const size_t cap = std::max(need, cap_ + cap_ / 2) + 4096;
-  uint8_t* p = nullptr;
-  CJS_HIP_TRY(hipMalloc((void**)&p, cap));
-  if (buf) {
-    if (hipMemcpyAsync(p, buf, cap_, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipFree(p); return CJS_E_HIP; }
-    (void)hipFree(buf);
-  }
-  buf = p; cap_ = cap;
-  return 0;
-}
-
 // One sub-batch: blocks it[0..nb) in slots of `stride`, through every stage in one pass.  framed: every block is a stream of its
 // own (into the staging buffer), else a bare bit string (into the scratch buffer), both from byte `base` on.  Per block: byte
 // offset, byte length, bit length, CRC.
@@ -168,7 +154,7 @@ int run_sub(cjs_ctx* c, const uint8_t* d_in, const BItem* it, uint32_t nb, uint3
   const uint64_t total = b.h_sc[0];
   uint8_t*& buf = framed ? b.stage : b.scratch;
   size_t& cap = framed ? b.stage_cap : b.scratch_cap;
-  CJS_TRY(grow(buf, cap, s, base + total + 16));
+  CJS_TRY(DevCache::grow(buf, cap, base + total + 16, true, s));
   CJS_HIP_TRY(hipMemsetAsync(buf + base, 0, total + 16, s));
   CJS_TRY(huff_batch_pack_run(s, b.huff, nb, level, framed ? 1 : 0, b.mtf.b.A, b.mtf.b.a_stride, b.mtf.b.npos, b.mtf.b.asz, b.mtf.b.alist,
                               d_crc, d_pidx, d_soff, (uint32_t*)buf));
@@ -223,9 +209,9 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
   std::vector<uint64_t> se(2 * count);
   for (size_t k = 0; k < count; k++) { se[2 * k] = st[k]; se[2 * k + 1] = en[k]; }
   // RLE1 length of every input
-  uint64_t* d_se = (uint64_t*)DevPool::take(16 * count + 8 * count);
+  DevBuf se_buf(16 * count + 8 * count);
+  uint64_t* d_se = (uint64_t*)se_buf.p;
   if (!d_se) return CJS_E_OUT_OF_MEMORY;
-  struct Give { void* p; ~Give() { DevPool::give(p); } } give{d_se};
   uint64_t* d_len2 = d_se + 2 * count;
   CJS_HIP_TRY(hipMemcpyAsync(d_se, se.data(), 16 * count, hipMemcpyHostToDevice, s));
   CJS_TRY(rle1_batch_len(s, d_in, d_se, (uint32_t)count, c->cap, d_len2));
@@ -245,9 +231,9 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
     std::vector<uint32_t> tbase(multi.size() + 1, 0);
     for (size_t j = 0; j < multi.size(); j++) tbase[j + 1] = tbase[j] + (uint32_t)Rle1Work::max_blocks_for(en[multi[j]] - st[multi[j]], c->cap);
     const size_t nt = tbase.back();
-    uint8_t* w = (uint8_t*)DevPool::take(4 * multi.size() + 4 * (multi.size() + 1) + 4 * multi.size() + sizeof(RleBlock) * nt + 64);
+    DevBuf wb(4 * multi.size() + 4 * (multi.size() + 1) + 4 * multi.size() + sizeof(RleBlock) * nt + 64);
+    uint8_t* w = (uint8_t*)wb.p;
     if (!w) return CJS_E_OUT_OF_MEMORY;
-    struct Give2 { void* p; ~Give2() { DevPool::give(p); } } give2{w};
     RleBlock* d_tab = (RleBlock*)w;
     uint32_t* d_item = (uint32_t*)(w + sizeof(RleBlock) * nt);
     uint32_t* d_tbase = d_item + multi.size();
@@ -303,11 +289,11 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
       out_off[multi[j]] = (size_t)used; out_len[multi[j]] = (size_t)((bit + 80 - used * 8 + 7) / 8);
       used += (out_len[multi[j]] + 3) & ~(size_t)3;
     }
-    CJS_TRY(grow(b.stage, b.stage_cap, s, used + 16));
+    CJS_TRY(DevCache::grow(b.stage, b.stage_cap, used + 16, true, s));
     CJS_HIP_TRY(hipMemsetAsync(b.stage + used0, 0, used - used0 + 16, s));
-    uint8_t* t = (uint8_t*)DevPool::take(sizeof(AsmBlock) * ab.size() + sizeof(AsmStream) * as.size() + 64);
+    DevBuf tb(sizeof(AsmBlock) * ab.size() + sizeof(AsmStream) * as.size() + 64);
+    uint8_t* t = (uint8_t*)tb.p;
     if (!t) return CJS_E_OUT_OF_MEMORY;
-    struct Give3 { void* p; ~Give3() { DevPool::give(p); } } give3{t};
     AsmBlock* d_ab = (AsmBlock*)t;
     AsmStream* d_as = (AsmStream*)(t + ((sizeof(AsmBlock) * ab.size() + 15) & ~(size_t)15));
     CJS_HIP_TRY(hipMemcpyAsync(d_ab, ab.data(), sizeof(AsmBlock) * ab.size(), hipMemcpyHostToDevice, s));
@@ -318,7 +304,7 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
     CJS_HIP_TRY(hipStreamSynchronize(s));
   }
   if (!empty.empty()) {
-    CJS_TRY(grow(b.stage, b.stage_cap, s, used + 16 * empty.size()));
+    CJS_TRY(DevCache::grow(b.stage, b.stage_cap, used + 16 * empty.size(), true, s));
     std::vector<uint64_t> eo(empty.size());
     for (size_t i = 0; i < empty.size(); i++) { eo[i] = used + 16 * i; out_off[empty[i]] = (size_t)eo[i]; out_len[empty[i]] = 14; }
     CJS_HIP_TRY(hipMemcpyAsync(d_len2, eo.data(), 8 * eo.size(), hipMemcpyHostToDevice, s));      // (d_len2 is free again)
@@ -330,41 +316,12 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
   uint64_t last = 0;
   for (size_t k = 0; k < count; k++) last = std::max<uint64_t>(last, (uint64_t)out_off[k] + out_len[k]);
   *end = last;
-  static const bool dbg = getenv("CJS_DEBUG") != nullptr;
-  if (dbg) fprintf(stderr, "[cjs batch] %zu inputs: %u passes (%zu one-block inputs, %zu blocks of %zu inputs of several blocks), %zu empty\n",
+  if (env_debug()) fprintf(stderr, "[cjs batch] %zu inputs: %u passes (%zu one-block inputs, %zu blocks of %zu inputs of several blocks), %zu empty\n",
                    count, passes, one.size(), parts.size(), multi.size(), empty.size());
   return 0;
 }
 
-// ---- per-device cache of the host-buffer entry point: a batch context and an input staging buffer
-namespace {
-struct BatchCache {
-  std::mutex mu;
-  cjs_ctx* ctx = nullptr;
-  uint8_t* d_in = nullptr;
-  size_t in_cap = 0;
-  void release() {
-    if (ctx) cjs_ctx_destroy(ctx);
-    if (d_in) (void)hipFree(d_in);
-    ctx = nullptr; d_in = nullptr; in_cap = 0;
-  }
-};
-constexpr int MAX_BATCH_DEVICES = 64;
-BatchCache g_batch_cache[MAX_BATCH_DEVICES];
 constexpr size_t BATCH_GROUP_BYTES = (size_t)256 << 20;      // input bytes the host-buffer entry point uploads at a time
-}  // namespace
-
-void batch_trim() {
-  int cur = 0;
-  const bool have = hipGetDevice(&cur) == hipSuccess;
-  for (int d = 0; d < MAX_BATCH_DEVICES; d++) {
-    BatchCache& bc = g_batch_cache[d];
-    std::lock_guard<std::mutex> lock(bc.mu);
-    if (!bc.ctx && !bc.d_in) continue;
-    if (hipSetDevice(d) == hipSuccess) bc.release();
-  }
-  if (have) (void)hipSetDevice(cur);
-}
 
 }  // namespace cjs
 
@@ -428,14 +385,12 @@ extern "C" int cjs_bzip2_compress_batch(const uint8_t* const* in, const size_t* 
   CJS_GUARD_BEGIN
   CJS_TRY(select_device(opts));
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_BATCH_DEVICES) return CJS_E_HIP;
-  static const bool no_cache = getenv("CJS_NO_CTX_CACHE") != nullptr;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return CJS_E_HIP;
   std::vector<uint8_t> acc;                                             // the streams of all groups, in call order
   std::vector<size_t> goff(count), glen(count);
   int rc = 0;
   {
-    BatchCache& bc = g_batch_cache[dev];
-    std::lock_guard<std::mutex> lock(bc.mu);
+    CacheLease bc{dev_cache(dev, BATCH_SLOT)};                          // (not slot 0: see host.h)
     std::vector<uint8_t> host_in;
     for (size_t k0 = 0; k0 < count && !rc;) {
       if (n[k0] > BATCH_GROUP_BYTES) {                                   // an input of its own: the single-stream host path
@@ -449,29 +404,22 @@ extern "C" int cjs_bzip2_compress_batch(const uint8_t* const* in, const size_t* 
       size_t k1 = k0, bytes = 0;                                        // inputs at 16-byte-aligned offsets (wide loads)
       while (k1 < count && n[k1] <= BATCH_GROUP_BYTES && (k1 == k0 || bytes + n[k1] <= BATCH_GROUP_BYTES)) bytes += (n[k1++] + 15) & ~(size_t)15;
       const size_t items = k1 - k0;
-      if (!bc.ctx || bc.ctx->level != level || !bc.ctx->batch || bc.ctx->batch->elems < std::min<size_t>(bytes + bytes / 4, BATCH_MAX_ELEMS) ||
-          bc.ctx->batch->items < std::min<size_t>(items, BATCH_MAX_ITEMS)) {
-        if (bc.ctx) cjs_ctx_destroy(bc.ctx);
-        bc.ctx = nullptr;
-        rc = cjs_ctx_create_batch(&bc.ctx, dev, std::max<size_t>(bytes, 1), items, level);
-        if (rc) { bc.ctx = nullptr; break; }
+      cjs_ctx*& c = bc.c.ctx;
+      if (!c || c->level != level || !c->batch || c->batch->elems < std::min<size_t>(bytes + bytes / 4, BATCH_MAX_ELEMS) ||
+          c->batch->items < std::min<size_t>(items, BATCH_MAX_ITEMS)) {
+        cjs_ctx_destroy(c); c = nullptr;
+        if ((rc = cjs_ctx_create_batch(&c, dev, std::max<size_t>(bytes, 1), items, level)) != 0) break;
       }
-      if (bc.in_cap < bytes + 16 || !bc.d_in) {
-        if (bc.d_in) (void)hipFree(bc.d_in);
-        bc.d_in = nullptr; bc.in_cap = 0;
-        if (hipMalloc((void**)&bc.d_in, bytes + 16) != hipSuccess) { rc = CJS_E_OUT_OF_MEMORY; break; }
-        bc.in_cap = bytes + 16;
-      }
+      if ((rc = DevCache::grow(bc.c.d_in, bc.c.in_cap, bytes + 16)) != 0) break;
       host_in.resize(bytes + 1);
       std::vector<uint64_t> st(items), en(items);
       for (size_t i = 0, o = 0; i < items; i++) {
         if (n[k0 + i]) memcpy(host_in.data() + o, in[k0 + i], n[k0 + i]);
         st[i] = o; en[i] = o + n[k0 + i]; o += (n[k0 + i] + 15) & ~(size_t)15;
       }
-      cjs_ctx* c = bc.ctx;
-      if (bytes && hipMemcpyAsync(bc.d_in, host_in.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = CJS_E_HIP; break; }
+      if (bytes && hipMemcpyAsync(bc.c.d_in, host_in.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = CJS_E_HIP; break; }
       uint64_t total = 0;
-      rc = batch_core(c, bc.d_in, st, en, items, level, goff.data() + k0, glen.data() + k0, &total);
+      rc = batch_core(c, bc.c.d_in, st, en, items, level, goff.data() + k0, glen.data() + k0, &total);
       if (rc) break;
       const size_t base = (acc.size() + 3) & ~(size_t)3;
       acc.resize(base + total);
@@ -479,7 +427,7 @@ extern "C" int cjs_bzip2_compress_batch(const uint8_t* const* in, const size_t* 
       for (size_t i = 0; i < items; i++) { off[k0 + i] = base + goff[k0 + i]; len[k0 + i] = glen[k0 + i]; }
       k0 = k1;
     }
-    if (rc || no_cache) bc.release();                                   // after an error the cached state is not trusted
+    bc.check(rc);
   }
   if (rc) return rc;
   uint8_t* res = (uint8_t*)HostPool::take(acc.size() ? acc.size() : 1);

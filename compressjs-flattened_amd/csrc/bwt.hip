@@ -1410,7 +1410,7 @@ static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int
   hipLaunchKernelGGL(scan_u32_single, dim3(1), dim3(1024), 0, s, tcount, Tg, w.counters + 2, w.h_counters + 2);      // the kernel writes the pinned mirror itself
   CJS_HIP_TRY(hipStreamSynchronize(s));
   const uint32_t D = w.h_counters[2];
-  if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs bwt]   tile sort: %u of %u suffixes in groups > %u\n", D, A, TS_MAXGRP);
+  if (env_debug()) fprintf(stderr, "[cjs bwt]   tile sort: %u of %u suffixes in groups > %u\n", D, A, TS_MAXGRP);
   if (D == 0) w.no_large_groups = true;
   if (D == 0) return 0;
   if ((size_t)D > w.cap / 2) return radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, lt);
@@ -1517,7 +1517,7 @@ static int bwt_run_impl(hipStream_t s, BwtWork& w, const uint8_t* d_T, const G g
     rounds++;
     const uint32_t A2 = w.h_counters[0], NG = w.h_counters[1];
     if (w.h_counters[4] == 0) w.no_large_groups = true;       // every group of the new grouping fits the tile sorters
-    if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs bwt] round %u h=%u A=%u bits=%d -> A'=%u groups=%u\n", rounds, h, A, bits, A2, NG);
+    if (env_debug()) fprintf(stderr, "[cjs bwt] round %u h=%u A=%u bits=%d -> A'=%u groups=%u\n", rounds, h, A, bits, A2, NG);
     c = 1 - c; pc = 1 - pc;
     A = A2; ngroups = NG;
     if (A == 0) break;

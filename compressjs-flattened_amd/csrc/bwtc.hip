@@ -9,6 +9,7 @@
 // range' = floor(range / tot) * sy is a serial integer chain over the whole file, so that tail runs on
 // one host thread, in block order, over the GPU-produced steps.
 #include "cjs_internal.h"
+#include "host.h"
 #include "prims.hpp"
 #include "mtf.h"
 #include <stdlib.h>
@@ -24,7 +25,6 @@
 #include <vector>
 
 namespace cjs {
-int select_device(const cjs_opts* opts);
 int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint32_t nb, const uint32_t* lens, const uint32_t* pidx, uint8_t* d_out);
 }
 using namespace cjs;
@@ -547,12 +547,11 @@ struct BwtcJob {
 };
 
 void bwtc_batch_body(BwtcJob* J, BwtcBatch* B);
-// nothing may leave a worker thread (std::terminate): an exception becomes the batch's return code and stops the job
+// an exception of the body becomes the batch's return code and stops the job
 void bwtc_batch_worker(BwtcJob* J, BwtcBatch* B) {
   int rc = 0;
-  try { bwtc_batch_body(J, B); return; }
-  catch (const std::bad_alloc&) { rc = CJS_E_OUT_OF_MEMORY; }
-  catch (...) { rc = CJS_E_HIP; }
+  guarded(rc, [&] { bwtc_batch_body(J, B); });
+  if (!rc) return;
   std::lock_guard<std::mutex> lk(J->mu);
   B->rc = rc; B->done = true; J->abort = true;
   J->cv.notify_all();
@@ -635,8 +634,8 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
   o.reserve(n / 3 + 64);
   o.push_back('b'); o.push_back('w'); o.push_back('t'); o.push_back('c');
   uint8_t vb[12]; int nv = 0;                                        // writeUnsignedNumber(size+1) :605-620
-  const bool size_unknown = opts && opts->struct_size >= sizeof(cjs_opts) && (opts->flags & CJS_FLAG_SIZE_UNKNOWN);
-  { uint64_t v = size_unknown ? 0 : (uint64_t)n + 1; do { vb[nv++] = (uint8_t)(v & 0x7F); v >>= 7; } while (v); vb[0] |= 0x80; }   // W1: a stream without .size gives varint(0)
+  const Opts op(opts);
+  { uint64_t v = (op.flags & CJS_FLAG_SIZE_UNKNOWN) ? 0 : (uint64_t)n + 1; do { vb[nv++] = (uint8_t)(v & 0x7F); v >>= 7; } while (v); vb[0] |= 0x80; }   // W1: a stream without .size gives varint(0)
   for (int i = nv - 1; i >= 1; i--) o.push_back(vb[i]);
   HostCoder coder(o);
   coder.start(vb[0], 1);                                             // :1700 (the last varint byte is the coder's first byte)
@@ -650,8 +649,7 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
   double ms_coder = 0, ms_stall = 0, ms_first = 0;
   if (nb) {
     // ---- plan: contiguous block ranges per device slot, cut into batches
-    uint32_t nslots = (opts && opts->struct_size >= sizeof(cjs_opts)) ? opts->n_devices : 0;
-    if (const char* e = getenv("CJS_DEVICES")) nslots = (uint32_t)atoi(e);
+    uint32_t nslots = op.n_devices;
     if (nslots < 1) nslots = 1;
     if (nslots > 64) nslots = 64;
     if (nslots > nb) nslots = nb;
@@ -673,20 +671,17 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
     }
     // on every path out of this scope (an exception of the coder side included: out.resize in reserve_steps) the workers are
     // stopped and joined, the batches give their device memory back and the pinned step buffers are freed
-    struct Workers {
-      BwtcJob& J; int dev0; std::vector<std::thread> th; uint64_t* h_buf[2] = {nullptr, nullptr};
-      ~Workers() {
-        bool running = false;
-        for (auto& t : th) running |= t.joinable();
-        if (running) { { std::lock_guard<std::mutex> lk(J.mu); J.abort = true; } J.cv.notify_all(); for (auto& t : th) if (t.joinable()) t.join(); }
+    struct Stop {
+      BwtcJob& J; int dev0; Workers th; uint64_t* h_buf[2] = {nullptr, nullptr};
+      ~Stop() {
+        if (!th.th.empty()) { { std::lock_guard<std::mutex> lk(J.mu); J.abort = true; } J.cv.notify_all(); th.join(); }
         for (auto& B : J.batches) B.release();
         (void)hipSetDevice(dev0);
         for (int q = 0; q < 2; q++) if (h_buf[q]) (void)hipHostFree(h_buf[q]);
       }
     } wk{J, dev0};
-    std::vector<std::thread>& workers = wk.th;
     uint64_t** h_buf = wk.h_buf;
-    for (auto& B : J.batches) workers.emplace_back(bwtc_batch_worker, &J, &B);
+    for (auto& B : J.batches) wk.th.run(B.rc, [&J, &B] { bwtc_batch_worker(&J, &B); });     // (the worker's own guard leaves the outer one nothing to catch)
     // reciprocals floor(2^64 / tot) + 1 for every total a step can carry (17 bits); tot < 2 keeps the division
     static std::vector<uint64_t> rcp;
     static std::once_flag rcp_once;
@@ -760,13 +755,13 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
       ms_coder += since(Tc);
     }
     if (rc) { std::lock_guard<std::mutex> lk(J.mu); J.abort = true; J.cv.notify_all(); }
-    for (auto& t : workers) t.join();
+    wk.th.join();
     double ms_gpu_max = 0;
     for (auto& B : J.batches) { if (!rc && B.rc) rc = B.rc; ms_gpu_max = std::max(ms_gpu_max, B.ms); }
-    if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs bwtc] %zu batch(es) on %u slot(s): first step list after %.1f ms, longest batch (workspace + H2D + BWT + MTF + model) %.1f ms, "
-                                             "range coder over the step lists (host, serial) %.1f ms, coder waited for the GPU %.1f ms, total %.1f ms\n",
-                                     J.batches.size(), (unsigned)J.live.size(), ms_first, ms_gpu_max, ms_coder, ms_stall, since(T0));
-    cjs_stats* st = (opts && opts->struct_size >= sizeof(cjs_opts)) ? opts->stats : nullptr;
+    if (env_debug()) fprintf(stderr, "[cjs bwtc] %zu batch(es) on %u slot(s): first step list after %.1f ms, longest batch (workspace + H2D + BWT + MTF + model) %.1f ms, "
+                                     "range coder over the step lists (host, serial) %.1f ms, coder waited for the GPU %.1f ms, total %.1f ms\n",
+                             J.batches.size(), (unsigned)J.live.size(), ms_first, ms_gpu_max, ms_coder, ms_stall, since(T0));
+    cjs_stats* st = op.stats;
     if (st && !rc) {                                                 // BWTC meaning of the fields: see include/cjs_hip.h
       memset(st, 0, sizeof *st);
       st->ms_total = since(T0); st->ms_bwt = ms_gpu_max; st->ms_pack = ms_coder; st->ms_rle1 = ms_stall; st->ms_mtf = ms_first;
@@ -779,13 +774,13 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
   const int dbg_cpu1 = sched_getcpu();
   coder.finish();
   if (coder.failed.load()) return CJS_E_OUT_OF_MEMORY;
-  if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs bwtc] split coder: range side on cpu %d -> %d, low side on cpu %d -> %d, polls with the ring full %llu, empty %llu\n", dbg_cpu0, dbg_cpu1,
-                                   coder.dbg_low_cpu[0], coder.dbg_low_cpu[1], (unsigned long long)coder.dbg_full_spins, (unsigned long long)coder.dbg_empty_spins);
+  if (env_debug()) fprintf(stderr, "[cjs bwtc] split coder: range side on cpu %d -> %d, low side on cpu %d -> %d, polls with the ring full %llu, empty %llu\n", dbg_cpu0, dbg_cpu1,
+                           coder.dbg_low_cpu[0], coder.dbg_low_cpu[1], (unsigned long long)coder.dbg_full_spins, (unsigned long long)coder.dbg_empty_spins);
   uint8_t* host = (uint8_t*)malloc(o.size() ? o.size() : 1);
   if (!host) return CJS_E_OUT_OF_MEMORY;
   memcpy(host, o.data(), o.size());
   *out = host; *out_n = o.size();
-  if (opts && opts->struct_size >= sizeof(cjs_opts) && opts->stats) opts->stats->bytes_out = o.size();
+  if (op.stats) op.stats->bytes_out = o.size();
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
@@ -984,7 +979,7 @@ int bwtc_entropy_decode(const uint8_t* in, size_t n, BwtcBlocks& B) {
   B.level = (int)lv;
   const bool fast = lv <= 5;
   const uint32_t bs = lv * 100000u;
-  static const bool dbg = getenv("CJS_DEBUG") != nullptr;
+  const bool dbg = env_debug();
   for (;;) {
     const uint32_t flag = d.target(3); d.commit(1, flag, 3);
     uint32_t length;

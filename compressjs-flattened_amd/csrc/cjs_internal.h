@@ -22,6 +22,8 @@ namespace cjs {
 // thread-local detail text behind cjs_last_error_detail() (api.hip)
 void clear_detail();
 void set_detail(const char* fmt, ...);
+// read from the environment once per process (api.hip): CJS_DEBUG (timings and decisions on stderr), CJS_NO_CTX_CACHE
+bool env_debug(); bool env_no_ctx_cache();
 
 // Body of an extern "C" entry point: C++ exceptions (std::bad_alloc from a container fed by untrusted sizes) never
 // cross the C ABI, they become return codes.

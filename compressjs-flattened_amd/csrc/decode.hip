@@ -18,17 +18,16 @@
 //                        state (does the stretch start with a count byte?) is a 2-state function scan;
 //   6. CRC check         per block over the output bytes (rle1.hip's slice + GF(2) combine), :1756-1761.
 #include "cjs_internal.h"
+#include "host.h"
 #include "prims.hpp"
 #include "rle1.h"
 #include <algorithm>
 #include <chrono>
 #include <stdlib.h>
 #include <string.h>
-#include <thread>
 #include <vector>
 
 namespace cjs {
-int select_device(const cjs_opts* opts);
 template <typename K>
 int radix_passes_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit);
 template <typename K>
@@ -1591,7 +1590,7 @@ static int ibwt_sentinel_slab(hipStream_t s, const uint8_t* d_T, uint32_t max_le
   // The chain visits n distinct rows and then re-enters at row pidx (the step the reference computes last and never
   // uses, BWTC:1163-1165), so the last segment may overshoot; a chain that closes before n rows is corrupt input.
   for (uint32_t k = 0; k < nb; k++) if ((uint32_t)errs[k] < lens[k]) {
-    if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs ibwt] block %u: chain covers %d of %u\n", k, errs[k], lens[k]);
+    if (env_debug()) fprintf(stderr, "[cjs ibwt] block %u: chain covers %d of %u\n", k, errs[k], lens[k]);
     return CJS_E_DATA_ERROR;
   }
   return 0;
@@ -1630,7 +1629,7 @@ constexpr uint32_t DEC_BATCH_BLOCKS = 65535;          // grid.y of the per-block
 struct DecShare {
   int device = 0, rc = 0;
   hipStream_t s = nullptr;
-  std::vector<void*> bufs;
+  std::vector<DevBuf> bufs;          // device scratch of the share, given back at release() (or early, by drop())
   uint64_t lo = 0, hi = 0;            // candidates starting in bytes [lo, hi) are this share's
   uint64_t up_lo = 0, up_hi = 0;      // uploaded byte range
   const uint8_t* d_in = nullptr;      // addressed by absolute byte: d_in[b] is valid for up_lo <= b < up_hi
@@ -1646,12 +1645,11 @@ struct DecShare {
   std::vector<uint64_t> ebase;        // element offset of block c0+i inside d_w (size c1-c0+1)
   double ms_a = 0, ms_b = 0, ms_c = 0;
   char detail[96] = {0};            // error detail found by this share's worker thread (the detail text is per calling thread)
-  int take(void** p, size_t bytes) { *p = DevPool::take(bytes); if (!*p) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(*p); return 0; }
-  void drop(void* p) { for (size_t i = 0; i < bufs.size(); i++) if (bufs[i] == p) { bufs.erase(bufs.begin() + (long)i); break; } DevPool::give(p); }
+  int take(void** p, size_t bytes) { DevBuf b(bytes); if (!(*p = b.p)) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(std::move(b)); return 0; }
+  void drop(void* p) { for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; } DevPool::give(p); }
   void release() {
     if (hipSetDevice(device) != hipSuccess) return;
     if (s) (void)hipStreamSynchronize(s);
-    for (void* p : bufs) DevPool::give(p);
     bufs.clear();
     if (s) (void)hipStreamDestroy(s);
     s = nullptr;
@@ -1796,7 +1794,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   }
   S->drop(d_ops); S->drop(d_opoff); S->drop(d_l0); S->drop(d_pl); S->drop(d_nops); S->drop(d_tabs); S->drop(d_sel); S->drop(d_gstart); S->drop(d_syms);
   if (!single) { S->drop(d_ttb); S->drop(d_gdst); }
-  if (getenv("CJS_DEBUG")) {
+  if (env_debug()) {
     uint64_t clk[8];
     if (hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_dec_clk), sizeof clk) == hipSuccess) {
       fprintf(stderr, "[cjs dec] candidate 0: header + tables %.1f us, group chain %.1f us for %llu groups\n", clk[5] / 100.0, clk[6] / 100.0, (unsigned long long)clk[7]);
@@ -1948,7 +1946,7 @@ void dec_phase_c(DecJob* J, DecShare* S) {
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc) for (uint32_t k = 0; k < nb; k++) if (crcs[k] != blk[k].crc) {                    // Bad block CRC (:1756-1761)
       snprintf(S->detail, sizeof S->detail, "Bad block CRC (got %x expected %x)", crcs[k], blk[k].crc);
-      if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs dec] block %zu: Bad block CRC (got %08x expected %08x) out_len %u\n", b0 + k, crcs[k], blk[k].crc, blk[k].out_len);
+      if (env_debug()) fprintf(stderr, "[cjs dec] block %zu: Bad block CRC (got %08x expected %08x) out_len %u\n", b0 + k, crcs[k], blk[k].crc, blk[k].out_len);
       rc = CJS_E_DATA_ERROR; break;
     }
     S->drop(d_blocks); S->drop(d_out); S->drop(d_ranges); S->drop(d_nb); S->drop(d_seg); S->drop(d_crc);
@@ -1960,17 +1958,9 @@ void dec_phase_c(DecJob* J, DecShare* S) {
 
 template <typename F>
 int for_each_share(std::vector<DecShare>& sh, DecJob* J, F fn) {
-  // nothing may leave a worker thread (std::terminate): an exception of a phase becomes the share's return code
-  auto guarded = [fn](DecJob* j, DecShare* s) {
-    try { fn(j, s); }
-    catch (const std::bad_alloc&) { s->rc = CJS_E_OUT_OF_MEMORY; }
-    catch (...) { s->rc = CJS_E_HIP; }
-  };
-  if (sh.size() == 1) guarded(J, &sh[0]);
-  else {
-    struct JoinAll { std::vector<std::thread> th; ~JoinAll() { for (auto& t : th) if (t.joinable()) t.join(); } } workers;      // joined on every path
-    for (auto& x : sh) workers.th.emplace_back(guarded, J, &x);
-  }
+  // an exception of a phase becomes the share's return code
+  if (sh.size() == 1) guarded(sh[0].rc, [&] { fn(J, &sh[0]); });
+  else { Workers workers; for (auto& x : sh) workers.run(x.rc, [fn, J, &x] { fn(J, &x); }); }      // (joined here)
   for (auto& x : sh) if (x.rc) { if (x.detail[0]) set_detail("%s", x.detail); return x.rc; }
   return 0;
 }
@@ -1992,7 +1982,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev0) != hipSuccess) return CJS_E_NO_DEVICE;
 
   DecJob J; J.in = in; J.n = n; J.mode = mode;
-  J.timing = getenv("CJS_DEBUG") != nullptr;
+  J.timing = env_debug();
   // The scratch rows are sized for the largest level any member stream can have: a multistream file may change level
   // between members (:1787-1792), so every byte-aligned "BZh<d>" followed by a block or end-of-stream magic counts.
   int max_level = level;
@@ -2006,8 +1996,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   J.tt_stride = 100000u * (uint32_t)max_level;
 
   // shares: contiguous byte ranges, one per requested device slot
-  uint32_t nsh = (opts && opts->struct_size >= sizeof(cjs_opts)) ? opts->n_devices : 0;
-  if (const char* e = getenv("CJS_DEVICES")) nsh = (uint32_t)atoi(e);
+  uint32_t nsh = Opts(opts).n_devices;
   if (nsh < 1 || mode == 2) nsh = 1;
   if (nsh > 64) nsh = 64;
   if ((size_t)nsh * 65536 > n) nsh = (uint32_t)(n / 65536 ? n / 65536 : 1);     // tiny inputs: one share
@@ -2047,7 +2036,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   auto take_block = [&](long ci, uint64_t bitpos) -> int {
     const DecShare& S = sh[cshare[(size_t)ci]];
     const BlockOut& bo = S.bos[clocal[(size_t)ci]];
-    if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs dec] block at bit %llu: err %d count %u orig %u crc %08x end %llu\n", (unsigned long long)bitpos, bo.err, bo.count, bo.orig, bo.crc, (unsigned long long)bo.end_bit);
+    if (J.timing) fprintf(stderr, "[cjs dec] block at bit %llu: err %d count %u orig %u crc %08x end %llu\n", (unsigned long long)bitpos, bo.err, bo.count, bo.orig, bo.crc, (unsigned long long)bo.end_bit);
     if (bo.err != CJS_E_OBSOLETE_INPUT && bo.orig > dbuf_size) { set_detail("initial position out of bounds"); return CJS_E_DATA_ERROR; }   // :1449-1450
     if (bo.err) return bo.err;
     if (bo.count > dbuf_size) return CJS_E_DATA_ERROR;             // decoded with the largest level's limit: this stream's is lower (:1647,1663)
@@ -2075,7 +2064,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
       const uint32_t target = (uint32_t)read_bits(pos + 48, 32);
       pos += 80;
       if ((pos + 7) / 8 > n) pos = (uint64_t)n * 8;
-      if (getenv("CJS_DEBUG")) fprintf(stderr, "[cjs dec] end of stream at bit %llu: stream crc %08x stored %08x\n", (unsigned long long)pos - 80, stream_crc, target);
+      if (J.timing) fprintf(stderr, "[cjs dec] end of stream at bit %llu: stream crc %08x stored %08x\n", (unsigned long long)pos - 80, stream_crc, target);
       if (mode == 0 && target != stream_crc) {                   // Bunzip.table ignores the stream crc (:1852)
         set_detail("Bad stream CRC (got %x expected %x)", stream_crc, target);
         rc = CJS_E_DATA_ERROR; break;

@@ -841,7 +841,7 @@ int HuffWork::carve(Arena& a, size_t max_blocks_, uint32_t stride) {
 int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
                     const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist) {
   if (nb == 0) return 0;
-  static const bool dbg = getenv("CJS_DEBUG") != nullptr;
+  const bool dbg = env_debug();
   // one workgroup per block (huff_block) keeps nb CUs busy; with fewer blocks than CUs the chain of kernels spreads the
   // data-parallel phases over the whole chip
   const bool split = nb >= 8 && nb <= 512 && (size_t)nb * w.max_stride >= ((size_t)8 << 20);

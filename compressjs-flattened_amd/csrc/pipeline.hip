@@ -6,6 +6,7 @@
 #include "mtf.h"
 #include "huff.h"
 #include "ctx.h"
+#include "host.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -13,12 +14,9 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 using namespace cjs;
-
-namespace cjs { int select_device(const cjs_opts* opts); }
 
 
 extern "C" int cjs_ctx_create(cjs_ctx** out, int device, size_t max_input, int level) {
@@ -94,45 +92,18 @@ extern "C" void cjs_ctx_destroy(cjs_ctx* c) {
   delete c;
 }
 
-// Per-device state kept between host-buffer calls (cjs_bzip2_compress); guarded by its mutex for the whole call.
-// Slot 0 of a device serves the one-GPU call and the first shard of a multi-GPU call on that device; further slots serve the
-// other shards that land on the same device (more shards than GPUs); the last slot is the boundary pass of a multi-GPU call.
-constexpr int MAX_CACHED_DEVICES = 64, CACHE_SLOTS = 5, BOUNDARY_SLOT = CACHE_SLOTS - 1;
-struct HostCache {
-  std::mutex mu;
-  cjs_ctx* ctx = nullptr;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  size_t in_cap = 0, out_cap = 0;
-  void release() {
-    if (ctx) cjs_ctx_destroy(ctx);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    ctx = nullptr; d_in = d_out = nullptr; in_cap = out_cap = 0;
+// The context of cache slot `hc` (host.h) for n input bytes at `level` on the CURRENT device (range_blocks as in
+// cjs_ctx_create_sharded), staging buffers of at least in_bytes / out_bytes (0 = not needed).  Grows, never shrinks.
+static int ensure(DevCache& hc, size_t n, int level, long range_blocks, size_t in_bytes, size_t out_bytes) {
+  const cjs_ctx* c = hc.ctx;
+  if (!c || c->level != level || c->max_input < n || (range_blocks ? c->range_blocks != (size_t)range_blocks : c->range_blocks != c->max_blocks)) {
+    cjs_ctx_destroy(hc.ctx); hc.ctx = nullptr;
+    CJS_TRY(cjs_ctx_create_sharded(&hc.ctx, -1, n, range_blocks, level));
   }
-  // context for n input bytes at `level` on the CURRENT device (range_blocks as in cjs_ctx_create_sharded), staging buffers of at
-  // least in_bytes / out_bytes (0 = not needed).  Grows, never shrinks; the caller holds mu.
-  int ensure(size_t n, int level, long range_blocks, size_t in_bytes, size_t out_bytes) {
-    if (!ctx || ctx->level != level || ctx->max_input < n || (range_blocks ? ctx->range_blocks != (size_t)range_blocks : ctx->range_blocks != ctx->max_blocks)) {
-      if (ctx) { cjs_ctx_destroy(ctx); ctx = nullptr; }
-      const int rc = cjs_ctx_create_sharded(&ctx, -1, n, range_blocks, level);
-      if (rc) { ctx = nullptr; return rc; }
-    }
-    if (in_bytes && (in_cap < in_bytes || !d_in)) {
-      if (d_in) (void)hipFree(d_in);
-      d_in = nullptr; in_cap = 0;
-      if (hipMalloc((void**)&d_in, in_bytes) != hipSuccess) return CJS_E_OUT_OF_MEMORY;
-      in_cap = in_bytes;
-    }
-    if (out_bytes && (out_cap < out_bytes || !d_out)) {
-      if (d_out) (void)hipFree(d_out);
-      d_out = nullptr; out_cap = 0;
-      if (hipMalloc((void**)&d_out, out_bytes) != hipSuccess) return CJS_E_OUT_OF_MEMORY;
-      out_cap = out_bytes;
-    }
-    return 0;
-  }
-};
-static HostCache g_host_cache[MAX_CACHED_DEVICES][CACHE_SLOTS];
+  if (in_bytes) CJS_TRY(DevCache::grow(hc.d_in, hc.in_cap, in_bytes));
+  if (out_bytes) CJS_TRY(DevCache::grow(hc.d_out, hc.out_cap, out_bytes));
+  return 0;
+}
 
 // Shared body: stage 0..tables for the whole stream, then pack blocks [first, first+count).
 static int compress_core_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, long first, long count, bool framed,
@@ -422,30 +393,26 @@ static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* s
   const size_t n = (size_t)(sh->byte_hi - sh->byte_lo);
   const size_t per = (size_t)sh->count * ((size_t)level * 100000);
   const size_t out_cap = (per + per / 4 + 65536 + 3) & ~(size_t)3;
-  static const bool no_cache = getenv("CJS_NO_CTX_CACHE") != nullptr;
-  HostCache local;                                                       // shards beyond the cached slots of a device: a context of their own
-  HostCache& hc = sh->slot < BOUNDARY_SLOT ? g_host_cache[sh->device][sh->slot] : local;
-  std::lock_guard<std::mutex> lock(hc.mu);
-  struct Cleanup { HostCache& h; bool drop; ~Cleanup() { if (drop) h.release(); } } cleanup{hc, &hc == &local || no_cache};
-  sh->rc = hc.ensure(n, level, 0, sh->d_resident ? 0 : (n ? n : 4), out_cap);
-  if (sh->rc) { cleanup.drop = true; return; }
-  cjs_ctx* c = hc.ctx;
-  const uint8_t* d_in = sh->d_resident ? sh->d_resident : hc.d_in;
-  if (!sh->d_resident && n && hipMemcpyAsync(hc.d_in, in + sh->byte_lo, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { sh->rc = CJS_E_HIP; cleanup.drop = true; return; }
-  static const bool dbg = getenv("CJS_DEBUG") != nullptr;
-  if (dbg) fprintf(stderr, "[cjs] shard %u on device %d (slot %d): blocks [%ld, %ld), bytes [%llu, %llu): H2D %zu B%s\n", sh->index, sh->device, sh->slot, sh->first, sh->first + sh->count,
-                   (unsigned long long)sh->byte_lo, (unsigned long long)sh->byte_hi, sh->d_resident ? (size_t)0 : n, sh->d_resident ? " (resident from the boundary pass)" : "");
+  DevCache local;                                                        // shards beyond the cached slots of a device: a context of their own
+  CacheLease hc{sh->slot < BOUNDARY_SLOT ? dev_cache(sh->device, sh->slot) : local};
+  if (sh->slot >= BOUNDARY_SLOT) hc.drop();
+  if ((sh->rc = hc.check(ensure(hc.c, n, level, 0, sh->d_resident ? 0 : (n ? n : 4), out_cap))) != 0) return;
+  cjs_ctx* c = hc.c.ctx;
+  const uint8_t* d_in = sh->d_resident ? sh->d_resident : hc.c.d_in;
+  if (!sh->d_resident && n && hipMemcpyAsync(hc.c.d_in, in + sh->byte_lo, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { sh->rc = CJS_E_HIP; hc.drop(); return; }
+  if (env_debug()) fprintf(stderr, "[cjs] shard %u on device %d (slot %d): blocks [%ld, %ld), bytes [%llu, %llu): H2D %zu B%s\n", sh->index, sh->device, sh->slot, sh->first, sh->first + sh->count,
+                           (unsigned long long)sh->byte_lo, (unsigned long long)sh->byte_hi, sh->d_resident ? (size_t)0 : n, sh->d_resident ? " (resident from the boundary pass)" : "");
   if (!sync) {                                                           // wave mode: bare bit string from bit 0
     long total = 0;
     std::vector<uint32_t> crcs((size_t)sh->count + 1, 0u);
-    sh->rc = cjs_bzip2_compress_device_range(c, d_in, n, level, 0, -1, hc.d_out, out_cap, &sh->bits, crcs.data(), (long)crcs.size(), &total, nullptr);
+    sh->rc = cjs_bzip2_compress_device_range(c, d_in, n, level, 0, -1, hc.c.d_out, out_cap, &sh->bits, crcs.data(), (long)crcs.size(), &total, nullptr);
     if (!sh->rc && total != sh->count) sh->rc = CJS_E_HIP;          // cannot happen: the range was cut at block starts
     if (!sh->rc) {
       for (long k = 0; k < sh->count; k++) sh->crc_fold = ((sh->crc_fold << 1) | (sh->crc_fold >> 31)) ^ crcs[(size_t)k];
       sh->bytes.resize((size_t)((sh->bits + 7) / 8) + 16);
-      if (hipMemcpy(sh->bytes.data(), hc.d_out, sh->bytes.size(), hipMemcpyDeviceToHost) != hipSuccess) sh->rc = CJS_E_HIP;
+      if (hipMemcpy(sh->bytes.data(), hc.c.d_out, sh->bytes.size(), hipMemcpyDeviceToHost) != hipSuccess) sh->rc = CJS_E_HIP;
     }
-    if (sh->rc) cleanup.drop = true;
+    hc.check(sh->rc);
     return;
   }
   cjs_shard_meta meta{};
@@ -453,7 +420,7 @@ static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* s
   if (!sh->rc && (long)meta.total_blocks != sh->count) sh->rc = CJS_E_HIP;           // cannot happen: the range was cut at block starts
   sync->publish(sh->index, meta, sh->rc);
   published = true;
-  if (sh->rc) { (void)hipStreamSynchronize(c->stream); if (c->side) (void)hipStreamSynchronize(c->side); cleanup.drop = true; return; }
+  if (sh->rc) { (void)hipStreamSynchronize(c->stream); if (c->side) (void)hipStreamSynchronize(c->side); hc.drop(); return; }
   {
     std::unique_lock<std::mutex> lk(sync->mu);
     sync->cv.wait(lk, [&] { return sync->out_ready || sync->rc; });
@@ -463,24 +430,18 @@ static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* s
   shard_layout(sync->metas.data(), (int)sync->nshards, (int)sh->index, start, total, scrc, writer);
   if (!meta.blocks && sh->index) { c->sh_state = 0; return; }
   size_t fo = 0, fl = 0; uint64_t so = 0;
-  sh->rc = shard_pack_core(c, level, sh->index == 0, (int)sh->index == writer, start, meta.bits, scrc, hc.d_out, out_cap, &fo, &fl, &so);
+  sh->rc = shard_pack_core(c, level, sh->index == 0, (int)sh->index == writer, start, meta.bits, scrc, hc.c.d_out, out_cap, &fo, &fl, &so);
   c->sh_state = 0;
-  if (!sh->rc && fl && hipMemcpy(sync->out + so, hc.d_out + fo, fl, hipMemcpyDeviceToHost) != hipSuccess) sh->rc = CJS_E_HIP;
-  if (sh->rc) cleanup.drop = true;
+  if (!sh->rc && fl && hipMemcpy(sync->out + so, hc.c.d_out + fo, fl, hipMemcpyDeviceToHost) != hipSuccess) sh->rc = CJS_E_HIP;
+  hc.check(sh->rc);
 }
 static void run_shard(Shard* sh, const uint8_t* in, int level, MultiSync* sync) {
   bool published = false;
   if (sh->count == 0) { if (sync) sync->publish(sh->index, cjs_shard_meta{}, 0); return; }      // no blocks: nothing of the stream comes from here
-  try { run_shard_body(sh, in, level, sync, published); }              // nothing may leave a worker thread (std::terminate)
-  catch (const std::bad_alloc&) { sh->rc = CJS_E_OUT_OF_MEMORY; }
-  catch (...) { sh->rc = CJS_E_HIP; }
+  guarded(sh->rc, [&] { run_shard_body(sh, in, level, sync, published); });     // (after an exception too, the others hear of it below)
   if (sync && !published) sync->publish(sh->index, cjs_shard_meta{}, sh->rc ? sh->rc : CJS_E_HIP);
   if (sync && sh->rc) { std::lock_guard<std::mutex> lock(sync->mu); if (!sync->rc) sync->rc = sh->rc; sync->cv.notify_all(); }
 }
-struct JoinAll {                         // worker threads are joined on every path out of the scope that started them
-  std::vector<std::thread> th;
-  ~JoinAll() { for (auto& t : th) if (t.joinable()) t.join(); }
-};
 // dst bits [pos, pos + nbits) |= the first nbits bits of src (MSB first); src is readable 9 bytes past its last bit.  Bytes
 // that lie wholly inside the range are STORED (8 at a time, one 64-bit funnel shift), the partial bytes at the two ends OR-ed
 // (the neighbours' bits live there): ranges of different shards may be merged by different threads when `edges` tells them
@@ -521,23 +482,20 @@ static void funnel_merge(uint8_t* dst, uint64_t pos, const uint8_t* src, uint64_
 static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshards, uint8_t** out, size_t* out_n, uint32_t max_parallel = 0) {
   int ndev = 0, dev0 = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev0) != hipSuccess) return CJS_E_NO_DEVICE;
-  if (ndev > MAX_CACHED_DEVICES) ndev = MAX_CACHED_DEVICES;
+  if (ndev > MAX_DEVICES) ndev = MAX_DEVICES;
   struct RestoreDevice { int d; ~RestoreDevice() { (void)hipSetDevice(d); } } restore{dev0};
-  static const bool no_cache = getenv("CJS_NO_CTX_CACHE") != nullptr;
   // ---- boundary pass: block starts of the whole stream (device 0; its copy of the input serves the shards that run there)
-  HostCache& bc = g_host_cache[0][BOUNDARY_SLOT];
-  std::lock_guard<std::mutex> block(bc.mu);
-  struct DropBoundary { HostCache& h; bool drop; ~DropBoundary() { if (drop) { (void)hipSetDevice(0); h.release(); } } } dropb{bc, no_cache};
+  CacheLease bc{dev_cache(0, BOUNDARY_SLOT)};
   std::vector<uint64_t> starts;
   {
     CJS_HIP_TRY(hipSetDevice(0));
-    int rc = bc.ensure(n, level, 1, n ? n : 4, 0);
+    int rc = ensure(bc.c, n, level, 1, n ? n : 4, 0);
     uint32_t nbk = 0;
-    if (!rc && hipMemcpyAsync(bc.d_in, in, n, hipMemcpyHostToDevice, bc.ctx->stream) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc) rc = rle1_run(bc.ctx->stream, bc.ctx->rle, bc.d_in, n, &nbk);
+    if (!rc && hipMemcpyAsync(bc.c.d_in, in, n, hipMemcpyHostToDevice, bc.c.ctx->stream) != hipSuccess) rc = CJS_E_HIP;
+    if (!rc) rc = rle1_run(bc.c.ctx->stream, bc.c.ctx->rle, bc.c.d_in, n, &nbk);
     std::vector<RleBlock> hb(nbk);
-    if (!rc && nbk && hipMemcpy(hb.data(), bc.ctx->rle.blocks, sizeof(RleBlock) * nbk, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (rc) { dropb.drop = true; return rc; }
+    if (!rc && nbk && hipMemcpy(hb.data(), bc.c.ctx->rle.blocks, sizeof(RleBlock) * nbk, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
+    CJS_TRY(bc.check(rc));
     starts.resize((size_t)nbk + 1);
     for (uint32_t k = 0; k < nbk; k++) starts[k] = hb[k].s;
     starts[nbk] = n;
@@ -553,15 +511,15 @@ static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshar
     sh[i].first = std::min<long>((long)i * share, total);
     sh[i].count = std::min<long>(share, total - sh[i].first);
     sh[i].byte_lo = starts[(size_t)sh[i].first]; sh[i].byte_hi = starts[(size_t)(sh[i].first + sh[i].count)];
-    if (sh[i].device == 0) sh[i].d_resident = bc.d_in + sh[i].byte_lo;
+    if (sh[i].device == 0) sh[i].d_resident = bc.c.d_in + sh[i].byte_lo;
   }
   if (!waves) {
     MultiSync sync;
     sync.nshards = nshards; sync.metas.assign(nshards, cjs_shard_meta{});
     uint8_t* result = nullptr; size_t len = 0;
     {
-      JoinAll workers;
-      for (uint32_t i = 0; i < nshards; i++) workers.th.emplace_back(run_shard, &sh[i], in, level, &sync);
+      Workers workers;
+      for (uint32_t i = 0; i < nshards; i++) workers.run(sh[i].rc, [&, i] { run_shard(&sh[i], in, level, &sync); });
       std::unique_lock<std::mutex> lk(sync.mu);
       sync.cv.wait(lk, [&] { return sync.published == nshards; });
       if (!sync.rc) {
@@ -581,8 +539,8 @@ static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshar
     return 0;
   }
   for (uint32_t i0 = 0; i0 < nshards; i0 += max_parallel) {
-    JoinAll workers;
-    for (uint32_t i = i0; i < nshards && i < i0 + max_parallel; i++) workers.th.emplace_back(run_shard, &sh[i], in, level, (MultiSync*)nullptr);
+    Workers workers;
+    for (uint32_t i = i0; i < nshards && i < i0 + max_parallel; i++) workers.run(sh[i].rc, [&, i] { run_shard(&sh[i], in, level, nullptr); });
   }
   uint64_t total_bits = 32 + 80;
   for (auto& x : sh) { if (x.rc) return x.rc; total_bits += x.bits; }
@@ -597,12 +555,14 @@ static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshar
     const uint32_t rot = (uint32_t)sh[i].count & 31u;
     scrc = (rot ? ((scrc << rot) | (scrc >> (32 - rot))) : scrc) ^ sh[i].crc_fold;
   }
+  // interiors by a few threads (disjoint whole bytes), then the shared end bytes one shard after the other
+  const uint32_t nt = std::min<uint32_t>(nshards, 8u);
+  std::vector<int> mrc(nt, 0);
   {
-    // interiors by a few threads (disjoint whole bytes), then the shared end bytes one shard after the other
-    JoinAll mergers;
-    const uint32_t nt = std::min<uint32_t>(nshards, 8u);
-    for (uint32_t t = 0; t < nt; t++) mergers.th.emplace_back([&, t] { for (uint32_t i = t; i < nshards; i += nt) if (sh[i].bits) funnel_merge(o, at[i], sh[i].bytes.data(), sh[i].bits, 0); });
+    Workers mergers;
+    for (uint32_t t = 0; t < nt; t++) mergers.run(mrc[t], [&, t] { for (uint32_t i = t; i < nshards; i += nt) if (sh[i].bits) funnel_merge(o, at[i], sh[i].bytes.data(), sh[i].bits, 0); });
   }
+  for (int r : mrc) if (r) { free(o); return r; }
   for (uint32_t i = 0; i < nshards; i++) if (sh[i].bits) funnel_merge(o, at[i], sh[i].bytes.data(), sh[i].bits, 1);
   const uint64_t trailer[2] = {0x177245385090ull, scrc}; const int tb[2] = {48, 32};
   for (int q = 0; q < 2; q++) for (int i = tb[q] - 1; i >= 0; i--, pos++) if ((trailer[q] >> i) & 1) o[pos >> 3] |= (uint8_t)(0x80 >> (pos & 7));
@@ -617,8 +577,8 @@ extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_
   if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;                 // J/Bzip2_joined_.js:2208
   CJS_GUARD_BEGIN
   CJS_TRY(select_device(opts));
-  uint32_t nshards = (opts && opts->struct_size >= sizeof(cjs_opts)) ? opts->n_devices : 0;
-  if (const char* e = getenv("CJS_DEVICES")) nshards = (uint32_t)atoi(e);   // lets JS / Python callers shard without an opts struct
+  const Opts o(opts);
+  uint32_t nshards = o.n_devices;
   {
     // several GPUs and / or a very large input: contiguous block ranges.  With more ranges than devices (inputs above
     // CJS_CHUNK_BYTES, default 2 GiB, are cut so that a range's workspace stays bounded) the ranges run in waves of one per device.
@@ -634,54 +594,47 @@ extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_
   // The workspace (~70 B per input byte), the staging buffers and the streams are kept per device between calls
   // (creating and freeing them costs more than compressing 100 MB); cjs_trim() or CJS_NO_CTX_CACHE=1 gives them back.
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_CACHED_DEVICES) return CJS_E_HIP;
-  static const bool no_cache = getenv("CJS_NO_CTX_CACHE") != nullptr;
-  HostCache& hc = g_host_cache[dev][0];
-  std::lock_guard<std::mutex> lock(hc.mu);
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return CJS_E_HIP;
+  CacheLease hc{dev_cache(dev, 0)};
   const size_t out_cap = (n + n / 4 + 4096 + 3) & ~(size_t)3;
-  static const bool dbg = getenv("CJS_DEBUG") != nullptr;
+  const bool dbg = env_debug();
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto t0 = now();
-  int rc = hc.ensure(n, level, 0, n ? n : 4, out_cap);
-  if (rc) { hc.release(); return rc; }
-  cjs_ctx* c = hc.ctx;
+  CJS_TRY(hc.check(ensure(hc.c, n, level, 0, n ? n : 4, out_cap)));
+  cjs_ctx* c = hc.c.ctx;
   const auto t1 = now();
-  if (!rc && n && hipMemcpyAsync(hc.d_in, in, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = CJS_E_HIP;
+  int rc = 0;
+  if (n && hipMemcpyAsync(hc.c.d_in, in, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = CJS_E_HIP;
   if (dbg && !rc) (void)hipStreamSynchronize(c->stream);
   const auto t2 = now();
   size_t len = 0;
-  cjs_stats* st = (opts && opts->struct_size >= sizeof(cjs_opts)) ? opts->stats : nullptr;
-  c->stage_times = !(opts && opts->struct_size >= sizeof(cjs_opts) && (opts->flags & CJS_FLAG_NO_STAGE_TIMES));
-  if (!rc) rc = cjs_bzip2_compress_device(c, hc.d_in, n, level, hc.d_out, out_cap, &len, st);
+  c->stage_times = !(o.flags & CJS_FLAG_NO_STAGE_TIMES);
+  if (!rc) rc = cjs_bzip2_compress_device(c, hc.c.d_in, n, level, hc.c.d_out, out_cap, &len, o.stats);
   const auto t3 = now();
   uint8_t* host = nullptr;
   if (!rc) { host = (uint8_t*)HostPool::take(len ? len : 1); if (!host) rc = CJS_E_OUT_OF_MEMORY; }
-  if (!rc && hipMemcpy(host, hc.d_out, len, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
+  if (!rc && hipMemcpy(host, hc.c.d_out, len, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
   const auto t4 = now();
   if (dbg) fprintf(stderr, "[cjs] host compress: workspace %.2f ms, H2D %.2f ms, pipeline %.2f ms, malloc + D2H %.2f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
-  if (rc || no_cache) hc.release();           // after an error the cached state is not trusted
-  if (rc) { HostPool::give(host); return rc; }
+  if (hc.check(rc)) { HostPool::give(host); return rc; }
   *out = host; *out_n = len;
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
-namespace cjs { void batch_trim(); }
 extern "C" void cjs_trim(void) {
-  batch_trim();
-  DevPool::trim();
-  HostPool::trim();
   int cur = 0;
   const bool have = hipGetDevice(&cur) == hipSuccess;
-  for (int d = 0; d < MAX_CACHED_DEVICES; d++)
+  for (int d = 0; d < MAX_DEVICES; d++)             // (first: the batch contexts' workspaces go back to the DevPool, emptied next)
     for (int k = 0; k < CACHE_SLOTS; k++) {
-      HostCache& hc = g_host_cache[d][k];
-      std::lock_guard<std::mutex> lock(hc.mu);
-      if (!hc.ctx && !hc.d_in && !hc.d_out) continue;
-      if (hipSetDevice(d) == hipSuccess) hc.release();
+      DevCache& dc = dev_cache(d, k);
+      std::lock_guard<std::mutex> lock(dc.mu);
+      if ((dc.ctx || dc.d_in || dc.d_out) && hipSetDevice(d) == hipSuccess) dc.release();
     }
   if (have) (void)hipSetDevice(cur);
+  DevPool::trim();
+  HostPool::trim();
 }
 
 // ------------------------------------------------------------------ stage-level entry points (tests)

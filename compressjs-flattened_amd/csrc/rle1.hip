@@ -1093,7 +1093,7 @@ int rle1_walk_run(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, u
   CJS_HIP_TRY(hipStreamSynchronize(s));
   *nblocks_host = w.h_n[0];
   if (last_len_host) *last_len_host = w.h_n[0] ? w.h_n[1] : 0u;
-  if (getenv("CJS_DEBUG")) {
+  if (env_debug()) {
     uint64_t d[8];
     if (hipMemcpyFromSymbol(d, HIP_SYMBOL(g_walk_dbg), sizeof d) == hipSuccess)
       fprintf(stderr, "[cjs rle] boundary walk: %llu speculative rounds %.1f us, %llu serial steps %.1f us, %u blocks; thread 0 of the rounds: tile eval %.1f us, own search %.1f us, wait for the slowest lane %.1f us\n", (unsigned long long)d[0], d[2] / 100.0,
