@@ -60,130 +60,121 @@ const char* cjs_strerror(int code) {
 
 namespace cjs {
 
-// ---- DevPool (see cjs_internal.h)
+// ---- DevPool and HostPool (see cjs_internal.h): one design, two instances
 namespace {
-struct PoolBuf { void* p; size_t bytes; int device; bool busy; };
-std::mutex g_pool_mu;
-std::vector<PoolBuf> g_pool;
+// A table of buffers, each handed out (busy) or cached (idle), keyed by device.  take(): the smallest idle buffer of the key that
+// holds the request and is at most twice as large (or any size up to 1 MiB: requests below that are plain allocations of their
+// own size class and never claim a big idle buffer), else a new one.  give(): beyond limit() bytes of idle buffers the largest
+// idle ones are freed.  Under the lock only the table is edited; buffers are freed after it is released.
+struct Pool {
+  struct Buf { void* p; size_t bytes; int key; bool busy; };
+  void* (*alloc)(size_t bytes, size_t& got);       // a new buffer of got >= bytes bytes, nullptr if none
+  void (*release)(const std::vector<Buf>& gone);   // frees buffers that have left the table
+  size_t (*limit)();
+  std::mutex mu;
+  std::vector<Buf> bufs;
+
+  void* take(size_t bytes, int key) {
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      Buf* best = nullptr;
+      for (auto& b : bufs)
+        if (!b.busy && b.key == key && b.bytes >= bytes && (b.bytes / 2 <= bytes || b.bytes <= ((size_t)1 << 20)) && (!best || b.bytes < best->bytes)) best = &b;
+      if (best) { best->busy = true; return best->p; }
+    }
+    size_t got = 0;
+    void* p = alloc(bytes, got);
+    if (!p) return nullptr;
+    std::lock_guard<std::mutex> lock(mu);
+    bufs.push_back(Buf{p, got, key, true});
+    return p;
+  }
+  bool give(void* p) {                              // false: p is not a buffer of the pool
+    std::vector<Buf> gone;
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      size_t i = 0;
+      while (i < bufs.size() && bufs[i].p != p) i++;
+      if (i == bufs.size()) return false;
+      bufs[i].busy = false;
+      size_t idle = 0;
+      for (auto& b : bufs) if (!b.busy) idle += b.bytes;
+      while (idle > limit()) {                      // over the limit: the largest idle buffers go first
+        size_t big = bufs.size();
+        for (size_t k = 0; k < bufs.size(); k++) if (!bufs[k].busy && (big == bufs.size() || bufs[k].bytes > bufs[big].bytes)) big = k;
+        if (big == bufs.size()) break;
+        idle -= bufs[big].bytes;
+        gone.push_back(bufs[big]);
+        bufs.erase(bufs.begin() + (long)big);
+      }
+    }
+    if (!gone.empty()) release(gone);
+    return true;
+  }
+  void trim() {                                     // frees every idle buffer
+    std::vector<Buf> gone;
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      for (size_t i = 0; i < bufs.size();) {
+        if (bufs[i].busy) { i++; continue; }
+        gone.push_back(bufs[i]);
+        bufs.erase(bufs.begin() + (long)i);
+      }
+    }
+    if (!gone.empty()) release(gone);
+  }
+};
+
+size_t env_mb(const char* name, size_t dflt) { const char* e = getenv(name); return (e ? (size_t)strtoull(e, nullptr, 10) : dflt) << 20; }
+
+// device buffers: hipMalloc, keyed by device.  CJS_DEVICE_POOL_MB (default 65536) of idle buffers per process; none under
+// CJS_NO_CTX_CACHE (give() frees at once).  A failed hipMalloc trims the pool and tries once more.
+Pool g_dev{
+    [](size_t bytes, size_t& got) -> void* {
+      void* p = nullptr;
+      if (hipMalloc(&p, bytes) != hipSuccess) {
+        DevPool::trim();                            // cached-but-idle buffers may be what is in the way
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+      }
+      got = bytes;
+      return p;
+    },
+    [](const std::vector<Pool::Buf>& gone) {        // each on its own device; the caller's device is restored
+      int cur = 0;
+      const bool have = hipGetDevice(&cur) == hipSuccess;
+      for (auto& b : gone) if (hipSetDevice(b.key) == hipSuccess) (void)hipFree(b.p);
+      if (have) (void)hipSetDevice(cur);
+    },
+    [] { static const size_t lim = env_no_ctx_cache() ? 0 : env_mb("CJS_DEVICE_POOL_MB", 65536); return lim; }};
+
+// pinned result buffers: portable (every GPU of a multi-device call copies into them), 1/16 larger than asked for (a later result
+// of about the same size fits too), CJS_PINNED_RESULT_MB (default 2048) of idle buffers
+Pool g_host{
+    [](size_t bytes, size_t& got) -> void* {
+      void* p = nullptr;
+      got = bytes + bytes / 16;
+      if (hipHostMalloc(&p, got, hipHostMallocPortable) != hipSuccess || !p) { (void)hipGetLastError(); return nullptr; }
+      return p;
+    },
+    [](const std::vector<Pool::Buf>& gone) { for (auto& b : gone) (void)hipHostFree(b.p); },
+    [] { static const size_t lim = env_mb("CJS_PINNED_RESULT_MB", 2048); return lim; }};
 }  // namespace
-// Fit rule (the same as HostPool's): requests below 1 MiB are plain allocations of their own size class and never claim a big
-// idle buffer; a cached buffer serves a request only if it is at most twice as large.  give() keeps at most
-// CJS_DEVICE_POOL_MB (default 65536) of idle buffers per process: beyond that the largest idle ones are freed.
-namespace {
-size_t dev_idle_limit() {
-  static const size_t mb = getenv("CJS_DEVICE_POOL_MB") ? (size_t)strtoull(getenv("CJS_DEVICE_POOL_MB"), nullptr, 10) : 65536;
-  return mb << 20;
-}
-}  // namespace
+
 void* DevPool::take(size_t bytes) {
-  if (!bytes) bytes = 4;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  {
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    PoolBuf* best = nullptr;
-    for (auto& b : g_pool)
-      if (!b.busy && b.device == dev && b.bytes >= bytes && (b.bytes / 2 <= bytes || b.bytes <= ((size_t)1 << 20)) && (!best || b.bytes < best->bytes)) best = &b;
-    if (best) { best->busy = true; return best->p; }
-  }
-  void* p = nullptr;
-  if (hipMalloc(&p, bytes) != hipSuccess) {
-    trim();                                              // cached-but-idle buffers may be what is in the way
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-  }
-  std::lock_guard<std::mutex> lock(g_pool_mu);
-  g_pool.push_back(PoolBuf{p, bytes, dev, true});
-  return p;
+  return g_dev.take(bytes ? bytes : 4, dev);
 }
-void DevPool::give(void* p) {
-  if (!p) return;
-  std::lock_guard<std::mutex> lock(g_pool_mu);
-  for (size_t i = 0; i < g_pool.size(); i++) if (g_pool[i].p == p) {
-    if (env_no_ctx_cache()) { (void)hipFree(p); g_pool.erase(g_pool.begin() + (long)i); return; }
-    g_pool[i].busy = false;
-    size_t idle = 0;
-    for (auto& b : g_pool) if (!b.busy) idle += b.bytes;
-    while (idle > dev_idle_limit()) {                    // over the limit: the largest idle buffers go first
-      size_t big = g_pool.size();
-      for (size_t k = 0; k < g_pool.size(); k++) if (!g_pool[k].busy && (big == g_pool.size() || g_pool[k].bytes > g_pool[big].bytes)) big = k;
-      if (big == g_pool.size()) break;
-      idle -= g_pool[big].bytes;
-      (void)hipFree(g_pool[big].p);                      // (hipFree finds the owning device from the pointer)
-      g_pool.erase(g_pool.begin() + (long)big);
-    }
-    return;
-  }
-  (void)hipFree(p);                                      // not ours: plain buffer
-}
-void DevPool::trim() {
-  int cur = 0;
-  const bool have = hipGetDevice(&cur) == hipSuccess;
-  std::lock_guard<std::mutex> lock(g_pool_mu);
-  for (size_t i = 0; i < g_pool.size();) {
-    if (g_pool[i].busy) { i++; continue; }
-    if (hipSetDevice(g_pool[i].device) == hipSuccess) (void)hipFree(g_pool[i].p);
-    g_pool.erase(g_pool.begin() + (long)i);
-  }
-  if (have) (void)hipSetDevice(cur);
-}
+void DevPool::give(void* p) { if (p && !g_dev.give(p)) (void)hipFree(p); }      // not ours: a plain buffer
+void DevPool::trim() { g_dev.trim(); }
 
-// ---- HostPool (see cjs_internal.h)
-namespace {
-struct HostBuf { void* p; size_t bytes; bool busy; };
-std::mutex g_host_mu;
-std::vector<HostBuf> g_host;
-size_t host_idle_limit() {
-  static const size_t mb = getenv("CJS_PINNED_RESULT_MB") ? (size_t)strtoull(getenv("CJS_PINNED_RESULT_MB"), nullptr, 10) : 2048;
-  return mb << 20;
-}
-}  // namespace
 void* HostPool::take(size_t bytes) {
   if (!bytes) bytes = 1;
-  const size_t limit = host_idle_limit();
-  if (bytes < ((size_t)1 << 20) || !limit) return malloc(bytes);
-  {
-    std::lock_guard<std::mutex> lock(g_host_mu);
-    HostBuf* best = nullptr;
-    for (auto& b : g_host) if (!b.busy && b.bytes >= bytes && b.bytes / 2 <= bytes && (!best || b.bytes < best->bytes)) best = &b;
-    if (best) { best->busy = true; return best->p; }
-  }
-  void* p = nullptr;
-  const size_t cap = bytes + bytes / 16;                 // a later result of about the same size fits too
-  // (portable: every GPU of a multi-device call copies into it)
-  if (hipHostMalloc(&p, cap, hipHostMallocPortable) != hipSuccess || !p) { (void)hipGetLastError(); return malloc(bytes); }
-  std::lock_guard<std::mutex> lock(g_host_mu);
-  g_host.push_back(HostBuf{p, cap, true});
-  return p;
+  void* p = bytes < ((size_t)1 << 20) || !g_host.limit() ? nullptr : g_host.take(bytes, 0);
+  return p ? p : malloc(bytes);                                                    // small, unpinned by setting, or pinning failed
 }
-void HostPool::give(void* p) {
-  if (!p) return;
-  {
-    std::lock_guard<std::mutex> lock(g_host_mu);
-    for (size_t i = 0; i < g_host.size(); i++) if (g_host[i].p == p) {
-      g_host[i].busy = false;
-      size_t idle = 0;
-      for (auto& b : g_host) if (!b.busy) idle += b.bytes;
-      for (size_t j = 0; j < g_host.size() && idle > host_idle_limit();) {      // over the limit: the largest idle buffers go first
-        size_t big = g_host.size();
-        for (size_t k = 0; k < g_host.size(); k++) if (!g_host[k].busy && (big == g_host.size() || g_host[k].bytes > g_host[big].bytes)) big = k;
-        if (big == g_host.size()) break;
-        idle -= g_host[big].bytes;
-        (void)hipHostFree(g_host[big].p);
-        g_host.erase(g_host.begin() + (long)big);
-      }
-      return;
-    }
-  }
-  free(p);                                               // not pinned: plain malloc
-}
-void HostPool::trim() {
-  std::lock_guard<std::mutex> lock(g_host_mu);
-  for (size_t i = 0; i < g_host.size();) {
-    if (g_host[i].busy) { i++; continue; }
-    (void)hipHostFree(g_host[i].p);
-    g_host.erase(g_host.begin() + (long)i);
-  }
-}
+void HostPool::give(void* p) { if (p && !g_host.give(p)) free(p); }              // not pinned: plain malloc
+void HostPool::trim() { g_host.trim(); }
 
 Opts::Opts(const cjs_opts* o) {
   if (o && o->struct_size >= sizeof(cjs_opts)) { device = o->device; n_devices = o->n_devices; flags = o->flags; stats = o->stats; }
@@ -215,22 +206,19 @@ extern "C" int cjs_stage_bwt(const uint8_t* in, size_t n, int block_len, int cyc
   Arena arena;
   CJS_TRY(arena.init(BwtWork::bytes_needed(n) + 2 * ((n + 511) & ~(size_t)255) + 4 * (size_t)nb + 8192));
   BwtWork w;
-  int rc = w.carve(arena, n);
+  CJS_TRY(w.carve(arena, n));
   uint8_t* d_T = arena.take<uint8_t>(n);
   uint8_t* d_U = arena.take<uint8_t>(n);
   uint32_t* d_p = arena.take<uint32_t>(nb);
-  hipStream_t s = nullptr;
-  if (!rc && (!d_T || !d_U || !d_p)) rc = CJS_E_OUT_OF_MEMORY;
-  if (!rc && hipStreamCreate(&s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpyAsync(d_T, in, n, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = bwt_run(s, w, d_T, nb, stride, n_last, cyclic != 0, d_U, d_p, Opts(opts).stats);
-  if (!rc && hipMemcpyAsync(out, d_U, n, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpyAsync(pidx, d_p, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
-  if (s) (void)hipStreamDestroy(s);
-  w.release_host();
-  arena.destroy();
-  return rc;
+  if (!d_T || !d_U || !d_p) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpyAsync(d_T, in, n, hipMemcpyHostToDevice, s));
+  CJS_TRY(bwt_run(s, w, d_T, nb, stride, n_last, cyclic != 0, d_U, d_p, Opts(opts).stats));
+  CJS_HIP_TRY(hipMemcpyAsync(out, d_U, n, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(pidx, d_p, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
@@ -247,31 +235,28 @@ extern "C" int cjs_stage_rle1(const uint8_t* in, size_t n, int level, uint8_t* b
   const size_t maxb = Rle1Work::max_blocks_for(n, cap);
   CJS_TRY(arena.init(Rle1Work::bytes_needed(n, cap) + n + maxb * cap + 65536));
   Rle1Work w;
-  int rc = w.carve(arena, n, cap);
+  CJS_TRY(w.carve(arena, n, cap));
   uint8_t* d_in = arena.take<uint8_t>(n);
   uint8_t* d_blocks = arena.take<uint8_t>(maxb * cap);
-  hipStream_t s = nullptr;
-  if (!rc && (!d_in || !d_blocks)) rc = CJS_E_OUT_OF_MEMORY;
-  if (!rc && hipStreamCreate(&s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
+  if (!d_in || !d_blocks) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s));
   uint32_t nb = 0;
-  if (!rc) rc = rle1_run(s, w, d_in, n, &nb);
-  if (!rc) rc = rle1_finish(s, w, d_in, n, 0, nb, d_blocks);
-  if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && ((long)nb > cap_blocks || (size_t)nb * cap > blocks_cap)) rc = CJS_E_OUTPUT_TOO_SMALL;
-  if (!rc && nb) {
-    std::vector<RleBlock> hb(nb);
-    if (hipMemcpy(hb.data(), w.blocks, sizeof(RleBlock) * nb, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc && hipMemcpy(block_len, w.block_len, 4 * (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc && hipMemcpy(block_crc, w.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc && hipMemcpy(blocks, d_blocks, (size_t)nb * cap, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc) for (uint32_t k = 0; k < nb; k++) block_start[k] = hb[k].s;
-  }
+  const int rc = rle1_run(s, w, d_in, n, &nb);
   *nblocks = (long)nb;
-  if (s) (void)hipStreamDestroy(s);
-  w.release();
-  arena.destroy();
-  return rc;
+  CJS_TRY(rc);
+  CJS_TRY(rle1_finish(s, w, d_in, n, 0, nb, d_blocks));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  if ((long)nb > cap_blocks || (size_t)nb * cap > blocks_cap) return CJS_E_OUTPUT_TOO_SMALL;
+  if (nb) {
+    std::vector<RleBlock> hb(nb);
+    CJS_HIP_TRY(hipMemcpy(hb.data(), w.blocks, sizeof(RleBlock) * nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(block_len, w.block_len, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(block_crc, w.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(blocks, d_blocks, (size_t)nb * cap, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < nb; k++) block_start[k] = hb[k].s;
+  }
+  return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
-

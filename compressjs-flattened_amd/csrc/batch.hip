@@ -34,22 +34,14 @@ struct BatchWork {
   BwtWork bwt;
   MtfWork mtf;
   HuffWork huff;
-  uint8_t* stage = nullptr;        // the streams of a call, back to back
+  DevMem<uint8_t> stage;           // the streams of a call, back to back
   size_t stage_cap = 0;
-  uint8_t* scratch = nullptr;      // bare bit strings of the blocks of inputs of several blocks, before they are assembled
+  DevMem<uint8_t> scratch;         // bare bit strings of the blocks of inputs of several blocks, before they are assembled
   size_t scratch_cap = 0;
-  uint64_t* h_sc = nullptr;        // pinned scalars
+  Pinned<uint64_t> h_sc;           // scalars
 };
 
-void batch_destroy(BatchWork* b) {
-  if (!b) return;
-  if (b->stage) (void)hipFree(b->stage);
-  if (b->scratch) (void)hipFree(b->scratch);
-  if (b->h_sc) (void)hipHostFree(b->h_sc);
-  b->bwt.release_host();
-  b->arena.destroy();
-  delete b;
-}
+void batch_destroy(BatchWork* b) { delete b; }
 
 namespace {
 
@@ -152,12 +144,12 @@ int run_sub(cjs_ctx* c, const uint8_t* d_in, const BItem* it, uint32_t nb, uint3
   CJS_HIP_TRY(hipMemcpyAsync(b.h_sc, b.huff.scalars, 8, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipStreamSynchronize(s));                  // (the output buffer may have to grow before the streams are written)
   const uint64_t total = b.h_sc[0];
-  uint8_t*& buf = framed ? b.stage : b.scratch;
+  DevMem<uint8_t>& buf = framed ? b.stage : b.scratch;
   size_t& cap = framed ? b.stage_cap : b.scratch_cap;
   CJS_TRY(DevCache::grow(buf, cap, base + total + 16, true, s));
   CJS_HIP_TRY(hipMemsetAsync(buf + base, 0, total + 16, s));
   CJS_TRY(huff_batch_pack_run(s, b.huff, nb, level, framed ? 1 : 0, b.mtf.b.A, b.mtf.b.a_stride, b.mtf.b.npos, b.mtf.b.asz, b.mtf.b.alist,
-                              d_crc, d_pidx, d_soff, (uint32_t*)buf));
+                              d_crc, d_pidx, d_soff, (uint32_t*)buf.p));
   so.resize(nb); sl.resize(nb); bits.resize(nb); crc.resize(nb);
   CJS_HIP_TRY(hipMemcpyAsync(so.data(), d_soff, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipMemcpyAsync(sl.data(), d_slen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
@@ -298,8 +290,8 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
     AsmStream* d_as = (AsmStream*)(t + ((sizeof(AsmBlock) * ab.size() + 15) & ~(size_t)15));
     CJS_HIP_TRY(hipMemcpyAsync(d_ab, ab.data(), sizeof(AsmBlock) * ab.size(), hipMemcpyHostToDevice, s));
     CJS_HIP_TRY(hipMemcpyAsync(d_as, as.data(), sizeof(AsmStream) * as.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(batch_asm_blocks, dim3((unsigned)ab.size()), dim3(256), 0, s, d_ab, (const uint32_t*)b.scratch, (uint32_t*)b.stage);
-    hipLaunchKernelGGL(batch_asm_frame, dim3((unsigned)((as.size() + 255) / 256)), dim3(256), 0, s, d_as, (uint32_t)as.size(), level, (uint32_t*)b.stage);
+    hipLaunchKernelGGL(batch_asm_blocks, dim3((unsigned)ab.size()), dim3(256), 0, s, d_ab, (const uint32_t*)b.scratch.p, (uint32_t*)b.stage.p);
+    hipLaunchKernelGGL(batch_asm_frame, dim3((unsigned)((as.size() + 255) / 256)), dim3(256), 0, s, d_as, (uint32_t)as.size(), level, (uint32_t*)b.stage.p);
     CJS_HIP_TRY(hipGetLastError());
     CJS_HIP_TRY(hipStreamSynchronize(s));
   }
@@ -308,7 +300,7 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
     std::vector<uint64_t> eo(empty.size());
     for (size_t i = 0; i < empty.size(); i++) { eo[i] = used + 16 * i; out_off[empty[i]] = (size_t)eo[i]; out_len[empty[i]] = 14; }
     CJS_HIP_TRY(hipMemcpyAsync(d_len2, eo.data(), 8 * eo.size(), hipMemcpyHostToDevice, s));      // (d_len2 is free again)
-    hipLaunchKernelGGL(batch_empty_streams, dim3((unsigned)((eo.size() + 255) / 256)), dim3(256), 0, s, d_len2, (uint32_t)eo.size(), level, (uint32_t*)b.stage);
+    hipLaunchKernelGGL(batch_empty_streams, dim3((unsigned)((eo.size() + 255) / 256)), dim3(256), 0, s, d_len2, (uint32_t)eo.size(), level, (uint32_t*)b.stage.p);
     CJS_HIP_TRY(hipGetLastError());
     CJS_HIP_TRY(hipStreamSynchronize(s));
     used += 16 * empty.size();
@@ -334,7 +326,7 @@ extern "C" int cjs_ctx_create_batch(cjs_ctx** out, int device, size_t max_input,
   CJS_TRY(cjs_ctx_create_sharded(&c, device, 1, 0, level));        // streams and events; the single-stream workspace stays minimal
   BatchWork* b = new (std::nothrow) BatchWork();
   if (!b) { cjs_ctx_destroy(c); return CJS_E_OUT_OF_MEMORY; }
-  c->batch = b;
+  c->batch.reset(b);
   if (max_items == 0) max_items = 1;
   b->items = (uint32_t)std::min<size_t>(max_items, BATCH_MAX_ITEMS);
   // slots: the inputs' RLE1 bytes (at most 5/4 of the input) and up to SMALL_SLOT per input for the narrow slots of tiny inputs.
@@ -344,7 +336,7 @@ extern "C" int cjs_ctx_create_batch(cjs_ctx** out, int device, size_t max_input,
   const size_t segs = Rle1Work::max_segs_for(c->cap) + 2;
   const size_t bytes = BwtWork::bytes_needed(b->elems) + 12 * b->elems + (size_t)b->items * (24576 + 4 * segs + 128) + ((size_t)1 << 20);
   int rc = b->arena.init_pooled(bytes);
-  if (!rc && hipHostMalloc((void**)&b->h_sc, 64) != hipSuccess) rc = CJS_E_HIP;
+  if (!rc && hipHostMalloc((void**)b->h_sc.put(), 64) != hipSuccess) rc = CJS_E_HIP;
   if (rc) { cjs_ctx_destroy(c); return rc; }
   *out = c;
   return 0;

@@ -1317,8 +1317,8 @@ int BwtWork::carve(Arena& a, size_t cap_) {
   tile_cnt = a.take<uint32_t>(3 * T); counters = a.take<uint32_t>(16);
   ghist = a.take<uint32_t>(16 * 256);
   if (!counters || !ghist) return CJS_E_OUT_OF_MEMORY;
-  if (!h_counters) CJS_HIP_TRY(hipHostMalloc((void**)&h_counters, 64));
-  if (!ev_scan) CJS_HIP_TRY(hipEventCreateWithFlags(&ev_scan, hipEventDisableTiming));
+  if (!h_counters) CJS_HIP_TRY(hipHostMalloc((void**)h_counters.put(), 64));
+  if (!ev_scan) CJS_HIP_TRY(hipEventCreateWithFlags(ev_scan.put(), hipEventDisableTiming));
   return 0;
 }
 

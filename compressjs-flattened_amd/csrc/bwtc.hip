@@ -20,13 +20,11 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 
-namespace cjs {
-int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint32_t nb, const uint32_t* lens, const uint32_t* pidx, uint8_t* d_out);
-}
 using namespace cjs;
 
 namespace cjs {
@@ -519,21 +517,20 @@ struct BwtcBatch {
   uint32_t first = 0, count = 0;
   int rc = 0;
   bool done = false;
-  Arena arena; BwtWork bw;
-  hipStream_t s = nullptr, cs = nullptr;      // work stream, copy stream (step lists -> pinned host buffers)
-  hipEvent_t cev[2] = {nullptr, nullptr};
+  struct Gpu {                                 // destroyed in reverse order: events, streams, then the workspace
+    Arena arena; BwtWork bw;
+    Stream s, cs;                             // work stream, copy stream (step lists -> pinned host buffers)
+    Event cev[2];
+  };
+  std::unique_ptr<Gpu> g;
   uint64_t* d_steps = nullptr; size_t step_stride = 0;
   std::vector<uint32_t> pidx, asz, nsteps; std::vector<uint8_t> alist;
   double ms = 0;
-  void release() {
-    if (hipSetDevice(device) != hipSuccess) return;
-    if (s) (void)hipStreamSynchronize(s);
-    if (cs) (void)hipStreamSynchronize(cs);
-    for (int q = 0; q < 2; q++) if (cev[q]) { (void)hipEventDestroy(cev[q]); cev[q] = nullptr; }
-    if (cs) { (void)hipStreamDestroy(cs); cs = nullptr; }
-    if (s) { (void)hipStreamDestroy(s); s = nullptr; }
-    bw.release_host();
-    arena.destroy();
+  void release() {                            // once its streams have drained, on its device
+    if (!g || hipSetDevice(device) != hipSuccess) return;
+    if (g->s) (void)hipStreamSynchronize(g->s);
+    if (g->cs) (void)hipStreamSynchronize(g->cs);
+    g.reset();
   }
 };
 
@@ -575,26 +572,28 @@ void bwtc_batch_body(BwtcJob* J, BwtcBatch* B) {
   MtfWork mw;
   uint8_t *d_T = nullptr, *d_U = nullptr; uint32_t *d_pidx = nullptr, *d_len = nullptr, *d_nsteps = nullptr;
   if (hipSetDevice(B->device) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = B->arena.init_pooled(BwtWork::bytes_needed(elems) + MtfWork::bytes_needed(cnt, bs) + 2 * (elems + 512) + 8 * (size_t)cnt * B->step_stride + 16 * (size_t)cnt + 65536);
-  if (!rc) rc = B->bw.carve(B->arena, elems);
-  if (!rc) rc = mw.carve(B->arena, cnt, bs);
+  B->g.reset(new BwtcBatch::Gpu());
+  BwtcBatch::Gpu& G = *B->g;
+  if (!rc) rc = G.arena.init_pooled(BwtWork::bytes_needed(elems) + MtfWork::bytes_needed(cnt, bs) + 2 * (elems + 512) + 8 * (size_t)cnt * B->step_stride + 16 * (size_t)cnt + 65536);
+  if (!rc) rc = G.bw.carve(G.arena, elems);
+  if (!rc) rc = mw.carve(G.arena, cnt, bs);
   if (!rc) {
-    d_T = B->arena.take<uint8_t>(elems); d_U = B->arena.take<uint8_t>(elems);
-    d_pidx = B->arena.take<uint32_t>(cnt); d_len = B->arena.take<uint32_t>(cnt); d_nsteps = B->arena.take<uint32_t>(cnt);
-    B->d_steps = B->arena.take<uint64_t>((size_t)cnt * B->step_stride);
+    d_T = G.arena.take<uint8_t>(elems); d_U = G.arena.take<uint8_t>(elems);
+    d_pidx = G.arena.take<uint32_t>(cnt); d_len = G.arena.take<uint32_t>(cnt); d_nsteps = G.arena.take<uint32_t>(cnt);
+    B->d_steps = G.arena.take<uint64_t>((size_t)cnt * B->step_stride);
     if (!B->d_steps) rc = CJS_E_OUT_OF_MEMORY;
   }
   if (!rc && B->slot == 0 && B->seq == 0 && J->batches.size() > 1) {   // the batch the coder is waiting for goes ahead of the others' kernels
     int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || hipStreamCreateWithPriority(&B->s, hipStreamDefault, greatest) != hipSuccess) B->s = nullptr;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) (void)hipStreamCreateWithPriority(G.s.put(), hipStreamDefault, greatest);
   }
-  if (!rc && ((!B->s && hipStreamCreate(&B->s) != hipSuccess) || hipStreamCreate(&B->cs) != hipSuccess ||
-              hipEventCreateWithFlags(&B->cev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&B->cev[1], hipEventDisableTiming) != hipSuccess)) rc = CJS_E_HIP;
+  if (!rc && ((!G.s && hipStreamCreate(G.s.put()) != hipSuccess) || hipStreamCreate(G.cs.put()) != hipSuccess ||
+              hipEventCreateWithFlags(G.cev[0].put(), hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(G.cev[1].put(), hipEventDisableTiming) != hipSuccess)) rc = CJS_E_HIP;
   std::vector<uint32_t> lens(cnt, bs); lens[cnt - 1] = n_last;
-  hipStream_t s = B->s;
+  hipStream_t s = G.s;
   if (!rc && hipMemcpyAsync(d_T, J->in + (size_t)B->first * bs, nbytes, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
   if (!rc && hipMemcpyAsync(d_len, lens.data(), 4 * (size_t)cnt, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = bwt_run(s, B->bw, d_T, cnt, bs, n_last, false, d_U, d_pidx, nullptr);
+  if (!rc) rc = bwt_run(s, G.bw, d_T, cnt, bs, n_last, false, d_U, d_pidx, nullptr);
   if (!rc) rc = mtf_run(s, mw, d_U, cnt, d_len);
   if (!rc) {
     if (J->fast) hipLaunchKernelGGL(bwtc_defsum, dim3(cnt), dim3(64), 0, s, mw.b, B->d_steps, B->step_stride, d_nsteps);
@@ -670,17 +669,17 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
       }
     }
     // on every path out of this scope (an exception of the coder side included: out.resize in reserve_steps) the workers are
-    // stopped and joined, the batches give their device memory back and the pinned step buffers are freed
+    // stopped and joined, the batches give their device memory back, device dev0 is made current again and the pinned step
+    // buffers are freed (members and locals go in reverse order)
+    Pinned<uint64_t> h_buf[2];
+    RestoreDevice restore{dev0};
     struct Stop {
-      BwtcJob& J; int dev0; Workers th; uint64_t* h_buf[2] = {nullptr, nullptr};
+      BwtcJob& J; Workers th;
       ~Stop() {
         if (!th.th.empty()) { { std::lock_guard<std::mutex> lk(J.mu); J.abort = true; } J.cv.notify_all(); th.join(); }
         for (auto& B : J.batches) B.release();
-        (void)hipSetDevice(dev0);
-        for (int q = 0; q < 2; q++) if (h_buf[q]) (void)hipHostFree(h_buf[q]);
       }
-    } wk{J, dev0};
-    uint64_t** h_buf = wk.h_buf;
+    } wk{J};
     for (auto& B : J.batches) wk.th.run(B.rc, [&J, &B] { bwtc_batch_worker(&J, &B); });     // (the worker's own guard leaves the outer one nothing to catch)
     // reciprocals floor(2^64 / tot) + 1 for every total a step can carry (17 bits); tot < 2 keeps the division
     static std::vector<uint64_t> rcp;
@@ -688,7 +687,7 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
     std::call_once(rcp_once, [] { rcp.assign(1u << 17, 0ull); for (uint32_t t = 2; t < (1u << 17); t++) rcp[t] = (uint64_t)(((unsigned __int128)1 << 64) / t) + 1; });
     // the steps of block k+1 travel (pinned buffer, copy stream of its batch) while block k goes through the coder
     const size_t step_stride = 2 * MtfWork::a_stride_for(bs);
-    if (hipHostMalloc((void**)&h_buf[0], 8 * step_stride, hipHostMallocPortable) != hipSuccess || hipHostMalloc((void**)&h_buf[1], 8 * step_stride, hipHostMallocPortable) != hipSuccess) rc = CJS_E_HIP;
+    if (hipHostMalloc((void**)h_buf[0].put(), 8 * step_stride, hipHostMallocPortable) != hipSuccess || hipHostMalloc((void**)h_buf[1].put(), 8 * step_stride, hipHostMallocPortable) != hipSuccess) rc = CJS_E_HIP;
     size_t bi_of_next = 0;                                           // batch that holds the next block to fetch
     hipEvent_t pending[2] = {nullptr, nullptr}; int pending_dev[2] = {0, 0};
     auto wait_batch = [&](size_t bi) -> int {                        // blocks until the batch's GPU work is done
@@ -704,9 +703,9 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
       CJS_TRY(wait_batch(bi_of_next));
       const uint32_t r = k - B.first;
       if (hipSetDevice(B.device) != hipSuccess) return (int)CJS_E_HIP;
-      if (B.nsteps[r] && hipMemcpyAsync(h_buf[k & 1], B.d_steps + (size_t)r * B.step_stride, 8 * (size_t)B.nsteps[r], hipMemcpyDeviceToHost, B.cs) != hipSuccess) return (int)CJS_E_HIP;
-      if (hipEventRecord(B.cev[k & 1], B.cs) != hipSuccess) return (int)CJS_E_HIP;
-      pending[k & 1] = B.cev[k & 1]; pending_dev[k & 1] = B.device;
+      if (B.nsteps[r] && hipMemcpyAsync(h_buf[k & 1], B.d_steps + (size_t)r * B.step_stride, 8 * (size_t)B.nsteps[r], hipMemcpyDeviceToHost, B.g->cs) != hipSuccess) return (int)CJS_E_HIP;
+      if (hipEventRecord(B.g->cev[k & 1], B.g->cs) != hipSuccess) return (int)CJS_E_HIP;
+      pending[k & 1] = B.g->cev[k & 1]; pending_dev[k & 1] = B.device;
       return 0;
     };
     auto retire = [&](size_t bi) {                                   // the coder is through with the batch: give its memory back
@@ -1061,24 +1060,20 @@ extern "C" int cjs_bwtc_decompress(const uint8_t* in, size_t n, uint8_t** out, s
   CJS_TRY(bwtc_entropy_decode(in, n, B));
   const uint32_t nb = (uint32_t)B.lens.size();
   const uint64_t total = B.cols.size();
-  uint8_t* host = (uint8_t*)malloc(total ? (size_t)total : 1);
+  std::unique_ptr<uint8_t, void (*)(void*)> host((uint8_t*)malloc(total ? (size_t)total : 1), free);
   if (!host) return CJS_E_OUT_OF_MEMORY;
   if (nb) {
     // n <= 1 blocks: unbwtransform copies (:1149-1152); handled by the same kernels (a 1-element chain)
-    uint8_t *d_T = nullptr, *d_out = nullptr; hipStream_t s = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&d_T, (size_t)total + 64) != hipSuccess) rc = CJS_E_OUT_OF_MEMORY;
-    if (!rc && hipMalloc((void**)&d_out, (size_t)total + 64) != hipSuccess) rc = CJS_E_OUT_OF_MEMORY;
-    if (!rc && hipStreamCreate(&s) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc && hipMemcpyAsync(d_T, B.cols.data(), (size_t)total, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc) rc = ibwt_sentinel_run(s, d_T, (uint32_t)B.level * 100000u, nb, B.lens.data(), B.pidx.data(), d_out);
-    if (!rc && total && hipMemcpy(host, d_out, (size_t)total, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (s) (void)hipStreamDestroy(s);
-    if (d_T) (void)hipFree(d_T);
-    if (d_out) (void)hipFree(d_out);
-    if (rc) { free(host); return rc; }
+    DevMem<uint8_t> d_T, d_out;
+    Stream s;
+    CJS_TRY(d_T.alloc((size_t)total + 64));
+    CJS_TRY(d_out.alloc((size_t)total + 64));
+    CJS_HIP_TRY(hipStreamCreate(s.put()));
+    CJS_HIP_TRY(hipMemcpyAsync(d_T, B.cols.data(), (size_t)total, hipMemcpyHostToDevice, s));
+    CJS_TRY(ibwt_sentinel_run(s, d_T, (uint32_t)B.level * 100000u, nb, B.lens.data(), B.pidx.data(), d_out));
+    if (total) CJS_HIP_TRY(hipMemcpy(host.get(), d_out, (size_t)total, hipMemcpyDeviceToHost));
   }
-  *out = host; *out_n = (size_t)total;
+  *out = host.release(); *out_n = (size_t)total;
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }

@@ -32,12 +32,44 @@ bool env_debug(); bool env_no_ctx_cache();
   } catch (const std::bad_alloc&) { return (oom_value); }              \
   catch (...) { return (other_value); }
 
+// Move-only owner of one HIP handle or allocation; null is empty.  The destructor and reset() release it with Free.  Releasing
+// never synchronises and never changes the current device: a caller that needs either does it first.
+template <typename T, typename Free> struct Owner {
+  T p = nullptr;
+  Owner() = default;
+  Owner(Owner&& o) noexcept : p(o.p) { o.p = nullptr; }
+  Owner& operator=(Owner&& o) noexcept { if (this != &o) { reset(o.p); o.p = nullptr; } return *this; }
+  ~Owner() { reset(); }
+  void reset(T v = nullptr) { if (p) Free{}(p); p = v; }
+  T* put() { reset(); return &p; }          // for the call that creates it: hipStreamCreate(s.put())
+  operator T() const { return p; }
+  T operator->() const { return p; }
+};
+struct StreamFree { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+struct EventFree { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct PinnedFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
+using Stream = Owner<hipStream_t, StreamFree>;
+using Event = Owner<hipEvent_t, EventFree>;
+template <typename T> using Pinned = Owner<T*, PinnedFree>;   // hipHostMalloc
+template <typename T> struct DevMem : Owner<T*, DevFree> {    // hipMalloc
+  int alloc(size_t bytes) {
+    if (hipMalloc((void**)this->put(), bytes) == hipSuccess) return 0;
+    this->p = nullptr;
+    return CJS_E_OUT_OF_MEMORY;
+  }
+};
+
 struct DevPool;
-// simple device arena: one hipMalloc (or one buffer of the per-device pool), bump allocation, 256-byte aligned
+// simple device arena: one hipMalloc (or one buffer of the per-device pool), bump allocation, 256-byte aligned; freed by its owner
 struct Arena {
   uint8_t* base = nullptr;
   size_t cap = 0, used = 0;
   bool pooled = false;
+  Arena() = default;
+  Arena(const Arena&) = delete;
+  Arena& operator=(const Arena&) = delete;
+  ~Arena() { destroy(); }
   int init(size_t bytes) {
     CJS_HIP_TRY(hipMalloc((void**)&base, bytes));
     cap = bytes; used = 0; pooled = false;
@@ -55,11 +87,9 @@ struct Arena {
 };
 
 struct EventTimer {   // accumulates device time of bracketed regions on one stream
-  hipStream_t s;
-  hipEvent_t a, b;
-  bool ok = false;
-  int init(hipStream_t st) { s = st; CJS_HIP_TRY(hipEventCreate(&a)); CJS_HIP_TRY(hipEventCreate(&b)); ok = true; return 0; }
-  void destroy() { if (ok) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); ok = false; } }
+  hipStream_t s = nullptr;
+  Event a, b;
+  int init(hipStream_t st) { s = st; CJS_HIP_TRY(hipEventCreate(a.put())); CJS_HIP_TRY(hipEventCreate(b.put())); return 0; }
   void start() { (void)hipEventRecord(a, s); }
   double stop() { (void)hipEventRecord(b, s); (void)hipEventSynchronize(b); float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
 };
@@ -145,9 +175,8 @@ struct BwtWork {
   uint32_t* tile_cnt = nullptr;  // 3 * tiles (+ scanned copies)
   uint32_t* counters = nullptr;  // 16: [0] survivors [1] groups [8] tile ticket [9] look-back error
   uint32_t* ghist = nullptr;     // [8][256] digit histograms + [8][256] their exclusive scans (onesweep passes)
-  uint32_t* h_counters = nullptr;  // pinned host mirror
-  hipEvent_t ev_scan = nullptr;    // recorded behind the tile scan of a round (the host waits for the counters, not for the round)
-  void release_host() { if (h_counters) (void)hipHostFree(h_counters); h_counters = nullptr; if (ev_scan) (void)hipEventDestroy(ev_scan); ev_scan = nullptr; lt.reset(); }
+  Pinned<uint32_t> h_counters;     // host mirror
+  Event ev_scan;                   // recorded behind the tile scan of a round (the host waits for the counters, not for the round)
   uint32_t hist_tiles = 0, bintot_segs = 0;   // capacity of hist (tiles) and bintot (segments)
   LaunchTimes lt;                  // dominant-kernel events of the last bwt_run that was given a stats struct
   bool no_large_groups = false;    // per bwt_run: no unresolved group exceeds the tile sorter's limit any more
@@ -167,5 +196,13 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
 // 1 <= d_len[k] <= stride (device array); BWT bytes to d_U with the same layout.  The slots past a block's length are ignored.
 int bwt_run_var(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, const uint32_t* d_len,
                 uint8_t* d_U, uint32_t* d_pidx);
+// The radix passes of the suffix sorter over n keys / nseg segments of `stride` keys (k0 / v0 in, cur: which buffer holds the
+// result), for the inverse BWT of decode.hip (instantiated for K = uint32_t).
+template <typename K>
+int radix_passes_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit);
+template <typename K>
+int radix_pass_segments_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride, int lo_bit, int hi_bit, bool noval, bool first_hist_ready);
+// Inverse sentinel BWT of nb blocks back to back in d_T (lengths lens[], primary indices pidx[], host arrays) into d_out (decode.hip)
+int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint32_t nb, const uint32_t* lens, const uint32_t* pidx, uint8_t* d_out);
 
 }  // namespace cjs

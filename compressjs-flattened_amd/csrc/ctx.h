@@ -7,17 +7,16 @@
 
 namespace cjs {
 struct BatchWork;
-void batch_destroy(BatchWork* b);
+void batch_destroy(BatchWork* b);                                // delete b (batch.hip, where BatchWork is complete)
+struct BatchDelete { void operator()(BatchWork* b) const { batch_destroy(b); } };
 }  // namespace cjs
 
+// Members are destroyed in reverse order: the timer, events and streams first, the workspace last.  cjs_ctx_destroy makes the
+// context's device current first.
 struct cjs_ctx {
   int device = 0, level = 0;
   uint32_t cap = 0;
   size_t max_input = 0, max_blocks = 0, range_blocks = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t side = nullptr;            // block CRCs run here, beside the suffix sort
-  hipStream_t tail = nullptr;            // MTF / Huffman tables of a finished piece run here, beside the suffix sort of the next piece
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_piece[8] = {}, ev_tail = nullptr;
   cjs::Arena arena;
   cjs::Rle1Work rle;
   cjs::BwtWork bwt;
@@ -26,10 +25,15 @@ struct cjs_ctx {
   uint8_t* d_blocks = nullptr;
   uint8_t* d_U = nullptr;
   uint32_t* d_pidx = nullptr;
-  uint64_t* h_scalars = nullptr;   // pinned
+  cjs::Owner<cjs::BatchWork*, cjs::BatchDelete> batch;   // cjs_ctx_create_batch: workspace of the batch path (batch.hip)
+  cjs::Pinned<uint64_t> h_scalars;
+  cjs::Stream stream;
+  cjs::Stream side;                // block CRCs run here, beside the suffix sort
+  cjs::Event ev_join, ev_fork;
+  cjs::Stream tail;                // MTF / Huffman tables of a finished piece run here, beside the suffix sort of the next piece
+  cjs::Event ev_tail, ev_piece[8];
   cjs::EventTimer timer;
   // phase state of a multi-GPU job (cjs_bzip2_shard_tiles -> _blocks -> _pack)
   uint32_t sh_nb = 0, sh_first = 0, sh_cnt = 0, sh_state = 0;
   bool stage_times = true;         // cjs_ctx_set_stage_times
-  cjs::BatchWork* batch = nullptr; // cjs_ctx_create_batch: workspace of the batch path (batch.hip)
 };

@@ -27,14 +27,6 @@
 #include <string.h>
 #include <vector>
 
-namespace cjs {
-template <typename K>
-int radix_passes_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit);
-template <typename K>
-int radix_pass_segments_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride, int lo_bit, int hi_bit, bool noval, bool first_hist_ready);
-int crc_ranges(hipStream_t s, const uint8_t* d_data, const RleBlock* d_blocks, const uint32_t* d_nblocks, uint32_t count, uint32_t max_segs,
-               uint32_t* d_seg_crc, uint32_t* d_crc_out);
-}
 using namespace cjs;
 
 namespace cjs {
@@ -1554,39 +1546,33 @@ static int ibwt_sentinel_slab(hipStream_t s, const uint8_t* d_T, uint32_t max_le
   }
   if (M64 >= 0xFFFFF000ull) return CJS_E_UNSUPPORTED;
   const uint32_t M = (uint32_t)M64;
-  std::vector<void*> to_free;
-  auto dmalloc = [&](void** p, size_t bytes) { if (hipMalloc(p, bytes ? bytes : 4) != hipSuccess) return CJS_E_OUT_OF_MEMORY; to_free.push_back(*p); return 0; };
-  auto cleanup = [&]() { for (void* p : to_free) (void)hipFree(p); };
-  IbBlock* d_blocks = nullptr; uint32_t *d_key0 = nullptr, *d_key1 = nullptr, *d_val0 = nullptr, *d_val1 = nullptr;
-  uint32_t *d_snext = nullptr, *d_ssteps = nullptr, *d_srank = nullptr; int32_t* d_err = nullptr;
+  DevMem<IbBlock> d_blocks;
+  DevMem<uint32_t> d_key0, d_key1, d_val0, d_val1, d_snext, d_ssteps, d_srank, d_hist, d_bintot;
+  DevMem<int32_t> d_err;
   const uint32_t spl_stride = max_len / SPL + 4;
-  BwtWork sw;
-  int rc = dmalloc((void**)&d_blocks, sizeof(IbBlock) * nb);
-  if (!rc) rc = dmalloc((void**)&d_key0, 4 * (size_t)M + 64); if (!rc) rc = dmalloc((void**)&d_key1, 4 * (size_t)M + 64);
-  if (!rc) rc = dmalloc((void**)&d_val0, 4 * (size_t)M + 64); if (!rc) rc = dmalloc((void**)&d_val1, 4 * (size_t)M + 64);
-  if (!rc) rc = dmalloc((void**)&d_snext, 4 * (size_t)nb * spl_stride); if (!rc) rc = dmalloc((void**)&d_ssteps, 4 * (size_t)nb * spl_stride);
-  if (!rc) rc = dmalloc((void**)&d_srank, 4 * (size_t)nb * spl_stride); if (!rc) rc = dmalloc((void**)&d_err, 4 * (size_t)nb);
   const size_t T = ((size_t)M + RS_TILE - 1) / RS_TILE + 1;
-  if (!rc) rc = dmalloc((void**)&sw.hist, BwtWork::hist_words(T) * 4); if (!rc) rc = dmalloc((void**)&sw.bintot, 256 * 4);
-  sw.hist_tiles = (uint32_t)T; sw.bintot_segs = 1;
-  if (!rc && hipMemcpyAsync(d_blocks, chain.data(), sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-  if (rc) { cleanup(); return rc; }
-  hipLaunchKernelGGL(ib_make_keys, dim3(64, nb), dim3(256), 0, s, d_blocks, d_key0, d_val0, 0u);
+  CJS_TRY(d_blocks.alloc(sizeof(IbBlock) * nb));
+  CJS_TRY(d_key0.alloc(4 * (size_t)M + 64)); CJS_TRY(d_key1.alloc(4 * (size_t)M + 64));
+  CJS_TRY(d_val0.alloc(4 * (size_t)M + 64)); CJS_TRY(d_val1.alloc(4 * (size_t)M + 64));
+  CJS_TRY(d_snext.alloc(4 * (size_t)nb * spl_stride)); CJS_TRY(d_ssteps.alloc(4 * (size_t)nb * spl_stride));
+  CJS_TRY(d_srank.alloc(4 * (size_t)nb * spl_stride)); CJS_TRY(d_err.alloc(4 * (size_t)nb));
+  CJS_TRY(d_hist.alloc(BwtWork::hist_words(T) * 4)); CJS_TRY(d_bintot.alloc(256 * 4));
+  BwtWork sw;
+  sw.hist = d_hist; sw.bintot = d_bintot; sw.hist_tiles = (uint32_t)T; sw.bintot_segs = 1;
+  if (hipMemcpyAsync(d_blocks, chain.data(), sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) return CJS_E_HIP;
+  hipLaunchKernelGGL(ib_make_keys, dim3(64, nb), dim3(256), 0, s, d_blocks.p, d_key0.p, d_val0.p, 0u);
   int cur = 0;
   int kbits = 8; { uint32_t x = nb - 1; while (x) { kbits++; x >>= 1; } }
-  rc = radix_passes_public<uint32_t>(s, sw, d_key0, d_val0, d_key1, d_val1, cur, M, 0, kbits);
-  if (rc) { cleanup(); return rc; }
+  CJS_TRY(radix_passes_public<uint32_t>(s, sw, d_key0, d_val0, d_key1, d_val1, cur, M, 0, kbits));
   uint32_t* sval = cur ? d_val1 : d_val0;
   uint32_t* d_dbuf = cur ? d_key0 : d_key1;
-  hipLaunchKernelGGL(ib_pack_sentinel, dim3(64, nb), dim3(256), 0, s, d_blocks, sval, d_dbuf);
+  hipLaunchKernelGGL(ib_pack_sentinel, dim3(64, nb), dim3(256), 0, s, d_blocks.p, sval, d_dbuf);
   const uint32_t cpb = walk_chunks(max_len), wgrid = ((nb * cpb + 7u) >> 3) << 3;
-  hipLaunchKernelGGL(ib_walk1, dim3(wgrid), dim3(WALK_T), WALK_LDS, s, d_dbuf, d_blocks, nb, cpb, spl_stride, d_snext, d_ssteps, 1, nullptr, nullptr);
-  hipLaunchKernelGGL(ib_rank, dim3(nb), dim3(1024), 0, s, d_blocks, nb, spl_stride, d_snext, d_ssteps, d_srank, d_err);
-  hipLaunchKernelGGL(ib_walk2, dim3(wgrid), dim3(WALK_T), WALK_LDS, s, d_dbuf, d_blocks, nb, cpb, spl_stride, d_srank, d_ssteps, d_out, 1, nullptr, nullptr);
+  hipLaunchKernelGGL(ib_walk1, dim3(wgrid), dim3(WALK_T), WALK_LDS, s, d_dbuf, d_blocks.p, nb, cpb, spl_stride, d_snext.p, d_ssteps.p, 1, nullptr, nullptr);
+  hipLaunchKernelGGL(ib_rank, dim3(nb), dim3(1024), 0, s, d_blocks.p, nb, spl_stride, d_snext.p, d_ssteps.p, d_srank.p, d_err.p);
+  hipLaunchKernelGGL(ib_walk2, dim3(wgrid), dim3(WALK_T), WALK_LDS, s, d_dbuf, d_blocks.p, nb, cpb, spl_stride, d_srank.p, d_ssteps.p, d_out, 1, nullptr, nullptr);
   std::vector<int32_t> errs(nb);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(errs.data(), d_err, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
-  cleanup();
-  if (rc) return rc;
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(errs.data(), d_err, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return CJS_E_HIP;
   // The chain visits n distinct rows and then re-enters at row pidx (the step the reference computes last and never
   // uses, BWTC:1163-1165), so the last segment may overshoot; a chain that closes before n rows is corrupt input.
   for (uint32_t k = 0; k < nb; k++) if ((uint32_t)errs[k] < lens[k]) {
@@ -1628,7 +1614,7 @@ constexpr uint32_t DEC_BATCH_BLOCKS = 65535;          // grid.y of the per-block
 
 struct DecShare {
   int device = 0, rc = 0;
-  hipStream_t s = nullptr;
+  Stream s;
   std::vector<DevBuf> bufs;          // device scratch of the share, given back at release() (or early, by drop())
   uint64_t lo = 0, hi = 0;            // candidates starting in bytes [lo, hi) are this share's
   uint64_t up_lo = 0, up_hi = 0;      // uploaded byte range
@@ -1647,13 +1633,13 @@ struct DecShare {
   char detail[96] = {0};            // error detail found by this share's worker thread (the detail text is per calling thread)
   int take(void** p, size_t bytes) { DevBuf b(bytes); if (!(*p = b.p)) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(std::move(b)); return 0; }
   void drop(void* p) { for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; } DevPool::give(p); }
-  void release() {
+  void release() {                    // on the share's device, once its stream has drained; again: nothing
     if (hipSetDevice(device) != hipSuccess) return;
     if (s) (void)hipStreamSynchronize(s);
     bufs.clear();
-    if (s) (void)hipStreamDestroy(s);
-    s = nullptr;
+    s.reset();
   }
+  ~DecShare() { release(); }
 };
 
 struct DecJob {
@@ -1672,7 +1658,7 @@ double ms_since(std::chrono::steady_clock::time_point a) { return std::chrono::d
 // ---- phase A
 void dec_phase_a(DecJob* J, DecShare* S) {
   const auto T0 = std::chrono::steady_clock::now();
-  if (hipSetDevice(S->device) != hipSuccess || hipStreamCreate(&S->s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  if (hipSetDevice(S->device) != hipSuccess || hipStreamCreate(S->s.put()) != hipSuccess) { S->rc = CJS_E_HIP; return; }
   hipStream_t s = S->s;
   const size_t up_n = (size_t)(S->up_hi - S->up_lo);
   uint8_t* d_raw = nullptr; Cand* d_cand = nullptr; uint32_t* d_count = nullptr;
@@ -2001,6 +1987,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   if (nsh > 64) nsh = 64;
   if ((size_t)nsh * 65536 > n) nsh = (uint32_t)(n / 65536 ? n / 65536 : 1);     // tiny inputs: one share
   const uint64_t overlap = (uint64_t)J.tt_stride * 5 / 2 + 65536;               // one block at 20 bits per symbol + tables
+  RestoreDevice restore{dev0};                                                  // after the shares have been released
   std::vector<DecShare> sh(nsh);
   for (uint32_t i = 0; i < nsh; i++) {
     DecShare& S = sh[i];
@@ -2014,10 +2001,8 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
     sh[0].up_lo = sh[0].lo & ~(uint64_t)255; sh[0].up_hi = std::min<uint64_t>(n, sh[0].hi + overlap);
   }
   const auto T0 = std::chrono::steady_clock::now();
-  auto release_all = [&]() { for (auto& x : sh) x.release(); (void)hipSetDevice(dev0); };
-  struct ReleaseGuard { decltype(release_all)& f; ~ReleaseGuard() { f(); } } release_guard{release_all};      // also when an exception unwinds (release is idempotent)
   int rc = for_each_share(sh, &J, dec_phase_a);
-  if (rc) { release_all(); return rc; }
+  if (rc) return rc;
   const double ms_a = ms_since(T0);
 
   // ---- chain walk over all shares' candidates (Bunzip.decode :1776-1794)
@@ -2090,7 +2075,6 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   rc = 0;
   const size_t nb = J.chain.size();
   if (nb == 0) {
-    release_all();
     if (pending_rc) { set_detail("%s", pending_detail); return pending_rc; }
     if (out) { *out = (uint8_t*)malloc(1); if (!*out) return CJS_E_OUT_OF_MEMORY; }
     return 0;
@@ -2098,20 +2082,20 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   {  // the chain is increasing in bit position, so every share owns one contiguous run of it
     size_t k = 0;
     for (uint32_t i = 0; i < nsh; i++) { sh[i].c0 = k; while (k < nb && chain_share[k] == i) k++; sh[i].c1 = k; }
-    if (k != nb) { release_all(); return CJS_E_DATA_ERROR; }      // a chain that runs backwards: corrupt input
+    if (k != nb) return CJS_E_DATA_ERROR;      // a chain that runs backwards: corrupt input
   }
   const auto T1 = std::chrono::steady_clock::now();
   rc = for_each_share(sh, &J, dec_phase_b);
-  if (rc) { release_all(); return rc; }
+  if (rc) return rc;
   const double ms_b = ms_since(T1);
   J.out_off.assign(nb + 1, 0);
   for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
   const uint64_t total = J.out_off[nb];
-  if (out && !pending_rc) { J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1); if (!J.host) { release_all(); return CJS_E_OUT_OF_MEMORY; } }
+  if (out && !pending_rc) { J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1); if (!J.host) return CJS_E_OUT_OF_MEMORY; }
   const auto T2 = std::chrono::steady_clock::now();
   rc = for_each_share(sh, &J, dec_phase_c);
   const double ms_c = ms_since(T2);
-  release_all();
+  for (auto& x : sh) x.release();                              // (the streams have drained before J.host can go back)
   if (J.timing) {
     fprintf(stderr, "[cjs dec] %u share(s): upload + magic scan + block decode %.2f ms, inverse BWT + RLE1 lengths %.2f ms, RLE1 + CRC + D2H %.2f ms\n", nsh, ms_a, ms_b, ms_c);
     for (uint32_t i = 0; i < nsh; i++) fprintf(stderr, "[cjs dec]   share %u (device %d): %zu candidates, blocks [%zu, %zu): %.2f / %.2f / %.2f ms\n", i, sh[i].device,

@@ -29,33 +29,27 @@ constexpr int MAX_DEVICES = 64, SHARD_SLOTS = 4, BOUNDARY_SLOT = SHARD_SLOTS, BA
 struct DevCache {
   std::mutex mu;
   cjs_ctx* ctx = nullptr;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
+  DevMem<uint8_t> d_in, d_out;
   size_t in_cap = 0, out_cap = 0;
   void release() {
     cjs_ctx_destroy(ctx);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    ctx = nullptr; d_in = d_out = nullptr; in_cap = out_cap = 0;
+    ctx = nullptr; d_in.reset(); d_out.reset(); in_cap = out_cap = 0;
   }
   // Device buffer `buf` of `cap` bytes made to hold `need`; never shrinks.  keep = false: the contents go, exactly `need` bytes
   // (failure: buf empty); keep = true: the contents are copied on stream s into max(need, 1.5 cap) + 4096 bytes (failure: unchanged).
-  static int grow(uint8_t*& buf, size_t& cap, size_t need, bool keep = false, hipStream_t s = nullptr) {
+  static int grow(DevMem<uint8_t>& buf, size_t& cap, size_t need, bool keep = false, hipStream_t s = nullptr) {
     if (buf && need <= cap) return 0;
     if (!keep) {
-      if (buf) (void)hipFree(buf);
-      buf = nullptr; cap = 0;
-      if (hipMalloc((void**)&buf, need) != hipSuccess) { buf = nullptr; return CJS_E_OUT_OF_MEMORY; }
+      cap = 0;
+      CJS_TRY(buf.alloc(need));
       cap = need;
       return 0;
     }
     const size_t to = std::max(need, cap + cap / 2) + 4096;
-    uint8_t* p = nullptr;
-    CJS_HIP_TRY(hipMalloc((void**)&p, to));
-    if (buf) {
-      if (hipMemcpyAsync(p, buf, cap, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipFree(p); return CJS_E_HIP; }
-      (void)hipFree(buf);
-    }
-    buf = p; cap = to;
+    DevMem<uint8_t> p;
+    CJS_HIP_TRY(hipMalloc((void**)p.put(), to));
+    if (buf && (hipMemcpyAsync(p, buf, cap, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) return CJS_E_HIP;
+    buf = std::move(p); cap = to;
     return 0;
   }
 };
@@ -73,13 +67,15 @@ struct CacheLease {
 };
 
 // One DevPool buffer, given back when its owner goes or at reset().
-struct DevBuf {
-  void* p = nullptr;
-  explicit DevBuf(size_t bytes) : p(DevPool::take(bytes)) {}
-  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
-  ~DevBuf() { reset(); }
-  void reset() { DevPool::give(p); p = nullptr; }
+struct PoolGive { void operator()(void* p) const { DevPool::give(p); } };
+struct DevBuf : Owner<void*, PoolGive> {
+  explicit DevBuf(size_t bytes) { p = DevPool::take(bytes); }
+};
+
+// Device d made current at scope exit (the caller's device, restored on every path out).
+struct RestoreDevice {
+  int d;
+  ~RestoreDevice() { (void)hipSetDevice(d); }
 };
 
 // f(), an exception that leaves it turned into rc (std::bad_alloc: CJS_E_OUT_OF_MEMORY, else CJS_E_HIP); rc untouched otherwise

@@ -13,6 +13,7 @@
 #include <new>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -33,7 +34,7 @@ extern "C" int cjs_ctx_create_sharded(cjs_ctx** out, int device, size_t max_inpu
   if (device < 0) { if (hipGetDevice(&device) != hipSuccess) return CJS_E_NO_DEVICE; }
   if (device >= ndev) return CJS_E_INVALID_ARG;
   CJS_HIP_TRY(hipSetDevice(device));
-  cjs_ctx* c = new (std::nothrow) cjs_ctx();
+  std::unique_ptr<cjs_ctx> c(new (std::nothrow) cjs_ctx());
   if (!c) return CJS_E_OUT_OF_MEMORY;
   c->device = device; c->level = level; c->cap = (uint32_t)level * 100000u - 19u;
   if (max_input == 0) max_input = 1;
@@ -45,28 +46,25 @@ extern "C" int cjs_ctx_create_sharded(cjs_ctx** out, int device, size_t max_inpu
   size_t bytes = Rle1Work::bytes_needed(max_input, c->cap, rb) + BwtWork::bytes_needed(elems) +
                  MtfWork::bytes_needed(rb, c->cap) + HuffWork::bytes_needed(rb, c->cap) +
                  2 * (elems + 512) + 4 * rb + 65536;
-  int rc = c->arena.init(bytes);
-  if (!rc) rc = c->rle.carve(c->arena, max_input, c->cap, rb);
-  if (!rc) rc = c->bwt.carve(c->arena, elems);
-  if (!rc) rc = c->mtf.carve(c->arena, rb, c->cap);
-  if (!rc) rc = c->huff.carve(c->arena, rb, c->cap);
-  if (!rc) {
-    c->d_blocks = c->arena.take<uint8_t>(elems);
-    c->d_U = c->arena.take<uint8_t>(elems);
-    c->d_pidx = c->arena.take<uint32_t>(rb);
-    if (!c->d_pidx) rc = CJS_E_OUT_OF_MEMORY;
-  }
-  if (!rc && hipStreamCreate(&c->stream) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipStreamCreateWithFlags(&c->tail, hipStreamNonBlocking) != hipSuccess) rc = CJS_E_HIP;
-  for (int i = 0; i < 8 && !rc; i++) if (hipEventCreateWithFlags(&c->ev_piece[i], hipEventDisableTiming) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipHostMalloc((void**)&c->h_scalars, 256) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = c->timer.init(c->stream);
-  if (rc) { cjs_ctx_destroy(c); return rc; }
-  *out = c;
+  CJS_TRY(c->arena.init(bytes));
+  CJS_TRY(c->rle.carve(c->arena, max_input, c->cap, rb));
+  CJS_TRY(c->bwt.carve(c->arena, elems));
+  CJS_TRY(c->mtf.carve(c->arena, rb, c->cap));
+  CJS_TRY(c->huff.carve(c->arena, rb, c->cap));
+  c->d_blocks = c->arena.take<uint8_t>(elems);
+  c->d_U = c->arena.take<uint8_t>(elems);
+  c->d_pidx = c->arena.take<uint32_t>(rb);
+  if (!c->d_pidx) return CJS_E_OUT_OF_MEMORY;
+  CJS_HIP_TRY(hipStreamCreate(c->stream.put()));
+  CJS_HIP_TRY(hipStreamCreateWithFlags(c->side.put(), hipStreamNonBlocking));
+  CJS_HIP_TRY(hipStreamCreateWithFlags(c->tail.put(), hipStreamNonBlocking));
+  for (auto& e : c->ev_piece) CJS_HIP_TRY(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+  CJS_HIP_TRY(hipEventCreateWithFlags(c->ev_tail.put(), hipEventDisableTiming));
+  CJS_HIP_TRY(hipEventCreateWithFlags(c->ev_fork.put(), hipEventDisableTiming));
+  CJS_HIP_TRY(hipEventCreateWithFlags(c->ev_join.put(), hipEventDisableTiming));
+  CJS_HIP_TRY(hipHostMalloc((void**)c->h_scalars.put(), 256));
+  CJS_TRY(c->timer.init(c->stream));
+  *out = c.release();
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
@@ -76,19 +74,6 @@ extern "C" void cjs_ctx_set_stage_times(cjs_ctx* c, int on) { if (c) c->stage_ti
 extern "C" void cjs_ctx_destroy(cjs_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  c->timer.destroy();
-  for (int i = 0; i < 8; i++) if (c->ev_piece[i]) (void)hipEventDestroy(c->ev_piece[i]);
-  if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-  if (c->tail) (void)hipStreamDestroy(c->tail);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-  if (c->batch) batch_destroy(c->batch);
-  c->bwt.release_host();
-  c->rle.release();
-  c->arena.destroy();
   delete c;
 }
 
@@ -105,6 +90,13 @@ static int ensure(DevCache& hc, size_t n, int level, long range_blocks, size_t i
   return 0;
 }
 
+// rc; after an error (rc != 0) the context's three streams have drained first: an early return may leave kernels in flight (block
+// CRCs on the side stream, MTF / Huffman tables of earlier pieces on the tail stream) against a context the caller reuses
+static int drain_on_error(cjs_ctx* c, int rc) {
+  if (rc && c)
+    for (hipStream_t s : {c->side.p, c->tail.p, c->stream.p}) if (s) (void)hipStreamSynchronize(s);
+  return rc;
+}
 // Shared body: stage 0..tables for the whole stream, then pack blocks [first, first+count).
 static int compress_core_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, long first, long count, bool framed,
                               uint8_t* d_out, size_t out_cap, uint64_t* out_bits, uint32_t* block_crcs, long crc_cap,
@@ -113,17 +105,9 @@ static int compress_core(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, l
                          uint8_t* d_out, size_t out_cap, uint64_t* out_bits, uint32_t* block_crcs, long crc_cap,
                          long* total_blocks, cjs_stats* st) {
   CJS_GUARD_BEGIN
-  const int rc = compress_core_impl(c, d_in, n, level, first, count, framed, d_out, out_cap, out_bits, block_crcs, crc_cap, total_blocks, st);
-  // an early return may leave the block-CRC kernels of the side stream in flight against a context the caller reuses
-  if (rc && c) { if (c->side) (void)hipStreamSynchronize(c->side); if (c->stream) (void)hipStreamSynchronize(c->stream); }
-  return rc;
+  return drain_on_error(c, compress_core_impl(c, d_in, n, level, first, count, framed, d_out, out_cap, out_bits, block_crcs, crc_cap, total_blocks, st));
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
-// whole-call timing events; released on every return path
-struct EvPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EvPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 // blocks [f, f + cnt) of the stream whose boundaries the context's tables hold (nb blocks in all): RLE1 bytes + CRCs, suffix
 // sort, MTF / RLE2, Huffman tables.  Everything but the bit packing; nothing here waits for the stream.
 static int blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32_t nb, uint32_t last_len, uint32_t f, uint32_t cnt, cjs_stats* st, bool stage_times) {
@@ -179,10 +163,9 @@ static int compress_core_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int lev
   CJS_HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   c->sh_state = 0;
-  EvPair evp;
-  hipEvent_t &ev0 = evp.a, &ev1 = evp.b;
+  EventTimer whole;                                        // whole-call time
   const bool stage_times = st && c->stage_times;
-  if (st) { memset(st, 0, sizeof *st); CJS_HIP_TRY(hipEventCreate(&ev0)); CJS_HIP_TRY(hipEventCreate(&ev1)); (void)hipEventRecord(ev0, s); }
+  if (st) { memset(st, 0, sizeof *st); CJS_TRY(whole.init(s)); whole.start(); }
   uint32_t nb = 0, last_len = 0;
   if (stage_times) c->timer.start();
   CJS_TRY(rle1_run(s, c->rle, d_in, n, &nb, &last_len));
@@ -208,9 +191,7 @@ static int compress_core_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int lev
   if (st) {
     if (stage_times) st->ms_pack = c->timer.stop();
     if (!stage_times && cnt) c->bwt.lt.resolve(st);      // the stream has drained
-    (void)hipEventRecord(ev1, s); (void)hipEventSynchronize(ev1);
-    float ms = 0; (void)hipEventElapsedTime(&ms, ev0, ev1);
-    st->ms_total = ms;
+    st->ms_total = whole.stop();
     st->blocks = cnt; st->bytes_in = n; st->bytes_out = (*out_bits + 7) / 8;
   }
   return 0;
@@ -257,9 +238,9 @@ static int shard_blocks_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int leve
   CJS_HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   c->sh_state = 0;
-  EvPair evp;
+  EventTimer whole;                                        // whole-call time
   const bool stage_times = st && c->stage_times;
-  if (st) { memset(st, 0, sizeof *st); CJS_HIP_TRY(hipEventCreate(&evp.a)); CJS_HIP_TRY(hipEventCreate(&evp.b)); (void)hipEventRecord(evp.a, s); }
+  if (st) { memset(st, 0, sizeof *st); CJS_TRY(whole.init(s)); whole.start(); }
   if (stage_times) c->timer.start();
   uint32_t nb = 0, last_len = 0;
   if (d_shares) CJS_TRY(rle1_tables_from_shares(s, c->rle, n, (const uint8_t*)d_shares, Rle1Work::tiles_per_rank(n, (uint32_t)world)));
@@ -277,18 +258,14 @@ static int shard_blocks_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int leve
   c->sh_nb = nb; c->sh_first = f; c->sh_cnt = cnt; c->sh_state = 2;
   if (st) {
     if (!stage_times && cnt) c->bwt.lt.resolve(st);
-    (void)hipEventRecord(evp.b, s); (void)hipEventSynchronize(evp.b);
-    float ms = 0; (void)hipEventElapsedTime(&ms, evp.a, evp.b);
-    st->ms_total = ms; st->blocks = cnt; st->bytes_in = n; st->bytes_out = (meta->bits + 7) / 8;
+    st->ms_total = whole.stop(); st->blocks = cnt; st->bytes_in = n; st->bytes_out = (meta->bits + 7) / 8;
   }
   return 0;
 }
 extern "C" int cjs_bzip2_shard_blocks(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, int rank, int world, const void* d_shares,
                                       cjs_shard_meta* meta, cjs_stats* stats) {
   CJS_GUARD_BEGIN
-  const int rc = shard_blocks_impl(c, d_in, n, level, rank, world, d_shares, meta, stats);
-  if (rc && c) { if (c->side) (void)hipStreamSynchronize(c->side); if (c->stream) (void)hipStreamSynchronize(c->stream); }
-  return rc;
+  return drain_on_error(c, shard_blocks_impl(c, d_in, n, level, rank, world, d_shares, meta, stats));
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 // Packs the context's blocks (phase 2 left them behind) at the stream's bit `start` (the rank's first block; rank 0: 32).
@@ -420,7 +397,7 @@ static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* s
   if (!sh->rc && (long)meta.total_blocks != sh->count) sh->rc = CJS_E_HIP;           // cannot happen: the range was cut at block starts
   sync->publish(sh->index, meta, sh->rc);
   published = true;
-  if (sh->rc) { (void)hipStreamSynchronize(c->stream); if (c->side) (void)hipStreamSynchronize(c->side); hc.drop(); return; }
+  if (drain_on_error(c, sh->rc)) { hc.drop(); return; }
   {
     std::unique_lock<std::mutex> lk(sync->mu);
     sync->cv.wait(lk, [&] { return sync->out_ready || sync->rc; });
@@ -483,7 +460,7 @@ static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshar
   int ndev = 0, dev0 = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev0) != hipSuccess) return CJS_E_NO_DEVICE;
   if (ndev > MAX_DEVICES) ndev = MAX_DEVICES;
-  struct RestoreDevice { int d; ~RestoreDevice() { (void)hipSetDevice(d); } } restore{dev0};
+  RestoreDevice restore{dev0};
   // ---- boundary pass: block starts of the whole stream (device 0; its copy of the input serves the shards that run there)
   CacheLease bc{dev_cache(0, BOUNDARY_SLOT)};
   std::vector<uint64_t> starts;
@@ -649,31 +626,27 @@ extern "C" int cjs_stage_mtf(const uint8_t* U, const uint8_t* blocks, size_t n, 
   Arena arena;
   CJS_TRY(arena.init(MtfWork::bytes_needed(nb, stride) + (size_t)nb * stride + 4 * (size_t)nb + 65536));
   MtfWork w;
-  int rc = w.carve(arena, nb, stride);
+  CJS_TRY(w.carve(arena, nb, stride));
   uint8_t* d_U = arena.take<uint8_t>((size_t)nb * stride);
   uint32_t* d_len = arena.take<uint32_t>(nb);
-  if (!rc && (!d_U || !d_len)) rc = CJS_E_OUT_OF_MEMORY;
+  if (!d_U || !d_len) return CJS_E_OUT_OF_MEMORY;
   std::vector<uint32_t> lens(nb, stride);
   lens[nb - 1] = (uint32_t)(n - (size_t)(nb - 1) * stride);
-  hipStream_t s = nullptr;
-  if (!rc && hipStreamCreate(&s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(d_U, U, n, hipMemcpyHostToDevice) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(d_len, lens.data(), 4 * (size_t)nb, hipMemcpyHostToDevice) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = mtf_run(s, w, d_U, nb, d_len);
-  if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) {
-    std::vector<uint32_t> hnpos(nb);
-    if (hipMemcpy(hnpos.data(), w.b.npos, 4 * (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc && hipMemcpy(freq, w.b.freq, 4 * 258 * (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc && hipMemcpy(alphabet, w.b.asz, 4 * (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    for (uint32_t k = 0; k < nb && !rc; k++) {
-      npos[k] = hnpos[k];
-      if (hipMemcpy(A + (size_t)k * (stride + 1), w.b.A + (size_t)k * w.b.a_stride, 2 * (size_t)hnpos[k], hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-    }
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpy(d_U, U, n, hipMemcpyHostToDevice));
+  CJS_HIP_TRY(hipMemcpy(d_len, lens.data(), 4 * (size_t)nb, hipMemcpyHostToDevice));
+  CJS_TRY(mtf_run(s, w, d_U, nb, d_len));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  std::vector<uint32_t> hnpos(nb);
+  CJS_HIP_TRY(hipMemcpy(hnpos.data(), w.b.npos, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(freq, w.b.freq, 4 * 258 * (size_t)nb, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(alphabet, w.b.asz, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < nb; k++) {
+    npos[k] = hnpos[k];
+    CJS_HIP_TRY(hipMemcpy(A + (size_t)k * (stride + 1), w.b.A + (size_t)k * w.b.a_stride, 2 * (size_t)hnpos[k], hipMemcpyDeviceToHost));
   }
-  if (s) (void)hipStreamDestroy(s);
-  arena.destroy();
-  return rc;
+  return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
@@ -686,28 +659,27 @@ extern "C" int cjs_stage_huff(const uint16_t* A, uint32_t npos, uint32_t alphabe
   Arena arena;
   CJS_TRY(arena.init(HuffWork::bytes_needed(1, stride) + 2 * (size_t)npos + 4096 * 4 + 65536));
   HuffWork w;
-  int rc = w.carve(arena, 1, stride);
+  const int rc = w.carve(arena, 1, stride);
   uint16_t* d_A = arena.take<uint16_t>(npos);
   uint32_t* d_misc = arena.take<uint32_t>(2 + 258);
   uint8_t* d_alist = arena.take<uint8_t>(256);
-  if (!rc && (!d_A || !d_misc || !d_alist)) rc = CJS_E_OUT_OF_MEMORY;
   std::vector<uint32_t> misc(2 + 258, 0);
   misc[0] = npos; misc[1] = alphabet;
-  for (uint32_t i = 0; i < npos; i++) { if (A[i] > alphabet + 1) { arena.destroy(); return CJS_E_INVALID_ARG; } misc[2 + A[i]]++; }
+  for (uint32_t i = 0; i < npos; i++) { if (A[i] > alphabet + 1) return CJS_E_INVALID_ARG; misc[2 + A[i]]++; }
+  CJS_TRY(rc);
+  if (!d_A || !d_misc || !d_alist) return CJS_E_OUT_OF_MEMORY;
   uint8_t al[256]; for (int i = 0; i < 256; i++) al[i] = (uint8_t)i;
-  hipStream_t s = nullptr;
-  if (!rc && hipStreamCreate(&s) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(d_A, A, 2 * (size_t)npos, hipMemcpyHostToDevice) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(d_misc, misc.data(), 4 * misc.size(), hipMemcpyHostToDevice) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(d_alist, al, 256, hipMemcpyHostToDevice) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc) rc = huff_tables_run(s, w, 1, d_A, npos, d_misc, d_misc + 1, d_misc + 2, d_alist);
-  if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpy(d_A, A, 2 * (size_t)npos, hipMemcpyHostToDevice));
+  CJS_HIP_TRY(hipMemcpy(d_misc, misc.data(), 4 * misc.size(), hipMemcpyHostToDevice));
+  CJS_HIP_TRY(hipMemcpy(d_alist, al, 256, hipMemcpyHostToDevice));
+  CJS_TRY(huff_tables_run(s, w, 1, d_A, npos, d_misc, d_misc + 1, d_misc + 2, d_alist));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
   const uint32_t nsel = (npos + 49) / 50;
-  if (!rc && hipMemcpy(selectors, w.b.sel, nsel, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(lengths, w.b.lens, 6 * 258, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-  if (!rc && hipMemcpy(ngroups, w.b.ngroups, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = CJS_E_HIP;
-  if (s) (void)hipStreamDestroy(s);
-  arena.destroy();
-  return rc;
+  CJS_HIP_TRY(hipMemcpy(selectors, w.b.sel, nsel, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(lengths, w.b.lens, 6 * 258, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(ngroups, w.b.ngroups, 4, hipMemcpyDeviceToHost));
+  return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }

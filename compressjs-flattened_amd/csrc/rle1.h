@@ -15,7 +15,7 @@ struct RleBlock {
 struct Rle1Work {
   size_t max_in = 0;
   uint32_t cap = 0, max_blocks = 0, max_segs = 0, range_blocks = 0;
-  uint32_t* h_n = nullptr;       // pinned host scalar
+  Pinned<uint32_t> h_n;          // host scalar
   uint64_t *fb = nullptr, *lb = nullptr, *gt = nullptr;
   unsigned long long* agg = nullptr;     // chunk aggregates of the three-phase tile scans
   uint16_t* subpre = nullptr;    // [tiles][16] emitted bytes of the tile before each 256-byte subtile
@@ -32,7 +32,6 @@ struct Rle1Work {
   // range_blocks = max number of blocks materialised / CRC'd per call (0 = all blocks of the stream)
   static size_t bytes_needed(size_t max_in, uint32_t cap, size_t range_blocks = 0);
   int carve(Arena& a, size_t max_in, uint32_t cap, size_t range_blocks = 0);
-  void release() { if (h_n) (void)hipHostFree(h_n); h_n = nullptr; }
 };
 
 int rle1_run(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, uint32_t* nblocks_host, uint32_t* last_len_host = nullptr);

@@ -1088,7 +1088,7 @@ int rle1_walk_run(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, u
   hipLaunchKernelGGL(rle_walk, dim3(1), dim3(1024), 0, s, d_in, N, w.cap, Tn, w.lb, w.fb, w.gt, w.subpre, w.dmod, w.blocks, w.max_blocks, w.nblocks);
   hipLaunchKernelGGL(rle_block_lens, dim3((w.max_blocks + 255) / 256), dim3(256), 0, s, w.blocks, w.nblocks, w.block_len);
   CJS_HIP_TRY(hipGetLastError());
-  if (!w.h_n) CJS_HIP_TRY(hipHostMalloc((void**)&w.h_n, 16));
+  if (!w.h_n) CJS_HIP_TRY(hipHostMalloc((void**)w.h_n.put(), 16));
   CJS_HIP_TRY(hipMemcpyAsync(w.h_n, w.nblocks, 8, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipStreamSynchronize(s));
   *nblocks_host = w.h_n[0];
