@@ -83,6 +83,7 @@ def load_library():
                                                   V, ctypes.c_long, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(Stats)]
     L.cjs_bzip2_compress_batch.argtypes = [ctypes.POINTER(u8p), PS, S, I, PP, PS, PS, V]
     L.cjs_ctx_create_batch.argtypes = [ctypes.POINTER(V), I, S, S, I]
+    L.cjs_bzip2_decompress_batch.argtypes = [ctypes.POINTER(u8p), PS, S, I, PP, PS, PS, ctypes.POINTER(ctypes.c_int32), V]
     L.cjs_bzip2_compress_batch_device.argtypes = [V, V, PS, S, I, V, S, PS, PS]
     L.cjs_bzip2_shard_share_bytes.argtypes = [S, I]
     L.cjs_bzip2_shard_share_bytes.restype = S
@@ -170,6 +171,33 @@ class Bzip2:
     def decompressFile(input, output=None, multistream=False):
         res = _stream_call(load_library().cjs_bzip2_decompress, input, 1 if multistream else 0)
         return _deliver(res, output)
+
+    @staticmethod
+    def decompressFiles(inputs, multistream=False):
+        """decompressFile over a batch: one uint8 ndarray per input, in input order, decoded in shared GPU passes
+        (cjs_bzip2_decompress_batch); views of one result buffer.  If an input fails, CjsError for the lowest-index one,
+        with decompressFile's message for it and the attribute `index`."""
+        arrs = [_coerce_input(x) for x in inputs]
+        L = load_library()
+        count = len(arrs)
+        if not count:
+            return []
+        ptrs = (u8p * count)(*[a.ctypes.data_as(u8p) for a in arrs])
+        lens = (ctypes.c_size_t * count)(*[a.size for a in arrs])
+        off = (ctypes.c_size_t * count)()
+        ln = (ctypes.c_size_t * count)()
+        status = (ctypes.c_int32 * count)()
+        out = u8p()
+        _check(L.cjs_bzip2_decompress_batch(ptrs, lens, count, 1 if multistream else 0, ctypes.byref(out), off, ln, status, None))
+        total = max(off[k] + ln[k] for k in range(count))
+        buf = _adopt(out, total)
+        for k in range(count):
+            if status[k]:
+                detail = L.cjs_last_error_detail().decode()
+                e = CjsError(status[k], L.cjs_strerror(status[k]).decode() + (": " + detail if detail else ""))
+                e.index = k
+                raise e
+        return [buf[off[k]: off[k] + ln[k]] for k in range(count)]
 
 
 class BWTC:

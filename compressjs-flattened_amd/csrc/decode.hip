@@ -25,27 +25,14 @@
 #include <chrono>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <vector>
 
 using namespace cjs;
 
+#include "decode_dev.h"
+
 namespace cjs {
-
-constexpr uint64_t MAGIC_BLOCK = 0x314159265359ull, MAGIC_END = 0x177245385090ull;
-// One splitter every SPL slots of the LF vector.  A walk ends where it lands on a splitter slot -- a 1-in-SPL chance per step --,
-// so the segments are geometric and the walk kernels last as long as the LONGEST of a block's segments, ~SPL x ln(n / SPL) steps
-// of dependent loads (1,100 at 128, 610 at 64): halving SPL halves them; the splitter chain of a block (14,064 nodes at level 9)
-// still fits the ranking kernel's LDS.
-constexpr int SPL = 64;
-
-struct Cand { uint64_t bit; uint32_t kind; uint32_t pad; };      // kind 0 = block, 1 = end of stream; pad = row of the block candidate in the decode buffer (set by the host)
-struct BlockOut {
-  uint64_t end_bit;       // first bit after the block's EOB code
-  uint32_t count;         // decoded BWT bytes (dbufCount)
-  uint32_t orig;          // origPointer
-  uint32_t crc;           // stored block CRC
-  int32_t err;            // 0 or a CJS_E_* code
-};
 
 // ---------------------------------------------------------------- 1. magic scan
 // `in` is addressed by absolute stream byte; bytes [byte0, byte1) are tested as candidate starts, reads stay below n
@@ -64,756 +51,13 @@ __global__ __launch_bounds__(256) void bz_magic_scan(const uint8_t* __restrict__
     }
   }
 }
-
-// ---------------------------------------------------------------- 2. block decode (one wave per candidate)
-struct BitReader {
-  const uint8_t* p; uint64_t nbits, pos;
-  uint64_t win; uint64_t wbyte;                                      // cached big-endian window of bytes [wbyte, wbyte+8)
-  __device__ __forceinline__ void refill() {
-    wbyte = pos >> 3;
-    const uint64_t nbytes = (nbits + 7) >> 3;
-    uint64_t w = 0;
-    if (wbyte + 8 <= nbytes) {
-#pragma unroll
-      for (int i = 0; i < 8; i++) w = (w << 8) | p[wbyte + i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; i++) w = (w << 8) | (wbyte + i < nbytes ? p[wbyte + i] : 0);   // zeros past EOF (:149)
-    }
-    win = w;
-  }
-  __device__ __forceinline__ uint32_t peek(int k) {                  // next k <= 25 bits
-    uint64_t off = pos - (wbyte << 3);
-    if (pos < (wbyte << 3) || off + (uint64_t)k > 64) { refill(); off = pos - (wbyte << 3); }
-    return (uint32_t)((win << off) >> (64 - k));
-  }
-  __device__ __forceinline__ void skip(int k) { pos += k; if (pos > nbits) pos = nbits; }
-  __device__ __forceinline__ uint32_t get(int k) { const uint32_t v = peek(k); skip(k); return v; }
-};
-
-// Canonical code of one table in first-code form: the codes of length L are first[L] .. first[L] + cnt[L] - 1, handed out in
-// symbol order (bysym[start[L] ..]), and first[L + 1] = (first[L] + cnt[L]) << 1.  A prefix j of L bits that is not a code of a
-// shorter length satisfies j >= first[L], so "j - first[L] < cnt[L]" decides -- the same decisions as the reference's
-// limit / base / permute walk (:1522-1581, :1605-1616) on every length table, complete or not.
-struct DecShared {
-  uint32_t first[6][22];           // first code of each length
-  uint16_t cnt[6][22];             // symbols of each length
-  uint16_t start[6][22];           // index of the first symbol of each length in bysym
-  uint16_t bysym[6][260];          // symbols ordered by (length, symbol)
-  uint8_t minlen[8], maxlen[8];
-  uint8_t length[6][260];
-  uint8_t sym_to_byte[256];
-  // left-justified (20-bit) end of the codes of each length, for the branch-free length rule of bz_chain: the code that starts
-  // with the 20 bits x has length 1 + #{L in 1..19 : x >= limp[L]} and exists iff x < limp[20]  (limp[L] = 0 below the shortest
-  // length, = (first[L] + cnt[L]) << (20 - L) from there to the longest, then 2^20 up to L = 19; limp[20] = the longest's)
-  uint32_t limp[6][21];
-};
-
-// big-endian 32-bit word `dw` of the stream, zeros past the end (the reference's reader yields zero bits there, :149)
-__device__ __forceinline__ uint32_t load_be32(const uint8_t* in, uint64_t n, uint64_t dw) {
-  const uint64_t b = dw * 4;
-  if (b + 4 <= n) return __builtin_bswap32(*reinterpret_cast<const uint32_t*>(in + b));       // `in` is a hipMalloc'd copy: 4-byte aligned
-  uint32_t v = 0;
-  for (int i = 0; i < 4; i++) v = (v << 8) | (b + i < n ? in[b + i] : 0u);
-  return v;
-}
-// 4096-bit register window on the stream: lane j holds words base+j (A) and base+64+j (B); all cursor state is wave-uniform
-struct BitWin {
-  const uint8_t* in; uint64_t n; uint64_t base; uint32_t A, B;
-  __device__ __forceinline__ void init(uint64_t pos, int lane) { base = pos >> 5; A = load_be32(in, n, base + lane); B = load_be32(in, n, base + 64 + lane); }
-  __device__ __forceinline__ void ensure(uint64_t pos, int lane) {        // afterwards (pos >> 5) - base < 64
-    while ((pos >> 5) - base >= 64) {
-      if ((pos >> 5) - base >= 128) { init(pos, lane); return; }
-      A = B; base += 64; B = load_be32(in, n, base + 64 + lane);
-    }
-  }
-  __device__ __forceinline__ uint32_t word(uint32_t k) const { return k < 64 ? __builtin_amdgcn_readlane(A, k) : __builtin_amdgcn_readlane(B, k - 64); }
-  __device__ __forceinline__ uint32_t peek(uint64_t pos, int k) const {   // k <= 32 bits at pos (uniform), window must cover it
-    const uint32_t d = (uint32_t)((pos >> 5) - base);
-    const uint64_t w = ((uint64_t)word(d) << 32) | word(d + 1);
-    return (uint32_t)((w << (pos & 31)) >> (64 - k));
-  }
-};
-
-// Block header and code lengths (lane 0, serial), selector list and decode tables (whole wave).  Executed by ONE wave; the results
-// are wave-uniform scalars.  Returns 0 or a CJS_E_* code.  `selp`: LDS scratch of 4096 words (the unary values, a nibble each).
 __device__ uint64_t g_dec_clk[8];      // phase clock of candidate 0 (CJS_DEBUG): 100 MHz ticks
-// a list of eight nibbles: nibble j to the front / the list x read at the positions y holds
-__device__ __forceinline__ uint32_t nib_to_front(uint32_t st, uint32_t j) {
-  const uint32_t val = (st >> (4u * j)) & 15u, low = st & ((1u << (4u * j)) - 1u);
-  return (st & ~((1u << (4u * j + 4u)) - 1u)) | (low << 4) | val;
-}
-__device__ __forceinline__ uint32_t nib_compose(uint32_t x, uint32_t y) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int p = 0; p < 8; p++) r |= ((x >> (4u * ((y >> (4 * p)) & 15u))) & 15u) << (4 * p);
-  return r;
-}
-__device__ int dec_prologue(DecShared& S, BitReader& r, uint32_t dbuf_size, uint32_t& crc, uint32_t& orig, uint32_t& sym_total,
-                            uint32_t& group_count, uint32_t& n_sel, uint8_t* __restrict__ selectors /* global, room for 32768 */, uint32_t* __restrict__ selp) {
-  int err = 0;
-  sym_total = 0; group_count = 0; n_sel = 0; orig = 0;
-  const int lane = lane_id();
-  if (lane == 0) {                                           // header (:1440-1493)
-    crc = r.get(16) << 16; crc |= r.get(16);
-    if (r.get(1)) err = CJS_E_OBSOLETE_INPUT;
-    orig = r.get(24);
-    if (!err && orig > dbuf_size) err = CJS_E_DATA_ERROR;
-    const uint32_t t = r.get(16);
-    for (int i = 0; i < 256; i++) S.sym_to_byte[i] = 0;
-    for (int i = 0; i < 16; i++) if (t & (1u << (15 - i))) {
-      const uint32_t k = r.get(16);
-      for (int j = 0; j < 16; j++) if (k & (1u << (15 - j))) S.sym_to_byte[sym_total++] = (uint8_t)(i * 16 + j);
-    }
-    group_count = r.get(3);
-    if (!err && (group_count < 2 || group_count > 6)) err = CJS_E_DATA_ERROR;
-    n_sel = r.get(15);
-    if (!err && n_sel == 0) err = CJS_E_DATA_ERROR;
-  }
-  err = __builtin_amdgcn_readfirstlane(err);
-  group_count = __builtin_amdgcn_readfirstlane(group_count); n_sel = __builtin_amdgcn_readfirstlane(n_sel); sym_total = __builtin_amdgcn_readfirstlane(sym_total);
-  uint64_t pos = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)r.pos) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(r.pos >> 32)) << 32);
-  if (!err) {
-    // Selector list (:1487-1493): n_sel unary numbers (ones closed by a zero).  Every lane takes 32 bits of a 2048-bit stretch:
-    // its zeros are selector ends, the ones in front of a zero (back to the previous zero, which may sit in the lane before) the
-    // value.  A value may equal group_count (the reference tests the count BEFORE it reads on: j ones pass for j <= group_count,
-    // and its list holds zeros behind the groups); one more is an error.
-    for (uint32_t i = lane; i < (n_sel + 7) / 8; i += 64) selp[i] = 0;
-    __builtin_amdgcn_wave_barrier();
-    const uint64_t nbytes = (r.nbits + 7) >> 3;
-    uint32_t done = 0, carry = 0; int bad = 0; uint64_t endpos = pos;
-    while (done < n_sel) {
-      const uint64_t bp = pos + 32u * (uint32_t)lane;
-      const uint32_t w0 = load_be32(r.p, nbytes, bp >> 5), w1 = load_be32(r.p, nbytes, (bp >> 5) + 1);
-      const uint32_t v = (uint32_t)(((((uint64_t)w0 << 32) | w1) << (bp & 31)) >> 32);
-      const uint32_t nz = (uint32_t)__builtin_popcount(~v);
-      const uint32_t incl = wave_incl_sum(nz), excl = incl - nz;
-      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-      const uint32_t t1 = v == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~v);      // ones at the end of my word (32: all of it -- more than any value)
-      uint32_t pend = (uint32_t)__shfl_up((int)t1, 1, 64);
-      if (lane == 0) pend = carry;
-      uint32_t z = ~v, k = done + excl; int prevb = -1 - (int)pend;
-      while (z && k < n_sel) {
-        const int bidx = __builtin_clz(z);
-        const uint32_t j = (uint32_t)(bidx - prevb - 1);
-        if (j > group_count) bad = 1;
-        else atomicOr(&selp[k >> 3], j << (4u * (k & 7u)));
-        if (k + 1 == n_sel) endpos = bp + (uint32_t)bidx + 1u;
-        z &= ~(0x80000000u >> bidx); prevb = bidx; k++;
-      }
-      if (done + total >= n_sel) {                                       // the lane that holds the last selector knows where the list ends
-        const uint64_t m = __ballot(done + incl >= n_sel);
-        const int l = (int)__builtin_ctzll(m);
-        endpos = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)endpos, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(endpos >> 32), l) << 32);
-        done = n_sel;
-      } else { done += total; carry = (uint32_t)__builtin_amdgcn_readlane((int)t1, 63); pos += 2048; }
-    }
-    if (__ballot(bad != 0)) err = CJS_E_DATA_ERROR;
-    __builtin_amdgcn_wave_barrier();
-    if (!err) {
-      // Move-to-front over the values, the list as nibbles of one register.  A stretch of the list acts on the positions as a
-      // permutation whatever they hold: every lane composes its stretch's (from the identity), a scan composes those in front of each
-      // lane, and a second walk from the list the lane really starts with writes the selectors.  (Position group_count holds the
-      // zero of the reference's zero-initialised list: a value equal to the count reads it, and moves it.)
-      const uint32_t cs = (((n_sel + 63u) >> 6) + 7u) & ~7u;             // values per lane: whole words of selp
-      const uint32_t c0 = min((uint32_t)lane * cs, n_sel), c1 = min(c0 + cs, n_sel);
-      uint32_t R = 0x76543210u, wv = 0;
-      for (uint32_t i = c0; i < c1; i++) {
-        if ((i & 7u) == 0) wv = selp[i >> 3];
-        R = nib_to_front(R, wv & 15u); wv >>= 4;
-      }
-      uint32_t I = R;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)I, d, 64);
-        if (lane >= d) I = nib_compose(up, I);
-      }
-      uint32_t E = (uint32_t)__shfl_up((int)I, 1, 64);
-      if (lane == 0) E = 0x76543210u;
-      uint32_t st = 0;
-      for (uint32_t i = 0; i < group_count; i++) st |= i << (4u * i);
-      st = nib_compose(st, E);
-      for (uint32_t i = c0; i < c1; i++) {
-        if ((i & 7u) == 0) wv = selp[i >> 3];
-        const uint32_t j = wv & 15u; wv >>= 4;
-        selectors[i] = (uint8_t)((st >> (4u * j)) & 15u);
-        st = nib_to_front(st, j);
-      }
-    }
-    pos = endpos > r.nbits ? r.nbits : endpos;
-  }
-  if (!err) {
-    // Code lengths (:1500-1520): per table 5 bits, then per symbol a run of (1, direction) pairs closed by a 0.  Behind a 0 and behind
-    // a direction bit stands a control bit, so in a run of ones the bits alternate control / direction from the run's first (a control
-    // bit): what a lane's first bit is follows from the parity of the ones in front of it.  Every lane walks 32 bits of a 2048-bit
-    // stretch twice: once for its count of symbol ends and its sum of steps, and -- with the sums of the lanes in front -- once more
-    // to write the lengths.  The reference tests the running length wherever it has changed (and where a table starts): 1 .. 20.
-    const uint64_t nbytes = (r.nbits + 7) >> 3;
-    const uint32_t sym_count0 = sym_total + 2;
-    int bad = 0;
-    for (uint32_t g = 0; g < group_count && !__ballot(bad != 0); g++) {
-      int cur0;
-      { const uint32_t w0 = load_be32(r.p, nbytes, pos >> 5), w1 = load_be32(r.p, nbytes, (pos >> 5) + 1);
-        cur0 = (int)((((((uint64_t)w0 << 32) | w1) << (pos & 31)) >> 59)); pos += 5; }
-      if (cur0 < 1 || cur0 > 20) bad = 1;
-      uint32_t done = 0, par_in = 0;
-      for (;;) {
-        const uint64_t bp = pos + 32u * (uint32_t)lane;
-        const uint32_t w0 = load_be32(r.p, nbytes, bp >> 5), w1 = load_be32(r.p, nbytes, (bp >> 5) + 1);
-        const uint32_t v = (uint32_t)(((((uint64_t)w0 << 32) | w1) << (bp & 31)) >> 32);
-        const uint32_t t1 = v == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~v);
-        const uint64_t m_ao = __ballot(v == 0xFFFFFFFFu), m_par = __ballot((t1 & 1u) != 0);
-        const uint64_t below = ~m_ao & ((1ull << lane) - 1ull);
-        const uint32_t par = below ? (uint32_t)((m_par >> (63 - __builtin_clzll(below))) & 1ull) : par_in;      // 1: my first bit is a direction bit
-        uint32_t state = par, ne = 0; int nd = 0;
-        for (int b = 31; b >= 0; b--) {
-          const uint32_t bit = (v >> b) & 1u;
-          if (state) { nd += bit ? -1 : 1; state = 0; }
-          else if (bit) state = 1;
-          else ne++;
-        }
-        const uint32_t ie = wave_incl_sum(ne); const int id = wave_incl_sum(nd);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)ie, 63);
-        uint32_t idx = done + ie - ne; int cur = cur0 + id - nd; uint64_t endpos = 0;
-        state = par;
-        for (int b = 31; b >= 0 && idx < sym_count0; b--) {
-          const uint32_t bit = (v >> b) & 1u;
-          if (state) { cur += bit ? -1 : 1; if (cur < 1 || cur > 20) bad = 1; state = 0; }
-          else if (bit) state = 1;
-          else { S.length[g][idx] = (uint8_t)cur; if (++idx == sym_count0) endpos = bp + (uint32_t)(32 - b); }
-        }
-        if (__ballot(bad != 0)) break;                                   // (the reference stops at the first length out of range; so must a stretch of ones)
-        if (done + total >= sym_count0) {                                // the lane that wrote the last length knows where the table ends
-          const int l = (int)__builtin_ctzll(__ballot(done + ie >= sym_count0));
-          pos = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)endpos, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(endpos >> 32), l) << 32);
-          break;
-        }
-        done += total; cur0 += __builtin_amdgcn_readlane(id, 63);
-        if (~m_ao) par_in = (uint32_t)((m_par >> (63 - __builtin_clzll(~m_ao))) & 1ull);
-        pos += 2048;
-      }
-    }
-    if (__ballot(bad != 0)) err = CJS_E_DATA_ERROR;
-  }
-  if (lane == 0) r.pos = pos > r.nbits ? r.nbits : pos;
-  // lane 0's results become wave-uniform scalars (readfirstlane, not a shuffle: the compiler must KNOW they are uniform,
-  // or the whole symbol loop is compiled as divergent code under exec masks)
-  err = __builtin_amdgcn_readfirstlane(err);
-  sym_total = __builtin_amdgcn_readfirstlane(sym_total); group_count = __builtin_amdgcn_readfirstlane(group_count);
-  n_sel = __builtin_amdgcn_readfirstlane(n_sel);
-  const uint32_t sym_count = sym_total + 2;
-  __builtin_amdgcn_wave_barrier();
-  if (!err) {
-    // canonical tables: lane g builds table g -- a counting sort of the symbols by length, then the first codes
-    if ((uint32_t)lane < group_count) {
-      const int g = lane;
-      for (int i = 0; i < 22; i++) { S.cnt[g][i] = 0; S.first[g][i] = 0; S.start[g][i] = 0; }
-      int mn = 20, mx = 1;
-      for (uint32_t i = 0; i < sym_count; i++) { const int l = S.length[g][i]; S.cnt[g][l]++; mn = l < mn ? l : mn; mx = l > mx ? l : mx; }
-      S.minlen[g] = (uint8_t)mn; S.maxlen[g] = (uint8_t)mx;
-      uint32_t code = 0, at = 0; uint16_t fillp[22];
-      for (int l = mn; l <= mx; l++) {
-        S.first[g][l] = code; S.start[g][l] = (uint16_t)at; fillp[l] = (uint16_t)at;
-        at += S.cnt[g][l];
-        code = (code + S.cnt[g][l]) << 1;
-      }
-      for (uint32_t i = 0; i < sym_count; i++) S.bysym[g][fillp[S.length[g][i]]++] = (uint16_t)i;
-      for (int l = 1; l <= 20; l++) {
-        const uint32_t lj = l < mn ? 0u : l <= mx ? (S.first[g][l] + S.cnt[g][l]) << (20 - l) : (1u << 20);
-        S.limp[g][l] = l == 20 ? (mx == 20 ? lj : (S.first[g][mx] + S.cnt[g][mx]) << (20 - mx)) : (l < mx ? lj : (l >= mn ? (1u << 20) : 0u));
-      }
-      S.limp[g][0] = 0;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  crc = __builtin_amdgcn_readfirstlane(crc);
-  orig = __builtin_amdgcn_readfirstlane(orig);
-  r.pos = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)r.pos) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(r.pos >> 32)) << 32);   // (the builtin returns int: no sign extension of a low half >= 2^31)
-  return err;
-}
 
-// ---------------------------------------------------------------- 2b. block decode in stages
-// The Huffman chain of a block looks serial -- the table changes every 50 symbols, so there is no self-synchronisation to exploit
-// -- but the only thing one group of 50 symbols hands to the next is WHERE IT ENDS.  So:
-//   bz_chain        one workgroup per candidate: header, selector list and code tables (wave 0, in 2048-bit stretches), then up to
-//                   four groups per step: for every bit position i of a group's positions thread i looks up the length of the code
-//                   that WOULD start there: next[i] = i + len.  Five rounds of pointer doubling in LDS (next^2 .. next^32) give
-//                   next^50(0) = 2 + 16 + 32 for the first group; the groups behind it get tables of their own over positions
-//                   placed ahead, built in the same rounds (chain_tables).  About ten LDS round trips per 200 symbols instead of
-//                   50 x (lookup + hop) per group by one lone wave.
-//   bz_group_syms   one lane per group, all groups of all candidates at once: the 50 symbols from the group's start; the first
-//                   end-of-block symbol and the first undecodable code of the block by 64-bit atomic minima.
-//   bz_sym_ops      one workgroup per candidate over the symbols in front of the end-of-block: RUNA/RUNB digits -> byte counts,
-//                   running output offset, every rank symbol leaves as (rank, output offset).  No move-to-front, no output bytes.
-//   bz_mtf_tiles    the move-to-front of 256 consecutive rank ops of a block, started from the identity list, by one wave
-//                   (list as bytes across the lanes, shift by wave_shr DPP): op j becomes q_j = the slot of the TILE-START
-//                   list it reads, and the tile leaves its permutation P_t.   All tiles of all blocks in parallel.
-//   bz_mtf_chunk_perm + bz_mtf_compose  chain the tiles: start list L_(t+1)[p] = L_t[P_t[p]] (an LDS gather per tile), in chunks of 64 tiles.
-//   bz_mtf_emit     one thread per op: byte = L_t[q_j] at its offset, and the zero-rank run behind it (the gap to the next
-//                   op's offset) is filled with the same byte (long runs by the whole wave).
-// Same results as the reference loop (:1597-1670): every way it can fail there is DATA_ERROR, so a block is good iff its first
-// end-of-block symbol comes before its first undecodable code, the selectors do not run out first, and the bytes fit the block.
-struct RowTab {                    // per candidate row, in global memory between the stages
-  uint16_t fast[6][1024];          // (sym << 5) | len by the next 10 bits, 0 = not decodable within 10 bits
-  uint32_t first[6][22];
-  uint16_t cnt[6][22], start[6][22], bysym[6][260];
-  uint8_t minlen[8], maxlen[8];
-  uint32_t sym_total, group_count, n_sel, err;      // err: the header's verdict
-  uint64_t data_bit;               // first bit of the symbol data
-  uint32_t crc, orig;
-  uint32_t ngroups_ok;             // groups whose start bit is known (the chain's extent)
-  uint32_t pad;
-  unsigned long long eob_key;      // min over end-of-block symbols of (symbol index << 32 | bit behind the code - data_bit); ~0 = none
-  unsigned long long err_key;      // min over undecodable codes of (symbol index << 32); ~0 = none
-};
-constexpr uint32_t CH_T = 512;                  // threads of bz_chain
-constexpr uint32_t CH_SPAN = 1024;              // bit positions of a group's span (50 codes of <= 20 bits)
-constexpr uint32_t CH_ARR = CH_SPAN + 64;
-constexpr uint32_t CH_NONE = CH_ARR - 1;         // next[] of a position where no code of the table starts (an entry of its own, like the positions behind a span)
-constexpr uint32_t CH_WIN = CH_T - 64;          // positions of a table in a step's first attempt: one per thread, the last 64 map to themselves
-constexpr uint32_t CH_ARR2 = CH_T + 64;         // the later groups' tables: CH_WIN positions, and 64 + 64 that map to themselves
-constexpr uint32_t CH_NONE2 = CH_ARR2 - 1;
-constexpr uint32_t CH_WORDS = 2048;             // 32-bit words of the stream kept in LDS (65536 bits: ~180 groups of text)
-constexpr uint32_t GROUP_SYMS = 50;
-constexpr uint32_t MAX_SELECTORS = 32768;
+// stage 2b's kernels, single-stream form (the batch form: batch_dec.hip)
+#define BZ_BATCH 0
+#include "bz_stage2.h"
+#undef BZ_BATCH
 
-
-// bz_chain's tables: level lv (next^(2^lv)) of table t by byte offset.  A level is read by the round behind it only (the hops aside: 1, 4
-// and 5), so four arrays hold the six: 0 and 3 share one, 2 and 5 another -- and the step behind writes its level 0 where this step's
-// last lookups (level 5) do not read.
-__host__ __device__ constexpr int ch_slot(int lv) { return lv == 1 ? 0 : lv == 4 ? 1 : (lv == 2 || lv == 5) ? 2 : 3; }
-template <uint32_t N> __device__ __forceinline__ uint32_t ch_ld(uint16_t (*t)[N], int lv, uint32_t off) { return *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(t[ch_slot(lv)]) + off); }
-template <uint32_t N> __device__ __forceinline__ void ch_st(uint16_t (*t)[N], int lv, uint32_t i, uint32_t v) { t[ch_slot(lv)][i] = (uint16_t)v; }
-// The 20 bits at bit o of the window
-__device__ __forceinline__ uint32_t chain_bits(const uint32_t* wbuf, uint32_t o) {
-  const uint32_t w0 = wbuf[o >> 5], w1 = wbuf[(o >> 5) + 1];
-  return (uint32_t)(((((uint64_t)w0 << 32) | w1) << (o & 31)) >> 44);
-}
-// The position behind the code that starts at position i with the 20 bits x20 under table g (CH_NONE: no code starts there).  e is the
-// entry of the 12-bit direct table: the length of a code of <= 12 bits, CH_NOCODE, or 0 for a longer code, whose length is 13 + the
-// number of lengths 13 .. 19 whose left-justified codes all lie below x20 (well under a percent of ARBITRARY bit offsets: one wave in
-// four holds one; with a 10-bit table nearly every wave did and paid the compares).
-constexpr uint32_t CH_NOCODE = 0xFF;
-__device__ __forceinline__ uint32_t chain_next(const DecShared& S, int g, uint32_t e, uint32_t x20, uint32_t i, uint32_t none) {
-  if (e) return e == CH_NOCODE ? none : i + e;
-  uint32_t len = 13;
-#pragma unroll
-  for (int l = 13; l <= 19; l++) len += x20 >= S.limp[g][l] ? 1u : 0u;
-  return x20 < S.limp[g][20] ? i + len : none;
-}
-// One step's tables for NT groups (k on A from its known start, k + q on L[q - 1] from bit start[q - 1] of the step): next^1, then five
-// rounds of doubling.  Tables hold BYTE OFFSETS (2 x position) into a level's array, and every position behind a table's last (>= 64 of
-// them: a code is at most 20 bits) maps to itself, as does CH_NONE: a chain that has left its positions, or met one where no code
-// starts, stays where it is without a compare -- a round is one gather and one store per table, all threads on all tables, no branch
-// (the CU's scalar unit serves every wave's branches and address arithmetic: with one thread per position and table, and a branch
-// around each, those instructions outnumbered the vector ones three to one and set the pace).  e[q]: where group k + q ends, in
-// positions of its table (every lane the same value; CH_NONE / CH_NONE2 or beyond the table's positions: not known from this step).
-// Group k's 50 codes are 2 + 16 + 32: the first two hops as soon as their table stands, beside the following round's gathers.
-struct ChainLater { uint16_t (*t)[CH_ARR2]; int g; uint32_t start; };
-template <int NT>
-__device__ __forceinline__ void chain_tables(const DecShared& S, const uint8_t (*len12)[4096], const uint32_t* wbuf, uint16_t (*A)[CH_ARR], const ChainLater (&L)[3],
-                                             uint32_t i, uint32_t o0, int g, uint32_t span, bool whole, uint32_t (&e)[4]) {
-  // (the tables' loads side by side: two LDS latencies for all of them)
-  uint32_t x[NT], en[NT], m[NT];
-  x[0] = chain_bits(wbuf, o0 + i);
-#pragma unroll
-  for (int q = 1; q < NT; q++) x[q] = chain_bits(wbuf, o0 + L[q - 1].start + i);
-  en[0] = len12[g][x[0] >> 8];
-#pragma unroll
-  for (int q = 1; q < NT; q++) en[q] = len12[L[q - 1].g][x[q] >> 8];
-  m[0] = chain_next(S, g, en[0], x[0], i, CH_NONE);
-  m[0] = 2 * (i < span ? m[0] : i);
-#pragma unroll
-  for (int q = 1; q < NT; q++) { m[q] = chain_next(S, L[q - 1].g, en[q], x[q], i, CH_NONE2); m[q] = 2 * (i < CH_WIN ? m[q] : i); }
-  ch_st(A, 0, i, m[0]);
-#pragma unroll
-  for (int q = 1; q < NT; q++) ch_st(L[q - 1].t, 0, i, m[q]);
-  __syncthreads();
-  uint32_t hop = 0;
-#pragma unroll
-  for (int lv = 1; lv <= 4; lv++) {
-    m[0] = ch_ld(A, lv - 1, m[0]);
-#pragma unroll
-    for (int q = 1; q < NT; q++) m[q] = ch_ld(L[q - 1].t, lv - 1, m[q]);
-    ch_st(A, lv, i, m[0]);
-#pragma unroll
-    for (int q = 1; q < NT; q++) ch_st(L[q - 1].t, lv, i, m[q]);
-    __syncthreads();
-    if (lv == 1) hop = ch_ld(A, 1, 0);
-    if (lv == 4) hop = ch_ld(A, 4, hop);
-  }
-  // The last round: A's next^32 (one hop is left for it), but the later tables' next^50 = next^2 . next^16 . next^32 outright: two more
-  // gathers here (every position at once) instead of two more hops each behind the barrier (one after the other).
-  m[0] = ch_ld(A, 4, m[0]);
-#pragma unroll
-  for (int q = 1; q < NT; q++) m[q] = ch_ld(L[q - 1].t, 4, m[q]);
-  ch_st(A, 5, i, m[0]);
-#pragma unroll
-  for (int q = 1; q < NT; q++) m[q] = ch_ld(L[q - 1].t, 4, m[q]);
-#pragma unroll
-  for (int q = 1; q < NT; q++) m[q] = ch_ld(L[q - 1].t, 1, m[q]);
-#pragma unroll
-  for (int q = 1; q < NT; q++) ch_st(L[q - 1].t, 5, i, m[q]);
-  __syncthreads();
-  // Where the groups end.  A chain that has left its positions STAYS on the value it left with, and a value equal to the number of
-  // positions may be such a stop in the middle of the group: only a value below it is the end of 50 codes for sure -- except on the
-  // whole span, whose last position nothing but 50 codes of the longest length reach.  A group that starts outside its table's
-  // positions is looked up at CH_NONE2, which maps to itself.
-  e[0] = ch_ld(A, 5, hop) >> 1;
-  e[1] = e[2] = e[3] = CH_NONE2;
-  bool known = e[0] < span || (whole && e[0] == span);
-  uint32_t at = e[0];                            // where the group in front ends, in bits of the step
-#pragma unroll
-  for (int q = 1; q < NT; q++) {
-    const bool in = known && at >= L[q - 1].start && at - L[q - 1].start < CH_WIN;
-    e[q] = ch_ld(L[q - 1].t, 5, 2 * (in ? at - L[q - 1].start : CH_NONE2)) >> 1;
-    known = e[q] < CH_WIN;
-    at = L[q - 1].start + e[q];
-  }
-}
-// The same for group k alone on its whole span (two positions per thread)
-__device__ __forceinline__ uint32_t chain_table_full(const DecShared& S, const uint8_t (*len12)[4096], const uint32_t* wbuf, uint16_t (*A)[CH_ARR], uint32_t i, uint32_t o0, int g, uint32_t span) {
-  const uint32_t j = i + CH_T;
-  const uint32_t x0 = chain_bits(wbuf, o0 + i), x1 = chain_bits(wbuf, o0 + j);
-  uint32_t m0 = chain_next(S, g, len12[g][x0 >> 8], x0, i, CH_NONE), m1 = chain_next(S, g, len12[g][x1 >> 8], x1, j, CH_NONE);
-  m0 = 2 * (i < span ? m0 : i); m1 = 2 * (j < span ? m1 : j);
-  ch_st(A, 0, i, m0); ch_st(A, 0, j, m1);
-  __syncthreads();
-  uint32_t hop = 0;
-#pragma unroll
-  for (int lv = 1; lv <= 5; lv++) {
-    m0 = ch_ld(A, lv - 1, m0); m1 = ch_ld(A, lv - 1, m1);
-    ch_st(A, lv, i, m0); ch_st(A, lv, j, m1);
-    __syncthreads();
-    if (lv == 1) hop = ch_ld(A, 1, 0);
-    if (lv == 4) hop = ch_ld(A, 4, hop);
-  }
-  return hop;
-}
-
-__global__ __launch_bounds__(CH_T) void bz_chain(const uint8_t* __restrict__ in, uint64_t n, const Cand* __restrict__ cands, uint32_t ncand, uint32_t dbuf_size,
-                                                 RowTab* __restrict__ tabs, uint8_t* __restrict__ sel_all, uint32_t* __restrict__ gstart_all,
-                                                 uint8_t* __restrict__ l0_all, BlockOut* __restrict__ outs, uint32_t row0) {
-  __shared__ DecShared S;
-  __shared__ uint32_t scratch[4 * CH_ARR / 2 + 12 * CH_ARR2 / 2 + CH_WORDS + 2];         // the prologue's selector values (4096 words), then the chain's arrays
-  uint16_t (*A)[CH_ARR] = reinterpret_cast<uint16_t (*)[CH_ARR]>(scratch);                     // group k: next^(2^lv), lv = 0 .. 5, in four arrays (ch_slot)
-  uint16_t (*B)[CH_ARR2] = reinterpret_cast<uint16_t (*)[CH_ARR2]>(scratch + 4 * CH_ARR / 2);                    // groups k + 1, k + 2, k + 3: four arrays each
-  uint32_t* wbuf = scratch + 4 * CH_ARR / 2 + 12 * CH_ARR2 / 2;
-  __shared__ uint8_t len12[6][4096];            // code length by the next 12 bits (chain_next)
-  __shared__ uint64_t s_pos;
-  __shared__ uint32_t s_hdr[8];
-  const uint32_t c = blockIdx.x;
-  if (c >= ncand) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (cands[c].kind != 0) {                     // end-of-stream candidate: nothing to decode
-    if (tid == 0) { BlockOut bo; bo.end_bit = cands[c].bit + 48; bo.count = 0; bo.orig = 0; bo.crc = 0; bo.err = 0; outs[c] = bo; }
-    return;
-  }
-  const uint32_t row = cands[c].pad - row0;     // row of this batch's scratch
-  RowTab& T = tabs[row];
-  uint8_t* sel = sel_all + (size_t)row * MAX_SELECTORS;
-  uint32_t* gstart = gstart_all + (size_t)row * (MAX_SELECTORS + 1);
-  const uint64_t t_k0 = wall_clock64();
-  if (tid < 64) {                               // wave 0: header, selectors, code lengths, tables
-    BitReader r{in, n * 8, cands[c].bit + 48, 0, ~0ull >> 4};
-    uint32_t sym_total = 0, group_count = 0, n_sel = 0, orig = 0, crc = 0;
-    const int err = dec_prologue(S, r, dbuf_size, crc, orig, sym_total, group_count, n_sel, sel, scratch);
-    if (lane == 0) {
-      s_hdr[0] = (uint32_t)err; s_hdr[1] = sym_total; s_hdr[2] = group_count; s_hdr[3] = n_sel; s_hdr[4] = crc; s_hdr[5] = orig;
-      s_pos = r.pos;
-    }
-  }
-  __threadfence_block();
-  __syncthreads();
-  const uint64_t t_hdr = wall_clock64();
-  if (tid == 0 && blockIdx.x == 0) g_dec_clk[5] = t_hdr - t_k0;
-  const int herr = (int)s_hdr[0];
-  const uint32_t group_count = s_hdr[2], n_sel = s_hdr[3];
-  const uint64_t data_bit = s_pos;
-  // the tables go to global memory for the symbol stage
-  // ... with the 10-bit direct tables: entry x = the code that is a prefix of the 10 bits x, if it has one of <= 10 bits
-  if (!herr) {
-    for (uint32_t e = tid; e < group_count * 1024u; e += CH_T) {
-      const uint32_t t = e >> 10, x = e & 1023u;
-      const int mn = S.minlen[t], mx = S.maxlen[t];
-      uint16_t v = 0;
-      for (int l = mn; l <= 10 && l <= mx; l++) {
-        const uint32_t k = (x >> (10 - l)) - S.first[t][l];              // (not below first: no shorter code matched)
-        if (k < S.cnt[t][l]) { v = (uint16_t)((S.bysym[t][S.start[t][l] + k] << 5) | l); break; }
-      }
-      T.fast[t][x] = v;
-    }
-  }
-  for (uint32_t i = tid; i < 6 * 22; i += CH_T) { (&T.first[0][0])[i] = (&S.first[0][0])[i]; (&T.cnt[0][0])[i] = (&S.cnt[0][0])[i]; (&T.start[0][0])[i] = (&S.start[0][0])[i]; }
-  for (uint32_t i = tid; i < 6 * 260; i += CH_T) (&T.bysym[0][0])[i] = (&S.bysym[0][0])[i];
-  if (tid < 8) { T.minlen[tid] = S.minlen[tid]; T.maxlen[tid] = S.maxlen[tid]; }
-  for (int i = tid; i < 256; i += CH_T) l0_all[(size_t)row * 256 + i] = S.sym_to_byte[i];
-  // 12-bit direct length tables.  The length rule is 1 + #{L in 1..19 : x20 >= limp[L]}, and a limit of a length <= 12 has its low 8
-  // bits clear: the 12 bits x decide those; with all 12 below x the code is longer (or there is none) and the entry is 0.
-  if (!herr) {
-    for (uint32_t e = tid; e < group_count * 4096u; e += CH_T) {
-      const uint32_t t = e >> 12, x = e & 4095u;
-      uint32_t c = 0;
-#pragma unroll
-      for (int l = 1; l <= 12; l++) c += x >= (S.limp[t][l] >> 8) ? 1u : 0u;
-      len12[t][x] = (uint8_t)(c == 12 ? 0u : (x << 8) < S.limp[t][20] ? c + 1 : CH_NOCODE);
-    }
-  }
-  // (the positions behind the last a thread writes, once for every level)
-  if (tid < 64) { for (int a = 0; a < 4; a++) A[a][CH_SPAN + tid] = (uint16_t)(2 * (CH_SPAN + tid)); for (int a = 0; a < 12; a++) B[a][CH_T + tid] = (uint16_t)(2 * (CH_T + tid)); }
-  __syncthreads();
-  uint32_t ok_groups = 0;
-  if (!herr) {
-    // Nothing the step's first instructions need comes from memory: the tables' shortest / longest lengths sit in registers (5 / 10 bits
-    // each: the longest, and 50 x the shortest), and lane j of every wave holds the selectors kb + 8 j .. kb + 8 j + 7 as nibbles (15:
-    // none) -- written by wave 0 above, visible after the barrier; 512 selectors per fill.
-    uint32_t maxp = 0; uint64_t minp = 0;
-    for (int t = 0; t < 6; t++) { minp |= (uint64_t)(GROUP_SYMS * ((uint32_t)S.minlen[t] & 31u)) << (10 * t); maxp |= ((uint32_t)S.maxlen[t] & 31u) << (5 * t); }
-    maxp = (uint32_t)__builtin_amdgcn_readfirstlane((int)maxp);
-    minp = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)minp) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(minp >> 32)) << 32);
-    uint32_t kb = 0, sw = 0, lp = 0;
-    uint32_t rel = 0, o0 = CH_WORDS * 32;          // bits from data_bit / from the window's first word to the step's first bit (o0 past the window: fill it)
-    for (uint32_t k = 0; k < n_sel;) {
-      if (k == 0 || k - kb >= 512 - 16) {          // (uniform) the next 512 selectors
-        kb = k & ~7u;
-        const uint32_t at = kb + 8u * (uint32_t)lane;
-        uint64_t v = ~0ull;
-        if (at < n_sel) v = *reinterpret_cast<const uint64_t*>(sel + at);                  // (the row is 8-byte aligned; bytes behind the list: masked)
-        if (at + 8 > n_sel && at < n_sel) v |= ~0ull << (8u * (n_sel - at));
-        v = (v | (v >> 4)) & 0x00FF00FF00FF00FFull; v = (v | (v >> 8)) & 0x0000FFFF0000FFFFull; v = v | (v >> 16);
-        sw = (uint32_t)v;
-      }
-      const uint32_t kj = (uint32_t)__builtin_amdgcn_readfirstlane((int)(k - kb));
-      const uint64_t sn = (((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)sw, (int)((kj >> 3) + 1)) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)sw, (int)(kj >> 3))) >> (4u * (kj & 7u));
-      // Up to FOUR groups per step.  The tables next^1 .. next^32 of a group do not depend on where the group starts, only on its
-      // code table and on the bit positions they cover.  So beside group k's tables from its known start (A) the same threads build
-      // those of group k + 1 under ITS code table over CH_WIN positions from the earliest bit it can start at (50 x the shortest code
-      // of group k's table), and of groups k + 2 and k + 3 likewise -- in the same rounds, behind the same barriers.  When the hops
-      // on A have found where group k ends, the later tables are looked up there, one after the other.  The span that is safe for
-      // any 50 codes (50 x the longest) is about five times what 50 codes of text take (~210 bits): the first attempt works on CH_WIN
-      // positions; a group k that leaves them (or meets a position where no code starts) is worked out again, alone, on its whole
-      // span; a later group that leaves its table's positions, or starts in front of them, simply is the first group of the next step.
-      const int g = (int)(sn & 15u);
-      const uint32_t n1 = (uint32_t)(sn >> 4) & 15u, n2 = (uint32_t)(sn >> 8) & 15u, n3 = (uint32_t)(sn >> 12) & 15u;
-      const int g1 = n1 < 6 ? (int)n1 : -1, g2 = n2 < 6 ? (int)n2 : -1, g3 = n3 < 6 ? (int)n3 : -1;
-      const uint32_t full_span = min(GROUP_SYMS * ((maxp >> (5 * g)) & 31u), CH_SPAN);
-      const uint32_t base1 = (uint32_t)(minp >> (10 * g)) & 1023u;                          // group k + 1 starts at or behind this offset
-      const uint32_t base2 = base1 + ((uint32_t)(minp >> (10 * min(n1, 5u))) & 1023u);       // ... group k + 2 at or behind this one
-      const uint32_t base3 = base2 + ((uint32_t)(minp >> (10 * min(n2, 5u))) & 1023u);       // ... and group k + 3 here (no group: not used)
-      if (o0 + 2 * CH_SPAN + 128 > CH_WORDS * 32) {                                         // (uniform) refill the bit window
-        __syncthreads();
-        const uint64_t pos = data_bit + rel, wbase = pos >> 5;
-        for (uint32_t i = tid; i < CH_WORDS + 2; i += CH_T) wbuf[i] = load_be32(in, n, wbase + i);
-        o0 = (uint32_t)(pos & 31u);
-        __syncthreads();
-      }
-      const uint32_t i = (uint32_t)tid;
-      // (where the later tables start: the earliest bit the group can start at, or -- lp = the bits of the last group -- half a group in
-      // front of where groups of that length would put it, if that is more: its CH_WIN positions must hold the group's start AND end)
-      const ChainLater L[3] = {{B, g1, min(base1, CH_SPAN)},
-                               {B + 4, g2, min(max(base2, lp * 3 / 2), 2 * CH_SPAN - CH_T)},
-                               {B + 8, g3, min(max(base3, lp * 5 / 2), 2 * CH_SPAN - CH_T)}};
-      uint32_t span = min(full_span, CH_WIN), e[4];
-      if (g3 >= 0) chain_tables<4>(S, len12, wbuf, A, L, i, o0, g, span, span == full_span, e);
-      else if (g2 >= 0) chain_tables<3>(S, len12, wbuf, A, L, i, o0, g, span, span == full_span, e);
-      else if (g1 >= 0) chain_tables<2>(S, len12, wbuf, A, L, i, o0, g, span, span == full_span, e);
-      else chain_tables<1>(S, len12, wbuf, A, L, i, o0, g, span, span == full_span, e);
-      uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[0]);
-      const uint32_t e1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[1]), e2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[2]), e3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[3]);
-      bool ok0 = e0 < span || (span == full_span && e0 == span);
-      if (!ok0 && span < full_span) {              // (uniform) group k alone on its whole span
-        span = full_span;
-        e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ch_ld(A, 5, chain_table_full(S, len12, wbuf, A, i, o0, g, span))) >> 1;
-        ok0 = e0 <= span;
-      }
-      if (tid == 0) gstart[k] = rel;
-      ok_groups = k + 1;
-      if (!ok0) break;                             // (uniform) a code of the group is undecodable: the symbol stage reports it -- or finds the end of the block in front of it
-      // (a later group's end is known only if those in front of it are: chain_tables)
-      uint32_t adv;
-      if (e3 < CH_WIN) {                           // four groups
-        if (tid == 0) { gstart[k + 1] = rel + e0; gstart[k + 2] = rel + L[0].start + e1; gstart[k + 3] = rel + L[1].start + e2; }
-        ok_groups = k + 4;
-        lp = L[2].start + e3 - (L[1].start + e2);
-        adv = L[2].start + e3; k += 4;
-      } else if (e2 < CH_WIN) {                    // three
-        if (tid == 0) { gstart[k + 1] = rel + e0; gstart[k + 2] = rel + L[0].start + e1; }
-        ok_groups = k + 3;
-        lp = L[1].start + e2 - (L[0].start + e1);
-        adv = L[1].start + e2; k += 3;
-      } else if (e1 < CH_WIN) {                    // two
-        if (tid == 0) gstart[k + 1] = rel + e0;
-        ok_groups = k + 2;
-        lp = L[0].start + e1 - e0;
-        adv = L[0].start + e1; k += 2;
-      } else { lp = e0; adv = e0; k += 1; }        // (the second group left its table's positions, met an undecodable position, or there was none: next step)
-      rel += adv; o0 += adv;
-    }
-  }
-  if (tid == 0 && blockIdx.x == 0) { g_dec_clk[6] = wall_clock64() - t_hdr; g_dec_clk[7] = ok_groups; }
-  if (tid == 0) {
-    T.sym_total = s_hdr[1]; T.group_count = group_count; T.n_sel = n_sel; T.err = (uint32_t)herr; T.data_bit = data_bit; T.crc = s_hdr[4]; T.orig = s_hdr[5];
-    T.ngroups_ok = ok_groups; T.pad = 0; T.eob_key = ~0ull; T.err_key = ~0ull;
-  }
-}
-
-// one lane per group of 50 symbols; the block's tables in LDS
-__global__ __launch_bounds__(256) void bz_group_syms(const uint8_t* __restrict__ in, uint64_t n, RowTab* __restrict__ tabs, const uint8_t* __restrict__ sel_all,
-                                                     const uint32_t* __restrict__ gstart_all, uint16_t* __restrict__ syms_all, uint32_t sym_stride, uint32_t sym_groups, uint32_t row0) {
-  __shared__ uint16_t fast[6][1024];
-  __shared__ uint32_t first[6][22];
-  __shared__ uint16_t cnt[6][22], start[6][22], bysym[6][260];
-  __shared__ uint8_t maxlen[8];
-  const uint32_t row = row0 + blockIdx.y;
-  RowTab& T = tabs[row];
-  const uint32_t ng = T.err ? 0u : T.ngroups_ok;
-  if (blockIdx.x * 256u >= ng) return;
-  const int tid = threadIdx.x;
-  for (uint32_t i = tid; i < 6 * 1024; i += 256) (&fast[0][0])[i] = (&T.fast[0][0])[i];
-  for (uint32_t i = tid; i < 6 * 22; i += 256) { (&first[0][0])[i] = (&T.first[0][0])[i]; (&cnt[0][0])[i] = (&T.cnt[0][0])[i]; (&start[0][0])[i] = (&T.start[0][0])[i]; }
-  for (uint32_t i = tid; i < 6 * 260; i += 256) (&bysym[0][0])[i] = (&T.bysym[0][0])[i];
-  if (tid < 8) maxlen[tid] = T.maxlen[tid];
-  __syncthreads();
-  const uint32_t k = blockIdx.x * 256u + tid;
-  if (k >= ng) return;
-  const int g = sel_all[(size_t)row * MAX_SELECTORS + k];
-  const uint32_t sym_total = T.sym_total;
-  const uint64_t data_bit = T.data_bit;
-  uint64_t pos = data_bit + gstart_all[(size_t)row * (MAX_SELECTORS + 1) + k];
-  // symbol j of group k is stored at [j][k]: the lanes of a wave (64 groups) write one line, not 64
-  uint16_t* syms = syms_all + (size_t)row * sym_groups * GROUP_SYMS + k;
-  const int mx = maxlen[g];
-  // a 64-bit window on the stream: a code is at most 20 bits, so the cursor crosses at most one word per symbol (one load every
-  // four or five symbols of text instead of two per symbol)
-  uint64_t wdw = pos >> 5;
-  uint32_t w0 = load_be32(in, n, wdw), w1 = load_be32(in, n, wdw + 1);
-  for (uint32_t j = 0; j < GROUP_SYMS; j++) {
-    const uint64_t idx = (uint64_t)k * GROUP_SYMS + j;
-    if ((pos >> 5) != wdw) { wdw++; w0 = w1; w1 = load_be32(in, n, wdw + 1); }
-    const uint32_t x20 = (uint32_t)(((((uint64_t)w0 << 32) | w1) << (pos & 31)) >> 44);
-    uint32_t e = fast[g][x20 >> 10], sym = 0, len = 0;
-    if (e) { sym = e >> 5; len = e & 31u; }
-    else {
-      for (int i = 11; i <= mx; i++) {
-        const uint32_t q = (x20 >> (20 - i)) - first[g][i];
-        if (q < cnt[g][i]) { len = (uint32_t)i; sym = bysym[g][start[g][i] + q]; break; }
-      }
-    }
-    if (!len || idx >= sym_stride) { atomicMin(&T.err_key, (unsigned long long)idx << 32); break; }      // no code starts here (or more symbols than any block has room for)
-    pos += len;
-    if (sym > sym_total) { atomicMin(&T.eob_key, ((unsigned long long)idx << 32) | (unsigned long long)(uint32_t)(pos - data_bit)); break; }      // end of block (:1640)
-    syms[(size_t)j * sym_groups] = (uint16_t)sym;
-  }
-}
-
-// One workgroup per row: the symbols in front of the end-of-block symbol, 4096 per tile, front to back.
-//   RUNA (0) / RUNB (1) are the bijective base-2 digits of a zero-rank run (:1621-1638): digit d adds (sym + 1) << d bytes.  The
-//   reference keeps the digit weight in an int32 that it shifts left: the 32nd digit of a run adds (sym + 1) * -2^31, leaves the
-//   weight 0, and with it the run is forgotten (the flush at :1643 tests the weight); a 33rd digit starts a fresh run.  So the
-//   digit of a run symbol is its position in the run mod 32, and a symbol with digit 31 takes back what the 31 in front of it added.
-//   rank symbols (>= 2) emit one byte each and leave as op (rank - 1, output offset); the bytes must fit the block (:1647, :1663).
-constexpr int SO_PT = 8;                       // symbols per thread (a tile is a dozen barriers whatever it holds: 0.58 / 0.47 / 0.87 ms per 100 MB with 4 / 8 / 16)
-constexpr uint32_t SO_TILE = 1024 * SO_PT, SO_KG = SO_TILE / GROUP_SYMS + 2;      // a tile's symbols lie in SO_KG groups at most
-__global__ __launch_bounds__(1024) void bz_sym_ops(RowTab* __restrict__ tabs, const Cand* __restrict__ cands, uint32_t ncand, const uint16_t* __restrict__ syms_all,
-                                                   uint32_t sym_groups, uint32_t dbuf_size, uint8_t* __restrict__ ops_all, uint32_t* __restrict__ opoff_all,
-                                                   uint32_t ops_stride, uint32_t* __restrict__ nops_all, BlockOut* __restrict__ outs, uint32_t row0, uint64_t nbits) {
-  __shared__ uint16_t st[SO_TILE + 32];          // the tile's symbols behind the last 32 of the tile in front
-  __shared__ unsigned long long sm64[16];
-  __shared__ uint32_t sm[16];
-  __shared__ uint32_t mx[1024];
-  const uint32_t c = blockIdx.x;
-  if (c >= ncand || cands[c].kind != 0) return;
-  const uint32_t row = cands[c].pad - row0;
-  const RowTab& T = tabs[row];
-  const int tid = threadIdx.x;
-  int err = (int)T.err;
-  const unsigned long long ek = T.eob_key, xk = T.err_key;
-  if (!err && (ek == ~0ull || xk < ek)) err = CJS_E_DATA_ERROR;      // no end of block in the selectors' reach, or an undecodable code in front of it
-  const uint32_t nsym = err ? 0u : (uint32_t)(ek >> 32);
-  const uint16_t* syms = syms_all + (size_t)row * sym_groups * GROUP_SYMS;      // [symbol of the group][group] (bz_group_syms)
-  uint8_t* ops = ops_all + (size_t)row * ops_stride;
-  uint32_t* opoff = opoff_all + (size_t)row * ops_stride;
-  unsigned long long off = 0;                    // bytes so far
-  uint32_t j0 = 0, last_nonrun = 0;              // ops so far; (index of the last rank symbol so far) + 1
-  if (tid < 32) st[tid] = 2;                     // in front of the first symbol: not a run
-  for (uint32_t base = 0; base < nsym && !err; base += SO_TILE) {
-    __syncthreads();
-    {                                             // along the groups, symbol by symbol of the group
-      const uint32_t k0 = base / GROUP_SYMS;
-      constexpr int LR = (GROUP_SYMS * SO_KG + 1023) / 1024;
-      uint32_t at[LR]; uint16_t v[LR];            // (all of a thread's loads on their way before the first is stored; fetching the tile
-                                                  // behind during this one's work as well: 0.44 -> 0.70 ms)
-#pragma unroll
-      for (int q = 0; q < LR; q++) {
-        const uint32_t u = (uint32_t)tid + 1024u * (uint32_t)q, j = u / SO_KG, k = k0 + (u - SO_KG * j), i = k * GROUP_SYMS + j;
-        const bool in = u < GROUP_SYMS * SO_KG && i >= base && i < base + SO_TILE;
-        at[q] = in ? 32u + i - base : ~0u;
-        v[q] = in && i < nsym ? syms[(size_t)j * sym_groups + k] : (uint16_t)2;
-      }
-#pragma unroll
-      for (int q = 0; q < LR; q++) if (at[q] != ~0u) st[at[q]] = v[q];
-    }
-    __syncthreads();
-    // position in the run: i - (index of the last rank symbol in front of i) - 1, by a max scan of (index + 1) of the rank symbols
-    uint32_t lastb = 0;
-#pragma unroll
-    for (int q = 0; q < SO_PT; q++) { const uint32_t i = base + (uint32_t)tid * (uint32_t)SO_PT + q; if (i < nsym && st[32 + tid * SO_PT + q] >= 2) lastb = i + 1; }
-    const uint32_t incl = block_incl_max<1024>(lastb, sm);
-    mx[tid] = incl;
-    __syncthreads();
-    uint32_t prevnr = tid ? mx[tid - 1] : 0u;
-    const uint32_t tile_last = mx[1023];
-    __syncthreads();
-    if (prevnr < last_nonrun) prevnr = last_nonrun;
-    long long cb[SO_PT]; unsigned long long mine = 0; uint32_t nops = 0;
-#pragma unroll
-    for (int q = 0; q < SO_PT; q++) {
-      const uint32_t i = base + (uint32_t)tid * (uint32_t)SO_PT + q, sy = st[32 + tid * SO_PT + q];
-      cb[q] = 0;
-      if (i < nsym) {
-        if (sy >= 2) { cb[q] = 1; nops++; prevnr = i + 1; }
-        else {
-          const uint32_t d = (i - prevnr) & 31u;
-          if (d < 31) cb[q] = (long long)(sy + 1u) << d;
-          else { long long t = 0; for (uint32_t b = 1; b <= 31; b++) t += (long long)((uint32_t)st[32 + tid * SO_PT + q - b] + 1u) << (31u - b); cb[q] = -t; }
-        }
-      }
-      mine += (unsigned long long)cb[q];
-    }
-    unsigned long long tot;
-    unsigned long long ex = off + block_excl_sum<1024>(mine, sm64, tot);
-    uint32_t ntot;
-    uint32_t jx = j0 + block_excl_sum<1024>(nops, sm, ntot);
-#pragma unroll
-    for (int q = 0; q < SO_PT; q++) {
-      const uint32_t i = base + (uint32_t)tid * (uint32_t)SO_PT + q, sy = st[32 + tid * SO_PT + q];
-      if (i < nsym && sy >= 2) {
-        if (jx < ops_stride - 1u && ex < 0xFFFFFFFFull) { ops[jx] = (uint8_t)(sy - 1u); opoff[jx] = (uint32_t)ex; }      // rank symbol s reads list slot s - 1 (:1664)
-        jx++;
-      }
-      ex += (unsigned long long)cb[q];
-    }
-    off += tot; j0 += ntot;                       // (off may hold digits of a run that is still open: the byte limit is tested at the end)
-    if (tile_last > last_nonrun) last_nonrun = tile_last;
-    if (j0 >= ops_stride - 1u) err = CJS_E_DATA_ERROR;                           // (uniform) more rank symbols than the block has bytes
-    __syncthreads();
-    if (tid < 32) st[tid] = st[SO_TILE + tid];   // the last 32 symbols stay in front of the next tile
-  }
-  // Offsets at rank symbols never decrease, so every "fits the block" test of the reference (:1647 before a flush, :1663 before
-  // a literal) passes iff the final byte count does
-  if (!err && off > dbuf_size) err = CJS_E_DATA_ERROR;
-  if (!err && T.orig >= off) err = CJS_E_DATA_ERROR;                            // :1677
-  if (tid == 0) {
-    if (err) { j0 = 0; off = 0; }
-    opoff[j0] = (uint32_t)off;                   // the end-of-block pseudo op: where the output ends
-    nops_all[row] = j0;
-    BlockOut bo;
-    const uint64_t endb = T.data_bit + (uint32_t)ek;
-    bo.end_bit = err ? 0 : (endb > nbits ? nbits : endb);
-    bo.count = err ? 0u : (uint32_t)off; bo.orig = T.orig; bo.crc = T.crc; bo.err = err;
-    outs[c] = bo;
-  }
-}
 
 constexpr uint32_t MT_TILE = 256;
 // grid = (tile groups, rows of a slab): rows come in slabs of <= 65535 (grid.y), and a grid may not exceed 2^32 threads in all
@@ -1631,6 +875,9 @@ struct DecShare {
   std::vector<uint64_t> ebase;        // element offset of block c0+i inside d_w (size c1-c0+1)
   double ms_a = 0, ms_b = 0, ms_c = 0;
   char detail[96] = {0};            // error detail found by this share's worker thread (the detail text is per calling thread)
+  // batch (cjs_bzip2_decompress_batch): input k is bytes [bst[k], ben[k]) of the upload, its blocks at most bdsz[k] bytes
+  std::vector<uint32_t> bst, ben, bdsz;
+  uint32_t a_batches = 0, b_batches = 0;      // row batches of phase A, inverse-BWT batches of phase B
   int take(void** p, size_t bytes) { DevBuf b(bytes); if (!(*p = b.p)) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(std::move(b)); return 0; }
   void drop(void* p) { for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; } DevPool::give(p); }
   void release() {                    // on the share's device, once its stream has drained; again: nothing
@@ -1651,6 +898,8 @@ struct DecJob {
   std::vector<uint64_t> out_off;      // size chain.size()+1
   uint8_t* host = nullptr;            // final output (mode 0 / 2)
   bool timing = false;
+  bool batch = false;                 // phase C: a CRC verdict for every block (crc_got) instead of stopping at the first bad one
+  std::vector<uint32_t> crc_got;
 };
 
 double ms_since(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); }
@@ -1671,7 +920,15 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   uint8_t* d_al = d_raw + (S->up_lo & 3u);
   S->d_in = d_al - S->up_lo;
   if (hipMemcpyAsync(d_al, J->in + S->up_lo, up_n, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(d_count, 0, 64, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  uint32_t *d_bst = nullptr, *d_ben = nullptr;
+  const uint32_t nin = (uint32_t)S->bst.size();
+  if (nin) {
+    if ((rc = S->take((void**)&d_bst, 4 * (size_t)nin)) != 0 || (rc = S->take((void**)&d_ben, 4 * (size_t)nin)) != 0) { S->rc = rc; return; }
+    if (hipMemcpyAsync(d_bst, S->bst.data(), 4 * (size_t)nin, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_ben, S->ben.data(), 4 * (size_t)nin, hipMemcpyHostToDevice, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  }
   auto launch_scan = [&]() {                                            // (slabs: a grid may not exceed 2^32 threads)
+    if (nin) { launch_magic_scan_batch(s, S->d_in, d_bst, d_ben, nin, S->hi, d_cand, cand_cap, d_count); return; }
     for (uint64_t b0 = S->lo; b0 < S->hi; b0 += 1ull << 31) {
       const uint64_t b1 = std::min<uint64_t>(S->hi, b0 + (1ull << 31));
       hipLaunchKernelGGL(bz_magic_scan, dim3((unsigned)((b1 - b0 + 255) / 256)), dim3(256), 0, s, S->d_in, b0, b1, S->up_hi, d_cand, cand_cap, d_count);
@@ -1692,6 +949,13 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   S->cands.resize(ncand);
   if (ncand && hipMemcpy(S->cands.data(), d_cand, sizeof(Cand) * ncand, hipMemcpyDeviceToHost) != hipSuccess) { S->rc = CJS_E_HIP; return; }
   std::sort(S->cands.begin(), S->cands.end(), [](const Cand& a, const Cand& b) { return a.bit < b.bit; });
+  uint32_t* d_cend = nullptr;                                      // batch: per candidate, its input's end and block size (cend, then cdsz)
+  if (nin && ncand) {                                              // the batch scan left each candidate's input in pad
+    std::vector<uint32_t> cend(2 * (size_t)ncand);
+    for (uint32_t c = 0; c < ncand; c++) { cend[c] = S->ben[S->cands[c].pad]; cend[ncand + c] = S->bdsz[S->cands[c].pad]; }
+    if ((rc = S->take((void**)&d_cend, 8 * (size_t)ncand)) != 0) { S->rc = rc; return; }
+    if (hipMemcpy(d_cend, cend.data(), 8 * (size_t)ncand, hipMemcpyHostToDevice) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  }
   uint32_t nrows = 0;                                              // only block candidates get a row of the decode buffer
   for (auto& c : S->cands) c.pad = c.kind == 0 ? nrows++ : 0u;
   if (ncand && hipMemcpy(d_cand, S->cands.data(), sizeof(Cand) * ncand, hipMemcpyHostToDevice) != hipSuccess) { S->rc = CJS_E_HIP; return; }
@@ -1728,6 +992,8 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   if (!rc) rc = S->take((void**)&d_gstart, 4 * (size_t)(MAX_SELECTORS + 1) * nr);
   if (!rc) rc = S->take((void**)&d_syms, 2 * (size_t)sym_groups * GROUP_SYMS * nr);
   if (!rc && !single) rc = S->take((void**)&d_gdst, sizeof(RowDst) * (size_t)nr);
+  uint32_t* d_rlim = nullptr;
+  if (!rc && nin) rc = S->take((void**)&d_rlim, 4 * (size_t)nr);
   if (rc) { S->rc = rc; return; }
   if (single) S->d_tt = d_ttb;
   std::vector<RowDst> gdst(single ? 0 : nr);
@@ -1736,9 +1002,14 @@ void dec_phase_a(DecJob* J, DecShare* S) {
     uint32_t c1 = c0, rows = 0, r0 = 0;
     while (c1 < ncand && (S->cands[c1].kind != 0 || rows < nr)) { if (S->cands[c1].kind == 0) { if (!rows) r0 = S->cands[c1].pad; rows++; } c1++; }
     const uint32_t nc = c1 - c0;
-    hipLaunchKernelGGL(bz_chain, dim3(nc), dim3(CH_T), 0, s, S->d_in, S->up_hi, d_cand + c0, nc, dsz, d_tabs, d_sel, d_gstart, d_l0, d_bo + c0, r0);
-    if (rows) hipLaunchKernelGGL(bz_group_syms, dim3(group_tiles, rows), dim3(256), 0, s, S->d_in, S->up_hi, d_tabs, d_sel, d_gstart, d_syms, sym_stride, sym_groups, 0u);
-    hipLaunchKernelGGL(bz_sym_ops, dim3(nc), dim3(1024), 0, s, d_tabs, d_cand + c0, nc, d_syms, sym_groups, dsz, d_ops, d_opoff, ops_stride, d_nops, d_bo + c0, r0, S->up_hi * 8);
+    S->a_batches++;
+    if (nin) launch_block_decode_batch(s, S->d_in, d_cend + c0, d_cend + ncand + c0, d_rlim, d_cand + c0, nc, rows, dsz, d_tabs, d_sel, d_gstart, d_l0, d_bo + c0, r0, group_tiles, d_syms, sym_stride,
+                                       sym_groups, d_ops, d_opoff, ops_stride, d_nops);
+    else {
+      hipLaunchKernelGGL(bz_chain, dim3(nc), dim3(CH_T), 0, s, S->d_in, S->up_hi, d_cand + c0, nc, dsz, d_tabs, d_sel, d_gstart, d_l0, d_bo + c0, r0);
+      if (rows) hipLaunchKernelGGL(bz_group_syms, dim3(group_tiles, rows), dim3(256), 0, s, S->d_in, S->up_hi, d_tabs, d_sel, d_gstart, d_syms, sym_stride, sym_groups, 0u);
+      hipLaunchKernelGGL(bz_sym_ops, dim3(nc), dim3(1024), 0, s, d_tabs, d_cand + c0, nc, d_syms, sym_groups, dsz, d_ops, d_opoff, ops_stride, d_nops, d_bo + c0, r0, S->up_hi * 8);
+    }
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(S->bos.data() + c0, d_bo + c0, sizeof(BlockOut) * nc, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
     uint32_t maxc = 0; uint64_t packed = 0;
@@ -1780,15 +1051,17 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   }
   S->drop(d_ops); S->drop(d_opoff); S->drop(d_l0); S->drop(d_pl); S->drop(d_nops); S->drop(d_tabs); S->drop(d_sel); S->drop(d_gstart); S->drop(d_syms);
   if (!single) { S->drop(d_ttb); S->drop(d_gdst); }
+  if (nin) S->drop(d_rlim);
   if (env_debug()) {
     uint64_t clk[8];
-    if (hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_dec_clk), sizeof clk) == hipSuccess) {
+    if (!nin && hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_dec_clk), sizeof clk) == hipSuccess) {
       fprintf(stderr, "[cjs dec] candidate 0: header + tables %.1f us, group chain %.1f us for %llu groups\n", clk[5] / 100.0, clk[6] / 100.0, (unsigned long long)clk[7]);
     }
     fprintf(stderr, "[cjs dec] share on device %d: bytes [%llu, %llu) uploaded [%llu, %llu) = %zu B, %u candidates\n", S->device, (unsigned long long)S->lo,
             (unsigned long long)S->hi, (unsigned long long)S->up_lo, (unsigned long long)S->up_hi, up_n, ncand);
   }
   S->drop(d_cand); S->drop(d_count); S->drop(d_bo);
+  if (nin) { S->drop(d_bst); S->drop(d_ben); if (d_cend) S->drop(d_cend); }      // (batch: the phase clock of candidate 0 is not kept)
   S->ms_a = ms_since(T0);
 }
 
@@ -1824,6 +1097,7 @@ void dec_phase_b(DecJob* J, DecShare* S) {
   for (size_t b0 = S->c0; b0 < S->c1 && !rc;) {
     const size_t b1 = dec_next_batch(J, b0, S->c1);
     const uint32_t nb = (uint32_t)(b1 - b0);
+    S->b_batches++;
     const uint64_t e0 = S->ebase[b0 - S->c0], M64 = S->ebase[b1 - S->c0] - e0;
     if (M64 >= 0xFFFFF000ull) { rc = CJS_E_UNSUPPORTED; break; }     // a single block list beyond the batch limit cannot happen (count <= 900000)
     // Blocks of (nearly) one size -- a stream's are, but for its last -- get a slot range of that size each and ONE pass of the sort,
@@ -1930,7 +1204,8 @@ void dec_phase_c(DecJob* J, DecShare* S) {
     if (!rc && hipMemcpyAsync(crcs.data(), d_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc && J->host && obytes && hipMemcpyAsync(J->host + o0, d_out, (size_t)obytes, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
-    if (!rc) for (uint32_t k = 0; k < nb; k++) if (crcs[k] != blk[k].crc) {                    // Bad block CRC (:1756-1761)
+    if (!rc && J->batch) for (uint32_t k = 0; k < nb; k++) J->crc_got[b0 + k] = crcs[k];      // (each input's verdict: the batch's host side)
+    else if (!rc) for (uint32_t k = 0; k < nb; k++) if (crcs[k] != blk[k].crc) {                    // Bad block CRC (:1756-1761)
       snprintf(S->detail, sizeof S->detail, "Bad block CRC (got %x expected %x)", crcs[k], blk[k].crc);
       if (env_debug()) fprintf(stderr, "[cjs dec] block %zu: Bad block CRC (got %08x expected %08x) out_len %u\n", b0 + k, crcs[k], blk[k].crc, blk[k].out_len);
       rc = CJS_E_DATA_ERROR; break;
@@ -1951,6 +1226,71 @@ int for_each_share(std::vector<DecShare>& sh, DecJob* J, F fn) {
   return 0;
 }
 
+// The scratch rows are sized for the largest level any member stream can have: a multistream file may change level
+// between members (:1787-1792), so every byte-aligned "BZh<d>" followed by a block or end-of-stream magic counts.
+int bz_max_level(const uint8_t* in, size_t n, int level, bool multistream) {
+  int max_level = level;
+  if (multistream) {
+    for (const uint8_t* p = in + 4; p + 10 <= in + n && (p = (const uint8_t*)memchr(p, 'B', (size_t)(in + n - 9 - p))) != nullptr; p++) {
+      if (p[1] != 'Z' || p[2] != 'h' || p[3] < '1' || p[3] > '9') continue;
+      uint64_t m = 0; for (int i = 0; i < 6; i++) m = (m << 8) | p[4 + i];
+      if ((m == MAGIC_BLOCK || m == MAGIC_END) && p[3] - '0' > max_level) max_level = p[3] - '0';
+    }
+  }
+  return max_level;
+}
+
+// A decoded block candidate as the walk meets it (:1440-1450, 1647, 1663): 0 if it joins the chain, else the error.
+int bz_block_verdict(const BlockOut& bo, uint32_t dbuf_size, uint64_t bitpos, bool timing) {
+  if (timing) fprintf(stderr, "[cjs dec] block at bit %llu: err %d count %u orig %u crc %08x end %llu\n", (unsigned long long)bitpos, bo.err, bo.count, bo.orig, bo.crc, (unsigned long long)bo.end_bit);
+  if (bo.err != CJS_E_OBSOLETE_INPUT && bo.orig > dbuf_size) { set_detail("initial position out of bounds"); return CJS_E_DATA_ERROR; }   // :1449-1450
+  if (bo.err) return bo.err;
+  if (bo.count > dbuf_size) return CJS_E_DATA_ERROR;             // decoded with the largest level's limit: this stream's is lower (:1647,1663)
+  return 0;
+}
+
+// The chain walk of one input (Bunzip.decode :1776-1794): 32 -> end(block 0) -> end(block 1) ... over the candidates, stream CRC
+// fold, multistream restarts (each member keeps its own level, :1787-1792).  in / n: the input's own bytes, whose header
+// _start_bunzip has passed; positions are bits of the input.  at(pos, &kind, &bo) finds the candidate whose magic starts at bit
+// pos (false: none) with its decode result, end_bit in bits of the input; take(bo, pos) appends a good block to the chain.
+// Returns 0 or the first error the walk meets, its detail set.  mode 1 (Bunzip.table) does not test the stream CRC.
+template <typename At, typename Take>
+int bz_walk(const uint8_t* in, size_t n, int multistream, int mode, uint32_t tt_stride, bool timing, At at, Take take) {
+  auto read_bits = [&](uint64_t bit, int k) -> uint64_t { uint64_t v = 0; for (int i = 0; i < k; i++) { const uint64_t b = bit + i; v = (v << 1) | ((b >> 3) < n ? (in[b >> 3] >> (7 - (b & 7))) & 1u : 0u); } return v; };
+  uint32_t dbuf_size = 100000u * (uint32_t)(in[3] - '0');         // of the member stream being walked
+  uint64_t pos = 32; uint32_t stream_crc = 0;
+  for (;;) {
+    if ((pos + 7) / 8 >= n) return 0;                            // inputStream.eof() (:1777)
+    uint32_t kind = 0; BlockOut bo;
+    if (!at(pos, &kind, &bo)) return CJS_E_NOT_BZIP_DATA;        // h !== WHOLEPI (:1438)
+    if (kind == 0) {
+      const int rc = bz_block_verdict(bo, dbuf_size, pos, timing);
+      if (rc) return rc;
+      take(bo, pos);
+      stream_crc = bo.crc ^ ((stream_crc << 1) | (stream_crc >> 31));
+      pos = bo.end_bit;
+    } else {
+      const uint32_t target = (uint32_t)read_bits(pos + 48, 32);
+      pos += 80;
+      if ((pos + 7) / 8 > n) pos = (uint64_t)n * 8;
+      if (timing) fprintf(stderr, "[cjs dec] end of stream at bit %llu: stream crc %08x stored %08x\n", (unsigned long long)pos - 80, stream_crc, target);
+      if (mode == 0 && target != stream_crc) {                   // Bunzip.table ignores the stream crc (:1852)
+        set_detail("Bad stream CRC (got %x expected %x)", stream_crc, target);
+        return CJS_E_DATA_ERROR;
+      }
+      const uint64_t byte = (pos + 7) / 8;
+      if (!multistream || byte >= n) return 0;
+      // _start_bunzip again, byte aligned (:1787-1792)
+      if (byte + 4 > n || in[byte] != 'B' || in[byte + 1] != 'Z' || in[byte + 2] != 'h') { set_detail("bad magic"); return CJS_E_NOT_BZIP_DATA; }
+      const int lv = in[byte + 3] - '0';
+      if (lv < 1 || lv > 9) { set_detail("level out of range"); return CJS_E_NOT_BZIP_DATA; }
+      dbuf_size = 100000u * (uint32_t)lv;
+      if (dbuf_size > tt_stride) return CJS_E_UNSUPPORTED;      // cannot happen: the pre-scan saw this header
+      pos = (byte + 4) * 8; stream_crc = 0;
+    }
+  }
+}
+
 }  // namespace
 
 static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, uint64_t at_bit, uint8_t** out, size_t* out_n,
@@ -1969,17 +1309,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
 
   DecJob J; J.in = in; J.n = n; J.mode = mode;
   J.timing = env_debug();
-  // The scratch rows are sized for the largest level any member stream can have: a multistream file may change level
-  // between members (:1787-1792), so every byte-aligned "BZh<d>" followed by a block or end-of-stream magic counts.
-  int max_level = level;
-  if (multistream && mode != 2) {
-    for (const uint8_t* p = in + 4; p + 10 <= in + n && (p = (const uint8_t*)memchr(p, 'B', (size_t)(in + n - 9 - p))) != nullptr; p++) {
-      if (p[1] != 'Z' || p[2] != 'h' || p[3] < '1' || p[3] > '9') continue;
-      uint64_t m = 0; for (int i = 0; i < 6; i++) m = (m << 8) | p[4 + i];
-      if ((m == MAGIC_BLOCK || m == MAGIC_END) && p[3] - '0' > max_level) max_level = p[3] - '0';
-    }
-  }
-  J.tt_stride = 100000u * (uint32_t)max_level;
+  J.tt_stride = 100000u * (uint32_t)bz_max_level(in, n, level, multistream && mode != 2);
 
   // shares: contiguous byte ranges, one per requested device slot
   uint32_t nsh = Opts(opts).n_devices;
@@ -2015,55 +1345,30 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
     const auto it = std::lower_bound(cbit.begin(), cbit.end(), bit);
     return (it != cbit.end() && *it == bit) ? (long)(it - cbit.begin()) : -1;
   };
-  auto read_bits = [&](uint64_t bit, int k) -> uint64_t { uint64_t v = 0; for (int i = 0; i < k; i++) { const uint64_t b = bit + i; v = (v << 1) | ((b >> 3) < n ? (in[b >> 3] >> (7 - (b & 7))) & 1u : 0u); } return v; };
   std::vector<uint32_t> chain_share;
-  uint32_t dbuf_size = 100000u * (uint32_t)level;                  // of the member stream being walked
-  auto take_block = [&](long ci, uint64_t bitpos) -> int {
+  auto take_block = [&](long ci, uint64_t bitpos) {
     const DecShare& S = sh[cshare[(size_t)ci]];
     const BlockOut& bo = S.bos[clocal[(size_t)ci]];
-    if (J.timing) fprintf(stderr, "[cjs dec] block at bit %llu: err %d count %u orig %u crc %08x end %llu\n", (unsigned long long)bitpos, bo.err, bo.count, bo.orig, bo.crc, (unsigned long long)bo.end_bit);
-    if (bo.err != CJS_E_OBSOLETE_INPUT && bo.orig > dbuf_size) { set_detail("initial position out of bounds"); return CJS_E_DATA_ERROR; }   // :1449-1450
-    if (bo.err) return bo.err;
-    if (bo.count > dbuf_size) return CJS_E_DATA_ERROR;             // decoded with the largest level's limit: this stream's is lower (:1647,1663)
     IbBlock ib; ib.tt = S.tt_ptr[clocal[(size_t)ci]]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
     J.chain.push_back(ib); J.chain_bits.push_back(bitpos); chain_share.push_back(cshare[(size_t)ci]);
-    return 0;
   };
-  uint64_t pos = 32; uint32_t stream_crc = 0;
   if (mode == 2) {                                               // reader.seekBit(pos); _get_next_block() (:1803-1805)
     const long ci = find(at_bit);
     if (ci < 0) rc = CJS_E_NOT_BZIP_DATA;
-    else if (sh[cshare[(size_t)ci]].cands[clocal[(size_t)ci]].kind == 0) rc = take_block(ci, at_bit);
-  } else for (;;) {
-    if ((pos + 7) / 8 >= n) break;                               // inputStream.eof() (:1777)
-    const long ci = find(pos);
-    if (ci < 0) { rc = CJS_E_NOT_BZIP_DATA; break; }             // h !== WHOLEPI (:1438)
-    const DecShare& S = sh[cshare[(size_t)ci]];
-    if (S.cands[clocal[(size_t)ci]].kind == 0) {
-      rc = take_block(ci, pos);
-      if (rc) break;
-      const BlockOut& bo = S.bos[clocal[(size_t)ci]];
-      stream_crc = bo.crc ^ ((stream_crc << 1) | (stream_crc >> 31));
-      pos = bo.end_bit;
-    } else {
-      const uint32_t target = (uint32_t)read_bits(pos + 48, 32);
-      pos += 80;
-      if ((pos + 7) / 8 > n) pos = (uint64_t)n * 8;
-      if (J.timing) fprintf(stderr, "[cjs dec] end of stream at bit %llu: stream crc %08x stored %08x\n", (unsigned long long)pos - 80, stream_crc, target);
-      if (mode == 0 && target != stream_crc) {                   // Bunzip.table ignores the stream crc (:1852)
-        set_detail("Bad stream CRC (got %x expected %x)", stream_crc, target);
-        rc = CJS_E_DATA_ERROR; break;
-      }
-      const uint64_t byte = (pos + 7) / 8;
-      if (multistream && byte < n) {                            // _start_bunzip again, byte aligned (:1787-1792)
-        if (byte + 4 > n || in[byte] != 'B' || in[byte + 1] != 'Z' || in[byte + 2] != 'h') { set_detail("bad magic"); rc = CJS_E_NOT_BZIP_DATA; break; }
-        const int lv = in[byte + 3] - '0';
-        if (lv < 1 || lv > 9) { set_detail("level out of range"); rc = CJS_E_NOT_BZIP_DATA; break; }
-        dbuf_size = 100000u * (uint32_t)lv;
-        if (dbuf_size > J.tt_stride) { rc = CJS_E_UNSUPPORTED; break; }        // cannot happen: the pre-scan saw this header
-        pos = (byte + 4) * 8; stream_crc = 0;
-      } else break;
+    else if (sh[cshare[(size_t)ci]].cands[clocal[(size_t)ci]].kind == 0) {
+      rc = bz_block_verdict(sh[cshare[(size_t)ci]].bos[clocal[(size_t)ci]], 100000u * (uint32_t)level, at_bit, J.timing);
+      if (!rc) take_block(ci, at_bit);
     }
+  } else {
+    long last = -1;
+    rc = bz_walk(in, n, multistream, mode, J.tt_stride, J.timing,
+                 [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
+                   if ((last = find(pos)) < 0) return false;
+                   const DecShare& S = sh[cshare[(size_t)last]];
+                   *kind = S.cands[clocal[(size_t)last]].kind; *bo = S.bos[clocal[(size_t)last]];
+                   return true;
+                 },
+                 [&](const BlockOut&, uint64_t pos) { take_block(last, pos); });
   }
   // The reference decodes block after block and checks every block's CRC before it reads on (:1756-1761), so an error met
   // by the walk (bad stream CRC, damaged later block, broken chain) is reported only if every block in front of it
@@ -2129,4 +1434,179 @@ extern "C" long cjs_bzip2_table(const uint8_t* in, size_t n, int multistream, ui
   const int rc = bunzip_core(in, n, multistream, 1, 0, nullptr, nullptr, bitpos, size, cap, &nbk, opts);
   return rc ? (long)rc : nbk;
   CJS_GUARD_END((long)CJS_E_OUT_OF_MEMORY, (long)CJS_E_HIP)
+}
+
+// ---------------------------------------------------------------- batch (Bzip2.decompressFiles)
+// Inputs go in groups of up to BATCH_DEC_GROUP_BYTES, each group one upload with every input at a 4-byte-aligned offset and one
+// share of phases A-C: one magic scan over the group (a candidate never straddles two inputs), block decode of all candidates
+// with every read bounded by the candidate's own input, then the walk of each input over the candidates of its bytes, phase B
+// over all chain blocks, phase C with a CRC verdict per block.  Input k's verdict is the single call's: the first block of its
+// chain, in stream order, whose CRC fails; else the walk's error; else success.  An input larger than a group goes through
+// cjs_bzip2_decompress.  See DESIGN.md §6c.
+namespace {
+
+constexpr size_t BATCH_DEC_GROUP_BYTES = (size_t)256 << 20;
+
+size_t dec_group_bytes() {
+  static const size_t g = getenv("CJS_DEC_GROUP_BYTES") ? (size_t)strtoull(getenv("CJS_DEC_GROUP_BYTES"), nullptr, 10) : BATCH_DEC_GROUP_BYTES;   // (tests shrink it)
+  return g && g <= ((size_t)1 << 30) ? g : BATCH_DEC_GROUP_BYTES;      // (group offsets are 32-bit)
+}
+
+struct BatchPiece { uint8_t* buf; size_t size; };       // a HostPool result buffer and the bytes used in it
+
+// one group: inputs [k0, k1); every status / off (inside the group's piece) / len and detail is set
+int dec_batch_group(const uint8_t* const* in, const size_t* n, size_t k0, size_t k1, int multistream, int dev, size_t* off, size_t* len,
+                    int32_t* status, std::vector<std::string>& detail, BatchPiece* piece) {
+  piece->buf = nullptr; piece->size = 0;
+  const size_t items = k1 - k0;
+  DecJob J; J.mode = 0; J.batch = true; J.timing = env_debug();
+  DecShare S; S.device = dev;
+  S.bst.resize(items); S.ben.resize(items); S.bdsz.assign(items, 100000u);
+  int max_level = 1;
+  std::vector<uint8_t> ok(items, 0);
+  size_t bytes = 0;
+  for (size_t i = 0; i < items; i++) {                         // _start_bunzip (:1408-1427) of every input
+    const uint8_t* p = in[k0 + i]; const size_t m = n[k0 + i];
+    status[k0 + i] = 0; off[k0 + i] = 0; len[k0 + i] = 0;
+    S.bst[i] = S.ben[i] = (uint32_t)bytes;
+    if (m < 4 || p[0] != 'B' || p[1] != 'Z' || p[2] != 'h') { status[k0 + i] = CJS_E_NOT_BZIP_DATA; detail[k0 + i] = "bad magic"; continue; }
+    const int level = p[3] - '0';
+    if (level < 1 || level > 9) { status[k0 + i] = CJS_E_NOT_BZIP_DATA; detail[k0 + i] = "level out of range"; continue; }
+    const int own = bz_max_level(p, m, level, multistream != 0);      // the scratch of its single call: the kernels' limits for its blocks
+    S.bdsz[i] = 100000u * (uint32_t)own;
+    max_level = std::max(max_level, own);
+    ok[i] = 1;
+    S.ben[i] = (uint32_t)(bytes + m);
+    bytes = (bytes + m + 3) & ~(size_t)3;
+  }
+  J.tt_stride = 100000u * (uint32_t)max_level;
+  uint8_t* host_in = (uint8_t*)HostPool::take(bytes ? bytes : 1);
+  if (!host_in) return CJS_E_OUT_OF_MEMORY;
+  struct GiveBack { uint8_t* p; ~GiveBack() { HostPool::give(p); } } give_in{host_in};
+  for (size_t i = 0; i < items; i++) if (ok[i]) memcpy(host_in + S.bst[i], in[k0 + i], S.ben[i] - S.bst[i]);
+  J.in = host_in; J.n = bytes;
+  S.lo = 0; S.hi = bytes; S.up_lo = 0; S.up_hi = bytes;
+  if (bytes) {
+    guarded(S.rc, [&] { dec_phase_a(&J, &S); });
+    if (S.rc) return S.rc;
+  }
+  // the walk of every input over the candidates of its bytes (bits of the group: 8 x bst[i] + bits of the input)
+  std::vector<uint64_t> cbit(S.cands.size());
+  for (size_t c = 0; c < S.cands.size(); c++) cbit[c] = S.cands[c].bit;
+  std::vector<size_t> ch0(items, 0), ch1(items, 0);
+  for (size_t i = 0; i < items; i++) {
+    ch0[i] = ch1[i] = J.chain.size();
+    if (!ok[i]) continue;
+    const uint64_t base = 8ull * S.bst[i];
+    long last = -1;
+    clear_detail();
+    const int rc = bz_walk(in[k0 + i], n[k0 + i], multistream, 0, J.tt_stride, J.timing,
+                           [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
+                             const auto it = std::lower_bound(cbit.begin(), cbit.end(), base + pos);
+                             if (it == cbit.end() || *it != base + pos) return false;
+                             last = (long)(it - cbit.begin());
+                             *kind = S.cands[(size_t)last].kind; *bo = S.bos[(size_t)last]; bo->end_bit -= base;
+                             return true;
+                           },
+                           [&](const BlockOut& bo, uint64_t) {
+                             IbBlock ib; ib.tt = S.tt_ptr[(size_t)last]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
+                             J.chain.push_back(ib);
+                           });
+    ch1[i] = J.chain.size();
+    if (rc) { status[k0 + i] = rc; detail[k0 + i] = cjs_last_error_detail(); }     // pending: a bad block CRC in front of it wins
+  }
+  clear_detail();
+  const size_t nb = J.chain.size();
+  S.c0 = 0; S.c1 = nb;
+  if (nb) {
+    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
+    // (phase B's own CJS_E_UNSUPPORTED / CJS_E_DATA_ERROR exits cannot happen -- a block holds <= 900000 bytes, a walk makes a step;
+    // should one, it is a failure of the call, reported as one of the call's codes)
+    if (S.rc == CJS_E_OUT_OF_MEMORY || S.rc == CJS_E_NO_DEVICE) return S.rc;
+    if (S.rc) return CJS_E_HIP;
+  }
+  J.out_off.assign(nb + 1, 0);
+  for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
+  const uint64_t total = J.out_off[nb];
+  J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1);
+  if (!J.host) return CJS_E_OUT_OF_MEMORY;
+  J.crc_got.assign(nb, 0);
+  if (nb) guarded(S.rc, [&] { dec_phase_c(&J, &S); });
+  S.release();                                                 // (the stream has drained before J.host is read or given back)
+  if (S.rc) { HostPool::give(J.host); return S.rc; }
+  for (size_t i = 0; i < items; i++) {
+    for (size_t b = ch0[i]; b < ch1[i]; b++) if (J.crc_got[b] != J.chain[b].crc) {      // Bad block CRC (:1756-1761)
+      char d[96];
+      snprintf(d, sizeof d, "Bad block CRC (got %x expected %x)", J.crc_got[b], J.chain[b].crc);
+      status[k0 + i] = CJS_E_DATA_ERROR; detail[k0 + i] = d;
+      break;
+    }
+    off[k0 + i] = (size_t)J.out_off[ch0[i]];
+    len[k0 + i] = status[k0 + i] ? 0 : (size_t)(J.out_off[ch1[i]] - J.out_off[ch0[i]]);
+  }
+  if (J.timing)
+    fprintf(stderr, "[cjs dec batch] group: %zu inputs, %zu candidates, %u row batches (phase A), %u inverse-BWT batches (phase B), %zu chain blocks, %llu bytes out\n",
+            items, S.cands.size(), S.a_batches, S.b_batches, nb, (unsigned long long)total);
+  piece->buf = J.host; piece->size = (size_t)total;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cjs_bzip2_decompress_batch(const uint8_t* const* in, const size_t* n, size_t count, int multistream, uint8_t** out, size_t* off,
+                                          size_t* len, int32_t* status, const cjs_opts* opts) {
+  if (!out) return CJS_E_INVALID_ARG;
+  *out = nullptr;
+  clear_detail();
+  if (count == 0) return 0;
+  if (!in || !n || !off || !len || !status) return CJS_E_INVALID_ARG;
+  for (size_t k = 0; k < count; k++) if (n[k] && !in[k]) return CJS_E_INVALID_ARG;
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  int dev = 0, ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  RestoreDevice restore{dev};
+  cjs_opts one; memset(&one, 0, sizeof one);                   // (the large inputs: this device, n_devices and stats ignored)
+  one.struct_size = sizeof one; one.device = dev;
+  const size_t G = dec_group_bytes();
+  std::vector<std::string> detail(count);
+  std::vector<BatchPiece> pieces;
+  std::vector<size_t> piece_of(count);
+  struct Pieces { std::vector<BatchPiece>& v; ~Pieces() { for (auto& p : v) HostPool::give(p.buf); } } keep{pieces};
+  int rc = 0;
+  for (size_t k0 = 0; k0 < count && !rc;) {
+    if (n[k0] > G) {                                           // an input of its own: the single-stream path
+      uint8_t* o = nullptr; size_t on = 0;
+      const int r = cjs_bzip2_decompress(in[k0], n[k0], multistream, &o, &on, &one);
+      if (r == CJS_E_OUT_OF_MEMORY || r == CJS_E_NO_DEVICE || r == CJS_E_HIP || r == CJS_E_INVALID_ARG) { rc = r; break; }
+      status[k0] = r; off[k0] = 0; len[k0] = r ? 0 : on;
+      if (r) detail[k0] = cjs_last_error_detail();
+      else { pieces.push_back(BatchPiece{o, on}); piece_of[k0] = pieces.size() - 1; }
+      if (r) { piece_of[k0] = pieces.size(); pieces.push_back(BatchPiece{nullptr, 0}); }
+      k0++;
+      continue;
+    }
+    size_t k1 = k0, bytes = 0;
+    while (k1 < count && n[k1] <= G && (k1 == k0 || bytes + n[k1] <= G)) bytes += (n[k1++] + 3) & ~(size_t)3;
+    BatchPiece p{nullptr, 0};
+    if ((rc = dec_batch_group(in, n, k0, k1, multistream, dev, off, len, status, detail, &p)) != 0) break;
+    pieces.push_back(p);
+    for (size_t k = k0; k < k1; k++) piece_of[k] = pieces.size() - 1;
+    k0 = k1;
+  }
+  clear_detail();
+  if (rc) return rc;
+  uint8_t* res = nullptr;
+  if (pieces.size() == 1 && pieces[0].buf) { res = pieces[0].buf; pieces[0].buf = nullptr; }      // (one group: its buffer is the result)
+  else {
+    std::vector<size_t> base(pieces.size() + 1, 0);
+    for (size_t i = 0; i < pieces.size(); i++) base[i + 1] = base[i] + pieces[i].size;
+    if (!(res = (uint8_t*)HostPool::take(base.back() ? base.back() : 1))) return CJS_E_OUT_OF_MEMORY;
+    for (size_t i = 0; i < pieces.size(); i++) if (pieces[i].size) memcpy(res + base[i], pieces[i].buf, pieces[i].size);
+    for (size_t k = 0; k < count; k++) off[k] += base[piece_of[k]];
+  }
+  *out = res;
+  for (size_t k = 0; k < count; k++) if (status[k]) { set_detail("%s", detail[k].c_str()); break; }      // the lowest-index failing input's
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }

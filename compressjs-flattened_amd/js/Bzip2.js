@@ -51,6 +51,15 @@ Bzip2.decompressFile = function (inStream, outStream, multistream) {
   try { result = common.addon().bzip2Decompress(input.bytes, multistream ? 1 : 0); } catch (e) { rethrow(e); }
   return common.deliver(result, outStream);
 };
+// Bzip2.decompressFile over a batch: one output per input, in input order, decoded in shared GPU passes.  If an input fails,
+// the error decompressFile would throw for the lowest-index failing one, with e.index = its index.
+Bzip2.decompressFiles = function (inStreams, multistream) {
+  var inputs = [];
+  for (var i = 0; i < inStreams.length; i++) { inputs.push(common.coerceInput(inStreams[i]).bytes); }
+  try { return common.addon().bzip2DecompressBatch(inputs, multistream ? 1 : 0); } catch (e) {
+    try { rethrow(e); } catch (t) { if (typeof e.cjsIndex === 'number') { t.index = e.cjsIndex; } throw t; }
+  }
+};
 // Bunzip.decodeBlock (J/Bzip2_joined_.js:1797-1818): the block whose magic starts at bit `pos`
 Bzip2.decompressBlock = function (inStream, pos, outStream) {
   var input = common.coerceInput(inStream);

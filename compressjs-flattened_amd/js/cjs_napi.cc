@@ -23,6 +23,7 @@ struct Api {
   long (*bzip2_table)(const uint8_t*, size_t, int, uint64_t*, uint32_t*, long, const cjs_opts*) = nullptr;
   int (*bzip2_decompress_block)(const uint8_t*, size_t, uint64_t, uint8_t**, size_t*, const cjs_opts*) = nullptr;
   int (*bzip2_compress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, const cjs_opts*) = nullptr;
+  int (*bzip2_decompress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, int32_t*, const cjs_opts*) = nullptr;
   void (*free_)(void*) = nullptr;
   const char* (*strerror_)(int) = nullptr;
   const char* (*detail_)(void) = nullptr;
@@ -49,7 +50,7 @@ bool load_api() {
   SYM(bzip2_compress, "cjs_bzip2_compress") SYM(bzip2_decompress, "cjs_bzip2_decompress")
   SYM(bwtc_compress, "cjs_bwtc_compress") SYM(bwtc_decompress, "cjs_bwtc_decompress")
   SYM(bzip2_table, "cjs_bzip2_table") SYM(bzip2_decompress_block, "cjs_bzip2_decompress_block")
-  SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch")
+  SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch") SYM(bzip2_decompress_batch, "cjs_bzip2_decompress_batch")
   SYM(free_, "cjs_free") SYM(strerror_, "cjs_strerror") SYM(detail_, "cjs_last_error_detail") SYM(device_count, "cjs_device_count") SYM(version, "cjs_version") SYM(trim, "cjs_trim")
 #undef SYM
   return true;
@@ -218,6 +219,64 @@ napi_value bzip2_batch(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// bzip2DecompressBatch(array of Uint8Array / Buffer, multistream) -> array of Uint8Array   (Bzip2.decompressFiles)
+// The outputs are views of ONE external ArrayBuffer over the library's result buffer.  If an input fails, the error of the
+// lowest-index one is thrown (throw_code: its detail) with `cjsIndex`.
+napi_value bzip2_decompress_batch(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool is_arr = false;
+  if (argc >= 1) napi_is_array(env, argv[0], &is_arr);
+  if (!is_arr) { napi_throw_type_error(env, nullptr, "expected an array of Uint8Array or Buffer"); return nullptr; }
+  int32_t multi = 0;
+  if (argc >= 2) napi_get_value_int32(env, argv[1], &multi);
+  uint32_t count = 0;
+  napi_get_array_length(env, argv[0], &count);
+  std::vector<const uint8_t*> ptr(count + 1, nullptr);
+  std::vector<size_t> len(count + 1, 0), off(count + 1, 0), olen(count + 1, 0);
+  std::vector<int32_t> status(count + 1, 0);
+  for (uint32_t k = 0; k < count; k++) {
+    napi_value v;
+    napi_get_element(env, argv[0], k, &v);
+    if (!get_bytes(env, v, &ptr[k], &len[k])) { napi_throw_type_error(env, nullptr, "expected an array of Uint8Array or Buffer"); return nullptr; }
+  }
+  uint8_t* out = nullptr;
+  const int rc = api.bzip2_decompress_batch(ptr.data(), len.data(), count, multi, &out, off.data(), olen.data(), status.data(), nullptr);
+  if (rc != 0) return throw_code(env, rc);
+  for (uint32_t k = 0; k < count; k++) if (status[k] != 0) {
+    api.free_(out);
+    throw_code(env, status[k]);
+    napi_value exc, idx;
+    if (napi_get_and_clear_last_exception(env, &exc) == napi_ok) {
+      napi_create_uint32(env, k, &idx);
+      napi_set_named_property(env, exc, "cjsIndex", idx);
+      napi_throw(env, exc);
+    }
+    return nullptr;
+  }
+  size_t total = 0;
+  for (uint32_t k = 0; k < count; k++) total = off[k] + olen[k] > total ? off[k] + olen[k] : total;
+  napi_value res;
+  napi_create_array_with_length(env, count, &res);
+  if (!count) return res;
+  napi_value ab;
+  int64_t adj = 0;
+  if (napi_create_external_arraybuffer(env, out, total, finalize_buf, (void*)(intptr_t)total, &ab) == napi_ok) napi_adjust_external_memory(env, (int64_t)total, &adj);
+  else {
+    void* dst;
+    napi_create_arraybuffer(env, total, &dst, &ab);
+    if (total) memcpy(dst, out, total);
+    api.free_(out);
+  }
+  for (uint32_t k = 0; k < count; k++) {
+    napi_value ta;
+    napi_create_typedarray(env, napi_uint8_array, olen[k], ab, off[k], &ta);
+    napi_set_element(env, res, k, ta);
+  }
+  return res;
+}
+
 napi_value device_count(napi_env env, napi_callback_info) {
   if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
   napi_value v; napi_create_int32(env, api.device_count(), &v); return v;
@@ -240,6 +299,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bwtcCompress", nullptr, call_stream<2>, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bwtcDecompress", nullptr, call_stream<3>, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2CompressBatch", nullptr, bzip2_batch, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecompressBatch", nullptr, bzip2_decompress_batch, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Table", nullptr, bzip2_table, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2DecompressBlock", nullptr, bzip2_block, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_default, nullptr},

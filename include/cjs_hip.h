@@ -91,6 +91,18 @@ int cjs_bzip2_compress_batch(const uint8_t *const *in, const size_t *n, size_t c
  * whose 48-bit magic starts at bit `bitpos`. */
 long cjs_bzip2_table(const uint8_t *in, size_t n, int multistream, uint64_t *bitpos, uint32_t *size, long cap, const cjs_opts *opts);
 int cjs_bzip2_decompress_block(const uint8_t *in, size_t n, uint64_t bitpos, uint8_t **out, size_t *out_n, const cjs_opts *opts);
+/* Bzip2.decompressFile over a batch: `count` independent inputs (in[k], n[k] bytes; n[k] may be 0, in[k] may then be NULL),
+ * each decoded exactly as cjs_bzip2_decompress(in[k], n[k], multistream) would decode it, in shared GPU passes.  Returns 0 when
+ * every input got its own verdict: status[k] = 0 or the code cjs_bzip2_decompress gives for input k (CJS_E_NOT_BZIP_DATA,
+ * CJS_E_DATA_ERROR, CJS_E_OBSOLETE_INPUT, CJS_E_UNSUPPORTED).  One result buffer (*out, release with cjs_free): input k's bytes are
+ * [off[k], off[k] + len[k]), offsets ascend in input order, a failed input has len[k] = 0.  When some status[k] != 0,
+ * cjs_last_error_detail() returns the detail of the LOWEST-index failing input, as cjs_bzip2_decompress of that input alone
+ * would leave it -- the one case where the detail belongs to a call that returned 0.  A negative return is a failure of the
+ * call itself (CJS_E_INVALID_ARG, CJS_E_NO_DEVICE, CJS_E_HIP, CJS_E_OUT_OF_MEMORY); *out is then NULL.  count == 0: success,
+ * *out = NULL.  NULL out / off / len / status / in / n with count > 0, or n[k] > 0 with in[k] == NULL: CJS_E_INVALID_ARG before the
+ * device is touched.  opts->device is honoured; opts->n_devices and opts->stats are ignored. */
+int cjs_bzip2_decompress_batch(const uint8_t *const *in, const size_t *n, size_t count, int multistream, uint8_t **out, size_t *off,
+                               size_t *len, int32_t *status, const cjs_opts *opts);
 void cjs_free(void *p);
 /* Memory kept between calls (allocating and freeing multi-GB scratch costs more than compressing 100 MB):
  * cjs_bzip2_compress keeps its per-device workspace (~70 B per input byte of the largest call so far) and staging buffers;
