@@ -40,8 +40,11 @@ struct HuffWork {
   }
 };
 
+// which implementation builds the tables: HUFF_AUTO = by the shape of the call (what every production caller uses), or forced
+// (the stage-level tests run both on the same blocks)
+enum HuffPath { HUFF_AUTO = 0, HUFF_PER_BLOCK = 1, HUFF_CHAIN = 2 };
 int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                    const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist);
+                    const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist, int path = HUFF_AUTO);
 // a rank of a multi-GPU job: the stream CRC folded over ALL ranks' blocks (the trailer writer needs it), and whether the next
 // rank's blocks follow this fragment (pack_frame then completes the fragment's last word with the leading bits of the block magic)
 struct PackShard { uint32_t stream_crc; int follow_magic; };

@@ -839,12 +839,13 @@ int HuffWork::carve(Arena& a, size_t max_blocks_, uint32_t stride) {
 }
 
 int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                    const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist) {
+                    const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist, int path) {
   if (nb == 0) return 0;
+  if (path != HUFF_AUTO && path != HUFF_PER_BLOCK && path != HUFF_CHAIN) return CJS_E_INVALID_ARG;
   const bool dbg = env_debug();
   // one workgroup per block (huff_block) keeps nb CUs busy; with fewer blocks than CUs the chain of kernels spreads the
   // data-parallel phases over the whole chip
-  const bool split = nb >= 8 && nb <= 512 && (size_t)nb * w.max_stride >= ((size_t)8 << 20);
+  const bool split = path == HUFF_AUTO ? nb >= 8 && nb <= 512 && (size_t)nb * w.max_stride >= ((size_t)8 << 20) : path == HUFF_CHAIN;
   if (split) {
     const uint32_t max_sel = (uint32_t)(((size_t)w.max_stride + 1 + GSZ - 1) / GSZ);
     const uint32_t ga = (max_sel + HS_STEPS * AS_GROUPS - 1) / (HS_STEPS * AS_GROUPS), gc = (w.max_stride + 1 + HS_CNT - 1) / HS_CNT;

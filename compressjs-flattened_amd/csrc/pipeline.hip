@@ -683,3 +683,85 @@ extern "C" int cjs_stage_huff(const uint16_t* A, uint32_t npos, uint32_t alphabe
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
+
+extern "C" int cjs_stage_huff_blocks(const uint16_t* A, size_t a_stride, uint32_t nb, const uint32_t* npos, const uint32_t* alphabet,
+                                     const uint8_t* used, const uint32_t* block_crc, const uint32_t* pidx, int path,
+                                     uint32_t* ngroups, uint8_t* selectors, uint8_t* lengths, uint8_t* bits, size_t bits_stride,
+                                     uint64_t* nbits, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (nb == 0 || nb > 65535 || a_stride == 0 || (path != HUFF_AUTO && path != HUFF_PER_BLOCK && path != HUFF_CHAIN)) return CJS_E_INVALID_ARG;
+  // the blocks' symbol counts (the MTF stage's freq[]) and the checks the kernels rely on: symbols index tables of asz + 2 entries
+  std::vector<uint32_t> freq((size_t)nb * 258, 0);
+  std::vector<uint8_t> alist((size_t)nb * 256, 0);
+  uint32_t max_npos = 0;
+  for (uint32_t k = 0; k < nb; k++) {
+    const uint32_t n = npos[k], asz = alphabet[k];
+    if (n == 0 || n > a_stride || n > 50u * 32767u || asz == 0 || asz > 256) return CJS_E_INVALID_ARG;     // (15-bit selector count)
+    for (uint32_t i = 0; i < asz; i++) {
+      if (i && used[(size_t)k * 256 + i] <= used[(size_t)k * 256 + i - 1]) return CJS_E_INVALID_ARG;     // ascending, distinct
+      alist[(size_t)k * 256 + i] = used[(size_t)k * 256 + i];
+    }
+    const uint16_t* a = A + (size_t)k * a_stride;
+    for (uint32_t i = 0; i < n; i++) { if (a[i] > asz + 1) return CJS_E_INVALID_ARG; freq[(size_t)k * 258 + a[i]]++; }
+    max_npos = std::max(max_npos, n);
+  }
+  // device rows as the pipeline carves them: a block of up to `stride` bytes yields up to stride + 1 symbols
+  const uint32_t stride = max_npos > 1 ? max_npos - 1 : 1;
+  const size_t das = MtfWork::a_stride_for(stride);
+  Arena arena;
+  CJS_TRY(arena.init(HuffWork::bytes_needed(nb, stride) + 2 * das * nb + (size_t)nb * (258 * 4 + 256 + 5 * 4 + 8) + 16 * 256 + 65536));
+  HuffWork w;
+  CJS_TRY(w.carve(arena, nb, stride));
+  uint16_t* d_A = arena.take<uint16_t>(das * nb);
+  uint32_t* d_npos = arena.take<uint32_t>(nb);
+  uint32_t* d_asz = arena.take<uint32_t>(nb);
+  uint32_t* d_freq = arena.take<uint32_t>((size_t)nb * 258);
+  uint8_t* d_alist = arena.take<uint8_t>((size_t)nb * 256);
+  uint32_t* d_crc = arena.take<uint32_t>(nb);
+  uint32_t* d_pidx = arena.take<uint32_t>(nb);
+  uint64_t* d_soff = arena.take<uint64_t>(nb);
+  uint32_t* d_slen = arena.take<uint32_t>(nb);
+  if (!d_A || !d_npos || !d_asz || !d_freq || !d_alist || !d_crc || !d_pidx || !d_soff || !d_slen) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemsetAsync(d_A, 0, 2 * das * nb, s));
+  CJS_HIP_TRY(hipMemsetAsync(w.b.lens, 0, (size_t)nb * 6 * 258, s));
+  CJS_HIP_TRY(hipMemcpy2DAsync(d_A, 2 * das, A, 2 * a_stride, 2 * (size_t)max_npos, nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_npos, npos, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_asz, alphabet, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_freq, freq.data(), 4 * freq.size(), hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_alist, alist.data(), alist.size(), hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_crc, block_crc, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_pidx, pidx, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_TRY(huff_tables_run(s, w, nb, d_A, das, d_npos, d_asz, d_freq, d_alist, path));
+  // the blocks' bare bit strings (no stream header / trailer), each from bit 0 at a 4-byte aligned offset
+  CJS_TRY(huff_batch_offsets_run(s, w, nb, 0, 0, d_soff, d_slen));
+  uint64_t total = 0;
+  CJS_HIP_TRY(hipMemcpyAsync(&total, w.scalars, 8, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  Arena oarena;
+  CJS_TRY(oarena.init(total + 4096));
+  uint32_t* d_out = oarena.take<uint32_t>((total + 16 + 3) / 4);
+  if (!d_out) return CJS_E_OUT_OF_MEMORY;
+  CJS_HIP_TRY(hipMemsetAsync(d_out, 0, total + 16, s));
+  CJS_TRY(huff_batch_pack_run(s, w, nb, 9, 0, d_A, das, d_npos, d_asz, d_alist, d_crc, d_pidx, d_soff, d_out));
+  std::vector<uint64_t> soff(nb);
+  std::vector<uint32_t> slen(nb), blen(nb);
+  CJS_HIP_TRY(hipMemcpyAsync(soff.data(), d_soff, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(slen.data(), d_slen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(blen.data(), w.b.bitlen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(ngroups, w.b.ngroups, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(lengths, w.b.lens, (size_t)nb * 6 * 258, hipMemcpyDeviceToHost, s));
+  const size_t hsel = (a_stride + 49) / 50;
+  CJS_HIP_TRY(hipMemcpy2DAsync(selectors, hsel, w.b.sel, w.b.sel_stride, ((size_t)max_npos + 49) / 50, nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  for (uint32_t k = 0; k < nb; k++) if (slen[k] > bits_stride) return CJS_E_INVALID_ARG;      // (nothing of the bits written yet)
+  for (uint32_t k = 0; k < nb; k++) {
+    CJS_HIP_TRY(hipMemcpyAsync(bits + (size_t)k * bits_stride, (const uint8_t*)d_out + soff[k], slen[k], hipMemcpyDeviceToHost, s));
+    nbits[k] = blen[k];
+  }
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}

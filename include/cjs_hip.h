@@ -203,6 +203,19 @@ int cjs_stage_mtf(const uint8_t *U, const uint8_t *blocks, size_t n, int block_l
 /* Huffman tables + selectors (J/Bzip2_joined_.js:1989-2054,2147-2163) for one symbol stream */
 int cjs_stage_huff(const uint16_t *A, uint32_t npos, uint32_t alphabet, uint8_t *selectors, uint8_t *lengths /* 6*258 */,
                    uint32_t *ngroups, const cjs_opts *opts);
+/* The same for nb blocks at once, followed by the bit packing of each block, so that both implementations of the tables can be
+ * pinned block by block.  A holds nb*a_stride symbols; block k: A[k*a_stride .. + npos[k]) (values 0 .. alphabet[k]+1, end of
+ * block last; npos[k] <= a_stride and < 50*32768), used byte values used[k*256 .. + alphabet[k]) ascending, block CRC and BWT
+ * index as given.  path: 0 = the rule of the compressors, 1 = one workgroup per block, 2 = the chain of kernels.
+ * Out: ngroups[k]; selectors at k*ceil(a_stride/50) (ceil(npos[k]/50) of them); code lengths [nb][6][258] (tables >= ngroups[k]
+ * and symbols >= alphabet[k]+2 are 0); the block's bare bit string (magic, CRC, randomised bit, pidx, used map, table count,
+ * selectors, code lengths, data; zero-padded to whole bytes) at bits + k*bits_stride and its length in bits nbits[k].
+ * CJS_E_INVALID_ARG for symbols out of range, a used list that is not ascending, nb > 65535, or a bit string longer than
+ * bits_stride bytes. */
+int cjs_stage_huff_blocks(const uint16_t *A, size_t a_stride, uint32_t nb, const uint32_t *npos, const uint32_t *alphabet,
+                          const uint8_t *used, const uint32_t *block_crc, const uint32_t *pidx, int path,
+                          uint32_t *ngroups, uint8_t *selectors, uint8_t *lengths, uint8_t *bits, size_t bits_stride,
+                          uint64_t *nbits, const cjs_opts *opts);
 
 /* Serial entropy stage of BWTC.decompressFile (J/BWTC_joined_.js:1827-1913): range decoder + adaptive model + RLE2 + MTF
  * inverse, i.e. everything before BWT.unbwtransform.  Host logic only (the one entry point that needs no device; the chain

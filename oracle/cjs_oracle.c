@@ -364,24 +364,20 @@ int cjs_oracle_huff_groups(const uint16_t *A, int pos, int alphabet_size, uint8_
 }
 
 /* ------------------------------------------------------------------ compressBlock (Bzip2:2056-2196) */
-static int compress_block(const uint8_t *block, int n, bitw_t *w) {
-  uint8_t *U = (uint8_t *)malloc((size_t)n);
-  uint16_t *A = (uint16_t *)malloc(sizeof(uint16_t) * ((size_t)n + 1));
-  uint8_t *sel = (uint8_t *)malloc((size_t)n / 50 + 2);
-  if (!U || !A || !sel) { free(U); free(A); free(sel); return CJSO_OUT_OF_MEMORY; }
-  int pidx = cjs_oracle_bwt_cyclic(block, n, U);
-  if (pidx < 0) { free(U); free(A); free(sel); return CJSO_OUT_OF_MEMORY; }
+/* The entropy-coded block from its MTF/RLE2 symbols: magic, CRC, randomised bit, origPtr, used map, table count, selector
+ * MTF, delta-coded lengths, data (Bzip2:2056-2060, 2071-2080, 2147-2194). */
+static int emit_block(bitw_t *w, const uint16_t *A, int pos, int asz, const uint8_t *used, uint32_t crc, uint32_t pidx) {
+  uint8_t *sel = (uint8_t *)malloc((size_t)pos / 50 + 2);
+  if (!sel) return CJSO_OUT_OF_MEMORY;
+  bw_bits(w, 48, 0x314159265359ull);
+  bw_bits(w, 32, crc);
   bw_bits(w, 1, 0);
   bw_bits(w, 24, (uint64_t)pidx);
-  uint8_t used[256]; memset(used, 0, sizeof used);
-  for (int i = 0; i < n; i++) used[block[i]] = 1;
   for (int i = 0; i < 16; i++) { int any = 0; for (int j = 0; j < 16; j++) any |= used[i * 16 + j]; bw_bits(w, 1, (uint64_t)any); }
   for (int i = 0; i < 16; i++) {
     int any = 0; for (int j = 0; j < 16; j++) any |= used[i * 16 + j];
-    if (any) for (int j = 0; j < 16; j++) bw_bits(w, 1, used[i * 16 + j]);
+    if (any) for (int j = 0; j < 16; j++) bw_bits(w, 1, used[i * 16 + j] ? 1 : 0);
   }
-  uint32_t freq[258]; int asz;
-  int pos = cjs_oracle_mtf_rle2(U, block, n, A, freq, &asz);
   uint8_t lens[6 * 258];
   int ng = cjs_oracle_huff_groups(A, pos, asz, sel, lens);
   int nsel = (pos + 49) / 50, asz2 = asz + 2;
@@ -416,8 +412,36 @@ static int compress_block(const uint8_t *block, int n, bitw_t *w) {
     int t = sel[i / 50];
     bw_bits(w, lens[t * 258 + A[i]], code[t][A[i]]);
   }
-  free(U); free(A); free(sel);
+  free(sel);
   return w->b->oom ? CJSO_OUT_OF_MEMORY : 0;
+}
+int cjs_oracle_bzip2_block_bits(const uint16_t *A, int pos, int asz, const uint8_t *used, uint32_t crc, uint32_t pidx,
+                                uint8_t **out, uint64_t *out_bits) {
+  if (pos < 1 || asz < 1 || asz > 256) return CJSO_DATA_ERROR;
+  for (int i = 0; i < pos; i++) if (A[i] > asz + 1) return CJSO_DATA_ERROR;
+  buf_t b = {0, 0, 0, 0};
+  bitw_t w = {&b, 0, 0};
+  int rc = emit_block(&w, A, pos, asz, used, crc, pidx);
+  if (rc) { free(b.p); return rc; }
+  *out_bits = (uint64_t)b.n * 8 + (uint64_t)w.nacc;
+  bw_flush(&w);
+  if (b.oom) { free(b.p); return CJSO_OUT_OF_MEMORY; }
+  *out = b.p;
+  return 0;
+}
+static int compress_block(const uint8_t *block, int n, uint32_t crc, bitw_t *w) {
+  uint8_t *U = (uint8_t *)malloc((size_t)n);
+  uint16_t *A = (uint16_t *)malloc(sizeof(uint16_t) * ((size_t)n + 1));
+  if (!U || !A) { free(U); free(A); return CJSO_OUT_OF_MEMORY; }
+  int pidx = cjs_oracle_bwt_cyclic(block, n, U);
+  if (pidx < 0) { free(U); free(A); return CJSO_OUT_OF_MEMORY; }
+  uint8_t used[256]; memset(used, 0, sizeof used);
+  for (int i = 0; i < n; i++) used[block[i]] = 1;
+  uint32_t freq[258]; int asz;
+  int pos = cjs_oracle_mtf_rle2(U, block, n, A, freq, &asz);
+  int rc = emit_block(w, A, pos, asz, used, crc, (uint32_t)pidx);
+  free(U); free(A);
+  return rc;
 }
 
 /* Block loop of Bzip2.compressFile (Bzip2:2199-2249).  framed: 'BZh'+level header and trailer are written and
@@ -442,9 +466,7 @@ static int bzip2_blocks(const uint8_t *in, size_t n, int level, int framed, long
       stream_crc = ((stream_crc << 1) | (stream_crc >> 31)) ^ crc;
       if (crcs && k < crc_cap) crcs[k] = crc;
       if (framed || (k >= first && (count < 0 || k < first + count))) {
-        bw_bits(&w, 48, 0x314159265359ull);
-        bw_bits(&w, 32, crc);
-        rc = compress_block(block, length, &w);
+        rc = compress_block(block, length, crc, &w);
         if (rc) break;
       }
       k++;

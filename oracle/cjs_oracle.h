@@ -57,6 +57,11 @@ int cjs_oracle_mtf_rle2(const uint8_t *U, const uint8_t *block, int n, uint16_t 
 /* selectors + tables for one block (optimizeHuffmanGroups + final assignSelectors).
  * lengths is [6][258]; returns number of tables; selectors has ceil(pos/50) entries */
 int cjs_oracle_huff_groups(const uint16_t *A, int pos, int alphabet_size, uint8_t *selectors, uint8_t *lengths);
+/* the entropy-coded part of compressBlock (Bzip2:2056-2196) for one block's MTF/RLE2 symbols A[0..pos) (EOB last), as a bare
+ * bit string from bit 0: block magic, crc, randomised bit, pidx, used map (used[256] != 0 = byte present), table count,
+ * selectors, code lengths, data.  *out (cjs_oracle_free) holds ceil(*out_bits / 8) bytes, zero-padded */
+int cjs_oracle_bzip2_block_bits(const uint16_t *A, int pos, int asz, const uint8_t *used, uint32_t crc, uint32_t pidx,
+                                uint8_t **out, uint64_t *out_bits);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,8 @@ class Oracle(_StreamLib):
         L.cjs_oracle_rle1_block.argtypes = [V, S, ctypes.POINTER(S), V, I, ctypes.POINTER(ctypes.c_uint32)]
         L.cjs_oracle_mtf_rle2.argtypes = [V, V, I, V, V, ctypes.POINTER(I)]
         L.cjs_oracle_huff_groups.argtypes = [V, I, I, V, V]
+        L.cjs_oracle_bzip2_block_bits.argtypes = [V, I, I, V, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(u8p),
+                                                  ctypes.POINTER(ctypes.c_uint64)]
         L.cjs_oracle_bzip2_compress_range.argtypes = [u8p, S, I, ctypes.c_long, ctypes.c_long, ctypes.POINTER(u8p),
                                                       ctypes.POINTER(ctypes.c_uint64), V, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
 
@@ -183,6 +185,22 @@ class Oracle(_StreamLib):
         ng = self.L.cjs_oracle_huff_groups(A.ctypes.data, A.size, alphabet_size, sel.ctypes.data, lens.ctypes.data)
         return ng, sel[:nsel].copy(), lens.reshape(6, 258)[:ng, : alphabet_size + 2].copy()
 
+    def bzip2_block_bits(self, A, alphabet_size, used_bytes, crc, pidx):
+        """one block's bare bit string from its MTF/RLE2 symbols (magic .. data): (rc, bytes, nbits); used_bytes = the byte
+        values present (ascending list or array)"""
+        A = np.ascontiguousarray(A, dtype=np.uint16)
+        used = np.zeros(256, dtype=np.uint8)
+        used[np.asarray(used_bytes, dtype=np.int64)] = 1
+        out, bits = u8p(), ctypes.c_uint64(0)
+        rc = self.L.cjs_oracle_bzip2_block_bits(A.ctypes.data, A.size, alphabet_size, used.ctypes.data, crc, pidx,
+                                                ctypes.byref(out), ctypes.byref(bits))
+        if rc:
+            return rc, None, 0
+        nb = (bits.value + 7) // 8
+        arr = np.ctypeslib.as_array(out, shape=(max(nb, 1),))[:nb].copy()
+        self.L.cjs_oracle_free(out)
+        return 0, arr, bits.value
+
 
 class HipLib(_StreamLib):
     """The product: compressjs-flattened_amd/libcjs_hip.so through its C ABI (include/cjs_hip.h)."""
@@ -209,6 +227,7 @@ class HipLib(_StreamLib):
             "cjs_stage_rle1": [V, S, I, V, S, V, V, V, ctypes.c_long, ctypes.POINTER(ctypes.c_long), V],
             "cjs_stage_mtf": [V, V, S, I, V, V, V, V, V],
             "cjs_stage_huff": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
+            "cjs_stage_huff_blocks": [V, S, ctypes.c_uint32, V, V, V, V, V, I, V, V, V, V, S, V, V],
             "cjs_stage_bwtc_entropy_decode": [u8p, S, PP, PS, V, V, ctypes.c_long, ctypes.POINTER(I)],
             "cjs_last_error_detail": [],
         }
@@ -326,3 +345,40 @@ class HipLib(_StreamLib):
         ng = ctypes.c_uint32(0)
         rc = self.L.cjs_stage_huff(A.ctypes.data, A.size, alphabet, sel.ctypes.data, lens.ctypes.data, ctypes.byref(ng), None)
         return rc, ng.value, sel[:nsel], lens.reshape(6, 258)[: ng.value, : alphabet + 2]
+
+    def stage_huff_blocks(self, blocks, path):
+        """Huffman tables + bare bit packing of several blocks in one call (cjs_stage_huff_blocks).  blocks: list of dicts with
+        A (u16 symbols, EOB last), asz, used (ascending byte values), crc, pidx.  path 0 = the compressors' rule, 1 = one
+        workgroup per block, 2 = the chain of kernels.  Returns (rc, [(ngroups, selectors, lengths[ng][asz+2], bytes, nbits)])"""
+        nb = len(blocks)
+        a_stride = max(b["A"].size for b in blocks)
+        A = np.zeros(nb * a_stride, dtype=np.uint16)
+        npos = np.zeros(nb, dtype=np.uint32)
+        asz = np.zeros(nb, dtype=np.uint32)
+        used = np.zeros(nb * 256, dtype=np.uint8)
+        crc = np.zeros(nb, dtype=np.uint32)
+        pidx = np.zeros(nb, dtype=np.uint32)
+        for k, b in enumerate(blocks):
+            a = np.asarray(b["A"], dtype=np.uint16)
+            A[k * a_stride: k * a_stride + a.size] = a
+            npos[k], asz[k], crc[k], pidx[k] = a.size, b["asz"], b["crc"], b["pidx"]
+            u = np.asarray(b["used"], dtype=np.uint8)
+            used[k * 256: k * 256 + u.size] = u
+        hsel = (a_stride + 49) // 50
+        ng = np.zeros(nb, dtype=np.uint32)
+        sel = np.zeros(nb * hsel, dtype=np.uint8)
+        lens = np.zeros(nb * 6 * 258, dtype=np.uint8)
+        bits_stride = ((a_stride * 20 + 6 * 258 * 41 + 6 * hsel + 512) // 8 + 7) & ~7     # > any block's bit string
+        bits = np.zeros(nb * bits_stride, dtype=np.uint8)
+        nbits = np.zeros(nb, dtype=np.uint64)
+        rc = self.L.cjs_stage_huff_blocks(A.ctypes.data, a_stride, nb, npos.ctypes.data, asz.ctypes.data, used.ctypes.data,
+                                          crc.ctypes.data, pidx.ctypes.data, path, ng.ctypes.data, sel.ctypes.data,
+                                          lens.ctypes.data, bits.ctypes.data, bits_stride, nbits.ctypes.data, None)
+        if rc:
+            return rc, None
+        out = []
+        for k in range(nb):
+            g, n, b = int(ng[k]), int(nbits[k]), k * bits_stride
+            out.append((g, sel[k * hsel: k * hsel + (int(npos[k]) + 49) // 50].copy(),
+                        lens.reshape(nb, 6, 258)[k, :g, : int(asz[k]) + 2].copy(), bits[b: b + (n + 7) // 8].copy(), n))
+        return 0, out

@@ -65,6 +65,19 @@ def test_no_cpu_fallback_without_a_device():
     assert e.value.errorCode == -30          # CJS_E_NO_DEVICE: the product never routes through a CPU path
 
 
+def test_stage_huff_blocks_needs_a_device():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import support
+    blk = {"A": np.array([2, 0, 3], dtype=np.uint16), "asz": 2, "used": [65, 66], "crc": 0, "pidx": 0}
+    for path in (0, 1, 2):
+        rc, out = support.HipLib().stage_huff_blocks([blk], path)
+        assert rc == -30 and out is None          # CJS_E_NO_DEVICE before any argument is looked at
+
+
 def test_free_and_trim_need_no_device():
     # cjs_free takes what the library handed out (plain malloc or a pinned result buffer) and, like free(), a null pointer;
     # memory it does not know is plain malloc'd memory.  cjs_trim with nothing cached is a no-op.  Neither needs a GPU.

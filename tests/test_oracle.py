@@ -126,6 +126,35 @@ def test_huffman_allocator_reference_test_vectors(oracle):
     assert oracle.huff_alloc([0, 0, 0, 1, 1000], 20) == [4, 4, 3, 2, 1]
 
 
+def _block_bits_cases():
+    return [c for c in SMALL["cases"] if c["algo"] == "Bzip2" and c["in_len"] > 0 and c["in_len"] <= 400000]
+
+
+@pytest.mark.parametrize("case", _block_bits_cases(), ids=_id)
+def test_block_bits_equals_compress_range(oracle, case):
+    # the exported block emitter, fed the oracle's own BWT / MTF output of every block, gives the block bit for bit as the
+    # bare range stream does (compress_block is a caller of it, so the goldens above pin the same body)
+    data = recipes.build(case["recipe"])
+    level = case["level"]
+    blocks = oracle.rle1_blocks(data, level)
+    assert blocks
+    for k, (blk, crc, _, _) in enumerate(blocks):
+        U, pidx = oracle.bwt_cyclic(blk)
+        A, _, asz = oracle.mtf_rle2(U, blk)
+        rc, got, nbits = oracle.bzip2_block_bits(A, asz, np.unique(blk), crc, pidx)
+        assert rc == 0
+        rc, want, wbits, total, crcs = oracle.bzip2_compress_range(data, level, k, 1)
+        assert rc == 0 and total == len(blocks) and crcs[k] == crc
+        assert nbits == wbits, "block %d: %d bits, want %d" % (k, nbits, wbits)
+        assert np.array_equal(got, want), "block %d: first differing byte %d" % (k, np.nonzero(got != want)[0][0])
+
+
+def test_block_bits_rejects_bad_symbols(oracle):
+    A = np.array([0, 1, 2, 4], dtype=np.uint16)            # asz 2: symbols 0..3 only
+    assert oracle.bzip2_block_bits(A, 2, [7, 9], 0, 0)[0] == -5
+    assert oracle.bzip2_block_bits(A[:0], 2, [7, 9], 0, 0)[0] == -5
+
+
 def test_crc_kats(oracle):
     for k in KAT["crc"]:
         assert oracle.crc32(k["ascii"].encode()) == k["crc"]
