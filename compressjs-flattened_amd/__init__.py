@@ -85,6 +85,8 @@ def load_library():
     L.cjs_ctx_create_batch.argtypes = [ctypes.POINTER(V), I, S, S, I]
     L.cjs_bzip2_decompress_batch.argtypes = [ctypes.POINTER(u8p), PS, S, I, PP, PS, PS, ctypes.POINTER(ctypes.c_int32), V]
     L.cjs_bzip2_compress_batch_device.argtypes = [V, V, PS, S, I, V, S, PS, PS]
+    L.cjs_bzip2_decompress_device.argtypes = [V, S, I, V, S, PS, V]
+    L.cjs_bzip2_decompress_batch_device.argtypes = [V, PS, S, I, V, S, PS, PS, ctypes.POINTER(ctypes.c_int32), PS, V]
     L.cjs_bzip2_shard_share_bytes.argtypes = [S, I]
     L.cjs_bzip2_shard_share_bytes.restype = S
     L.cjs_bzip2_shard_tiles.argtypes = [V, V, S, I, I, V]
@@ -314,6 +316,54 @@ class DeviceContext:
         _check(self.L.cjs_bzip2_shard_pack(self.h, self.level, rank, len(metas), arr, d_out_ptr, out_cap, ctypes.byref(fo), ctypes.byref(fl),
                                            ctypes.byref(so), ctypes.byref(sl)))
         return fo.value, fl.value, so.value, sl.value
+
+
+class _Opts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("device", ctypes.c_int32), ("n_devices", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("stats", ctypes.c_void_p)]
+
+
+def decompress_device(d_in_ptr, n, d_out_ptr, out_cap, multistream=False, device=-1):
+    """Bzip2.decompressFile with the stream and the result in GPU memory (cjs_bzip2_decompress_device): d_in_ptr / d_out_ptr are
+    device addresses (e.g. tensor.data_ptr()) on `device` (-1: the current one).  Returns the bytes written.  Raises CjsError with
+    decompressFile's message; on CJS_E_OUTPUT_TOO_SMALL (-33) the error carries `need`, the bytes the result takes."""
+    L = load_library()
+    out_n = ctypes.c_size_t(0)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    rc = L.cjs_bzip2_decompress_device(d_in_ptr, n, 1 if multistream else 0, d_out_ptr, out_cap, ctypes.byref(out_n), ctypes.byref(opts))
+    if rc == -33:
+        e = CjsError(rc, L.cjs_strerror(rc).decode())
+        e.need = out_n.value
+        raise e
+    _check(rc)
+    return out_n.value
+
+
+def decompress_batch_device(d_in_ptr, in_off, d_out_ptr, out_cap, multistream=False, device=-1):
+    """decompressFiles with the inputs and the result in GPU memory (cjs_bzip2_decompress_batch_device): input k is
+    d_in[in_off[k] .. in_off[k+1]) (in_off on the host).  -> (out_off, out_len, status, detail): uint64 / int32 arrays (input k's
+    bytes at d_out + out_off[k]) and the lowest-index failing input's detail ("" if none).  Per-input failures are in status;
+    CjsError for a failure of the call, with `need` on CJS_E_OUTPUT_TOO_SMALL (-33)."""
+    L = load_library()
+    o = np.ascontiguousarray(in_off, dtype=np.uint64)
+    count = max(o.size - 1, 0)
+    PS = ctypes.POINTER(ctypes.c_size_t)
+    keep = o if o.size else np.zeros(1, dtype=np.uint64)
+    off = np.zeros(max(count, 1), dtype=np.uint64)
+    ln = np.zeros(max(count, 1), dtype=np.uint64)
+    st = np.zeros(max(count, 1), dtype=np.int32)
+    need = ctypes.c_size_t(0)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    rc = L.cjs_bzip2_decompress_batch_device(d_in_ptr, keep.ctypes.data_as(PS), count, 1 if multistream else 0, d_out_ptr, out_cap,
+                                             off.ctypes.data_as(PS), ln.ctypes.data_as(PS), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                             ctypes.byref(need), ctypes.byref(opts))
+    if rc == -33:
+        e = CjsError(rc, L.cjs_strerror(rc).decode())
+        e.need = need.value
+        raise e
+    _check(rc)
+    detail = L.cjs_last_error_detail().decode() if st[:count].any() else ""
+    return off[:count], ln[:count], st[:count], detail
 
 
 def trim():

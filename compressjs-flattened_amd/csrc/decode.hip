@@ -23,6 +23,8 @@
 #include "rle1.h"
 #include <algorithm>
 #include <chrono>
+#include <functional>
+#include <memory>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
@@ -874,6 +876,7 @@ struct DecShare {
   RleCarry* d_carry = nullptr; uint32_t carry_tiles = 0;      // per chain block and UR_TILE-byte tile: the RLE1 expansion state at the tile start
   std::vector<uint64_t> ebase;        // element offset of block c0+i inside d_w (size c1-c0+1)
   double ms_a = 0, ms_b = 0, ms_c = 0;
+  uint64_t h2d = 0, d2h = 0;          // bytes of the share's host <-> device copies
   char detail[96] = {0};            // error detail found by this share's worker thread (the detail text is per calling thread)
   // batch (cjs_bzip2_decompress_batch): input k is bytes [bst[k], ben[k]) of the upload, its blocks at most bdsz[k] bytes
   std::vector<uint32_t> bst, ben, bdsz;
@@ -900,6 +903,12 @@ struct DecJob {
   bool timing = false;
   bool batch = false;                 // phase C: a CRC verdict for every block (crc_got) instead of stopping at the first bad one
   std::vector<uint32_t> crc_got;
+  // device-resident source and sink (cjs_bzip2_decompress_device[_batch]).  upload: fills the share's scratch [0, up_hi - up_lo)
+  // on its stream in place of phase A's H2D of `in`; eos: called once phase A's candidates are sorted (a batch candidate's pad
+  // still names its input); dev_out: phase C expands straight into dev_out at the final offsets instead of scratch + D2H
+  std::function<int(DecShare* S, uint8_t* dst)> upload;
+  std::function<int(DecShare* S)> eos;
+  uint8_t* dev_out = nullptr;
 };
 
 double ms_since(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); }
@@ -907,7 +916,7 @@ double ms_since(std::chrono::steady_clock::time_point a) { return std::chrono::d
 // ---- phase A
 void dec_phase_a(DecJob* J, DecShare* S) {
   const auto T0 = std::chrono::steady_clock::now();
-  if (hipSetDevice(S->device) != hipSuccess || hipStreamCreate(S->s.put()) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  if (hipSetDevice(S->device) != hipSuccess || (!S->s && hipStreamCreate(S->s.put()) != hipSuccess)) { S->rc = CJS_E_HIP; return; }      // (a device source made it for the header pass)
   hipStream_t s = S->s;
   const size_t up_n = (size_t)(S->up_hi - S->up_lo);
   uint8_t* d_raw = nullptr; Cand* d_cand = nullptr; uint32_t* d_count = nullptr;
@@ -919,13 +928,17 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   // keep the dword phase of the stream: the decoders fetch aligned big-endian words by absolute word index
   uint8_t* d_al = d_raw + (S->up_lo & 3u);
   S->d_in = d_al - S->up_lo;
-  if (hipMemcpyAsync(d_al, J->in + S->up_lo, up_n, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(d_count, 0, 64, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  if (J->upload) rc = J->upload(S, d_al);                               // (a device source: its own copy or gather)
+  else if (hipMemcpyAsync(d_al, J->in + S->up_lo, up_n, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
+  else S->h2d += up_n;
+  if (rc || hipMemsetAsync(d_count, 0, 64, s) != hipSuccess) { S->rc = rc ? rc : CJS_E_HIP; return; }
   uint32_t *d_bst = nullptr, *d_ben = nullptr;
   const uint32_t nin = (uint32_t)S->bst.size();
   if (nin) {
     if ((rc = S->take((void**)&d_bst, 4 * (size_t)nin)) != 0 || (rc = S->take((void**)&d_ben, 4 * (size_t)nin)) != 0) { S->rc = rc; return; }
     if (hipMemcpyAsync(d_bst, S->bst.data(), 4 * (size_t)nin, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_ben, S->ben.data(), 4 * (size_t)nin, hipMemcpyHostToDevice, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+    S->h2d += 8 * (size_t)nin;
   }
   auto launch_scan = [&]() {                                            // (slabs: a grid may not exceed 2^32 threads)
     if (nin) { launch_magic_scan_batch(s, S->d_in, d_bst, d_ben, nin, S->hi, d_cand, cand_cap, d_count); return; }
@@ -937,6 +950,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   launch_scan();
   uint32_t ncand = 0;
   if (hipMemcpyAsync(&ncand, d_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  S->d2h += 4;
   if (ncand > cand_cap) {                                             // more magics than planned for (many tiny member streams): scan again with room for all
     S->drop(d_cand);
     cand_cap = ncand;
@@ -944,21 +958,26 @@ void dec_phase_a(DecJob* J, DecShare* S) {
     if (hipMemsetAsync(d_count, 0, 64, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
     launch_scan();
     if (hipMemcpyAsync(&ncand, d_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+    S->d2h += 4;
     if (ncand > cand_cap) { S->rc = CJS_E_HIP; return; }
   }
   S->cands.resize(ncand);
   if (ncand && hipMemcpy(S->cands.data(), d_cand, sizeof(Cand) * ncand, hipMemcpyDeviceToHost) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  S->d2h += sizeof(Cand) * (size_t)ncand;
   std::sort(S->cands.begin(), S->cands.end(), [](const Cand& a, const Cand& b) { return a.bit < b.bit; });
+  if (J->eos && ncand && (rc = J->eos(S)) != 0) { S->rc = rc; return; }
   uint32_t* d_cend = nullptr;                                      // batch: per candidate, its input's end and block size (cend, then cdsz)
   if (nin && ncand) {                                              // the batch scan left each candidate's input in pad
     std::vector<uint32_t> cend(2 * (size_t)ncand);
     for (uint32_t c = 0; c < ncand; c++) { cend[c] = S->ben[S->cands[c].pad]; cend[ncand + c] = S->bdsz[S->cands[c].pad]; }
     if ((rc = S->take((void**)&d_cend, 8 * (size_t)ncand)) != 0) { S->rc = rc; return; }
     if (hipMemcpy(d_cend, cend.data(), 8 * (size_t)ncand, hipMemcpyHostToDevice) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+    S->h2d += 8 * (size_t)ncand;
   }
   uint32_t nrows = 0;                                              // only block candidates get a row of the decode buffer
   for (auto& c : S->cands) c.pad = c.kind == 0 ? nrows++ : 0u;
   if (ncand && hipMemcpy(d_cand, S->cands.data(), sizeof(Cand) * ncand, hipMemcpyHostToDevice) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+  S->h2d += sizeof(Cand) * (size_t)ncand;
   S->bos.resize(ncand);
   S->tt_ptr.assign(ncand, 0ull);
   if (!ncand) { S->ms_a = ms_since(T0); return; }
@@ -1012,6 +1031,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
     }
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(S->bos.data() + c0, d_bo + c0, sizeof(BlockOut) * nc, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+    S->d2h += sizeof(BlockOut) * (size_t)nc;
     uint32_t maxc = 0; uint64_t packed = 0;
     for (uint32_t c = c0; c < c1; c++) if (S->cands[c].kind == 0 && !S->bos[c].err) { maxc = std::max(maxc, S->bos[c].count); packed += ((uint64_t)S->bos[c].count + 15u) & ~15ull; }
     if (rows) {
@@ -1042,6 +1062,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
           at += ((uint64_t)cnt + 15u) & ~15ull;
         }
         if (hipMemcpyAsync(d_gdst, gdst.data(), sizeof(RowDst) * (size_t)rows, hipMemcpyHostToDevice, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
+        S->h2d += sizeof(RowDst) * (size_t)rows;
         hipLaunchKernelGGL(bz_rows_pack, dim3(16, rows), dim3(256), 0, s, d_ttb, dsz, d_gdst);
         if (hipGetLastError() != hipSuccess) { S->rc = CJS_E_HIP; return; }
       }
@@ -1055,6 +1076,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   if (env_debug()) {
     uint64_t clk[8];
     if (!nin && hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_dec_clk), sizeof clk) == hipSuccess) {
+      S->d2h += sizeof clk;
       fprintf(stderr, "[cjs dec] candidate 0: header + tables %.1f us, group chain %.1f us for %llu groups\n", clk[5] / 100.0, clk[6] / 100.0, (unsigned long long)clk[7]);
     }
     fprintf(stderr, "[cjs dec] share on device %d: bytes [%llu, %llu) uploaded [%llu, %llu) = %zu B, %u candidates\n", S->device, (unsigned long long)S->lo,
@@ -1159,6 +1181,7 @@ void dec_phase_b(DecJob* J, DecShare* S) {
     std::vector<int32_t> errs(nb);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(J->chain.data() + b0, q.d_blocks, sizeof(IbBlock) * nb, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(errs.data(), q.d_err, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = CJS_E_HIP; break; }
+    S->h2d += sizeof(IbBlock) * (size_t)nb; S->d2h += (sizeof(IbBlock) + 4) * (size_t)nb;
     for (uint32_t k = 0; k < nb; k++) if (errs[k] <= 0) rc = CJS_E_DATA_ERROR;      // cannot happen: the walk makes >= 1 step
     S->drop(q.d_blocks); S->drop(q.key0); S->drop(q.key1); if (q.val0) S->drop(q.val0); if (q.val1) S->drop(q.val1); S->drop(q.snext); S->drop(q.ssteps);
     S->drop(q.srank); S->drop(q.d_err); S->drop(q.resume); if (q.seg) S->drop(q.seg); S->drop(q.sw.hist); S->drop(q.sw.bintot);
@@ -1188,9 +1211,11 @@ void dec_phase_c(DecJob* J, DecShare* S) {
       const uint32_t sg = (uint32_t)((blk[k].out_len + 16383) / 16384 + 1);
       if (sg > need_segs) need_segs = sg;
     }
-    IbBlock* d_blocks = nullptr; uint8_t* d_out = nullptr; RleBlock* d_ranges = nullptr; uint32_t *d_nb = nullptr, *d_seg = nullptr, *d_crc = nullptr;
+    // (a device sink: unrle1_write stores only inside [out_off, out_off + out_len) of each block, crc_ranges reads aligned 16-byte
+    // pieces that hold a byte of the range: the caller's buffer takes the bytes at their final offsets)
+    IbBlock* d_blocks = nullptr; uint8_t* d_out = J->dev_out ? J->dev_out + o0 : nullptr; RleBlock* d_ranges = nullptr; uint32_t *d_nb = nullptr, *d_seg = nullptr, *d_crc = nullptr;
     rc = S->take((void**)&d_blocks, sizeof(IbBlock) * nb);
-    if (!rc) rc = S->take((void**)&d_out, (size_t)obytes + 64);
+    if (!rc && !J->dev_out) rc = S->take((void**)&d_out, (size_t)obytes + 64);
     if (!rc) rc = S->take((void**)&d_ranges, sizeof(RleBlock) * nb);
     if (!rc) rc = S->take((void**)&d_nb, 64);
     if (!rc) rc = S->take((void**)&d_seg, 4 * (size_t)nb * need_segs);
@@ -1204,13 +1229,14 @@ void dec_phase_c(DecJob* J, DecShare* S) {
     if (!rc && hipMemcpyAsync(crcs.data(), d_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc && J->host && obytes && hipMemcpyAsync(J->host + o0, d_out, (size_t)obytes, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
+    if (!rc) { S->h2d += sizeof(IbBlock) * (size_t)nb; S->d2h += 4 * (size_t)nb + (J->host ? (size_t)obytes : 0); }
     if (!rc && J->batch) for (uint32_t k = 0; k < nb; k++) J->crc_got[b0 + k] = crcs[k];      // (each input's verdict: the batch's host side)
     else if (!rc) for (uint32_t k = 0; k < nb; k++) if (crcs[k] != blk[k].crc) {                    // Bad block CRC (:1756-1761)
       snprintf(S->detail, sizeof S->detail, "Bad block CRC (got %x expected %x)", crcs[k], blk[k].crc);
       if (env_debug()) fprintf(stderr, "[cjs dec] block %zu: Bad block CRC (got %08x expected %08x) out_len %u\n", b0 + k, crcs[k], blk[k].crc, blk[k].out_len);
       rc = CJS_E_DATA_ERROR; break;
     }
-    S->drop(d_blocks); S->drop(d_out); S->drop(d_ranges); S->drop(d_nb); S->drop(d_seg); S->drop(d_crc);
+    S->drop(d_blocks); if (!J->dev_out) S->drop(d_out); S->drop(d_ranges); S->drop(d_nb); S->drop(d_seg); S->drop(d_crc);
     b0 = b1;
   }
   S->rc = rc;
@@ -1251,11 +1277,13 @@ int bz_block_verdict(const BlockOut& bo, uint32_t dbuf_size, uint64_t bitpos, bo
 
 // The chain walk of one input (Bunzip.decode :1776-1794): 32 -> end(block 0) -> end(block 1) ... over the candidates, stream CRC
 // fold, multistream restarts (each member keeps its own level, :1787-1792).  in / n: the input's own bytes, whose header
-// _start_bunzip has passed; positions are bits of the input.  at(pos, &kind, &bo) finds the candidate whose magic starts at bit
+// _start_bunzip has passed; positions are bits of the input.  `in` is anything indexable by byte: the host bytes, or (device
+// source) an accessor over the few bytes the walk reads -- the header, and at an end-of-stream candidate the stored stream CRC and
+// the restart header behind it.  at(pos, &kind, &bo) finds the candidate whose magic starts at bit
 // pos (false: none) with its decode result, end_bit in bits of the input; take(bo, pos) appends a good block to the chain.
 // Returns 0 or the first error the walk meets, its detail set.  mode 1 (Bunzip.table) does not test the stream CRC.
-template <typename At, typename Take>
-int bz_walk(const uint8_t* in, size_t n, int multistream, int mode, uint32_t tt_stride, bool timing, At at, Take take) {
+template <typename Bytes, typename At, typename Take>
+int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_stride, bool timing, At at, Take take) {
   auto read_bits = [&](uint64_t bit, int k) -> uint64_t { uint64_t v = 0; for (int i = 0; i < k; i++) { const uint64_t b = bit + i; v = (v << 1) | ((b >> 3) < n ? (in[b >> 3] >> (7 - (b & 7))) & 1u : 0u); } return v; };
   uint32_t dbuf_size = 100000u * (uint32_t)(in[3] - '0');         // of the member stream being walked
   uint64_t pos = 32; uint32_t stream_crc = 0;
@@ -1436,6 +1464,264 @@ extern "C" long cjs_bzip2_table(const uint8_t* in, size_t n, int multistream, ui
   CJS_GUARD_END((long)CJS_E_OUT_OF_MEMORY, (long)CJS_E_HIP)
 }
 
+// ---------------------------------------------------------------- device-resident source and sink (cjs_bzip2_decompress_device)
+// bunzip_core with the input and the output in the GPU's memory.  The host path reads its host copy of the input in four places;
+// each is a device pass here (dec_device.hip): the header (dd_headers, one 8-byte D2H), the level pre-scan of a multistream input
+// (dd_level_scan: bz_max_level's rule), the upload (a device-to-device copy into phase A's dword-phased scratch) and, after the
+// magic scan, the stored stream CRC and restart header of every end-of-stream candidate (dd_eos_bytes), which bz_walk reads
+// through DevWalkBytes.  Phase C expands into the caller's buffer at the final offsets.  One share: the input lives on one GPU.
+// See DESIGN.md §6d.
+namespace {
+
+bool on_device(const void* p, int dev) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return a.type == hipMemoryTypeDevice && a.device == dev;
+}
+
+// what bz_walk reads of a device input: its 4 header bytes, and EOS_REC bytes from byte `at` on at the end-of-stream candidate
+// the walk stands on
+struct DevWalkBytes {
+  const uint8_t* hdr; const uint8_t* rec = nullptr; uint64_t at = 0;
+  uint8_t operator[](uint64_t i) const { if (rec && i - at < (uint64_t)EOS_REC) return rec[i - at]; return i < 4 ? hdr[i] : (uint8_t)0; }
+};
+
+// J->eos of a device source: EOS_REC bytes per end-of-stream candidate (rec_of[c]: its record, -1 for a block candidate)
+int dev_eos_gather(DecShare* S, std::vector<uint8_t>& rec, std::vector<long>& rec_of) {
+  const size_t nc = S->cands.size();
+  std::vector<uint64_t> tab;
+  rec_of.assign(nc, -1);
+  for (size_t c = 0; c < nc; c++) if (S->cands[c].kind) {
+    rec_of[c] = (long)(tab.size() / 2);
+    tab.push_back((S->cands[c].bit + 48) >> 3);
+    tab.push_back(S->bst.empty() ? S->up_hi : S->ben[S->cands[c].pad]);      // (a batch candidate: its own input's end)
+  }
+  const uint32_t ne = (uint32_t)(tab.size() / 2);
+  rec.assign((size_t)ne * EOS_REC, 0);
+  if (!ne) return 0;
+  uint64_t* d_tab = nullptr; uint8_t* d_rec = nullptr;
+  CJS_TRY(S->take((void**)&d_tab, 16 * (size_t)ne));
+  CJS_TRY(S->take((void**)&d_rec, (size_t)ne * EOS_REC));
+  if (hipMemcpyAsync(d_tab, tab.data(), 16 * (size_t)ne, hipMemcpyHostToDevice, S->s) != hipSuccess) return CJS_E_HIP;
+  launch_dev_eos_bytes(S->s, S->d_in, d_tab, ne, d_rec);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rec.data(), d_rec, (size_t)ne * EOS_REC, hipMemcpyDeviceToHost, S->s) != hipSuccess ||
+      hipStreamSynchronize(S->s) != hipSuccess) return CJS_E_HIP;
+  S->h2d += 16 * (size_t)ne; S->d2h += (size_t)ne * EOS_REC;
+  S->drop(d_tab); S->drop(d_rec);
+  return 0;
+}
+
+// One decode of a device-resident source: a single stream (bunzip_core with one share) or a batch group (dec_batch_group).
+// Prepared up to phase B, so that every size is known before anything is written, then emitted (phase C into the caller's buffer).
+struct DevUnit {
+  DecJob J;
+  DecShare S;
+  std::vector<uint8_t> rec; std::vector<long> rec_of;      // the end-of-stream candidates' bytes (dev_eos_gather)
+  int pending = 0; char pending_detail[192] = {0};         // single: the walk's error, reported if every block in front passes its CRC
+  uint64_t total = 0;                                       // bytes of the unit's output
+  size_t k0 = 0, k1 = 0;                                    // batch group: inputs [k0, k1) of the call
+  std::vector<size_t> ch0, ch1;                             //   input k0 + i's chain blocks
+  std::vector<GatherPiece> pieces;                          //   the gather of the inputs into the group layout
+};
+
+// _start_bunzip's bytes of `count` inputs (input k = d_in[off[k] .. off[k+1])), and for a multistream call the largest member level
+// of each (bz_max_level), on S's stream and from its pool
+int dev_headers(DecShare& S, const uint8_t* d_in, const std::vector<uint64_t>& off, bool multistream, std::vector<DevHdr>& hd) {
+  const size_t count = off.size() - 1;
+  hd.assign(count, DevHdr{});
+  if (off.back() == off.front()) return 0;                       // (no bytes at all: every header is empty)
+  if (hipSetDevice(S.device) != hipSuccess || (!S.s && hipStreamCreate(S.s.put()) != hipSuccess)) return CJS_E_HIP;
+  uint64_t* d_off = nullptr; DevHdr* d_hdr = nullptr;
+  CJS_TRY(S.take((void**)&d_off, 8 * off.size()));
+  CJS_TRY(S.take((void**)&d_hdr, sizeof(DevHdr) * count));
+  if (hipMemcpyAsync(d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, S.s) != hipSuccess) return CJS_E_HIP;
+  launch_dev_headers(S.s, d_in, d_off, (uint32_t)count, multistream, off.front(), off.back(), d_hdr);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hd.data(), d_hdr, sizeof(DevHdr) * count, hipMemcpyDeviceToHost, S.s) != hipSuccess ||
+      hipStreamSynchronize(S.s) != hipSuccess) return CJS_E_HIP;
+  S.h2d += 8 * off.size(); S.d2h += sizeof(DevHdr) * count;
+  S.drop(d_off); S.drop(d_hdr);
+  return 0;
+}
+
+// the walk over the candidates of one input whose bytes start at byte `bst` of the share's upload
+int dev_walk(DevUnit& U, const DevHdr& hd, size_t n, uint64_t bst, int multistream, const std::vector<uint64_t>& cbit) {
+  DecShare& S = U.S;
+  DevWalkBytes acc{hd.h};
+  const uint64_t base = 8 * bst;
+  long last = -1;
+  return bz_walk(acc, n, multistream, 0, U.J.tt_stride, U.J.timing,
+                 [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
+                   const auto it = std::lower_bound(cbit.begin(), cbit.end(), base + pos);
+                   if (it == cbit.end() || *it != base + pos) return false;
+                   last = (long)(it - cbit.begin());
+                   *kind = S.cands[(size_t)last].kind; *bo = S.bos[(size_t)last]; bo->end_bit -= base;
+                   if (*kind) { acc.rec = U.rec.data() + (size_t)U.rec_of[(size_t)last] * EOS_REC; acc.at = ((pos + 48) >> 3); }
+                   return true;
+                 },
+                 [&](const BlockOut& bo, uint64_t) {
+                   IbBlock ib; ib.tt = S.tt_ptr[(size_t)last]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
+                   U.J.chain.push_back(ib);
+                 });
+}
+
+int dev_phase_b(DevUnit& U) {
+  const size_t nb = U.J.chain.size();
+  U.total = 0;
+  U.J.out_off.assign(nb + 1, 0);
+  if (!nb) return 0;
+  U.S.c0 = 0; U.S.c1 = nb;
+  guarded(U.S.rc, [&] { dec_phase_b(&U.J, &U.S); });
+  if (U.S.rc) return U.S.rc;
+  for (size_t k = 0; k < nb; k++) U.J.out_off[k + 1] = U.J.out_off[k] + U.J.chain[k].out_len;
+  U.total = U.J.out_off[nb];
+  return 0;
+}
+
+// single stream, up to phase B: 0 (U.pending, U.total set) or what cjs_bzip2_decompress returns before its output stage
+int dev_single_prepare(DevUnit& U, const uint8_t* d_in, size_t n, int multistream, const DevHdr& hd) {
+  // _start_bunzip (:1408-1427)
+  if (n < 4 || hd.h[0] != 'B' || hd.h[1] != 'Z' || hd.h[2] != 'h') { set_detail("bad magic"); return CJS_E_NOT_BZIP_DATA; }
+  const int level = hd.h[3] - '0';
+  if (level < 1 || level > 9) { set_detail("level out of range"); return CJS_E_NOT_BZIP_DATA; }
+  DecJob& J = U.J; DecShare& S = U.S;
+  J.n = n; J.mode = 0; J.timing = env_debug();
+  J.tt_stride = 100000u * (uint32_t)(multistream ? std::max<int>(level, (int)hd.level) : level);
+  J.upload = [d_in, n](DecShare* s, uint8_t* dst) { return hipMemcpyAsync(dst, d_in, n, hipMemcpyDeviceToDevice, s->s) != hipSuccess ? (int)CJS_E_HIP : 0; };
+  J.eos = [&U](DecShare* s) { return dev_eos_gather(s, U.rec, U.rec_of); };
+  S.lo = 0; S.hi = n; S.up_lo = 0; S.up_hi = n;
+  guarded(S.rc, [&] { dec_phase_a(&J, &S); });
+  if (S.rc) return S.rc;
+  std::vector<uint64_t> cbit(S.cands.size());
+  for (size_t c = 0; c < S.cands.size(); c++) cbit[c] = S.cands[c].bit;
+  U.pending = dev_walk(U, hd, n, 0, multistream, cbit);
+  snprintf(U.pending_detail, sizeof U.pending_detail, "%s", cjs_last_error_detail());
+  clear_detail();
+  return dev_phase_b(U);
+}
+
+// single stream, phase C into d_out (nullptr: the CRC verdicts alone, in scratch; so with a pending error) -> the final verdict
+int dev_single_emit(DevUnit& U, uint8_t* d_out) {
+  if (!U.J.chain.empty()) {
+    U.J.dev_out = U.pending ? nullptr : d_out; U.J.host = nullptr;
+    U.S.rc = 0;
+    guarded(U.S.rc, [&] { dec_phase_c(&U.J, &U.S); });
+    if (U.S.rc) { if (U.S.detail[0]) set_detail("%s", U.S.detail); return U.S.rc; }
+  }
+  if (U.pending) { set_detail("%s", U.pending_detail); return U.pending; }
+  return 0;
+}
+
+// a batch group (dec_batch_group's layout and verdicts), up to phase B: status / detail of inputs refused by their header or their walk
+int dev_group_prepare(DevUnit& U, const uint8_t* d_in, const size_t* in_off, size_t k0, size_t k1, int multistream, const std::vector<DevHdr>& hd,
+                      int32_t* status, std::vector<std::string>& detail) {
+  DecJob& J = U.J; DecShare& S = U.S;
+  const size_t items = k1 - k0;
+  U.k0 = k0; U.k1 = k1;
+  J.mode = 0; J.batch = true; J.timing = env_debug();
+  S.bst.resize(items); S.ben.resize(items); S.bdsz.assign(items, 100000u);
+  int max_level = 1;
+  std::vector<uint8_t> ok(items, 0);
+  size_t bytes = 0;
+  for (size_t i = 0; i < items; i++) {                          // _start_bunzip (:1408-1427) of every input
+    const size_t k = k0 + i, m = in_off[k + 1] - in_off[k];
+    const uint8_t* h = hd[k].h;
+    status[k] = 0;
+    S.bst[i] = S.ben[i] = (uint32_t)bytes;
+    if (m < 4 || h[0] != 'B' || h[1] != 'Z' || h[2] != 'h') { status[k] = CJS_E_NOT_BZIP_DATA; detail[k] = "bad magic"; continue; }
+    const int level = h[3] - '0';
+    if (level < 1 || level > 9) { status[k] = CJS_E_NOT_BZIP_DATA; detail[k] = "level out of range"; continue; }
+    const int own = multistream ? std::max<int>(level, (int)hd[k].level) : level;
+    S.bdsz[i] = 100000u * (uint32_t)own;
+    max_level = std::max(max_level, own);
+    ok[i] = 1;
+    for (size_t p = 0; p < m; p += GATHER_PIECE)                 // (pieces of whole words: the last one of an input is zero-filled to one)
+      U.pieces.push_back(GatherPiece{in_off[k] + p, (uint32_t)(bytes + p), (uint32_t)std::min<size_t>(GATHER_PIECE, m - p)});
+    S.ben[i] = (uint32_t)(bytes + m);
+    bytes = (bytes + m + 3) & ~(size_t)3;
+  }
+  J.tt_stride = 100000u * (uint32_t)max_level;
+  J.n = bytes;
+  J.upload = [&U, d_in](DecShare* s, uint8_t* dst) {
+    GatherPiece* d_pc = nullptr;
+    CJS_TRY(s->take((void**)&d_pc, sizeof(GatherPiece) * U.pieces.size()));
+    if (hipMemcpyAsync(d_pc, U.pieces.data(), sizeof(GatherPiece) * U.pieces.size(), hipMemcpyHostToDevice, s->s) != hipSuccess) return (int)CJS_E_HIP;
+    s->h2d += sizeof(GatherPiece) * U.pieces.size();
+    launch_dev_gather(s->s, d_in, d_pc, (uint32_t)U.pieces.size(), dst);
+    return hipGetLastError() != hipSuccess ? (int)CJS_E_HIP : 0;
+  };
+  J.eos = [&U](DecShare* s) { return dev_eos_gather(s, U.rec, U.rec_of); };
+  S.lo = 0; S.hi = bytes; S.up_lo = 0; S.up_hi = bytes;
+  if (bytes) {
+    guarded(S.rc, [&] { dec_phase_a(&J, &S); });
+    if (S.rc) return S.rc;
+  }
+  std::vector<uint64_t> cbit(S.cands.size());
+  for (size_t c = 0; c < S.cands.size(); c++) cbit[c] = S.cands[c].bit;
+  U.ch0.assign(items, 0); U.ch1.assign(items, 0);
+  for (size_t i = 0; i < items; i++) {
+    U.ch0[i] = U.ch1[i] = J.chain.size();
+    if (!ok[i]) continue;
+    clear_detail();
+    const int rc = dev_walk(U, hd[k0 + i], in_off[k0 + i + 1] - in_off[k0 + i], S.bst[i], multistream, cbit);
+    U.ch1[i] = J.chain.size();
+    if (rc) { status[k0 + i] = rc; detail[k0 + i] = cjs_last_error_detail(); }     // pending: a bad block CRC in front of it wins
+  }
+  clear_detail();
+  const int rc = dev_phase_b(U);
+  if (rc == CJS_E_OUT_OF_MEMORY || rc == CJS_E_NO_DEVICE) return rc;
+  return rc ? (int)CJS_E_HIP : 0;                               // (as dec_batch_group)
+}
+
+// a batch group, phase C into d_out (the group's region): every input's status, offset (from d_out) and length
+int dev_group_emit(DevUnit& U, uint8_t* d_out, size_t base, size_t* out_off, size_t* out_len, int32_t* status, std::vector<std::string>& detail) {
+  DecJob& J = U.J;
+  const size_t nb = J.chain.size();
+  J.crc_got.assign(nb, 0);
+  J.dev_out = d_out;
+  if (nb) { U.S.rc = 0; guarded(U.S.rc, [&] { dec_phase_c(&J, &U.S); }); }
+  if (U.S.rc) return U.S.rc;
+  for (size_t i = 0; i < U.k1 - U.k0; i++) {
+    const size_t k = U.k0 + i;
+    for (size_t b = U.ch0[i]; b < U.ch1[i]; b++) if (J.crc_got[b] != J.chain[b].crc) {      // Bad block CRC (:1756-1761)
+      char d[96];
+      snprintf(d, sizeof d, "Bad block CRC (got %x expected %x)", J.crc_got[b], J.chain[b].crc);
+      status[k] = CJS_E_DATA_ERROR; detail[k] = d;
+      break;
+    }
+    out_off[k] = base + (size_t)J.out_off[U.ch0[i]];
+    out_len[k] = status[k] ? 0 : (size_t)(J.out_off[U.ch1[i]] - J.out_off[U.ch0[i]]);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cjs_bzip2_decompress_device(const uint8_t* d_in, size_t n, int multistream, uint8_t* d_out, size_t out_cap, size_t* out_n, const cjs_opts* opts) {
+  if (!out_n || (!d_in && n) || (!d_out && out_cap)) return CJS_E_INVALID_ARG;
+  *out_n = 0;
+  clear_detail();
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  int ndev = 0, dev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  RestoreDevice restore{dev};
+  if ((n && !on_device(d_in, dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
+  DevUnit U;
+  U.S.device = dev;
+  std::vector<DevHdr> hd;
+  CJS_TRY(dev_headers(U.S, d_in, {0, (uint64_t)n}, multistream != 0, hd));
+  int rc = dev_single_prepare(U, d_in, n, multistream, hd[0]);
+  if (!rc && !U.pending && U.total > out_cap) { *out_n = (size_t)U.total; rc = CJS_E_OUTPUT_TOO_SMALL; }      // (d_out untouched)
+  else if (!rc) rc = dev_single_emit(U, d_out);
+  U.S.release();
+  if (U.J.timing)
+    fprintf(stderr, "[cjs dec dev] single: %zu bytes in, %llu bytes out, H2D %llu D2H %llu candidates %zu blocks %zu\n", n, (unsigned long long)U.total,
+            (unsigned long long)U.S.h2d, (unsigned long long)U.S.d2h, U.S.cands.size(), U.J.chain.size());
+  if (!rc) *out_n = (size_t)U.total;
+  return rc;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
 // ---------------------------------------------------------------- batch (Bzip2.decompressFiles)
 // Inputs go in groups of up to BATCH_DEC_GROUP_BYTES, each group one upload with every input at a 4-byte-aligned offset and one
 // share of phases A-C: one magic scan over the group (a candidate never straddles two inputs), block decode of all candidates
@@ -1606,6 +1892,84 @@ extern "C" int cjs_bzip2_decompress_batch(const uint8_t* const* in, const size_t
     for (size_t k = 0; k < count; k++) off[k] += base[piece_of[k]];
   }
   *out = res;
+  for (size_t k = 0; k < count; k++) if (status[k]) { set_detail("%s", detail[k].c_str()); break; }      // the lowest-index failing input's
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+// ---------------------------------------------------------------- device-resident batch (cjs_bzip2_decompress_batch_device)
+// cjs_bzip2_decompress_batch with the inputs and the result in GPU memory: the same groups (dec_group_bytes), verdicts and layout.
+// Every group and every input above the group size (the single device path) is prepared up to phase B first -- the single
+// ones also through a CRC-only phase C, as a failed one takes no bytes -- so the layout and its size are known before anything
+// is written; then each emits into its region of d_out.  See DESIGN.md §6d.
+extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size_t* in_off, size_t count, int multistream, uint8_t* d_out, size_t out_cap,
+                                                 size_t* out_off, size_t* out_len, int32_t* status, size_t* out_need, const cjs_opts* opts) {
+  clear_detail();
+  if (count == 0) { if (out_need) *out_need = 0; return 0; }
+  if (!in_off || !out_off || !out_len || !status || !out_need || count >= 0xFFFFFFFFu) return CJS_E_INVALID_ARG;
+  for (size_t k = 0; k < count; k++) if (in_off[k + 1] < in_off[k]) return CJS_E_INVALID_ARG;
+  if ((!d_in && in_off[count] > in_off[0]) || (!d_out && out_cap)) return CJS_E_INVALID_ARG;
+  *out_need = 0;
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  int ndev = 0, dev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  RestoreDevice restore{dev};
+  if ((in_off[count] > in_off[0] && !on_device(d_in + in_off[0], dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;
+  DecShare H;                                                   // the header pass: its stream, pool and copy tally
+  H.device = dev;
+  std::vector<DevHdr> hd;
+  CJS_TRY(dev_headers(H, d_in, std::vector<uint64_t>(in_off, in_off + count + 1), multistream != 0, hd));
+  H.release();
+  const size_t G = dec_group_bytes();
+  std::vector<std::string> detail(count);
+  std::vector<std::unique_ptr<DevUnit>> units;
+  std::vector<size_t> unit_base;
+  uint64_t need = 0;
+  for (size_t k0 = 0; k0 < count;) {
+    const size_t n0 = in_off[k0 + 1] - in_off[k0];
+    units.emplace_back(new DevUnit);
+    DevUnit& U = *units.back();
+    U.S.device = dev;
+    if (n0 > G) {                                               // an input of its own: the single device path
+      U.k0 = k0; U.k1 = k0 + 1;
+      clear_detail();
+      int r = dev_single_prepare(U, d_in + in_off[k0], n0, multistream, hd[k0]);
+      if (!r) r = dev_single_emit(U, nullptr);                  // (the verdict: a failed input takes no bytes)
+      if (r == CJS_E_OUT_OF_MEMORY || r == CJS_E_NO_DEVICE || r == CJS_E_HIP || r == CJS_E_INVALID_ARG) return r;
+      status[k0] = r;
+      if (r) { detail[k0] = cjs_last_error_detail(); U.S.release(); }
+      unit_base.push_back((size_t)need);
+      out_off[k0] = (size_t)need; out_len[k0] = r ? 0 : (size_t)U.total;
+      need += r ? 0 : U.total;
+      k0++;
+      continue;
+    }
+    size_t k1 = k0, bytes = 0;
+    while (k1 < count && in_off[k1 + 1] - in_off[k1] <= G && (k1 == k0 || bytes + (in_off[k1 + 1] - in_off[k1]) <= G)) { bytes += (in_off[k1 + 1] - in_off[k1] + 3) & ~(size_t)3; k1++; }
+    CJS_TRY(dev_group_prepare(U, d_in, in_off, k0, k1, multistream, hd, status, detail));
+    unit_base.push_back((size_t)need);
+    need += U.total;
+    k0 = k1;
+  }
+  clear_detail();
+  *out_need = (size_t)need;
+  uint64_t h2d = H.h2d, d2h = H.d2h, cands = 0, blocks = 0;
+  auto tally = [&]() {
+    for (auto& u : units) { h2d += u->S.h2d; d2h += u->S.d2h; cands += u->S.cands.size(); blocks += u->J.chain.size(); }
+    if (env_debug())
+      fprintf(stderr, "[cjs dec dev] batch: %zu inputs, %zu units, %llu bytes out, H2D %llu D2H %llu candidates %llu blocks %llu\n", count, units.size(),
+              (unsigned long long)need, (unsigned long long)h2d, (unsigned long long)d2h, (unsigned long long)cands, (unsigned long long)blocks);
+  };
+  if (need > out_cap) { tally(); return CJS_E_OUTPUT_TOO_SMALL; }      // (d_out untouched)
+  for (size_t u = 0; u < units.size(); u++) {
+    DevUnit& U = *units[u];
+    if (U.J.batch) CJS_TRY(dev_group_emit(U, d_out + unit_base[u], unit_base[u], out_off, out_len, status, detail));
+    else if (!status[U.k0] && dev_single_emit(U, d_out + unit_base[u]) != 0) return CJS_E_HIP;      // (its verdict was 0 a moment ago)
+    U.S.release();
+  }
+  tally();
+  clear_detail();
   for (size_t k = 0; k < count; k++) if (status[k]) { set_detail("%s", detail[k].c_str()); break; }      // the lowest-index failing input's
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)

@@ -283,4 +283,14 @@ void launch_block_decode_batch(hipStream_t s, const uint8_t* d_in, const uint32_
                                RowTab* d_tabs, uint8_t* d_sel, uint32_t* d_gstart, uint8_t* d_l0, BlockOut* d_bo, uint32_t r0, uint32_t group_tiles,
                                uint16_t* d_syms, uint32_t sym_stride, uint32_t sym_groups, uint8_t* d_ops, uint32_t* d_opoff, uint32_t ops_stride, uint32_t* d_nops);
 
+// dec_device.hip: the device-resident source (cjs_bzip2_decompress_device).  Input k = d_in[off[k] .. off[k+1]).
+struct DevHdr { uint8_t h[4]; uint32_t level; };      // first 4 bytes (zeros past the end), largest member level found (multistream)
+constexpr int EOS_REC = 12;                            // bytes kept per end-of-stream candidate, from byte (bit + 48) / 8 on
+void launch_dev_headers(hipStream_t s, const uint8_t* d_in, const uint64_t* d_off, uint32_t count, bool multistream, uint64_t b0, uint64_t b1, DevHdr* d_hdr);
+void launch_dev_eos_bytes(hipStream_t s, const uint8_t* d_in, const uint64_t* d_tab, uint32_t n, uint8_t* d_out);
+// a batch group's upload: piece i = len bytes of d_in from src to dst + dst (4-byte aligned), zeros up to the next whole word
+struct GatherPiece { uint64_t src; uint32_t dst, len; };
+constexpr size_t GATHER_PIECE = 65536;                 // bytes per piece of an input (a multiple of 4)
+void launch_dev_gather(hipStream_t s, const uint8_t* d_in, const GatherPiece* d_pc, uint32_t npieces, uint8_t* dst);
+
 }  // namespace cjs

@@ -103,6 +103,29 @@ int cjs_bzip2_decompress_block(const uint8_t *in, size_t n, uint64_t bitpos, uin
  * device is touched.  opts->device is honoured; opts->n_devices and opts->stats are ignored. */
 int cjs_bzip2_decompress_batch(const uint8_t *const *in, const size_t *n, size_t count, int multistream, uint8_t **out, size_t *off,
                                size_t *len, int32_t *status, const cjs_opts *opts);
+/* cjs_bzip2_decompress with the stream and the result in GPU memory: d_in (n bytes) and d_out (out_cap bytes) are device memory
+ * of the GPU opts->device names (-1: the current one), any byte alignment; bytes past d_in + n are never read.  The caller has
+ * finished writing d_in (e.g. synchronised its stream); synchronous on return.  Return code, bytes and cjs_last_error_detail() are
+ * what cjs_bzip2_decompress gives for the same bytes on the host; on success *out_n = the decoded size.  A decoded size above
+ * out_cap: CJS_E_OUTPUT_TOO_SMALL with *out_n = the bytes needed and d_out untouched (out_cap = 0, d_out = NULL: the size query).
+ * No byte at or past min(out_cap, decoded size) is written, and every failure but a bad block CRC leaves d_out untouched.
+ * Before any launch d_in (n > 0) and d_out (out_cap > 0) must be device memory of that GPU (hipPointerGetAttributes), else
+ * CJS_E_INVALID_ARG, as for out_n NULL, d_in NULL with n > 0 or d_out NULL with out_cap > 0 (checked before the device is
+ * touched).  opts->n_devices and opts->stats are ignored. */
+int cjs_bzip2_decompress_device(const uint8_t *d_in, size_t n, int multistream, uint8_t *d_out, size_t out_cap, size_t *out_n,
+                                const cjs_opts *opts);
+/* cjs_bzip2_decompress_batch with the inputs and the result in GPU memory (the memory rules of cjs_bzip2_decompress_device): input k
+ * is d_in[in_off[k] .. in_off[k+1]) (in_off: HOST array of count + 1 ascending offsets).  status[k], out_off[k], out_len[k] (from
+ * d_out), the bytes and the lowest-index detail are what cjs_bzip2_decompress_batch gives for the same inputs; the same groups
+ * (CJS_DEC_GROUP_BYTES), a larger input through the single device path.  On success *out_need = the end of the last input's
+ * region.  A layout larger than out_cap: CJS_E_OUTPUT_TOO_SMALL with *out_need = the bytes needed, d_out untouched and the other
+ * out arrays not meaningful.  No byte at or past min(out_cap, out_need) is written; a failed input's region holds unspecified
+ * bytes.  count == 0: 0 with *out_need = 0.  CJS_E_INVALID_ARG before the device is touched for in_off / out_off / out_len /
+ * status / out_need NULL, in_off not ascending, d_in NULL with input bytes, d_out NULL with out_cap > 0; and before any launch
+ * for memory that is not the GPU's. */
+int cjs_bzip2_decompress_batch_device(const uint8_t *d_in, const size_t *in_off, size_t count, int multistream, uint8_t *d_out,
+                                      size_t out_cap, size_t *out_off, size_t *out_len, int32_t *status, size_t *out_need,
+                                      const cjs_opts *opts);
 void cjs_free(void *p);
 /* Memory kept between calls (allocating and freeing multi-GB scratch costs more than compressing 100 MB):
  * cjs_bzip2_compress keeps its per-device workspace (~70 B per input byte of the largest call so far) and staging buffers;
