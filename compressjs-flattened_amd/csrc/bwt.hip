@@ -478,6 +478,72 @@ __global__ __launch_bounds__(256) void bwt_flags(const uint64_t* __restrict__ ke
   }
 }
 
+// Rounds >= 2: the sorters leave one flag byte per slot instead of a 64-bit key -- all that the regroup ever took out of the key.
+// A slot has exactly one writer per round (the window that owns its group, else bwt_defer_scatter, else bwt_key_flags).
+constexpr uint32_t HF_NEW = 1u, HF_OLD = 2u;     // head of the new grouping / of the previous round's grouping
+// bit `bit` of each of the 16 flag bytes in v -> 16-bit mask (byte j -> bit j)
+__device__ __forceinline__ uint32_t hf_bits16(const uint4& v, int bit) {
+  const uint32_t M = 0x01020408u;                // bits 0, 8, 16, 24 of x land on bits 24..27 of x * M (no two partial products meet)
+  const uint32_t n0 = (((v.x >> bit) & 0x01010101u) * M) >> 24, n1 = (((v.y >> bit) & 0x01010101u) * M) >> 24;
+  const uint32_t n2 = (((v.z >> bit) & 0x01010101u) * M) >> 24, n3 = (((v.w >> bit) & 0x01010101u) * M) >> 24;
+  return (n0 & 15u) | ((n1 & 15u) << 4) | ((n2 & 15u) << 8) | ((n3 & 15u) << 12);
+}
+// the 16 flag bytes of slots [base + 16 * tid, +16) of a tile (tile bases and hflag are 16-byte aligned; chunks that start at or
+// past A are not read) and the mask of those slots that lie below A
+__device__ __forceinline__ uint4 hf_load16(const uint8_t* __restrict__ hflag, uint64_t base, uint32_t nvalid, int tid, uint32_t& valid) {
+  const uint32_t first = (uint32_t)tid * 16u;
+  const uint32_t nv = nvalid > first ? (nvalid - first < 16u ? nvalid - first : 16u) : 0u;
+  valid = (1u << nv) - 1u;
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (nv) v = *reinterpret_cast<const uint4*>(hflag + base + first);
+  return v;
+}
+// sorted 64-bit keys (group ordinal << 20 | rank key) -> flag bytes: the whole-array fallbacks of a round >= 2
+__global__ __launch_bounds__(256) void bwt_key_flags(const uint64_t* __restrict__ key, uint32_t A, uint8_t* __restrict__ hflag) {
+  for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < A; a += (uint64_t)gridDim.x * 256) {
+    const uint64_t k = key[a], p = a ? key[a - 1] : ~k;
+    hflag[a] = (uint8_t)((k != p ? HF_NEW : 0u) | ((k >> 20) != (p >> 20) ? HF_OLD : 0u));
+  }
+}
+// bwt_flags of a round >= 2, from the flag bytes: 1 B per slot
+__global__ __launch_bounds__(256) void bwt_flags_bytes(const uint8_t* __restrict__ hflag, uint32_t A, uint32_t* __restrict__ tile_cnt, uint32_t T,
+                                                       uint32_t* __restrict__ big_flag) {
+  __shared__ uint32_t nhs[257];           // per thread: new-head mask of its 16 slots (slots at or past A count as heads)
+  __shared__ uint32_t sm[4];
+  const int tid = threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * RS_TILE;
+  const uint32_t nvalid = (uint32_t)((uint64_t)A - base < RS_TILE ? (uint64_t)A - base : RS_TILE);
+  uint32_t valid;
+  const uint4 v = hf_load16(hflag, base, nvalid, tid, valid);
+  const uint32_t nh = hf_bits16(v, 0) & valid;
+  nhs[tid] = nh | (~valid & 0xFFFFu);
+  if (tid == 0) nhs[256] = base + RS_TILE < A ? (uint32_t)hflag[base + RS_TILE] & HF_NEW : 1u;
+  __syncthreads();
+  const uint32_t nx = ((nhs[tid] >> 1) | (nhs[tid + 1] << 15)) & 0xFFFFu;      // the slot behind is a head (or the end of the array)
+  const uint32_t single = nh & nx;
+  uint32_t surv = (uint32_t)__popc(valid & ~single), heads = (uint32_t)__popc(nh & ~single);
+  uint32_t last = nh ? (uint32_t)base + (uint32_t)tid * 16u + 32u - (uint32_t)__clz(nh) : 0u;
+  // a group of more than 1023 slots covers a whole aligned run of 512 slots (32 threads): see bwt_flags
+  {
+    const uint64_t any = __ballot(nh != 0);
+    const uint32_t run0 = (uint32_t)wave_id() * 2u;
+    if (lane_id() == 0) {
+      bool bad = false;
+      for (uint32_t b = 0; b < 2; b++) bad |= base + (uint64_t)(run0 + b + 1u) * 512u <= A && (uint32_t)(any >> (32 * b)) == 0u;
+      if (bad) atomicOr(big_flag, 1u);
+    }
+  }
+  surv = block_sum<256>(surv, sm);
+  heads = block_sum<256>(heads, sm);
+  last = wave_max(last);
+  if (lane_id() == 0) sm[wave_id()] = last;
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t m = sm[0]; for (int i = 1; i < 4; i++) m = sm[i] > m ? sm[i] : m;
+    tile_cnt[blockIdx.x] = surv; tile_cnt[T + blockIdx.x] = heads; tile_cnt[2 * (size_t)T + blockIdx.x] = m;
+  }
+}
+
 // single workgroup: exclusive sums of [0],[1]; exclusive prefix-max of [2]; totals -> counters[0..1]
 // (eight consecutive tiles per thread, one round of workgroup scans per 8 K tiles: 78 instead of 44 us for the 24 K tiles of
 // round 1 -- the strided accesses cost more than the barriers saved)
@@ -543,17 +609,18 @@ __device__ __forceinline__ uint64_t class_head_before(const uint64_t* __restrict
 // (it finds the one class head it cannot see by search: class_head_before); sweep 2 stores the upper half and, with the
 // scanned counts, everything else.
 template <bool FIRST, bool PACKED, int SWEEP = 0, typename G = Geom>      // FIRST: round 1 - slot a is sorted position a, and there is no previous grouping
-__global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val,
+__global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ key /* FIRST */, const uint8_t* __restrict__ hflag /* !FIRST: flag bytes instead */,
+                                                 const uint32_t* __restrict__ val,
                                                  const uint32_t* __restrict__ pos, uint32_t A, G g,
                                                  uint32_t* tile_cnt, uint32_t T,
                                                  uint32_t* __restrict__ R, uint32_t* __restrict__ SA,
                                                  uint32_t* __restrict__ nval, uint32_t* __restrict__ npos, uint32_t* __restrict__ ngord, HalfMap hm_,
                                                  const uint8_t* __restrict__ Tx, uint8_t* __restrict__ U, uint32_t* __restrict__ big_flag,
                                                  int gs1 /* FIRST: group key = key >> gs1 */, int carried /* the byte in front of a suffix rides in its record / val */) {
-  __shared__ uint64_t sk[RS_TILE + 2];
+  __shared__ uint64_t sk[FIRST ? RS_TILE + 2 : 1];        // rounds >= 2 stage no keys: 4 KB of LDS instead of 36
   __shared__ uint64_t m_nh[64], m_sg[64], m_oh[64];
   __shared__ uint32_t wp_s[64], wp_h[64], wp_head[64];
-  __shared__ uint32_t carry_s;
+  __shared__ uint32_t carry_s, nx_s;
   const uint32_t tile = xcd_tile(blockIdx.x, T), half = SWEEP == 2 ? 1u : 0u;
   if (tile >= T) return;
   const uint32_t hsplit = hm_.stride >> 1;
@@ -570,12 +637,16 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
   }
   uint32_t p16[FIRST ? 1 : 16], v16[PACKED ? 1 : 16];
   {
-    uint64_t k16[16];
+    uint64_t k16[FIRST ? 16 : 1];
+    uint4 hv = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t hvalid = 0;
+    if constexpr (FIRST) {
 #pragma unroll
-    for (int it = 0; it < 16; it++) {
-      const uint32_t e = (uint32_t)it * 256u + tid;
-      k16[it] = __builtin_nontemporal_load(key + base + (e < nvalid ? e : nvalid - 1u));     // streamed once: keep the L2 for R
-    }
+      for (int it = 0; it < 16; it++) {
+        const uint32_t e = (uint32_t)it * 256u + tid;
+        k16[it] = __builtin_nontemporal_load(key + base + (e < nvalid ? e : nvalid - 1u));     // streamed once: keep the L2 for R
+      }
+    } else hv = hf_load16(hflag, base, nvalid, tid, hvalid);      // this thread's 16 slots are [16 * tid, +16): one load
     if (!FIRST) {
 #pragma unroll
       for (int it = 0; it < 16; it++) { const uint32_t e = (uint32_t)it * 256u + tid; p16[it] = __builtin_nontemporal_load(pos + base + (e < nvalid ? e : nvalid - 1u)); }
@@ -584,39 +655,52 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
 #pragma unroll
       for (int it = 0; it < 16; it++) { const uint32_t e = (uint32_t)it * 256u + tid; v16[it] = __builtin_nontemporal_load(val + base + (e < nvalid ? e : nvalid - 1u)); }
     }
-    if (tid == 0) sk[0] = base ? key[base - 1] : ~0ull;
-    if (tid == 64) sk[RS_TILE + 1] = base + RS_TILE < A ? key[base + RS_TILE] : ~0ull;
+    if constexpr (FIRST) {
+      if (tid == 0) sk[0] = base ? key[base - 1] : ~0ull;
+      if (tid == 64) sk[RS_TILE + 1] = base + RS_TILE < A ? key[base + RS_TILE] : ~0ull;
 #pragma unroll
+      for (int it = 0; it < 16; it++) {
+        const uint32_t e = (uint32_t)it * 256u + tid;
+        sk[e + 1] = e < nvalid ? k16[it] : ~0ull;
+      }
+    } else {
+      // the head masks are the flag bits themselves: 16 bits per thread, laid over the 64 mask words
+      reinterpret_cast<uint16_t*>(m_nh)[tid] = (uint16_t)(hf_bits16(hv, 0) & hvalid);
+      reinterpret_cast<uint16_t*>(m_oh)[tid] = (uint16_t)(hf_bits16(hv, 1) & hvalid);
+      if (tid == 64) nx_s = base + RS_TILE < A ? (uint32_t)hflag[base + RS_TILE] & HF_NEW : 1u;      // the slot behind the tile is a head
+    }
+  }
+  __syncthreads();
+  if constexpr (FIRST) {
+    const int GS = gs1;                          // packed records: the group key sits above the position (and carried byte) bits
+    const uint64_t bnd = (base + g.stride - 1u) / g.stride * g.stride;      // round 1: a block start is a head (slot = sorted position)
+#pragma unroll 4
     for (int it = 0; it < 16; it++) {
       const uint32_t e = (uint32_t)it * 256u + tid;
-      sk[e + 1] = e < nvalid ? k16[it] : ~0ull;
+      const uint64_t a = base + e;
+      const bool ok = e < nvalid;
+      const uint64_t k = sk[e + 1] >> GS;
+      const bool nh = ok && (a == 0 || a == bnd || (sk[e] >> GS) != k);
+      const bool nx = a + 1 == A || a + 1 == bnd || (sk[e + 2] >> GS) != k;
+      const uint64_t mnh = __ballot(nh), msg = __ballot(nh && nx);
+      if (lane == 0) { m_nh[it * 4 + w] = mnh; m_sg[it * 4 + w] = msg; }
     }
+    __syncthreads();
   }
-  __syncthreads();
-  const int GS = FIRST ? gs1 : 0;                // packed records: the group key sits above the position (and carried byte) bits
-  const uint64_t bnd = FIRST ? (base + g.stride - 1u) / g.stride * g.stride : ~0ull;      // round 1: a block start is a head (slot = sorted position)
-#pragma unroll 4
-  for (int it = 0; it < 16; it++) {
-    const uint32_t e = (uint32_t)it * 256u + tid;
-    const uint64_t a = base + e;
-    const bool ok = e < nvalid;
-    const uint64_t k = sk[e + 1] >> GS;
-    const bool nh = ok && (a == 0 || a == bnd || (sk[e] >> GS) != k);
-    const bool nx = a + 1 == A || a + 1 == bnd || (sk[e + 2] >> GS) != k;
-    const uint64_t mnh = __ballot(nh), msg = __ballot(nh && nx);
-    if (lane == 0) { m_nh[it * 4 + w] = mnh; m_sg[it * 4 + w] = msg; }
-    if (!FIRST) {
-      const bool oh = ok && (a == 0 || (sk[e] >> 20) != (sk[e + 1] >> 20));      // head of a group of the previous round
-      const uint64_t moh = __ballot(oh);
-      if (lane == 0) m_oh[it * 4 + w] = moh;
-    }
-  }
-  __syncthreads();
   if (w == 0) {                          // 64 mask words, one per lane
-    const uint64_t mh = m_nh[lane], ms = m_sg[lane];
+    const uint64_t mh = m_nh[lane];
     const uint32_t first = (uint32_t)lane * 64u;
     const uint32_t nv = nvalid > first ? (nvalid - first < 64u ? nvalid - first : 64u) : 0u;
     const uint64_t vm = nv == 64 ? ~0ull : ((1ull << nv) - 1ull);
+    uint64_t ms;
+    if constexpr (FIRST) ms = m_sg[lane];
+    else {                               // singleton = head whose next slot is a head (or the end of the array)
+      const uint64_t mhx = mh | ~vm;
+      uint32_t nb = __shfl_down((uint32_t)(mhx & 1ull), 1, 64);
+      if (lane == 63) nb = nx_s;
+      ms = mh & ((mhx >> 1) | ((uint64_t)nb << 63));
+      m_sg[lane] = ms;
+    }
     const uint32_t sv = (uint32_t)__popcll(vm & ~ms), hd = (uint32_t)__popcll(mh & ~ms);
     const uint32_t lastrel = mh ? first + 63u - (uint32_t)__builtin_clzll(mh) + 1u : 0u;
     const uint32_t is = wave_incl_sum(sv), ih = wave_incl_sum(hd), im = wave_incl_max(lastrel);
@@ -669,7 +753,7 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
         if (!FIRST) keeps_rank = (m_oh[hrel >> 6] >> (hrel & 63u)) & 1ull;
       } else {
         head_a = carry - 1u;
-        if (!FIRST) keeps_rank = head_a == 0 || (key[head_a] >> 20) != (key[head_a - 1] >> 20);
+        if (!FIRST) keeps_rank = (hflag[head_a] & HF_OLD) != 0;
       }
       const uint32_t p = FIRST ? (uint32_t)a : p16[FIRST ? 0 : it];
       const uint32_t vraw = PACKED ? (uint32_t)sk[e + 1] : v16[PACKED ? 0 : it];
@@ -710,7 +794,8 @@ constexpr uint32_t TS_WIN = 4096, TS_MAXGRP = 1024, TS_NOM = TS_WIN - TS_MAXGRP,
 // ordinal from gord[], rank of suffix val + h out of R -- instead of reading back a key array that bwt_gather_keys wrote: the
 // random rank fetches (bound by the number of 64-byte transactions) then overlap the VALU-bound sorting of the other
 // workgroups of the CU, and 16 B per suffix of key traffic are gone.  Windows overlap, so every slot has ONE window that
-// fetches its rank and writes its key: the window that owns its group, else the window whose nominal range holds it.  The
+// fetches its rank: the window that owns its group (it stores the flag bytes of the group's slots at their sorted places, no
+// keys), else the window whose nominal range holds it (it stores the key as gathered, for the deferral kernels).  The
 // only group a window cannot see whole is the one that runs into it from the left; whether the window before owns that one
 // (<= TS_MAXGRP members, all inside its 4096 slots) follows from the 1024 ordinals in front of the window.
 template <typename G> struct TsGatherT { const uint32_t* R; const uint32_t* pos; const uint32_t* gord; uint32_t h; int cyclic; G g; };
@@ -776,7 +861,7 @@ __device__ __forceinline__ void ts_ce(uint64_t& a, uint64_t& b, bool up) {
   a = x; b = y;
 }
 template <typename TG>
-__global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t A,
+__global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint8_t* __restrict__ hflag, uint32_t A,
                                                      uint8_t* __restrict__ dflag, TG tg, uint32_t Tt) {
   __shared__ uint64_t sk[TS_WIN];
   __shared__ uint64_t hm[64];                    // head mask of the window
@@ -881,10 +966,15 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
     if (gmax == 0) continue;
     const uint64_t mine = r[it];
     const uint32_t mine32 = ((uint32_t)(mine >> 32) << 12) | ((uint32_t)it * 256u + tid);
-    uint32_t rank = 0;
-    for (uint32_t d = 0; d < gmax; d++) rank += (d < g && sk32[hx + d] < mine32) ? 1u : 0u;
+    uint32_t rank = 0, same = 0;        // same: members with my rank key that sort in front of me (none: I start a new group)
+    for (uint32_t d = 0; d < gmax; d++) {
+      const uint32_t o = sk32[hx + d];
+      const bool lt = d < g && o < mine32;
+      rank += lt ? 1u : 0u;
+      same += (lt && (o >> 12) == (mine32 >> 12)) ? 1u : 0u;
+    }
     if (own) {
-      key[wb + hx + rank] = ((uint64_t)go[it] << 20) | ((mine >> 32) & 0xFFFFFull);
+      hflag[wb + hx + rank] = (uint8_t)((same ? 0u : HF_NEW) | (rank ? 0u : HF_OLD));
       val[wb + hx + rank] = (uint32_t)mine;
     }
   }
@@ -941,8 +1031,9 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
   for (int it = 0; it < 16; it++) {
     if (cix[it] != 0xFFFFFFFFu) {
       const uint32_t x = (uint32_t)it * 256u + tid;
-      const uint64_t e = sk[cix[it]];
-      key[wb + x] = ((uint64_t)go[it] << 20) | ((e >> 32) & 0xFFFFFull);
+      const uint32_t c = cix[it];
+      const uint64_t e = sk[c], pe = c ? sk[c - 1] : ~e;          // (head slot, rank key) of the sorted predecessor
+      hflag[wb + x] = (uint8_t)(((e >> 32) != (pe >> 32) ? HF_NEW : 0u) | ((e >> 52) != (pe >> 52) ? HF_OLD : 0u));
       val[wb + x] = (uint32_t)e;
     }
   }
@@ -953,7 +1044,7 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
 // group: exactly h slots carry a composite below (h << 20), so the members of the group headed at h land on [h, h + size).
 // The cost does not depend on the group sizes (the counting / bitonic version above degrades with them).
 template <typename TG>
-__global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t A,
+__global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint8_t* __restrict__ hflag, uint32_t A,
                                                            uint8_t* __restrict__ dflag, TG tg, uint32_t Tt) {
   __shared__ uint64_t se[TS_WIN];                // (composite << 32) | suffix: staging of a pass
   __shared__ uint64_t hm[64];
@@ -1067,7 +1158,8 @@ __global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict_
   for (int s = 0; s < 16; s++) {
     if ((ownm >> s) & 1u) {
       const uint32_t x = (uint32_t)w * 1024u + (uint32_t)s * 64u + lane;
-      key[wb + x] = ((uint64_t)go[s] << 20) | (comp[s] & 0xFFFFFu);
+      const uint32_t pc = x ? (uint32_t)(se[x - 1] >> 32) : ~comp[s];      // composite of the sorted predecessor (se[] still holds the last pass)
+      hflag[wb + x] = (uint8_t)((comp[s] != pc ? HF_NEW : 0u) | ((comp[s] >> 20) != (pc >> 20) ? HF_OLD : 0u));
       val[wb + x] = pv[s];
     }
   }
@@ -1138,10 +1230,11 @@ __global__ __launch_bounds__(256) void bwt_defer_gather(const uint64_t* __restri
   }
 }
 __global__ __launch_bounds__(256) void bwt_defer_scatter(uint32_t D, const uint64_t* __restrict__ dk, const uint32_t* __restrict__ dv,
-                                                         const uint32_t* __restrict__ dpos, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+                                                         const uint32_t* __restrict__ dpos, uint8_t* __restrict__ hflag, uint32_t* __restrict__ val) {
   for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < D; j += (uint64_t)gridDim.x * 256) {
-    const uint32_t a = dpos[j];          // a slot of the same group: its ordinal stays, the rank key is the sorted one
-    key[a] = (key[a] & ~0xFFFFFull) | (dk[j] & 0xFFFFFull); val[a] = dv[j];
+    const uint32_t a = dpos[j];          // a slot of the same group (deferred slots and sorted records are both in group order)
+    const uint64_t k = dk[j], p = j ? dk[j - 1] : ~k;      // (dense ordinal << 20 | rank key) of the record and of the one in front
+    hflag[a] = (uint8_t)((k != p ? HF_NEW : 0u) | ((k >> 20) != (p >> 20) ? HF_OLD : 0u)); val[a] = dv[j];
   }
 }
 
@@ -1300,7 +1393,7 @@ size_t BwtWork::bytes_needed(size_t cap) {
   size_t b = 0;
   auto add = [&](size_t n) { b += (n + 255) & ~(size_t)255; };
   add(cap * 8); add(cap * 8); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4);  // key x2, val x2, pos x2, gord
-  add(cap * 4); add(cap * 4); add(cap);           // R, SA, dflag
+  add(cap * 4); add(cap * 4); add(cap); add(cap);  // R, SA, dflag, hflag
   add(hist_words(T) * 4); add(256 * segs_for(cap) * 4); add(3 * T * 4); add(64); add(16 * 256 * 4);
   return b + 4096;
 }
@@ -1312,7 +1405,7 @@ int BwtWork::carve(Arena& a, size_t cap_) {
   val[0] = a.take<uint32_t>(cap); val[1] = a.take<uint32_t>(cap);
   pos[0] = a.take<uint32_t>(cap); pos[1] = a.take<uint32_t>(cap);
   gord = a.take<uint32_t>(cap);
-  R = a.take<uint32_t>(cap); SA = a.take<uint32_t>(cap); dflag = a.take<uint8_t>(cap);
+  R = a.take<uint32_t>(cap); SA = a.take<uint32_t>(cap); dflag = a.take<uint8_t>(cap); hflag = a.take<uint8_t>(cap);
   hist = a.take<uint32_t>(hist_words(T)); bintot = a.take<uint32_t>(256 * (size_t)bintot_segs);
   tile_cnt = a.take<uint32_t>(3 * T); counters = a.take<uint32_t>(16);
   ghist = a.take<uint32_t>(16 * 256);
@@ -1383,27 +1476,35 @@ template int radix_pass_segments_public<uint32_t>(hipStream_t, BwtWork&, uint32_
 // bitonic version is cheaper once the groups are tiny (round 2 of the bench text, 7.7 suffixes per group: 1.51 vs 1.82 ms;
 // round 3, 3.5 per group: 0.67 vs 0.64 ms; later rounds up to 2x in favour of counting).
 template <typename TG>
-static void launch_tile_sort(hipStream_t s, uint32_t Tt, uint64_t* key, uint32_t* val, uint32_t A, uint8_t* dflag, uint32_t ngroups, const TG& tg) {
-  if (ngroups && A / ngroups >= 5) hipLaunchKernelGGL(bwt_tile_sort_radix<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, A, dflag, tg, Tt);
-  else hipLaunchKernelGGL(bwt_tile_sort<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, A, dflag, tg, Tt);
+static void launch_tile_sort(hipStream_t s, uint32_t Tt, uint64_t* key, uint32_t* val, uint8_t* hflag, uint32_t A, uint8_t* dflag, uint32_t ngroups, const TG& tg) {
+  if (ngroups && A / ngroups >= 5) hipLaunchKernelGGL(bwt_tile_sort_radix<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, hflag, A, dflag, tg, Tt);
+  else hipLaunchKernelGGL(bwt_tile_sort<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, hflag, A, dflag, tg, Tt);
+}
+// whole-array fallback of a round >= 2: radix passes over the 64-bit keys in key[c], then the flag bytes from the sorted keys
+static int sort_round_whole(hipStream_t s, BwtWork& w, int& c, uint32_t A, int bits, LaunchTimes* lt) {
+  CJS_TRY((radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, lt)));
+  hipLaunchKernelGGL(bwt_key_flags, dim3((A + 255) / 256 < 8192u ? (A + 255) / 256 : 8192u), dim3(256), 0, s, w.key[c], A, w.hflag);
+  CJS_HIP_TRY(hipGetLastError());
+  return 0;
 }
 // the tile sorters take the round (small remainders: whole-array radix passes on keys that bwt_gather_keys writes first)
 static bool tile_sorted_round(uint32_t A) { return A >= 2 * TS_WIN; }
 // One sort of a round >= 2: in-LDS tile sort of the small groups + global radix passes for the large ones.
-// Works in place on (key[c], val[c]); only the whole-array fallback flips c.
+// Works in place on val[c] and leaves the head flags of the sorted order in hflag[]; only the whole-array fallback flips c.
+// key[c] only ever holds the keys of the slots the tile sorters do not own (the deferral kernels read them).
 template <typename TG>
 static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int bits, LaunchTimes* lt, uint32_t ngroups, const TG& tg) {
-  if (!tile_sorted_round(A)) return radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, lt);      // (bwt_gather_keys made the keys)
+  if (!tile_sorted_round(A)) return sort_round_whole(s, w, c, A, bits, lt);      // (bwt_gather_keys made the keys)
   const uint32_t Tt = (A + TS_NOM - 1) / TS_NOM, Tg = (A + TS_GT - 1) / TS_GT;
   uint8_t* dflag = w.dflag;
   uint32_t* tcount = w.tile_cnt;                        // 3*cap/4096 entries >= cap/2048
   if (w.no_large_groups) {                              // groups only ever split: once none exceeds TS_MAXGRP, none will
-    launch_tile_sort(s, Tt, w.key[c], w.val[c], A, nullptr, ngroups, tg);
+    launch_tile_sort(s, Tt, w.key[c], w.val[c], w.hflag, A, nullptr, ngroups, tg);
     CJS_HIP_TRY(hipGetLastError());
     return 0;
   }
   dev_fill(s, dflag, 1, A);
-  launch_tile_sort(s, Tt, w.key[c], w.val[c], A, dflag, ngroups, tg);
+  launch_tile_sort(s, Tt, w.key[c], w.val[c], w.hflag, A, dflag, ngroups, tg);
   uint32_t* hcount = w.hist;                            // (free until the radix passes below, which come after the last reader of hcount)
   hipLaunchKernelGGL(bwt_defer_count, dim3(Tg), dim3(256), 0, s, A, dflag, w.key[c], tcount, hcount);
   hipLaunchKernelGGL(scan_u32_single, dim3(1), dim3(1024), 0, s, hcount, Tg, w.counters + 3, w.h_counters + 3);      // deferred groups
@@ -1413,7 +1514,11 @@ static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int
   if (env_debug()) fprintf(stderr, "[cjs bwt]   tile sort: %u of %u suffixes in groups > %u\n", D, A, TS_MAXGRP);
   if (D == 0) w.no_large_groups = true;
   if (D == 0) return 0;
-  if ((size_t)D > w.cap / 2) return radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, lt);
+  if ((size_t)D > w.cap / 2) {       // no room to sort them apart: the whole array by its keys (the sorted slots hold none: gathered again)
+    const uint32_t Tk = (A + RS_TILE - 1) / RS_TILE;
+    hipLaunchKernelGGL(bwt_gather_keys<decltype(tg.g)>, dim3(xcd_grid(Tk)), dim3(256), 0, s, tg.g, tg.cyclic, A, tg.h, tg.R, w.val[c], tg.pos, tg.gord, w.key[c], Tk);
+    return sort_round_whole(s, w, c, A, bits, lt);
+  }
   uint64_t* dk0 = w.key[1 - c]; uint64_t* dk1 = dk0 + w.cap / 2;
   uint32_t* dv0 = w.val[1 - c]; uint32_t* dv1 = dv0 + w.cap / 2;
   uint32_t* dpos = w.pos[1 - pc];
@@ -1422,7 +1527,7 @@ static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int
   const uint32_t ndg = w.h_counters[3];                 // deferred groups: dense ordinals 0 .. ndg-1 above the 20-bit rank key
   CJS_TRY((radix_passes<uint64_t>(s, w, dk0, dv0, dk1, dv1, cur, D, 0, 20 + bits_for(ndg ? ndg - 1 : 0), lt)));
   hipLaunchKernelGGL(bwt_defer_scatter, dim3((D + 255) / 256 < 8192u ? (D + 255) / 256 : 8192u), dim3(256), 0, s, D, cur ? dk1 : dk0, cur ? dv1 : dv0, dpos,
-                     w.key[c], w.val[c]);
+                     w.hflag, w.val[c]);
   CJS_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1491,24 +1596,25 @@ static int bwt_run_impl(hipStream_t s, BwtWork& w, const uint8_t* d_T, const G g
     const uint32_t T = (A + RS_TILE - 1) / RS_TILE;
     if (rounds == 0 && sweeps) {                                       // two launches, no counting pass (see bwt_apply)
       const HalfMap hm{2u, stride};
-      hipLaunchKernelGGL((bwt_apply<true, true, 1, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      hipLaunchKernelGGL((bwt_apply<true, true, 1, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                          w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
       hipLaunchKernelGGL(bwt_scan_tiles, dim3(1), dim3(1024), 0, s, w.tile_cnt, T, w.counters, w.h_counters);
       CJS_HIP_TRY(hipEventRecord(w.ev_scan, s));
-      hipLaunchKernelGGL((bwt_apply<true, true, 2, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      hipLaunchKernelGGL((bwt_apply<true, true, 2, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                          w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
     } else {
-    hipLaunchKernelGGL(bwt_flags, dim3(T), dim3(256), 0, s, w.key[c], A, w.tile_cnt, T, rounds == 0 ? gs1 : 0, w.counters + 4, rounds == 0 ? stride : 0u);
+    if (rounds == 0) hipLaunchKernelGGL(bwt_flags, dim3(T), dim3(256), 0, s, w.key[c], A, w.tile_cnt, T, gs1, w.counters + 4, stride);
+    else hipLaunchKernelGGL(bwt_flags_bytes, dim3(T), dim3(256), 0, s, w.hflag, A, w.tile_cnt, T, w.counters + 4);
     hipLaunchKernelGGL(bwt_scan_tiles, dim3(1), dim3(1024), 0, s, w.tile_cnt, T, w.counters, w.h_counters);
     CJS_HIP_TRY(hipEventRecord(w.ev_scan, s));
     if (rounds == 0) {
       const HalfMap hm{1u, stride};
       const uint32_t grid = xcd_grid(T);
-      if (packed) hipLaunchKernelGGL((bwt_apply<true, true, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      if (packed) hipLaunchKernelGGL((bwt_apply<true, true, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                                      w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-      else hipLaunchKernelGGL((bwt_apply<true, false, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+      else hipLaunchKernelGGL((bwt_apply<true, false, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                               w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-    } else hipLaunchKernelGGL((bwt_apply<false, false, 0, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
+    } else hipLaunchKernelGGL((bwt_apply<false, false, 0, G>), dim3(xcd_grid(T)), dim3(256), 0, s, nullptr, w.hflag, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
                               w.val[1 - c], w.pos[1 - pc], w.gord, HalfMap{1u, stride}, dT, dU, w.counters + 4, gs1, carried);
     }
     // the host only needs the counters of the tile scan: it waits for THAT kernel and queues the next round behind the regroup
