@@ -216,14 +216,73 @@ __global__ __launch_bounds__(MTF_CL_THREADS) void mtf_chunk_lists(MtfBufs mb) {
 }
 
 // ---- C2: replay each chunk from its start list; one lane per chunk.
-// The first 16 list positions live in four registers (byte k of the 128-bit value = list position k): finding a
-// symbol there is a SWAR zero-byte test and the move-to-front is a byte shift under a mask, no memory access.
-// Positions >= 16 stay in LDS (row stride 260 B, no bank aliasing between lanes) and are only walked for the few
-// heads whose rank is that large.
+// The first 64 list positions live in 16 registers (byte j of word k = list position 4k + j): finding a symbol there is a
+// SWAR zero-byte test and the move-to-front is a byte shift under a mask, no memory access.  Positions >= 64 stay in LDS
+// (row stride 260 B, no bank aliasing between lanes) and are only walked for the few heads whose rank is that large.
+//
+// The kernel is bound by the vector instructions it issues, and the lanes of a wave run in lock step, so a head costs what
+// the DEEPEST of the wave's 64 lanes needs.  The words are therefore walked in tiers (MTF_TIER: words 0-3, 4-7, then two at
+// a time): the search goes on into the next tier only while some lane has not found its symbol, and the shift covers the
+// tiers the search reached -- both under wave-uniform (scalar) branches.  A skipped word is one in which no lane would have
+// found anything and whose shift mask is zero in every lane.  On the bench text the deepest rank of a wave step is 37 on
+// average (10 words of 16; profiles/r05_mtf_tiers/rank_tiers.txt).  Inside a walked word nothing is compared and selected
+// (a v_cmp that feeds a v_cndmask costs wait states on top of the two instructions):
+//   search: the key of a word is the bit number of its first zero byte (v_ffbl gives -1 when there is none) | 32 k, and the
+//           rank is the minimum of the keys >> 3;
+//   shift : word k becomes alignbyte(l[k], l[k-1], 3) under a byte mask that is all ones below the word of the rank, the
+//           low (rank & 3) + 1 bytes in it and zero above: two sign-extended bits of a per-head thermometer and one
+//           per-head partial mask, put together by one three-input bit operation.
 constexpr int LROW = 260;
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t v) { return (v - 0x01010101u) & ~v & 0x80808080u; }   // lowest set bit is exact
-__device__ __forceinline__ uint32_t low_bytes_mask(int nb) { return nb <= 0 ? 0u : nb >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u); }
 constexpr int MTF_RW = 16;                 // list words held in registers (4 positions each)
+constexpr uint32_t MTF_NR = 4 * MTF_RW;    // positions in registers
+#ifndef CJS_MTF_TIERS
+#define CJS_MTF_TIERS 0, 4, 8, 10, 12, 14, 16      /* seven even bounds; fewer tiers: repeat the 16 */
+#endif
+constexpr int MTF_NTIER = 6;
+__device__ constexpr int MTF_TIER[MTF_NTIER + 1] = {CJS_MTF_TIERS};      // tier t = words MTF_TIER[t] .. MTF_TIER[t+1]-1
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t v) { return (v - 0x01010101u) & ~v & 0x80808080u; }   // lowest set bit is exact
+__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+// The two instructions the walk leans on, spelled out: written in C++ (`z ? ctz(z) : ~0u`, `(int)(v << (31 - K)) >> 31`) the
+// compiler turns both back into a compare and a select.
+__device__ __forceinline__ uint32_t first_bit_or_ones(uint32_t z) {      // number of the lowest set bit; ~0 when z == 0
+  uint32_t f;
+  asm("v_ffbl_b32 %0, %1" : "=v"(f) : "v"(z));
+  return f;
+}
+template <int K> __device__ __forceinline__ uint32_t spread_bit(uint32_t v) {      // bit K of v in all 32 bits
+  uint32_t f;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(f) : "v"(v), "n"(K));
+  return f;
+}
+// search of list words K .. K1-1 (two at a time).  The key of word k: 32 k + the number of bit 7 of its first byte equal to the
+// symbol (bc = the symbol in all four bytes), ~0 when it has none; m = the smallest key so far
+template <int K, int K1> __device__ __forceinline__ uint32_t mtf_search_words(const uint32_t (&l)[MTF_RW], uint32_t bc, uint32_t m) {
+  if constexpr (K < K1) {
+    const uint32_t ka = first_bit_or_ones(zero_bytes(l[K] ^ bc)) | (32u * K);
+    const uint32_t kb = first_bit_or_ones(zero_bytes(l[K + 1] ^ bc)) | (32u * (K + 1));
+    return mtf_search_words<K + 2, K1>(l, bc, umin(m, umin(ka, kb)));
+  } else {
+    return m;
+  }
+}
+template <int T> __device__ __forceinline__ uint32_t mtf_search_tier(const uint32_t (&l)[MTF_RW], uint32_t bc, uint32_t m) {
+  return mtf_search_words<MTF_TIER[T], MTF_TIER[T + 1]>(l, bc, m);
+}
+// shift of list words K down to K0, top word first: every word takes the byte that falls out of the word below it as that
+// word was.  above = ~1 << (word of the rank): bit k set = word k lies above the word of the rank; g1 = that bit of word K + 1 in all
+// 32 bits; pm = byte mask inside the word of the rank.  Mask of word k: all ones below the word of the rank, pm in it, zero above
+template <int K, int K0> __device__ __forceinline__ void mtf_shift_words(uint32_t (&l)[MTF_RW], uint32_t bc, uint32_t above, uint32_t g1, uint32_t pm) {
+  if constexpr (K >= K0) {
+    const uint32_t g = spread_bit<K>(above);
+    const uint32_t sh = __builtin_amdgcn_alignbyte(l[K], K ? l[K ? K - 1 : 0] : bc, 3);        // (l[K] << 8) | top byte of the word below (word 0: the symbol)
+    const uint32_t mk = ~g1 | (~g & pm);
+    l[K] = (sh & mk) | (l[K] & ~mk);
+    mtf_shift_words<K - 1, K0>(l, bc, above, g, pm);
+  }
+}
+template <int T> __device__ __forceinline__ void mtf_shift_tier(uint32_t (&l)[MTF_RW], uint32_t bc, uint32_t above, uint32_t pm) {
+  mtf_shift_words<MTF_TIER[T + 1] - 1, MTF_TIER[T]>(l, bc, above, spread_bit<MTF_TIER[T + 1]>(above), pm);
+}
 __global__ __launch_bounds__(256) void mtf_replay(uint32_t stride, MtfBufs mb) {
   __shared__ uint8_t L[256 * LROW];
   const uint32_t blk = blockIdx.y, H = mb.nheads[blk], asz = mb.asz[blk];
@@ -235,14 +294,13 @@ __global__ __launch_bounds__(256) void mtf_replay(uint32_t stride, MtfBufs mb) {
   uint8_t* hrank = mb.hrank + (size_t)blk * mb.hstride;
   const uint8_t* lst = mb.lists + (size_t)blk * mb.list_stride + (size_t)c * 256;
   uint8_t* my = L + threadIdx.x * LROW;
-  constexpr uint32_t NR = 4 * MTF_RW;      // positions in registers
   uint32_t l[MTF_RW];
 #pragma unroll
   for (int k = 0; k < MTF_RW; k += 4) {    // rows of lists[] are 256-byte aligned; bytes >= asz are never matched first
     const uint4 f = *reinterpret_cast<const uint4*>(lst + 4 * k);
     l[k] = f.x; l[k + 1] = f.y; l[k + 2] = f.z; l[k + 3] = f.w;
   }
-  for (uint32_t j = NR; j < asz; j++) my[j] = lst[j];
+  for (uint32_t j = MTF_NR; j < asz; j++) my[j] = lst[j];
   const uint32_t h0 = c * MTF_CHUNK, h1 = h0 + MTF_CHUNK < H ? h0 + MTF_CHUNK : H;
   // 16 heads at a time: one 16-byte load of symbols, one 16-byte store of ranks per lane (hsym/hrank rows
   // are 256-byte aligned: h0 is a multiple of 256 and the per-block stride is padded to 16)
@@ -251,39 +309,50 @@ __global__ __launch_bounds__(256) void mtf_replay(uint32_t stride, MtfBufs mb) {
     const uint4 sv = sv_next;
     if (hb + 16 < h1) sv_next = *reinterpret_cast<const uint4*>(hsym + hb + 16);      // in flight while these 16 heads are replayed
     uint32_t sw[4] = {sv.x, sv.y, sv.z, sv.w}, rw[4] = {0, 0, 0, 0};
+    if (hb + 16 > h1) {
+      // the last heads of the block: the bytes behind head h1-1 repeat its symbol, which then stands at the front of the list --
+      // rank 0, nothing moves -- so the walk below needs no test per head
+      const uint32_t nv = h1 - hb;
+#pragma unroll
+      for (int q = 1; q < 16; q++)
+        if ((uint32_t)q >= nv) {
+          const uint32_t p = (sw[(q - 1) >> 2] >> (8 * ((q - 1) & 3))) & 0xFFu;
+          sw[q >> 2] = (sw[q >> 2] & ~(0xFFu << (8 * (q & 3)))) | (p << (8 * (q & 3)));
+        }
+    }
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-      const uint32_t h = hb + q;
-      uint32_t r = 0;
-      if (h < h1) {
-        const uint32_t s8 = (sw[q >> 2] >> (8 * (q & 3))) & 0xFFu;
-        const uint32_t bc = s8 * 0x01010101u;
-        r = NR;
-#pragma unroll
-        for (int k = MTF_RW - 1; k >= 0; k--) {
-          const uint32_t z = zero_bytes(l[k] ^ bc);
-          if (z) r = 4u * (uint32_t)k + ((uint32_t)__builtin_ctz(z) >> 3);
-        }
-        if (r == NR) {
-          uint8_t prev = (uint8_t)(l[MTF_RW - 1] >> 24);      // falls out of the register part
-          for (; r < asz; r++) {
-            const uint8_t x = my[r];
-            my[r] = prev;
-            prev = x;
-            if (x == (uint8_t)s8) break;
-          }
-        }
-        // positions 0..min(r,NR-1) shift up by one, the symbol goes to the front
-        const int nb = (int)(r < NR ? r : NR - 1) + 1;
-        uint32_t carry_in = s8;
-#pragma unroll
-        for (int k = 0; k < MTF_RW; k++) {
-          const uint32_t sh = (l[k] << 8) | carry_in;
-          carry_in = l[k] >> 24;
-          const uint32_t m = low_bytes_mask(nb - 4 * k);
-          l[k] = (sh & m) | (l[k] & ~m);
+      const uint32_t bc = __builtin_amdgcn_perm(0u, sw[q >> 2], 0x01010101u * (uint32_t)(q & 3));      // the symbol in all four bytes
+      // search: tier by tier while a lane of the wave has not found its symbol (m = ~0); tier = the last one searched
+      uint32_t m = mtf_search_tier<0>(l, bc, ~0u);
+      int tier = 0;
+      bool more = __any(m == ~0u);
+      if (more) { m = mtf_search_tier<1>(l, bc, m); tier = 1; more = __any(m == ~0u); }
+      if (more) { m = mtf_search_tier<2>(l, bc, m); tier = 2; more = __any(m == ~0u); }
+      if (more) { m = mtf_search_tier<3>(l, bc, m); tier = 3; more = __any(m == ~0u); }
+      if (more) { m = mtf_search_tier<4>(l, bc, m); tier = 4; more = __any(m == ~0u); }
+      if (more) { m = mtf_search_tier<5>(l, bc, m); tier = 5; }
+      uint32_t r = m >> 3;
+      if (m == ~0u) {
+        const uint8_t s8 = (uint8_t)bc;
+        uint8_t prev = (uint8_t)(l[MTF_RW - 1] >> 24);      // falls out of the register part
+        for (r = MTF_NR; r < asz; r++) {
+          const uint8_t x = my[r];
+          my[r] = prev;
+          prev = x;
+          if (x == s8) break;
         }
       }
+      // positions 0..min(r,63) shift up by one, the symbol goes to the front: me = 8 min(r,63) + 7
+      const uint32_t me = umin(m, 8u * MTF_NR - 1u);
+      const uint32_t above = 0xFFFFFFFEu << (me >> 5);
+      const uint32_t pm = 0xFFFFFFFFu >> (~me & 31u);        // low (min(r,63) & 3) + 1 bytes
+      if (tier >= 5) mtf_shift_tier<5>(l, bc, above, pm);
+      if (tier >= 4) mtf_shift_tier<4>(l, bc, above, pm);
+      if (tier >= 3) mtf_shift_tier<3>(l, bc, above, pm);
+      if (tier >= 2) mtf_shift_tier<2>(l, bc, above, pm);
+      if (tier >= 1) mtf_shift_tier<1>(l, bc, above, pm);
+      mtf_shift_tier<0>(l, bc, above, pm);
       rw[q >> 2] |= r << (8 * (q & 3));
     }
     *reinterpret_cast<uint4*>(hrank + hb) = make_uint4(rw[0], rw[1], rw[2], rw[3]);
