@@ -92,6 +92,14 @@ def load_library():
     L.cjs_bzip2_shard_tiles.argtypes = [V, V, S, I, I, V]
     L.cjs_bzip2_shard_blocks.argtypes = [V, V, S, I, I, I, V, ctypes.POINTER(ShardMeta), ctypes.POINTER(Stats)]
     L.cjs_bzip2_shard_pack.argtypes = [V, I, I, I, ctypes.POINTER(ShardMeta), V, S, PS, PS, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
+    L.cjs_bzip2_enc_write.argtypes = [V, V, S]
+    L.cjs_bzip2_enc_finish.argtypes = [V]
+    L.cjs_bzip2_enc_pending.argtypes = [V]
+    L.cjs_bzip2_enc_pending.restype = S
+    L.cjs_bzip2_enc_read.argtypes = [V, V, S, PS]
+    L.cjs_bzip2_enc_destroy.argtypes = [V]
+    L.cjs_bzip2_enc_destroy.restype = None
     _lib = L
     return L
 
@@ -170,6 +178,23 @@ class Bzip2:
         return [buf[off[k]: off[k] + ln[k]] for k in range(count)]
 
     @staticmethod
+    def compressStream(chunks, props=None, chunk_bytes=0):
+        """compressFile over an iterable of byte chunks, in bounded memory: a generator of uint8 ndarrays, the pieces of the
+        .bz2 stream as they become ready; joined they are compressFile(all chunks joined, None, props)."""
+        level = _bzip2_level(props)
+
+        def gen():
+            with Bzip2Encoder(level, chunk_bytes) as enc:
+                for c in chunks:
+                    enc.write(c)
+                    if enc.pending:
+                        yield enc.read()
+                enc.finish()
+                if enc.pending:
+                    yield enc.read()
+        return gen()
+
+    @staticmethod
     def decompressFile(input, output=None, multistream=False):
         res = _stream_call(load_library().cjs_bzip2_decompress, input, 1 if multistream else 0)
         return _deliver(res, output)
@@ -200,6 +225,55 @@ class Bzip2:
                 e.index = k
                 raise e
         return [buf[off[k]: off[k] + ln[k]] for k in range(count)]
+
+
+class Bzip2Encoder:
+    """Streaming Bzip2.compressFile (cjs_bzip2_enc_*): write() input in pieces of any size, read() the stream in pieces; after
+    finish() the bytes read are those of compressFile over everything written.  The device and pinned memory it holds depend
+    on chunk_bytes (0: the library's default) and level, not on the bytes written.  One worker thread runs the GPU steps."""
+
+    def __init__(self, level=9, chunk_bytes=0, device=-1):
+        self.L = load_library()
+        self.h = ctypes.c_void_p()
+        opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+        _check(self.L.cjs_bzip2_enc_create(ctypes.byref(self.h), level, chunk_bytes, ctypes.byref(opts)))
+
+    def write(self, data):
+        a = _coerce_input(data)
+        _check(self.L.cjs_bzip2_enc_write(self.h, a.ctypes.data if a.size else None, a.size))
+
+    def finish(self):
+        _check(self.L.cjs_bzip2_enc_finish(self.h))
+
+    @property
+    def pending(self):
+        """output bytes read() can hand out now"""
+        return self.L.cjs_bzip2_enc_pending(self.h)
+
+    def read(self, max_bytes=None):
+        n = self.pending if max_bytes is None else min(int(max_bytes), self.pending)
+        out = np.empty(n, dtype=np.uint8)
+        got = ctypes.c_size_t(0)
+        _check(self.L.cjs_bzip2_enc_read(self.h, out.ctypes.data if n else None, n, ctypes.byref(got)))
+        return out[: got.value]
+
+    def close(self):
+        if self.h:
+            self.L.cjs_bzip2_enc_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BWTC:

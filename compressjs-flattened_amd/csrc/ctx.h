@@ -37,3 +37,9 @@ struct cjs_ctx {
   uint32_t sh_nb = 0, sh_first = 0, sh_cnt = 0, sh_state = 0;
   bool stage_times = true;         // cjs_ctx_set_stage_times
 };
+
+namespace cjs {
+// pipeline.hip: blocks [f, f + cnt) of the stream whose boundaries c->rle holds (rle1_run: nb blocks, the last of last_len bytes)
+// through RLE1 bytes / CRCs, suffix sort, MTF / RLE2 and the Huffman tables; the caller packs (huff_pack_run)
+int blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32_t nb, uint32_t last_len, uint32_t f, uint32_t cnt, cjs_stats* st, bool stage_times);
+}  // namespace cjs

@@ -109,8 +109,9 @@ static int compress_core(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, l
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 // blocks [f, f + cnt) of the stream whose boundaries the context's tables hold (nb blocks in all): RLE1 bytes + CRCs, suffix
-// sort, MTF / RLE2, Huffman tables.  Everything but the bit packing; nothing here waits for the stream.
-static int blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32_t nb, uint32_t last_len, uint32_t f, uint32_t cnt, cjs_stats* st, bool stage_times) {
+// sort, MTF / RLE2, Huffman tables.  Everything but the bit packing; nothing here waits for the stream.  (Also the step of the
+// streaming encoder, enc_stream.hip: declared in ctx.h.)
+int cjs::blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32_t nb, uint32_t last_len, uint32_t f, uint32_t cnt, cjs_stats* st, bool stage_times) {
   hipStream_t s = c->stream;
   if (cnt > c->range_blocks) return CJS_E_INVALID_ARG;
   uint32_t n_last = c->cap;

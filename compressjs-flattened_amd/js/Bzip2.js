@@ -26,11 +26,61 @@ function rethrow(e) {
   throw e;
 }
 
+// A stream object in the reference's sense (Util.coerceInputStream / coerceOutputStream): it has the byte method and no backing
+// buffer of its own (a Buffer, a typed array and a plain array are not streams).
+function isStream(x, method) {
+  return x !== null && typeof x === 'object' && method in x && !(x instanceof Uint8Array) && !Array.isArray(x);
+}
+var IN_PIECE = 4 << 20, OUT_PIECE = 4 << 20;
+// up to buf.length bytes of the stream into buf; 0 at its end
+function fillFrom(inStream, buf) {
+  if (typeof inStream.read === 'function') { var got = inStream.read(buf, 0, buf.length); return got > 0 ? got : 0; }
+  var n = 0, ch;
+  while (n < buf.length && (ch = inStream.readByte()) !== -1 && ch !== undefined && ch >= 0) { buf[n++] = ch; }
+  return n;
+}
+function writeTo(outStream, piece) {
+  if (typeof outStream.write === 'function') { outStream.write(piece, 0, piece.length); return; }
+  for (var i = 0; i < piece.length; i++) { outStream.writeByte(piece[i]); }
+}
+// compressFile with a stream object on either side: the input is fed to the streaming encoder piece by piece and the output is
+// drained as it appears; neither the whole input nor (with an output stream) the whole result is ever held.
+function compressPiecewise(inStream, inIsStream, outStream, outIsStream, level) {
+  var a = common.addon(), enc = null, pieces = [], total = 0;
+  function drain() {
+    while (a.bzip2EncPending(enc) > 0) {
+      var p = a.bzip2EncRead(enc, OUT_PIECE);
+      if (outIsStream) { writeTo(outStream, p); } else { pieces.push(p); total += p.length; }
+    }
+  }
+  try {
+    enc = a.bzip2EncCreate(level, 0);
+    if (inIsStream) {
+      var buf = new Uint8Array(IN_PIECE), n;
+      while ((n = fillFrom(inStream, buf)) > 0) { a.bzip2EncWrite(enc, buf.subarray(0, n)); drain(); }
+    } else {
+      var bytes = common.coerceInput(inStream).bytes;
+      for (var off = 0; off < bytes.length; off += IN_PIECE) { a.bzip2EncWrite(enc, bytes.subarray(off, Math.min(bytes.length, off + IN_PIECE))); drain(); }
+    }
+    a.bzip2EncFinish(enc);
+    drain();
+  } catch (e) { rethrow(e); } finally { if (enc) { a.bzip2EncDestroy(enc); } }
+  if (outIsStream) {
+    if (outStream.flush) { outStream.flush(); }
+    return outStream;
+  }
+  var result = new Uint8Array(total), o = 0;
+  pieces.forEach(function (p) { result.set(p, o); o += p.length; });
+  return common.deliver(result, outStream);
+}
+
 var Bzip2 = Object.create(null);
 Bzip2.compressFile = function (inStream, outStream, props) {
   var level = 9;
   if (typeof props === 'number') { level = props; }
   if (level < 1 || level > 9) { throw new Error('Invalid block size multiplier'); }
+  var inIsStream = isStream(inStream, 'readByte'), outIsStream = isStream(outStream, 'writeByte');
+  if (inIsStream || outIsStream) { return compressPiecewise(inStream, inIsStream, outStream, outIsStream, level); }
   var input = common.coerceInput(inStream);
   var result;
   try { result = common.addon().bzip2Compress(input.bytes, level); } catch (e) { rethrow(e); }

@@ -24,6 +24,12 @@ struct Api {
   int (*bzip2_decompress_block)(const uint8_t*, size_t, uint64_t, uint8_t**, size_t*, const cjs_opts*) = nullptr;
   int (*bzip2_compress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, const cjs_opts*) = nullptr;
   int (*bzip2_decompress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, int32_t*, const cjs_opts*) = nullptr;
+  int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
+  int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
+  int (*enc_finish)(cjs_bz_enc*) = nullptr;
+  size_t (*enc_pending)(const cjs_bz_enc*) = nullptr;
+  int (*enc_read)(cjs_bz_enc*, uint8_t*, size_t, size_t*) = nullptr;
+  void (*enc_destroy)(cjs_bz_enc*) = nullptr;
   void (*free_)(void*) = nullptr;
   const char* (*strerror_)(int) = nullptr;
   const char* (*detail_)(void) = nullptr;
@@ -51,6 +57,8 @@ bool load_api() {
   SYM(bwtc_compress, "cjs_bwtc_compress") SYM(bwtc_decompress, "cjs_bwtc_decompress")
   SYM(bzip2_table, "cjs_bzip2_table") SYM(bzip2_decompress_block, "cjs_bzip2_decompress_block")
   SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch") SYM(bzip2_decompress_batch, "cjs_bzip2_decompress_batch")
+  SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
+  SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(free_, "cjs_free") SYM(strerror_, "cjs_strerror") SYM(detail_, "cjs_last_error_detail") SYM(device_count, "cjs_device_count") SYM(version, "cjs_version") SYM(trim, "cjs_trim")
 #undef SYM
   return true;
@@ -277,6 +285,93 @@ napi_value bzip2_decompress_batch(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// ---- streaming encoder (cjs_bzip2_enc_*): bzip2EncCreate(level, chunkBytes) -> handle; bzip2EncWrite(handle, bytes);
+// bzip2EncFinish(handle); bzip2EncPending(handle) -> number; bzip2EncRead(handle, maxBytes) -> Uint8Array (at most maxBytes of
+// what is pending, never blocks); bzip2EncDestroy(handle).  The handle is an external whose finalizer destroys the encoder if
+// bzip2EncDestroy has not.
+struct EncHandle { cjs_bz_enc* e = nullptr; };
+void finalize_enc(napi_env, void* data, void*) {
+  EncHandle* h = (EncHandle*)data;
+  if (h->e && api.enc_destroy) api.enc_destroy(h->e);
+  delete h;
+}
+EncHandle* enc_arg(napi_env env, napi_callback_info info, size_t want, napi_value* argv) {
+  size_t argc = want;
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  void* p = nullptr;
+  if (argc < want || napi_get_value_external(env, argv[0], &p) != napi_ok || !p || !((EncHandle*)p)->e) {
+    napi_throw_type_error(env, nullptr, "expected an open encoder handle");
+    return nullptr;
+  }
+  return (EncHandle*)p;
+}
+napi_value enc_create(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  int32_t level = 9; double chunk = 0;
+  if (argc >= 1) napi_get_value_int32(env, argv[0], &level);
+  if (argc >= 2) napi_get_value_double(env, argv[1], &chunk);
+  EncHandle* h = new EncHandle();
+  const int rc = api.enc_create(&h->e, level, chunk > 0 ? (size_t)chunk : 0, nullptr);
+  if (rc != 0) { delete h; return throw_code(env, rc); }
+  napi_value v;
+  if (napi_create_external(env, h, finalize_enc, nullptr, &v) != napi_ok) { api.enc_destroy(h->e); delete h; napi_throw_error(env, nullptr, "cannot create the encoder handle"); return nullptr; }
+  return v;
+}
+napi_value enc_write(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  EncHandle* h = enc_arg(env, info, 2, argv);
+  if (!h) return nullptr;
+  const uint8_t* p = nullptr; size_t n = 0;
+  if (!get_bytes(env, argv[1], &p, &n)) { napi_throw_type_error(env, nullptr, "expected a Uint8Array or Buffer"); return nullptr; }
+  const int rc = api.enc_write(h->e, n ? p : nullptr, n);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value v; napi_get_undefined(env, &v); return v;
+}
+napi_value enc_finish(napi_env env, napi_callback_info info) {
+  napi_value argv[1];
+  EncHandle* h = enc_arg(env, info, 1, argv);
+  if (!h) return nullptr;
+  const int rc = api.enc_finish(h->e);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value v; napi_get_undefined(env, &v); return v;
+}
+napi_value enc_pending(napi_env env, napi_callback_info info) {
+  napi_value argv[1];
+  EncHandle* h = enc_arg(env, info, 1, argv);
+  if (!h) return nullptr;
+  napi_value v; napi_create_double(env, (double)api.enc_pending(h->e), &v); return v;
+}
+napi_value enc_read(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  EncHandle* h = enc_arg(env, info, 2, argv);
+  if (!h) return nullptr;
+  double cap = 0;
+  napi_get_value_double(env, argv[1], &cap);
+  size_t n = api.enc_pending(h->e);
+  if (cap < (double)n) n = cap > 0 ? (size_t)cap : 0;
+  napi_value ab, ta; void* dst = nullptr;
+  if (napi_create_arraybuffer(env, n, &dst, &ab) != napi_ok) { napi_throw_error(env, nullptr, "cannot allocate the output piece"); return nullptr; }
+  size_t got = 0;
+  static uint8_t dummy;
+  const int rc = api.enc_read(h->e, dst ? (uint8_t*)dst : &dummy, n, &got);
+  if (rc != 0) return throw_code(env, rc);
+  napi_create_typedarray(env, napi_uint8_array, got, ab, 0, &ta);
+  return ta;
+}
+napi_value enc_destroy(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  void* p = nullptr;
+  if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
+    EncHandle* h = (EncHandle*)p;
+    if (h->e && api.enc_destroy) api.enc_destroy(h->e);
+    h->e = nullptr;
+  }
+  napi_value v; napi_get_undefined(env, &v); return v;
+}
+
 napi_value device_count(napi_env env, napi_callback_info) {
   if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
   napi_value v; napi_create_int32(env, api.device_count(), &v); return v;
@@ -302,6 +397,12 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2DecompressBatch", nullptr, bzip2_decompress_batch, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Table", nullptr, bzip2_table, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2DecompressBlock", nullptr, bzip2_block, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncWrite", nullptr, enc_write, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncFinish", nullptr, enc_finish, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncPending", nullptr, enc_pending, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncRead", nullptr, enc_read, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncDestroy", nullptr, enc_destroy, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"version", nullptr, version, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"trim", nullptr, trim, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -62,8 +62,39 @@ function writeAll(fd, bytes) {
   while (off < buf.length) { off += fs.writeSync(fd, buf, off, Math.min(buf.length - off, 1 << 24)); }
 }
 
+// fd-backed stream objects (NPM/bin/compressjs:60-120): the fronts read and write them in pieces
+function fdInput(fd) {
+  var one = Buffer.allocUnsafe(1);
+  var s = {
+    read: function (buf, off, len) {
+      var view = Buffer.from(buf.buffer, buf.byteOffset + off, len);
+      for (;;) {
+        try { return fs.readSync(fd, view, 0, len, null); } catch (e) { if (e.code === 'EAGAIN') { continue; } if (e.code === 'EOF') { return 0; } throw e; }
+      }
+    },
+    readByte: function () { return s.read(one, 0, 1) > 0 ? one[0] : -1; }
+  };
+  return s;
+}
+function fdOutput(fd) {
+  var one = new Uint8Array(1);
+  var s = {
+    write: function (buf, off, len) { writeAll(fd, buf.subarray(off, off + len)); return len; },
+    writeByte: function (b) { one[0] = b; s.write(one, 0, 1); },
+    flush: function () {}
+  };
+  return s;
+}
+
 var inFd = opt.files.length > 0 ? fs.openSync(opt.files[0], 'r') : 0;
 var outFd = opt.files.length > 1 ? fs.openSync(opt.files[1], 'w') : 1;
+if (opt.compress && type === 'bzip2') {
+  // streaming: the input is read in pieces and the output written as it appears, file and pipe alike -- no buffer of the whole file
+  try { fronts.bzip2.compressFile(fdInput(inFd), fdOutput(outFd), level); } catch (e) { fail(String(e && e.message ? e.message : e)); }
+  if (inFd !== 0) { fs.closeSync(inFd); }
+  if (outFd !== 1) { fs.closeSync(outFd); }
+  process.exit(0);
+}
 var input = readAll(inFd), result;
 try {
   if (opt.decompress) {

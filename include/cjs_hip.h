@@ -126,6 +126,34 @@ int cjs_bzip2_decompress_device(const uint8_t *d_in, size_t n, int multistream, 
 int cjs_bzip2_decompress_batch_device(const uint8_t *d_in, const size_t *in_off, size_t count, int multistream, uint8_t *d_out,
                                       size_t out_cap, size_t *out_off, size_t *out_len, int32_t *status, size_t *out_need,
                                       const cjs_opts *opts);
+/* Streaming form of cjs_bzip2_compress: the input is written in pieces of any size (zero included), the .bz2 stream is read in
+ * pieces of any size, and the bytes read, in order, once cjs_bzip2_enc_finish has returned, are exactly what
+ * cjs_bzip2_compress(all written bytes, level) returns -- for every level, every split of the input, every chunk_bytes and every
+ * pattern of reads; no input at all gives the 14-byte stream 'BZh<level>', end-of-stream magic, CRC 0.
+ * The encoder works in steps of up to chunk_bytes new input bytes (0 = the default, 64 MiB; clamped to 64 KiB .. 1 GiB).  The
+ * device and pinned host memory it holds depend on chunk_bytes and level, never on the total written: two pinned and two device
+ * staging chunks, the device input buffer (chunk_bytes + the carried block's input; it grows when a step finds no complete block,
+ * up to ~51 x level x 100000 bytes of runs), two packed-output buffers and a workspace of ~70 B per byte of chunk_bytes.
+ * _write takes all n bytes; it blocks only while both staging chunks wait for the device.  One worker thread per encoder runs the
+ * steps beside the caller.  Output not yet read is kept in host memory; _pending is the number of bytes _read can hand out now.
+ * The worker hands a step's output over only when all earlier output has been read, or while the caller waits for it inside
+ * _write or _finish: a caller that drains after each write of at most chunk_bytes never holds more than one step's output, and
+ * one that never reads is never held up.  _read copies up to cap bytes and never blocks.
+ * _finish says that no more input follows and returns when the whole stream is ready to be read (after a drain that is the
+ * output of at most four steps: those still under way and the final one); a second _finish is harmless.
+ * The memory is given back by _destroy (or by the failure that ended the worker), not by _finish.
+ * level outside 1..9: CJS_E_BAD_LEVEL; NULL e, NULL in with n > 0, NULL out with cap > 0, NULL got: CJS_E_INVALID_ARG; both before
+ * the device is touched (the device is first touched by the first write of n > 0 bytes).  _write after _finish:
+ * CJS_E_INVALID_ARG.  After any failing call the encoder stays failed: every later call returns the same code (and _pending 0);
+ * _destroy is always safe.  opts->device is honoured, n_devices and stats are ignored.  Encoders are independent of each other
+ * and of the contexts cjs_bzip2_compress keeps; one encoder is driven by one thread at a time. */
+typedef struct cjs_bz_enc cjs_bz_enc;
+int cjs_bzip2_enc_create(cjs_bz_enc **e, int level, size_t chunk_bytes, const cjs_opts *opts);
+int cjs_bzip2_enc_write(cjs_bz_enc *e, const uint8_t *in, size_t n);
+int cjs_bzip2_enc_finish(cjs_bz_enc *e);
+size_t cjs_bzip2_enc_pending(const cjs_bz_enc *e);
+int cjs_bzip2_enc_read(cjs_bz_enc *e, uint8_t *out, size_t cap, size_t *got);
+void cjs_bzip2_enc_destroy(cjs_bz_enc *e);
 void cjs_free(void *p);
 /* Memory kept between calls (allocating and freeing multi-GB scratch costs more than compressing 100 MB):
  * cjs_bzip2_compress keeps its per-device workspace (~70 B per input byte of the largest call so far) and staging buffers;
