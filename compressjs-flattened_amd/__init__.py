@@ -100,6 +100,13 @@ def load_library():
     L.cjs_bzip2_enc_read.argtypes = [V, V, S, PS]
     L.cjs_bzip2_enc_destroy.argtypes = [V]
     L.cjs_bzip2_enc_destroy.restype = None
+    L.cjs_bzip2_dec_create.argtypes = [ctypes.POINTER(V), I, S, S, V]
+    L.cjs_bzip2_dec_write.argtypes = [V, V, S, PS]
+    L.cjs_bzip2_dec_finish.argtypes = [V]
+    L.cjs_bzip2_dec_read.argtypes = [V, V, S, PS]
+    L.cjs_bzip2_dec_done.argtypes = [V]
+    L.cjs_bzip2_dec_destroy.argtypes = [V]
+    L.cjs_bzip2_dec_destroy.restype = None
     _lib = L
     return L
 
@@ -200,6 +207,31 @@ class Bzip2:
         return _deliver(res, output)
 
     @staticmethod
+    def decompressStream(chunks, multistream=False, chunk_bytes=0, out_bytes=0):
+        """decompressFile over an iterable of pieces of a .bz2 stream, in bounded memory: a generator of uint8 ndarrays, the
+        decoded bytes as they become ready; joined they are decompressFile(all chunks joined, None, multistream).  A stream
+        that fails raises decompressFile's error once every block in front of the failure has been yielded."""
+        def gen():
+            with Bzip2Decoder(multistream, chunk_bytes, out_bytes) as dec:
+                def drain():
+                    while True:
+                        piece = dec.read(_DEC_READ_BYTES)
+                        if not piece.size:
+                            return
+                        yield piece
+                for c in chunks:
+                    a = _coerce_input(c)
+                    while a.size:
+                        took = dec.write(a)
+                        a = a[took:]
+                        if a.size:                  # the window is full: after a drain the next write takes at least a byte
+                            yield from drain()
+                    yield from drain()
+                dec.finish()
+                yield from drain()
+        return gen()
+
+    @staticmethod
     def decompressFiles(inputs, multistream=False):
         """decompressFile over a batch: one uint8 ndarray per input, in input order, decoded in shared GPU passes
         (cjs_bzip2_decompress_batch); views of one result buffer.  If an input fails, CjsError for the lowest-index one,
@@ -260,6 +292,64 @@ class Bzip2Encoder:
     def close(self):
         if self.h:
             self.L.cjs_bzip2_enc_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_DEC_READ_BYTES = 16 << 20      # piece size of decompressStream
+
+
+class Bzip2Decoder:
+    """Streaming Bzip2.decompressFile (cjs_bzip2_dec_*), a pull model: write() takes as much of a piece of the .bz2 stream as
+    the input window has room for and returns the count; read(max_bytes) hands out decoded bytes and is what runs the GPU steps.
+    An empty read means "write more, or finish()"; after finish() it means the stream has ended (`done`).  After a write that
+    took less than it was given, reading until an empty read guarantees that the next write takes at least a byte.  The bytes
+    read are those of decompressFile over everything written, and a stream that fails raises the same error from read() once
+    the blocks in front of the failure have been read.  The memory held depends on chunk_bytes and out_bytes (0: the library's
+    defaults), not on the bytes written or produced."""
+
+    def __init__(self, multistream=False, chunk_bytes=0, out_bytes=0, device=-1):
+        self.L = load_library()
+        self.h = ctypes.c_void_p()
+        opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+        _check(self.L.cjs_bzip2_dec_create(ctypes.byref(self.h), 1 if multistream else 0, chunk_bytes, out_bytes, ctypes.byref(opts)))
+
+    def write(self, data):
+        a = _coerce_input(data)
+        taken = ctypes.c_size_t(0)
+        _check(self.L.cjs_bzip2_dec_write(self.h, a.ctypes.data if a.size else None, a.size, ctypes.byref(taken)))
+        return taken.value
+
+    def finish(self):
+        _check(self.L.cjs_bzip2_dec_finish(self.h))
+
+    def read(self, max_bytes):
+        n = int(max_bytes)
+        out = np.empty(n, dtype=np.uint8)
+        got = ctypes.c_size_t(0)
+        _check(self.L.cjs_bzip2_dec_read(self.h, out.ctypes.data if n else None, n, ctypes.byref(got)))
+        return out[: got.value]
+
+    @property
+    def done(self):
+        """the stream has ended and every byte has been read"""
+        return bool(self.h) and self.L.cjs_bzip2_dec_done(self.h) == 1
+
+    def close(self):
+        if self.h:
+            self.L.cjs_bzip2_dec_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __enter__(self):

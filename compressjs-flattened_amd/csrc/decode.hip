@@ -858,10 +858,56 @@ namespace {
 constexpr uint64_t DEC_BATCH_ELEMS = 1ull << 28;      // BWT bytes per inverse-BWT batch (scratch ~ 21 B each)
 constexpr uint32_t DEC_BATCH_BLOCKS = 65535;          // grid.y of the per-block kernels
 
+// Device scratch of one streaming decoder (cjs_bzip2_dec_*): ONE allocation made at the decoder's first step, handed out first fit
+// in 256-byte units and taken back piece by piece, so what a decoder holds between its steps never changes.  A request that does
+// not fit (the size is an estimate) becomes a hipMalloc of its own, freed when it is given back.
+struct DecArena {
+  DevMem<uint8_t> base; size_t cap = 0;
+  std::vector<std::pair<size_t, size_t>> free_;      // (offset, bytes), ascending, coalesced
+  std::vector<std::pair<void*, size_t>> used;        // bytes == 0: a hipMalloc of its own
+  uint32_t spills = 0;
+  int init(size_t bytes) { CJS_TRY(base.alloc(bytes)); cap = bytes; free_.assign(1, {0, bytes}); return 0; }
+  void* take(size_t bytes) {
+    bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    for (size_t i = 0; i < free_.size(); i++) if (free_[i].second >= bytes) {
+      void* p = base.p + free_[i].first;
+      if (free_[i].second == bytes) free_.erase(free_.begin() + (long)i); else { free_[i].first += bytes; free_[i].second -= bytes; }
+      used.push_back({p, bytes});
+      return p;
+    }
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    spills++;
+    used.push_back({p, 0});
+    return p;
+  }
+  void give(void* p) {
+    size_t i = 0;
+    while (i < used.size() && used[i].first != p) i++;
+    if (i == used.size()) return;
+    const size_t bytes = used[i].second, off = bytes ? (size_t)((uint8_t*)p - base.p) : 0;
+    used.erase(used.begin() + (long)i);
+    if (!bytes) { (void)hipFree(p); return; }
+    size_t k = 0;
+    while (k < free_.size() && free_[k].first < off) k++;
+    free_.insert(free_.begin() + (long)k, {off, bytes});
+    if (k + 1 < free_.size() && free_[k].first + free_[k].second == free_[k + 1].first) { free_[k].second += free_[k + 1].second; free_.erase(free_.begin() + (long)k + 1); }
+    if (k > 0 && free_[k - 1].first + free_[k - 1].second == free_[k].first) { free_[k - 1].second += free_[k].second; free_.erase(free_.begin() + (long)k); }
+  }
+  void release() { for (auto& u : used) if (!u.second) (void)hipFree(u.first); used.clear(); free_.clear(); base.reset(); cap = 0; }
+  ~DecArena() { release(); }
+};
+
 struct DecShare {
   int device = 0, rc = 0;
   Stream s;
   std::vector<DevBuf> bufs;          // device scratch of the share, given back at release() (or early, by drop())
+  // a streaming decoder's step: scratch from the decoder's own arena instead of the pool, and rows only for the first row_limit
+  // block candidates at or after bit row_from.  Candidates in front of row_from are dropped, as is everything from the first
+  // block candidate past the limit on: cut_bit is that candidate's bit (none: ~0).
+  DecArena* arena = nullptr; std::vector<void*> abufs;
+  uint32_t row_limit = ~0u; uint64_t row_from = 0, cut_bit = ~0ull;
+  uint32_t ncand_seen = 0;            // candidates the magic scan found (before the row limit dropped any)
   uint64_t lo = 0, hi = 0;            // candidates starting in bytes [lo, hi) are this share's
   uint64_t up_lo = 0, up_hi = 0;      // uploaded byte range
   const uint8_t* d_in = nullptr;      // addressed by absolute byte: d_in[b] is valid for up_lo <= b < up_hi
@@ -881,14 +927,24 @@ struct DecShare {
   // batch (cjs_bzip2_decompress_batch): input k is bytes [bst[k], ben[k]) of the upload, its blocks at most bdsz[k] bytes
   std::vector<uint32_t> bst, ben, bdsz;
   uint32_t a_batches = 0, b_batches = 0;      // row batches of phase A, inverse-BWT batches of phase B
-  int take(void** p, size_t bytes) { DevBuf b(bytes); if (!(*p = b.p)) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(std::move(b)); return 0; }
-  void drop(void* p) { for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; } DevPool::give(p); }
+  int take(void** p, size_t bytes) {
+    if (arena) { if (!(*p = arena->take(bytes))) return (int)CJS_E_OUT_OF_MEMORY; abufs.push_back(*p); return 0; }
+    DevBuf b(bytes); if (!(*p = b.p)) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(std::move(b)); return 0;
+  }
+  void drop(void* p) {
+    if (arena) { for (size_t i = 0; i < abufs.size(); i++) if (abufs[i] == p) { abufs.erase(abufs.begin() + (long)i); arena->give(p); return; } return; }
+    for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; } DevPool::give(p);
+  }
   void release() {                    // on the share's device, once its stream has drained; again: nothing
     if (hipSetDevice(device) != hipSuccess) return;
     if (s) (void)hipStreamSynchronize(s);
+    if (arena) for (void* p : abufs) arena->give(p);
+    abufs.clear();
     bufs.clear();
     s.reset();
   }
+  void release_keep_stream(Stream& to) { Stream keep = std::move(s); if (keep && hipSetDevice(device) == hipSuccess) (void)hipStreamSynchronize(keep); release(); to = std::move(keep); }
+  uint32_t nrows_given() const { uint32_t r = 0; for (auto& c : cands) r += c.kind == 0; return r; }
   ~DecShare() { release(); }
 };
 
@@ -965,6 +1021,16 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   if (ncand && hipMemcpy(S->cands.data(), d_cand, sizeof(Cand) * ncand, hipMemcpyDeviceToHost) != hipSuccess) { S->rc = CJS_E_HIP; return; }
   S->d2h += sizeof(Cand) * (size_t)ncand;
   std::sort(S->cands.begin(), S->cands.end(), [](const Cand& a, const Cand& b) { return a.bit < b.bit; });
+  S->ncand_seen = ncand;
+  if (S->row_limit != ~0u) {                                          // (a streaming step: see DecShare)
+    size_t a = 0, b;
+    while (a < S->cands.size() && S->cands[a].bit < S->row_from) a++;
+    uint32_t blocks = 0;
+    for (b = a; b < S->cands.size(); b++) if (S->cands[b].kind == 0 && ++blocks > S->row_limit) { S->cut_bit = S->cands[b].bit; break; }
+    S->cands.erase(S->cands.begin() + (long)b, S->cands.end());
+    S->cands.erase(S->cands.begin(), S->cands.begin() + (long)a);
+    ncand = (uint32_t)S->cands.size();
+  }
   if (J->eos && ncand && (rc = J->eos(S)) != 0) { S->rc = rc; return; }
   uint32_t* d_cend = nullptr;                                      // batch: per candidate, its input's end and block size (cend, then cdsz)
   if (nin && ncand) {                                              // the batch scan left each candidate's input in pad
@@ -1282,22 +1348,46 @@ int bz_block_verdict(const BlockOut& bo, uint32_t dbuf_size, uint64_t bitpos, bo
 // the restart header behind it.  at(pos, &kind, &bo) finds the candidate whose magic starts at bit
 // pos (false: none) with its decode result, end_bit in bits of the input; take(bo, pos) appends a good block to the chain.
 // Returns 0 or the first error the walk meets, its detail set.  mode 1 (Bunzip.table) does not test the stream CRC.
+//
+// `st` (a streaming decoder's step; nullptr: a walk of the whole input from its header on) holds the state the walk starts from
+// and is left with the state it stopped in.  With st->partial the n bytes are only the stream so far, and the walk stops
+// (st->stop != WALK_RUNS, return 0) in front of anything whose verdict the bytes still to come could change; with a row limit
+// (st->cut_bit) it stops at the first candidate that was not decoded.  The state is that of the point where the walk stands:
+// a later call with more bytes goes on from it.  take() sees *st as it was in front of the block it is given.
+enum { WALK_RUNS = 0, WALK_ENDED, WALK_NEED_MAGIC, WALK_NEED_CRC, WALK_NEED_HEADER, WALK_NO_ROW, WALK_BLOCK_OPEN, WALK_ERR_NEAR_END, WALK_OUT_BUDGET };
+struct WalkState {
+  uint64_t pos = 32; uint32_t crc = 0, dbuf_size = 0;            // dbuf_size 0: from the input's header byte
+  bool partial = false;
+  uint64_t cut_bit = ~0ull, extent = 0;                          // extent: bytes a block can span (partial)
+  int stop = WALK_RUNS;
+};
 template <typename Bytes, typename At, typename Take>
-int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_stride, bool timing, At at, Take take) {
+int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_stride, bool timing, At at, Take take, WalkState* st = nullptr) {
   auto read_bits = [&](uint64_t bit, int k) -> uint64_t { uint64_t v = 0; for (int i = 0; i < k; i++) { const uint64_t b = bit + i; v = (v << 1) | ((b >> 3) < n ? (in[b >> 3] >> (7 - (b & 7))) & 1u : 0u); } return v; };
-  uint32_t dbuf_size = 100000u * (uint32_t)(in[3] - '0');         // of the member stream being walked
-  uint64_t pos = 32; uint32_t stream_crc = 0;
+  WalkState whole;
+  if (!st) st = &whole;
+  const bool partial = st->partial;
+  uint32_t& dbuf_size = st->dbuf_size;                            // of the member stream being walked
+  if (!dbuf_size) dbuf_size = 100000u * (uint32_t)(in[3] - '0');
+  uint64_t& pos = st->pos; uint32_t& stream_crc = st->crc;
+  auto stop = [&](int why) { st->stop = why; return 0; };
   for (;;) {
-    if ((pos + 7) / 8 >= n) return 0;                            // inputStream.eof() (:1777)
+    if (partial ? pos + 48 > (uint64_t)n * 8 : (pos + 7) / 8 >= n) return stop(partial ? WALK_NEED_MAGIC : WALK_ENDED);      // inputStream.eof() (:1777)
+    if (pos >= st->cut_bit) return stop(WALK_NO_ROW);
     uint32_t kind = 0; BlockOut bo;
     if (!at(pos, &kind, &bo)) return CJS_E_NOT_BZIP_DATA;        // h !== WHOLEPI (:1438)
     if (kind == 0) {
       const int rc = bz_block_verdict(bo, dbuf_size, pos, timing);
+      // (partial) an error found less than a block's extent before the end may come from the zeros read past it; a good block
+      // read nothing behind its end-of-block code, unless that was cut off (end_bit is clamped to the end)
+      if (partial && rc && (pos >> 3) + st->extent > n) { clear_detail(); return stop(WALK_ERR_NEAR_END); }
       if (rc) return rc;
+      if (partial && bo.end_bit >= (uint64_t)n * 8) return stop(WALK_BLOCK_OPEN);
       take(bo, pos);
       stream_crc = bo.crc ^ ((stream_crc << 1) | (stream_crc >> 31));
       pos = bo.end_bit;
     } else {
+      if (partial && (pos + 80 > (uint64_t)n * 8 || (multistream && (pos + 80 + 7) / 8 + 4 > n))) return stop(pos + 80 > (uint64_t)n * 8 ? WALK_NEED_CRC : WALK_NEED_HEADER);
       const uint32_t target = (uint32_t)read_bits(pos + 48, 32);
       pos += 80;
       if ((pos + 7) / 8 > n) pos = (uint64_t)n * 8;
@@ -1307,7 +1397,7 @@ int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_st
         return CJS_E_DATA_ERROR;
       }
       const uint64_t byte = (pos + 7) / 8;
-      if (!multistream || byte >= n) return 0;
+      if (!multistream || byte >= n) return stop(WALK_ENDED);
       // _start_bunzip again, byte aligned (:1787-1792)
       if (byte + 4 > n || in[byte] != 'B' || in[byte + 1] != 'Z' || in[byte + 2] != 'h') { set_detail("bad magic"); return CJS_E_NOT_BZIP_DATA; }
       const int lv = in[byte + 3] - '0';
@@ -1974,3 +2064,286 @@ extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
+
+// ---------------------------------------------------------------- streaming decode (cjs_bzip2_dec_*)
+// The phases above over a sliding window of the stream.  The decoder keeps the stream bytes from the carry point on (host copy;
+// uploaded per step at their absolute byte offset, so the dword phase holds), the walk state (WalkState: bit position, folded
+// stream CRC, the member's block size) and one output buffer of out_bytes.  A step: phase A over the window with rows for the
+// first R block candidates at the walk position; bz_walk resumed from the kept state, stopping in front of whatever the bytes
+// still to come could change; phase B over the chain; the chain cut to the output budget (the walk state rolled back to the first
+// block not emitted); phase C into the device output buffer and one D2H.  All device scratch comes from the decoder's DecArena.
+// Synchronous: no worker thread.  See DESIGN.md §6f.
+namespace {
+constexpr size_t DEC_DEFAULT_CHUNK = (size_t)64 << 20, DEC_DEFAULT_OUT = (size_t)256 << 20;      // DESIGN.md §6f (placeholders, UNMEASURED)
+constexpr size_t DEC_MIN_CHUNK = (size_t)64 << 10, DEC_MAX_CHUNK = (size_t)1 << 30;
+constexpr uint64_t dec_extent(uint32_t tt_stride) { return (uint64_t)tt_stride * 5 / 2 + 65536; }      // bunzip_core's share overlap
+const char* const WALK_WHY[] = {"runs", "end of stream", "block magic not all here", "stream crc not all here", "member header not all here", "candidate without a row",
+                                "block not all here", "error too near the end", "output budget"};
+struct WinBytes {                        // the window by absolute stream byte
+  const uint8_t* p; uint64_t off;
+  uint8_t operator[](uint64_t i) const { return p[i - off]; }
+};
+}  // namespace
+
+struct cjs_bz_dec {
+  int multistream = 0, device = -1;
+  size_t chunk = 0, out_req = 0;
+  bool eager = false, debug = false;
+  int rc = 0; char detail[192] = {0};      // first failure: every later call returns it
+  // input window: stream bytes [win_off, win_off + win_len); the first `seen` of them have been through a step
+  uint8_t* win = nullptr; size_t win_cap = 0, win_len = 0, seen = 0; uint64_t win_off = 0, written = 0;
+  bool win_pinned = false, finished = false, header_ok = false, ended = false, dev_ready = false;
+  int level = 0;                           // of the header; rows and blocks are sized for L = 9 with multistream
+  uint32_t tt_stride = 0, rows = 0;
+  WalkState W;
+  // output of the last step: held - held_pos bytes still to be read; then the pending verdict
+  size_t out_cap = 0, held = 0, held_pos = 0;
+  Pinned<uint8_t> h_out; DevMem<uint8_t> d_out;
+  int pend_rc = 0; char pend_detail[192] = {0};
+  DecArena arena; Stream s;
+  uint32_t steps = 0;
+  int fail(int code, const char* text) {
+    if (!rc) { rc = code; snprintf(detail, sizeof detail, "%s", text ? text : ""); }
+    clear_detail();
+    if (detail[0]) set_detail("%s", detail);
+    return rc;
+  }
+  ~cjs_bz_dec() {
+    int cur = 0;
+    if (dev_ready && hipGetDevice(&cur) == hipSuccess) {
+      RestoreDevice restore{cur};          // the caller's device stays current
+      if (hipSetDevice(device) == hipSuccess) {
+        if (s) (void)hipStreamSynchronize(s);
+        if (win_pinned) (void)hipHostUnregister(win);
+        s.reset(); h_out.reset(); d_out.reset(); arena.release();
+      }
+    }
+    free(win);
+  }
+};
+
+namespace {
+
+// _start_bunzip (:1408-1427) on the first four bytes: no device
+int dec_header(cjs_bz_dec* d) {
+  if (d->written < 4) return d->fail(CJS_E_NOT_BZIP_DATA, "bad magic");
+  const uint8_t* in = d->win;
+  if (in[0] != 'B' || in[1] != 'Z' || in[2] != 'h') return d->fail(CJS_E_NOT_BZIP_DATA, "bad magic");
+  d->level = in[3] - '0';
+  if (d->level < 1 || d->level > 9) return d->fail(CJS_E_NOT_BZIP_DATA, "level out of range");
+  const uint32_t L = d->multistream ? 9u : (uint32_t)d->level;      // later members cannot be seen ahead
+  d->tt_stride = 100000u * L;
+  d->out_cap = std::max<size_t>(d->out_req ? d->out_req : DEC_DEFAULT_OUT, (size_t)52 * d->tt_stride);
+  d->rows = (uint32_t)std::min<size_t>(65535, std::max<size_t>(1, d->out_cap / d->tt_stride));
+  d->W = WalkState{};
+  d->W.dbuf_size = 100000u * (uint32_t)d->level;
+  d->header_ok = true;
+  return 0;
+}
+
+int dec_device_init(cjs_bz_dec* d) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CJS_E_NO_DEVICE; }
+  if (d->device >= ndev) return CJS_E_INVALID_ARG;
+  if (d->device < 0 && hipGetDevice(&d->device) != hipSuccess) return CJS_E_NO_DEVICE;
+  CJS_HIP_TRY(hipSetDevice(d->device));
+  d->dev_ready = true;
+  CJS_HIP_TRY(hipStreamCreate(d->s.put()));
+  if (hipHostRegister(d->win, d->win_cap, hipHostRegisterDefault) == hipSuccess) d->win_pinned = true; else (void)hipGetLastError();
+  CJS_HIP_TRY(hipHostMalloc((void**)d->h_out.put(), d->out_cap));
+  CJS_TRY(d->d_out.alloc(d->out_cap + 256));
+  // rows ~10 B and inverse BWT ~24 B per byte of rows x block size, the window twice (upload + candidates)
+  return d->arena.init((size_t)28 * d->rows * ((size_t)d->tt_stride + 4096) + 2 * d->win_cap + ((size_t)16 << 20));
+}
+
+int dec_step(cjs_bz_dec* d) {
+  int cur = 0;
+  if (!d->dev_ready) {
+    const bool had = hipGetDevice(&cur) == hipSuccess;
+    const int rc = dec_device_init(d);
+    if (rc) { if (had) (void)hipSetDevice(cur); return rc; }
+    if (had) (void)hipSetDevice(cur);
+  }
+  if (hipGetDevice(&cur) != hipSuccess) return CJS_E_NO_DEVICE;
+  RestoreDevice restore{cur};
+  CJS_HIP_TRY(hipSetDevice(d->device));
+  const bool final = d->finished, was_full = d->win_len == d->win_cap;
+  const uint32_t spills0 = d->arena.spills;
+  const uint64_t n = d->win_off + d->win_len, pos0 = d->W.pos;
+  const size_t len0 = d->win_len;
+  DecJob J; J.n = (size_t)n; J.mode = 0; J.timing = env_debug(); J.tt_stride = d->tt_stride; J.batch = true;
+  DecShare S; S.device = d->device; S.arena = &d->arena; S.s = std::move(d->s);
+  struct Back { cjs_bz_dec* d; DecShare& S; ~Back() { S.release_keep_stream(d->s); } } back{d, S};      // on every path out
+  S.lo = S.up_lo = d->win_off; S.hi = S.up_hi = n; S.row_limit = d->rows; S.row_from = d->W.pos;
+  J.upload = [d](DecShare* sh, uint8_t* dst) {
+    if (d->win_len && hipMemcpyAsync(dst, d->win, d->win_len, hipMemcpyHostToDevice, sh->s) != hipSuccess) return (int)CJS_E_HIP;
+    sh->h2d += d->win_len;
+    return 0;
+  };
+  guarded(S.rc, [&] { dec_phase_a(&J, &S); });
+  if (S.rc) return S.rc;
+  // ---- the walk, resumed
+  WalkState& W = d->W;
+  W.partial = !final; W.cut_bit = S.cut_bit; W.extent = dec_extent(d->tt_stride); W.stop = WALK_RUNS;
+  std::vector<WalkState> before;           // the state in front of each chain block
+  long last = -1;
+  clear_detail();
+  int wrc = bz_walk(WinBytes{d->win, d->win_off}, (size_t)n, d->multistream, 0, d->tt_stride, J.timing,
+                    [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
+                      const auto it = std::lower_bound(S.cands.begin(), S.cands.end(), pos, [](const Cand& c, uint64_t b) { return c.bit < b; });
+                      if (it == S.cands.end() || it->bit != pos) return false;
+                      last = (long)(it - S.cands.begin());
+                      *kind = it->kind; *bo = S.bos[(size_t)last];
+                      return true;
+                    },
+                    [&](const BlockOut& bo, uint64_t) {
+                      IbBlock ib; ib.tt = S.tt_ptr[(size_t)last]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
+                      J.chain.push_back(ib); before.push_back(W);
+                    },
+                    &W);
+  char wdetail[192];
+  snprintf(wdetail, sizeof wdetail, "%s", cjs_last_error_detail());
+  clear_detail();
+  // ---- phase B over the chain, then the cut to the output budget
+  size_t nb = J.chain.size();
+  const size_t walked = nb;
+  J.out_off.assign(nb + 1, 0);
+  if (nb) {
+    S.c0 = 0; S.c1 = nb;
+    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
+    if (S.rc) return S.rc;
+    for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
+    if (J.out_off[1] > d->out_cap) return CJS_E_UNSUPPORTED;      // cannot happen: out_cap >= a block's largest expansion
+    size_t k = 1;
+    while (k < nb && J.out_off[k + 1] <= d->out_cap) k++;
+    if (k < nb) {                          // block k and what the walk met behind it: the next step's
+      const WalkState& b = before[k];
+      W.pos = b.pos; W.crc = b.crc; W.dbuf_size = b.dbuf_size; W.stop = WALK_OUT_BUDGET;
+      wrc = 0;
+      J.chain.resize(k); J.out_off.resize(k + 1); S.c1 = nb = k;
+    }
+    // ---- phase C: a CRC verdict per block; the first bad block in chain order comes before the walk's error
+    J.dev_out = d->d_out; J.host = nullptr; J.crc_got.assign(nb, 0);
+    S.rc = 0;
+    guarded(S.rc, [&] { dec_phase_c(&J, &S); });
+    if (S.rc) return S.rc;
+  }
+  size_t bad = 0;
+  while (bad < nb && J.crc_got[bad] == J.chain[bad].crc) bad++;
+  const size_t deliver = (size_t)J.out_off[bad];
+  if (deliver) { CJS_HIP_TRY(hipMemcpyAsync(d->h_out, d->d_out, deliver, hipMemcpyDeviceToHost, S.s)); CJS_HIP_TRY(hipStreamSynchronize(S.s)); S.d2h += deliver; }
+  d->held = deliver; d->held_pos = 0;
+  if (bad < nb) {                          // Bad block CRC (:1756-1761): nothing of the block is delivered
+    d->pend_rc = CJS_E_DATA_ERROR;
+    snprintf(d->pend_detail, sizeof d->pend_detail, "Bad block CRC (got %x expected %x)", J.crc_got[bad], J.chain[bad].crc);
+  } else if (wrc) {
+    d->pend_rc = wrc;
+    snprintf(d->pend_detail, sizeof d->pend_detail, "%s", wdetail);
+  } else if (W.stop == WALK_ENDED) d->ended = true;
+  // ---- the carry: the window from the walk position's byte on
+  if (!d->pend_rc) {
+    const uint64_t keep_from = d->ended ? n : std::min<uint64_t>(W.pos >> 3, n);
+    const size_t gone = (size_t)(keep_from - d->win_off);
+    if (gone) memmove(d->win, d->win + gone, d->win_len - gone);
+    d->win_off = keep_from; d->win_len -= gone;
+  }
+  d->seen = d->win_len;
+  if (d->debug)
+    fprintf(stderr, "[cjs dec step] %u: window %zu B at byte %llu, carry %zu B, candidates %u rows %u, blocks walked %zu emitted %zu, %zu B out, walk stopped: %s%s%s\n",
+            d->steps, len0, (unsigned long long)(n - len0), d->win_len, S.ncand_seen, S.nrows_given(), walked, std::min(bad, nb), deliver,
+            d->pend_rc ? "error" : WALK_WHY[W.stop], final ? " (final)" : "", d->arena.spills != spills0 ? " [arena spilled]" : "");
+  d->steps++;
+  // (cannot happen: a full window holds a whole block behind the walk position, and the final steps end or emit)
+  if (!d->pend_rc && !d->ended && (final ? W.pos == pos0 : was_full && d->win_len == d->win_cap)) return CJS_E_UNSUPPORTED;
+  return 0;
+}
+
+// A full window always has fresh bytes: the step that last ran on a full window either moved the walk position, and with it the
+// carry point (a block, an end-of-stream record or a member header: whole bytes each), so the window was no longer full and only
+// a _write can have filled it again; or it failed the decoder (CJS_E_UNSUPPORTED in dec_step).  So a _write that took nothing is
+// always followed by a step.
+bool dec_step_due(const cjs_bz_dec* d) {
+  if (d->ended || d->pend_rc) return false;
+  if (d->finished) return true;
+  const size_t fresh = d->win_len - d->seen;
+  return d->eager ? fresh > 0 : (fresh >= d->chunk || (d->win_len == d->win_cap && fresh > 0));
+}
+
+}  // namespace
+
+extern "C" int cjs_bzip2_dec_create(cjs_bz_dec** out, int multistream, size_t chunk_bytes, size_t out_bytes, const cjs_opts* opts) {
+  if (!out) return CJS_E_INVALID_ARG;
+  *out = nullptr;
+  CJS_GUARD_BEGIN
+  cjs_bz_dec* d = new cjs_bz_dec();
+  d->multistream = multistream ? 1 : 0;
+  if (!chunk_bytes) {                      // the default; CJS_DEC_CHUNK_BYTES replaces it (callers without a chunk argument: the JS fronts, cli.js)
+    const char* env = getenv("CJS_DEC_CHUNK_BYTES");
+    chunk_bytes = env ? (size_t)strtoull(env, nullptr, 10) : 0;
+    if (!chunk_bytes) chunk_bytes = DEC_DEFAULT_CHUNK;
+  }
+  d->chunk = std::min(std::max(chunk_bytes, DEC_MIN_CHUNK), DEC_MAX_CHUNK);
+  d->out_req = out_bytes;
+  d->device = Opts(opts).device;
+  const char* eager = getenv("CJS_DEC_STREAM_EAGER");
+  d->eager = eager && eager[0] == '1';
+  d->debug = getenv("CJS_DEBUG") != nullptr;
+  d->win_cap = d->chunk + (size_t)dec_extent(900000u);
+  *out = d;
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_bzip2_dec_write(cjs_bz_dec* d, const uint8_t* in, size_t n, size_t* taken) {
+  if (taken) *taken = 0;
+  if (!d) return CJS_E_INVALID_ARG;
+  if (d->rc) return d->fail(d->rc, nullptr);
+  if (!taken || (!in && n) || d->finished) return d->fail(CJS_E_INVALID_ARG, nullptr);
+  if (d->ended || d->pend_rc) { *taken = n; return 0; }      // the end has been decided: the reference never reads these bytes
+  if (!n) return 0;
+  if (!d->win && !(d->win = (uint8_t*)malloc(d->win_cap))) return d->fail(CJS_E_OUT_OF_MEMORY, nullptr);
+  const size_t take = std::min(n, d->win_cap - d->win_len);
+  memcpy(d->win + d->win_len, in, take);
+  d->win_len += take; d->written += take;
+  *taken = take;
+  return 0;
+}
+
+extern "C" int cjs_bzip2_dec_finish(cjs_bz_dec* d) {
+  if (!d) return CJS_E_INVALID_ARG;
+  if (d->rc) return d->fail(d->rc, nullptr);
+  d->finished = true;
+  return 0;
+}
+
+extern "C" int cjs_bzip2_dec_read(cjs_bz_dec* d, uint8_t* out, size_t cap, size_t* got) {
+  if (got) *got = 0;
+  if (!d) return CJS_E_INVALID_ARG;
+  if (d->rc) return d->fail(d->rc, nullptr);
+  if (!got || (!out && cap)) return d->fail(CJS_E_INVALID_ARG, nullptr);
+  CJS_GUARD_BEGIN
+  for (;;) {
+    if (d->held_pos < d->held) {
+      const size_t take = std::min(cap, d->held - d->held_pos);
+      if (take) memcpy(out, d->h_out.p + d->held_pos, take);
+      d->held_pos += take;
+      *got = take;
+      return 0;
+    }
+    if (d->pend_rc) return d->fail(d->pend_rc, d->pend_detail);      // every byte in front of it has been read
+    if (d->ended) return 0;
+    if (!d->header_ok) {
+      if (d->written < 4 && !d->finished) return 0;
+      CJS_TRY(dec_header(d));
+    }
+    if (!dec_step_due(d)) return 0;
+    if (!d->win && !(d->win = (uint8_t*)malloc(d->win_cap))) return d->fail(CJS_E_OUT_OF_MEMORY, nullptr);
+    const int rc = dec_step(d);
+    if (rc) return d->fail(rc, cjs_last_error_detail());
+  }
+  CJS_GUARD_END(d->fail(CJS_E_OUT_OF_MEMORY, nullptr), d->fail(CJS_E_HIP, nullptr))
+}
+
+extern "C" int cjs_bzip2_dec_done(const cjs_bz_dec* d) { return d && !d->rc && d->ended && d->held_pos == d->held ? 1 : 0; }
+
+extern "C" void cjs_bzip2_dec_destroy(cjs_bz_dec* d) { delete d; }

@@ -31,7 +31,11 @@ function rethrow(e) {
 function isStream(x, method) {
   return x !== null && typeof x === 'object' && method in x && !(x instanceof Uint8Array) && !Array.isArray(x);
 }
-var IN_PIECE = 4 << 20, OUT_PIECE = 4 << 20;
+var IN_PIECE = 4 << 20, OUT_PIECE = 4 << 20, FEED_PIECE = 64 << 10;
+// Output budget of the decoder behind decompressFile and cli.js -d: a quarter of the library's default.  The decoder's device
+// scratch is proportional to it (~2 GB at 64 MiB for a level-9 stream, held even for a small file), and a front has no caller
+// who could size it.
+var FRONT_OUT_BYTES = 64 << 20;
 // up to buf.length bytes of the stream into buf; 0 at its end
 function fillFrom(inStream, buf) {
   if (typeof inStream.read === 'function') { var got = inStream.read(buf, 0, buf.length); return got > 0 ? got : 0; }
@@ -74,6 +78,48 @@ function compressPiecewise(inStream, inIsStream, outStream, outIsStream, level) 
   return common.deliver(result, outStream);
 }
 
+// decompressFile with a stream object on either side: the .bz2 stream is fed to the streaming decoder piece by piece and the
+// decoded bytes are drained as they appear (a pull model: the decoder takes what its window has room for, reading runs the GPU
+// steps).  A stream that fails throws the reference's error once every block in front of the failure has reached the sink.
+function decompressPiecewise(inStream, inIsStream, outStream, outIsStream, multistream) {
+  var a = common.addon(), dec = null, pieces = [], total = 0, obuf = new Uint8Array(OUT_PIECE);
+  function drain() {
+    var got;
+    while ((got = a.bzip2DecRead(dec, obuf)) > 0) {
+      if (outIsStream) { writeTo(outStream, obuf.subarray(0, got)); } else { pieces.push(obuf.slice(0, got)); total += got; }
+    }
+  }
+  // Fed in pieces of the smallest chunk the decoder can have, with a drain behind each: a step then runs as soon as chunk_bytes
+  // wait, whatever the chunk is, and the output never lags the input by more than that.  A short write means the window is full:
+  // after a drain the next one takes at least a byte.
+  function feed(piece) {
+    while (piece.length > 0) {
+      var part = piece.subarray(0, Math.min(piece.length, FEED_PIECE));
+      piece = piece.subarray(a.bzip2DecWrite(dec, part));
+      drain();
+    }
+  }
+  try {
+    dec = a.bzip2DecCreate(multistream ? 1 : 0, 0, FRONT_OUT_BYTES);
+    if (inIsStream) {
+      var buf = new Uint8Array(IN_PIECE), n;
+      while ((n = fillFrom(inStream, buf)) > 0) { feed(buf.subarray(0, n)); }
+    } else {
+      var bytes = common.coerceInput(inStream).bytes;
+      for (var off = 0; off < bytes.length; off += IN_PIECE) { feed(bytes.subarray(off, Math.min(bytes.length, off + IN_PIECE))); }
+    }
+    a.bzip2DecFinish(dec);
+    drain();
+  } catch (e) { rethrow(e); } finally { if (dec) { a.bzip2DecDestroy(dec); } }
+  if (outIsStream) {
+    if (outStream.flush) { outStream.flush(); }
+    return outStream;
+  }
+  var result = new Uint8Array(total), o = 0;
+  pieces.forEach(function (p) { result.set(p, o); o += p.length; });
+  return common.deliver(result, outStream);
+}
+
 var Bzip2 = Object.create(null);
 Bzip2.compressFile = function (inStream, outStream, props) {
   var level = 9;
@@ -96,6 +142,8 @@ Bzip2.compressFiles = function (inStreams, props) {
   try { return common.addon().bzip2CompressBatch(inputs, level); } catch (e) { rethrow(e); }
 };
 Bzip2.decompressFile = function (inStream, outStream, multistream) {
+  var inIsStream = isStream(inStream, 'readByte'), outIsStream = isStream(outStream, 'writeByte');
+  if (inIsStream || outIsStream) { return decompressPiecewise(inStream, inIsStream, outStream, outIsStream, multistream); }
   var input = common.coerceInput(inStream);
   var result;
   try { result = common.addon().bzip2Decompress(input.bytes, multistream ? 1 : 0); } catch (e) { rethrow(e); }

@@ -30,6 +30,12 @@ struct Api {
   size_t (*enc_pending)(const cjs_bz_enc*) = nullptr;
   int (*enc_read)(cjs_bz_enc*, uint8_t*, size_t, size_t*) = nullptr;
   void (*enc_destroy)(cjs_bz_enc*) = nullptr;
+  int (*dec_create)(cjs_bz_dec**, int, size_t, size_t, const cjs_opts*) = nullptr;
+  int (*dec_write)(cjs_bz_dec*, const uint8_t*, size_t, size_t*) = nullptr;
+  int (*dec_finish)(cjs_bz_dec*) = nullptr;
+  int (*dec_read)(cjs_bz_dec*, uint8_t*, size_t, size_t*) = nullptr;
+  int (*dec_done)(const cjs_bz_dec*) = nullptr;
+  void (*dec_destroy)(cjs_bz_dec*) = nullptr;
   void (*free_)(void*) = nullptr;
   const char* (*strerror_)(int) = nullptr;
   const char* (*detail_)(void) = nullptr;
@@ -59,6 +65,8 @@ bool load_api() {
   SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch") SYM(bzip2_decompress_batch, "cjs_bzip2_decompress_batch")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
+  SYM(dec_create, "cjs_bzip2_dec_create") SYM(dec_write, "cjs_bzip2_dec_write") SYM(dec_finish, "cjs_bzip2_dec_finish")
+  SYM(dec_read, "cjs_bzip2_dec_read") SYM(dec_done, "cjs_bzip2_dec_done") SYM(dec_destroy, "cjs_bzip2_dec_destroy")
   SYM(free_, "cjs_free") SYM(strerror_, "cjs_strerror") SYM(detail_, "cjs_last_error_detail") SYM(device_count, "cjs_device_count") SYM(version, "cjs_version") SYM(trim, "cjs_trim")
 #undef SYM
   return true;
@@ -372,6 +380,88 @@ napi_value enc_destroy(napi_env env, napi_callback_info info) {
   napi_value v; napi_get_undefined(env, &v); return v;
 }
 
+// ---- streaming decoder (cjs_bzip2_dec_*), a pull model: bzip2DecCreate(multistream, chunkBytes, outBytes) -> handle;
+// bzip2DecWrite(handle, bytes) -> number of bytes taken (may be 0: read until empty, then write again); bzip2DecFinish(handle);
+// bzip2DecRead(handle, buf) -> number of decoded bytes put at the front of the Uint8Array buf (0: write more, or after finish the
+// end; this call runs the GPU steps and throws the stream's error once the bytes in front of it have been read);
+// bzip2DecDone(handle) -> boolean; bzip2DecDestroy(handle).  The handle's finalizer destroys a decoder still open.
+struct DecHandle { cjs_bz_dec* d = nullptr; };
+void finalize_dec(napi_env, void* data, void*) {
+  DecHandle* h = (DecHandle*)data;
+  if (h->d && api.dec_destroy) api.dec_destroy(h->d);
+  delete h;
+}
+DecHandle* dec_arg(napi_env env, napi_callback_info info, size_t want, napi_value* argv) {
+  size_t argc = want;
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  void* p = nullptr;
+  if (argc < want || napi_get_value_external(env, argv[0], &p) != napi_ok || !p || !((DecHandle*)p)->d) {
+    napi_throw_type_error(env, nullptr, "expected an open decoder handle");
+    return nullptr;
+  }
+  return (DecHandle*)p;
+}
+napi_value dec_create(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  int32_t multi = 0; double chunk = 0, out_bytes = 0;
+  if (argc >= 1) napi_get_value_int32(env, argv[0], &multi);
+  if (argc >= 2) napi_get_value_double(env, argv[1], &chunk);
+  if (argc >= 3) napi_get_value_double(env, argv[2], &out_bytes);
+  DecHandle* h = new DecHandle();
+  const int rc = api.dec_create(&h->d, multi, chunk > 0 ? (size_t)chunk : 0, out_bytes > 0 ? (size_t)out_bytes : 0, nullptr);
+  if (rc != 0) { delete h; return throw_code(env, rc); }
+  napi_value v;
+  if (napi_create_external(env, h, finalize_dec, nullptr, &v) != napi_ok) { api.dec_destroy(h->d); delete h; napi_throw_error(env, nullptr, "cannot create the decoder handle"); return nullptr; }
+  return v;
+}
+napi_value dec_write(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  DecHandle* h = dec_arg(env, info, 2, argv);
+  if (!h) return nullptr;
+  const uint8_t* p = nullptr; size_t n = 0, taken = 0;
+  if (!get_bytes(env, argv[1], &p, &n)) { napi_throw_type_error(env, nullptr, "expected a Uint8Array or Buffer"); return nullptr; }
+  const int rc = api.dec_write(h->d, n ? p : nullptr, n, &taken);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value v; napi_create_double(env, (double)taken, &v); return v;
+}
+napi_value dec_finish(napi_env env, napi_callback_info info) {
+  napi_value argv[1];
+  DecHandle* h = dec_arg(env, info, 1, argv);
+  if (!h) return nullptr;
+  const int rc = api.dec_finish(h->d);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value v; napi_get_undefined(env, &v); return v;
+}
+napi_value dec_read(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  DecHandle* h = dec_arg(env, info, 2, argv);
+  if (!h) return nullptr;
+  const uint8_t* p = nullptr; size_t cap = 0, got = 0;
+  if (!get_bytes(env, argv[1], &p, &cap)) { napi_throw_type_error(env, nullptr, "expected a Uint8Array or Buffer to read into"); return nullptr; }
+  const int rc = api.dec_read(h->d, cap ? const_cast<uint8_t*>(p) : nullptr, cap, &got);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value v; napi_create_double(env, (double)got, &v); return v;
+}
+napi_value dec_done(napi_env env, napi_callback_info info) {
+  napi_value argv[1];
+  DecHandle* h = dec_arg(env, info, 1, argv);
+  if (!h) return nullptr;
+  napi_value v; napi_get_boolean(env, api.dec_done(h->d) == 1, &v); return v;
+}
+napi_value dec_destroy(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  void* p = nullptr;
+  if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
+    DecHandle* h = (DecHandle*)p;
+    if (h->d && api.dec_destroy) api.dec_destroy(h->d);
+    h->d = nullptr;
+  }
+  napi_value v; napi_get_undefined(env, &v); return v;
+}
+
 napi_value device_count(napi_env env, napi_callback_info) {
   if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
   napi_value v; napi_create_int32(env, api.device_count(), &v); return v;
@@ -403,6 +493,12 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2EncPending", nullptr, enc_pending, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncRead", nullptr, enc_read, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncDestroy", nullptr, enc_destroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecCreate", nullptr, dec_create, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecWrite", nullptr, dec_write, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecFinish", nullptr, dec_finish, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecRead", nullptr, dec_read, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecDone", nullptr, dec_done, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2DecDestroy", nullptr, dec_destroy, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"version", nullptr, version, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"trim", nullptr, trim, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -95,6 +95,13 @@ if (opt.compress && type === 'bzip2') {
   if (outFd !== 1) { fs.closeSync(outFd); }
   process.exit(0);
 }
+if (opt.decompress && type === 'bzip2' && opt.block < 0) {
+  // streaming as well: the stream is read in pieces and the decoded bytes are written as they appear, file and pipe alike
+  try { fronts.bzip2.decompressFile(fdInput(inFd), fdOutput(outFd)); } catch (e) { fail(String(e && e.message ? e.message : e)); }
+  if (inFd !== 0) { fs.closeSync(inFd); }
+  if (outFd !== 1) { fs.closeSync(outFd); }
+  process.exit(0);
+}
 var input = readAll(inFd), result;
 try {
   if (opt.decompress) {

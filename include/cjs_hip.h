@@ -154,6 +154,41 @@ int cjs_bzip2_enc_finish(cjs_bz_enc *e);
 size_t cjs_bzip2_enc_pending(const cjs_bz_enc *e);
 int cjs_bzip2_enc_read(cjs_bz_enc *e, uint8_t *out, size_t cap, size_t *got);
 void cjs_bzip2_enc_destroy(cjs_bz_enc *e);
+/* Streaming form of cjs_bzip2_decompress: the .bz2 stream is written in pieces of any size, the decoded bytes are read in pieces
+ * of any size, and the bytes read, in order, are exactly what cjs_bzip2_decompress(all written bytes, multistream) returns; a
+ * stream that fails fails with the same code and the same cjs_last_error_detail().  The device and host memory a decoder holds
+ * depend on chunk_bytes, out_bytes and the stream's level, never on the bytes written or produced.
+ * A PULL model, unlike the encoder (a block of ~45 stream bytes can decode to 46 MB): _write only copies into the input window,
+ * as much as it has room for (*taken, which may be 0), and never starts GPU work.  _read hands out bytes still held from the
+ * last step; when none are left it runs steps while one is due and hands out from the first that produced bytes.  *got == 0
+ * with return code 0 means "write more, or finish"; after _finish it means the stream has ended (_done returns 1).
+ * PROGRESS: after a _write that took fewer than n bytes, calling _read until *got == 0 guarantees that the next _write takes at
+ * least one byte.  Once the stream's end has been decided (the end-of-stream of a non-multistream decoder, or a failure that is
+ * still waiting behind unread bytes) later writes are taken and dropped: the reference never reads those bytes.
+ * A step is due when chunk_bytes new stream bytes wait (0 = the default, 64 MiB, or CJS_DEC_CHUNK_BYTES; clamped to 64 KiB ..
+ * 1 GiB), when the input window (chunk_bytes + one block's extent) is full, or after _finish.  It decodes the whole blocks the
+ * window holds, at most out_bytes of output (0 = the default, 256 MiB; raised to one block's largest expansion, 52 x 100000 x L
+ * with L the header's level, 9 with multistream).  Held: the window on the host (pinned) and one upload of it on the device, one
+ * output buffer of out_bytes on each side, and one device scratch arena of ~28 B per byte of (out_bytes / (100000 L)) blocks.
+ * Stream errors come from _read, and only once every byte in front of the failing point has been read: exactly the decoded
+ * bytes of all blocks in front of the first failing block (for an error of the chain walk -- bad magic, bad stream CRC, initial
+ * position out of bounds -- the blocks in front of where the walk stopped).  Nothing of a failing block is delivered: the
+ * reference's output stream has also seen the bytes of a block whose CRC then fails (it writes before it checks); this decoder
+ * withholds them.  The verdicts of the first four bytes (bad magic, level out of range, fewer than four bytes at _finish) are
+ * decided on the host, with no device.  NULL d, NULL in with n > 0, NULL taken, NULL got, NULL out with cap > 0 and _write after
+ * _finish: CJS_E_INVALID_ARG at once, before the device is touched (the device is first touched by the first _read that runs a
+ * step).  After any failing call the decoder stays failed: every later call returns the same code; _destroy is always safe.
+ * opts->device is honoured, n_devices and stats are ignored.  One decoder is driven by one thread at a time; decoders are
+ * independent of each other and of the pools cjs_bzip2_decompress keeps.  Synchronous: no worker thread.
+ * CJS_DEBUG (read at _create): one "[cjs dec step]" line per step on stderr.  CJS_DEC_STREAM_EAGER=1 (read at _create; for
+ * tests): a step is due on whatever has been written. */
+typedef struct cjs_bz_dec cjs_bz_dec;
+int cjs_bzip2_dec_create(cjs_bz_dec **d, int multistream, size_t chunk_bytes, size_t out_bytes, const cjs_opts *opts);
+int cjs_bzip2_dec_write(cjs_bz_dec *d, const uint8_t *in, size_t n, size_t *taken);
+int cjs_bzip2_dec_finish(cjs_bz_dec *d);
+int cjs_bzip2_dec_read(cjs_bz_dec *d, uint8_t *out, size_t cap, size_t *got);
+int cjs_bzip2_dec_done(const cjs_bz_dec *d);     /* 1: the stream has ended and every byte has been read */
+void cjs_bzip2_dec_destroy(cjs_bz_dec *d);
 void cjs_free(void *p);
 /* Memory kept between calls (allocating and freeing multi-GB scratch costs more than compressing 100 MB):
  * cjs_bzip2_compress keeps its per-device workspace (~70 B per input byte of the largest call so far) and staging buffers;
