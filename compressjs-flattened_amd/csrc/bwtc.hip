@@ -259,6 +259,14 @@ __global__ __launch_bounds__(64) void bwtc_defsum(MtfBufs mb, uint64_t* __restri
   nsteps[blk] = n;
 }
 
+// the model evaluation of `nb` blocks as the compressor launches it: one workgroup per block, DefSumModel on one lane of one
+// wave (levels 1-5), FenwickModel on FP_WAVES waves (levels 6-9).  Reads mb.A / a_stride / asz / npos only.
+static int bwtc_model_launch(hipStream_t s, bool fast, const MtfBufs& mb, uint32_t nb, uint64_t* d_steps, size_t step_stride, uint32_t* d_nsteps) {
+  if (fast) hipLaunchKernelGGL(bwtc_defsum, dim3(nb), dim3(64), 0, s, mb, d_steps, step_stride, d_nsteps);
+  else hipLaunchKernelGGL(bwtc_fenwick_par, dim3(nb), dim3(64 * FP_WAVES), 0, s, mb, d_steps, step_stride, d_nsteps);
+  return hipGetLastError() != hipSuccess ? (int)CJS_E_HIP : 0;
+}
+
 }  // namespace cjs
 
 // ---------------------------------------------------------------- host: framing + serial range coder
@@ -492,6 +500,24 @@ struct HostCoder {
     out.resize(len);
   }
 };
+// reciprocals floor(2^64 / tot) + 1 for every total a step can carry (17 bits); tot < 2 keeps the division
+const uint64_t* rcp_table() {
+  static std::vector<uint64_t> rcp;
+  static std::once_flag rcp_once;
+  std::call_once(rcp_once, [] { rcp.assign(1u << 17, 0ull); for (uint32_t t = 2; t < (1u << 17); t++) rcp[t] = (uint64_t)(((unsigned __int128)1 << 64) / t) + 1; });
+  return rcp.data();
+}
+// the serial tail: one list of model steps through the coder.  The compressor's block loop and cjs_stage_bwtc_code
+// both run THIS loop (always inlined: the compressor's copy is the loop it had in place)
+__attribute__((always_inline)) inline void code_steps(HostCoder& coder, const uint64_t* steps, uint32_t ns, const uint64_t* rc_tab) {
+  for (uint32_t i = 0; i < ns; i++) {
+    const uint64_t st = steps[i];
+    const uint32_t sy = (uint32_t)(st & 0xFFFF), lt = (uint32_t)((st >> 16) & 0xFFFF), tot = (uint32_t)((st >> 32) & 0x1FFFF);
+    if (st & STEP_SHIFT_FLAG) coder.shift(sy, lt, (int)tot);
+    else if (tot >= 2) coder.freq_rcp(sy, lt, tot, rc_tab);
+    else coder.freq(sy, lt, tot);
+  }
+}
 int fls32(uint32_t v) { int r = 0; while (v) { r++; v >>= 1; } return r; }
 void nomodel(HostCoder& c, int bits, uint32_t sym) { for (int i = bits - 1; i >= 0; i--) c.shift(1, (sym >> i) & 1, 1); }   // :1281-1287
 void logdist(HostCoder& c, int block_size, uint32_t d) {                                                                   // :1241-1253
@@ -595,11 +621,7 @@ void bwtc_batch_body(BwtcJob* J, BwtcBatch* B) {
   if (!rc && hipMemcpyAsync(d_len, lens.data(), 4 * (size_t)cnt, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
   if (!rc) rc = bwt_run(s, G.bw, d_T, cnt, bs, n_last, false, d_U, d_pidx, nullptr);
   if (!rc) rc = mtf_run(s, mw, d_U, cnt, d_len);
-  if (!rc) {
-    if (J->fast) hipLaunchKernelGGL(bwtc_defsum, dim3(cnt), dim3(64), 0, s, mw.b, B->d_steps, B->step_stride, d_nsteps);
-    else hipLaunchKernelGGL(bwtc_fenwick_par, dim3(cnt), dim3(64 * FP_WAVES), 0, s, mw.b, B->d_steps, B->step_stride, d_nsteps);
-    if (hipGetLastError() != hipSuccess) rc = CJS_E_HIP;
-  }
+  if (!rc) rc = bwtc_model_launch(s, J->fast, mw.b, cnt, B->d_steps, B->step_stride, d_nsteps);
   B->pidx.resize(cnt); B->asz.resize(cnt); B->nsteps.resize(cnt); B->alist.resize((size_t)cnt * 256);
   if (!rc && hipMemcpyAsync(B->pidx.data(), d_pidx, 4 * (size_t)cnt, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
   if (!rc && hipMemcpyAsync(B->asz.data(), mw.b.asz, 4 * (size_t)cnt, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
@@ -681,10 +703,7 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
       }
     } wk{J};
     for (auto& B : J.batches) wk.th.run(B.rc, [&J, &B] { bwtc_batch_worker(&J, &B); });     // (the worker's own guard leaves the outer one nothing to catch)
-    // reciprocals floor(2^64 / tot) + 1 for every total a step can carry (17 bits); tot < 2 keeps the division
-    static std::vector<uint64_t> rcp;
-    static std::once_flag rcp_once;
-    std::call_once(rcp_once, [] { rcp.assign(1u << 17, 0ull); for (uint32_t t = 2; t < (1u << 17); t++) rcp[t] = (uint64_t)(((unsigned __int128)1 << 64) / t) + 1; });
+    const uint64_t* rc_tab = rcp_table();
     // the steps of block k+1 travel (pinned buffer, copy stream of its batch) while block k goes through the coder
     const size_t step_stride = 2 * MtfWork::a_stride_for(bs);
     if (hipHostMalloc((void**)h_buf[0].put(), 8 * step_stride, hipHostMallocPortable) != hipSuccess || hipHostMalloc((void**)h_buf[1].put(), 8 * step_stride, hipHostMallocPortable) != hipSuccess) rc = CJS_E_HIP;
@@ -741,16 +760,7 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
         else coder.freq(1, tree[i] == 0 ? 0u : tree[i] == full ? 2u : 1u, 3);
       }
       if (hipSetDevice(pending_dev[k & 1]) != hipSuccess || hipEventSynchronize(pending[k & 1]) != hipSuccess) { rc = CJS_E_HIP; break; }
-      const uint64_t* h_steps = h_buf[k & 1];
-      const uint64_t* rc_tab = rcp.data();
-      const uint32_t ns = B.nsteps[r];
-      for (uint32_t i = 0; i < ns; i++) {                             // the serial tail
-        const uint64_t st = h_steps[i];
-        const uint32_t sy = (uint32_t)(st & 0xFFFF), lt = (uint32_t)((st >> 16) & 0xFFFF), tot = (uint32_t)((st >> 32) & 0x1FFFF);
-        if (st & STEP_SHIFT_FLAG) coder.shift(sy, lt, (int)tot);
-        else if (tot >= 2) coder.freq_rcp(sy, lt, tot, rc_tab);
-        else coder.freq(sy, lt, tot);
-      }
+      code_steps(coder, h_buf[k & 1], B.nsteps[r], rc_tab);
       ms_coder += since(Tc);
     }
     if (rc) { std::lock_guard<std::mutex> lk(J.mu); J.abort = true; J.cv.notify_all(); }
@@ -780,6 +790,81 @@ extern "C" int cjs_bwtc_compress(const uint8_t* in, size_t n, int level, uint8_t
   memcpy(host, o.data(), o.size());
   *out = host; *out_n = o.size();
   if (op.stats) op.stats->bytes_out = o.size();
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+// ---------------------------------------------------------------- stage-level entry points of the compressor's back half (tests)
+// The model kernels on caller-made symbol blocks: what bwtc_batch_body launches behind mtf_run, on rows laid out as MtfWork
+// carves them.  Of MtfBufs the kernels read A, a_stride, asz and npos (symbols + 1: the MTF stage counts bzip2's end-of-block).
+extern "C" int cjs_stage_bwtc_model(const uint16_t* A, size_t a_stride, uint32_t nb, const uint32_t* nsym, const uint32_t* alphabet, int level,
+                                    uint64_t* steps, size_t step_stride, uint32_t* nsteps, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (!A || !nsym || !alphabet || !steps || !nsteps || nb == 0 || nb > (1u << 20) || a_stride == 0 || step_stride < 2 || level < 1 || level > 9) return CJS_E_INVALID_ARG;
+  // what the kernels rely on: symbols index model arrays of asz + 2 slots, a block writes at most two steps per symbol
+  uint32_t max_nsym = 1;
+  for (uint32_t k = 0; k < nb; k++) {
+    const uint32_t n = nsym[k], asz = alphabet[k];
+    if (asz == 0 || asz > 256 || n > a_stride || n > 900000u || 2 * (size_t)n > step_stride) return CJS_E_INVALID_ARG;
+    const uint16_t* a = A + (size_t)k * a_stride;
+    for (uint32_t i = 0; i < n; i++) if (a[i] > asz) return CJS_E_INVALID_ARG;
+    max_nsym = std::max(max_nsym, n);
+  }
+  const size_t das = MtfWork::a_stride_for(max_nsym), dss = 2 * das;      // rows as bwtc_batch_body sizes them
+  Arena arena;
+  CJS_TRY(arena.init(2 * das * nb + 8 * dss * nb + 12 * (size_t)nb + 65536));
+  MtfBufs mb{};
+  mb.A = arena.take<uint16_t>(das * nb); mb.a_stride = das;
+  mb.asz = arena.take<uint32_t>(nb); mb.npos = arena.take<uint32_t>(nb);
+  uint32_t* d_nsteps = arena.take<uint32_t>(nb);
+  uint64_t* d_steps = arena.take<uint64_t>(dss * nb);
+  if (!mb.A || !mb.asz || !mb.npos || !d_nsteps || !d_steps) return CJS_E_OUT_OF_MEMORY;
+  std::vector<uint32_t> npos(nb);
+  for (uint32_t k = 0; k < nb; k++) npos[k] = nsym[k] + 1;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemsetAsync(mb.A, 0, 2 * das * nb, s));
+  CJS_HIP_TRY(hipMemsetAsync(d_steps, 0, 8 * dss * nb, s));
+  CJS_HIP_TRY(hipMemsetAsync(d_nsteps, 0, 4 * (size_t)nb, s));
+  CJS_HIP_TRY(hipMemcpy2DAsync(mb.A, 2 * das, A, 2 * a_stride, 2 * (size_t)std::min<size_t>(max_nsym, a_stride), nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(mb.asz, alphabet, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(mb.npos, npos.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_TRY(bwtc_model_launch(s, level <= 5, mb, nb, d_steps, dss, d_nsteps));
+  CJS_HIP_TRY(hipMemcpyAsync(nsteps, d_nsteps, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpy2DAsync(steps, 8 * step_stride, d_steps, 8 * dss, 8 * std::min<size_t>(2 * (size_t)max_nsym, step_stride), nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+// The host range coder on a caller-made step list: encodeStart(first_byte, 1), the compressor's step loop, encodeFinish.
+// Host only (no device is touched).  mode 0 = both chains on the calling thread, 1 = split across two threads.
+extern "C" int cjs_stage_bwtc_code(const uint64_t* steps, size_t n, int first_byte, int mode, uint8_t** out, size_t* out_n) {
+  if (!out || !out_n) return CJS_E_INVALID_ARG;
+  *out = nullptr; *out_n = 0;
+  CJS_GUARD_BEGIN
+  if ((n && !steps) || n > (1u << 30) || first_byte < 0 || first_byte > 255 || (mode != 0 && mode != 1)) return CJS_E_INVALID_ARG;
+  for (size_t i = 0; i < n; i++) {                      // a step the reference's models could not make is refused, not coded
+    const uint64_t st = steps[i];
+    const uint32_t sy = (uint32_t)(st & 0xFFFF), lt = (uint32_t)((st >> 16) & 0xFFFF), tot = (uint32_t)((st >> 32) & 0x1FFFF);
+    if (((st >> 49) & 0x3FFF) || sy < 1) return CJS_E_INVALID_ARG;
+    if (st & STEP_SHIFT_FLAG) { if (tot < 1 || tot > 16 || lt + sy > (1u << tot)) return CJS_E_INVALID_ARG; }
+    else if (lt + sy > tot) return CJS_E_INVALID_ARG;
+  }
+  std::vector<uint8_t> o;
+  HostCoder coder(o);
+  coder.start(first_byte, 1);
+  if (mode == 1) coder.start_split();
+  coder.reserve_steps(n);
+  code_steps(coder, steps, (uint32_t)n, rcp_table());
+  coder.reserve_steps(64);
+  coder.finish();
+  if (coder.failed.load()) return CJS_E_OUT_OF_MEMORY;
+  uint8_t* host = (uint8_t*)malloc(o.size() ? o.size() : 1);
+  if (!host) return CJS_E_OUT_OF_MEMORY;
+  memcpy(host, o.data(), o.size());
+  *out = host; *out_n = o.size();
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }

@@ -310,6 +310,22 @@ int cjs_stage_huff_blocks(const uint16_t *A, size_t a_stride, uint32_t nb, const
 long cjs_stage_bwtc_entropy_decode(const uint8_t *in, size_t n, uint8_t **cols, size_t *cols_n, uint32_t *lens, uint32_t *pidx,
                                    long cap, int *level);
 
+/* The back half of BWTC.compressFile in its two parts, so that a mismatch of a stream can be placed (tests/bwtc_cases.py).
+ * A coder step is one 64-bit word: sy | lt << 16 | tot << 32 for encodeFreq(sy, lt, tot), the same with bit 63 set and the
+ * shift in tot's place for encodeShift (J/BWTC_joined_.js:92-113).
+ * cjs_stage_bwtc_model: the adaptive model (J/BWTC_joined_.js:1791-1819) of nb blocks in ONE launch of the kernel the compressor
+ * uses at `level` (DefSumModel for 1..5, FenwickModel for 6..9), with the compressor's launch shape.  Block k: RLE2 symbols
+ * A[k*a_stride .. + nsym[k]), values 0 .. alphabet[k] (alphabet[k] = number of byte values of the block, 1..256), no end-of-block
+ * symbol.  Out: nsteps[k] and the steps at steps + k*step_stride (step_stride >= 2 * nsym[k]).  CJS_E_INVALID_ARG for symbols
+ * out of range, a row longer than its stride, nb == 0 or level outside 1..9. */
+int cjs_stage_bwtc_model(const uint16_t *A, size_t a_stride, uint32_t nb, const uint32_t *nsym, const uint32_t *alphabet, int level,
+                         uint64_t *steps, size_t step_stride, uint32_t *nsteps, const cjs_opts *opts);
+/* cjs_stage_bwtc_code: the host range coder over a caller's step list: encodeStart(first_byte, 1), the step loop of
+ * cjs_bwtc_compress, encodeFinish (J/BWTC_joined_.js:40-153).  Host logic only, needs no device.  mode 0: one thread;
+ * mode 1: split across two threads (what cjs_bwtc_compress does unless CJS_BWTC_SPLIT_CODER=0).  *out: malloc'd, cjs_free.
+ * CJS_E_INVALID_ARG for a step with sy == 0, lt + sy > tot (or > 1 << shift), a shift outside 1..16 or bits 49..62 set. */
+int cjs_stage_bwtc_code(const uint64_t *steps, size_t n, int first_byte, int mode, uint8_t **out, size_t *out_n);
+
 #ifdef __cplusplus
 }
 #endif

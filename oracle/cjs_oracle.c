@@ -764,29 +764,47 @@ int cjs_oracle_bzip2_decompress_block(const uint8_t *in, size_t n, uint64_t bitp
 #define RC_BOTTOM 0x00800000u
 #define RC_SHIFT 23
 #define RC_EXTRA 7
+/* optional recorder of the encoder's calls: one packed word per rc_encode_freq / rc_encode_shift (sy | lt << 16 | tot << 32,
+ * bit 63 set for a shift step whose shift stands in tot's place), and `tag` of the moment beside it when tags != NULL */
+typedef struct { uint64_t *steps; uint32_t *tags; size_t n, cap; uint32_t tag; } rc_rec_t;
+/* optional counters of the encoder's normalisation: largest help, carries, most byte shifts in one call, finish's carry */
+typedef struct { uint32_t max_help, carries, max_shifts, finish_carry; } rc_stat_t;
 typedef struct {
   uint32_t low, range; int32_t buffer; uint32_t help; uint32_t bytecount;
   buf_t *out;                       /* encoder */
   const uint8_t *in; size_t in_n, in_pos;   /* decoder */
+  rc_rec_t *rec; rc_stat_t *stat;   /* encoder, both optional */
 } rc_t;
+static void rc_record(rc_rec_t *r, int is_shift, uint32_t sy, uint32_t lt, uint32_t tot) {
+  if (r->n < r->cap) {
+    r->steps[r->n] = (uint64_t)sy | ((uint64_t)lt << 16) | ((uint64_t)tot << 32) | (is_shift ? 1ull << 63 : 0ull);
+    if (r->tags) r->tags[r->n] = r->tag;
+  }
+  r->n++;                            /* (counts on past cap: the caller sees that the list did not fit) */
+}
 static void rc_enc_normalize(rc_t *rc) {                              /* BWTC:51-73 */
+  uint32_t shifts = 0;
   while (rc->range <= RC_BOTTOM) {
+    shifts++;
     if (rc->low < (0xFFu << RC_SHIFT)) {
       buf_put(rc->out, rc->buffer & 0xff);
       for (; rc->help; rc->help--) buf_put(rc->out, 0xFF);
       rc->buffer = (int32_t)((rc->low >> RC_SHIFT) & 0xFF);
     } else if (rc->low & RC_TOP) {
+      if (rc->stat) rc->stat->carries++;
       buf_put(rc->out, (rc->buffer + 1) & 0xff);
       for (; rc->help; rc->help--) buf_put(rc->out, 0x00);
       rc->buffer = (int32_t)((rc->low >> RC_SHIFT) & 0xFF);
-    } else rc->help++;
+    } else { rc->help++; if (rc->stat && rc->help > rc->stat->max_help) rc->stat->max_help = rc->help; }
     rc->range <<= 8;
     rc->low = (rc->low << 8) & (RC_TOP - 1);
     rc->bytecount++;
   }
+  if (rc->stat && shifts > rc->stat->max_shifts) rc->stat->max_shifts = shifts;
 }
 static void rc_encode_start(rc_t *rc, int c, uint32_t initlen) { rc->low = 0; rc->range = RC_TOP; rc->buffer = c; rc->help = 0; rc->bytecount = initlen; }
 static void rc_encode_freq(rc_t *rc, uint32_t sy, uint32_t lt, uint32_t tot) {   /* BWTC:92-102 */
+  if (rc->rec) rc_record(rc->rec, 0, sy, lt, tot);
   rc_enc_normalize(rc);
   uint32_t r = rc->range / tot;
   uint32_t tmp = r * lt;
@@ -794,6 +812,7 @@ static void rc_encode_freq(rc_t *rc, uint32_t sy, uint32_t lt, uint32_t tot) {  
   if (lt + sy < tot) rc->range = r * sy; else rc->range -= tmp;
 }
 static void rc_encode_shift(rc_t *rc, uint32_t sy, uint32_t lt, int shift) {    /* BWTC:103-113 */
+  if (rc->rec) rc_record(rc->rec, 1, sy, lt, (uint32_t)shift);
   rc_enc_normalize(rc);
   uint32_t r = rc->range >> shift;
   uint32_t tmp = r * lt;
@@ -805,7 +824,8 @@ static uint32_t rc_encode_finish(rc_t *rc) {                                    
   rc->bytecount += 5;
   uint32_t tmp = rc->low >> RC_SHIFT;
   if ((rc->low & (RC_BOTTOM - 1)) >= ((rc->bytecount & 0xFFFFFF) >> 1)) tmp++;
-  if (tmp > 0xFF) { buf_put(rc->out, (rc->buffer + 1) & 0xff); for (; rc->help; rc->help--) buf_put(rc->out, 0x00); }
+  if (tmp > 0xFF) { if (rc->stat) { rc->stat->carries++; rc->stat->finish_carry = 1; }
+                    buf_put(rc->out, (rc->buffer + 1) & 0xff); for (; rc->help; rc->help--) buf_put(rc->out, 0x00); }
   else { buf_put(rc->out, rc->buffer & 0xff); for (; rc->help; rc->help--) buf_put(rc->out, 0xFF); }
   buf_put(rc->out, (int)(tmp & 0xFF));
   buf_put(rc->out, (int)((rc->bytecount >> 16) & 0xFF));
@@ -865,10 +885,11 @@ static uint32_t logdist_decode(rc_t *rc, int block_size) {
 }
 
 /* FenwickModel (BWTC:1496-1661) */
-typedef struct { rc_t *rc; int num_syms; uint32_t *tree; uint32_t increment, max_prob; } fen_t;
+typedef struct { rc_t *rc; int num_syms; uint32_t *tree; uint32_t increment, max_prob; uint64_t *ev; } fen_t;
+#define FEN_EV(m, k) do { if ((m)->ev) (m)->ev[k]++; } while (0)      /* event counters (CJSO_FEN_*), optional */
 static void fen_sum(fen_t *m) { for (int i = m->num_syms - 1; i > 0; i--) m->tree[i] = m->tree[2 * i] + m->tree[2 * i + 1]; }
 static int fen_init(fen_t *m, rc_t *rc, int size, uint32_t max_prob, uint32_t increment) {
-  m->rc = rc; m->num_syms = size + 1; m->increment = increment; m->max_prob = max_prob;
+  m->rc = rc; m->num_syms = size + 1; m->increment = increment; m->max_prob = max_prob; m->ev = 0;
   m->tree = (uint32_t *)calloc((size_t)m->num_syms * 2, sizeof(uint32_t));
   if (!m->tree) return -1;
   int i;
@@ -880,16 +901,17 @@ static int fen_init(fen_t *m, rc_t *rc, int size, uint32_t max_prob, uint32_t in
 static void fen_rescale(fen_t *m) {                                              /* BWTC:1623-1654 */
   int i, no_escape = 1;
   uint32_t prob;
+  FEN_EV(m, CJSO_FEN_RESCALE);
   for (i = 0; i < m->num_syms - 1; i++) {
     prob = m->tree[m->num_syms + i];
     if (prob & 0xFFFFu) { no_escape = 0; continue; }
     prob = (prob & 0xFFFEFFFEu) >> 1;
-    if (prob == 0) { prob = 1u; no_escape = 0; }
+    if (prob == 0) { prob = 1u; no_escape = 0; FEN_EV(m, CJSO_FEN_DECAY); }
     m->tree[m->num_syms + i] = prob;
   }
   prob = m->tree[m->num_syms + i];
   prob = (prob & 0xFFFEFFFEu) >> 1;
-  if (no_escape) prob = 0; else if (prob == 0) prob = 1u << 16;
+  if (no_escape) { prob = 0; FEN_EV(m, CJSO_FEN_ESC_ZEROED); } else if (prob == 0) { prob = 1u << 16; FEN_EV(m, CJSO_FEN_ESC_REINSTATED); }
   m->tree[m->num_syms + i] = prob;
   fen_sum(m);
 }
@@ -897,8 +919,8 @@ static void fen_encode(fen_t *m, int symbol) {                                  
   int i = m->num_syms + symbol;
   uint32_t sy = m->tree[i], mask = 0xFFFF0000u; int shift = 16;
   uint32_t update = m->increment << 16;
-  if ((sy & 0xFFFF0000u) == 0) { fen_encode(m, m->num_syms - 1); mask = 0x0000FFFFu; update -= 1u; shift = 0; }
-  else if (symbol == m->num_syms - 1 && (m->tree[1] & 0xFFFFu) == 1) update = 0u - m->tree[i];
+  if ((sy & 0xFFFF0000u) == 0) { FEN_EV(m, CJSO_FEN_ESCAPE); fen_encode(m, m->num_syms - 1); mask = 0x0000FFFFu; update -= 1u; shift = 0; }
+  else if (symbol == m->num_syms - 1 && (m->tree[1] & 0xFFFFu) == 1) { update = 0u - m->tree[i]; FEN_EV(m, CJSO_FEN_LAST_ESCAPE); }
   uint32_t lt = 0;
   while (i > 1) {
     int parent = i >> 1;
@@ -909,7 +931,11 @@ static void fen_encode(fen_t *m, int symbol) {                                  
   uint32_t tot = m->tree[1];
   m->tree[1] += update;
   rc_encode_freq(m->rc, (sy & mask) >> shift, (lt & mask) >> shift, (tot & mask) >> shift);
-  if ((m->tree[1] >> 16) >= m->max_prob) fen_rescale(m);
+  if ((m->tree[1] >> 16) >= m->max_prob) {
+    /* the escape symbol is coded only from the line above that announces a novel symbol, whose own step is still to come */
+    if (symbol == m->num_syms - 1) FEN_EV(m, CJSO_FEN_RESCALE_BETWEEN);
+    fen_rescale(m);
+  }
 }
 static int fen_decode1(fen_t *m, int is_escape) {                                /* BWTC:1572-1614 */
   uint32_t mask = 0xFFFF0000u; int shift = 16;
@@ -939,7 +965,8 @@ static int fen_decode(fen_t *m) { int s = fen_decode1(m, 0); if (s == m->num_sym
 
 /* DefSumModel (BWTC:1327-1459) */
 typedef struct { rc_t *rc; int num_syms; uint16_t prob[304], escape[304], update[304]; int update_count, update_thresh;
-                 uint16_t prob_to_sym[256], esc_prob_to_sym[304]; int is_decoder; } dsm_t;
+                 uint16_t prob_to_sym[256], esc_prob_to_sym[304]; int is_decoder; uint64_t *ev; } dsm_t;
+#define DSM_EV(m, k) do { if ((m)->ev) (m)->ev[k]++; } while (0)      /* event counters (CJSO_DSM_*), optional */
 static void dsm_init(dsm_t *m, rc_t *rc, int size, int is_decoder) {
   memset(m, 0, sizeof *m);
   m->rc = rc; m->num_syms = size; m->is_decoder = is_decoder;
@@ -953,12 +980,13 @@ static void dsm_init(dsm_t *m, rc_t *rc, int size, int is_decoder) {
 }
 static void dsm_update(dsm_t *m, int symbol) {                                   /* BWTC:1359-1421 */
   if (symbol == m->num_syms) {
-    if (m->update[symbol] >= 40) return;
-    if (m->update_count >= m->update_thresh - 1) return;
+    if (m->update[symbol] >= 40) { DSM_EV(m, CJSO_DSM_REFUSED_CAP); return; }
+    if (m->update_count >= m->update_thresh - 1) { DSM_EV(m, CJSO_DSM_REFUSED_THRESH); return; }
   }
   m->update[symbol]++;
   m->update_count++;
   if (m->update_count < m->update_thresh) return;
+  DSM_EV(m, CJSO_DSM_FOLD);
   int cum = 0, cum_esc = 0, odd = 0, i;
   m->escape[0] = 0; m->prob[0] = 0;
   for (i = 0; i < m->num_syms + 1; i++) {
@@ -984,6 +1012,7 @@ static void dsm_update(dsm_t *m, int symbol) {                                  
 static void dsm_encode(dsm_t *m, int symbol) {                                   /* BWTC:1422-1439 */
   uint32_t lt = m->prob[symbol], sy = (uint32_t)m->prob[symbol + 1] - lt;
   if (sy) { rc_encode_shift(m->rc, sy, lt, 8); dsm_update(m, symbol); return; }
+  DSM_EV(m, CJSO_DSM_ESCAPE);
   dsm_encode(m, m->num_syms);
   lt = m->escape[symbol]; sy = (uint32_t)m->escape[symbol + 1] - lt;
   rc_encode_freq(m->rc, sy, lt, m->escape[m->num_syms]);
@@ -1006,15 +1035,21 @@ static int dsm_decode(dsm_t *m) {                                               
 }
 
 /* BWTC.compressFile (BWTC:1698-1825) + Util.compressFileHelper (BWTC:516-553) */
-int cjs_oracle_bwtc_compress(const uint8_t *in, size_t n, int level, uint8_t **out, size_t *out_n) {
+/* rec (optional) records every coder call; *prefix_n = bytes in front of the coder's output, *first_byte = the coder's first
+ * byte; blk_lo / blk_hi (optional, cap entries) = the step range of each block's model section; *nblocks = blocks coded */
+static int bwtc_compress_impl(const uint8_t *in, size_t n, int level, uint8_t **out, size_t *out_n, rc_rec_t *rec,
+                              size_t *prefix_n, int *first_byte, uint64_t *blk_lo, uint64_t *blk_hi, long cap, long *nblocks) {
   buf_t b = {0, 0, 0, 0};
+  long nblk = 0;
   buf_put(&b, 'b'); buf_put(&b, 'w'); buf_put(&b, 't'); buf_put(&b, 'c');
   uint8_t vb[12]; int nv = 0;                                         /* writeUnsignedNumber BWTC:605-620 */
   uint64_t v = (uint64_t)n + 1;
   do { vb[nv++] = (uint8_t)(v & 0x7F); v >>= 7; } while (v);
   vb[0] |= 0x80;
   for (int i = nv - 1; i >= 1; i--) buf_put(&b, vb[i]);
-  rc_t rc; memset(&rc, 0, sizeof rc); rc.out = &b;
+  rc_t rc; memset(&rc, 0, sizeof rc); rc.out = &b; rc.rec = rec;
+  if (prefix_n) *prefix_n = b.n;
+  if (first_byte) *first_byte = vb[0];
   rc_encode_start(&rc, vb[0], 1);
   if (level < 1 || level > 9) level = 9;                             /* W2 */
   rc_encode_shift(&rc, 1, (uint32_t)level, 8);
@@ -1056,6 +1091,7 @@ int cjs_oracle_bwtc_compress(const uint8_t *in, size_t n, int level, uint8_t **o
     if (fast) { dm = (dsm_t *)malloc(sizeof(dsm_t)); dsm_init(dm, &rc, asz + 1, 0); }
     else if (fen_init(&fm, &rc, asz + 1, 0xFF00, 0x100)) { rcode = CJSO_OUT_OF_MEMORY; break; }
 #define MENC(s) do { if (fast) dsm_encode(dm, (s)); else fen_encode(&fm, (s)); } while (0)
+    if (rec && blk_lo && nblk < cap) blk_lo[nblk] = rec->n;
     uint32_t run = 0;
     for (int i = 0; i < length; i++) {                               /* RLE2 BWTC:1794-1819 */
       int c = U[i];
@@ -1067,6 +1103,8 @@ int cjs_oracle_bwtc_compress(const uint8_t *in, size_t n, int level, uint8_t **o
     }
     while (run) { if (run & 1) { MENC(0); run -= 1; } else { MENC(1); run -= 2; } run >>= 1; }
 #undef MENC
+    if (rec && blk_hi && nblk < cap) blk_hi[nblk] = rec->n;
+    nblk++;
     free(fm.tree); free(dm);
   } while (length == block_size);
   free(U);
@@ -1074,6 +1112,71 @@ int cjs_oracle_bwtc_compress(const uint8_t *in, size_t n, int level, uint8_t **o
   rc_encode_freq(&rc, 1, 2, 3);
   rc_encode_finish(&rc);
   if (b.oom) { free(b.p); return CJSO_OUT_OF_MEMORY; }
+  if (nblocks) *nblocks = nblk;
+  if (out) { *out = b.p; *out_n = b.n; } else free(b.p);
+  return 0;
+}
+int cjs_oracle_bwtc_compress(const uint8_t *in, size_t n, int level, uint8_t **out, size_t *out_n) {
+  return bwtc_compress_impl(in, n, level, out, out_n, 0, 0, 0, 0, 0, 0, 0);
+}
+
+/* ---- step traces of the code above (tests/test_oracle.py pins them to cjs_oracle_bwtc_compress) */
+long cjs_oracle_bwtc_stream_steps(const uint8_t *in, size_t n, int level, uint64_t **steps, size_t *nsteps, size_t *prefix_n,
+                                  int *first_byte, uint64_t *blk_lo, uint64_t *blk_hi, long cap) {
+  /* every input byte costs at most two model steps; framing: < 1100 steps per block (use-tree 511, two distances) */
+  int lv = (level < 1 || level > 9) ? 9 : level;
+  size_t nblk = n / ((size_t)lv * 100000) + 2, scap = 2 * n + 1200 * nblk + 64;
+  rc_rec_t rec; memset(&rec, 0, sizeof rec);
+  rec.steps = (uint64_t *)malloc(scap * sizeof(uint64_t)); rec.cap = scap;
+  if (!rec.steps) return CJSO_OUT_OF_MEMORY;
+  long nb = 0;
+  int rcode = bwtc_compress_impl(in, n, level, 0, 0, &rec, prefix_n, first_byte, blk_lo, blk_hi, cap, &nb);
+  if (!rcode && rec.n > rec.cap) rcode = CJSO_DATA_ERROR;
+  if (rcode) { free(rec.steps); return rcode; }
+  *steps = rec.steps; *nsteps = rec.n;
+  return nb;
+}
+long cjs_oracle_bwtc_model_steps(const uint16_t *A, size_t nsym, int asz, int fast, uint64_t *steps, uint32_t *pos, size_t cap,
+                                 uint64_t *events) {
+  if (asz < 0 || asz > 256) return CJSO_DATA_ERROR;
+  for (size_t i = 0; i < nsym; i++) if (A[i] > asz) return CJSO_DATA_ERROR;
+  buf_t b = {0, 0, 0, 0};
+  rc_rec_t rec; memset(&rec, 0, sizeof rec);
+  rec.steps = steps; rec.tags = pos; rec.cap = cap;
+  rc_t rc; memset(&rc, 0, sizeof rc); rc.out = &b; rc.rec = &rec;
+  rc_encode_start(&rc, 0x80, 1);
+  if (events) memset(events, 0, CJSO_N_EVENTS * sizeof(uint64_t));
+  if (fast) {
+    dsm_t *dm = (dsm_t *)malloc(sizeof(dsm_t));
+    if (!dm) return CJSO_OUT_OF_MEMORY;
+    dsm_init(dm, &rc, asz + 1, 0);
+    dm->ev = events;
+    for (size_t i = 0; i < nsym; i++) { rec.tag = (uint32_t)i; dsm_encode(dm, A[i]); }
+    free(dm);
+  } else {
+    fen_t fm;
+    if (fen_init(&fm, &rc, asz + 1, 0xFF00, 0x100)) return CJSO_OUT_OF_MEMORY;
+    fm.ev = events;
+    for (size_t i = 0; i < nsym; i++) { rec.tag = (uint32_t)i; fen_encode(&fm, A[i]); }
+    free(fm.tree);
+  }
+  free(b.p);
+  return (long)rec.n;
+}
+int cjs_oracle_rc_encode_steps(int first_byte, const uint64_t *steps, size_t n, uint8_t **out, size_t *out_n, uint32_t *stats) {
+  buf_t b = {0, 0, 0, 0};
+  rc_stat_t st; memset(&st, 0, sizeof st);
+  rc_t rc; memset(&rc, 0, sizeof rc); rc.out = &b; rc.stat = &st;
+  rc_encode_start(&rc, first_byte, 1);
+  for (size_t i = 0; i < n; i++) {
+    uint64_t w = steps[i];
+    uint32_t sy = (uint32_t)(w & 0xFFFF), lt = (uint32_t)((w >> 16) & 0xFFFF), tot = (uint32_t)((w >> 32) & 0x1FFFF);
+    if (w >> 63) { if (tot < 1 || tot > 16 || sy < 1 || lt + sy > (1u << tot)) { free(b.p); return CJSO_DATA_ERROR; } rc_encode_shift(&rc, sy, lt, (int)tot); }
+    else { if (sy < 1 || lt + sy > tot) { free(b.p); return CJSO_DATA_ERROR; } rc_encode_freq(&rc, sy, lt, tot); }
+  }
+  rc_encode_finish(&rc);
+  if (b.oom) { free(b.p); return CJSO_OUT_OF_MEMORY; }
+  if (stats) { stats[0] = st.max_help; stats[1] = st.carries; stats[2] = st.max_shifts; stats[3] = st.finish_carry; }
   *out = b.p; *out_n = b.n;
   return 0;
 }

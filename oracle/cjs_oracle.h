@@ -63,6 +63,42 @@ int cjs_oracle_huff_groups(const uint16_t *A, int pos, int alphabet_size, uint8_
 int cjs_oracle_bzip2_block_bits(const uint16_t *A, int pos, int asz, const uint8_t *used, uint32_t crc, uint32_t pidx,
                                 uint8_t **out, uint64_t *out_bits);
 
+
+/* ---- step traces of the BWTC back half (for stage-level parity of the model kernels and the host range coder).
+ * A coder step is one call of RangeCoder.encodeFreq / encodeShift (J/BWTC:92-113), packed as the product packs it:
+ * sy | lt << 16 | tot << 32, bit 63 set for a shift step (the shift stands in tot's place).  The traces are written by a
+ * recorder inside the coder that cjs_oracle_bwtc_compress runs: the models and the framing are the pinned code, unchanged. */
+/* event counters of cjs_oracle_bwtc_model_steps, each incremented at the model's own line that names the state */
+enum {
+  CJSO_FEN_RESCALE = 0,          /* _rescale calls */
+  CJSO_FEN_ESCAPE = 1,           /* novel symbols (the escape symbol coded first) */
+  CJSO_FEN_LAST_ESCAPE = 2,      /* the escape that announces the last unseen symbol (update = -tree[i]) */
+  CJSO_FEN_DECAY = 3,            /* leaves that a rescale halved to nothing and set back to "unseen" */
+  CJSO_FEN_ESC_ZEROED = 4,       /* rescales that found no unseen symbol and zeroed the escape leaf */
+  CJSO_FEN_ESC_REINSTATED = 5,   /* rescales that gave a zero escape leaf its 1 << 16 back */
+  CJSO_FEN_RESCALE_BETWEEN = 6,  /* rescales after an escape step and before the step of its symbol */
+  CJSO_DSM_FOLD = 0,             /* updates that folded the deferred counts in */
+  CJSO_DSM_REFUSED_CAP = 1,      /* escape updates refused because 40 are pending */
+  CJSO_DSM_REFUSED_THRESH = 2,   /* escape updates refused by update_count >= update_thresh - 1 */
+  CJSO_DSM_ESCAPE = 3,           /* symbols coded through the escape */
+  CJSO_N_EVENTS = 8
+};
+/* one block's model section as compressFile runs it (J/BWTC:1791-1819): A[0..nsym) = the block's RLE2 symbols, values 0..asz,
+ * without an end-of-block symbol; fast != 0: DefSumModel(asz + 1), else FenwickModel(asz + 1, 0xFF00, 0x100).  Writes up to cap
+ * steps and, when pos != NULL, the index into A each step belongs to; events[CJSO_N_EVENTS].  Returns the number of steps (may
+ * exceed cap: nothing past cap is written) or a negative code */
+long cjs_oracle_bwtc_model_steps(const uint16_t *A, size_t nsym, int asz, int fast, uint64_t *steps, uint32_t *pos, size_t cap,
+                                 uint64_t *events);
+/* every coder call of cjs_oracle_bwtc_compress(in, n, level) in order, framing included: *steps (cjs_oracle_free) / *nsteps.
+ * *prefix_n = stream bytes in front of the coder's output (magic, leading size bytes), *first_byte = the byte the coder starts
+ * with; steps [blk_lo[k], blk_hi[k]) are block k's model section (up to cap blocks).  Returns the number of blocks or <0 */
+long cjs_oracle_bwtc_stream_steps(const uint8_t *in, size_t n, int level, uint64_t **steps, size_t *nsteps, size_t *prefix_n,
+                                  int *first_byte, uint64_t *blk_lo, uint64_t *blk_hi, long cap);
+/* encodeStart(first_byte, 1), the steps, encodeFinish: the coder's bytes (cjs_oracle_free).  A step must be valid (sy >= 1,
+ * lt + sy <= tot < 2^17, or shift 1..16 with lt + sy <= 1 << shift), else CJSO_DATA_ERROR.  stats[4] (optional): largest count
+ * of pending bytes (help), carries (finish's included), most byte shifts in one normalisation, 1 if finish took tmp > 0xFF */
+int cjs_oracle_rc_encode_steps(int first_byte, const uint64_t *steps, size_t n, uint8_t **out, size_t *out_n, uint32_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

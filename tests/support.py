@@ -73,6 +73,12 @@ class Oracle(_StreamLib):
                                                   ctypes.POINTER(ctypes.c_uint64)]
         L.cjs_oracle_bzip2_compress_range.argtypes = [u8p, S, I, ctypes.c_long, ctypes.c_long, ctypes.POINTER(u8p),
                                                       ctypes.POINTER(ctypes.c_uint64), V, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
+        L.cjs_oracle_bwtc_model_steps.argtypes = [V, S, I, I, V, V, S, V]
+        L.cjs_oracle_bwtc_model_steps.restype = ctypes.c_long
+        L.cjs_oracle_bwtc_stream_steps.argtypes = [u8p, S, I, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint64)), ctypes.POINTER(S),
+                                                   ctypes.POINTER(S), ctypes.POINTER(I), V, V, ctypes.c_long]
+        L.cjs_oracle_bwtc_stream_steps.restype = ctypes.c_long
+        L.cjs_oracle_rc_encode_steps.argtypes = [I, V, S, ctypes.POINTER(u8p), ctypes.POINTER(S), V]
 
     def _free(self, p):
         self.L.cjs_oracle_free(p)
@@ -106,6 +112,53 @@ class Oracle(_StreamLib):
 
     def bzip2_decompress_block(self, data, bitpos):
         return self._call_stream(self.L.cjs_oracle_bzip2_decompress_block, self._free, data, ctypes.c_uint64(bitpos))
+
+    # event counters of bwtc_model_steps (oracle/cjs_oracle.h, CJSO_FEN_* / CJSO_DSM_*)
+    FEN_EVENTS = ("rescale", "escape", "last_escape", "decay", "esc_zeroed", "esc_reinstated", "rescale_between")
+    DSM_EVENTS = ("fold", "refused_cap", "refused_thresh", "escape")
+
+    def bwtc_model_steps(self, A, asz, fast):
+        """one block's model section: (steps u64, symbol position of each step u32, {event: count})"""
+        A = np.ascontiguousarray(A, dtype=np.uint16)
+        cap = 2 * A.size + 1
+        steps = np.zeros(cap, dtype=np.uint64)
+        pos = np.zeros(cap, dtype=np.uint32)
+        ev = np.zeros(8, dtype=np.uint64)
+        n = self.L.cjs_oracle_bwtc_model_steps(A.ctypes.data, A.size, asz, 1 if fast else 0, steps.ctypes.data, pos.ctypes.data, cap,
+                                               ev.ctypes.data)
+        assert 0 <= n < cap, "cjs_oracle_bwtc_model_steps: %d" % n
+        names = self.DSM_EVENTS if fast else self.FEN_EVENTS
+        return steps[:n], pos[:n], {k: int(ev[i]) for i, k in enumerate(names)}
+
+    def bwtc_stream_steps(self, data, level, cap=4096):
+        """every coder call of bwtc_compress(data, level): (rc, steps u64, prefix_n, first_byte, [(lo, hi) of each block's model
+        section])"""
+        data = as_u8(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        p, n, pre, fb = ctypes.POINTER(ctypes.c_uint64)(), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
+        lo = np.zeros(cap, dtype=np.uint64)
+        hi = np.zeros(cap, dtype=np.uint64)
+        nb = self.L.cjs_oracle_bwtc_stream_steps(keep.ctypes.data_as(u8p), data.size, level, ctypes.byref(p), ctypes.byref(n),
+                                                 ctypes.byref(pre), ctypes.byref(fb), lo.ctypes.data, hi.ctypes.data, cap)
+        if nb < 0:
+            return nb, None, 0, 0, None
+        steps = np.ctypeslib.as_array(p, shape=(max(n.value, 1),))[: n.value].copy()
+        self.L.cjs_oracle_free(p)
+        return 0, steps, pre.value, fb.value, [(int(lo[k]), int(hi[k])) for k in range(min(nb, cap))]
+
+    def rc_encode_steps(self, first_byte, steps):
+        """(rc, coder bytes, {max_help, carries, max_shifts, finish_carry})"""
+        steps = np.ascontiguousarray(steps, dtype=np.uint64)
+        keep = steps if steps.size else np.zeros(1, dtype=np.uint64)
+        out, out_n = u8p(), ctypes.c_size_t(0)
+        st = np.zeros(4, dtype=np.uint32)
+        rc = self.L.cjs_oracle_rc_encode_steps(first_byte, keep.ctypes.data, steps.size, ctypes.byref(out), ctypes.byref(out_n),
+                                               st.ctypes.data)
+        if rc:
+            return rc, None, None
+        res = np.ctypeslib.as_array(out, shape=(max(out_n.value, 1),))[: out_n.value].copy()
+        self.L.cjs_oracle_free(out)
+        return 0, res, dict(zip(("max_help", "carries", "max_shifts", "finish_carry"), (int(v) for v in st)))
 
     def bzip2_table(self, data, multistream=0, cap=100000):
         data = as_u8(data)
@@ -229,6 +282,8 @@ class HipLib(_StreamLib):
             "cjs_stage_huff": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
             "cjs_stage_huff_blocks": [V, S, ctypes.c_uint32, V, V, V, V, V, I, V, V, V, V, S, V, V],
             "cjs_stage_bwtc_entropy_decode": [u8p, S, PP, PS, V, V, ctypes.c_long, ctypes.POINTER(I)],
+            "cjs_stage_bwtc_model": [V, S, ctypes.c_uint32, V, V, I, V, S, V, V],
+            "cjs_stage_bwtc_code": [V, S, I, I, PP, PS],
             "cjs_last_error_detail": [],
         }
         self.missing = []
@@ -299,6 +354,38 @@ class HipLib(_StreamLib):
             out.append((flat[off: off + int(lens[k])], int(pidx[k])))
             off += int(lens[k])
         return nb, level.value, out
+
+    def stage_bwtc_model(self, blocks, level):
+        """the model kernel of `level` on many blocks in one launch (cjs_stage_bwtc_model).  blocks: list of (A u16 symbols,
+        asz).  Returns (rc, [steps u64 of each block])"""
+        nb = len(blocks)
+        a_stride = max(1, max(len(a) for a, _ in blocks))
+        A = np.zeros((nb, a_stride), dtype=np.uint16)
+        nsym = np.zeros(nb, dtype=np.uint32)
+        asz = np.zeros(nb, dtype=np.uint32)
+        for k, (a, z) in enumerate(blocks):
+            A[k, : len(a)] = a
+            nsym[k], asz[k] = len(a), z
+        step_stride = 2 * a_stride
+        steps = np.zeros((nb, step_stride), dtype=np.uint64)
+        nsteps = np.zeros(nb, dtype=np.uint32)
+        rc = self.L.cjs_stage_bwtc_model(A.ctypes.data, a_stride, nb, nsym.ctypes.data, asz.ctypes.data, level, steps.ctypes.data,
+                                         step_stride, nsteps.ctypes.data, None)
+        if rc:
+            return rc, None
+        return 0, [steps[k, : min(int(nsteps[k]), step_stride)] if nsteps[k] <= step_stride else None for k in range(nb)]
+
+    def stage_bwtc_code(self, steps, first_byte, mode):
+        """the host range coder over a step list (cjs_stage_bwtc_code; mode 0 one thread, 1 split): (rc, bytes).  No GPU"""
+        steps = np.ascontiguousarray(steps, dtype=np.uint64)
+        keep = steps if steps.size else np.zeros(1, dtype=np.uint64)
+        out, out_n = u8p(), ctypes.c_size_t(0)
+        rc = self.L.cjs_stage_bwtc_code(keep.ctypes.data, steps.size, first_byte, mode, ctypes.byref(out), ctypes.byref(out_n))
+        if rc:
+            return rc, None
+        res = np.ctypeslib.as_array(out, shape=(max(out_n.value, 1),))[: out_n.value].copy() if out_n.value else np.empty(0, np.uint8)
+        self.L.cjs_free(out)
+        return 0, res
 
     def stage_bwt(self, data, block_len, cyclic):
         data = as_u8(data)

@@ -38,6 +38,46 @@ def test_compress_matches_reference(oracle, case):
     assert back is not None and back.size == data.size and np.array_equal(back, data)
 
 
+# step traces of the BWTC back half: every BWTC case up to 300000 input bytes (the larger ones add minutes of suffix sorting and
+# no new code path)
+BWTC_TRACED = [c for c in SMALL["cases"] if c["algo"] == "BWTC" and c["in_len"] <= 300000]
+
+
+@pytest.mark.parametrize("case", BWTC_TRACED, ids=_id)
+def test_bwtc_step_traces_make_the_stream(oracle, case):
+    data = recipes.build(case["recipe"])
+    level = case["level"]
+    rc, want = oracle.bwtc_compress(data, level)
+    assert rc == 0 and support.sha256(want) == case["out_sha256"]
+    rc, steps, prefix_n, first_byte, blocks = oracle.bwtc_stream_steps(data, level)
+    assert rc == 0
+    # magic, then the leading bytes of the size; its last byte is the coder's first
+    v, size = [], data.size + 1
+    while True:
+        v.append(size & 0x7F)
+        size >>= 7
+        if not size:
+            break
+    head = b"bwtc" + bytes(v[:0:-1])
+    assert want[:prefix_n].tobytes() == head and first_byte == (v[0] | 0x80)
+    rc, out, _ = oracle.rc_encode_steps(first_byte, steps)
+    assert rc == 0 and np.array_equal(out, want[prefix_n:])
+    # each block's slice is the model section of that block's RLE2 symbols
+    bs = level * 100000
+    assert len(blocks) == -(-data.size // bs)
+    for k, (lo, hi) in enumerate(blocks):
+        U, _ = oracle.bwt_sentinel(data[k * bs: (k + 1) * bs])
+        A, _, asz = oracle.mtf_rle2(U, U)
+        got, pos, _ = oracle.bwtc_model_steps(A[:-1], asz, level <= 5)
+        assert np.array_equal(got, steps[lo:hi]), "block %d" % k
+        assert pos.size == got.size and (pos.size == 0 or (int(pos[-1]) == A.size - 2 and np.all(np.diff(pos.astype(np.int64)) >= 0)))
+
+
+def test_rc_encode_steps_refuses_invalid_steps(oracle):
+    for w in (0, 1 | (3 << 16) | (3 << 32), (1 << 63) | 1 | (17 << 32), (1 << 63) | 2 | (255 << 16) | (8 << 32)):
+        assert oracle.rc_encode_steps(0x80, np.array([w], dtype=np.uint64))[0] == -5
+
+
 # tiny full streams recorded in SURVEY.md §8(c) (Bzip2 -9 / BWTC -9)
 SURVEY_STREAMS = [
     (b"", "425a683917724538509000000000", "627774638109ab000007"),
