@@ -853,6 +853,12 @@ int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint3
 //   -  host        exclusive prefix sum of the decoded lengths -> output offsets
 //   C  per share   RLE1 expansion + block CRCs per batch, D2H straight to the final offsets
 // No data moves between devices; the exchanged quantities are (end bit, count, crc) per candidate and a length per block.
+//
+// Five drivers sit on the phases: bunzip_core (single stream, shares over devices), dev_single_* (device-resident single stream),
+// dec_batch_group (host batch), dev_group_* (device-resident batch) and dec_step (streaming).  The glue between the phases is
+// written once: bz_header_check (_start_bunzip), WalkCands + walk_chain (candidate lookup, bz_walk, chain append),
+// chain_out_offsets (the prefix sum), group_layout / group_prepare / group_verdicts (a batch group, both forms), ShareScratch
+// (a phase's own scratch).  A driver holds what is particular to it: where the bytes come from and where they go.
 namespace {
 
 constexpr uint64_t DEC_BATCH_ELEMS = 1ull << 28;      // BWT bytes per inverse-BWT batch (scratch ~ 21 B each)
@@ -915,7 +921,6 @@ struct DecShare {
   std::vector<BlockOut> bos;
   uint8_t* d_tt = nullptr;            // decoded BWT bytes of a one-batch share, tt_stride per row (several batches: packed segments)
   std::vector<uint64_t> tt_ptr;       // per candidate: device address of its decoded bytes
-  size_t cand_base = 0;               // index of cands[0] in the job's candidate list
   // chain part
   size_t c0 = 0, c1 = 0;              // chain blocks [c0, c1) were decoded here
   uint8_t* d_w = nullptr;             // pre-RLE1 bytes of those blocks, contiguous in chain order
@@ -933,7 +938,7 @@ struct DecShare {
   }
   void drop(void* p) {
     if (arena) { for (size_t i = 0; i < abufs.size(); i++) if (abufs[i] == p) { abufs.erase(abufs.begin() + (long)i); arena->give(p); return; } return; }
-    for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; } DevPool::give(p);
+    for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; }
   }
   void release() {                    // on the share's device, once its stream has drained; again: nothing
     if (hipSetDevice(device) != hipSuccess) return;
@@ -946,6 +951,17 @@ struct DecShare {
   void release_keep_stream(Stream& to) { Stream keep = std::move(s); if (keep && hipSetDevice(device) == hipSuccess) (void)hipStreamSynchronize(keep); release(); to = std::move(keep); }
   uint32_t nrows_given() const { uint32_t r = 0; for (auto& c : cands) r += c.kind == 0; return r; }
   ~DecShare() { release(); }
+};
+
+// Scratch a phase takes from its share for its own duration.  done() gives all of it back, and is called only where the share's
+// stream has been synchronised behind the last kernel that used it (another thread may get the memory at once).  On an error exit
+// nothing goes back: the buffers stay with the share until DecShare::release(), which synchronises first.  So no destructor.
+struct ShareScratch {
+  DecShare* S; std::vector<void*> got;
+  explicit ShareScratch(DecShare* s) : S(s) {}
+  int take(void** p, size_t bytes) { const int rc = S->take(p, bytes); if (!rc) got.push_back(*p); return rc; }
+  void drop(void* p) { got.erase(std::find(got.begin(), got.end(), p)); S->drop(p); }      // one buffer, early
+  void done() { for (void* p : got) S->drop(p); got.clear(); }
 };
 
 struct DecJob {
@@ -977,9 +993,10 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   const size_t up_n = (size_t)(S->up_hi - S->up_lo);
   uint8_t* d_raw = nullptr; Cand* d_cand = nullptr; uint32_t* d_count = nullptr;
   uint32_t cand_cap = (uint32_t)((S->hi - S->lo) / 64 + 1024);      // grown to the exact count if a file of tiny streams has more
+  ShareScratch q(S);                                                    // (the upload stays with the share)
   int rc = S->take((void**)&d_raw, up_n + 256 + 16);
-  if (!rc) rc = S->take((void**)&d_cand, sizeof(Cand) * cand_cap);
-  if (!rc) rc = S->take((void**)&d_count, 64);
+  if (!rc) rc = q.take((void**)&d_cand, sizeof(Cand) * cand_cap);
+  if (!rc) rc = q.take((void**)&d_count, 64);
   if (rc) { S->rc = rc; return; }
   // keep the dword phase of the stream: the decoders fetch aligned big-endian words by absolute word index
   uint8_t* d_al = d_raw + (S->up_lo & 3u);
@@ -991,7 +1008,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   uint32_t *d_bst = nullptr, *d_ben = nullptr;
   const uint32_t nin = (uint32_t)S->bst.size();
   if (nin) {
-    if ((rc = S->take((void**)&d_bst, 4 * (size_t)nin)) != 0 || (rc = S->take((void**)&d_ben, 4 * (size_t)nin)) != 0) { S->rc = rc; return; }
+    if ((rc = q.take((void**)&d_bst, 4 * (size_t)nin)) != 0 || (rc = q.take((void**)&d_ben, 4 * (size_t)nin)) != 0) { S->rc = rc; return; }
     if (hipMemcpyAsync(d_bst, S->bst.data(), 4 * (size_t)nin, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_ben, S->ben.data(), 4 * (size_t)nin, hipMemcpyHostToDevice, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
     S->h2d += 8 * (size_t)nin;
@@ -1008,9 +1025,9 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   if (hipMemcpyAsync(&ncand, d_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
   S->d2h += 4;
   if (ncand > cand_cap) {                                             // more magics than planned for (many tiny member streams): scan again with room for all
-    S->drop(d_cand);
+    q.drop(d_cand);
     cand_cap = ncand;
-    if ((rc = S->take((void**)&d_cand, sizeof(Cand) * cand_cap)) != 0) { S->rc = rc; return; }
+    if ((rc = q.take((void**)&d_cand, sizeof(Cand) * cand_cap)) != 0) { S->rc = rc; return; }
     if (hipMemsetAsync(d_count, 0, 64, s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
     launch_scan();
     if (hipMemcpyAsync(&ncand, d_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { S->rc = CJS_E_HIP; return; }
@@ -1036,7 +1053,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   if (nin && ncand) {                                              // the batch scan left each candidate's input in pad
     std::vector<uint32_t> cend(2 * (size_t)ncand);
     for (uint32_t c = 0; c < ncand; c++) { cend[c] = S->ben[S->cands[c].pad]; cend[ncand + c] = S->bdsz[S->cands[c].pad]; }
-    if ((rc = S->take((void**)&d_cend, 8 * (size_t)ncand)) != 0) { S->rc = rc; return; }
+    if ((rc = q.take((void**)&d_cend, 8 * (size_t)ncand)) != 0) { S->rc = rc; return; }
     if (hipMemcpy(d_cend, cend.data(), 8 * (size_t)ncand, hipMemcpyHostToDevice) != hipSuccess) { S->rc = CJS_E_HIP; return; }
     S->h2d += 8 * (size_t)ncand;
   }
@@ -1065,20 +1082,20 @@ void dec_phase_a(DecJob* J, DecShare* S) {
   const bool single = nrows <= nr;
   uint8_t *d_ttb = nullptr, *d_ops = nullptr, *d_l0 = nullptr, *d_pl = nullptr, *d_sel = nullptr; uint32_t *d_opoff = nullptr, *d_nops = nullptr, *d_gstart = nullptr;
   RowDst* d_gdst = nullptr; RowTab* d_tabs = nullptr; uint16_t* d_syms = nullptr;
-  rc = S->take((void**)&d_ttb, (size_t)nr * dsz);
-  if (!rc) rc = S->take((void**)&d_bo, sizeof(BlockOut) * ncand);
-  if (!rc) rc = S->take((void**)&d_ops, (size_t)nr * ops_stride);
-  if (!rc) rc = S->take((void**)&d_opoff, 4 * (size_t)nr * ops_stride);
-  if (!rc) rc = S->take((void**)&d_l0, (size_t)nr * 256);
-  if (!rc) rc = S->take((void**)&d_pl, (size_t)nr * ops_stride);
-  if (!rc) rc = S->take((void**)&d_nops, 4 * (size_t)nr);
-  if (!rc) rc = S->take((void**)&d_tabs, sizeof(RowTab) * (size_t)nr);
-  if (!rc) rc = S->take((void**)&d_sel, (size_t)MAX_SELECTORS * nr);
-  if (!rc) rc = S->take((void**)&d_gstart, 4 * (size_t)(MAX_SELECTORS + 1) * nr);
-  if (!rc) rc = S->take((void**)&d_syms, 2 * (size_t)sym_groups * GROUP_SYMS * nr);
-  if (!rc && !single) rc = S->take((void**)&d_gdst, sizeof(RowDst) * (size_t)nr);
+  rc = single ? S->take((void**)&d_ttb, (size_t)nr * dsz) : q.take((void**)&d_ttb, (size_t)nr * dsz);      // (one batch: the rows are phase B's input)
+  if (!rc) rc = q.take((void**)&d_bo, sizeof(BlockOut) * ncand);
+  if (!rc) rc = q.take((void**)&d_ops, (size_t)nr * ops_stride);
+  if (!rc) rc = q.take((void**)&d_opoff, 4 * (size_t)nr * ops_stride);
+  if (!rc) rc = q.take((void**)&d_l0, (size_t)nr * 256);
+  if (!rc) rc = q.take((void**)&d_pl, (size_t)nr * ops_stride);
+  if (!rc) rc = q.take((void**)&d_nops, 4 * (size_t)nr);
+  if (!rc) rc = q.take((void**)&d_tabs, sizeof(RowTab) * (size_t)nr);
+  if (!rc) rc = q.take((void**)&d_sel, (size_t)MAX_SELECTORS * nr);
+  if (!rc) rc = q.take((void**)&d_gstart, 4 * (size_t)(MAX_SELECTORS + 1) * nr);
+  if (!rc) rc = q.take((void**)&d_syms, 2 * (size_t)sym_groups * GROUP_SYMS * nr);
+  if (!rc && !single) rc = q.take((void**)&d_gdst, sizeof(RowDst) * (size_t)nr);
   uint32_t* d_rlim = nullptr;
-  if (!rc && nin) rc = S->take((void**)&d_rlim, 4 * (size_t)nr);
+  if (!rc && nin) rc = q.take((void**)&d_rlim, 4 * (size_t)nr);
   if (rc) { S->rc = rc; return; }
   if (single) S->d_tt = d_ttb;
   std::vector<RowDst> gdst(single ? 0 : nr);
@@ -1136,9 +1153,6 @@ void dec_phase_a(DecJob* J, DecShare* S) {
     }
     c0 = c1;
   }
-  S->drop(d_ops); S->drop(d_opoff); S->drop(d_l0); S->drop(d_pl); S->drop(d_nops); S->drop(d_tabs); S->drop(d_sel); S->drop(d_gstart); S->drop(d_syms);
-  if (!single) { S->drop(d_ttb); S->drop(d_gdst); }
-  if (nin) S->drop(d_rlim);
   if (env_debug()) {
     uint64_t clk[8];
     if (!nin && hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_dec_clk), sizeof clk) == hipSuccess) {
@@ -1148,8 +1162,7 @@ void dec_phase_a(DecJob* J, DecShare* S) {
     fprintf(stderr, "[cjs dec] share on device %d: bytes [%llu, %llu) uploaded [%llu, %llu) = %zu B, %u candidates\n", S->device, (unsigned long long)S->lo,
             (unsigned long long)S->hi, (unsigned long long)S->up_lo, (unsigned long long)S->up_hi, up_n, ncand);
   }
-  S->drop(d_cand); S->drop(d_count); S->drop(d_bo);
-  if (nin) { S->drop(d_bst); S->drop(d_ben); if (d_cend) S->drop(d_cend); }      // (batch: the phase clock of candidate 0 is not kept)
+  q.done();                                                             // (every batch ended with the stream drained)
   S->ms_a = ms_since(T0);
 }
 
@@ -1200,20 +1213,20 @@ void dec_phase_b(DecJob* J, DecShare* S) {
       J->chain[k].woff = (uint32_t)(S->ebase[k - S->c0] - e0);
       J->chain[k].off = strided ? (uint32_t)(k - b0) * seg_stride : J->chain[k].woff;
     }
-    IbScratch q;
-    rc = S->take((void**)&q.d_blocks, sizeof(IbBlock) * nb);
-    if (!rc) rc = S->take((void**)&q.key0, 4 * (size_t)M + 64); if (!rc) rc = S->take((void**)&q.key1, 4 * (size_t)M + 64);
-    if (!strided) { if (!rc) rc = S->take((void**)&q.val0, 4 * (size_t)M + 64); if (!rc) rc = S->take((void**)&q.val1, 4 * (size_t)M + 64); }
-    if (!rc) rc = S->take((void**)&q.snext, 4 * (size_t)nb * spl_stride); if (!rc) rc = S->take((void**)&q.ssteps, 4 * (size_t)nb * spl_stride);
-    if (!rc) rc = S->take((void**)&q.srank, 4 * (size_t)nb * spl_stride); if (!rc) rc = S->take((void**)&q.d_err, 4 * (size_t)nb);
-    if (!rc) rc = S->take((void**)&q.resume, 4 * (size_t)nb * spl_stride);
+    IbScratch q; ShareScratch g(S);
+    rc = g.take((void**)&q.d_blocks, sizeof(IbBlock) * nb);
+    if (!rc) rc = g.take((void**)&q.key0, 4 * (size_t)M + 64); if (!rc) rc = g.take((void**)&q.key1, 4 * (size_t)M + 64);
+    if (!strided) { if (!rc) rc = g.take((void**)&q.val0, 4 * (size_t)M + 64); if (!rc) rc = g.take((void**)&q.val1, 4 * (size_t)M + 64); }
+    if (!rc) rc = g.take((void**)&q.snext, 4 * (size_t)nb * spl_stride); if (!rc) rc = g.take((void**)&q.ssteps, 4 * (size_t)nb * spl_stride);
+    if (!rc) rc = g.take((void**)&q.srank, 4 * (size_t)nb * spl_stride); if (!rc) rc = g.take((void**)&q.d_err, 4 * (size_t)nb);
+    if (!rc) rc = g.take((void**)&q.resume, 4 * (size_t)nb * spl_stride);
     // (the first walk's kept bytes: without them -- one large block among very many tiny ones would ask for SEG_CAP x 14,066 bytes for
     // each -- the second walk does all the work, as it does for the sentinel form)
     const uint64_t seg_bytes = (uint64_t)nb * spl_stride * SEG_CAP;
-    if (!rc && seg_bytes <= (8ull << 30) && S->take((void**)&q.seg, (size_t)seg_bytes) != 0) q.seg = nullptr;
+    if (!rc && seg_bytes <= (8ull << 30) && g.take((void**)&q.seg, (size_t)seg_bytes) != 0) q.seg = nullptr;
     const uint32_t tps = (seg_stride + RS_TILE - 1) / RS_TILE;
     const size_t T = strided ? (size_t)nb * tps + 1 : ((size_t)M + RS_TILE - 1) / RS_TILE + 1;
-    if (!rc) rc = S->take((void**)&q.sw.hist, BwtWork::hist_words(T) * 4); if (!rc) rc = S->take((void**)&q.sw.bintot, 256 * 4 * (size_t)(strided ? nb : 1u));
+    if (!rc) rc = g.take((void**)&q.sw.hist, BwtWork::hist_words(T) * 4); if (!rc) rc = g.take((void**)&q.sw.bintot, 256 * 4 * (size_t)(strided ? nb : 1u));
     q.sw.hist_tiles = (uint32_t)T; q.sw.bintot_segs = strided ? nb : 1u;
     if (!rc && hipMemcpyAsync(q.d_blocks, J->chain.data() + b0, sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc && hipMemsetAsync(q.d_err, 0, 4 * (size_t)nb, s) != hipSuccess) rc = CJS_E_HIP;
@@ -1249,14 +1262,16 @@ void dec_phase_b(DecJob* J, DecShare* S) {
         hipMemcpyAsync(errs.data(), q.d_err, 4 * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = CJS_E_HIP; break; }
     S->h2d += sizeof(IbBlock) * (size_t)nb; S->d2h += (sizeof(IbBlock) + 4) * (size_t)nb;
     for (uint32_t k = 0; k < nb; k++) if (errs[k] <= 0) rc = CJS_E_DATA_ERROR;      // cannot happen: the walk makes >= 1 step
-    S->drop(q.d_blocks); S->drop(q.key0); S->drop(q.key1); if (q.val0) S->drop(q.val0); if (q.val1) S->drop(q.val1); S->drop(q.snext); S->drop(q.ssteps);
-    S->drop(q.srank); S->drop(q.d_err); S->drop(q.resume); if (q.seg) S->drop(q.seg); S->drop(q.sw.hist); S->drop(q.sw.bintot);
+    g.done();
     b0 = b1;
   }
   if (S->d_tt) { S->drop(S->d_tt); S->d_tt = nullptr; }
   S->rc = rc;
   S->ms_b = ms_since(T0);
 }
+
+// Bad block CRC (:1756-1761): the detail text
+void bad_crc_detail(char* d, size_t cap, uint32_t got, uint32_t expected) { snprintf(d, cap, "Bad block CRC (got %x expected %x)", got, expected); }
 
 // ---- phase C: RLE1 expansion to the final byte offsets, block CRC check, D2H
 void dec_phase_c(DecJob* J, DecShare* S) {
@@ -1280,12 +1295,13 @@ void dec_phase_c(DecJob* J, DecShare* S) {
     // (a device sink: unrle1_write stores only inside [out_off, out_off + out_len) of each block, crc_ranges reads aligned 16-byte
     // pieces that hold a byte of the range: the caller's buffer takes the bytes at their final offsets)
     IbBlock* d_blocks = nullptr; uint8_t* d_out = J->dev_out ? J->dev_out + o0 : nullptr; RleBlock* d_ranges = nullptr; uint32_t *d_nb = nullptr, *d_seg = nullptr, *d_crc = nullptr;
-    rc = S->take((void**)&d_blocks, sizeof(IbBlock) * nb);
-    if (!rc && !J->dev_out) rc = S->take((void**)&d_out, (size_t)obytes + 64);
-    if (!rc) rc = S->take((void**)&d_ranges, sizeof(RleBlock) * nb);
-    if (!rc) rc = S->take((void**)&d_nb, 64);
-    if (!rc) rc = S->take((void**)&d_seg, 4 * (size_t)nb * need_segs);
-    if (!rc) rc = S->take((void**)&d_crc, 4 * (size_t)nb);
+    ShareScratch g(S);
+    rc = g.take((void**)&d_blocks, sizeof(IbBlock) * nb);
+    if (!rc && !J->dev_out) rc = g.take((void**)&d_out, (size_t)obytes + 64);
+    if (!rc) rc = g.take((void**)&d_ranges, sizeof(RleBlock) * nb);
+    if (!rc) rc = g.take((void**)&d_nb, 64);
+    if (!rc) rc = g.take((void**)&d_seg, 4 * (size_t)nb * need_segs);
+    if (!rc) rc = g.take((void**)&d_crc, 4 * (size_t)nb);
     if (!rc && hipMemcpyAsync(d_blocks, blk.data(), sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
     if (rc) break;
     hipLaunchKernelGGL(unrle1_write, dim3(S->carry_tiles, nb), dim3(1024), 0, s, S->d_w + e0, d_blocks, S->d_carry + (size_t)(b0 - S->c0) * S->carry_tiles, S->carry_tiles, d_out);
@@ -1298,11 +1314,11 @@ void dec_phase_c(DecJob* J, DecShare* S) {
     if (!rc) { S->h2d += sizeof(IbBlock) * (size_t)nb; S->d2h += 4 * (size_t)nb + (J->host ? (size_t)obytes : 0); }
     if (!rc && J->batch) for (uint32_t k = 0; k < nb; k++) J->crc_got[b0 + k] = crcs[k];      // (each input's verdict: the batch's host side)
     else if (!rc) for (uint32_t k = 0; k < nb; k++) if (crcs[k] != blk[k].crc) {                    // Bad block CRC (:1756-1761)
-      snprintf(S->detail, sizeof S->detail, "Bad block CRC (got %x expected %x)", crcs[k], blk[k].crc);
+      bad_crc_detail(S->detail, sizeof S->detail, crcs[k], blk[k].crc);
       if (env_debug()) fprintf(stderr, "[cjs dec] block %zu: Bad block CRC (got %08x expected %08x) out_len %u\n", b0 + k, crcs[k], blk[k].crc, blk[k].out_len);
       rc = CJS_E_DATA_ERROR; break;
     }
-    S->drop(d_blocks); if (!J->dev_out) S->drop(d_out); S->drop(d_ranges); S->drop(d_nb); S->drop(d_seg); S->drop(d_crc);
+    g.done();
     b0 = b1;
   }
   S->rc = rc;
@@ -1317,6 +1333,18 @@ int for_each_share(std::vector<DecShare>& sh, DecJob* J, F fn) {
   for (auto& x : sh) if (x.rc) { if (x.detail[0]) set_detail("%s", x.detail); return x.rc; }
   return 0;
 }
+
+// _start_bunzip (:1408-1427) on the first four bytes h of an input (or of a member stream) of n bytes: 0 and the level, or
+// CJS_E_NOT_BZIP_DATA and the detail text in *why (the caller sets it, or stores it with its input)
+int bz_header_check(const uint8_t* h, size_t n, int* level, const char** why) {
+  if (n < 4 || h[0] != 'B' || h[1] != 'Z' || h[2] != 'h') { *why = "bad magic"; return CJS_E_NOT_BZIP_DATA; }
+  *level = h[3] - '0';
+  if (*level < 1 || *level > 9) { *why = "level out of range"; return CJS_E_NOT_BZIP_DATA; }
+  return 0;
+}
+
+// bytes a block can span: 20 bits per symbol + tables (the overlap of two shares; a streaming decoder's window behind a chunk)
+constexpr uint64_t dec_extent(uint32_t tt_stride) { return (uint64_t)tt_stride * 5 / 2 + 65536; }
 
 // The scratch rows are sized for the largest level any member stream can have: a multistream file may change level
 // between members (:1787-1792), so every byte-aligned "BZh<d>" followed by a block or end-of-stream magic counts.
@@ -1399,14 +1427,64 @@ int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_st
       const uint64_t byte = (pos + 7) / 8;
       if (!multistream || byte >= n) return stop(WALK_ENDED);
       // _start_bunzip again, byte aligned (:1787-1792)
-      if (byte + 4 > n || in[byte] != 'B' || in[byte + 1] != 'Z' || in[byte + 2] != 'h') { set_detail("bad magic"); return CJS_E_NOT_BZIP_DATA; }
-      const int lv = in[byte + 3] - '0';
-      if (lv < 1 || lv > 9) { set_detail("level out of range"); return CJS_E_NOT_BZIP_DATA; }
+      uint8_t h[4] = {0, 0, 0, 0};
+      for (uint64_t i = 0; i < 4 && byte + i < n; i++) h[i] = in[byte + i];
+      int lv = 0; const char* why = nullptr;
+      if (bz_header_check(h, (size_t)(n - byte), &lv, &why)) { set_detail("%s", why); return CJS_E_NOT_BZIP_DATA; }
       dbuf_size = 100000u * (uint32_t)lv;
       if (dbuf_size > tt_stride) return CJS_E_UNSUPPORTED;      // cannot happen: the pre-scan saw this header
       pos = (byte + 4) * 8; stream_crc = 0;
     }
   }
+}
+
+// The candidates a walk runs over: the sorted bits of one share's candidates, or of all the shares of a single-stream call in
+// share order (their byte ranges ascend), each with its share and its index there.  base: the bit of the upload at which the
+// input being walked starts (a batch group: 8 x bst[i]), so that find() takes the walk's own positions.
+struct WalkCands {
+  const DecShare* sh;
+  std::vector<uint64_t> bit; std::vector<uint32_t> share, local;
+  uint64_t base = 0;
+  WalkCands(const DecShare* shares, size_t nsh) : sh(shares) {
+    for (size_t i = 0; i < nsh; i++)
+      for (size_t k = 0; k < sh[i].cands.size(); k++) { bit.push_back(sh[i].cands[k].bit); share.push_back((uint32_t)i); local.push_back((uint32_t)k); }
+  }
+  long find(uint64_t pos) const {
+    const auto it = std::lower_bound(bit.begin(), bit.end(), base + pos);
+    return (it != bit.end() && *it == base + pos) ? (long)(it - bit.begin()) : -1;
+  }
+  uint32_t kind(long ci) const { return sh[share[(size_t)ci]].cands[local[(size_t)ci]].kind; }
+  const BlockOut& bo(long ci) const { return sh[share[(size_t)ci]].bos[local[(size_t)ci]]; }
+  IbBlock chain_block(long ci) const {
+    const BlockOut& b = bo(ci);
+    IbBlock ib; ib.tt = sh[share[(size_t)ci]].tt_ptr[local[(size_t)ci]]; ib.count = b.count; ib.orig = b.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = b.crc;
+    return ib;
+  }
+};
+
+// bz_walk over C, the good blocks appended to J.chain.  met(ci, pos) is called for every candidate the walk accepts: an
+// end-of-stream candidate when the walk finds it, before it reads the record behind the magic; a block once it is on the chain
+// (a resumed walk's *st is then still the state in front of the block).
+template <typename Bytes, typename Met>
+int walk_chain(DecJob& J, const WalkCands& C, const Bytes& in, size_t n, int multistream, int mode, Met met, WalkState* st = nullptr) {
+  long last = -1;
+  return bz_walk(in, n, multistream, mode, J.tt_stride, J.timing,
+                 [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
+                   if ((last = C.find(pos)) < 0) return false;
+                   *kind = C.kind(last); *bo = C.bo(last); bo->end_bit -= C.base;
+                   if (*kind) met(last, pos);
+                   return true;
+                 },
+                 [&](const BlockOut&, uint64_t pos) { J.chain.push_back(C.chain_block(last)); met(last, pos); }, st);
+}
+inline void met_nothing(long, uint64_t) {}
+
+// exclusive prefix sum of the chain's decoded lengths (phase B's) -> J.out_off; returns the total
+uint64_t chain_out_offsets(DecJob& J) {
+  const size_t nb = J.chain.size();
+  J.out_off.assign(nb + 1, 0);
+  for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
+  return J.out_off[nb];
 }
 
 }  // namespace
@@ -1418,10 +1496,8 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   if (tab_n) *tab_n = 0;
   clear_detail();
   CJS_TRY(select_device(opts));
-  // _start_bunzip (:1408-1427)
-  if (n < 4 || in[0] != 'B' || in[1] != 'Z' || in[2] != 'h') { set_detail("bad magic"); return CJS_E_NOT_BZIP_DATA; }
-  int level = in[3] - '0';
-  if (level < 1 || level > 9) { set_detail("level out of range"); return CJS_E_NOT_BZIP_DATA; }
+  int level = 0; const char* why = nullptr;
+  if (bz_header_check(in, n, &level, &why)) { set_detail("%s", why); return CJS_E_NOT_BZIP_DATA; }
   int ndev = 0, dev0 = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev0) != hipSuccess) return CJS_E_NO_DEVICE;
 
@@ -1434,7 +1510,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   if (nsh < 1 || mode == 2) nsh = 1;
   if (nsh > 64) nsh = 64;
   if ((size_t)nsh * 65536 > n) nsh = (uint32_t)(n / 65536 ? n / 65536 : 1);     // tiny inputs: one share
-  const uint64_t overlap = (uint64_t)J.tt_stride * 5 / 2 + 65536;               // one block at 20 bits per symbol + tables
+  const uint64_t overlap = dec_extent(J.tt_stride);
   RestoreDevice restore{dev0};                                                  // after the shares have been released
   std::vector<DecShare> sh(nsh);
   for (uint32_t i = 0; i < nsh; i++) {
@@ -1454,40 +1530,17 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   const double ms_a = ms_since(T0);
 
   // ---- chain walk over all shares' candidates (Bunzip.decode :1776-1794)
-  std::vector<uint64_t> cbit; std::vector<uint32_t> cshare, clocal;
-  for (uint32_t i = 0; i < nsh; i++) {
-    sh[i].cand_base = cbit.size();
-    for (size_t k = 0; k < sh[i].cands.size(); k++) { cbit.push_back(sh[i].cands[k].bit); cshare.push_back(i); clocal.push_back((uint32_t)k); }
-  }
-  auto find = [&](uint64_t bit) -> long {
-    const auto it = std::lower_bound(cbit.begin(), cbit.end(), bit);
-    return (it != cbit.end() && *it == bit) ? (long)(it - cbit.begin()) : -1;
-  };
+  const WalkCands C(sh.data(), nsh);
   std::vector<uint32_t> chain_share;
-  auto take_block = [&](long ci, uint64_t bitpos) {
-    const DecShare& S = sh[cshare[(size_t)ci]];
-    const BlockOut& bo = S.bos[clocal[(size_t)ci]];
-    IbBlock ib; ib.tt = S.tt_ptr[clocal[(size_t)ci]]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
-    J.chain.push_back(ib); J.chain_bits.push_back(bitpos); chain_share.push_back(cshare[(size_t)ci]);
-  };
+  auto met = [&](long ci, uint64_t pos) { if (C.kind(ci) == 0) { J.chain_bits.push_back(pos); chain_share.push_back(C.share[(size_t)ci]); } };
   if (mode == 2) {                                               // reader.seekBit(pos); _get_next_block() (:1803-1805)
-    const long ci = find(at_bit);
+    const long ci = C.find(at_bit);
     if (ci < 0) rc = CJS_E_NOT_BZIP_DATA;
-    else if (sh[cshare[(size_t)ci]].cands[clocal[(size_t)ci]].kind == 0) {
-      rc = bz_block_verdict(sh[cshare[(size_t)ci]].bos[clocal[(size_t)ci]], 100000u * (uint32_t)level, at_bit, J.timing);
-      if (!rc) take_block(ci, at_bit);
+    else if (C.kind(ci) == 0) {
+      rc = bz_block_verdict(C.bo(ci), 100000u * (uint32_t)level, at_bit, J.timing);
+      if (!rc) { J.chain.push_back(C.chain_block(ci)); met(ci, at_bit); }
     }
-  } else {
-    long last = -1;
-    rc = bz_walk(in, n, multistream, mode, J.tt_stride, J.timing,
-                 [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
-                   if ((last = find(pos)) < 0) return false;
-                   const DecShare& S = sh[cshare[(size_t)last]];
-                   *kind = S.cands[clocal[(size_t)last]].kind; *bo = S.bos[clocal[(size_t)last]];
-                   return true;
-                 },
-                 [&](const BlockOut&, uint64_t pos) { take_block(last, pos); });
-  }
+  } else rc = walk_chain(J, C, in, n, multistream, mode, met);
   // The reference decodes block after block and checks every block's CRC before it reads on (:1756-1761), so an error met
   // by the walk (bad stream CRC, damaged later block, broken chain) is reported only if every block in front of it
   // passes its own CRC check: keep it pending and run the rest of the pipeline, without output, over the chain so far.
@@ -1511,9 +1564,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   rc = for_each_share(sh, &J, dec_phase_b);
   if (rc) return rc;
   const double ms_b = ms_since(T1);
-  J.out_off.assign(nb + 1, 0);
-  for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
-  const uint64_t total = J.out_off[nb];
+  const uint64_t total = chain_out_offsets(J);
   if (out && !pending_rc) { J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1); if (!J.host) return CJS_E_OUT_OF_MEMORY; }
   const auto T2 = std::chrono::steady_clock::now();
   rc = for_each_share(sh, &J, dec_phase_c);
@@ -1554,6 +1605,118 @@ extern "C" long cjs_bzip2_table(const uint8_t* in, size_t n, int multistream, ui
   CJS_GUARD_END((long)CJS_E_OUT_OF_MEMORY, (long)CJS_E_HIP)
 }
 
+// ---------------------------------------------------------------- batch group (host form: dec_batch_group, device form: dev_group_*)
+// Inputs go in groups of up to BATCH_DEC_GROUP_BYTES, each group one upload with every input at a 4-byte-aligned offset and one
+// share of phases A-C: one magic scan over the group (a candidate never straddles two inputs), block decode of all candidates
+// with every read bounded by the candidate's own input, then the walk of each input over the candidates of its bytes, phase B
+// over all chain blocks, phase C with a CRC verdict per block.  An input larger than a group goes through the single-stream
+// path.  What the two forms share is here; where the bytes come from and where they go is theirs.  See DESIGN.md §6c.
+namespace {
+
+constexpr size_t BATCH_DEC_GROUP_BYTES = (size_t)256 << 20;
+
+size_t dec_group_bytes() {
+  static const size_t g = getenv("CJS_DEC_GROUP_BYTES") ? (size_t)strtoull(getenv("CJS_DEC_GROUP_BYTES"), nullptr, 10) : BATCH_DEC_GROUP_BYTES;   // (tests shrink it)
+  return g && g <= ((size_t)1 << 30) ? g : BATCH_DEC_GROUP_BYTES;      // (group offsets are 32-bit)
+}
+
+// the group that starts at input k0 (n[k0] <= G): inputs [k0, k1) whose 4-byte-aligned sizes come to G at most
+size_t dec_group_end(const size_t* n, size_t count, size_t k0, size_t G) {
+  size_t k1 = k0, bytes = 0;
+  while (k1 < count && n[k1] <= G && (k1 == k0 || bytes + n[k1] <= G)) bytes += (n[k1++] + 3) & ~(size_t)3;
+  return k1;
+}
+
+struct BatchGroup {
+  size_t k0 = 0, k1 = 0;              // inputs [k0, k1) of the call
+  std::vector<uint8_t> ok;            // input k0 + i passed _start_bunzip
+  std::vector<size_t> ch0, ch1;       // input k0 + i's chain blocks
+};
+
+// The layout of a group: _start_bunzip (:1408-1427) of every input, the accepted ones at 4-byte-aligned offsets of one upload
+// (S.bst / S.ben), each with the block size of its own single call (S.bdsz: the kernels' limits for its blocks), the rows sized
+// for the largest of them.  hdr(k): the first bytes of input k; level(k, lv): its largest member level, lv being its header's;
+// placed(k, at): input k lies at byte `at` of the upload.
+template <typename Hdr, typename Level, typename Placed>
+void group_layout(DecJob& J, DecShare& S, BatchGroup& G, size_t k0, size_t k1, const size_t* n, int32_t* status, std::vector<std::string>& detail,
+                  Hdr hdr, Level level, Placed placed) {
+  const size_t items = k1 - k0;
+  G.k0 = k0; G.k1 = k1; G.ok.assign(items, 0);
+  J.mode = 0; J.batch = true; J.timing = env_debug();
+  S.bst.resize(items); S.ben.resize(items); S.bdsz.assign(items, 100000u);
+  int max_level = 1;
+  size_t bytes = 0;
+  for (size_t i = 0; i < items; i++) {
+    const size_t k = k0 + i;
+    S.bst[i] = S.ben[i] = (uint32_t)bytes;
+    int lv = 0; const char* why = nullptr;
+    if ((status[k] = bz_header_check(hdr(k), n[k], &lv, &why)) != 0) { detail[k] = why; continue; }
+    const int own = level(k, lv);
+    S.bdsz[i] = 100000u * (uint32_t)own;
+    max_level = std::max(max_level, own);
+    G.ok[i] = 1;
+    placed(k, bytes);
+    S.ben[i] = (uint32_t)(bytes + n[k]);
+    bytes = (bytes + n[k] + 3) & ~(size_t)3;
+  }
+  J.tt_stride = 100000u * (uint32_t)max_level;
+  J.n = bytes;
+  S.lo = 0; S.hi = bytes; S.up_lo = 0; S.up_hi = bytes;
+}
+
+// A laid-out group up to phase B: phase A over the upload, the walk of every accepted input over the candidates of its bytes
+// (walk(k, C), C.base being the input's first bit of the upload; its error is pending: a bad block CRC in front of it wins),
+// phase B over all chain blocks, the output offsets.  A failure of the call, or 0 and the bytes of the group's output.
+template <typename Walk>
+int group_prepare(DecJob& J, DecShare& S, BatchGroup& G, int32_t* status, std::vector<std::string>& detail, Walk walk, uint64_t* total) {
+  if (J.n) {
+    guarded(S.rc, [&] { dec_phase_a(&J, &S); });
+    if (S.rc) return S.rc;
+  }
+  WalkCands C(&S, 1);
+  const size_t items = G.k1 - G.k0;
+  G.ch0.assign(items, 0); G.ch1.assign(items, 0);
+  for (size_t i = 0; i < items; i++) {
+    G.ch0[i] = G.ch1[i] = J.chain.size();
+    if (!G.ok[i]) continue;
+    C.base = 8ull * S.bst[i];
+    clear_detail();
+    const int rc = walk(G.k0 + i, C);
+    G.ch1[i] = J.chain.size();
+    if (rc) { status[G.k0 + i] = rc; detail[G.k0 + i] = cjs_last_error_detail(); }
+  }
+  clear_detail();
+  S.c0 = 0; S.c1 = J.chain.size();
+  if (S.c1) {
+    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
+    // (phase B's own CJS_E_UNSUPPORTED / CJS_E_DATA_ERROR exits cannot happen -- a block holds <= 900000 bytes, a walk makes a step;
+    // should one, it is a failure of the call, reported as one of the call's codes)
+    if (S.rc == CJS_E_OUT_OF_MEMORY || S.rc == CJS_E_NO_DEVICE) return S.rc;
+    if (S.rc) return CJS_E_HIP;
+  }
+  *total = chain_out_offsets(J);
+  return 0;
+}
+
+// After phase C (J.crc_got): input k's verdict is the single call's -- the first block of its chain, in stream order, whose CRC
+// fails (:1756-1761); else what its header or its walk left in status / detail; else success -- and its bytes: off from `base`
+// on, len 0 for a failed input.
+void group_verdicts(const DecJob& J, const BatchGroup& G, size_t base, size_t* off, size_t* len, int32_t* status, std::vector<std::string>& detail) {
+  for (size_t i = 0; i < G.k1 - G.k0; i++) {
+    const size_t k = G.k0 + i;
+    for (size_t b = G.ch0[i]; b < G.ch1[i]; b++) if (J.crc_got[b] != J.chain[b].crc) {
+      char d[96];
+      bad_crc_detail(d, sizeof d, J.crc_got[b], J.chain[b].crc);
+      status[k] = CJS_E_DATA_ERROR; detail[k] = d;
+      break;
+    }
+    off[k] = base + (size_t)J.out_off[G.ch0[i]];
+    len[k] = status[k] ? 0 : (size_t)(J.out_off[G.ch1[i]] - J.out_off[G.ch0[i]]);
+  }
+}
+
+}  // namespace
+
 // ---------------------------------------------------------------- device-resident source and sink (cjs_bzip2_decompress_device)
 // bunzip_core with the input and the output in the GPU's memory.  The host path reads its host copy of the input in four places;
 // each is a device pass here (dec_device.hip): the header (dd_headers, one 8-byte D2H), the level pre-scan of a multistream input
@@ -1590,14 +1753,15 @@ int dev_eos_gather(DecShare* S, std::vector<uint8_t>& rec, std::vector<long>& re
   rec.assign((size_t)ne * EOS_REC, 0);
   if (!ne) return 0;
   uint64_t* d_tab = nullptr; uint8_t* d_rec = nullptr;
-  CJS_TRY(S->take((void**)&d_tab, 16 * (size_t)ne));
-  CJS_TRY(S->take((void**)&d_rec, (size_t)ne * EOS_REC));
+  ShareScratch q(S);
+  CJS_TRY(q.take((void**)&d_tab, 16 * (size_t)ne));
+  CJS_TRY(q.take((void**)&d_rec, (size_t)ne * EOS_REC));
   if (hipMemcpyAsync(d_tab, tab.data(), 16 * (size_t)ne, hipMemcpyHostToDevice, S->s) != hipSuccess) return CJS_E_HIP;
   launch_dev_eos_bytes(S->s, S->d_in, d_tab, ne, d_rec);
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rec.data(), d_rec, (size_t)ne * EOS_REC, hipMemcpyDeviceToHost, S->s) != hipSuccess ||
       hipStreamSynchronize(S->s) != hipSuccess) return CJS_E_HIP;
   S->h2d += 16 * (size_t)ne; S->d2h += (size_t)ne * EOS_REC;
-  S->drop(d_tab); S->drop(d_rec);
+  q.done();
   return 0;
 }
 
@@ -1609,9 +1773,8 @@ struct DevUnit {
   std::vector<uint8_t> rec; std::vector<long> rec_of;      // the end-of-stream candidates' bytes (dev_eos_gather)
   int pending = 0; char pending_detail[192] = {0};         // single: the walk's error, reported if every block in front passes its CRC
   uint64_t total = 0;                                       // bytes of the unit's output
-  size_t k0 = 0, k1 = 0;                                    // batch group: inputs [k0, k1) of the call
-  std::vector<size_t> ch0, ch1;                             //   input k0 + i's chain blocks
-  std::vector<GatherPiece> pieces;                          //   the gather of the inputs into the group layout
+  BatchGroup G;                                             // batch: inputs [G.k0, G.k1) of the call (a single stream of its own: one)
+  std::vector<GatherPiece> pieces;                          // batch group: the gather of the inputs into the group layout
 };
 
 // _start_bunzip's bytes of `count` inputs (input k = d_in[off[k] .. off[k+1])), and for a multistream call the largest member level
@@ -1622,57 +1785,31 @@ int dev_headers(DecShare& S, const uint8_t* d_in, const std::vector<uint64_t>& o
   if (off.back() == off.front()) return 0;                       // (no bytes at all: every header is empty)
   if (hipSetDevice(S.device) != hipSuccess || (!S.s && hipStreamCreate(S.s.put()) != hipSuccess)) return CJS_E_HIP;
   uint64_t* d_off = nullptr; DevHdr* d_hdr = nullptr;
-  CJS_TRY(S.take((void**)&d_off, 8 * off.size()));
-  CJS_TRY(S.take((void**)&d_hdr, sizeof(DevHdr) * count));
+  ShareScratch q(&S);
+  CJS_TRY(q.take((void**)&d_off, 8 * off.size()));
+  CJS_TRY(q.take((void**)&d_hdr, sizeof(DevHdr) * count));
   if (hipMemcpyAsync(d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, S.s) != hipSuccess) return CJS_E_HIP;
   launch_dev_headers(S.s, d_in, d_off, (uint32_t)count, multistream, off.front(), off.back(), d_hdr);
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hd.data(), d_hdr, sizeof(DevHdr) * count, hipMemcpyDeviceToHost, S.s) != hipSuccess ||
       hipStreamSynchronize(S.s) != hipSuccess) return CJS_E_HIP;
   S.h2d += 8 * off.size(); S.d2h += sizeof(DevHdr) * count;
-  S.drop(d_off); S.drop(d_hdr);
+  q.done();
   return 0;
 }
 
-// the walk over the candidates of one input whose bytes start at byte `bst` of the share's upload
-int dev_walk(DevUnit& U, const DevHdr& hd, size_t n, uint64_t bst, int multistream, const std::vector<uint64_t>& cbit) {
-  DecShare& S = U.S;
+// the walk of one input over the candidates of its bytes (C.base: its first bit of the share's upload): the bytes behind an
+// end-of-stream magic come from the candidate's record
+int dev_walk(DevUnit& U, const WalkCands& C, const DevHdr& hd, size_t n, int multistream) {
   DevWalkBytes acc{hd.h};
-  const uint64_t base = 8 * bst;
-  long last = -1;
-  return bz_walk(acc, n, multistream, 0, U.J.tt_stride, U.J.timing,
-                 [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
-                   const auto it = std::lower_bound(cbit.begin(), cbit.end(), base + pos);
-                   if (it == cbit.end() || *it != base + pos) return false;
-                   last = (long)(it - cbit.begin());
-                   *kind = S.cands[(size_t)last].kind; *bo = S.bos[(size_t)last]; bo->end_bit -= base;
-                   if (*kind) { acc.rec = U.rec.data() + (size_t)U.rec_of[(size_t)last] * EOS_REC; acc.at = ((pos + 48) >> 3); }
-                   return true;
-                 },
-                 [&](const BlockOut& bo, uint64_t) {
-                   IbBlock ib; ib.tt = S.tt_ptr[(size_t)last]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
-                   U.J.chain.push_back(ib);
-                 });
-}
-
-int dev_phase_b(DevUnit& U) {
-  const size_t nb = U.J.chain.size();
-  U.total = 0;
-  U.J.out_off.assign(nb + 1, 0);
-  if (!nb) return 0;
-  U.S.c0 = 0; U.S.c1 = nb;
-  guarded(U.S.rc, [&] { dec_phase_b(&U.J, &U.S); });
-  if (U.S.rc) return U.S.rc;
-  for (size_t k = 0; k < nb; k++) U.J.out_off[k + 1] = U.J.out_off[k] + U.J.chain[k].out_len;
-  U.total = U.J.out_off[nb];
-  return 0;
+  return walk_chain(U.J, C, acc, n, multistream, 0, [&](long ci, uint64_t pos) {
+    if (C.kind(ci)) { acc.rec = U.rec.data() + (size_t)U.rec_of[(size_t)ci] * EOS_REC; acc.at = (pos + 48) >> 3; }
+  });
 }
 
 // single stream, up to phase B: 0 (U.pending, U.total set) or what cjs_bzip2_decompress returns before its output stage
 int dev_single_prepare(DevUnit& U, const uint8_t* d_in, size_t n, int multistream, const DevHdr& hd) {
-  // _start_bunzip (:1408-1427)
-  if (n < 4 || hd.h[0] != 'B' || hd.h[1] != 'Z' || hd.h[2] != 'h') { set_detail("bad magic"); return CJS_E_NOT_BZIP_DATA; }
-  const int level = hd.h[3] - '0';
-  if (level < 1 || level > 9) { set_detail("level out of range"); return CJS_E_NOT_BZIP_DATA; }
+  int level = 0; const char* why = nullptr;
+  if (bz_header_check(hd.h, n, &level, &why)) { set_detail("%s", why); return CJS_E_NOT_BZIP_DATA; }
   DecJob& J = U.J; DecShare& S = U.S;
   J.n = n; J.mode = 0; J.timing = env_debug();
   J.tt_stride = 100000u * (uint32_t)(multistream ? std::max<int>(level, (int)hd.level) : level);
@@ -1681,12 +1818,16 @@ int dev_single_prepare(DevUnit& U, const uint8_t* d_in, size_t n, int multistrea
   S.lo = 0; S.hi = n; S.up_lo = 0; S.up_hi = n;
   guarded(S.rc, [&] { dec_phase_a(&J, &S); });
   if (S.rc) return S.rc;
-  std::vector<uint64_t> cbit(S.cands.size());
-  for (size_t c = 0; c < S.cands.size(); c++) cbit[c] = S.cands[c].bit;
-  U.pending = dev_walk(U, hd, n, 0, multistream, cbit);
+  U.pending = dev_walk(U, WalkCands(&S, 1), hd, n, multistream);
   snprintf(U.pending_detail, sizeof U.pending_detail, "%s", cjs_last_error_detail());
   clear_detail();
-  return dev_phase_b(U);
+  S.c0 = 0; S.c1 = J.chain.size();
+  if (S.c1) {
+    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
+    if (S.rc) return S.rc;
+  }
+  U.total = chain_out_offsets(J);
+  return 0;
 }
 
 // single stream, phase C into d_out (nullptr: the CRC verdicts alone, in scratch; so with a pending error) -> the final verdict
@@ -1701,36 +1842,17 @@ int dev_single_emit(DevUnit& U, uint8_t* d_out) {
   return 0;
 }
 
-// a batch group (dec_batch_group's layout and verdicts), up to phase B: status / detail of inputs refused by their header or their walk
-int dev_group_prepare(DevUnit& U, const uint8_t* d_in, const size_t* in_off, size_t k0, size_t k1, int multistream, const std::vector<DevHdr>& hd,
+// a batch group up to phase B: the inputs (n[k] bytes from d_in + in_off[k] on, their headers in hd) are gathered into the group
+// layout on the device, and a walk reads its bytes from hd and the end-of-stream records
+int dev_group_prepare(DevUnit& U, const uint8_t* d_in, const size_t* in_off, const size_t* n, size_t k0, size_t k1, int multistream, const std::vector<DevHdr>& hd,
                       int32_t* status, std::vector<std::string>& detail) {
-  DecJob& J = U.J; DecShare& S = U.S;
-  const size_t items = k1 - k0;
-  U.k0 = k0; U.k1 = k1;
-  J.mode = 0; J.batch = true; J.timing = env_debug();
-  S.bst.resize(items); S.ben.resize(items); S.bdsz.assign(items, 100000u);
-  int max_level = 1;
-  std::vector<uint8_t> ok(items, 0);
-  size_t bytes = 0;
-  for (size_t i = 0; i < items; i++) {                          // _start_bunzip (:1408-1427) of every input
-    const size_t k = k0 + i, m = in_off[k + 1] - in_off[k];
-    const uint8_t* h = hd[k].h;
-    status[k] = 0;
-    S.bst[i] = S.ben[i] = (uint32_t)bytes;
-    if (m < 4 || h[0] != 'B' || h[1] != 'Z' || h[2] != 'h') { status[k] = CJS_E_NOT_BZIP_DATA; detail[k] = "bad magic"; continue; }
-    const int level = h[3] - '0';
-    if (level < 1 || level > 9) { status[k] = CJS_E_NOT_BZIP_DATA; detail[k] = "level out of range"; continue; }
-    const int own = multistream ? std::max<int>(level, (int)hd[k].level) : level;
-    S.bdsz[i] = 100000u * (uint32_t)own;
-    max_level = std::max(max_level, own);
-    ok[i] = 1;
-    for (size_t p = 0; p < m; p += GATHER_PIECE)                 // (pieces of whole words: the last one of an input is zero-filled to one)
-      U.pieces.push_back(GatherPiece{in_off[k] + p, (uint32_t)(bytes + p), (uint32_t)std::min<size_t>(GATHER_PIECE, m - p)});
-    S.ben[i] = (uint32_t)(bytes + m);
-    bytes = (bytes + m + 3) & ~(size_t)3;
-  }
-  J.tt_stride = 100000u * (uint32_t)max_level;
-  J.n = bytes;
+  DecJob& J = U.J;
+  group_layout(J, U.S, U.G, k0, k1, n, status, detail, [&](size_t k) { return hd[k].h; },
+               [&](size_t k, int level) { return multistream ? std::max<int>(level, (int)hd[k].level) : level; },
+               [&](size_t k, size_t at) {
+                 for (size_t p = 0; p < n[k]; p += GATHER_PIECE)      // (pieces of whole words: the last one of an input is zero-filled to one)
+                   U.pieces.push_back(GatherPiece{in_off[k] + p, (uint32_t)(at + p), (uint32_t)std::min<size_t>(GATHER_PIECE, n[k] - p)});
+               });
   J.upload = [&U, d_in](DecShare* s, uint8_t* dst) {
     GatherPiece* d_pc = nullptr;
     CJS_TRY(s->take((void**)&d_pc, sizeof(GatherPiece) * U.pieces.size()));
@@ -1740,47 +1862,17 @@ int dev_group_prepare(DevUnit& U, const uint8_t* d_in, const size_t* in_off, siz
     return hipGetLastError() != hipSuccess ? (int)CJS_E_HIP : 0;
   };
   J.eos = [&U](DecShare* s) { return dev_eos_gather(s, U.rec, U.rec_of); };
-  S.lo = 0; S.hi = bytes; S.up_lo = 0; S.up_hi = bytes;
-  if (bytes) {
-    guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-    if (S.rc) return S.rc;
-  }
-  std::vector<uint64_t> cbit(S.cands.size());
-  for (size_t c = 0; c < S.cands.size(); c++) cbit[c] = S.cands[c].bit;
-  U.ch0.assign(items, 0); U.ch1.assign(items, 0);
-  for (size_t i = 0; i < items; i++) {
-    U.ch0[i] = U.ch1[i] = J.chain.size();
-    if (!ok[i]) continue;
-    clear_detail();
-    const int rc = dev_walk(U, hd[k0 + i], in_off[k0 + i + 1] - in_off[k0 + i], S.bst[i], multistream, cbit);
-    U.ch1[i] = J.chain.size();
-    if (rc) { status[k0 + i] = rc; detail[k0 + i] = cjs_last_error_detail(); }     // pending: a bad block CRC in front of it wins
-  }
-  clear_detail();
-  const int rc = dev_phase_b(U);
-  if (rc == CJS_E_OUT_OF_MEMORY || rc == CJS_E_NO_DEVICE) return rc;
-  return rc ? (int)CJS_E_HIP : 0;                               // (as dec_batch_group)
+  return group_prepare(J, U.S, U.G, status, detail, [&](size_t k, const WalkCands& C) { return dev_walk(U, C, hd[k], n[k], multistream); }, &U.total);
 }
 
 // a batch group, phase C into d_out (the group's region): every input's status, offset (from d_out) and length
 int dev_group_emit(DevUnit& U, uint8_t* d_out, size_t base, size_t* out_off, size_t* out_len, int32_t* status, std::vector<std::string>& detail) {
   DecJob& J = U.J;
-  const size_t nb = J.chain.size();
-  J.crc_got.assign(nb, 0);
+  J.crc_got.assign(J.chain.size(), 0);
   J.dev_out = d_out;
-  if (nb) { U.S.rc = 0; guarded(U.S.rc, [&] { dec_phase_c(&J, &U.S); }); }
+  if (!J.chain.empty()) { U.S.rc = 0; guarded(U.S.rc, [&] { dec_phase_c(&J, &U.S); }); }
   if (U.S.rc) return U.S.rc;
-  for (size_t i = 0; i < U.k1 - U.k0; i++) {
-    const size_t k = U.k0 + i;
-    for (size_t b = U.ch0[i]; b < U.ch1[i]; b++) if (J.crc_got[b] != J.chain[b].crc) {      // Bad block CRC (:1756-1761)
-      char d[96];
-      snprintf(d, sizeof d, "Bad block CRC (got %x expected %x)", J.crc_got[b], J.chain[b].crc);
-      status[k] = CJS_E_DATA_ERROR; detail[k] = d;
-      break;
-    }
-    out_off[k] = base + (size_t)J.out_off[U.ch0[i]];
-    out_len[k] = status[k] ? 0 : (size_t)(J.out_off[U.ch1[i]] - J.out_off[U.ch0[i]]);
-  }
+  group_verdicts(J, U.G, base, out_off, out_len, status, detail);
   return 0;
 }
 
@@ -1813,20 +1905,9 @@ extern "C" int cjs_bzip2_decompress_device(const uint8_t* d_in, size_t n, int mu
 }
 
 // ---------------------------------------------------------------- batch (Bzip2.decompressFiles)
-// Inputs go in groups of up to BATCH_DEC_GROUP_BYTES, each group one upload with every input at a 4-byte-aligned offset and one
-// share of phases A-C: one magic scan over the group (a candidate never straddles two inputs), block decode of all candidates
-// with every read bounded by the candidate's own input, then the walk of each input over the candidates of its bytes, phase B
-// over all chain blocks, phase C with a CRC verdict per block.  Input k's verdict is the single call's: the first block of its
-// chain, in stream order, whose CRC fails; else the walk's error; else success.  An input larger than a group goes through
-// cjs_bzip2_decompress.  See DESIGN.md §6c.
+// The groups above with the inputs and the result in host memory: a group's inputs are staged into one host buffer and uploaded
+// as phase A uploads a single stream; phase C copies the bytes back into a result buffer of the group.  See DESIGN.md §6c.
 namespace {
-
-constexpr size_t BATCH_DEC_GROUP_BYTES = (size_t)256 << 20;
-
-size_t dec_group_bytes() {
-  static const size_t g = getenv("CJS_DEC_GROUP_BYTES") ? (size_t)strtoull(getenv("CJS_DEC_GROUP_BYTES"), nullptr, 10) : BATCH_DEC_GROUP_BYTES;   // (tests shrink it)
-  return g && g <= ((size_t)1 << 30) ? g : BATCH_DEC_GROUP_BYTES;      // (group offsets are 32-bit)
-}
 
 struct BatchPiece { uint8_t* buf; size_t size; };       // a HostPool result buffer and the bytes used in it
 
@@ -1834,95 +1915,29 @@ struct BatchPiece { uint8_t* buf; size_t size; };       // a HostPool result buf
 int dec_batch_group(const uint8_t* const* in, const size_t* n, size_t k0, size_t k1, int multistream, int dev, size_t* off, size_t* len,
                     int32_t* status, std::vector<std::string>& detail, BatchPiece* piece) {
   piece->buf = nullptr; piece->size = 0;
-  const size_t items = k1 - k0;
-  DecJob J; J.mode = 0; J.batch = true; J.timing = env_debug();
-  DecShare S; S.device = dev;
-  S.bst.resize(items); S.ben.resize(items); S.bdsz.assign(items, 100000u);
-  int max_level = 1;
-  std::vector<uint8_t> ok(items, 0);
-  size_t bytes = 0;
-  for (size_t i = 0; i < items; i++) {                         // _start_bunzip (:1408-1427) of every input
-    const uint8_t* p = in[k0 + i]; const size_t m = n[k0 + i];
-    status[k0 + i] = 0; off[k0 + i] = 0; len[k0 + i] = 0;
-    S.bst[i] = S.ben[i] = (uint32_t)bytes;
-    if (m < 4 || p[0] != 'B' || p[1] != 'Z' || p[2] != 'h') { status[k0 + i] = CJS_E_NOT_BZIP_DATA; detail[k0 + i] = "bad magic"; continue; }
-    const int level = p[3] - '0';
-    if (level < 1 || level > 9) { status[k0 + i] = CJS_E_NOT_BZIP_DATA; detail[k0 + i] = "level out of range"; continue; }
-    const int own = bz_max_level(p, m, level, multistream != 0);      // the scratch of its single call: the kernels' limits for its blocks
-    S.bdsz[i] = 100000u * (uint32_t)own;
-    max_level = std::max(max_level, own);
-    ok[i] = 1;
-    S.ben[i] = (uint32_t)(bytes + m);
-    bytes = (bytes + m + 3) & ~(size_t)3;
-  }
-  J.tt_stride = 100000u * (uint32_t)max_level;
-  uint8_t* host_in = (uint8_t*)HostPool::take(bytes ? bytes : 1);
+  DecJob J; DecShare S; BatchGroup G;
+  S.device = dev;
+  for (size_t k = k0; k < k1; k++) off[k] = len[k] = 0;
+  group_layout(J, S, G, k0, k1, n, status, detail, [&](size_t k) { return in[k]; },
+               [&](size_t k, int level) { return bz_max_level(in[k], n[k], level, multistream != 0); }, [](size_t, size_t) {});
+  uint8_t* host_in = (uint8_t*)HostPool::take(J.n ? J.n : 1);
   if (!host_in) return CJS_E_OUT_OF_MEMORY;
   struct GiveBack { uint8_t* p; ~GiveBack() { HostPool::give(p); } } give_in{host_in};
-  for (size_t i = 0; i < items; i++) if (ok[i]) memcpy(host_in + S.bst[i], in[k0 + i], S.ben[i] - S.bst[i]);
-  J.in = host_in; J.n = bytes;
-  S.lo = 0; S.hi = bytes; S.up_lo = 0; S.up_hi = bytes;
-  if (bytes) {
-    guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-    if (S.rc) return S.rc;
-  }
-  // the walk of every input over the candidates of its bytes (bits of the group: 8 x bst[i] + bits of the input)
-  std::vector<uint64_t> cbit(S.cands.size());
-  for (size_t c = 0; c < S.cands.size(); c++) cbit[c] = S.cands[c].bit;
-  std::vector<size_t> ch0(items, 0), ch1(items, 0);
-  for (size_t i = 0; i < items; i++) {
-    ch0[i] = ch1[i] = J.chain.size();
-    if (!ok[i]) continue;
-    const uint64_t base = 8ull * S.bst[i];
-    long last = -1;
-    clear_detail();
-    const int rc = bz_walk(in[k0 + i], n[k0 + i], multistream, 0, J.tt_stride, J.timing,
-                           [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
-                             const auto it = std::lower_bound(cbit.begin(), cbit.end(), base + pos);
-                             if (it == cbit.end() || *it != base + pos) return false;
-                             last = (long)(it - cbit.begin());
-                             *kind = S.cands[(size_t)last].kind; *bo = S.bos[(size_t)last]; bo->end_bit -= base;
-                             return true;
-                           },
-                           [&](const BlockOut& bo, uint64_t) {
-                             IbBlock ib; ib.tt = S.tt_ptr[(size_t)last]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
-                             J.chain.push_back(ib);
-                           });
-    ch1[i] = J.chain.size();
-    if (rc) { status[k0 + i] = rc; detail[k0 + i] = cjs_last_error_detail(); }     // pending: a bad block CRC in front of it wins
-  }
-  clear_detail();
+  for (size_t k = k0; k < k1; k++) if (G.ok[k - k0]) memcpy(host_in + S.bst[k - k0], in[k], n[k]);
+  J.in = host_in;
+  uint64_t total = 0;
+  CJS_TRY(group_prepare(J, S, G, status, detail, [&](size_t k, const WalkCands& C) { return walk_chain(J, C, in[k], n[k], multistream, 0, met_nothing); }, &total));
   const size_t nb = J.chain.size();
-  S.c0 = 0; S.c1 = nb;
-  if (nb) {
-    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
-    // (phase B's own CJS_E_UNSUPPORTED / CJS_E_DATA_ERROR exits cannot happen -- a block holds <= 900000 bytes, a walk makes a step;
-    // should one, it is a failure of the call, reported as one of the call's codes)
-    if (S.rc == CJS_E_OUT_OF_MEMORY || S.rc == CJS_E_NO_DEVICE) return S.rc;
-    if (S.rc) return CJS_E_HIP;
-  }
-  J.out_off.assign(nb + 1, 0);
-  for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
-  const uint64_t total = J.out_off[nb];
   J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1);
   if (!J.host) return CJS_E_OUT_OF_MEMORY;
   J.crc_got.assign(nb, 0);
   if (nb) guarded(S.rc, [&] { dec_phase_c(&J, &S); });
   S.release();                                                 // (the stream has drained before J.host is read or given back)
   if (S.rc) { HostPool::give(J.host); return S.rc; }
-  for (size_t i = 0; i < items; i++) {
-    for (size_t b = ch0[i]; b < ch1[i]; b++) if (J.crc_got[b] != J.chain[b].crc) {      // Bad block CRC (:1756-1761)
-      char d[96];
-      snprintf(d, sizeof d, "Bad block CRC (got %x expected %x)", J.crc_got[b], J.chain[b].crc);
-      status[k0 + i] = CJS_E_DATA_ERROR; detail[k0 + i] = d;
-      break;
-    }
-    off[k0 + i] = (size_t)J.out_off[ch0[i]];
-    len[k0 + i] = status[k0 + i] ? 0 : (size_t)(J.out_off[ch1[i]] - J.out_off[ch0[i]]);
-  }
+  group_verdicts(J, G, 0, off, len, status, detail);
   if (J.timing)
     fprintf(stderr, "[cjs dec batch] group: %zu inputs, %zu candidates, %u row batches (phase A), %u inverse-BWT batches (phase B), %zu chain blocks, %llu bytes out\n",
-            items, S.cands.size(), S.a_batches, S.b_batches, nb, (unsigned long long)total);
+            k1 - k0, S.cands.size(), S.a_batches, S.b_batches, nb, (unsigned long long)total);
   piece->buf = J.host; piece->size = (size_t)total;
   return 0;
 }
@@ -1962,8 +1977,7 @@ extern "C" int cjs_bzip2_decompress_batch(const uint8_t* const* in, const size_t
       k0++;
       continue;
     }
-    size_t k1 = k0, bytes = 0;
-    while (k1 < count && n[k1] <= G && (k1 == k0 || bytes + n[k1] <= G)) bytes += (n[k1++] + 3) & ~(size_t)3;
+    const size_t k1 = dec_group_end(n, count, k0, G);
     BatchPiece p{nullptr, 0};
     if ((rc = dec_batch_group(in, n, k0, k1, multistream, dev, off, len, status, detail, &p)) != 0) break;
     pieces.push_back(p);
@@ -2012,19 +2026,20 @@ extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size
   CJS_TRY(dev_headers(H, d_in, std::vector<uint64_t>(in_off, in_off + count + 1), multistream != 0, hd));
   H.release();
   const size_t G = dec_group_bytes();
+  std::vector<size_t> n(count);
+  for (size_t k = 0; k < count; k++) n[k] = in_off[k + 1] - in_off[k];
   std::vector<std::string> detail(count);
   std::vector<std::unique_ptr<DevUnit>> units;
   std::vector<size_t> unit_base;
   uint64_t need = 0;
   for (size_t k0 = 0; k0 < count;) {
-    const size_t n0 = in_off[k0 + 1] - in_off[k0];
     units.emplace_back(new DevUnit);
     DevUnit& U = *units.back();
     U.S.device = dev;
-    if (n0 > G) {                                               // an input of its own: the single device path
-      U.k0 = k0; U.k1 = k0 + 1;
+    if (n[k0] > G) {                                            // an input of its own: the single device path
+      U.G.k0 = k0; U.G.k1 = k0 + 1;
       clear_detail();
-      int r = dev_single_prepare(U, d_in + in_off[k0], n0, multistream, hd[k0]);
+      int r = dev_single_prepare(U, d_in + in_off[k0], n[k0], multistream, hd[k0]);
       if (!r) r = dev_single_emit(U, nullptr);                  // (the verdict: a failed input takes no bytes)
       if (r == CJS_E_OUT_OF_MEMORY || r == CJS_E_NO_DEVICE || r == CJS_E_HIP || r == CJS_E_INVALID_ARG) return r;
       status[k0] = r;
@@ -2035,9 +2050,8 @@ extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size
       k0++;
       continue;
     }
-    size_t k1 = k0, bytes = 0;
-    while (k1 < count && in_off[k1 + 1] - in_off[k1] <= G && (k1 == k0 || bytes + (in_off[k1 + 1] - in_off[k1]) <= G)) { bytes += (in_off[k1 + 1] - in_off[k1] + 3) & ~(size_t)3; k1++; }
-    CJS_TRY(dev_group_prepare(U, d_in, in_off, k0, k1, multistream, hd, status, detail));
+    const size_t k1 = dec_group_end(n.data(), count, k0, G);
+    CJS_TRY(dev_group_prepare(U, d_in, in_off, n.data(), k0, k1, multistream, hd, status, detail));
     unit_base.push_back((size_t)need);
     need += U.total;
     k0 = k1;
@@ -2055,7 +2069,7 @@ extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size
   for (size_t u = 0; u < units.size(); u++) {
     DevUnit& U = *units[u];
     if (U.J.batch) CJS_TRY(dev_group_emit(U, d_out + unit_base[u], unit_base[u], out_off, out_len, status, detail));
-    else if (!status[U.k0] && dev_single_emit(U, d_out + unit_base[u]) != 0) return CJS_E_HIP;      // (its verdict was 0 a moment ago)
+    else if (!status[U.G.k0] && dev_single_emit(U, d_out + unit_base[u]) != 0) return CJS_E_HIP;      // (its verdict was 0 a moment ago)
     U.S.release();
   }
   tally();
@@ -2076,7 +2090,6 @@ extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size
 namespace {
 constexpr size_t DEC_DEFAULT_CHUNK = (size_t)64 << 20, DEC_DEFAULT_OUT = (size_t)256 << 20;      // DESIGN.md §6f (placeholders, UNMEASURED)
 constexpr size_t DEC_MIN_CHUNK = (size_t)64 << 10, DEC_MAX_CHUNK = (size_t)1 << 30;
-constexpr uint64_t dec_extent(uint32_t tt_stride) { return (uint64_t)tt_stride * 5 / 2 + 65536; }      // bunzip_core's share overlap
 const char* const WALK_WHY[] = {"runs", "end of stream", "block magic not all here", "stream crc not all here", "member header not all here", "candidate without a row",
                                 "block not all here", "error too near the end", "output budget"};
 struct WinBytes {                        // the window by absolute stream byte
@@ -2126,11 +2139,8 @@ namespace {
 
 // _start_bunzip (:1408-1427) on the first four bytes: no device
 int dec_header(cjs_bz_dec* d) {
-  if (d->written < 4) return d->fail(CJS_E_NOT_BZIP_DATA, "bad magic");
-  const uint8_t* in = d->win;
-  if (in[0] != 'B' || in[1] != 'Z' || in[2] != 'h') return d->fail(CJS_E_NOT_BZIP_DATA, "bad magic");
-  d->level = in[3] - '0';
-  if (d->level < 1 || d->level > 9) return d->fail(CJS_E_NOT_BZIP_DATA, "level out of range");
+  const char* why = nullptr;
+  if (bz_header_check(d->win, d->written, &d->level, &why)) return d->fail(CJS_E_NOT_BZIP_DATA, why);
   const uint32_t L = d->multistream ? 9u : (uint32_t)d->level;      // later members cannot be seen ahead
   d->tt_stride = 100000u * L;
   d->out_cap = std::max<size_t>(d->out_req ? d->out_req : DEC_DEFAULT_OUT, (size_t)52 * d->tt_stride);
@@ -2186,33 +2196,22 @@ int dec_step(cjs_bz_dec* d) {
   WalkState& W = d->W;
   W.partial = !final; W.cut_bit = S.cut_bit; W.extent = dec_extent(d->tt_stride); W.stop = WALK_RUNS;
   std::vector<WalkState> before;           // the state in front of each chain block
-  long last = -1;
   clear_detail();
-  int wrc = bz_walk(WinBytes{d->win, d->win_off}, (size_t)n, d->multistream, 0, d->tt_stride, J.timing,
-                    [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
-                      const auto it = std::lower_bound(S.cands.begin(), S.cands.end(), pos, [](const Cand& c, uint64_t b) { return c.bit < b; });
-                      if (it == S.cands.end() || it->bit != pos) return false;
-                      last = (long)(it - S.cands.begin());
-                      *kind = it->kind; *bo = S.bos[(size_t)last];
-                      return true;
-                    },
-                    [&](const BlockOut& bo, uint64_t) {
-                      IbBlock ib; ib.tt = S.tt_ptr[(size_t)last]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
-                      J.chain.push_back(ib); before.push_back(W);
-                    },
-                    &W);
+  int wrc = walk_chain(J, WalkCands(&S, 1), WinBytes{d->win, d->win_off}, (size_t)n, d->multistream, 0,
+                       [&](long ci, uint64_t) { if (S.cands[(size_t)ci].kind == 0) before.push_back(W); }, &W);
   char wdetail[192];
   snprintf(wdetail, sizeof wdetail, "%s", cjs_last_error_detail());
   clear_detail();
   // ---- phase B over the chain, then the cut to the output budget
   size_t nb = J.chain.size();
   const size_t walked = nb;
-  J.out_off.assign(nb + 1, 0);
   if (nb) {
     S.c0 = 0; S.c1 = nb;
     guarded(S.rc, [&] { dec_phase_b(&J, &S); });
     if (S.rc) return S.rc;
-    for (size_t k = 0; k < nb; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
+  }
+  chain_out_offsets(J);
+  if (nb) {
     if (J.out_off[1] > d->out_cap) return CJS_E_UNSUPPORTED;      // cannot happen: out_cap >= a block's largest expansion
     size_t k = 1;
     while (k < nb && J.out_off[k + 1] <= d->out_cap) k++;
@@ -2235,7 +2234,7 @@ int dec_step(cjs_bz_dec* d) {
   d->held = deliver; d->held_pos = 0;
   if (bad < nb) {                          // Bad block CRC (:1756-1761): nothing of the block is delivered
     d->pend_rc = CJS_E_DATA_ERROR;
-    snprintf(d->pend_detail, sizeof d->pend_detail, "Bad block CRC (got %x expected %x)", J.crc_got[bad], J.chain[bad].crc);
+    bad_crc_detail(d->pend_detail, sizeof d->pend_detail, J.crc_got[bad], J.chain[bad].crc);
   } else if (wrc) {
     d->pend_rc = wrc;
     snprintf(d->pend_detail, sizeof d->pend_detail, "%s", wdetail);
