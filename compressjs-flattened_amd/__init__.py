@@ -40,6 +40,14 @@ class ShardMeta(ctypes.Structure):
                 ("blocks", ctypes.c_uint32), ("crc_fold", ctypes.c_uint32)]
 
 
+class Found(ctypes.Structure):
+    """cjs_bz_found: one block candidate of a recovery (40 bytes)."""
+    _fields_ = [("bitpos", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("size", ctypes.c_uint32),
+                ("status", ctypes.c_int32), ("crc", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+REC_SHADOWED = 1      # CJS_REC_SHADOWED
+
 _lib = None
 
 
@@ -92,6 +100,8 @@ def load_library():
     L.cjs_bzip2_shard_tiles.argtypes = [V, V, S, I, I, V]
     L.cjs_bzip2_shard_blocks.argtypes = [V, V, S, I, I, I, V, ctypes.POINTER(ShardMeta), ctypes.POINTER(Stats)]
     L.cjs_bzip2_shard_pack.argtypes = [V, I, I, I, ctypes.POINTER(ShardMeta), V, S, PS, PS, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.cjs_bzip2_recover.argtypes = [u8p, S, I, PP, PS, ctypes.POINTER(Found), ctypes.c_long, ctypes.POINTER(ctypes.c_long), V]
+    L.cjs_bzip2_recover_device.argtypes = [V, S, I, V, S, PS, ctypes.POINTER(Found), ctypes.c_long, ctypes.POINTER(ctypes.c_long), V]
     L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
     L.cjs_bzip2_enc_write.argtypes = [V, V, S]
     L.cjs_bzip2_enc_finish.argtypes = [V]
@@ -257,6 +267,25 @@ class Bzip2:
                 e.index = k
                 raise e
         return [buf[off[k]: off[k] + ln[k]] for k in range(count)]
+
+
+    @staticmethod
+    def recoverFile(input, output=None, as_stream=False):
+        """What bzip2recover is for (cjs_bzip2_recover): the intact blocks of damaged .bz2 data -- any bytes, no header needed --
+        as their decoded bytes, or with as_stream as a repaired single-stream .bz2.  Returns (data, found): found has one
+        (bitpos, end_bit, out_off, size, status, crc) per block magic in the input, ascending; status 0 = recovered,
+        REC_SHADOWED = a false magic inside a recovered block, else the block's error code."""
+        L = load_library()
+        data = _coerce_input(input)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+
+        def call(cap):
+            out, out_n, nf = u8p(), ctypes.c_size_t(0), ctypes.c_long(0)
+            found = (Found * cap)()
+            _check(L.cjs_bzip2_recover(keep.ctypes.data_as(u8p), data.size, 1 if as_stream else 0, ctypes.byref(out), ctypes.byref(out_n),
+                                       found, cap, ctypes.byref(nf), None))
+            return _adopt(out, out_n.value), found, nf.value
+        return _deliver_found(call, data.size, output)
 
 
 class Bzip2Encoder:
@@ -501,6 +530,46 @@ def decompress_device(d_in_ptr, n, d_out_ptr, out_cap, multistream=False, device
         raise e
     _check(rc)
     return out_n.value
+
+
+def _found_cap(n):
+    return n // 64 + 1024      # (a block takes a few dozen bytes at least; more magics than that: one more call)
+
+
+def _found_list(found, count):
+    return [(f.bitpos, f.end_bit, f.out_off, f.size, f.status, f.crc) for f in found[:count]]
+
+
+def _deliver_found(call, n, output):
+    res, found, nf = call(_found_cap(n))
+    if nf > len(found):
+        res, found, nf = call(nf)
+    return _deliver(res, output), _found_list(found, nf)
+
+
+def recover_device(d_in_ptr, n, d_out_ptr, out_cap, as_stream=False, device=-1):
+    """Bzip2.recoverFile with the damaged data and the result in GPU memory (cjs_bzip2_recover_device; the memory rules of
+    decompress_device).  Returns (out_n, found).  On CJS_E_OUTPUT_TOO_SMALL (-33) the CjsError carries `need`, the bytes the
+    result takes, and `found`; out_cap = 0 with d_out_ptr = None is the size query."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    cap = _found_cap(n)
+    while True:
+        out_n, nf = ctypes.c_size_t(0), ctypes.c_long(0)
+        found = (Found * cap)()
+        rc = L.cjs_bzip2_recover_device(d_in_ptr, n, 1 if as_stream else 0, d_out_ptr, out_cap, ctypes.byref(out_n), found, cap,
+                                        ctypes.byref(nf), ctypes.byref(opts))
+        if rc in (0, -33) and nf.value > cap:
+            cap = nf.value
+            continue
+        break
+    if rc == -33:
+        e = CjsError(rc, L.cjs_strerror(rc).decode())
+        e.need = out_n.value
+        e.found = _found_list(found, nf.value)
+        raise e
+    _check(rc)
+    return out_n.value, _found_list(found, nf.value)
 
 
 def decompress_batch_device(d_in_ptr, in_off, d_out_ptr, out_cap, multistream=False, device=-1):

@@ -172,5 +172,19 @@ Bzip2.table = function (inStream, callback, multistream) {
   try { t = common.addon().bzip2Table(input.bytes, multistream ? 1 : 0); } catch (e) { rethrow(e); }
   for (var i = 0; i < t.length; i += 2) { callback(t[i], t[i + 1]); }
 };
+// What bzip2recover is for (cjs_bzip2_recover): the intact blocks of damaged .bz2 data -- any bytes, no header needed -- as their
+// decoded bytes, or with asStream as a repaired single-stream .bz2.  callback(position in bits, uncompressed size in bytes,
+// status) once per block magic in the input, ascending: status 0 = recovered, Bzip2.REC_SHADOWED = a false magic inside a
+// recovered block, else the block's error code (size 0 then).  The bytes are delivered like decompressFile's.
+Bzip2.recoverFile = function (inStream, outStream, callback, asStream) {
+  var input = common.coerceInput(inStream);
+  var r;
+  try { r = common.addon().bzip2Recover(input.bytes, asStream ? 1 : 0); } catch (e) { rethrow(e); }
+  if (typeof callback === 'function') {
+    for (var i = 0; i < r.found.length; i += 6) { callback(r.found[i], r.found[i + 3], r.found[i + 4]); }
+  }
+  return common.deliver(r.data, outStream);
+};
+Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

@@ -24,6 +24,7 @@ struct Api {
   int (*bzip2_decompress_block)(const uint8_t*, size_t, uint64_t, uint8_t**, size_t*, const cjs_opts*) = nullptr;
   int (*bzip2_compress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, const cjs_opts*) = nullptr;
   int (*bzip2_decompress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, int32_t*, const cjs_opts*) = nullptr;
+  int (*bzip2_recover)(const uint8_t*, size_t, int, uint8_t**, size_t*, cjs_bz_found*, long, long*, const cjs_opts*) = nullptr;
   int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
   int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
   int (*enc_finish)(cjs_bz_enc*) = nullptr;
@@ -63,6 +64,7 @@ bool load_api() {
   SYM(bwtc_compress, "cjs_bwtc_compress") SYM(bwtc_decompress, "cjs_bwtc_decompress")
   SYM(bzip2_table, "cjs_bzip2_table") SYM(bzip2_decompress_block, "cjs_bzip2_decompress_block")
   SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch") SYM(bzip2_decompress_batch, "cjs_bzip2_decompress_batch")
+  SYM(bzip2_recover, "cjs_bzip2_recover")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(dec_create, "cjs_bzip2_dec_create") SYM(dec_write, "cjs_bzip2_dec_write") SYM(dec_finish, "cjs_bzip2_dec_finish")
@@ -188,6 +190,42 @@ napi_value bzip2_block(napi_env env, napi_callback_info info) {
   const int rc = api.bzip2_decompress_block(p ? p : &dummy, n, (uint64_t)bit, &out, &out_n, nullptr);
   if (rc != 0) return throw_code(env, rc);
   return wrap_result(env, out, out_n);
+}
+
+// bzip2Recover(input, asStream) -> { data: Uint8Array, found: Float64Array }   (Bzip2.recoverFile)
+// found holds six numbers per block candidate, ascending: bitpos, end_bit, out_off, size, status, crc (cjs_bz_found).
+napi_value bzip2_recover(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* p = nullptr; size_t n = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &p, &n)) { napi_throw_type_error(env, nullptr, "expected a Uint8Array or Buffer"); return nullptr; }
+  int32_t as_stream = 0;
+  if (argc >= 2) napi_get_value_int32(env, argv[1], &as_stream);
+  static const uint8_t dummy = 0;
+  long cap = (long)(n / 64 + 1024), nf = 0;                     // (more magics than that: one more call)
+  std::vector<cjs_bz_found> found;
+  uint8_t* out = nullptr; size_t out_n = 0;
+  for (;;) {
+    found.resize((size_t)cap);
+    const int rc = api.bzip2_recover(p ? p : &dummy, n, as_stream, &out, &out_n, found.data(), cap, &nf, nullptr);
+    if (rc != 0) return throw_code(env, rc);
+    if (nf <= cap) break;
+    api.free_(out);
+    cap = nf;
+  }
+  napi_value res, ab, ta; void* dst;
+  napi_create_object(env, &res);
+  napi_set_named_property(env, res, "data", wrap_result(env, out, out_n));
+  napi_create_arraybuffer(env, sizeof(double) * 6 * (size_t)nf, &dst, &ab);
+  for (long i = 0; i < nf; i++) {
+    const cjs_bz_found& f = found[(size_t)i];
+    double* d = (double*)dst + 6 * i;
+    d[0] = (double)f.bitpos; d[1] = (double)f.end_bit; d[2] = (double)f.out_off; d[3] = (double)f.size; d[4] = (double)f.status; d[5] = (double)f.crc;
+  }
+  napi_create_typedarray(env, napi_float64_array, 6 * (size_t)nf, ab, 0, &ta);
+  napi_set_named_property(env, res, "found", ta);
+  return res;
 }
 
 // bzip2CompressBatch(array of Uint8Array / Buffer, level) -> array of Uint8Array   (Bzip2.compressFiles)
@@ -487,6 +525,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2DecompressBatch", nullptr, bzip2_decompress_batch, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Table", nullptr, bzip2_table, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2DecompressBlock", nullptr, bzip2_block, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2Recover", nullptr, bzip2_recover, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncWrite", nullptr, enc_write, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncFinish", nullptr, enc_finish, nullptr, nullptr, nullptr, napi_default, nullptr},

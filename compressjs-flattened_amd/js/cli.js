@@ -3,6 +3,9 @@
 /* cli.js — command line of the two fronts, with the switches of the reference's bin/compressjs for the algorithms in scope
  * (NPM/bin/compressjs:7-25 options, :31-58 checks and messages, :60-120 fd streams, :143-175 dispatch):
  *   cli.js -d|-z [-t bzip2|bwtc] [-1..-9] [-b <bits>] [infile] [outfile]
+ *   cli.js --recover|--repair -t bzip2 [infile] [outfile]
+ * --recover writes the decoded bytes of the intact blocks of damaged .bz2 data, --repair a .bz2 stream made of those blocks (what
+ * bzip2recover is for; Bzip2.recoverFile), each with one line "recovered K of M blocks (N bytes)" on stderr.
  * infile omitted: stdin; outfile omitted: stdout; neither -d nor -z: compress; default level 7 (:57).
  * The reference's default compressor (Lzp3) and its other -t values are not part of the MI355X core: -t must name bzip2
  * (alias bzip) or bwtc.  A file input knows its size, a pipe does not -- BWTC writes varint(0) then, as the reference does for a
@@ -21,17 +24,25 @@ for (var i = 0; i < argv.length; i++) {
   else if (a === '-z' || a === '--compress') { opt.compress = true; }
   else if (a === '-b' || a === '--block') { opt.block = +argv[++i]; }
   else if (a === '-t') { opt.type = argv[++i]; }
+  else if (a === '--recover' || a === '--repair') {
+    if (opt.recover && opt.recover !== a) { fail("Can't specify both " + opt.recover + ' and ' + a); }
+    opt.recover = a;
+  }
   else if (/^-[1-9]$/.test(a)) {
     if (level) { fail("Can't specify both -" + level + ' and ' + a); }
     level = +a.slice(1);
   } else if (a === '-h' || a === '--help') {
     console.log('Usage: cli.js -d|-z [-t bzip2|bwtc] [-1..-9] [-b <bits>] [infile] [outfile]\n' +
+                '       cli.js --recover|--repair -t bzip2 [infile] [outfile]\n' +
                 '  If <infile> is omitted, reads from stdin.\n  If <outfile> is omitted, writes to stdout.');
     process.exit(0);
   } else if (a[0] === '-' && a.length > 1) { fail('Unknown option: ' + a); }
   else { opt.files.push(a); }
 }
-if (!opt.decompress) { opt.compress = true; }
+if (opt.recover && (opt.compress || opt.decompress || opt.block >= 0 || level || !/^bzip2?$/i.test(String(opt.type || '')))) {
+  fail(opt.recover + ' can only be used alone with -t bzip2');
+}
+if (!opt.decompress && !opt.recover) { opt.compress = true; }
 if (opt.decompress && opt.compress) { fail('Must specify either -d or -z.'); }
 if (opt.compress && opt.block >= 0) { fail('--block can only be used with decompression'); }
 if (level && opt.decompress) { fail('Compression level has no effect when decompressing.'); }
@@ -104,7 +115,12 @@ if (opt.decompress && type === 'bzip2' && opt.block < 0) {
 }
 var input = readAll(inFd), result;
 try {
-  if (opt.decompress) {
+  if (opt.recover) {
+    var blocks = 0, good = 0;
+    result = fronts.bzip2.recoverFile(input.bytes, null, function (pos, size, status) { blocks++; if (status === 0) { good++; } },
+                                      opt.recover === '--repair');
+    console.error('recovered ' + good + ' of ' + blocks + ' blocks (' + result.length + ' bytes)');
+  } else if (opt.decompress) {
     if (opt.block >= 0) {
       if (type !== 'bzip2') { fail('--block needs -t bzip2'); }
       result = fronts.bzip2.decompressBlock(input.bytes, opt.block);

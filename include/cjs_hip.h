@@ -126,6 +126,44 @@ int cjs_bzip2_decompress_device(const uint8_t *d_in, size_t n, int multistream, 
 int cjs_bzip2_decompress_batch_device(const uint8_t *d_in, const size_t *in_off, size_t count, int multistream, uint8_t *d_out,
                                       size_t out_cap, size_t *out_off, size_t *out_len, int32_t *status, size_t *out_need,
                                       const cjs_opts *opts);
+/* Recovery of damaged .bz2 data (what bzip2recover is for): the blocks that are still intact, as their decoded bytes
+ * (as_stream == 0) or as a repaired single-stream .bz2 (as_stream != 0).  The input is any n bytes: no header is needed and
+ * none is checked.  A CANDIDATE is every bit position at which the 48-bit block magic 0x314159265359 starts (end-of-stream
+ * magics are ignored).  It is DECODABLE if the block decoder accepts it under the level-9 limits, whatever any header says
+ * (at most 900000 BWT bytes, origPtr below their count, not randomised -- bzip2recover's re-wrapping as 'BZh9'), and its
+ * end-of-block code ends strictly inside the input (end_bit < 8 n: a block that touches the end counts as cut off); INTACT if
+ * the CRC of its decoded bytes is the stored one.  The candidates are walked in ascending bit position with last_end = 0: one
+ * that starts below last_end is SHADOWED (a false magic inside a block already accepted); otherwise an intact one is RECOVERED
+ * and sets last_end to its end_bit; otherwise it is lost.  Only a recovered block shadows anything.
+ * Bytes form: the decoded bytes of the recovered blocks in order.  Stream form: 'BZh9', the bit strings [bitpos, end_bit) of the
+ * recovered blocks back to back from bit 32, the end-of-stream magic, the combined CRC (c = rol1(c) ^ stored crc, from 0), zero
+ * bits to a whole byte; with nothing recovered the 14-byte empty stream.  For input that cjs_bzip2_decompress(.., 1) accepts the
+ * bytes form is that call's output and the recovered (bitpos, size) are cjs_bzip2_table(.., 1)'s; the stream form always decodes
+ * to the bytes form of the same input.
+ * Returns 0 whenever the call itself worked, also when nothing was recovered; a negative code is a failure of the call
+ * (CJS_E_INVALID_ARG, CJS_E_NO_DEVICE, CJS_E_HIP, CJS_E_OUT_OF_MEMORY, CJS_E_OUTPUT_TOO_SMALL).  *n_found = the number of
+ * candidates; found (may be NULL with cap == 0) gets the first cap of them, ascending.  *out: the rules of cjs_bzip2_decompress
+ * (cjs_free).  NULL out / out_n / n_found, NULL in with n > 0, NULL found with cap > 0: CJS_E_INVALID_ARG before the device is
+ * touched; n < 6 (no magic fits): success with nothing found, also before the device is touched (the stream form is then the
+ * empty stream).  opts->device is honoured, n_devices and stats are ignored.
+ * _device: the memory rules of cjs_bzip2_decompress_device for d_in / d_out (any alignment, checked before any launch); found
+ * and n_found are host memory.  A result above out_cap: CJS_E_OUTPUT_TOO_SMALL with *out_n = the bytes needed (out_cap = 0,
+ * d_out = NULL: the size query; *n_found and found are filled all the same).  No byte at or past out_cap is ever written; the
+ * contents of d_out are unspecified after CJS_E_OUTPUT_TOO_SMALL, and in [*out_n, out_cap) on success. */
+#define CJS_REC_SHADOWED 1
+typedef struct cjs_bz_found {
+  uint64_t bitpos;    /* where the candidate's magic starts in the input */
+  uint64_t end_bit;   /* first bit behind its end-of-block code; 0 if not decodable */
+  uint64_t out_off;   /* recovered: byte offset in the bytes form / bit position of its magic in the stream form */
+  uint32_t size;      /* recovered: decoded bytes */
+  int32_t  status;    /* 0 recovered, CJS_REC_SHADOWED, else the block's code: CJS_E_DATA_ERROR, CJS_E_OBSOLETE_INPUT */
+  uint32_t crc;       /* stored block CRC; 0 if the header could not be read */
+  uint32_t reserved;  /* 0 */
+} cjs_bz_found;
+int cjs_bzip2_recover(const uint8_t *in, size_t n, int as_stream, uint8_t **out, size_t *out_n,
+                      cjs_bz_found *found, long cap, long *n_found, const cjs_opts *opts);
+int cjs_bzip2_recover_device(const uint8_t *d_in, size_t n, int as_stream, uint8_t *d_out, size_t out_cap, size_t *out_n,
+                             cjs_bz_found *found, long cap, long *n_found, const cjs_opts *opts);
 /* Streaming form of cjs_bzip2_compress: the input is written in pieces of any size (zero included), the .bz2 stream is read in
  * pieces of any size, and the bytes read, in order, once cjs_bzip2_enc_finish has returned, are exactly what
  * cjs_bzip2_compress(all written bytes, level) returns -- for every level, every split of the input, every chunk_bytes and every
