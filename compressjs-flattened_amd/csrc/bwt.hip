@@ -4,19 +4,41 @@
 // BWT.bwtransform (sentinel; J/BWTC_joined_.js:1125-1145) for ALL blocks of a batch at once.
 // The reference runs SA-IS (serial induced sorting) per block.  A suffix array is unique, so
 // any correct construction gives the same BWT; here it is prefix doubling (Manber-Myers /
-// Larsson-Sadakane) expressed as data-parallel passes over all blocks' suffixes together:
+// Larsson-Sadakane) expressed as data-parallel passes over all blocks' suffixes together.
 //
-//   round 0 : key = (block id, first 4 bytes)                      -> groups of depth 4
-//   round r : key = (group ordinal, rank[i + h]) for suffixes in unresolved groups only,
-//             h = 4, 8, 16, ...                                    -> depth doubles
-//   each round: LSD radix sort (8-bit digits, LDS-staged buckets, wave64 match-any ranking)
-//               -> regroup (flags + tile scan + apply) -> compaction of the still-unresolved set.
+// Round 1 sorts every suffix by its leading 7 symbols (fewer when the block id has to share the key) with the segmented radix
+// sorter of radix.hip, one segment per block:
+//   cyclic    packed two-phase records, one u64 per suffix and no value array: bytes 2..6 first, then bwt_phase2_records
+//             rebuilds the records as bytes 0..1 | rank of the class of bytes 2..6 | the byte in front | position, and two more
+//             passes finish depth 7
+//   sentinel  (u64 key, u32 value) records, 9-bit symbols
+//   fallback  more blocks or tiles than the workspace has segments for, blocks of different lengths (bwt_run_var), or
+//             CJS_NO_SEGMENTED_SORT: bwt_init_keys writes keys with the block id on top, sorted as one array
+// Rounds >= 2 sort only the suffixes of unresolved groups, by (group ordinal, rank of suffix + h), h = 7, 14, 28, ...  The array
+// is already ordered by group, so the tile sorters order every group of <= 1024 suffixes in LDS and fetch the ranks themselves;
+// larger groups are deferred: compacted, radix-sorted apart, scattered back.  Whole-array fallbacks (radix passes over keys that
+// bwt_gather_keys writes): fewer than 8192 unresolved suffixes, or more than half of the workspace deferred.
+// Every round ends in a regroup: new ranks into R, resolved suffixes out (cyclic: their BWT byte straight into the output;
+// sentinel: into SA), survivors compacted.  The host reads the survivor and group counts behind the tile scan and queues the
+// next round.  Cyclic blocks with h >= the block length hold only equal rotations: bwt_flush_active emits them as they stand.
+//
+// Launches of one round, in order ([..]: only when the condition holds):
+//   sort, round 1    [fallback: bwt_init_keys]  radix passes (rs_hist | rs_hist_bytes, rs_scan_*, rs_scatter per digit)
+//                    [packed: bwt_phase2_records, two more radix passes]
+//   sort, round >= 2 [large groups possible: dev_fill dflag]  bwt_tile_sort | bwt_tile_sort_radix
+//                    [large groups possible: bwt_defer_count, scan_u32_single x 2, HOST WAIT; if any:
+//                     bwt_defer_gather, radix passes, bwt_defer_scatter | over half deferred: bwt_gather_keys, whole-array sort]
+//     whole array:   radix passes, bwt_key_flags
+//   regroup          bwt_flags (round 1) | bwt_flags_bytes -> bwt_scan_tiles -> event -> bwt_apply
+//                    round 1, packed, >= 8 blocks: bwt_apply sweep 1 -> bwt_scan_tiles -> event -> bwt_apply sweep 2
+//   HOST WAIT on the event; then [equal rotations only: bwt_flush_active, done]  [next round whole-array: bwt_gather_keys]
+// After the last round: bwt_pidx, [sentinel: bwt_emit_sentinel].
 //
 // Integer sort/scan only (no MFMA); HBM-bound on the radix scatter passes.
-#include "cjs_internal.h"
-#include "prims.hpp"
+#include "radix.hpp"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 namespace cjs {
 
@@ -28,330 +50,11 @@ __device__ __forceinline__ uint32_t blk_len(const Geom& g, uint32_t blk) { retur
 // fixed-geometry instantiation (bwt_run) is the code it was before.
 struct VarGeom { uint32_t nb, stride, n_last; const uint32_t* len; };
 __device__ __forceinline__ uint32_t blk_len(const VarGeom& g, uint32_t blk) { return g.len[blk]; }
-template <typename G> struct is_var_geom { static constexpr bool value = false; };
-template <> struct is_var_geom<VarGeom> { static constexpr bool value = true; };
-
-// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2),
-// so workgroup w = 8*j + x works on tile x*ceil(T/8) + j: every XCD walks ONE contiguous range of the
-// suffix array, i.e. one block at a time, and that block's rank array (3.6 MB) stays in its L2 while the
-// kernel scatters / gathers ranks at random positions of it.  Speed only; any mapping is correct.
-__device__ __forceinline__ uint32_t xcd_tile(uint32_t wg, uint32_t T) {
-  const uint32_t per = (T + 7u) >> 3;
-  return (wg & 7u) * per + (wg >> 3);
-}
-__host__ __device__ __forceinline__ uint32_t xcd_grid(uint32_t T) { return ((T + 7u) >> 3) << 3; }
-
-// ------------------------------------------------------------------------------------------
-// LSD radix sort pass: histogram -> per-bin scan over tiles -> stable scatter
-// ------------------------------------------------------------------------------------------
-// Segments: the array is nseg runs of `stride` elements (the last one n_last) that are sorted independently in the
-// same launches (round 1 of the suffix sort: one segment per block, so the block id needs no digit passes of its
-// own).  Tiles never straddle segments: segment s owns tiles [s*tps, (s+1)*tps).  A plain sort is one segment.
-struct SegGeom { uint32_t nseg, stride, n_last, tps; };
-struct TileRef { uint32_t seg, off, nvalid; uint64_t base; };
-__device__ __forceinline__ TileRef tile_ref(const SegGeom& sg, uint32_t tile) {
-  TileRef t;
-  t.seg = tile / sg.tps;
-  t.off = (tile - t.seg * sg.tps) * RS_TILE;
-  const uint32_t sn = t.seg + 1 == sg.nseg ? sg.n_last : sg.stride;
-  t.nvalid = t.off < sn ? (sn - t.off < RS_TILE ? sn - t.off : RS_TILE) : 0u;
-  t.base = (uint64_t)t.seg * sg.stride + t.off;
-  return t;
-}
-// Key source of the first pass of round 1: keys are made on the fly from the block bytes (no key array is ever
-// written for them).  key = leading nsym symbols | block parity above them (adjacent blocks must not compare equal);
-// cyclic: bytes, wrapping; sentinel: 9-bit symbols byte+1, 0 = past the end.  value = position in the block.
-struct GenSrc { const uint8_t* T; int cyclic, nsym, packed; };
-// packed records (cyclic round 1): ONE u64 per suffix = 5 bytes (bits 63..24) | block parity (bit 20) | position in the block
-// (bits 19..0): a radix pass moves 8 B per suffix each way instead of 12, and there is no value array.  The first phase sorts by
-// bytes 2..6 of the suffix (packed == 2, the only packed form)
-constexpr int PK_SHIFT = 20, PK_KEY_LO = 24;
-constexpr uint32_t PK_POS_MASK = (1u << PK_SHIFT) - 1u;
-// records of the two-phase sort after bwt_phase2_records: byte0 . byte1 (63..48) | rank of the class of bytes 2..6 (47..28) | the byte IN
-// FRONT of the suffix (27..20) | position (19..0).  The group key is key >> PK2_GSHIFT; block boundaries are taken from the slot
-// number (no parity bit).  The byte in front is what the BWT emits for the suffix: it rides along (later in the top byte of val[])
-// so that the regroup kernels write BWT bytes without gathering them from the text.
-constexpr int PK2_GSHIFT = 28, PK2_PREV_SHIFT = 20, VAL_PREV_SHIFT = 24;
-constexpr uint32_t GEN_PAD = 8;
-// stages the tile's bytes (+GEN_PAD lookahead) in LDS; returns the byte offset of the tile's first byte inside tb (< 4):
-// tiles that do not touch the end of their block are copied as aligned 32-bit words from the aligned-down address
-__device__ __forceinline__ uint32_t gen_stage(const GenSrc& gs, const SegGeom& sg, const TileRef& t, uint8_t* tb) {
-  const uint32_t sn = t.seg + 1 == sg.nseg ? sg.n_last : sg.stride;
-  const uint8_t* src = gs.T + (size_t)t.seg * sg.stride;
-  if (t.off + RS_TILE + GEN_PAD <= sn) {
-    const uintptr_t a = (uintptr_t)(src + t.off);
-    const uint32_t* al = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-    uint32_t* tw = reinterpret_cast<uint32_t*>(tb);
-    for (uint32_t i = threadIdx.x; i < (RS_TILE + GEN_PAD) / 4 + 1; i += 256) tw[i] = al[i];
-    return (uint32_t)(a & 3);
-  }
-  for (uint32_t i = threadIdx.x; i < RS_TILE + GEN_PAD; i += 256) {
-    uint32_t p = t.off + i;
-    if (p >= sn) p = gs.cyclic ? p % sn : sn - 1;      // sentinel: never used (masked by position)
-    tb[i] = t.nvalid ? src[p] : 0;
-  }
-  return 0;
-}
-__device__ __forceinline__ uint64_t gen_key(const GenSrc& gs, const SegGeom& sg, const TileRef& t, const uint8_t* tb, uint32_t tb0, uint32_t loc) {
-  // the 8 bytes at tb[tb0 + loc ..] from three aligned LDS words
-  const uint32_t* tw = reinterpret_cast<const uint32_t*>(tb) + ((tb0 + loc) >> 2);
-  const uint32_t a0 = tw[0], a1 = tw[1], a2 = tw[2], sh = (tb0 + loc) & 3u;
-  const uint32_t lo = __builtin_amdgcn_alignbyte(a1, a0, sh), hi = __builtin_amdgcn_alignbyte(a2, a1, sh);   // byte j of (hi:lo) = tb[loc + j]
-  uint64_t k = 0;
-  if (gs.cyclic) {
-    k = ((uint64_t)__builtin_bswap32(lo) << 24) | (uint64_t)(__builtin_bswap32(hi) >> 8);     // 7 bytes, first byte on top
-    if (gs.packed) return ((k & 0xFFFFFFFFFFull) << PK_KEY_LO) | ((uint64_t)(t.seg & 1u) << PK_SHIFT) | (uint64_t)(t.off + loc);  // bytes 2..6 (two-phase sort)
-    k >>= 8 * (7 - gs.nsym);
-    k |= (uint64_t)(t.seg & 1u) << (8 * gs.nsym);
-  } else {
-    const uint32_t sn = t.seg + 1 == sg.nseg ? sg.n_last : sg.stride;
-    const uint64_t both = ((uint64_t)hi << 32) | lo;
-    for (int j = 0; j < gs.nsym; j++) k = (k << 9) | (t.off + loc + j < sn ? (uint32_t)((both >> (8 * j)) & 0xFFu) + 1u : 0u);
-    k |= (uint64_t)(t.seg & 1u) << (9 * gs.nsym);
-  }
-  return k;
-}
-
-// Per-tile digit counts, tile-major: hist[tile * 256 + digit] (one coalesced 1 KB row per workgroup; the digit-major
-// layout of round 1 cost a 64-byte memory transaction per 4-byte counter on both sides).
-// LDS atomics of one instruction that meet in one address OR in one bank are done one after the other, and text digits
-// are skewed (a fifth of the lanes carry a space; a pass over a sorted byte has all 64 lanes on one counter): each wave
-// counts into HR = 8 copies of its histogram picked by lane & 7 and laid out digit * 8 + copy, so the copies of a digit
-// sit in eight different banks.  100 M keys, MI355X: 237 us (text digit) / 344 us (sorted digit) with one copy per wave;
-// copies 1 KB apart (same bank) 141 / 190 us with two and slower again with more; interleaved copies 135 us for both,
-// against 125 us for the same loads without any atomic.
-constexpr int HR = 8;
-template <typename K, bool GEN>
-__global__ __launch_bounds__(256) void rs_hist(const K* __restrict__ keys, SegGeom sg, GenSrc gs, int shift,
-                                               uint32_t* __restrict__ hist, uint32_t T) {
-  __shared__ uint32_t h[4 * 256 * HR];
-  __shared__ __attribute__((aligned(16))) uint8_t tb[GEN ? RS_TILE + GEN_PAD + 16 : 16];
-  const int tid = threadIdx.x;
-  uint32_t* hw = h + (tid >> 6) * 256 * HR + (tid & (HR - 1));          // this lane's copy in this wave's histogram
-#pragma unroll
-  for (int i = 0; i < 4 * HR; i++) h[i * 256 + tid] = 0;
-  const uint32_t tile = blockIdx.x;
-  const TileRef t = tile_ref(sg, tile);
-  uint32_t tb0 = 0;
-  if (GEN) tb0 = gen_stage(gs, sg, t, tb);
-  __syncthreads();
-  if (GEN) {
-#pragma unroll 4
-    for (int it = 0; it < 16; it++) {
-      const uint32_t loc = (uint32_t)it * 256 + tid;
-      if (loc < t.nvalid) atomicAdd(&hw[((uint32_t)(gen_key(gs, sg, t, tb, tb0, loc) >> shift) & 255u) * HR], 1u);
-    }
-  } else if (t.nvalid) {
-    // all sixteen loads are issued before the first atomic (written as one loop the compiler waits for each load in turn)
-    K k[16];
-#pragma unroll
-    for (int it = 0; it < 16; it++) {
-      const uint32_t loc = (uint32_t)it * 256 + tid;
-      k[it] = keys[t.base + (loc < t.nvalid ? loc : t.nvalid - 1u)];
-    }
-#pragma unroll
-    for (int it = 0; it < 16; it++)
-      if ((uint32_t)it * 256 + tid < t.nvalid) atomicAdd(&hw[((uint32_t)((uint64_t)k[it] >> shift) & 255u) * HR], 1u);
-  }
-  __syncthreads();
-  uint32_t sum = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int r = 0; r < HR; r++) sum += h[i * 256 * HR + tid * HR + r];
-  hist[(size_t)tile * 256 + tid] = sum;
-}
-
-// The same counts from a byte per key: the scatter pass in front left the NEXT digit of every key it moved in dig[] (same
-// index as the key), so this pass reads 1 B per key instead of 8.  Aligned 32-bit loads over the tile's byte range.
-// With delta > 0 the bytes are the block TEXT (cyclic form): the first pass's digit of the suffix at position p is the text byte
-// at p + delta, so a tile's digits are the text bytes [off + delta, off + delta + nvalid) of its block -- no keys are built for
-// the count (rs_hist<GEN>: 130 us); the one tile per block whose range wraps around the block end counts byte by byte.
-constexpr int HB = 4;   // histogram copies per wave (the zeroing and folding of 4 * 256 * HB counters is most of this kernel's LDS traffic; 59-82 us per 100 M keys with 4, 72-85 with 8, 75-130 with 2)
-__global__ __launch_bounds__(256) void rs_hist_bytes(const uint8_t* __restrict__ dig, SegGeom sg, uint32_t* __restrict__ hist, uint32_t delta) {
-  __shared__ uint32_t h[4 * 256 * HB];
-  const int tid = threadIdx.x;
-  uint32_t* hw = h + (tid >> 6) * 256 * HB + (tid & (HB - 1));
-#pragma unroll
-  for (int i = 0; i < 4 * HB; i++) h[i * 256 + tid] = 0;
-  const uint32_t tile = blockIdx.x;
-  const TileRef t = tile_ref(sg, tile);
-  const uint32_t sn = t.seg + 1 == sg.nseg ? sg.n_last : sg.stride;
-  const bool wraps = delta && t.nvalid && t.off + delta + t.nvalid > sn;         // (wave-uniform)
-  if (wraps) {
-    __syncthreads();
-    const uint8_t* tx = dig + (size_t)t.seg * sg.stride;
-    for (uint32_t e = tid; e < t.nvalid; e += 256) atomicAdd(&hw[(uint32_t)tx[(t.off + e + delta) % sn] * HB], 1u);
-  }
-  const uintptr_t a0 = (uintptr_t)(dig + t.base + delta), a1 = a0 + (wraps ? 0u : t.nvalid);
-  const uint32_t* al = reinterpret_cast<const uint32_t*>(a0 & ~(uintptr_t)3);
-  uint32_t wv[5];
-#pragma unroll
-  for (int j = 0; j < 5; j++) {
-    const uint32_t wi = (uint32_t)j * 256u + tid;
-    wv[j] = (t.nvalid && (uintptr_t)(al + wi) < a1) ? al[wi] : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 5; j++) {
-    const uintptr_t wa = (uintptr_t)(al + ((uint32_t)j * 256u + tid));
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-      if (wa + b >= a0 && wa + b < a1) atomicAdd(&hw[((wv[j] >> (8 * b)) & 255u) * HB], 1u);
-  }
-  __syncthreads();
-  uint32_t sum = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int r = 0; r < HB; r++) sum += h[i * 256 * HB + tid * HB + r];
-  hist[(size_t)tile * 256 + tid] = sum;
-}
-
-// one workgroup per segment: exclusive scan over the segment's tiles of every digit's count (thread = digit; the rows are
-// read coalesced and the loads of a batch are independent, only the running sums are a chain); digit totals -> bintot
-__global__ __launch_bounds__(256) void rs_scan_bins(uint32_t* __restrict__ hist, uint32_t tps, uint32_t* __restrict__ bintot) {
-  uint32_t* p = hist + (size_t)blockIdx.x * tps * 256 + threadIdx.x;
-  uint32_t carry = 0;
-  uint32_t i = 0;
-  for (; i + 8 <= tps; i += 8) {
-    uint32_t v[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = p[(size_t)(i + j) * 256];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { p[(size_t)(i + j) * 256] = carry; carry += v[j]; }
-  }
-  for (; i < tps; i++) { const uint32_t v = p[(size_t)i * 256]; p[(size_t)i * 256] = carry; carry += v; }
-  bintot[(size_t)blockIdx.x * 256 + threadIdx.x] = carry;
-}
-// plain (one-segment) sorts have up to tens of thousands of tiles: three-phase scan, chunks of SB_CHUNK tiles
-constexpr uint32_t SB_CHUNK = 64;
-__global__ __launch_bounds__(256) void rs_scan_chunk_sum(const uint32_t* __restrict__ hist, uint32_t T, uint32_t* __restrict__ csum) {
-  const uint32_t t0 = blockIdx.x * SB_CHUNK, t1 = t0 + SB_CHUNK < T ? t0 + SB_CHUNK : T;
-  uint32_t acc = 0;
-  for (uint32_t t = t0; t < t1; t++) acc += hist[(size_t)t * 256 + threadIdx.x];
-  csum[(size_t)blockIdx.x * 256 + threadIdx.x] = acc;
-}
-__global__ __launch_bounds__(256) void rs_scan_chunk_mid(uint32_t* __restrict__ csum, uint32_t nch, uint32_t* __restrict__ bintot) {
-  uint32_t carry = 0;
-  for (uint32_t c = 0; c < nch; c++) { const uint32_t v = csum[(size_t)c * 256 + threadIdx.x]; csum[(size_t)c * 256 + threadIdx.x] = carry; carry += v; }
-  bintot[threadIdx.x] = carry;
-}
-__global__ __launch_bounds__(256) void rs_scan_chunk_apply(uint32_t* __restrict__ hist, uint32_t T, const uint32_t* __restrict__ csum) {
-  const uint32_t t0 = blockIdx.x * SB_CHUNK, t1 = t0 + SB_CHUNK < T ? t0 + SB_CHUNK : T;
-  uint32_t carry = csum[(size_t)blockIdx.x * 256 + threadIdx.x];
-  for (uint32_t t = t0; t < t1; t++) { const uint32_t v = hist[(size_t)t * 256 + threadIdx.x]; hist[(size_t)t * 256 + threadIdx.x] = carry; carry += v; }
-}
-
-// lanes of the wave that carry the same 8-bit digit.  Per bit: m = the bit spread over a word (v_bfe_i32), one ballot, and
-// the lanes whose bit differs from mine are ballot ^ m, folded into the running OR by one v_bitop3 per half (q | (m ^ bal) =
-// table 0xde): four VALU instructions per bit (the select form took nine).
-__device__ __forceinline__ uint64_t match_any8(uint32_t d) {
-  uint32_t qlo = 0, qhi = 0;
-#pragma unroll
-  for (int b = 0; b < 8; b++) {
-    const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)d, b, 1);      // 0 or ~0
-    const uint64_t bal = __ballot(m != 0);
-    qlo = __builtin_amdgcn_bitop3_b32(m, qlo, (uint32_t)bal, 0xde);
-    qhi = __builtin_amdgcn_bitop3_b32(m, qhi, (uint32_t)(bal >> 32), 0xde);
-  }
-  return ~(((uint64_t)qhi << 32) | qlo);
-}
-
-// One ranking step of a wave: the number of keys with this lane's digit that the wave has seen before this lane's key (earlier
-// steps, then lower lanes of this step); wc = the wave's 256 running digit counts.
-// (Measured and dropped: taking the peer mask out of LDS instead of eight ballots -- every lane ORs its lane bit into the
-// digit's 64-bit word, reads it back, the first lane clears it: 15 VALU + 5 DS instructions instead of ~70 VALU, bit-exact,
-// but same-address LDS atomics are done one lane after the other and text digits put a dozen lanes on one word:
-// rs_scatter 345 vs 320 us, tile sorter 1.07 ms both ways.)
-__device__ __forceinline__ uint32_t rank_step(uint32_t d, uint32_t* __restrict__ wc) {
-  const uint64_t peers = match_any8(d);
-  const uint32_t prior = wc[d];
-  const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
-  __builtin_amdgcn_wave_barrier();
-  if (r == 0) wc[d] = prior + (uint32_t)__popcll(peers);
-  __builtin_amdgcn_wave_barrier();
-  return prior + r;
-}
-
-template <typename K, bool GEN, bool NOVAL>
-__global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, const uint32_t* __restrict__ vin,
-                                                  K* __restrict__ kout, uint32_t* __restrict__ vout, SegGeom sg, GenSrc gs, int shift,
-                                                  const uint32_t* __restrict__ hist, uint32_t T, const uint32_t* __restrict__ bintot,
-                                                  uint8_t* __restrict__ dig /* next digit of every key, at the key's new index (or null) */) {
-  __shared__ __attribute__((aligned(16))) K skey[RS_TILE + 2];
-  __shared__ uint32_t sval[NOVAL ? 1 : RS_TILE];
-  __shared__ uint32_t wcnt[4][256];
-  __shared__ uint32_t goff[256];
-  __shared__ uint32_t sm[4];
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const uint32_t tile = blockIdx.x;
-  const TileRef t = tile_ref(sg, tile);
-  const uint64_t base = t.base;
-  const uint32_t nvalid = t.nvalid;
-  for (int i = tid; i < 1024; i += 256) (&wcnt[0][0])[i] = 0;
-  K k[16];
-  uint32_t v[16];
-  uint32_t rk[16];
-  if (GEN) {
-    uint8_t* tb = reinterpret_cast<uint8_t*>(skey);     // skey is not written before the ranking is done
-    const uint32_t tb0 = gen_stage(gs, sg, t, tb);
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      const uint32_t loc = (uint32_t)w * 1024u + (uint32_t)s * 64u + lane;
-      const bool ok = loc < nvalid;
-      k[s] = ok ? (K)gen_key(gs, sg, t, tb, tb0, loc) : (K)~(K)0;
-      v[s] = ok ? t.off + loc : 0u;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      const uint32_t loc = (uint32_t)w * 1024u + (uint32_t)s * 64u + lane;
-      const bool ok = loc < nvalid;
-      k[s] = ok ? kin[base + loc] : (K)~(K)0;           // (non-temporal loads here: no change, 12.69 vs 12.69 ms per step)
-      v[s] = (ok && !NOVAL) ? vin[base + loc] : 0u;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 16; s++) rk[s] = rank_step((uint32_t)(k[s] >> shift) & 255u, wcnt[w]);
-  __syncthreads();
-  {
-    const uint32_t c0 = wcnt[0][tid], c1 = wcnt[1][tid], c2 = wcnt[2][tid], c3 = wcnt[3][tid];
-    uint32_t total;
-    const uint32_t ex = block_excl_sum<256>(c0 + c1 + c2 + c3, sm, total);
-    uint32_t tot2;
-    const uint32_t binbase = block_excl_sum<256>(bintot[(size_t)t.seg * 256 + tid], sm, tot2);
-    wcnt[0][tid] = ex; wcnt[1][tid] = ex + c0; wcnt[2][tid] = ex + c0 + c1; wcnt[3][tid] = ex + c0 + c1 + c2;
-    goff[tid] = t.seg * sg.stride + binbase + hist[(size_t)tile * 256 + tid] - ex;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 16; s++) {
-    const uint32_t d = (uint32_t)(k[s] >> shift) & 255u;
-    const uint32_t p = wcnt[w][d] + rk[s];
-    skey[p] = k[s];
-    if (!NOVAL) sval[p] = v[s];
-  }
-  __syncthreads();
-#pragma unroll 4
-  for (int it = 0; it < 16; it++) {
-    const uint32_t j = (uint32_t)it * 256u + tid;
-    if (j < nvalid) {
-      const K kk = skey[j];
-      const uint32_t dst = goff[(uint32_t)(kk >> shift) & 255u] + j;
-      kout[dst] = kk;
-      if (!NOVAL) vout[dst] = sval[j];
-      if (dig) dig[dst] = (uint8_t)((uint64_t)kk >> (shift + 8));
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // suffix-sort kernels
 // ------------------------------------------------------------------------------------------
-// round 0 keys: (block id, first nsym symbols).  cyclic: bytes wrap; sentinel: 9-bit symbols, 0 = past the end
+// keys of the unsegmented round 1: (block id, first nsym symbols).  cyclic: bytes wrap; sentinel: 9-bit symbols, 0 = past the end
 // VarGeom: one more bit between the block id and the symbols flags a hole; a hole's symbols are its position (unique)
 template <typename G>
 __global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__ T, G g, int cyclic, int nsym, uint32_t M,
@@ -360,7 +63,7 @@ __global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__
     const uint32_t blk = (uint32_t)(a / g.stride), i = (uint32_t)(a - (uint64_t)blk * g.stride), n = blk_len(g, blk);
     const uint8_t* t = T + (size_t)blk * g.stride;
     uint64_t k = 0;
-    if constexpr (is_var_geom<G>::value) {
+    if constexpr (std::is_same_v<G, VarGeom>) {
       uint32_t x = i;
       if (i >= n) k = (1ull << (8 * nsym)) | i;
       else for (int j = 0; j < nsym; j++) { k = (k << 8) | t[x]; if (++x == n) x = 0; }
@@ -387,7 +90,7 @@ __global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__
 // in round 2) and is not kept.
 struct HalfMap { uint32_t halves, stride; };      // halves 2: the two sweeps are the launches SWEEP 1 and SWEEP 2 of bwt_apply
 
-// round r>=1 keys: (group ordinal, rank of suffix i+h)
+// keys of a round >= 2 for the whole-array sorts: (group ordinal, rank of suffix i+h)
 template <typename G>
 __global__ __launch_bounds__(256) void bwt_gather_keys(G g, int cyclic, uint32_t A, uint32_t h, const uint32_t* __restrict__ R,
                                                        const uint32_t* __restrict__ val, const uint32_t* __restrict__ pos,
@@ -799,7 +502,6 @@ constexpr uint32_t TS_WIN = 4096, TS_MAXGRP = 1024, TS_NOM = TS_WIN - TS_MAXGRP,
 // only group a window cannot see whole is the one that runs into it from the left; whether the window before owns that one
 // (<= TS_MAXGRP members, all inside its 4096 slots) follows from the 1024 ordinals in front of the window.
 template <typename G> struct TsGatherT { const uint32_t* R; const uint32_t* pos; const uint32_t* gord; uint32_t h; int cyclic; G g; };
-using TsGather = TsGatherT<Geom>;
 // slot of step s of a thread: 64 consecutive slots per wave instruction in both layouts (word of a slot = slot >> 6)
 template <bool WMAP> __device__ __forceinline__ uint32_t ts_slot(int s, int tid) {
   return WMAP ? (uint32_t)(tid >> 6) * 1024u + (uint32_t)s * 64u + (uint32_t)(tid & 63) : (uint32_t)s * 256u + (uint32_t)tid;
@@ -1387,90 +1089,91 @@ __global__ __launch_bounds__(256) void bwt_emit_sentinel(const uint8_t* __restri
 // ------------------------------------------------------------------------------------------
 // host orchestration
 // ------------------------------------------------------------------------------------------
-static int bits_for(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
+// Slots of BwtWork::counters and of their pinned mirror h_counters.  bwt_scan_tiles writes slots 0, 1 and 4 by number (it moves
+// the large-group flag to the mirror and clears it); the deferral scans of sort_round write 2 and 3.
+enum Counter { CN_SURVIVORS = 0, CN_GROUPS = 1, CN_DEFERRED = 2, CN_DEFERRED_GROUPS = 3, CN_LARGE_GROUP = 4 };
+
 size_t BwtWork::bytes_needed(size_t cap) {
-  const size_t T = hist_tiles_for(cap);
+  const size_t T = RadixWork::hist_tiles_for(cap);
   size_t b = 0;
   auto add = [&](size_t n) { b += (n + 255) & ~(size_t)255; };
   add(cap * 8); add(cap * 8); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4);  // key x2, val x2, pos x2, gord
   add(cap * 4); add(cap * 4); add(cap); add(cap);  // R, SA, dflag, hflag
-  add(hist_words(T) * 4); add(256 * segs_for(cap) * 4); add(3 * T * 4); add(64); add(16 * 256 * 4);
+  add(RadixWork::hist_words(T) * 4); add(256 * RadixWork::segs_for(cap) * 4); add(3 * T * 4); add(64);
   return b + 4096;
 }
 int BwtWork::carve(Arena& a, size_t cap_) {
   cap = cap_;
-  const size_t T = hist_tiles_for(cap);
-  hist_tiles = (uint32_t)T; bintot_segs = (uint32_t)segs_for(cap);
+  const size_t T = RadixWork::hist_tiles_for(cap);
   key[0] = a.take<uint64_t>(cap); key[1] = a.take<uint64_t>(cap);
   val[0] = a.take<uint32_t>(cap); val[1] = a.take<uint32_t>(cap);
   pos[0] = a.take<uint32_t>(cap); pos[1] = a.take<uint32_t>(cap);
   gord = a.take<uint32_t>(cap);
   R = a.take<uint32_t>(cap); SA = a.take<uint32_t>(cap); dflag = a.take<uint8_t>(cap); hflag = a.take<uint8_t>(cap);
-  hist = a.take<uint32_t>(hist_words(T)); bintot = a.take<uint32_t>(256 * (size_t)bintot_segs);
+  CJS_TRY(rs.carve(a, T, RadixWork::segs_for(cap)));
   tile_cnt = a.take<uint32_t>(3 * T); counters = a.take<uint32_t>(16);
-  ghist = a.take<uint32_t>(16 * 256);
-  if (!counters || !ghist) return CJS_E_OUT_OF_MEMORY;
+  if (!counters) return CJS_E_OUT_OF_MEMORY;
   if (!h_counters) CJS_HIP_TRY(hipHostMalloc((void**)h_counters.put(), 64));
   if (!ev_scan) CJS_HIP_TRY(hipEventCreateWithFlags(ev_scan.put(), hipEventDisableTiming));
   return 0;
 }
 
-template <typename K>
-static int radix_passes(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit,
-                        LaunchTimes* lt, const SegGeom* seg = nullptr, const GenSrc* gen = nullptr, bool noval = false,
-                        bool first_hist_ready = false,         // first_hist_ready: w.hist already holds the tile counts of the first digit
-                        uint8_t* dig = nullptr) {              // dig: byte per key for the next pass's counts (see rs_hist_bytes)
-  const uint32_t T1 = (n + RS_TILE - 1) / RS_TILE;
-  const SegGeom sg = seg ? *seg : SegGeom{1u, n, n, T1};
-  const uint32_t T = sg.nseg * sg.tps;
-  if (T > w.hist_tiles || sg.nseg > w.bintot_segs) return CJS_E_INVALID_ARG;
-  K* kk[2] = {k0, k1}; uint32_t* vv[2] = {v0, v1};
-  const GenSrc g0{nullptr, 0, 0, 0};
-  for (int shift = lo_bit; shift < hi_bit; shift += 8) {
-    const bool first_gen = gen && shift == lo_bit;        // the first pass makes its keys from the block bytes
-    const bool dig_out = dig && shift + 8 < hi_bit;          // a pass follows: leave its digits
-    if (first_hist_ready && shift == lo_bit) {}
-    else if (dig && shift != lo_bit) hipLaunchKernelGGL(rs_hist_bytes, dim3(T), dim3(256), 0, s, dig, sg, w.hist, 0u);
-    else if (first_gen && gen->cyclic && gen->packed && shift == PK_KEY_LO)       // packed cyclic sort: the first digit is the text byte at suffix + 6
-      hipLaunchKernelGGL(rs_hist_bytes, dim3(T), dim3(256), 0, s, gen->T, sg, w.hist, 6u);
-    else if (first_gen) hipLaunchKernelGGL((rs_hist<K, true>), dim3(T), dim3(256), 0, s, kk[cur], sg, *gen, shift, w.hist, T);
-    else hipLaunchKernelGGL((rs_hist<K, false>), dim3(T), dim3(256), 0, s, kk[cur], sg, g0, shift, w.hist, T);
-    if (sg.tps <= 4 * SB_CHUNK) hipLaunchKernelGGL(rs_scan_bins, dim3(sg.nseg), dim3(256), 0, s, w.hist, sg.tps, w.bintot);
-    else {                                    // one long segment (nseg > 1 with long segments: still correct, one launch per segment)
-      for (uint32_t sgi = 0; sgi < sg.nseg; sgi++) {
-        uint32_t* hseg = w.hist + (size_t)sgi * sg.tps * 256;
-        const uint32_t nch = (sg.tps + SB_CHUNK - 1) / SB_CHUNK;
-        uint32_t* csum = w.hist + (size_t)w.hist_tiles * 256;          // behind the per-tile rows (BwtWork::hist_words)
-        hipLaunchKernelGGL(rs_scan_chunk_sum, dim3(nch), dim3(256), 0, s, hseg, sg.tps, csum);
-        hipLaunchKernelGGL(rs_scan_chunk_mid, dim3(1), dim3(256), 0, s, csum, nch, w.bintot + (size_t)sgi * 256);
-        hipLaunchKernelGGL(rs_scan_chunk_apply, dim3(nch), dim3(256), 0, s, hseg, sg.tps, csum);
-      }
-    }
-    if (lt) lt->begin(s, n);
-#define RS_SCATTER(GEN_, NOVAL_, G_) hipLaunchKernelGGL((rs_scatter<K, GEN_, NOVAL_>), dim3(T), dim3(256), 0, s, kk[cur], vv[cur], kk[1 - cur], vv[1 - cur], sg, G_, shift, w.hist, T, w.bintot, dig_out ? dig : nullptr)
-    if (noval) { if (first_gen) RS_SCATTER(true, true, *gen); else RS_SCATTER(false, true, g0); }
-    else { if (first_gen) RS_SCATTER(true, false, *gen); else RS_SCATTER(false, false, g0); }
-#undef RS_SCATTER
-    if (lt) lt->end(s);
-    cur = 1 - cur;
-  }
-  CJS_HIP_TRY(hipGetLastError());
-  return 0;
+// Round 1, decided once per run.  Segmented (normal case): one segment per block, keys generated from the block bytes in the
+// first pass, 7 symbols + the block parity; cyclic blocks sort as packed two-phase records (file header; same-box A/Bs in
+// profiles/r02_*: the seven passes + the record rebuild cost more than five passes, but 61 M instead of 83.5 M suffixes stay
+// unresolved behind them and every suffix-round costs ~55 ps), and their scatter passes leave the next digit of every key as a
+// byte for the next pass's counts.  Fallback (more tiles / segments than the workspace was carved for, e.g. many tiny blocks):
+// keys materialised with the block id on top, sorted as one array.
+struct Plan {
+  bool segmented, packed;
+  bool sweeps;                        // two-sweep rank scatter of round 1 (see HalfMap): pays only with the packed records (the second sweep of the 12-byte form re-reads more than the merged stores save: 2.15 vs 1.64 ms)
+  int nsym, bits;                     // symbols and key bits of the round-1 sort
+  int gs1, carried;                   // group key of the round-1 records = key >> gs1; the records (then val[]) carry the byte in front of their suffix
+  SegGeom sg; GenSrc gen;
+  const uint8_t* Tx; uint8_t* U;      // cyclic form: the regroup kernels write the BWT bytes of the suffixes they resolve themselves; sentinel form: null, it keeps a suffix array
+};
+template <typename G>
+static Plan plan_round1(const BwtWork& w, const G& g, bool cyclic, const uint8_t* d_T, uint8_t* d_U) {
+  constexpr bool VAR = std::is_same_v<G, VarGeom>;
+  Plan p;
+  const int sym_bits = cyclic ? 8 : 9;
+  const uint32_t tps = ((g.nb > 1 ? g.stride : g.n_last) + RS_TILE - 1) / RS_TILE;
+  p.segmented = !VAR && (uint64_t)g.nb * tps <= w.rs.hist_tiles && g.nb <= w.rs.bintot_segs && getenv("CJS_NO_SEGMENTED_SORT") == nullptr;
+  p.packed = p.segmented && cyclic;
+  p.sweeps = g.nb >= 8 && p.packed;
+  const int blk_bits = bits_for(g.nb - 1) + (VAR ? 1 : 0);           // (VarGeom: + the hole bit)
+  p.nsym = p.segmented || (64 - blk_bits) / sym_bits > 7 ? 7 : (64 - blk_bits) / sym_bits;
+  p.bits = p.nsym * sym_bits + (p.segmented ? 0 : blk_bits);
+  p.gs1 = p.packed ? PK2_GSHIFT : 0;
+  p.carried = p.packed ? 1 : 0;
+  p.sg = SegGeom{g.nb, g.stride, g.n_last, tps};
+  p.gen = GenSrc{d_T, cyclic ? 1 : 0, p.nsym, p.packed ? 2 : 0};
+  p.Tx = cyclic ? d_T : nullptr; p.U = cyclic ? d_U : nullptr;
+  return p;
 }
 
-// 32-bit-key variant for other stages (decode.hip: stable partition of the BWT bytes = LF vector build)
-template <typename K>
-int radix_passes_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit) {
-  return radix_passes<K>(s, w, k0, v0, k1, v1, cur, n, lo_bit, hi_bit, nullptr);
+// What a run carries from round to round.
+struct Round {
+  int c = 0, pc = 0;                 // which key / val buffer and which pos buffer hold the active arrays
+  uint32_t A = 0, h = 0;             // active (unresolved) suffixes; depth they are sorted to
+  int bits = 0;                      // key bits of the next sort
+  uint32_t ngroups = 0, rounds = 0;  // groups among the active suffixes; rounds done
+  bool no_large_groups = false;      // no unresolved group exceeds the tile sorters' limit any more
+};
+
+template <typename G>
+static int sort_round1(hipStream_t s, BwtWork& w, const G& g, const Plan& p, Round& r, LaunchTimes* lt) {
+  if (!p.segmented) {
+    const int grid_lin = (int)((r.A + 255) / 256 < 65535u * 16u ? (r.A + 255) / 256 : 65535u * 16u);
+    hipLaunchKernelGGL(bwt_init_keys<G>, dim3(grid_lin), dim3(256), 0, s, p.gen.T, g, p.gen.cyclic, p.nsym, r.A, w.key[0], w.val[0]);
+    return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt);
+  }
+  if (!p.packed) return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt, &p.sg, &p.gen);
+  CJS_TRY((radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, PK_KEY_LO, 64, lt, &p.sg, &p.gen, true, false, w.dflag)));
+  hipLaunchKernelGGL(bwt_phase2_records, dim3(p.sg.nseg * p.sg.tps), dim3(256), 0, s, w.key[r.c], p.sg, p.gen.T, w.rs.hist, w.key[1 - r.c]);
+  r.c = 1 - r.c;
+  return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 48, 64, lt, &p.sg, nullptr, true, true, w.dflag);
 }
-template int radix_passes_public<uint32_t>(hipStream_t, BwtWork&, uint32_t*, uint32_t*, uint32_t*, uint32_t*, int&, uint32_t, int, int);
-// ... the same over nseg runs of `stride` elements, each sorted by itself (decode.hip: one run per block)
-template <typename K>
-int radix_pass_segments_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride, int lo_bit, int hi_bit, bool noval, bool first_hist_ready) {
-  const SegGeom sg{nseg, stride, stride, (stride + RS_TILE - 1) / RS_TILE};
-  return radix_passes<K>(s, w, k0, v0, k1, v1, cur, nseg * stride, lo_bit, hi_bit, nullptr, &sg, nullptr, noval, first_hist_ready);
-}
-template int radix_pass_segments_public<uint32_t>(hipStream_t, BwtWork&, uint32_t*, uint32_t*, uint32_t*, uint32_t*, int&, uint32_t, uint32_t, int, int, bool, bool);
 
 // Which tile sorter: the LDS radix version costs the same whatever the groups look like (18 ps per suffix), the counting /
 // bitonic version is cheaper once the groups are tiny (round 2 of the bench text, 7.7 suffixes per group: 1.51 vs 1.82 ms;
@@ -1481,9 +1184,9 @@ static void launch_tile_sort(hipStream_t s, uint32_t Tt, uint64_t* key, uint32_t
   else hipLaunchKernelGGL(bwt_tile_sort<TG>, dim3(xcd_grid(Tt)), dim3(256), 0, s, key, val, hflag, A, dflag, tg, Tt);
 }
 // whole-array fallback of a round >= 2: radix passes over the 64-bit keys in key[c], then the flag bytes from the sorted keys
-static int sort_round_whole(hipStream_t s, BwtWork& w, int& c, uint32_t A, int bits, LaunchTimes* lt) {
-  CJS_TRY((radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, lt)));
-  hipLaunchKernelGGL(bwt_key_flags, dim3((A + 255) / 256 < 8192u ? (A + 255) / 256 : 8192u), dim3(256), 0, s, w.key[c], A, w.hflag);
+static int sort_round_whole(hipStream_t s, BwtWork& w, Round& r, LaunchTimes* lt) {
+  CJS_TRY((radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt)));
+  hipLaunchKernelGGL(bwt_key_flags, dim3((r.A + 255) / 256 < 8192u ? (r.A + 255) / 256 : 8192u), dim3(256), 0, s, w.key[r.c], r.A, w.hflag);
   CJS_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1493,43 +1196,79 @@ static bool tile_sorted_round(uint32_t A) { return A >= 2 * TS_WIN; }
 // Works in place on val[c] and leaves the head flags of the sorted order in hflag[]; only the whole-array fallback flips c.
 // key[c] only ever holds the keys of the slots the tile sorters do not own (the deferral kernels read them).
 template <typename TG>
-static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int bits, LaunchTimes* lt, uint32_t ngroups, const TG& tg) {
-  if (!tile_sorted_round(A)) return sort_round_whole(s, w, c, A, bits, lt);      // (bwt_gather_keys made the keys)
-  const uint32_t Tt = (A + TS_NOM - 1) / TS_NOM, Tg = (A + TS_GT - 1) / TS_GT;
+static int sort_round(hipStream_t s, BwtWork& w, Round& r, LaunchTimes* lt, const TG& tg) {
+  if (!tile_sorted_round(r.A)) return sort_round_whole(s, w, r, lt);      // (bwt_gather_keys made the keys)
+  const uint32_t A = r.A, Tt = (A + TS_NOM - 1) / TS_NOM, Tg = (A + TS_GT - 1) / TS_GT;
+  const int c = r.c;
   uint8_t* dflag = w.dflag;
   uint32_t* tcount = w.tile_cnt;                        // 3*cap/4096 entries >= cap/2048
-  if (w.no_large_groups) {                              // groups only ever split: once none exceeds TS_MAXGRP, none will
-    launch_tile_sort(s, Tt, w.key[c], w.val[c], w.hflag, A, nullptr, ngroups, tg);
+  if (r.no_large_groups) {                              // groups only ever split: once none exceeds TS_MAXGRP, none will
+    launch_tile_sort(s, Tt, w.key[c], w.val[c], w.hflag, A, nullptr, r.ngroups, tg);
     CJS_HIP_TRY(hipGetLastError());
     return 0;
   }
   dev_fill(s, dflag, 1, A);
-  launch_tile_sort(s, Tt, w.key[c], w.val[c], w.hflag, A, dflag, ngroups, tg);
-  uint32_t* hcount = w.hist;                            // (free until the radix passes below, which come after the last reader of hcount)
+  launch_tile_sort(s, Tt, w.key[c], w.val[c], w.hflag, A, dflag, r.ngroups, tg);
+  uint32_t* hcount = w.rs.hist;                         // (free between sorts: the radix passes below come after the last reader of hcount)
   hipLaunchKernelGGL(bwt_defer_count, dim3(Tg), dim3(256), 0, s, A, dflag, w.key[c], tcount, hcount);
-  hipLaunchKernelGGL(scan_u32_single, dim3(1), dim3(1024), 0, s, hcount, Tg, w.counters + 3, w.h_counters + 3);      // deferred groups
-  hipLaunchKernelGGL(scan_u32_single, dim3(1), dim3(1024), 0, s, tcount, Tg, w.counters + 2, w.h_counters + 2);      // the kernel writes the pinned mirror itself
+  hipLaunchKernelGGL(scan_u32_single, dim3(1), dim3(1024), 0, s, hcount, Tg, w.counters + CN_DEFERRED_GROUPS, w.h_counters + CN_DEFERRED_GROUPS);
+  hipLaunchKernelGGL(scan_u32_single, dim3(1), dim3(1024), 0, s, tcount, Tg, w.counters + CN_DEFERRED, w.h_counters + CN_DEFERRED);      // the kernel writes the pinned mirror itself
   CJS_HIP_TRY(hipStreamSynchronize(s));
-  const uint32_t D = w.h_counters[2];
+  const uint32_t D = w.h_counters[CN_DEFERRED];
   if (env_debug()) fprintf(stderr, "[cjs bwt]   tile sort: %u of %u suffixes in groups > %u\n", D, A, TS_MAXGRP);
-  if (D == 0) w.no_large_groups = true;
-  if (D == 0) return 0;
+  if (D == 0) { r.no_large_groups = true; return 0; }
   if ((size_t)D > w.cap / 2) {       // no room to sort them apart: the whole array by its keys (the sorted slots hold none: gathered again)
     const uint32_t Tk = (A + RS_TILE - 1) / RS_TILE;
     hipLaunchKernelGGL(bwt_gather_keys<decltype(tg.g)>, dim3(xcd_grid(Tk)), dim3(256), 0, s, tg.g, tg.cyclic, A, tg.h, tg.R, w.val[c], tg.pos, tg.gord, w.key[c], Tk);
-    return sort_round_whole(s, w, c, A, bits, lt);
+    return sort_round_whole(s, w, r, lt);
   }
   uint64_t* dk0 = w.key[1 - c]; uint64_t* dk1 = dk0 + w.cap / 2;
   uint32_t* dv0 = w.val[1 - c]; uint32_t* dv1 = dv0 + w.cap / 2;
-  uint32_t* dpos = w.pos[1 - pc];
+  uint32_t* dpos = w.pos[1 - r.pc];
   hipLaunchKernelGGL(bwt_defer_gather, dim3(Tg), dim3(256), 0, s, w.key[c], w.val[c], A, dflag, tcount, hcount, dk0, dv0, dpos);
   int cur = 0;
-  const uint32_t ndg = w.h_counters[3];                 // deferred groups: dense ordinals 0 .. ndg-1 above the 20-bit rank key
-  CJS_TRY((radix_passes<uint64_t>(s, w, dk0, dv0, dk1, dv1, cur, D, 0, 20 + bits_for(ndg ? ndg - 1 : 0), lt)));
+  const uint32_t ndg = w.h_counters[CN_DEFERRED_GROUPS];      // dense ordinals 0 .. ndg-1 above the 20-bit rank key
+  CJS_TRY((radix_passes<uint64_t>(s, w.rs, dk0, dv0, dk1, dv1, cur, D, 0, 20 + bits_for(ndg ? ndg - 1 : 0), lt)));
   hipLaunchKernelGGL(bwt_defer_scatter, dim3((D + 255) / 256 < 8192u ? (D + 255) / 256 : 8192u), dim3(256), 0, s, D, cur ? dk1 : dk0, cur ? dv1 : dv0, dpos,
                      w.hflag, w.val[c]);
   CJS_HIP_TRY(hipGetLastError());
   return 0;
+}
+
+// The one place that spells out bwt_apply's arguments: the five launches of regroup differ in the template flags only.
+template <bool FIRST, bool PACKED, int SWEEP, typename G>
+static void launch_apply(hipStream_t s, BwtWork& w, const G& g, const Plan& p, const Round& r, uint32_t T) {
+  hipLaunchKernelGGL((bwt_apply<FIRST, PACKED, SWEEP, G>), dim3(xcd_grid(T)), dim3(256), 0, s, FIRST ? w.key[r.c] : nullptr, FIRST ? nullptr : w.hflag,
+                     w.val[r.c], w.pos[r.pc], r.A, g, w.tile_cnt, T, w.R, w.SA, w.val[1 - r.c], w.pos[1 - r.pc], w.gord, HalfMap{SWEEP ? 2u : 1u, g.stride},
+                     p.Tx, p.U, w.counters + CN_LARGE_GROUP, p.gs1, p.carried);
+}
+// Regroup behind a sort: per-tile counts, their scan (the event behind it is what the host waits for), then bwt_apply.
+template <typename G>
+static int regroup(hipStream_t s, BwtWork& w, const G& g, const Plan& p, const Round& r) {
+  const uint32_t T = (r.A + RS_TILE - 1) / RS_TILE;
+  const bool first = r.rounds == 0, sweeps = first && p.sweeps;
+  if (sweeps) launch_apply<true, true, 1>(s, w, g, p, r, T);            // sweep 1 counts as it goes: no counting pass (see bwt_apply)
+  else if (first) hipLaunchKernelGGL(bwt_flags, dim3(T), dim3(256), 0, s, w.key[r.c], r.A, w.tile_cnt, T, p.gs1, w.counters + CN_LARGE_GROUP, g.stride);
+  else hipLaunchKernelGGL(bwt_flags_bytes, dim3(T), dim3(256), 0, s, w.hflag, r.A, w.tile_cnt, T, w.counters + CN_LARGE_GROUP);
+  hipLaunchKernelGGL(bwt_scan_tiles, dim3(1), dim3(1024), 0, s, w.tile_cnt, T, w.counters, w.h_counters);
+  CJS_HIP_TRY(hipEventRecord(w.ev_scan, s));
+  if (sweeps) launch_apply<true, true, 2>(s, w, g, p, r, T);
+  else if (first && p.packed) launch_apply<true, true, 0>(s, w, g, p, r, T);
+  else if (first) launch_apply<true, false, 0>(s, w, g, p, r, T);
+  else launch_apply<false, false, 0>(s, w, g, p, r, T);
+  return 0;
+}
+
+// Behind a regroup: the keys of the next sort, its depth and its key bits
+template <typename G>
+static void prepare_next(hipStream_t s, BwtWork& w, const G& g, bool cyclic, Round& r, TsGatherT<G>& tg) {
+  if (tile_sorted_round(r.A)) tg = TsGatherT<G>{w.R, w.pos[r.pc], w.gord, r.h, (int)cyclic, g};       // the tile sorters fetch the ranks themselves
+  else {
+    const uint32_t Tg = (r.A + RS_TILE - 1) / RS_TILE;
+    hipLaunchKernelGGL(bwt_gather_keys<G>, dim3(xcd_grid(Tg)), dim3(256), 0, s, g, (int)cyclic, r.A, r.h, w.R, w.val[r.c], w.pos[r.pc], w.gord, w.key[r.c], Tg);
+  }
+  r.h = r.h < (1u << 29) ? r.h * 2 : r.h;
+  r.bits = 20 + bits_for(r.ngroups ? r.ngroups - 1 : 0);
 }
 
 // G = Geom: every block `stride` long but the last (n_last).  G = VarGeom: block k is g.len[k] <= stride long, every slot of
@@ -1537,7 +1276,7 @@ static int sort_round(hipStream_t s, BwtWork& w, int& c, int pc, uint32_t A, int
 template <typename G>
 static int bwt_run_impl(hipStream_t s, BwtWork& w, const uint8_t* d_T, const G g, bool cyclic, uint8_t* d_U, uint32_t* d_pidx,
                         cjs_stats* stats, bool resolve_stats) {
-  constexpr bool VAR = is_var_geom<G>::value;
+  constexpr bool VAR = std::is_same_v<G, VarGeom>;
   const uint32_t nb = g.nb, stride = g.stride, n_last = g.n_last;
   if (nb == 0) return 0;
   if (VAR && (!cyclic || n_last != stride)) return CJS_E_INVALID_ARG;
@@ -1546,107 +1285,42 @@ static int bwt_run_impl(hipStream_t s, BwtWork& w, const uint8_t* d_T, const G g
   if (stride > (1u << 20) - 2) return CJS_E_INVALID_ARG;          // ranks must fit 20 bits
   const uint32_t M = (uint32_t)M64;
   const uint32_t max_n = nb > 1 ? stride : n_last;
-  const int grid_lin = (int)((M + 255) / 256 < 65535u * 16u ? (M + 255) / 256 : 65535u * 16u);
   LaunchTimes& lt = w.lt; lt.reset(); lt.enabled = stats != nullptr; lt.min_elems = M;      // the roofline is priced on the full-size scatter passes
+  const Plan p = plan_round1(w, g, cyclic, d_T, d_U);
+  if (VAR && p.nsym < 3) return CJS_E_INVALID_ARG;                 // a hole's position must fit its symbol bits
 
-  int c = 0, pc = 0;        // current key/val buffer, current pos buffer
   dev_fill(s, w.counters, 0, 64);
-  // round 1 sorts by the leading symbols.  Segmented (normal case): one segment per block, keys generated from the
-  // block bytes in the first pass, 7 symbols + the block parity.  Fallback (more tiles/segments than the workspace
-  // was carved for, e.g. many tiny blocks): keys materialised with the block id on top, sorted as one array.
-  const int sym_bits = cyclic ? 8 : 9;
-  const uint32_t tps = ((nb > 1 ? stride : n_last) + RS_TILE - 1) / RS_TILE;
-  const bool segmented = !VAR && (uint64_t)nb * tps <= w.hist_tiles && nb <= w.bintot_segs && getenv("CJS_NO_SEGMENTED_SORT") == nullptr;
-  const int blk_bits = bits_for(nb - 1) + (VAR ? 1 : 0);           // (VarGeom: + the hole bit)
-  int nsym = segmented ? 7 : (64 - blk_bits) / sym_bits;
-  if (nsym > 7) nsym = 7;
-  // packed round-1 records (5 bytes + position in one u64, no value array) for cyclic, segmented sorts, as a two-phase sort:
-  // bytes 2..6 first, then bytes 0..1 with the class of bytes 2..6 carried as a rank (depth 7 at 8 bytes per record; same-box
-  // A/Bs in profiles/r02_*: the seven passes + the record rebuild cost more than five passes, but 61 M instead of 83.5 M suffixes
-  // stay unresolved behind them and every suffix-round costs ~55 ps).  The scatter passes leave the next digit of every key as a
-  // byte for the next pass's counts.  Everything else (sentinel form, unsegmented fallback): (u64 key, u32 value) records.
-  const bool packed = segmented && cyclic;
-  if (packed) nsym = 7;
-  const SegGeom sg{nb, stride, n_last, tps};
-  const GenSrc gen{d_T, cyclic ? 1 : 0, nsym, packed ? 2 : 0};
-  if (VAR && nsym < 3) return CJS_E_INVALID_ARG;                   // a hole's position must fit its symbol bits
-  if (!segmented) hipLaunchKernelGGL(bwt_init_keys<G>, dim3(grid_lin), dim3(256), 0, s, d_T, g, (int)cyclic, nsym, M, w.key[0], w.val[0]);
-  uint32_t A = M, h = (uint32_t)nsym, rounds = 0, ngroups = 0;
-  w.no_large_groups = false;
-  int bits = nsym * sym_bits + (segmented ? 0 : blk_bits);
-  // two-sweep scheduling of the round-1 rank scatter (see HalfMap): pays only with the packed records (the second sweep of the
-  // 12-byte key + value form re-reads more than the merged stores save: 2.15 vs 1.64 ms)
-  const bool sweeps = nb >= 8 && packed;
+  Round r;
+  r.A = M; r.h = (uint32_t)p.nsym; r.bits = p.bits;
   TsGatherT<G> tg{nullptr, nullptr, nullptr, 0u, 0, g};
-  // cyclic form: the regroup kernels write the BWT bytes of the suffixes they resolve themselves; the sentinel form keeps a suffix array
-  const uint8_t* dT = cyclic ? d_T : nullptr;
-  uint8_t* dU = cyclic ? d_U : nullptr;
-  const int gs1 = packed ? PK2_GSHIFT : 0;                              // group key of the round-1 records = key >> gs1
-  const int carried = packed ? 1 : 0;                                   // packed records (then val[]) carry the byte in front of their suffix
   for (;;) {
-    if (rounds == 0) {
-      if (packed) {
-        CJS_TRY((radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, PK_KEY_LO, 64, &lt, &sg, &gen, true, false, w.dflag)));
-        hipLaunchKernelGGL(bwt_phase2_records, dim3(sg.nseg * sg.tps), dim3(256), 0, s, w.key[c], sg, d_T, w.hist, w.key[1 - c]);
-        c = 1 - c;
-        CJS_TRY((radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 48, 64, &lt, &sg, nullptr, true, true, w.dflag)));
-      } else if (segmented) CJS_TRY((radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, &lt, &sg, &gen)));
-      else CJS_TRY((radix_passes<uint64_t>(s, w, w.key[0], w.val[0], w.key[1], w.val[1], c, A, 0, bits, &lt)));
-    } else CJS_TRY(sort_round(s, w, c, pc, A, bits, &lt, ngroups, tg));
-    const uint32_t T = (A + RS_TILE - 1) / RS_TILE;
-    if (rounds == 0 && sweeps) {                                       // two launches, no counting pass (see bwt_apply)
-      const HalfMap hm{2u, stride};
-      hipLaunchKernelGGL((bwt_apply<true, true, 1, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
-                         w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-      hipLaunchKernelGGL(bwt_scan_tiles, dim3(1), dim3(1024), 0, s, w.tile_cnt, T, w.counters, w.h_counters);
-      CJS_HIP_TRY(hipEventRecord(w.ev_scan, s));
-      hipLaunchKernelGGL((bwt_apply<true, true, 2, G>), dim3(xcd_grid(T)), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
-                         w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-    } else {
-    if (rounds == 0) hipLaunchKernelGGL(bwt_flags, dim3(T), dim3(256), 0, s, w.key[c], A, w.tile_cnt, T, gs1, w.counters + 4, stride);
-    else hipLaunchKernelGGL(bwt_flags_bytes, dim3(T), dim3(256), 0, s, w.hflag, A, w.tile_cnt, T, w.counters + 4);
-    hipLaunchKernelGGL(bwt_scan_tiles, dim3(1), dim3(1024), 0, s, w.tile_cnt, T, w.counters, w.h_counters);
-    CJS_HIP_TRY(hipEventRecord(w.ev_scan, s));
-    if (rounds == 0) {
-      const HalfMap hm{1u, stride};
-      const uint32_t grid = xcd_grid(T);
-      if (packed) hipLaunchKernelGGL((bwt_apply<true, true, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
-                                     w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-      else hipLaunchKernelGGL((bwt_apply<true, false, 0, G>), dim3(grid), dim3(256), 0, s, w.key[c], nullptr, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
-                              w.val[1 - c], w.pos[1 - pc], w.gord, hm, dT, dU, w.counters + 4, gs1, carried);
-    } else hipLaunchKernelGGL((bwt_apply<false, false, 0, G>), dim3(xcd_grid(T)), dim3(256), 0, s, nullptr, w.hflag, w.val[c], w.pos[pc], A, g, w.tile_cnt, T, w.R, w.SA,
-                              w.val[1 - c], w.pos[1 - pc], w.gord, HalfMap{1u, stride}, dT, dU, w.counters + 4, gs1, carried);
-    }
+    if (r.rounds == 0) CJS_TRY(sort_round1(s, w, g, p, r, &lt));
+    else CJS_TRY(sort_round(s, w, r, &lt, tg));
+    CJS_TRY(regroup(s, w, g, p, r));
     // the host only needs the counters of the tile scan: it waits for THAT kernel and queues the next round behind the regroup
     // kernel while it runs (a stream synchronisation here left the GPU idle for ~20 us per round)
     CJS_HIP_TRY(hipEventSynchronize(w.ev_scan));
-    rounds++;
-    const uint32_t A2 = w.h_counters[0], NG = w.h_counters[1];
-    if (w.h_counters[4] == 0) w.no_large_groups = true;       // every group of the new grouping fits the tile sorters
-    if (env_debug()) fprintf(stderr, "[cjs bwt] round %u h=%u A=%u bits=%d -> A'=%u groups=%u\n", rounds, h, A, bits, A2, NG);
-    c = 1 - c; pc = 1 - pc;
-    A = A2; ngroups = NG;
-    if (A == 0) break;
-    if (cyclic && h >= max_n) {     // only groups of equal rotations are left
-      hipLaunchKernelGGL(bwt_flush_active<G>, dim3((A + 255) / 256), dim3(256), 0, s, A, w.val[c], w.pos[pc], w.SA, g, dT, dU, carried);
+    r.rounds++;
+    const uint32_t A2 = w.h_counters[CN_SURVIVORS], NG = w.h_counters[CN_GROUPS];
+    if (w.h_counters[CN_LARGE_GROUP] == 0) r.no_large_groups = true;       // every group of the new grouping fits the tile sorters
+    if (env_debug()) fprintf(stderr, "[cjs bwt] round %u h=%u A=%u bits=%d -> A'=%u groups=%u\n", r.rounds, r.h, r.A, r.bits, A2, NG);
+    r.c = 1 - r.c; r.pc = 1 - r.pc;
+    r.A = A2; r.ngroups = NG;
+    if (r.A == 0) break;
+    if (cyclic && r.h >= max_n) {     // only groups of equal rotations are left
+      hipLaunchKernelGGL(bwt_flush_active<G>, dim3((r.A + 255) / 256), dim3(256), 0, s, r.A, w.val[r.c], w.pos[r.pc], w.SA, g, p.Tx, p.U, p.carried);
       break;
     }
-    if (rounds > 40) return CJS_E_HIP;    // cannot happen: depth doubles every round
-    if (tile_sorted_round(A)) tg = TsGatherT<G>{w.R, w.pos[pc], w.gord, h, (int)cyclic, g};       // the tile sorters fetch the ranks themselves
-    else {
-      const uint32_t Tg = (A + RS_TILE - 1) / RS_TILE;
-      hipLaunchKernelGGL(bwt_gather_keys<G>, dim3(xcd_grid(Tg)), dim3(256), 0, s, g, (int)cyclic, A, h, w.R, w.val[c], w.pos[pc], w.gord, w.key[c], Tg);
-    }
-    h = h < (1u << 29) ? h * 2 : h;
-    bits = 20 + bits_for(NG ? NG - 1 : 0);
+    if (r.rounds > 40) return CJS_E_HIP;    // cannot happen: depth doubles every round
+    prepare_next(s, w, g, cyclic, r, tg);
   }
-  hipLaunchKernelGGL(bwt_pidx<G>, dim3(nb), dim3(256), 0, s, g, (int)cyclic, (int)(A != 0), w.R, d_pidx);
+  hipLaunchKernelGGL(bwt_pidx<G>, dim3(nb), dim3(256), 0, s, g, (int)cyclic, (int)(r.A != 0), w.R, d_pidx);
   if constexpr (!VAR) if (!cyclic) {
     const uint32_t Tn = (M + RS_TILE - 1) / RS_TILE;
     hipLaunchKernelGGL(bwt_emit_sentinel, dim3(xcd_grid(Tn)), dim3(256), 0, s, d_T, g, M, w.SA, w.R, d_U, Tn);
   }
   CJS_HIP_TRY(hipGetLastError());
-  if (stats) stats->bwt_rounds = rounds;
+  if (stats) stats->bwt_rounds = r.rounds;
   if (stats && resolve_stats) {                  // (else the caller resolves w.lt once its stream has drained)
     CJS_HIP_TRY(hipStreamSynchronize(s));
     lt.resolve(stats);

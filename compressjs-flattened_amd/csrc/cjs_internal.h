@@ -124,8 +124,21 @@ inline void Arena::destroy() {
 }
 
 constexpr uint32_t RS_TILE = 4096;   // radix-sort tile (256 threads x 16 keys)
+inline int bits_for(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }      // bits needed to write x
 
-// Workspace of the suffix sorter for up to `cap` suffixes (all blocks of a batch together).
+// Workspace of the radix sorter (radix.hip): room for sorts of up to hist_tiles tiles in up to bintot_segs segments.  The rest of
+// the code relies on two things: hist is free between sorts (sort_round of bwt.hip borrows it as hcount), and the chunk sums of
+// the long-segment scan sit behind the hist_tiles per-tile rows (hist_words counts them in).
+struct RadixWork {
+  uint32_t* hist = nullptr;      // hist_words(hist_tiles): 256 per tile (tile-major) + the chunk sums
+  uint32_t* bintot = nullptr;    // 256 per segment
+  uint32_t hist_tiles = 0, bintot_segs = 0;
+  // sizes for sorting up to `cap` keys: segmented sorts round every segment up to whole tiles, one extra tile per 64 Ki keys
+  static size_t hist_tiles_for(size_t cap) { return (cap + RS_TILE - 1) / RS_TILE + cap / 65536 + 258; }
+  static size_t segs_for(size_t cap) { return cap / 65536 + 2; }
+  static size_t hist_words(size_t tiles) { return 256 * (tiles + tiles / 64 + 2); }
+  int carve(Arena& a, size_t tiles, size_t segs);
+};
 struct LaunchTimes {   // event pairs around the dominant kernel; resolved after the stream has drained
   static constexpr int MAXP = 512;
   hipEvent_t ev[2 * MAXP];
@@ -161,6 +174,19 @@ struct LaunchTimes {   // event pairs around the dominant kernel; resolved after
   }
 };
 
+struct SegGeom; struct GenSrc;      // radix.hpp
+// LSD radix passes over bits [lo_bit, hi_bit) of n keys (with their values unless noval) between k0 / v0 and k1 / v1; cur says
+// which pair holds the keys, before and after.  seg: sorted as segments (else one); gen: the first pass makes its keys from the
+// block bytes.  Instantiated for K = uint64_t and uint32_t.
+template <typename K>
+int radix_passes(hipStream_t s, RadixWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit,
+                 LaunchTimes* lt = nullptr, const SegGeom* seg = nullptr, const GenSrc* gen = nullptr, bool noval = false,
+                 bool first_hist_ready = false, uint8_t* dig = nullptr);
+// ... over nseg segments of `stride` 32-bit keys each (decode.hip: one segment per block)
+int radix_pass_segments(hipStream_t s, RadixWork& w, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride,
+                        int lo_bit, int hi_bit, bool noval, bool first_hist_ready);
+
+// Workspace of the suffix sorter for up to `cap` suffixes (all blocks of a batch together).
 struct BwtWork {
   size_t cap = 0;
   uint64_t* key[2] = {nullptr, nullptr};
@@ -171,20 +197,12 @@ struct BwtWork {
   uint32_t* SA = nullptr;
   uint8_t* dflag = nullptr;      // per slot of a round >= 2: 1 = its group is too large for the tile sorters
   uint8_t* hflag = nullptr;      // per slot of a round >= 2, behind the sort: bit 0 = head of the new grouping, bit 1 = head of the previous one
-  uint32_t* hist = nullptr;      // hist_words(tiles): 256 per tile (tile-major) + the chunk sums of the long-segment scan
-  uint32_t* bintot = nullptr;    // 256 per segment
+  RadixWork rs;                  // of the radix passes
   uint32_t* tile_cnt = nullptr;  // 3 * tiles (+ scanned copies)
-  uint32_t* counters = nullptr;  // 16: [0] survivors [1] groups [8] tile ticket [9] look-back error
-  uint32_t* ghist = nullptr;     // [8][256] digit histograms + [8][256] their exclusive scans (onesweep passes)
+  uint32_t* counters = nullptr;  // 16, of which five are in use: see enum Counter in bwt.hip
   Pinned<uint32_t> h_counters;     // host mirror
   Event ev_scan;                   // recorded behind the tile scan of a round (the host waits for the counters, not for the round)
-  uint32_t hist_tiles = 0, bintot_segs = 0;   // capacity of hist (tiles) and bintot (segments)
   LaunchTimes lt;                  // dominant-kernel events of the last bwt_run that was given a stats struct
-  bool no_large_groups = false;    // per bwt_run: no unresolved group exceeds the tile sorter's limit any more
-  // segmented sorts round every block up to whole tiles: room for one extra tile per 64 Ki elements
-  static size_t hist_tiles_for(size_t cap) { return (cap + RS_TILE - 1) / RS_TILE + cap / 65536 + 258; }
-  static size_t segs_for(size_t cap) { return cap / 65536 + 2; }
-  static size_t hist_words(size_t tiles) { return 256 * (tiles + tiles / 64 + 2); }
   static size_t bytes_needed(size_t cap);
   int carve(Arena& a, size_t cap);
 };
@@ -197,12 +215,6 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
 // 1 <= d_len[k] <= stride (device array); BWT bytes to d_U with the same layout.  The slots past a block's length are ignored.
 int bwt_run_var(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, const uint32_t* d_len,
                 uint8_t* d_U, uint32_t* d_pidx);
-// The radix passes of the suffix sorter over n keys / nseg segments of `stride` keys (k0 / v0 in, cur: which buffer holds the
-// result), for the inverse BWT of decode.hip (instantiated for K = uint32_t).
-template <typename K>
-int radix_passes_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit);
-template <typename K>
-int radix_pass_segments_public(hipStream_t s, BwtWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride, int lo_bit, int hi_bit, bool noval, bool first_hist_ready);
 // Inverse sentinel BWT of nb blocks back to back in d_T (lengths lens[], primary indices pidx[], host arrays) into d_out (decode.hip)
 int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint32_t nb, const uint32_t* lens, const uint32_t* pidx, uint8_t* d_out);
 

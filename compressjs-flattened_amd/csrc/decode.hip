@@ -805,14 +805,12 @@ static int ibwt_sentinel_slab(hipStream_t s, const uint8_t* d_T, uint32_t max_le
   CJS_TRY(d_val0.alloc(4 * (size_t)M + 64)); CJS_TRY(d_val1.alloc(4 * (size_t)M + 64));
   CJS_TRY(d_snext.alloc(4 * (size_t)nb * spl_stride)); CJS_TRY(d_ssteps.alloc(4 * (size_t)nb * spl_stride));
   CJS_TRY(d_srank.alloc(4 * (size_t)nb * spl_stride)); CJS_TRY(d_err.alloc(4 * (size_t)nb));
-  CJS_TRY(d_hist.alloc(BwtWork::hist_words(T) * 4)); CJS_TRY(d_bintot.alloc(256 * 4));
-  BwtWork sw;
-  sw.hist = d_hist; sw.bintot = d_bintot; sw.hist_tiles = (uint32_t)T; sw.bintot_segs = 1;
+  CJS_TRY(d_hist.alloc(RadixWork::hist_words(T) * 4)); CJS_TRY(d_bintot.alloc(256 * 4));
+  RadixWork sw{d_hist, d_bintot, (uint32_t)T, 1u};
   if (hipMemcpyAsync(d_blocks, chain.data(), sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) return CJS_E_HIP;
   hipLaunchKernelGGL(ib_make_keys, dim3(64, nb), dim3(256), 0, s, d_blocks.p, d_key0.p, d_val0.p, 0u);
   int cur = 0;
-  int kbits = 8; { uint32_t x = nb - 1; while (x) { kbits++; x >>= 1; } }
-  CJS_TRY(radix_passes_public<uint32_t>(s, sw, d_key0, d_val0, d_key1, d_val1, cur, M, 0, kbits));
+  CJS_TRY(radix_passes<uint32_t>(s, sw, d_key0, d_val0, d_key1, d_val1, cur, M, 0, 8 + bits_for(nb - 1)));
   uint32_t* sval = cur ? d_val1 : d_val0;
   uint32_t* d_dbuf = cur ? d_key0 : d_key1;
   hipLaunchKernelGGL(ib_pack_sentinel, dim3(64, nb), dim3(256), 0, s, d_blocks.p, sval, d_dbuf);
@@ -1174,7 +1172,7 @@ struct IbScratch {
   IbBlock* d_blocks = nullptr; uint32_t *key0 = nullptr, *key1 = nullptr, *val0 = nullptr, *val1 = nullptr;
   uint32_t *snext = nullptr, *ssteps = nullptr, *srank = nullptr, *resume = nullptr; int32_t* d_err = nullptr;
   uint8_t* seg = nullptr;      // ib_walk1's kept bytes: SEG_CAP per splitter
-  BwtWork sw;
+  RadixWork sw;
 };
 
 // batches of the share's chain blocks: [b0, b1) with <= DEC_BATCH_ELEMS elements and <= DEC_BATCH_BLOCKS blocks
@@ -1229,7 +1227,7 @@ void dec_phase_b(DecJob* J, DecShare* S) {
     if (!rc && seg_bytes <= (8ull << 30) && g.take((void**)&q.seg, (size_t)seg_bytes) != 0) q.seg = nullptr;
     const uint32_t tps = (seg_stride + RS_TILE - 1) / RS_TILE;
     const size_t T = strided ? (size_t)nb * tps + 1 : ((size_t)M + RS_TILE - 1) / RS_TILE + 1;
-    if (!rc) rc = g.take((void**)&q.sw.hist, BwtWork::hist_words(T) * 4); if (!rc) rc = g.take((void**)&q.sw.bintot, 256 * 4 * (size_t)(strided ? nb : 1u));
+    if (!rc) rc = g.take((void**)&q.sw.hist, RadixWork::hist_words(T) * 4); if (!rc) rc = g.take((void**)&q.sw.bintot, 256 * 4 * (size_t)(strided ? nb : 1u));
     q.sw.hist_tiles = (uint32_t)T; q.sw.bintot_segs = strided ? nb : 1u;
     if (!rc && hipMemcpyAsync(q.d_blocks, J->chain.data() + b0, sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
     if (!rc && hipMemsetAsync(q.d_err, 0, 4 * (size_t)nb, s) != hipSuccess) rc = CJS_E_HIP;
@@ -1238,11 +1236,8 @@ void dec_phase_b(DecJob* J, DecShare* S) {
     if (strided) hipLaunchKernelGGL(ib_make_keys_hist, dim3(tps, nb), dim3(256), 0, s, q.d_blocks, q.key0, seg_stride, tps, q.sw.hist);
     else hipLaunchKernelGGL(ib_make_keys, dim3(64, nb), dim3(256), 0, s, q.d_blocks, q.key0, q.val0, 0u);
     int cur = 0;
-    if (strided) rc = radix_pass_segments_public<uint32_t>(s, q.sw, q.key0, q.val0, q.key1, q.val1, cur, nb, seg_stride, 0, 8, true, true);
-    else {
-      int kbits = 8; { uint32_t x = nb - 1; while (x) { kbits++; x >>= 1; } }
-      rc = radix_passes_public<uint32_t>(s, q.sw, q.key0, q.val0, q.key1, q.val1, cur, M, 0, kbits);
-    }
+    if (strided) rc = radix_pass_segments(s, q.sw, q.key0, q.val0, q.key1, q.val1, cur, nb, seg_stride, 0, 8, true, true);
+    else rc = radix_passes<uint32_t>(s, q.sw, q.key0, q.val0, q.key1, q.val1, cur, M, 0, 8 + bits_for(nb - 1));
     if (rc) break;
     const uint32_t* sval = strided ? (cur ? q.key1 : q.key0) : (cur ? q.val1 : q.val0);      // (strided: the sorted keys carry the indices)
     uint32_t* d_dbuf = cur ? q.key0 : q.key1;                      // the buffer the sort is not sitting in

@@ -5,6 +5,8 @@ of the new grouping, bit 1 = head of the previous round's grouping).  Every slot
 owns its group, bwt_defer_scatter (groups of more than 1024 suffixes), or bwt_key_flags behind the whole-array fallbacks.
 The cases below put groups on the borders between those writers.  All of them compare block by block with the oracle's BWT
 through cjs_stage_bwt, in both forms (cyclic = bzip2, sentinel = BWTC).
+The last test sorts round 1 unsegmented; its second input is long enough for the radix sorter (radix.hip) to scan the tile
+counts of its one segment in three kernels instead of one.
 """
 import os
 import subprocess
@@ -175,21 +177,35 @@ def test_large_groups_and_fallbacks(hip, oracle, name, cyclic):
 
 
 # ---- unsegmented round 1 in front of the new rounds >= 2 ------------------------------------------------------------------
+# The inputs as expressions: the child process that sorts and the test that asks the oracle build the same bytes from them.
+# "long_scan": 1,000,000 + 34 * 3,000 = 1,102,000 bytes in blocks of 99,981 = 12 blocks (the last 2,209 bytes).  Unsegmented,
+# round 1 sorts them as ONE segment of M = 1,102,000 keys = ceil(M / 4096) = 270 tiles, more than the 256 up to which the radix
+# passes scan a segment's tile counts in one workgroup: the passes take the three-kernel scan (rs_scan_chunk_sum / _mid /
+# _apply), which no segmented sort reaches (a block has at most 2^20 - 2 suffixes = 256 tiles).
+_UNSEG_INPUTS = {
+    "mixed": "np.concatenate([recipes.textgen(250000, 51), np.tile(recipes.textgen(3000, 52), 40), recipes.textgen(30000, 53)])",
+    "long_scan": "np.concatenate([recipes.textgen(1000000, 61), np.tile(recipes.textgen(3000, 62), 34)])",
+}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("cyclic", [True, False], ids=["cyclic", "sentinel"])
-def test_unsegmented_round1_multi_block(oracle, cyclic):
+@pytest.mark.parametrize("cyclic,which", [(True, "mixed"), (False, "mixed"), (True, "long_scan"), (False, "long_scan")],
+                         ids=["cyclic", "sentinel", "cyclic-long_scan", "sentinel-long_scan"])
+def test_unsegmented_round1_multi_block(oracle, cyclic, which):
     """CJS_NO_SEGMENTED_SORT=1 (read per call; set for a child process so that no other test sees it): round 1 sorts all blocks
     as one array with the block id on top of the key, rounds >= 2 are the same kernels"""
     block_len = 99981
     code = ("import sys; sys.path.insert(0, 'tests'); import torch, support, recipes, numpy as np; "
-            "d = np.concatenate([recipes.textgen(250000, 51), np.tile(recipes.textgen(3000, 52), 40), recipes.textgen(30000, 53)]); "
+            "d = %s; "
             "rc, U, pidx = support.HipLib().stage_bwt(d, %d, %s); "
-            "print(rc, support.sha256(U), ','.join(str(int(p)) for p in pidx))" % (block_len, cyclic))
+            "print(rc, support.sha256(U), ','.join(str(int(p)) for p in pidx))" % (_UNSEG_INPUTS[which], block_len, cyclic))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, CJS_NO_SEGMENTED_SORT="1"),
                          cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-1500:]
     rc_s, sha, pidx_s = out.stdout.split()
-    data = np.concatenate([recipes.textgen(250000, 51), np.tile(recipes.textgen(3000, 52), 40), recipes.textgen(30000, 53)])
+    data = eval(_UNSEG_INPUTS[which], {"np": np, "recipes": recipes})
+    if which == "long_scan":
+        assert data.size == 1102000 and -(-data.size // block_len) == 12 and -(-data.size // 4096) == 270
     want_u, want_p = [], []
     for k in range(-(-data.size // block_len)):
         eu, ep = (oracle.bwt_cyclic if cyclic else oracle.bwt_sentinel)(data[k * block_len:(k + 1) * block_len])
