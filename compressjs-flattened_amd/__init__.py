@@ -48,6 +48,13 @@ class Found(ctypes.Structure):
 
 REC_SHADOWED = 1      # CJS_REC_SHADOWED
 
+
+class IndexEntry(ctypes.Structure):
+    """cjs_bz_index_entry: one block of a block index (32 bytes, also its serialised form)."""
+    _fields_ = [("bitpos", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("size", ctypes.c_uint32), ("crc", ctypes.c_uint32),
+                ("level", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 _lib = None
 
 
@@ -102,6 +109,18 @@ def load_library():
     L.cjs_bzip2_shard_pack.argtypes = [V, I, I, I, ctypes.POINTER(ShardMeta), V, S, PS, PS, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.cjs_bzip2_recover.argtypes = [u8p, S, I, PP, PS, ctypes.POINTER(Found), ctypes.c_long, ctypes.POINTER(ctypes.c_long), V]
     L.cjs_bzip2_recover_device.argtypes = [V, S, I, V, S, PS, ctypes.POINTER(Found), ctypes.c_long, ctypes.POINTER(ctypes.c_long), V]
+    PE, PU = ctypes.POINTER(IndexEntry), ctypes.POINTER(ctypes.c_uint64)
+    L.cjs_bzip2_index_build.argtypes = [u8p, S, I, ctypes.POINTER(V), V]
+    L.cjs_bzip2_index_create.argtypes = [PE, S, ctypes.c_uint64, I, ctypes.POINTER(V)]
+    L.cjs_bzip2_index_save.argtypes = [V, PP, PS]
+    L.cjs_bzip2_index_load.argtypes = [u8p, S, ctypes.POINTER(V)]
+    L.cjs_bzip2_index_info.argtypes = [V, PU, PU, PU, ctypes.POINTER(I)]
+    L.cjs_bzip2_index_entries.argtypes = [V, PE, ctypes.c_long]
+    L.cjs_bzip2_index_entries.restype = ctypes.c_long
+    L.cjs_bzip2_index_destroy.argtypes = [V]
+    L.cjs_bzip2_index_destroy.restype = None
+    L.cjs_bzip2_read_ranges.argtypes = [u8p, S, V, PU, PU, S, PP, PS, PS, ctypes.POINTER(ctypes.c_int32), V]
+    L.cjs_bzip2_read_ranges_device.argtypes = [V, S, V, PU, PU, S, V, S, PS, PS, ctypes.POINTER(ctypes.c_int32), PS, V]
     L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
     L.cjs_bzip2_enc_write.argtypes = [V, V, S]
     L.cjs_bzip2_enc_finish.argtypes = [V]
@@ -597,6 +616,135 @@ def decompress_batch_device(d_in_ptr, in_off, d_out_ptr, out_cap, multistream=Fa
     _check(rc)
     detail = L.cjs_last_error_detail().decode() if st[:count].any() else ""
     return off[:count], ln[:count], st[:count], detail
+
+
+def _range_arrays(ranges):
+    r = np.asarray(list(ranges), dtype=np.uint64).reshape(-1, 2)
+    count = r.shape[0]
+    off = np.ascontiguousarray(r[:, 0]) if count else np.zeros(1, dtype=np.uint64)
+    ln = np.ascontiguousarray(r[:, 1]) if count else np.zeros(1, dtype=np.uint64)
+    return count, off, ln, np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.int32)
+
+
+class Bzip2Index:
+    """The block index of a .bz2 stream (cjs_bz_index) and the range reads over it: bytes [off, off + length) of what
+    Bzip2.decompressFile(data, multistream) returns, decoding only the blocks they touch (cjs_bzip2_read_ranges).  Made by
+    build() (one table pass on the GPU), load() (the serialised form save() returns) or create() (a caller's entries)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self._fin = weakref.finalize(self, load_library().cjs_bzip2_index_destroy, handle)
+
+    @staticmethod
+    def build(data, multistream=False):
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        _check(L.cjs_bzip2_index_build(keep.ctypes.data_as(u8p), data.size, 1 if multistream else 0, ctypes.byref(h), None))
+        return Bzip2Index(h)
+
+    @staticmethod
+    def load(raw):
+        L = load_library()
+        raw = _coerce_input(raw)
+        keep = raw if raw.size else np.zeros(1, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        _check(L.cjs_bzip2_index_load(keep.ctypes.data_as(u8p), raw.size, ctypes.byref(h)))
+        return Bzip2Index(h)
+
+    @staticmethod
+    def create(entries, stream_bytes, multistream=False):
+        """entries: (bitpos, end_bit, size, crc, level[, reserved]) per block, in stream order"""
+        L = load_library()
+        entries = list(entries)
+        arr = (IndexEntry * max(len(entries), 1))()
+        for k, e in enumerate(entries):
+            arr[k] = IndexEntry(*e)
+        h = ctypes.c_void_p()
+        _check(L.cjs_bzip2_index_create(arr, len(entries), stream_bytes, 1 if multistream else 0, ctypes.byref(h)))
+        return Bzip2Index(h)
+
+    def save(self):
+        L = load_library()
+        out, out_n = u8p(), ctypes.c_size_t(0)
+        _check(L.cjs_bzip2_index_save(self._h, ctypes.byref(out), ctypes.byref(out_n)))
+        raw = ctypes.string_at(out, out_n.value)
+        L.cjs_free(out)
+        return raw
+
+    def _info(self):
+        b, t, sb, m = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        _check(load_library().cjs_bzip2_index_info(self._h, ctypes.byref(b), ctypes.byref(t), ctypes.byref(sb), ctypes.byref(m)))
+        return b.value, t.value, sb.value, bool(m.value)
+
+    blocks = property(lambda self: self._info()[0])
+    total = property(lambda self: self._info()[1])
+    stream_bytes = property(lambda self: self._info()[2])
+    multistream = property(lambda self: self._info()[3])
+
+    def entries(self):
+        """[(bitpos, end_bit, size, crc, level)] per block"""
+        nb = self.blocks
+        arr = (IndexEntry * max(nb, 1))()
+        load_library().cjs_bzip2_index_entries(self._h, arr, nb)
+        return [(e.bitpos, e.end_bit, e.size, e.crc, e.level) for e in arr[:nb]]
+
+    def read_ranges_raw(self, data, ranges):
+        """cjs_bzip2_read_ranges as it is: (buffer, out_off, out_len, status, detail) for ranges = [(off, length)]"""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        count, off, ln, o_off, o_len, st = _range_arrays(ranges)
+        PU, PS = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t)
+        out = u8p()
+        _check(L.cjs_bzip2_read_ranges(keep.ctypes.data_as(u8p), data.size, self._h, off.ctypes.data_as(PU), ln.ctypes.data_as(PU), count,
+                                       ctypes.byref(out), o_off.ctypes.data_as(PS), o_len.ctypes.data_as(PS),
+                                       st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), None))
+        detail = L.cjs_last_error_detail().decode() if st[:count].any() else ""
+        return _adopt(out, int(o_len[:count].sum())), o_off[:count], o_len[:count], st[:count], detail
+
+    def read_ranges(self, data, ranges):
+        """-> per range its bytes, or a CjsError (the lowest-index failing range's carries the detail)"""
+        L = load_library()
+        buf, o_off, o_len, st, detail = self.read_ranges_raw(data, ranges)
+        res = []
+        for k in range(len(st)):
+            if st[k]:
+                msg = L.cjs_strerror(int(st[k])).decode()
+                res.append(CjsError(int(st[k]), msg + (": " + detail if detail else "")))
+                detail = ""
+            else:
+                res.append(buf[int(o_off[k]):int(o_off[k] + o_len[k])].tobytes())
+        return res
+
+    def read(self, data, off, length):
+        r = self.read_ranges(data, [(off, length)])[0]
+        if isinstance(r, CjsError):
+            raise r
+        return r
+
+
+def read_ranges_device(d_in_ptr, n, index, ranges, d_out_ptr, out_cap, device=-1):
+    """Bzip2Index.read_ranges with the stream and the result in GPU memory (cjs_bzip2_read_ranges_device; the memory rules of
+    decompress_device).  -> (out_off, out_len, status, detail): range k's bytes at d_out + out_off[k]; a failed range keeps its
+    region.  CjsError for a failure of the call, with `need` on CJS_E_OUTPUT_TOO_SMALL (-33); out_cap = 0 with d_out_ptr = None
+    is the size query."""
+    L = load_library()
+    count, off, ln, o_off, o_len, st = _range_arrays(ranges)
+    PU, PS = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t)
+    need = ctypes.c_size_t(0)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    rc = L.cjs_bzip2_read_ranges_device(d_in_ptr, n, index._h, off.ctypes.data_as(PU), ln.ctypes.data_as(PU), count, d_out_ptr, out_cap,
+                                        o_off.ctypes.data_as(PS), o_len.ctypes.data_as(PS), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        ctypes.byref(need), ctypes.byref(opts))
+    if rc == -33:
+        e = CjsError(rc, L.cjs_strerror(rc).decode())
+        e.need = need.value
+        raise e
+    _check(rc)
+    detail = L.cjs_last_error_detail().decode() if st[:count].any() else ""
+    return o_off[:count], o_len[:count], st[:count], detail
 
 
 def trim():

@@ -185,6 +185,35 @@ Bzip2.recoverFile = function (inStream, outStream, callback, asStream) {
   }
   return common.deliver(r.data, outStream);
 };
+// Indexed range reads (cjs_bzip2_read_ranges): bytes [offset, offset + length) of what decompressFile(input, null, multistream)
+// returns, decoding only the blocks they touch.  buildIndex makes the block index of a stream in its serialised form (a
+// Uint8Array to keep beside the file); readRange and readRanges take it back.  A range is clipped at the end of the data, like
+// pread.  readRanges(input, index, [[offset, length], ...]) returns one entry per range: its bytes, or -- for a range that touches
+// a block that is damaged or does not agree with the index -- the TypeError readRange throws for it (the detail on the
+// lowest-index one).
+Bzip2.buildIndex = function (inStream, multistream) {
+  var input = common.coerceInput(inStream);
+  try { return common.addon().bzip2BuildIndex(input.bytes, multistream ? 1 : 0); } catch (e) { rethrow(e); }
+};
+Bzip2.readRanges = function (inStream, index, ranges) {
+  var input = common.coerceInput(inStream), flat = new Float64Array(2 * ranges.length), r;
+  for (var i = 0; i < ranges.length; i++) { flat[2 * i] = ranges[i][0]; flat[2 * i + 1] = ranges[i][1]; }
+  try { r = common.addon().bzip2ReadRanges(input.bytes, index, flat); } catch (e) { rethrow(e); }
+  var out = [], detail = r.detail;
+  for (var k = 0; k < ranges.length; k++) {
+    var code = r.layout[3 * k + 2];
+    if (code === 0) { out.push(r.data.subarray(r.layout[3 * k], r.layout[3 * k] + r.layout[3 * k + 1])); continue; }
+    var t = new TypeError((Messages[code] || 'Data error') + (detail ? ': ' + detail : ''));
+    t.errorCode = code; detail = '';
+    out.push(t);
+  }
+  return out;
+};
+Bzip2.readRange = function (inStream, index, offset, length) {
+  var r = Bzip2.readRanges(inStream, index, [[offset, length]])[0];
+  if (r instanceof Error) { throw r; }
+  return r;
+};
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

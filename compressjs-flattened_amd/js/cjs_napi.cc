@@ -25,6 +25,12 @@ struct Api {
   int (*bzip2_compress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, const cjs_opts*) = nullptr;
   int (*bzip2_decompress_batch)(const uint8_t* const*, const size_t*, size_t, int, uint8_t**, size_t*, size_t*, int32_t*, const cjs_opts*) = nullptr;
   int (*bzip2_recover)(const uint8_t*, size_t, int, uint8_t**, size_t*, cjs_bz_found*, long, long*, const cjs_opts*) = nullptr;
+  int (*index_build)(const uint8_t*, size_t, int, cjs_bz_index**, const cjs_opts*) = nullptr;
+  int (*index_save)(const cjs_bz_index*, uint8_t**, size_t*) = nullptr;
+  int (*index_load)(const uint8_t*, size_t, cjs_bz_index**) = nullptr;
+  void (*index_destroy)(cjs_bz_index*) = nullptr;
+  int (*read_ranges)(const uint8_t*, size_t, const cjs_bz_index*, const uint64_t*, const uint64_t*, size_t, uint8_t**, size_t*, size_t*, int32_t*,
+                     const cjs_opts*) = nullptr;
   int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
   int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
   int (*enc_finish)(cjs_bz_enc*) = nullptr;
@@ -65,6 +71,8 @@ bool load_api() {
   SYM(bzip2_table, "cjs_bzip2_table") SYM(bzip2_decompress_block, "cjs_bzip2_decompress_block")
   SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch") SYM(bzip2_decompress_batch, "cjs_bzip2_decompress_batch")
   SYM(bzip2_recover, "cjs_bzip2_recover")
+  SYM(index_build, "cjs_bzip2_index_build") SYM(index_save, "cjs_bzip2_index_save") SYM(index_load, "cjs_bzip2_index_load")
+  SYM(index_destroy, "cjs_bzip2_index_destroy") SYM(read_ranges, "cjs_bzip2_read_ranges")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(dec_create, "cjs_bzip2_dec_create") SYM(dec_write, "cjs_bzip2_dec_write") SYM(dec_finish, "cjs_bzip2_dec_finish")
@@ -190,6 +198,75 @@ napi_value bzip2_block(napi_env env, napi_callback_info info) {
   const int rc = api.bzip2_decompress_block(p ? p : &dummy, n, (uint64_t)bit, &out, &out_n, nullptr);
   if (rc != 0) return throw_code(env, rc);
   return wrap_result(env, out, out_n);
+}
+
+// bzip2BuildIndex(input, multistream) -> Uint8Array: the serialised block index (Bzip2.buildIndex)
+napi_value bzip2_build_index(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* p = nullptr; size_t n = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &p, &n)) { napi_throw_type_error(env, nullptr, "expected a Uint8Array or Buffer"); return nullptr; }
+  int32_t multi = 0;
+  if (argc >= 2) napi_get_value_int32(env, argv[1], &multi);
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_build(p ? p : &dummy, n, multi, &ix, nullptr);
+  if (rc != 0) return throw_code(env, rc);
+  uint8_t* raw = nullptr; size_t raw_n = 0;
+  rc = api.index_save(ix, &raw, &raw_n);
+  api.index_destroy(ix);
+  if (rc != 0) return throw_code(env, rc);
+  return wrap_result(env, raw, raw_n);
+}
+
+// bzip2ReadRanges(input, index, ranges) -> { data: Uint8Array, layout: Float64Array, detail: string }   (Bzip2.readRanges)
+// index: the serialised index; ranges: Float64Array of (offset, length) pairs.  layout holds (offset in data, length, status) per
+// range; detail is the lowest-index failing range's ("" when none failed).
+napi_value bzip2_read_ranges(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr; size_t n = 0, in = 0;
+  bool is_ta = false;
+  if (argc >= 3) napi_is_typedarray(env, argv[2], &is_ta);
+  napi_typedarray_type t = napi_int8_array; size_t len = 0; void* rd = nullptr; napi_value rab; size_t roff = 0;
+  if (is_ta) napi_get_typedarray_info(env, argv[2], &t, &len, &rd, &rab, &roff);
+  if (argc < 3 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !is_ta || t != napi_float64_array || len % 2) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Float64Array of offset / length pairs)"); return nullptr;
+  }
+  const size_t count = len / 2;
+  const double* r = (const double*)rd;
+  std::vector<uint64_t> off(count + 1), ln(count + 1);
+  for (size_t k = 0; k < count; k++) {
+    const uint64_t o = r[2 * k] >= 0 && r[2 * k] <= 9007199254740992.0 ? (uint64_t)r[2 * k] : 0, l = r[2 * k + 1] >= 0 && r[2 * k + 1] <= 9007199254740992.0 ? (uint64_t)r[2 * k + 1] : 0;
+    if ((double)o != r[2 * k] || (double)l != r[2 * k + 1]) {      // (negative, NaN, above 2^53 or with a fraction)
+      napi_throw_type_error(env, nullptr, "offsets and lengths are integers from 0 to 2^53"); return nullptr;
+    }
+    off[k] = (uint64_t)r[2 * k]; ln[k] = (uint64_t)r[2 * k + 1];
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  std::vector<size_t> o_off(count + 1), o_len(count + 1); std::vector<int32_t> status(count + 1);
+  uint8_t* out = nullptr;
+  rc = api.read_ranges(p ? p : &dummy, n, ix, off.data(), ln.data(), count, &out, o_off.data(), o_len.data(), status.data(), nullptr);
+  std::string detail = api.detail_();                            // (before the next call of the library on this thread)
+  api.index_destroy(ix);
+  if (rc != 0) return throw_code(env, rc);
+  size_t total = 0;
+  for (size_t k = 0; k < count; k++) total += o_len[k];
+  napi_value res, lab, lta, dstr; void* ldst;
+  napi_create_object(env, &res);
+  napi_set_named_property(env, res, "data", wrap_result(env, out, total));
+  napi_create_arraybuffer(env, sizeof(double) * 3 * count, &ldst, &lab);
+  for (size_t k = 0; k < count; k++) { ((double*)ldst)[3 * k] = (double)o_off[k]; ((double*)ldst)[3 * k + 1] = (double)o_len[k]; ((double*)ldst)[3 * k + 2] = (double)status[k]; }
+  napi_create_typedarray(env, napi_float64_array, 3 * count, lab, 0, &lta);
+  napi_set_named_property(env, res, "layout", lta);
+  napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &dstr);
+  napi_set_named_property(env, res, "detail", dstr);
+  return res;
 }
 
 // bzip2Recover(input, asStream) -> { data: Uint8Array, found: Float64Array }   (Bzip2.recoverFile)
@@ -526,6 +603,8 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2Table", nullptr, bzip2_table, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2DecompressBlock", nullptr, bzip2_block, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Recover", nullptr, bzip2_recover, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2BuildIndex", nullptr, bzip2_build_index, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2ReadRanges", nullptr, bzip2_read_ranges, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncWrite", nullptr, enc_write, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncFinish", nullptr, enc_finish, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -164,6 +164,68 @@ int cjs_bzip2_recover(const uint8_t *in, size_t n, int as_stream, uint8_t **out,
                       cjs_bz_found *found, long cap, long *n_found, const cjs_opts *opts);
 int cjs_bzip2_recover_device(const uint8_t *d_in, size_t n, int as_stream, uint8_t *d_out, size_t out_cap, size_t *out_n,
                              cjs_bz_found *found, long cap, long *n_found, const cjs_opts *opts);
+/* Indexed range reads: bytes [off, off + len) of what cjs_bzip2_decompress would return, decoding only the blocks they touch.
+ * A cjs_bz_index holds one entry per block of a stream, in stream order, with the stream's size in bytes and the multistream
+ * flag it was made with.  Decoded offsets are the prefix sums of `size`; their total is total_bytes.  Host logic only, except
+ * _build, which is one table pass (cjs_bzip2_table's: the same verdicts, codes and details on the same bytes, opts->n_devices
+ * honoured as there) that also hands out every block's end bit, stored CRC and the level of its member stream.
+ * _create takes a caller's entries (another tool's, or cjs_bzip2_table's plus the caller's own knowledge); _save gives the
+ * serialised form (*bytes: malloc'd, cjs_free), _load reads it:
+ *   32-byte header: the 8 bytes "CJSBZIX1", u32 version = 1, u32 flags (bit 0 = multistream), u64 stream_bytes, u64 count;
+ *   then `count` entries of 32 bytes, the struct below; everything little-endian.
+ * _create and _load refuse with CJS_E_INVALID_ARG and a detail text, before any device is touched: wrong magic, version or
+ * length; bitpos < 32; bitpos[k] < end_bit[k-1]; end_bit <= bitpos + 48 + 32; end_bit > 8 * stream_bytes; level outside 1..9;
+ * size > 52 * 100000 * level; reserved != 0; undefined flag bits.  NULL arguments: CJS_E_INVALID_ARG.
+ * _info: any out pointer may be NULL.  _entries copies the first min(cap, blocks) entries and returns the number of blocks.
+ * An index is immutable once made: any number of threads may read ranges through one index. */
+typedef struct cjs_bz_index_entry {   /* 32 bytes, also the serialised entry (little-endian) */
+  uint64_t bitpos;    /* where the block's 48-bit magic starts */
+  uint64_t end_bit;   /* first bit behind its end-of-block code */
+  uint32_t size;      /* decoded bytes */
+  uint32_t crc;       /* stored block CRC */
+  uint32_t level;     /* 1..9: level of the member stream the block belongs to */
+  uint32_t reserved;  /* 0 */
+} cjs_bz_index_entry;
+typedef struct cjs_bz_index cjs_bz_index;
+int cjs_bzip2_index_build(const uint8_t *in, size_t n, int multistream, cjs_bz_index **idx, const cjs_opts *opts);
+int cjs_bzip2_index_create(const cjs_bz_index_entry *entries, size_t count, uint64_t stream_bytes, int multistream, cjs_bz_index **idx);
+int cjs_bzip2_index_save(const cjs_bz_index *idx, uint8_t **bytes, size_t *nbytes);
+int cjs_bzip2_index_load(const uint8_t *bytes, size_t nbytes, cjs_bz_index **idx);
+int cjs_bzip2_index_info(const cjs_bz_index *idx, uint64_t *blocks, uint64_t *total_bytes, uint64_t *stream_bytes, int *multistream);
+long cjs_bzip2_index_entries(const cjs_bz_index *idx, cjs_bz_index_entry *entries, long cap);
+void cjs_bzip2_index_destroy(cjs_bz_index *idx);
+/* cjs_bzip2_read_ranges: `count` ranges of the address space [0, total_bytes) = the output of cjs_bzip2_decompress(in, n,
+ * the index's multistream flag).  Range k is [off[k], off[k] + len[k]) clipped to total_bytes, like pread: out_len[k] is what is
+ * delivered; a range that starts at or past the end, or has len[k] == 0, has out_len 0 and status 0.  Ranges may overlap, repeat
+ * and come in any order.  The results are packed back to back in range order: out_off[k] = the sum of the out_len in front.
+ * The TOUCHED blocks are those of non-zero size that overlap a clipped range.  Each is decoded once, however many ranges want it,
+ * and nothing else of the stream is read: not the other blocks' bytes, not a stream header, not a stream CRC; there is no magic
+ * scan.  What is uploaded (host form: staged in one pinned buffer, one copy per pass; device form: gathered on the device by one
+ * launch per pass) is the byte runs [bitpos >> 3, (end_bit + 7) >> 3) of the touched blocks, neighbours merged.  A touched block
+ * is GOOD only if the block magic stands at its bitpos, it decodes under its entry's level, ends at the entry's end_bit, decodes
+ * to the entry's size, and the CRC of its bytes equals the stored one, which equals the entry's.  A range that touches a bad block
+ * gets status[k] = CJS_E_DATA_ERROR and out_len[k] = 0; other ranges are unaffected, and the call returns 0.
+ * cjs_last_error_detail() is then the detail of the lowest-index failing range's first bad block: "Bad block CRC (got .. expected
+ * ..)" when everything but the computed CRC agrees, otherwise "index does not match the stream at block <k>".
+ * The touched blocks go through the decoder in ascending passes bounded by the batch decoder's group size (CJS_DEC_GROUP_BYTES of
+ * upload), the inverse-BWT batch and the row budget of the block decode: device memory depends on a pass, never on the stream.
+ * CJS_RANGE_PASS_BLOCKS (read at every call; for tests) caps the touched blocks of a pass.  A slice-gather kernel copies every
+ * piece of every range from a pass's expanded blocks to its place, one launch per slab of pieces.
+ * Host form: *out is allocated by the library (the rules of cjs_bzip2_decompress; cjs_free), the layout is made after the
+ * verdicts (a failed range takes no room).  Device form (the memory rules of cjs_bzip2_decompress_device for d_in / d_out): the
+ * layout comes from the index alone, so a failed range keeps its region, which holds unspecified bytes; a layout above out_cap:
+ * CJS_E_OUTPUT_TOO_SMALL with *out_need set, before any launch (out_cap = 0, d_out = NULL: the size query); no byte of d_out at
+ * or past min(out_cap, *out_need) is ever written.  On success *out_need = the end of the last region.
+ * Negative returns are failures of the call: CJS_E_INVALID_ARG before the device is touched for NULL idx, NULL arrays with
+ * count > 0 (out / out_need always), NULL in with n > 0, n != the index's stream_bytes and off[k] + len[k] overflowing; before any
+ * launch for memory that is not the GPU's; CJS_E_NO_DEVICE, CJS_E_HIP, CJS_E_OUT_OF_MEMORY.  count == 0, or no touched block:
+ * success without touching the device (host form: *out is a buffer all the same).  opts->device is honoured, n_devices and stats
+ * are ignored.  CJS_DEBUG: one "[cjs range]" line per call on stderr (blocks, passes, H2D and D2H bytes). */
+int cjs_bzip2_read_ranges(const uint8_t *in, size_t n, const cjs_bz_index *idx, const uint64_t *off, const uint64_t *len, size_t count,
+                          uint8_t **out, size_t *out_off, size_t *out_len, int32_t *status, const cjs_opts *opts);
+int cjs_bzip2_read_ranges_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint64_t *off, const uint64_t *len,
+                                 size_t count, uint8_t *d_out, size_t out_cap, size_t *out_off, size_t *out_len, int32_t *status,
+                                 size_t *out_need, const cjs_opts *opts);
 /* Streaming form of cjs_bzip2_compress: the input is written in pieces of any size (zero included), the .bz2 stream is read in
  * pieces of any size, and the bytes read, in order, once cjs_bzip2_enc_finish has returned, are exactly what
  * cjs_bzip2_compress(all written bytes, level) returns -- for every level, every split of the input, every chunk_bytes and every
