@@ -1,6 +1,6 @@
 // batch_dec.hip -- the device side of Bzip2.decompressFiles (cjs_bzip2_decompress_batch): the batch magic scan and the batch
 // form of block decode's per-candidate kernels (bz_stage2.h).  Kept out of decode.hip's module so that the single-stream
-// kernels there compile exactly as they do without a batch form beside them.  The host driver is in decode.hip.
+// kernels there compile exactly as they do without a batch form beside them.  The host driver is in dec_batch.hip.
 #include "decode_dev.h"
 #include <algorithm>
 

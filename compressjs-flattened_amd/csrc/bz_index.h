@@ -1,5 +1,5 @@
 // bz_index.h -- the block index of a .bz2 stream behind the C ABI's opaque cjs_bz_index (bz_index.hip: create / save / load / info;
-// decode.hip: cjs_bzip2_index_build and the range reads that run over it).
+// range.hip: cjs_bzip2_index_build and the range reads that run over it).
 #pragma once
 #include "cjs_internal.h"
 #include <vector>

@@ -1,4 +1,4 @@
-// dec_device.hip -- the kernels of the device-resident Bzip2 decode (cjs_bzip2_decompress_device, decode.hip): what the host path
+// dec_device.hip -- the kernels of the device-resident Bzip2 decode (cjs_bzip2_decompress_device, dec_batch.hip): what the host path
 // reads of its host copy of the input, read on the device.  Only metadata crosses PCIe:
 //   dd_headers     the first 4 bytes of every input (_start_bunzip's magic and level)
 //   dd_level_scan  bz_max_level of a multistream input: every byte-aligned "BZh<d>" from input byte 4 on whose 10 bytes lie inside

@@ -1,4 +1,6 @@
-// decode.hip — Bzip2.decompressFile (Bunzip.decode, J/Bzip2_joined_.js:1769-1796) on the MI355X.
+// decode.hip — Bzip2.decompressFile (Bunzip.decode, J/Bzip2_joined_.js:1769-1796) on the MI355X: the decode kernels, the engine
+// that runs them in three phases (dec_engine.h) and the single-stream driver.  The other drivers of the engine have files of
+// their own: dec_batch.hip (host batch, device-resident single and batch), dec_recover.hip, range.hip, dec_stream.hip.
 //
 // The reference decodes block after block from one bit cursor.  Blocks carry no length field, so here:
 //   1. bz_magic_scan     every bit offset of the stream is tested against the 48-bit block / end-of-stream
@@ -17,26 +19,16 @@
 //                        stretch of equal bytes the literal/count phase has period 5 and the only carried
 //                        state (does the stretch start with a count byte?) is a 2-state function scan;
 //   6. CRC check         per block over the output bytes (rle1.hip's slice + GF(2) combine), :1756-1761.
-// Recovery of damaged data (cjs_bzip2_recover, no reference equivalent: the job of bzip2recover) is 1, 2 and 4-6 over EVERY
-// decodable candidate, with step 3 replaced by a selection of the intact, non-overlapping ones; its repaired-stream form gathers
-// their bit strings into a new stream (bz_bits_gather).
-#include "cjs_internal.h"
-#include "bz_index.h"
-#include "host.h"
+// Recovery of damaged data (dec_recover.hip: cjs_bzip2_recover, no reference equivalent: the job of bzip2recover) is 1, 2 and 4-6
+// over EVERY decodable candidate, with step 3 replaced by a selection of the intact, non-overlapping ones; an indexed range read
+// (range.hip) is 2 and 4-6 over the blocks its index names.
+#include "dec_engine.h"
 #include "prims.hpp"
 #include "rle1.h"
-#include <algorithm>
-#include <chrono>
-#include <functional>
-#include <memory>
 #include <stdlib.h>
 #include <string.h>
-#include <string>
-#include <vector>
 
 using namespace cjs;
-
-#include "decode_dev.h"
 
 namespace cjs {
 
@@ -191,18 +183,7 @@ __global__ __launch_bounds__(256) void bz_rows_pack(const uint8_t* __restrict__ 
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) dst[i] = src[i];
 }
 
-// ---------------------------------------------------------------- 4. inverse BWT
-struct IbBlock {            // per valid block, in stream order
-  uint64_t tt;              // device address of the block's decoded BWT bytes
-  uint32_t count;           // n
-  uint32_t orig;
-  uint32_t off;             // element offset of the block in the concatenated sort / LF arrays
-  uint32_t woff;            // byte offset of the block in the walk's output (w)
-  uint64_t out_off;         // byte offset of the block in the final output
-  uint32_t out_len;
-  uint32_t crc;
-};
-
+// ---------------------------------------------------------------- 4. inverse BWT (IbBlock, a block of a batch: dec_engine.h)
 // keys (block << 8 | byte), vals = i
 __global__ __launch_bounds__(256) void ib_make_keys(const IbBlock* __restrict__ blocks, uint32_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t stride) {
   const IbBlock b = blocks[blockIdx.y];
@@ -856,138 +837,17 @@ int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint3
 //   C  per share   RLE1 expansion + block CRCs per batch, D2H straight to the final offsets
 // No data moves between devices; the exchanged quantities are (end bit, count, crc) per candidate and a length per block.
 //
-// Five drivers sit on the phases: bunzip_core (single stream, shares over devices), dev_single_* (device-resident single stream),
-// dec_batch_group (host batch), dev_group_* (device-resident batch) and dec_step (streaming).  The glue between the phases is
-// written once: bz_header_check (_start_bunzip), WalkCands + walk_chain (candidate lookup, bz_walk, chain append),
-// chain_out_offsets (the prefix sum), group_layout / group_prepare / group_verdicts (a batch group, both forms), ShareScratch
-// (a phase's own scratch).  A driver holds what is particular to it: where the bytes come from and where they go.
-namespace {
+// Eight drivers sit on the phases, through dec_engine.h (the arena, the share, the job, the walk and the glue between the phases):
+//   here             bunzip_core (single stream, shares over devices; cjs_bzip2_decompress, _decompress_block, _table, and the
+//                    table pass of cjs_bzip2_index_build)
+//   dec_batch.hip    dec_batch_group (host batch), dev_single_* (device-resident single stream), dev_group_* (device-resident batch)
+//   dec_recover.hip  recover_core (recovery, both forms)
+//   range.hip        range_run (indexed range reads, both forms)
+//   dec_stream.hip   dec_step (streaming)
+// A driver holds what is particular to it: where the bytes come from and where they go.
+namespace cjs {
 
 constexpr uint64_t DEC_BATCH_ELEMS = 1ull << 28;      // BWT bytes per inverse-BWT batch (scratch ~ 21 B each)
-constexpr uint32_t DEC_BATCH_BLOCKS = 65535;          // grid.y of the per-block kernels
-
-// Device scratch of one streaming decoder (cjs_bzip2_dec_*): ONE allocation made at the decoder's first step, handed out first fit
-// in 256-byte units and taken back piece by piece, so what a decoder holds between its steps never changes.  A request that does
-// not fit (the size is an estimate) becomes a hipMalloc of its own, freed when it is given back.
-struct DecArena {
-  DevMem<uint8_t> base; size_t cap = 0;
-  std::vector<std::pair<size_t, size_t>> free_;      // (offset, bytes), ascending, coalesced
-  std::vector<std::pair<void*, size_t>> used;        // bytes == 0: a hipMalloc of its own
-  uint32_t spills = 0;
-  int init(size_t bytes) { CJS_TRY(base.alloc(bytes)); cap = bytes; free_.assign(1, {0, bytes}); return 0; }
-  void* take(size_t bytes) {
-    bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    for (size_t i = 0; i < free_.size(); i++) if (free_[i].second >= bytes) {
-      void* p = base.p + free_[i].first;
-      if (free_[i].second == bytes) free_.erase(free_.begin() + (long)i); else { free_[i].first += bytes; free_[i].second -= bytes; }
-      used.push_back({p, bytes});
-      return p;
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    spills++;
-    used.push_back({p, 0});
-    return p;
-  }
-  void give(void* p) {
-    size_t i = 0;
-    while (i < used.size() && used[i].first != p) i++;
-    if (i == used.size()) return;
-    const size_t bytes = used[i].second, off = bytes ? (size_t)((uint8_t*)p - base.p) : 0;
-    used.erase(used.begin() + (long)i);
-    if (!bytes) { (void)hipFree(p); return; }
-    size_t k = 0;
-    while (k < free_.size() && free_[k].first < off) k++;
-    free_.insert(free_.begin() + (long)k, {off, bytes});
-    if (k + 1 < free_.size() && free_[k].first + free_[k].second == free_[k + 1].first) { free_[k].second += free_[k + 1].second; free_.erase(free_.begin() + (long)k + 1); }
-    if (k > 0 && free_[k - 1].first + free_[k - 1].second == free_[k].first) { free_[k - 1].second += free_[k].second; free_.erase(free_.begin() + (long)k); }
-  }
-  void release() { for (auto& u : used) if (!u.second) (void)hipFree(u.first); used.clear(); free_.clear(); base.reset(); cap = 0; }
-  ~DecArena() { release(); }
-};
-
-struct DecShare {
-  int device = 0, rc = 0;
-  Stream s;
-  std::vector<DevBuf> bufs;          // device scratch of the share, given back at release() (or early, by drop())
-  // a streaming decoder's step: scratch from the decoder's own arena instead of the pool, and rows only for the first row_limit
-  // block candidates at or after bit row_from.  Candidates in front of row_from are dropped, as is everything from the first
-  // block candidate past the limit on: cut_bit is that candidate's bit (none: ~0).
-  DecArena* arena = nullptr; std::vector<void*> abufs;
-  uint32_t row_limit = ~0u; uint64_t row_from = 0, cut_bit = ~0ull;
-  uint32_t ncand_seen = 0;            // candidates the magic scan found (before the row limit dropped any)
-  uint64_t lo = 0, hi = 0;            // candidates starting in bytes [lo, hi) are this share's
-  uint64_t up_lo = 0, up_hi = 0;      // uploaded byte range
-  const uint8_t* d_in = nullptr;      // addressed by absolute byte: d_in[b] is valid for up_lo <= b < up_hi
-  std::vector<Cand> cands;            // sorted by bit
-  std::vector<BlockOut> bos;
-  uint8_t* d_tt = nullptr;            // decoded BWT bytes of a one-batch share, tt_stride per row (several batches: packed segments)
-  std::vector<uint64_t> tt_ptr;       // per candidate: device address of its decoded bytes
-  // chain part
-  size_t c0 = 0, c1 = 0;              // chain blocks [c0, c1) were decoded here
-  uint8_t* d_w = nullptr;             // pre-RLE1 bytes of those blocks, contiguous in chain order
-  RleCarry* d_carry = nullptr; uint32_t carry_tiles = 0;      // per chain block and UR_TILE-byte tile: the RLE1 expansion state at the tile start
-  std::vector<uint64_t> ebase;        // element offset of block c0+i inside d_w (size c1-c0+1)
-  double ms_a = 0, ms_b = 0, ms_c = 0;
-  uint64_t h2d = 0, d2h = 0;          // bytes of the share's host <-> device copies
-  char detail[96] = {0};            // error detail found by this share's worker thread (the detail text is per calling thread)
-  // batch (cjs_bzip2_decompress_batch): input k is bytes [bst[k], ben[k]) of the upload, its blocks at most bdsz[k] bytes
-  std::vector<uint32_t> bst, ben, bdsz;
-  uint32_t a_batches = 0, b_batches = 0;      // row batches of phase A, inverse-BWT batches of phase B
-  int take(void** p, size_t bytes) {
-    if (arena) { if (!(*p = arena->take(bytes))) return (int)CJS_E_OUT_OF_MEMORY; abufs.push_back(*p); return 0; }
-    DevBuf b(bytes); if (!(*p = b.p)) return (int)CJS_E_OUT_OF_MEMORY; bufs.push_back(std::move(b)); return 0;
-  }
-  void drop(void* p) {
-    if (arena) { for (size_t i = 0; i < abufs.size(); i++) if (abufs[i] == p) { abufs.erase(abufs.begin() + (long)i); arena->give(p); return; } return; }
-    for (size_t i = 0; i < bufs.size(); i++) if (bufs[i].p == p) { bufs.erase(bufs.begin() + (long)i); return; }
-  }
-  void release() {                    // on the share's device, once its stream has drained; again: nothing
-    if (hipSetDevice(device) != hipSuccess) return;
-    if (s) (void)hipStreamSynchronize(s);
-    if (arena) for (void* p : abufs) arena->give(p);
-    abufs.clear();
-    bufs.clear();
-    s.reset();
-  }
-  void release_keep_stream(Stream& to) { Stream keep = std::move(s); if (keep && hipSetDevice(device) == hipSuccess) (void)hipStreamSynchronize(keep); release(); to = std::move(keep); }
-  uint32_t nrows_given() const { uint32_t r = 0; for (auto& c : cands) r += c.kind == 0; return r; }
-  ~DecShare() { release(); }
-};
-
-// Scratch a phase takes from its share for its own duration.  done() gives all of it back, and is called only where the share's
-// stream has been synchronised behind the last kernel that used it (another thread may get the memory at once).  On an error exit
-// nothing goes back: the buffers stay with the share until DecShare::release(), which synchronises first.  So no destructor.
-struct ShareScratch {
-  DecShare* S; std::vector<void*> got;
-  explicit ShareScratch(DecShare* s) : S(s) {}
-  int take(void** p, size_t bytes) { const int rc = S->take(p, bytes); if (!rc) got.push_back(*p); return rc; }
-  void drop(void* p) { got.erase(std::find(got.begin(), got.end(), p)); S->drop(p); }      // one buffer, early
-  void done() { for (void* p : got) S->drop(p); got.clear(); }
-};
-
-struct DecJob {
-  const uint8_t* in = nullptr; size_t n = 0;
-  uint32_t tt_stride = 0;             // = dbuf size of the largest level in the input
-  int mode = 0;
-  std::vector<IbBlock> chain;         // all valid blocks in stream order (cand = index local to the decoding share)
-  std::vector<uint64_t> chain_bits;
-  std::vector<uint64_t> out_off;      // size chain.size()+1
-  uint8_t* host = nullptr;            // final output (mode 0 / 2)
-  bool timing = false;
-  bool batch = false;                 // phase C: a CRC verdict for every block (crc_got) instead of stopping at the first bad one
-  std::vector<uint32_t> crc_got;
-  // device-resident source and sink (cjs_bzip2_decompress_device[_batch]).  upload: fills the share's scratch [0, up_hi - up_lo)
-  // on its stream in place of phase A's H2D of `in`; eos: called once phase A's candidates are sorted (a batch candidate's pad
-  // still names its input); dev_out: phase C expands straight into dev_out at the final offsets instead of scratch + D2H
-  std::function<int(DecShare* S, uint8_t* dst)> upload;
-  std::function<int(DecShare* S)> eos;
-  uint8_t* dev_out = nullptr;
-  // range reads: the share comes with its candidates (S->cands, sorted, kind 0) and phase A launches no magic scan.  vet, if
-  // set, is called once the upload is enqueued and may erase candidates (those whose magic is not there)
-  bool given = false;
-  std::function<int(DecShare* S)> vet;
-};
 
 double ms_since(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); }
 
@@ -1334,15 +1194,6 @@ void dec_phase_c(DecJob* J, DecShare* S) {
   S->ms_c = ms_since(T0);
 }
 
-template <typename F>
-int for_each_share(std::vector<DecShare>& sh, DecJob* J, F fn) {
-  // an exception of a phase becomes the share's return code
-  if (sh.size() == 1) guarded(sh[0].rc, [&] { fn(J, &sh[0]); });
-  else { Workers workers; for (auto& x : sh) workers.run(x.rc, [fn, J, &x] { fn(J, &x); }); }      // (joined here)
-  for (auto& x : sh) if (x.rc) { if (x.detail[0]) set_detail("%s", x.detail); return x.rc; }
-  return 0;
-}
-
 // _start_bunzip (:1408-1427) on the first four bytes h of an input (or of a member stream) of n bytes: 0 and the level, or
 // CJS_E_NOT_BZIP_DATA and the detail text in *why (the caller sets it, or stores it with its input)
 int bz_header_check(const uint8_t* h, size_t n, int* level, const char** why) {
@@ -1351,9 +1202,6 @@ int bz_header_check(const uint8_t* h, size_t n, int* level, const char** why) {
   if (*level < 1 || *level > 9) { *why = "level out of range"; return CJS_E_NOT_BZIP_DATA; }
   return 0;
 }
-
-// bytes a block can span: 20 bits per symbol + tables (the overlap of two shares; a streaming decoder's window behind a chunk)
-constexpr uint64_t dec_extent(uint32_t tt_stride) { return (uint64_t)tt_stride * 5 / 2 + 65536; }
 
 // The scratch rows are sized for the largest level any member stream can have: a multistream file may change level
 // between members (:1787-1792), so every byte-aligned "BZh<d>" followed by a block or end-of-stream magic counts.
@@ -1378,116 +1226,6 @@ int bz_block_verdict(const BlockOut& bo, uint32_t dbuf_size, uint64_t bitpos, bo
   return 0;
 }
 
-// The chain walk of one input (Bunzip.decode :1776-1794): 32 -> end(block 0) -> end(block 1) ... over the candidates, stream CRC
-// fold, multistream restarts (each member keeps its own level, :1787-1792).  in / n: the input's own bytes, whose header
-// _start_bunzip has passed; positions are bits of the input.  `in` is anything indexable by byte: the host bytes, or (device
-// source) an accessor over the few bytes the walk reads -- the header, and at an end-of-stream candidate the stored stream CRC and
-// the restart header behind it.  at(pos, &kind, &bo) finds the candidate whose magic starts at bit
-// pos (false: none) with its decode result, end_bit in bits of the input; take(bo, pos) appends a good block to the chain.
-// Returns 0 or the first error the walk meets, its detail set.  mode 1 (Bunzip.table) does not test the stream CRC.
-//
-// `st` (a streaming decoder's step; nullptr: a walk of the whole input from its header on) holds the state the walk starts from
-// and is left with the state it stopped in.  With st->partial the n bytes are only the stream so far, and the walk stops
-// (st->stop != WALK_RUNS, return 0) in front of anything whose verdict the bytes still to come could change; with a row limit
-// (st->cut_bit) it stops at the first candidate that was not decoded.  The state is that of the point where the walk stands:
-// a later call with more bytes goes on from it.  take() sees *st as it was in front of the block it is given.
-enum { WALK_RUNS = 0, WALK_ENDED, WALK_NEED_MAGIC, WALK_NEED_CRC, WALK_NEED_HEADER, WALK_NO_ROW, WALK_BLOCK_OPEN, WALK_ERR_NEAR_END, WALK_OUT_BUDGET };
-struct WalkState {
-  uint64_t pos = 32; uint32_t crc = 0, dbuf_size = 0;            // dbuf_size 0: from the input's header byte
-  bool partial = false;
-  uint64_t cut_bit = ~0ull, extent = 0;                          // extent: bytes a block can span (partial)
-  int stop = WALK_RUNS;
-};
-template <typename Bytes, typename At, typename Take>
-int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_stride, bool timing, At at, Take take, WalkState* st = nullptr) {
-  auto read_bits = [&](uint64_t bit, int k) -> uint64_t { uint64_t v = 0; for (int i = 0; i < k; i++) { const uint64_t b = bit + i; v = (v << 1) | ((b >> 3) < n ? (in[b >> 3] >> (7 - (b & 7))) & 1u : 0u); } return v; };
-  WalkState whole;
-  if (!st) st = &whole;
-  const bool partial = st->partial;
-  uint32_t& dbuf_size = st->dbuf_size;                            // of the member stream being walked
-  if (!dbuf_size) dbuf_size = 100000u * (uint32_t)(in[3] - '0');
-  uint64_t& pos = st->pos; uint32_t& stream_crc = st->crc;
-  auto stop = [&](int why) { st->stop = why; return 0; };
-  for (;;) {
-    if (partial ? pos + 48 > (uint64_t)n * 8 : (pos + 7) / 8 >= n) return stop(partial ? WALK_NEED_MAGIC : WALK_ENDED);      // inputStream.eof() (:1777)
-    if (pos >= st->cut_bit) return stop(WALK_NO_ROW);
-    uint32_t kind = 0; BlockOut bo;
-    if (!at(pos, &kind, &bo)) return CJS_E_NOT_BZIP_DATA;        // h !== WHOLEPI (:1438)
-    if (kind == 0) {
-      const int rc = bz_block_verdict(bo, dbuf_size, pos, timing);
-      // (partial) an error found less than a block's extent before the end may come from the zeros read past it; a good block
-      // read nothing behind its end-of-block code, unless that was cut off (end_bit is clamped to the end)
-      if (partial && rc && (pos >> 3) + st->extent > n) { clear_detail(); return stop(WALK_ERR_NEAR_END); }
-      if (rc) return rc;
-      if (partial && bo.end_bit >= (uint64_t)n * 8) return stop(WALK_BLOCK_OPEN);
-      take(bo, pos);
-      stream_crc = bo.crc ^ ((stream_crc << 1) | (stream_crc >> 31));
-      pos = bo.end_bit;
-    } else {
-      if (partial && (pos + 80 > (uint64_t)n * 8 || (multistream && (pos + 80 + 7) / 8 + 4 > n))) return stop(pos + 80 > (uint64_t)n * 8 ? WALK_NEED_CRC : WALK_NEED_HEADER);
-      const uint32_t target = (uint32_t)read_bits(pos + 48, 32);
-      pos += 80;
-      if ((pos + 7) / 8 > n) pos = (uint64_t)n * 8;
-      if (timing) fprintf(stderr, "[cjs dec] end of stream at bit %llu: stream crc %08x stored %08x\n", (unsigned long long)pos - 80, stream_crc, target);
-      if (mode == 0 && target != stream_crc) {                   // Bunzip.table ignores the stream crc (:1852)
-        set_detail("Bad stream CRC (got %x expected %x)", stream_crc, target);
-        return CJS_E_DATA_ERROR;
-      }
-      const uint64_t byte = (pos + 7) / 8;
-      if (!multistream || byte >= n) return stop(WALK_ENDED);
-      // _start_bunzip again, byte aligned (:1787-1792)
-      uint8_t h[4] = {0, 0, 0, 0};
-      for (uint64_t i = 0; i < 4 && byte + i < n; i++) h[i] = in[byte + i];
-      int lv = 0; const char* why = nullptr;
-      if (bz_header_check(h, (size_t)(n - byte), &lv, &why)) { set_detail("%s", why); return CJS_E_NOT_BZIP_DATA; }
-      dbuf_size = 100000u * (uint32_t)lv;
-      if (dbuf_size > tt_stride) return CJS_E_UNSUPPORTED;      // cannot happen: the pre-scan saw this header
-      pos = (byte + 4) * 8; stream_crc = 0;
-    }
-  }
-}
-
-// The candidates a walk runs over: the sorted bits of one share's candidates, or of all the shares of a single-stream call in
-// share order (their byte ranges ascend), each with its share and its index there.  base: the bit of the upload at which the
-// input being walked starts (a batch group: 8 x bst[i]), so that find() takes the walk's own positions.
-struct WalkCands {
-  const DecShare* sh;
-  std::vector<uint64_t> bit; std::vector<uint32_t> share, local;
-  uint64_t base = 0;
-  WalkCands(const DecShare* shares, size_t nsh) : sh(shares) {
-    for (size_t i = 0; i < nsh; i++)
-      for (size_t k = 0; k < sh[i].cands.size(); k++) { bit.push_back(sh[i].cands[k].bit); share.push_back((uint32_t)i); local.push_back((uint32_t)k); }
-  }
-  long find(uint64_t pos) const {
-    const auto it = std::lower_bound(bit.begin(), bit.end(), base + pos);
-    return (it != bit.end() && *it == base + pos) ? (long)(it - bit.begin()) : -1;
-  }
-  uint32_t kind(long ci) const { return sh[share[(size_t)ci]].cands[local[(size_t)ci]].kind; }
-  const BlockOut& bo(long ci) const { return sh[share[(size_t)ci]].bos[local[(size_t)ci]]; }
-  IbBlock chain_block(long ci) const {
-    const BlockOut& b = bo(ci);
-    IbBlock ib; ib.tt = sh[share[(size_t)ci]].tt_ptr[local[(size_t)ci]]; ib.count = b.count; ib.orig = b.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = b.crc;
-    return ib;
-  }
-};
-
-// bz_walk over C, the good blocks appended to J.chain.  met(ci, pos) is called for every candidate the walk accepts: an
-// end-of-stream candidate when the walk finds it, before it reads the record behind the magic; a block once it is on the chain
-// (a resumed walk's *st is then still the state in front of the block).
-template <typename Bytes, typename Met>
-int walk_chain(DecJob& J, const WalkCands& C, const Bytes& in, size_t n, int multistream, int mode, Met met, WalkState* st = nullptr) {
-  long last = -1;
-  return bz_walk(in, n, multistream, mode, J.tt_stride, J.timing,
-                 [&](uint64_t pos, uint32_t* kind, BlockOut* bo) {
-                   if ((last = C.find(pos)) < 0) return false;
-                   *kind = C.kind(last); *bo = C.bo(last); bo->end_bit -= C.base;
-                   if (*kind) met(last, pos);
-                   return true;
-                 },
-                 [&](const BlockOut&, uint64_t pos) { J.chain.push_back(C.chain_block(last)); met(last, pos); }, st);
-}
-inline void met_nothing(long, uint64_t) {}
-
 // exclusive prefix sum of the chain's decoded lengths (phase B's) -> J.out_off; returns the total
 uint64_t chain_out_offsets(DecJob& J) {
   const size_t nb = J.chain.size();
@@ -1496,11 +1234,10 @@ uint64_t chain_out_offsets(DecJob& J) {
   return J.out_off[nb];
 }
 
-}  // namespace
-
-static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, uint64_t at_bit, uint8_t** out, size_t* out_n,
-                       uint64_t* tab_pos, uint32_t* tab_size, long tab_cap, long* tab_n, const cjs_opts* opts,
-                       std::vector<cjs_bz_index_entry>* tab_ix = nullptr) {      // (mode 1: an index entry per block as well)
+// ---------------------------------------------------------------- the single-stream driver
+int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, uint64_t at_bit, uint8_t** out, size_t* out_n,
+                uint64_t* tab_pos, uint32_t* tab_size, long tab_cap, long* tab_n, const cjs_opts* opts,
+                std::vector<cjs_bz_index_entry>* tab_ix) {      // (mode 1: an index entry per block as well)
   if (out) *out = nullptr;
   if (out_n) *out_n = 0;
   if (tab_n) *tab_n = 0;
@@ -1522,6 +1259,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   if ((size_t)nsh * 65536 > n) nsh = (uint32_t)(n / 65536 ? n / 65536 : 1);     // tiny inputs: one share
   const uint64_t overlap = dec_extent(J.tt_stride);
   RestoreDevice restore{dev0};                                                  // after the shares have been released
+  HostBuf host;                                                                 // (in front of the shares: given back once their streams have drained)
   std::vector<DecShare> sh(nsh);
   for (uint32_t i = 0; i < nsh; i++) {
     DecShare& S = sh[i];
@@ -1580,7 +1318,7 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
   if (rc) return rc;
   const double ms_b = ms_since(T1);
   const uint64_t total = chain_out_offsets(J);
-  if (out && !pending_rc) { J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1); if (!J.host) return CJS_E_OUT_OF_MEMORY; }
+  if (out && !pending_rc) { host = HostBuf(total ? (size_t)total : 1); if (!(J.host = host.p)) return CJS_E_OUT_OF_MEMORY; }
   const auto T2 = std::chrono::steady_clock::now();
   rc = for_each_share(sh, &J, dec_phase_c);
   const double ms_c = ms_since(T2);
@@ -1590,16 +1328,18 @@ static int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, u
     for (uint32_t i = 0; i < nsh; i++) fprintf(stderr, "[cjs dec]   share %u (device %d): %zu candidates, blocks [%zu, %zu): %.2f / %.2f / %.2f ms\n", i, sh[i].device,
                                                sh[i].cands.size(), sh[i].c0, sh[i].c1, sh[i].ms_a, sh[i].ms_b, sh[i].ms_c);
   }
-  if (rc) { HostPool::give(J.host); return rc; }
+  if (rc) return rc;
   if (pending_rc) { set_detail("%s", pending_detail); return pending_rc; }
   if (tab_n) {
     *tab_n = (long)nb;
     for (size_t k = 0; k < nb && (long)k < tab_cap; k++) { tab_pos[k] = J.chain_bits[k]; tab_size[k] = J.chain[k].out_len; }
     if (tab_ix) for (size_t k = 0; k < nb; k++) (*tab_ix)[k].size = J.chain[k].out_len;
   }
-  if (out) { *out = J.host; *out_n = (size_t)total; }
+  if (out) { *out = host.release(); *out_n = (size_t)total; }
   return 0;
 }
+
+}  // namespace cjs
 
 extern "C" int cjs_bzip2_decompress(const uint8_t* in, size_t n, int multistream, uint8_t** out, size_t* out_n, const cjs_opts* opts) {
   if (!out || !out_n) return CJS_E_INVALID_ARG;
@@ -1620,1372 +1360,3 @@ extern "C" long cjs_bzip2_table(const uint8_t* in, size_t n, int multistream, ui
   return rc ? (long)rc : nbk;
   CJS_GUARD_END((long)CJS_E_OUT_OF_MEMORY, (long)CJS_E_HIP)
 }
-
-// ---------------------------------------------------------------- batch group (host form: dec_batch_group, device form: dev_group_*)
-// Inputs go in groups of up to BATCH_DEC_GROUP_BYTES, each group one upload with every input at a 4-byte-aligned offset and one
-// share of phases A-C: one magic scan over the group (a candidate never straddles two inputs), block decode of all candidates
-// with every read bounded by the candidate's own input, then the walk of each input over the candidates of its bytes, phase B
-// over all chain blocks, phase C with a CRC verdict per block.  An input larger than a group goes through the single-stream
-// path.  What the two forms share is here; where the bytes come from and where they go is theirs.  See DESIGN.md §6c.
-namespace {
-
-constexpr size_t BATCH_DEC_GROUP_BYTES = (size_t)256 << 20;
-
-size_t dec_group_bytes() {
-  static const size_t g = getenv("CJS_DEC_GROUP_BYTES") ? (size_t)strtoull(getenv("CJS_DEC_GROUP_BYTES"), nullptr, 10) : BATCH_DEC_GROUP_BYTES;   // (tests shrink it)
-  return g && g <= ((size_t)1 << 30) ? g : BATCH_DEC_GROUP_BYTES;      // (group offsets are 32-bit)
-}
-
-// the group that starts at input k0 (n[k0] <= G): inputs [k0, k1) whose 4-byte-aligned sizes come to G at most
-size_t dec_group_end(const size_t* n, size_t count, size_t k0, size_t G) {
-  size_t k1 = k0, bytes = 0;
-  while (k1 < count && n[k1] <= G && (k1 == k0 || bytes + n[k1] <= G)) bytes += (n[k1++] + 3) & ~(size_t)3;
-  return k1;
-}
-
-struct BatchGroup {
-  size_t k0 = 0, k1 = 0;              // inputs [k0, k1) of the call
-  std::vector<uint8_t> ok;            // input k0 + i passed _start_bunzip
-  std::vector<size_t> ch0, ch1;       // input k0 + i's chain blocks
-};
-
-// The layout of a group: _start_bunzip (:1408-1427) of every input, the accepted ones at 4-byte-aligned offsets of one upload
-// (S.bst / S.ben), each with the block size of its own single call (S.bdsz: the kernels' limits for its blocks), the rows sized
-// for the largest of them.  hdr(k): the first bytes of input k; level(k, lv): its largest member level, lv being its header's;
-// placed(k, at): input k lies at byte `at` of the upload.
-template <typename Hdr, typename Level, typename Placed>
-void group_layout(DecJob& J, DecShare& S, BatchGroup& G, size_t k0, size_t k1, const size_t* n, int32_t* status, std::vector<std::string>& detail,
-                  Hdr hdr, Level level, Placed placed) {
-  const size_t items = k1 - k0;
-  G.k0 = k0; G.k1 = k1; G.ok.assign(items, 0);
-  J.mode = 0; J.batch = true; J.timing = env_debug();
-  S.bst.resize(items); S.ben.resize(items); S.bdsz.assign(items, 100000u);
-  int max_level = 1;
-  size_t bytes = 0;
-  for (size_t i = 0; i < items; i++) {
-    const size_t k = k0 + i;
-    S.bst[i] = S.ben[i] = (uint32_t)bytes;
-    int lv = 0; const char* why = nullptr;
-    if ((status[k] = bz_header_check(hdr(k), n[k], &lv, &why)) != 0) { detail[k] = why; continue; }
-    const int own = level(k, lv);
-    S.bdsz[i] = 100000u * (uint32_t)own;
-    max_level = std::max(max_level, own);
-    G.ok[i] = 1;
-    placed(k, bytes);
-    S.ben[i] = (uint32_t)(bytes + n[k]);
-    bytes = (bytes + n[k] + 3) & ~(size_t)3;
-  }
-  J.tt_stride = 100000u * (uint32_t)max_level;
-  J.n = bytes;
-  S.lo = 0; S.hi = bytes; S.up_lo = 0; S.up_hi = bytes;
-}
-
-// A laid-out group up to phase B: phase A over the upload, the walk of every accepted input over the candidates of its bytes
-// (walk(k, C), C.base being the input's first bit of the upload; its error is pending: a bad block CRC in front of it wins),
-// phase B over all chain blocks, the output offsets.  A failure of the call, or 0 and the bytes of the group's output.
-template <typename Walk>
-int group_prepare(DecJob& J, DecShare& S, BatchGroup& G, int32_t* status, std::vector<std::string>& detail, Walk walk, uint64_t* total) {
-  if (J.n) {
-    guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-    if (S.rc) return S.rc;
-  }
-  WalkCands C(&S, 1);
-  const size_t items = G.k1 - G.k0;
-  G.ch0.assign(items, 0); G.ch1.assign(items, 0);
-  for (size_t i = 0; i < items; i++) {
-    G.ch0[i] = G.ch1[i] = J.chain.size();
-    if (!G.ok[i]) continue;
-    C.base = 8ull * S.bst[i];
-    clear_detail();
-    const int rc = walk(G.k0 + i, C);
-    G.ch1[i] = J.chain.size();
-    if (rc) { status[G.k0 + i] = rc; detail[G.k0 + i] = cjs_last_error_detail(); }
-  }
-  clear_detail();
-  S.c0 = 0; S.c1 = J.chain.size();
-  if (S.c1) {
-    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
-    // (phase B's own CJS_E_UNSUPPORTED / CJS_E_DATA_ERROR exits cannot happen -- a block holds <= 900000 bytes, a walk makes a step;
-    // should one, it is a failure of the call, reported as one of the call's codes)
-    if (S.rc == CJS_E_OUT_OF_MEMORY || S.rc == CJS_E_NO_DEVICE) return S.rc;
-    if (S.rc) return CJS_E_HIP;
-  }
-  *total = chain_out_offsets(J);
-  return 0;
-}
-
-// After phase C (J.crc_got): input k's verdict is the single call's -- the first block of its chain, in stream order, whose CRC
-// fails (:1756-1761); else what its header or its walk left in status / detail; else success -- and its bytes: off from `base`
-// on, len 0 for a failed input.
-void group_verdicts(const DecJob& J, const BatchGroup& G, size_t base, size_t* off, size_t* len, int32_t* status, std::vector<std::string>& detail) {
-  for (size_t i = 0; i < G.k1 - G.k0; i++) {
-    const size_t k = G.k0 + i;
-    for (size_t b = G.ch0[i]; b < G.ch1[i]; b++) if (J.crc_got[b] != J.chain[b].crc) {
-      char d[96];
-      bad_crc_detail(d, sizeof d, J.crc_got[b], J.chain[b].crc);
-      status[k] = CJS_E_DATA_ERROR; detail[k] = d;
-      break;
-    }
-    off[k] = base + (size_t)J.out_off[G.ch0[i]];
-    len[k] = status[k] ? 0 : (size_t)(J.out_off[G.ch1[i]] - J.out_off[G.ch0[i]]);
-  }
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------- device-resident source and sink (cjs_bzip2_decompress_device)
-// bunzip_core with the input and the output in the GPU's memory.  The host path reads its host copy of the input in four places;
-// each is a device pass here (dec_device.hip): the header (dd_headers, one 8-byte D2H), the level pre-scan of a multistream input
-// (dd_level_scan: bz_max_level's rule), the upload (a device-to-device copy into phase A's dword-phased scratch) and, after the
-// magic scan, the stored stream CRC and restart header of every end-of-stream candidate (dd_eos_bytes), which bz_walk reads
-// through DevWalkBytes.  Phase C expands into the caller's buffer at the final offsets.  One share: the input lives on one GPU.
-// See DESIGN.md §6d.
-namespace {
-
-bool on_device(const void* p, int dev) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return a.type == hipMemoryTypeDevice && a.device == dev;
-}
-
-// what bz_walk reads of a device input: its 4 header bytes, and EOS_REC bytes from byte `at` on at the end-of-stream candidate
-// the walk stands on
-struct DevWalkBytes {
-  const uint8_t* hdr; const uint8_t* rec = nullptr; uint64_t at = 0;
-  uint8_t operator[](uint64_t i) const { if (rec && i - at < (uint64_t)EOS_REC) return rec[i - at]; return i < 4 ? hdr[i] : (uint8_t)0; }
-};
-
-// J->eos of a device source: EOS_REC bytes per end-of-stream candidate (rec_of[c]: its record, -1 for a block candidate)
-int dev_eos_gather(DecShare* S, std::vector<uint8_t>& rec, std::vector<long>& rec_of) {
-  const size_t nc = S->cands.size();
-  std::vector<uint64_t> tab;
-  rec_of.assign(nc, -1);
-  for (size_t c = 0; c < nc; c++) if (S->cands[c].kind) {
-    rec_of[c] = (long)(tab.size() / 2);
-    tab.push_back((S->cands[c].bit + 48) >> 3);
-    tab.push_back(S->bst.empty() ? S->up_hi : S->ben[S->cands[c].pad]);      // (a batch candidate: its own input's end)
-  }
-  const uint32_t ne = (uint32_t)(tab.size() / 2);
-  rec.assign((size_t)ne * EOS_REC, 0);
-  if (!ne) return 0;
-  uint64_t* d_tab = nullptr; uint8_t* d_rec = nullptr;
-  ShareScratch q(S);
-  CJS_TRY(q.take((void**)&d_tab, 16 * (size_t)ne));
-  CJS_TRY(q.take((void**)&d_rec, (size_t)ne * EOS_REC));
-  if (hipMemcpyAsync(d_tab, tab.data(), 16 * (size_t)ne, hipMemcpyHostToDevice, S->s) != hipSuccess) return CJS_E_HIP;
-  launch_dev_eos_bytes(S->s, S->d_in, d_tab, ne, d_rec);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rec.data(), d_rec, (size_t)ne * EOS_REC, hipMemcpyDeviceToHost, S->s) != hipSuccess ||
-      hipStreamSynchronize(S->s) != hipSuccess) return CJS_E_HIP;
-  S->h2d += 16 * (size_t)ne; S->d2h += (size_t)ne * EOS_REC;
-  q.done();
-  return 0;
-}
-
-// One decode of a device-resident source: a single stream (bunzip_core with one share) or a batch group (dec_batch_group).
-// Prepared up to phase B, so that every size is known before anything is written, then emitted (phase C into the caller's buffer).
-struct DevUnit {
-  DecJob J;
-  DecShare S;
-  std::vector<uint8_t> rec; std::vector<long> rec_of;      // the end-of-stream candidates' bytes (dev_eos_gather)
-  int pending = 0; char pending_detail[192] = {0};         // single: the walk's error, reported if every block in front passes its CRC
-  uint64_t total = 0;                                       // bytes of the unit's output
-  BatchGroup G;                                             // batch: inputs [G.k0, G.k1) of the call (a single stream of its own: one)
-  std::vector<GatherPiece> pieces;                          // batch group: the gather of the inputs into the group layout
-};
-
-// _start_bunzip's bytes of `count` inputs (input k = d_in[off[k] .. off[k+1])), and for a multistream call the largest member level
-// of each (bz_max_level), on S's stream and from its pool
-int dev_headers(DecShare& S, const uint8_t* d_in, const std::vector<uint64_t>& off, bool multistream, std::vector<DevHdr>& hd) {
-  const size_t count = off.size() - 1;
-  hd.assign(count, DevHdr{});
-  if (off.back() == off.front()) return 0;                       // (no bytes at all: every header is empty)
-  if (hipSetDevice(S.device) != hipSuccess || (!S.s && hipStreamCreate(S.s.put()) != hipSuccess)) return CJS_E_HIP;
-  uint64_t* d_off = nullptr; DevHdr* d_hdr = nullptr;
-  ShareScratch q(&S);
-  CJS_TRY(q.take((void**)&d_off, 8 * off.size()));
-  CJS_TRY(q.take((void**)&d_hdr, sizeof(DevHdr) * count));
-  if (hipMemcpyAsync(d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, S.s) != hipSuccess) return CJS_E_HIP;
-  launch_dev_headers(S.s, d_in, d_off, (uint32_t)count, multistream, off.front(), off.back(), d_hdr);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hd.data(), d_hdr, sizeof(DevHdr) * count, hipMemcpyDeviceToHost, S.s) != hipSuccess ||
-      hipStreamSynchronize(S.s) != hipSuccess) return CJS_E_HIP;
-  S.h2d += 8 * off.size(); S.d2h += sizeof(DevHdr) * count;
-  q.done();
-  return 0;
-}
-
-// the walk of one input over the candidates of its bytes (C.base: its first bit of the share's upload): the bytes behind an
-// end-of-stream magic come from the candidate's record
-int dev_walk(DevUnit& U, const WalkCands& C, const DevHdr& hd, size_t n, int multistream) {
-  DevWalkBytes acc{hd.h};
-  return walk_chain(U.J, C, acc, n, multistream, 0, [&](long ci, uint64_t pos) {
-    if (C.kind(ci)) { acc.rec = U.rec.data() + (size_t)U.rec_of[(size_t)ci] * EOS_REC; acc.at = (pos + 48) >> 3; }
-  });
-}
-
-// single stream, up to phase B: 0 (U.pending, U.total set) or what cjs_bzip2_decompress returns before its output stage
-int dev_single_prepare(DevUnit& U, const uint8_t* d_in, size_t n, int multistream, const DevHdr& hd) {
-  int level = 0; const char* why = nullptr;
-  if (bz_header_check(hd.h, n, &level, &why)) { set_detail("%s", why); return CJS_E_NOT_BZIP_DATA; }
-  DecJob& J = U.J; DecShare& S = U.S;
-  J.n = n; J.mode = 0; J.timing = env_debug();
-  J.tt_stride = 100000u * (uint32_t)(multistream ? std::max<int>(level, (int)hd.level) : level);
-  J.upload = [d_in, n](DecShare* s, uint8_t* dst) { return hipMemcpyAsync(dst, d_in, n, hipMemcpyDeviceToDevice, s->s) != hipSuccess ? (int)CJS_E_HIP : 0; };
-  J.eos = [&U](DecShare* s) { return dev_eos_gather(s, U.rec, U.rec_of); };
-  S.lo = 0; S.hi = n; S.up_lo = 0; S.up_hi = n;
-  guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-  if (S.rc) return S.rc;
-  U.pending = dev_walk(U, WalkCands(&S, 1), hd, n, multistream);
-  snprintf(U.pending_detail, sizeof U.pending_detail, "%s", cjs_last_error_detail());
-  clear_detail();
-  S.c0 = 0; S.c1 = J.chain.size();
-  if (S.c1) {
-    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
-    if (S.rc) return S.rc;
-  }
-  U.total = chain_out_offsets(J);
-  return 0;
-}
-
-// single stream, phase C into d_out (nullptr: the CRC verdicts alone, in scratch; so with a pending error) -> the final verdict
-int dev_single_emit(DevUnit& U, uint8_t* d_out) {
-  if (!U.J.chain.empty()) {
-    U.J.dev_out = U.pending ? nullptr : d_out; U.J.host = nullptr;
-    U.S.rc = 0;
-    guarded(U.S.rc, [&] { dec_phase_c(&U.J, &U.S); });
-    if (U.S.rc) { if (U.S.detail[0]) set_detail("%s", U.S.detail); return U.S.rc; }
-  }
-  if (U.pending) { set_detail("%s", U.pending_detail); return U.pending; }
-  return 0;
-}
-
-// a batch group up to phase B: the inputs (n[k] bytes from d_in + in_off[k] on, their headers in hd) are gathered into the group
-// layout on the device, and a walk reads its bytes from hd and the end-of-stream records
-int dev_group_prepare(DevUnit& U, const uint8_t* d_in, const size_t* in_off, const size_t* n, size_t k0, size_t k1, int multistream, const std::vector<DevHdr>& hd,
-                      int32_t* status, std::vector<std::string>& detail) {
-  DecJob& J = U.J;
-  group_layout(J, U.S, U.G, k0, k1, n, status, detail, [&](size_t k) { return hd[k].h; },
-               [&](size_t k, int level) { return multistream ? std::max<int>(level, (int)hd[k].level) : level; },
-               [&](size_t k, size_t at) {
-                 for (size_t p = 0; p < n[k]; p += GATHER_PIECE)      // (pieces of whole words: the last one of an input is zero-filled to one)
-                   U.pieces.push_back(GatherPiece{in_off[k] + p, (uint32_t)(at + p), (uint32_t)std::min<size_t>(GATHER_PIECE, n[k] - p)});
-               });
-  J.upload = [&U, d_in](DecShare* s, uint8_t* dst) {
-    GatherPiece* d_pc = nullptr;
-    CJS_TRY(s->take((void**)&d_pc, sizeof(GatherPiece) * U.pieces.size()));
-    if (hipMemcpyAsync(d_pc, U.pieces.data(), sizeof(GatherPiece) * U.pieces.size(), hipMemcpyHostToDevice, s->s) != hipSuccess) return (int)CJS_E_HIP;
-    s->h2d += sizeof(GatherPiece) * U.pieces.size();
-    launch_dev_gather(s->s, d_in, d_pc, (uint32_t)U.pieces.size(), dst);
-    return hipGetLastError() != hipSuccess ? (int)CJS_E_HIP : 0;
-  };
-  J.eos = [&U](DecShare* s) { return dev_eos_gather(s, U.rec, U.rec_of); };
-  return group_prepare(J, U.S, U.G, status, detail, [&](size_t k, const WalkCands& C) { return dev_walk(U, C, hd[k], n[k], multistream); }, &U.total);
-}
-
-// a batch group, phase C into d_out (the group's region): every input's status, offset (from d_out) and length
-int dev_group_emit(DevUnit& U, uint8_t* d_out, size_t base, size_t* out_off, size_t* out_len, int32_t* status, std::vector<std::string>& detail) {
-  DecJob& J = U.J;
-  J.crc_got.assign(J.chain.size(), 0);
-  J.dev_out = d_out;
-  if (!J.chain.empty()) { U.S.rc = 0; guarded(U.S.rc, [&] { dec_phase_c(&J, &U.S); }); }
-  if (U.S.rc) return U.S.rc;
-  group_verdicts(J, U.G, base, out_off, out_len, status, detail);
-  return 0;
-}
-
-}  // namespace
-
-extern "C" int cjs_bzip2_decompress_device(const uint8_t* d_in, size_t n, int multistream, uint8_t* d_out, size_t out_cap, size_t* out_n, const cjs_opts* opts) {
-  if (!out_n || (!d_in && n) || (!d_out && out_cap)) return CJS_E_INVALID_ARG;
-  *out_n = 0;
-  clear_detail();
-  CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if ((n && !on_device(d_in, dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
-  DevUnit U;
-  U.S.device = dev;
-  std::vector<DevHdr> hd;
-  CJS_TRY(dev_headers(U.S, d_in, {0, (uint64_t)n}, multistream != 0, hd));
-  int rc = dev_single_prepare(U, d_in, n, multistream, hd[0]);
-  if (!rc && !U.pending && U.total > out_cap) { *out_n = (size_t)U.total; rc = CJS_E_OUTPUT_TOO_SMALL; }      // (d_out untouched)
-  else if (!rc) rc = dev_single_emit(U, d_out);
-  U.S.release();
-  if (U.J.timing)
-    fprintf(stderr, "[cjs dec dev] single: %zu bytes in, %llu bytes out, H2D %llu D2H %llu candidates %zu blocks %zu\n", n, (unsigned long long)U.total,
-            (unsigned long long)U.S.h2d, (unsigned long long)U.S.d2h, U.S.cands.size(), U.J.chain.size());
-  if (!rc) *out_n = (size_t)U.total;
-  return rc;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-// ---------------------------------------------------------------- recovery (cjs_bzip2_recover[_device])
-// Phases A, B and C without the chain walk: one share over the whole input with rows sized for level 9 and no header check; every
-// decodable block candidate becomes a "chain" block of phases B and C, which return a CRC verdict per block (DecJob::batch); the
-// host then picks the survivors in ascending order (the rule: include/cjs_hip.h).  Phases B and C run over one inverse-BWT batch
-// of the candidates at a time (dec_next_batch), phase C expanding into scratch of the batch's size, and only the survivors leave
-// it: so the memory held is phase A's (the upload and the decoded rows, as for decompression) plus one batch's, however many
-// candidates there are.  The stream form gathers the survivors' bit strings from the upload, which stays with the share, into a
-// zeroed buffer of the new stream's size (bz_bits_gather).  See DESIGN.md §6g.
-namespace cjs {
-
-// Bits [src_bit, src_bit + nbits) of a source go to bits [dst_bit, ..) of `out`; bit b of either is bit 31 - (b & 31) of the
-// big-endian 32-bit word b >> 5.  src: the device address of the source's word 0 (4-byte aligned), src_words: the words of it
-// that may be read.  nbits >= 1.
-struct BitRun { uint64_t src, src_words, src_bit, dst_bit, nbits; };
-// One thread per DESTINATION word of a run (workgroups along grid.x stride over the run's words, grid.y = the runs of a slab):
-// the two source words the word straddles, a funnel shift, and the mask of the destination bits that are the run's -- what lies
-// in front of the first and behind the last source bit belongs to other blocks or to damage.  A word wholly inside its run is
-// stored; the first and the last word of a run, which two runs may share, are ORed into the zeroed buffer.
-__global__ __launch_bounds__(256) void bz_bits_gather(const BitRun* __restrict__ runs, uint32_t run0, uint32_t* __restrict__ out) {
-  const BitRun r = runs[run0 + blockIdx.y];
-  const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(r.src);
-  const uint64_t d1 = r.dst_bit + r.nbits, w0 = r.dst_bit >> 5, w1 = (d1 - 1) >> 5;
-  for (uint64_t w = w0 + (uint64_t)blockIdx.x * 256 + threadIdx.x; w <= w1; w += (uint64_t)gridDim.x * 256) {
-    const int64_t t = (int64_t)r.src_bit + ((int64_t)(w << 5) - (int64_t)r.dst_bit);      // the source bit that lands on the word's first bit
-    const int64_t wi = t >> 5;                                                              // (floor: t >= -31)
-    const uint32_t sh = (uint32_t)(t & 31);
-    const uint32_t hi = wi >= 0 && (uint64_t)wi < r.src_words ? __builtin_bswap32(src[wi]) : 0u;
-    const uint32_t lo = sh && wi + 1 >= 0 && (uint64_t)(wi + 1) < r.src_words ? __builtin_bswap32(src[wi + 1]) : 0u;
-    uint32_t v = sh ? __builtin_amdgcn_alignbit(hi, lo, 32u - sh) : hi;
-    const uint32_t a = w == w0 ? (uint32_t)(r.dst_bit & 31) : 0u, b = w == w1 ? (uint32_t)((d1 - 1) & 31) + 1u : 32u;      // the run's bits [a, b) of the word
-    const uint32_t mask = (0xFFFFFFFFu >> a) & (b == 32u ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> b));
-    v = __builtin_bswap32(v & mask);
-    if (mask == 0xFFFFFFFFu) out[w] = v; else atomicOr(&out[w], v);
-  }
-}
-
-}  // namespace cjs
-
-namespace {
-
-// the recovered bytes on the host: a HostPool buffer that grows batch by batch (one batch -- the usual case -- never copies)
-struct RecHost {
-  uint8_t* p = nullptr; size_t cap = 0;
-  ~RecHost() { HostPool::give(p); }
-  int ensure(size_t used, size_t need) {
-    if (need <= cap && p) return 0;
-    const size_t nc = std::max<size_t>(std::max<size_t>(need, 2 * cap), 1);
-    uint8_t* q = (uint8_t*)HostPool::take(nc);
-    if (!q) return CJS_E_OUT_OF_MEMORY;
-    if (used) memcpy(q, p, used);
-    HostPool::give(p);
-    p = q; cap = nc;
-    return 0;
-  }
-  uint8_t* release() { uint8_t* q = p; p = nullptr; cap = 0; return q; }
-};
-
-// in: the input on the host, or nullptr with d_src: the input on device `dev`.  host_out: the host form's result; else d_out /
-// out_cap (checked by the caller).  found / cap / n_found as in the C ABI.
-int recover_core(const uint8_t* in, const uint8_t* d_src, size_t n, bool as_stream, uint8_t** host_out, uint8_t* d_out, size_t out_cap, size_t* out_n,
-                 cjs_bz_found* found, long cap, long* n_found, int dev) {
-  RecHost host;                                                   // (declared first: given back after the share's stream has drained)
-  DecJob J; DecShare S;
-  J.in = in; J.n = n; J.mode = 0; J.batch = true; J.timing = env_debug();
-  J.tt_stride = 900000u;
-  if (d_src) J.upload = [d_src, n](DecShare* s, uint8_t* dst) { return hipMemcpyAsync(dst, d_src, n, hipMemcpyDeviceToDevice, s->s) != hipSuccess ? (int)CJS_E_HIP : 0; };
-  S.device = dev; S.lo = 0; S.hi = n; S.up_lo = 0; S.up_hi = n;
-  guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-  if (S.rc) return S.rc;
-  hipStream_t s = S.s;
-  // phase B gives a one-batch share's rows back when it ends: here it runs once per batch of candidates, the rows stay to the end
-  uint8_t* rows = S.d_tt; S.d_tt = nullptr;
-
-  std::vector<uint32_t> bc;                                       // the block candidates (indices into S.cands), ascending
-  for (uint32_t c = 0; c < S.cands.size(); c++) if (S.cands[c].kind == 0) bc.push_back(c);
-  const size_t nc = bc.size();
-  *n_found = (long)nc;
-  const uint64_t nbits = (uint64_t)n * 8;
-  std::vector<uint32_t> chain_bc;                                 // chain block k is block candidate chain_bc[k]
-  for (size_t i = 0; i < nc; i++) {
-    const BlockOut& bo = S.bos[bc[i]];
-    if (bo.err || bo.end_bit >= nbits) continue;                  // (the decoder clamps end_bit to the end: a block that touches it may have been cut off)
-    IbBlock ib; ib.tt = S.tt_ptr[bc[i]]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
-    J.chain.push_back(ib); chain_bc.push_back((uint32_t)i);
-  }
-  const size_t nb = J.chain.size();
-  J.crc_got.assign(nb, 0);
-  J.out_off.assign(nb + 1, 0);
-
-  std::vector<BitRun> runs;                                       // stream form: header, survivors, trailer
-  uint64_t total = 0, last_end = 0, sbit = 32;                    // bytes recovered so far / the selection's state / the new stream's next bit
-  uint32_t fold = 0;
-  const uint64_t src_addr = (uint64_t)(uintptr_t)S.d_in, src_words = ((uint64_t)n + 3) / 4;      // (the upload has 256 bytes of slack)
-  size_t next = 0;                                                // block candidates in front of `next` have their entry
-  auto entry = [&](size_t i, int status, uint64_t end_bit, uint64_t off, uint32_t size) {
-    if (!found || (long)i >= cap) return;
-    cjs_bz_found& f = found[i];
-    f.bitpos = S.cands[bc[i]].bit; f.end_bit = end_bit; f.out_off = off; f.size = size; f.status = status; f.crc = S.bos[bc[i]].crc; f.reserved = 0;
-  };
-  auto lost_upto = [&](size_t i1) {                               // the candidates that are not decodable, up to i1
-    for (; next < i1; next++) {
-      const BlockOut& bo = S.bos[bc[next]];
-      entry(next, S.cands[bc[next]].bit < last_end ? CJS_REC_SHADOWED : bo.err ? bo.err : CJS_E_DATA_ERROR, 0, 0, 0);
-    }
-  };
-  int rc = 0;
-  for (size_t g0 = 0; g0 < nb && !rc;) {
-    const size_t g1 = dec_next_batch(&J, g0, nb);
-    S.c0 = g0; S.c1 = g1; S.rc = 0;
-    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
-    if (S.rc) { rc = S.rc == CJS_E_OUT_OF_MEMORY || S.rc == CJS_E_NO_DEVICE ? S.rc : CJS_E_HIP; break; }      // (its other exits cannot happen: see group_prepare)
-    J.out_off[g0] = 0;                                            // (offsets inside the batch's scratch)
-    for (size_t k = g0; k < g1; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
-    const uint64_t gbytes = J.out_off[g1];
-    uint8_t* d_exp = nullptr;
-    if ((rc = S.take((void**)&d_exp, (size_t)gbytes + 64)) != 0) break;
-    J.dev_out = d_exp; J.host = nullptr;
-    guarded(S.rc, [&] { dec_phase_c(&J, &S); });
-    if (S.rc) { rc = S.rc; break; }
-    // the selection over this batch, and the survivors' bytes as runs of neighbours in the scratch
-    struct Piece { uint64_t from, to, len; };
-    std::vector<Piece> pieces;
-    for (size_t k = g0; k < g1; k++) {
-      const size_t i = chain_bc[k];
-      lost_upto(i);
-      const uint64_t p = S.cands[bc[i]].bit, e = S.bos[bc[i]].end_bit;
-      next = i + 1;
-      if (p < last_end) { entry(i, CJS_REC_SHADOWED, e, 0, 0); continue; }
-      if (J.crc_got[k] != J.chain[k].crc) { entry(i, CJS_E_DATA_ERROR, e, 0, 0); continue; }
-      const uint32_t len = J.chain[k].out_len;
-      entry(i, 0, e, as_stream ? sbit : total, len);
-      last_end = e;
-      if (as_stream) {
-        runs.push_back(BitRun{src_addr, src_words, p, sbit, e - p});
-        sbit += e - p;
-        fold = ((fold << 1) | (fold >> 31)) ^ J.chain[k].crc;
-      } else if (len) {
-        if (!pieces.empty() && pieces.back().from + pieces.back().len == J.out_off[k]) pieces.back().len += len;
-        else pieces.push_back(Piece{J.out_off[k], total, len});
-      }
-      total += len;
-    }
-    if (!as_stream && !pieces.empty()) {
-      if (host_out && (rc = host.ensure((size_t)pieces[0].to, (size_t)total)) != 0) break;
-      for (const Piece& q : pieces) {
-        hipError_t e = hipSuccess;
-        if (host_out) e = hipMemcpyAsync(host.p + q.to, d_exp + q.from, (size_t)q.len, hipMemcpyDeviceToHost, s);
-        else if (q.to + q.len <= out_cap) e = hipMemcpyAsync(d_out + q.to, d_exp + q.from, (size_t)q.len, hipMemcpyDeviceToDevice, s);      // (what does not fit is only counted)
-        if (e != hipSuccess) { rc = CJS_E_HIP; break; }
-        if (host_out) S.d2h += q.len;
-      }
-      if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = CJS_E_HIP;
-      if (rc) break;
-    }
-    S.drop(d_exp); S.drop(S.d_w); S.drop(S.d_carry);              // (the stream has drained)
-    S.d_w = nullptr; S.d_carry = nullptr;
-    g0 = g1;
-  }
-  if (rc) return rc;
-  lost_upto(nc);
-  if (rows) S.drop(rows);
-
-  if (as_stream) {
-    // header and trailer are two more runs, from a 16-byte source of their own: 'BZh9', then the end magic and the combined CRC
-    uint8_t ht[16] = {'B', 'Z', 'h', '9', 0x17, 0x72, 0x45, 0x38, 0x50, 0x90, (uint8_t)(fold >> 24), (uint8_t)(fold >> 16), (uint8_t)(fold >> 8), (uint8_t)fold, 0, 0};
-    const uint64_t sbits = sbit + 80;
-    total = (sbits + 7) / 8;
-    const size_t words = (size_t)((sbits + 31) / 32);
-    uint8_t* d_ht = nullptr; BitRun* d_runs = nullptr; uint32_t* d_str = nullptr;
-    CJS_TRY(S.take((void**)&d_ht, 16));
-    runs.push_back(BitRun{(uint64_t)(uintptr_t)d_ht, 4, 0, 0, 32});
-    runs.push_back(BitRun{(uint64_t)(uintptr_t)d_ht, 4, 32, sbit, 80});
-    CJS_TRY(S.take((void**)&d_runs, sizeof(BitRun) * runs.size()));
-    CJS_TRY(S.take((void**)&d_str, 4 * words));
-    if (hipMemcpyAsync(d_ht, ht, 16, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(d_runs, runs.data(), sizeof(BitRun) * runs.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(d_str, 0, 4 * words, s) != hipSuccess) return CJS_E_HIP;
-    S.h2d += 16 + sizeof(BitRun) * runs.size();
-    for (size_t r0 = 0; r0 < runs.size(); r0 += 65535) {          // (grid.y)
-      const uint32_t nr = (uint32_t)std::min<size_t>(65535, runs.size() - r0);
-      uint64_t mx = 0;
-      for (size_t r = r0; r < r0 + nr; r++) mx = std::max(mx, runs[r].nbits);
-      const uint32_t gx = (uint32_t)std::min<uint64_t>(256, (mx / 32 + 2 + 255) / 256);
-      hipLaunchKernelGGL(bz_bits_gather, dim3(gx, nr), dim3(256), 0, s, d_runs, (uint32_t)r0, d_str);
-    }
-    if (hipGetLastError() != hipSuccess) return CJS_E_HIP;
-    hipError_t e = hipSuccess;
-    if (host_out) {
-      CJS_TRY(host.ensure(0, (size_t)total));
-      e = hipMemcpyAsync(host.p, d_str, (size_t)total, hipMemcpyDeviceToHost, s);
-      S.d2h += total;
-    } else if (total <= out_cap) e = hipMemcpyAsync(d_out, d_str, (size_t)total, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return CJS_E_HIP;
-  }
-  S.release();
-  if (J.timing)
-    fprintf(stderr, "[cjs recover] %zu bytes in, %zu candidates, %zu decodable, %u row batches (phase A), %u inverse-BWT batches, %llu bytes out (%s), H2D %llu D2H %llu\n", n, nc, nb,
-            S.a_batches, S.b_batches, (unsigned long long)total, as_stream ? "stream" : "bytes", (unsigned long long)S.h2d, (unsigned long long)S.d2h);
-  *out_n = (size_t)total;
-  if (host_out) {
-    CJS_TRY(host.ensure(0, 1));                                  // (nothing recovered: still a buffer, as cjs_bzip2_decompress gives)
-    *host_out = host.release();
-    return 0;
-  }
-  return total > out_cap ? (int)CJS_E_OUTPUT_TOO_SMALL : 0;
-}
-
-// the stream form of "nothing found" (n < 6: no device needed)
-const uint8_t REC_EMPTY_STREAM[14] = {'B', 'Z', 'h', '9', 0x17, 0x72, 0x45, 0x38, 0x50, 0x90, 0, 0, 0, 0};
-
-}  // namespace
-
-extern "C" int cjs_bzip2_recover(const uint8_t* in, size_t n, int as_stream, uint8_t** out, size_t* out_n, cjs_bz_found* found, long cap, long* n_found,
-                                 const cjs_opts* opts) {
-  if (!out || !out_n || !n_found || (!in && n) || (!found && cap > 0)) return CJS_E_INVALID_ARG;
-  *out = nullptr; *out_n = 0; *n_found = 0;
-  clear_detail();
-  CJS_GUARD_BEGIN
-  if (n < 6) {
-    const size_t sz = as_stream ? sizeof REC_EMPTY_STREAM : 0;
-    if (!(*out = (uint8_t*)malloc(sz ? sz : 1))) return CJS_E_OUT_OF_MEMORY;
-    if (sz) memcpy(*out, REC_EMPTY_STREAM, sz);
-    *out_n = sz;
-    return 0;
-  }
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  const int rc = recover_core(in, nullptr, n, as_stream != 0, out, nullptr, 0, out_n, found, cap, n_found, dev);
-  if (rc) { *out_n = 0; *n_found = 0; }
-  return rc;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-extern "C" int cjs_bzip2_recover_device(const uint8_t* d_in, size_t n, int as_stream, uint8_t* d_out, size_t out_cap, size_t* out_n, cjs_bz_found* found, long cap,
-                                        long* n_found, const cjs_opts* opts) {
-  if (!out_n || !n_found || (!d_in && n) || (!d_out && out_cap) || (!found && cap > 0)) return CJS_E_INVALID_ARG;
-  *out_n = 0; *n_found = 0;
-  clear_detail();
-  CJS_GUARD_BEGIN
-  if (n < 6 && !as_stream) return 0;
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if ((n && !on_device(d_in, dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
-  if (n < 6) {                                                    // the empty stream
-    *out_n = sizeof REC_EMPTY_STREAM;
-    if (out_cap < sizeof REC_EMPTY_STREAM) return CJS_E_OUTPUT_TOO_SMALL;
-    return hipMemcpy(d_out, REC_EMPTY_STREAM, sizeof REC_EMPTY_STREAM, hipMemcpyHostToDevice) != hipSuccess ? (int)CJS_E_HIP : 0;
-  }
-  const int rc = recover_core(nullptr, d_in, n, as_stream != 0, nullptr, d_out, out_cap, out_n, found, cap, n_found, dev);
-  if (rc && rc != CJS_E_OUTPUT_TOO_SMALL) { *out_n = 0; *n_found = 0; }
-  return rc;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-// ---------------------------------------------------------------- indexed range reads (cjs_bzip2_read_ranges[_device])
-// recover_core's shape with the candidates given by an index instead of found by the scan: the blocks that the ranges touch go
-// through phases A, B and C in ascending passes, a pass being what one upload of the batch decoder's group size holds.  Only the
-// byte runs of a pass's blocks are uploaded, packed (range_pass_upload), and phase A is told its candidates (DecJob::given): no
-// magic scan, no stream header, no chain walk -- a block stands or falls by its own index entry.  Phase C expands a batch of
-// blocks into scratch, where their CRCs are computed, and the slice gather (range.hip) takes every piece of every range from
-// there to its place.  See DESIGN.md §6h.
-namespace {
-
-enum { RG_GOOD = 0, RG_MISMATCH = 1, RG_BAD_CRC = 2 };
-struct RangePiece { uint32_t block, in_off, len, pad; uint64_t out; };      // len bytes from byte in_off of the block to byte `out` of the layout
-
-// What the index alone says about a call: the layout (lay_off / lay_len: range k clipped, packed in range order), the pieces
-// sorted by block and the touched blocks, ascending.
-struct RangePlan {
-  std::vector<uint64_t> lay_off, lay_len;
-  std::vector<RangePiece> pieces;
-  std::vector<uint32_t> touched;
-  uint64_t total = 0;
-  size_t first_block(const cjs_bz_index* ix, uint64_t o) const { return (size_t)(std::upper_bound(ix->off.begin(), ix->off.end(), o) - ix->off.begin()) - 1; }
-};
-
-int range_plan(const cjs_bz_index* ix, const uint64_t* off, const uint64_t* len, size_t count, RangePlan& P) {
-  const uint64_t end = ix->off.back();
-  P.lay_off.assign(count, 0); P.lay_len.assign(count, 0);
-  for (size_t k = 0; k < count; k++) {
-    if (off[k] + len[k] < off[k]) { set_detail("range %zu: offset + length overflows", k); return CJS_E_INVALID_ARG; }
-    P.lay_off[k] = P.total;
-    if (off[k] >= end || !len[k]) continue;
-    P.lay_len[k] = std::min<uint64_t>(len[k], end - off[k]);
-    uint64_t pos = off[k], left = P.lay_len[k];
-    for (size_t b = P.first_block(ix, pos); left; b++) {
-      const uint64_t take = std::min<uint64_t>(left, ix->off[b + 1] - pos);
-      if (take) P.pieces.push_back(RangePiece{(uint32_t)b, (uint32_t)(pos - ix->off[b]), (uint32_t)take, 0u, P.total + (pos - off[k])});
-      pos += take; left -= take;
-    }
-    P.total += P.lay_len[k];
-  }
-  std::stable_sort(P.pieces.begin(), P.pieces.end(), [](const RangePiece& a, const RangePiece& b) { return a.block < b.block; });
-  for (const RangePiece& p : P.pieces) if (P.touched.empty() || P.touched.back() != p.block) P.touched.push_back(p.block);
-  return 0;
-}
-
-// One pass's upload: the byte runs [bitpos >> 3, (end_bit + 7) >> 3) of touched blocks [t0, t1), neighbours merged, each run at a
-// packed offset congruent to its source address mod 16 (the device gather then stores aligned vectors from aligned vectors).
-struct RangeRun { uint64_t lo, hi, at; };      // stream bytes [lo, hi) at byte `at` of the upload
-struct RangeUpload {
-  std::vector<RangeRun> runs; std::vector<uint64_t> bit;      // bit[i]: where touched block t0 + i's magic starts in the upload
-  uint64_t bytes = 0;
-  uint64_t bytes_with(const cjs_bz_index_entry& e, uint64_t src_addr) const {      // `bytes` once e has been added
-    const uint64_t lo = e.bitpos >> 3, hi = (e.end_bit + 7) >> 3;
-    if (runs.empty() || lo > runs.back().hi) return ((bytes + 15) & ~15ull) + ((src_addr + lo) & 15u) + (hi - lo);
-    return runs.back().at + (std::max(runs.back().hi, hi) - runs.back().lo);
-  }
-  void add(const cjs_bz_index_entry& e, uint64_t src_addr) {
-    const uint64_t lo = e.bitpos >> 3, hi = (e.end_bit + 7) >> 3;
-    if (runs.empty() || lo > runs.back().hi) {
-      const uint64_t at = ((bytes + 15) & ~15ull) + ((src_addr + lo) & 15u);
-      runs.push_back(RangeRun{lo, hi, at});
-    } else runs.back().hi = std::max(runs.back().hi, hi);
-    bytes = runs.back().at + (runs.back().hi - runs.back().lo);
-    bit.push_back((runs.back().at - runs.back().lo) * 8 + e.bitpos);
-  }
-};
-
-constexpr uint64_t RANGE_PASS_DECODED = 4ull << 30;      // decoded bytes of a pass by the index (what phase A keeps of it is at most 1.25 x that)
-
-size_t range_pass_blocks() {      // (read at every call: tests run the several-pass path at small sizes)
-  const char* v = getenv("CJS_RANGE_PASS_BLOCKS");
-  const unsigned long long x = v ? strtoull(v, nullptr, 10) : 0;
-  return x ? (size_t)x : ~(size_t)0;
-}
-
-// slices of one piece of `len` bytes, cut where the destination crosses a multiple of SLICE_TASK behind its first 16-byte boundary
-void range_slices(std::vector<Slice>& sl, uint64_t src, uint64_t dst, uint64_t len) {
-  uint64_t cut = std::min<uint64_t>(len, SLICE_TASK - (dst & 15u));
-  for (uint64_t o = 0; o < len; cut = std::min<uint64_t>(len - o, SLICE_TASK)) { sl.push_back(Slice{src + o, dst + o, cut}); o += cut; }
-}
-
-struct RangeStats { uint64_t h2d = 0, d2h = 0, up = 0; uint32_t passes = 0, a_batches = 0, b_batches = 0; size_t slices = 0; };
-
-// in: the stream on the host, or nullptr with d_src: the stream on device `dev`.  host_out: the host form's buffer in the plan's
-// layout; else d_out.  verdict / crc_got: per block of the index (RG_*; the computed CRC of an RG_BAD_CRC block).
-int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const RangePlan& P, uint8_t* host_out, uint8_t* d_out,
-              std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st) {
-  const size_t nt = P.touched.size(), cap_blocks = range_pass_blocks(), G = dec_group_bytes();
-  Stream keep;                                                     // one stream for all passes
-  size_t piece_at = 0;                                             // pieces in front of it belong to earlier blocks
-  for (size_t t0 = 0; t0 < nt;) {
-    // ---- the pass: touched blocks [t0, t1)
-    RangeUpload U;
-    size_t t1 = t0; uint32_t max_level = 1; uint64_t decoded = 0;
-    while (t1 < nt && t1 - t0 < cap_blocks && t1 - t0 < DEC_BATCH_BLOCKS) {
-      const cjs_bz_index_entry& e = ix->e[P.touched[t1]];
-      if (t1 > t0 && (U.bytes_with(e, (uint64_t)(uintptr_t)d_src) > G || decoded + e.size > RANGE_PASS_DECODED)) break;
-      U.add(e, (uint64_t)(uintptr_t)d_src);
-      max_level = std::max(max_level, e.level); decoded += e.size; t1++;
-    }
-    st.passes++; st.up += U.bytes;
-    const uint64_t up_n = U.bytes;
-    struct HostGive { void* p; ~HostGive() { HostPool::give(p); } } staged{nullptr};      // (declared in front of the share: given back once its stream has drained)
-    DecJob J; DecShare S;
-    S.s = std::move(keep);
-    J.n = (size_t)up_n; J.mode = 0; J.batch = true; J.given = true; J.timing = false;
-    J.tt_stride = 100000u * max_level;
-    S.device = dev; S.lo = 0; S.hi = up_n; S.up_lo = 0; S.up_hi = up_n;
-    std::vector<uint32_t> cand_of(t1 - t0, ~0u);                  // touched block t0 + i's candidate (~0: its magic is not there)
-    if (in) {                                                      // host form: the runs staged in one buffer, the magics checked here
-      if (!(staged.p = HostPool::take((size_t)up_n))) return CJS_E_OUT_OF_MEMORY;
-      for (const RangeRun& r : U.runs) memcpy((uint8_t*)staged.p + r.at, in + r.lo, (size_t)(r.hi - r.lo));
-      J.in = (const uint8_t*)staged.p;
-      for (size_t i = 0; i < t1 - t0; i++) {
-        const uint64_t bp = ix->e[P.touched[t0 + i]].bitpos;
-        uint64_t w = 0;
-        for (int q = 0; q < 7; q++) w = (w << 8) | in[(bp >> 3) + q];      // (end_bit > bitpos + 80 and end_bit <= 8 n: inside the stream)
-        if (((w >> (8 - (bp & 7))) & 0xFFFFFFFFFFFFull) != MAGIC_BLOCK) continue;
-        cand_of[i] = (uint32_t)S.cands.size();
-        S.cands.push_back(Cand{U.bit[i], 0u, 0u});
-      }
-    } else {                                                       // device form: one gather launch, one magic-check launch
-      for (size_t i = 0; i < t1 - t0; i++) { cand_of[i] = (uint32_t)i; S.cands.push_back(Cand{U.bit[i], 0u, 0u}); }
-      J.upload = [&U, d_src](DecShare* s, uint8_t* dst) {
-        std::vector<Slice> sl;
-        for (const RangeRun& r : U.runs) range_slices(sl, (uint64_t)(uintptr_t)d_src + r.lo, (uint64_t)(uintptr_t)dst + r.at, r.hi - r.lo);
-        Slice* d_sl = nullptr;
-        CJS_TRY(s->take((void**)&d_sl, sizeof(Slice) * sl.size()));      // (stays with the share: the copy below may still read `sl` -- it is synchronous for pageable memory)
-        if (hipMemcpy(d_sl, sl.data(), sizeof(Slice) * sl.size(), hipMemcpyHostToDevice) != hipSuccess) return (int)CJS_E_HIP;
-        s->h2d += sizeof(Slice) * sl.size();
-        launch_slices(s->s, d_sl, sl.size());
-        return hipGetLastError() != hipSuccess ? (int)CJS_E_HIP : 0;
-      };
-      J.vet = [&cand_of](DecShare* s) {
-        const uint32_t nc = (uint32_t)s->cands.size();
-        std::vector<uint64_t> bits(nc); std::vector<uint32_t> ok(nc);
-        for (uint32_t c = 0; c < nc; c++) bits[c] = s->cands[c].bit;
-        uint64_t* d_bits = nullptr; uint32_t* d_ok = nullptr;
-        ShareScratch q(s);
-        CJS_TRY(q.take((void**)&d_bits, 8 * (size_t)nc));
-        CJS_TRY(q.take((void**)&d_ok, 4 * (size_t)nc));
-        if (hipMemcpy(d_bits, bits.data(), 8 * (size_t)nc, hipMemcpyHostToDevice) != hipSuccess) return (int)CJS_E_HIP;
-        launch_cand_magic(s->s, s->d_in, s->up_hi, d_bits, nc, d_ok);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(ok.data(), d_ok, 4 * (size_t)nc, hipMemcpyDeviceToHost, s->s) != hipSuccess ||
-            hipStreamSynchronize(s->s) != hipSuccess) return (int)CJS_E_HIP;
-        s->h2d += 8 * (size_t)nc; s->d2h += 4 * (size_t)nc;
-        std::vector<Cand> kept;                                      // (candidate c is touched block t0 + c until here)
-        for (uint32_t c = 0; c < nc; c++) {
-          cand_of[c] = ok[c] ? (uint32_t)kept.size() : ~0u;
-          if (ok[c]) kept.push_back(s->cands[c]);
-        }
-        s->cands.swap(kept);
-        q.done();
-        return 0;
-      };
-    }
-    if (!S.cands.empty()) {
-      guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-      if (S.rc) return S.rc;
-    }
-    hipStream_t s = S.s;
-    uint8_t* rows = S.d_tt; S.d_tt = nullptr;                      // (phase B runs once per batch here: see recover_core)
-
-    // ---- the blocks that agree with their entries so far become the chain of phases B and C
-    std::vector<uint32_t> chain_blk;
-    for (size_t i = 0; i < t1 - t0; i++) {
-      const uint32_t b = P.touched[t0 + i], c = cand_of[i];
-      const cjs_bz_index_entry& e = ix->e[b];
-      verdict[b] = RG_MISMATCH;
-      if (c == ~0u || S.cands[c].kind != 0) continue;
-      const BlockOut& bo = S.bos[c];
-      const int v = bz_block_verdict(bo, 100000u * e.level, e.bitpos, false);
-      clear_detail();
-      if (v || !bo.count || bo.end_bit - (U.bit[i] - e.bitpos) != e.end_bit || bo.crc != e.crc) continue;
-      IbBlock ib; ib.tt = S.tt_ptr[c]; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
-      J.chain.push_back(ib); chain_blk.push_back(b);
-    }
-    const size_t nb = J.chain.size();
-    J.crc_got.assign(nb, 0);
-    J.out_off.assign(nb + 1, 0);
-    int rc = 0;
-    for (size_t g0 = 0; g0 < nb && !rc;) {
-      const size_t g1 = dec_next_batch(&J, g0, nb);
-      S.c0 = g0; S.c1 = g1; S.rc = 0;
-      guarded(S.rc, [&] { dec_phase_b(&J, &S); });
-      if (S.rc) { rc = S.rc == CJS_E_OUT_OF_MEMORY || S.rc == CJS_E_NO_DEVICE ? S.rc : CJS_E_HIP; break; }
-      J.out_off[g0] = 0;                                            // (offsets inside the batch's scratch)
-      for (size_t k = g0; k < g1; k++) J.out_off[k + 1] = J.out_off[k] + J.chain[k].out_len;
-      uint8_t* d_exp = nullptr;
-      if ((rc = S.take((void**)&d_exp, (size_t)J.out_off[g1] + 64)) != 0) break;
-      J.dev_out = d_exp; J.host = nullptr;
-      guarded(S.rc, [&] { dec_phase_c(&J, &S); });
-      if (S.rc) { rc = S.rc; break; }
-      // the verdicts, and the good blocks' pieces as runs of the scratch (neighbours in both the scratch and the layout merged)
-      struct Run { uint64_t src, to, len; };                        // len bytes from byte src of d_exp to byte `to` of the layout
-      std::vector<Run> runs;
-      uint64_t packed = 0;
-      for (size_t k = g0; k < g1; k++) {
-        const uint32_t b = chain_blk[k];
-        while (piece_at < P.pieces.size() && P.pieces[piece_at].block < b) piece_at++;
-        if (J.chain[k].out_len != ix->e[b].size) continue;
-        if (J.crc_got[k] != J.chain[k].crc) { verdict[b] = RG_BAD_CRC; crc_got[b] = J.crc_got[k]; continue; }
-        verdict[b] = RG_GOOD;
-        for (; piece_at < P.pieces.size() && P.pieces[piece_at].block == b; piece_at++) {
-          const RangePiece& p = P.pieces[piece_at];
-          const uint64_t src = J.out_off[k] + p.in_off;
-          if (!runs.empty() && runs.back().src + runs.back().len == src && runs.back().to + runs.back().len == p.out) runs.back().len += p.len;
-          else runs.push_back(Run{src, p.out, p.len});
-          packed += p.len;
-        }
-      }
-      // Host form, a few long runs (one long range, the whole stream): each goes from the scratch straight to its place, no
-      // gather.  Else the slice gather: into d_out, or into a packed buffer that goes to the host in one copy.
-      const bool direct = host_out && runs.size() <= 16;
-      std::vector<Slice> sl;
-      uint8_t* d_pack = nullptr; Slice* d_sl = nullptr;
-      HostGive bounce{nullptr};
-      if (!direct && packed) {
-        if (host_out && (rc = S.take((void**)&d_pack, (size_t)packed + 64)) != 0) break;
-        if (host_out && !(bounce.p = HostPool::take((size_t)packed))) { rc = CJS_E_OUT_OF_MEMORY; break; }
-        uint64_t at = 0;
-        for (const Run& r : runs) {
-          range_slices(sl, (uint64_t)(uintptr_t)(d_exp + r.src), (uint64_t)(uintptr_t)(host_out ? d_pack + at : d_out + r.to), r.len);
-          at += r.len;
-        }
-        if ((rc = S.take((void**)&d_sl, sizeof(Slice) * sl.size())) != 0) break;
-        // from here on no way out without the synchronize below: the copy may still be reading `sl`
-        if (hipMemcpyAsync(d_sl, sl.data(), sizeof(Slice) * sl.size(), hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-        else {
-          S.h2d += sizeof(Slice) * sl.size(); st.slices += sl.size();
-          launch_slices(s, d_sl, sl.size());
-          if (hipGetLastError() != hipSuccess) rc = CJS_E_HIP;
-        }
-      }
-      if (!rc && host_out && packed) {
-        if (direct) { for (const Run& r : runs) if (hipMemcpyAsync(host_out + r.to, d_exp + r.src, (size_t)r.len, hipMemcpyDeviceToHost, s) != hipSuccess) { rc = CJS_E_HIP; break; } }
-        else if (hipMemcpyAsync(bounce.p, d_pack, (size_t)packed, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
-        S.d2h += packed;
-      }
-      if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = CJS_E_HIP;
-      if (rc) break;
-      if (bounce.p) { uint64_t at = 0; for (const Run& r : runs) { memcpy(host_out + r.to, (const uint8_t*)bounce.p + at, (size_t)r.len); at += r.len; } }
-      S.drop(d_exp); S.drop(S.d_w); S.drop(S.d_carry);              // (the stream has drained)
-      if (d_pack) S.drop(d_pack);
-      if (d_sl) S.drop(d_sl);
-      S.d_w = nullptr; S.d_carry = nullptr;
-      g0 = g1;
-    }
-    if (rc) return rc;
-    if (rows) S.drop(rows);
-    st.h2d += S.h2d; st.d2h += S.d2h; st.a_batches += S.a_batches; st.b_batches += S.b_batches;
-    S.release_keep_stream(keep);
-    t0 = t1;
-  }
-  return 0;
-}
-
-// The verdict of every range from the verdicts of the blocks: status, and the detail of the lowest-index failing range's first bad
-// block.  `fail` gets 1 for a failing range.
-void range_verdicts(const cjs_bz_index* ix, const RangePlan& P, const uint64_t* off, size_t count, const std::vector<uint8_t>& verdict,
-                    const std::vector<uint32_t>& crc_got, int32_t* status, std::vector<uint8_t>& fail) {
-  const size_t nblk = ix->e.size();
-  std::vector<size_t> next_bad(nblk + 1, nblk);                    // the first bad block at or behind b
-  for (size_t b = nblk; b-- > 0;) next_bad[b] = verdict[b] != RG_GOOD ? b : next_bad[b + 1];
-  fail.assign(count, 0);
-  bool first = true;
-  for (size_t k = 0; k < count; k++) {
-    status[k] = 0;
-    if (!P.lay_len[k]) continue;
-    const size_t b0 = P.first_block(ix, off[k]), b1 = P.first_block(ix, off[k] + P.lay_len[k] - 1), bad = next_bad[b0];
-    if (bad > b1) continue;
-    status[k] = CJS_E_DATA_ERROR; fail[k] = 1;
-    if (first) {
-      char d[96];
-      if (verdict[bad] == RG_BAD_CRC) { bad_crc_detail(d, sizeof d, crc_got[bad], ix->e[bad].crc); set_detail("%s", d); }
-      else set_detail("index does not match the stream at block %zu", bad);
-      first = false;
-    }
-  }
-}
-
-int range_check_args(const void* in, size_t n, const cjs_bz_index* idx, const uint64_t* off, const uint64_t* len, size_t count, const size_t* out_off,
-                     const size_t* out_len, const int32_t* status) {
-  if (!idx || (!in && n)) return CJS_E_INVALID_ARG;
-  if (count && (!off || !len || !out_off || !out_len || !status)) return CJS_E_INVALID_ARG;
-  if (idx->stream_bytes != n) { set_detail("the index is of a stream of %llu bytes", (unsigned long long)idx->stream_bytes); return CJS_E_INVALID_ARG; }
-  return 0;
-}
-
-void range_debug(const char* form, const cjs_bz_index* ix, const RangePlan& P, size_t count, const RangeStats& st) {
-  if (!env_debug()) return;
-  fprintf(stderr, "[cjs range] %s: %zu ranges, %llu bytes, %zu of %zu blocks touched, %u passes (%u row batches, %u inverse-BWT batches), upload %llu B, %zu slices, H2D %llu D2H %llu\n",
-          form, count, (unsigned long long)P.total, P.touched.size(), ix->e.size(), st.passes, st.a_batches, st.b_batches, (unsigned long long)st.up, st.slices,
-          (unsigned long long)st.h2d, (unsigned long long)st.d2h);
-}
-
-}  // namespace
-
-extern "C" int cjs_bzip2_index_build(const uint8_t* in, size_t n, int multistream, cjs_bz_index** idx, const cjs_opts* opts) {
-  if (!idx) return CJS_E_INVALID_ARG;
-  *idx = nullptr;
-  CJS_GUARD_BEGIN
-  long nbk = 0;
-  std::vector<cjs_bz_index_entry> e;
-  CJS_TRY(bunzip_core(in, n, multistream, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, &nbk, opts, &e));
-  e.resize((size_t)nbk);
-  return bz_index_make(e.data(), e.size(), n, multistream != 0, idx);
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-extern "C" int cjs_bzip2_read_ranges(const uint8_t* in, size_t n, const cjs_bz_index* idx, const uint64_t* off, const uint64_t* len, size_t count,
-                                     uint8_t** out, size_t* out_off, size_t* out_len, int32_t* status, const cjs_opts* opts) {
-  if (!out) return CJS_E_INVALID_ARG;
-  *out = nullptr;
-  clear_detail();
-  CJS_GUARD_BEGIN
-  CJS_TRY(range_check_args(in, n, idx, off, len, count, out_off, out_len, status));
-  RangePlan P;
-  CJS_TRY(range_plan(idx, off, len, count, P));
-  RecHost host;                                                   // (given back on every failing path)
-  CJS_TRY(host.ensure(0, (size_t)std::max<uint64_t>(P.total, 1)));
-  std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD), fail; std::vector<uint32_t> crc_got(idx->e.size(), 0);
-  RangeStats st;
-  if (!P.touched.empty()) {
-    CJS_TRY(select_device(opts));
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-    RestoreDevice restore{dev};
-    CJS_TRY(range_run(in, nullptr, idx, P, host.p, nullptr, verdict, crc_got, dev, st));
-  }
-  range_verdicts(idx, P, off, count, verdict, crc_got, status, fail);
-  size_t at = 0;                                                   // the layout behind the verdicts: a failed range takes no room
-  for (size_t k = 0; k < count; k++) {
-    out_off[k] = at; out_len[k] = fail[k] ? 0 : (size_t)P.lay_len[k];
-    if (out_len[k] && at != P.lay_off[k]) memmove(host.p + at, host.p + P.lay_off[k], out_len[k]);
-    at += out_len[k];
-  }
-  range_debug("host", idx, P, count, st);
-  *out = host.release();
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-extern "C" int cjs_bzip2_read_ranges_device(const uint8_t* d_in, size_t n, const cjs_bz_index* idx, const uint64_t* off, const uint64_t* len, size_t count,
-                                            uint8_t* d_out, size_t out_cap, size_t* out_off, size_t* out_len, int32_t* status, size_t* out_need,
-                                            const cjs_opts* opts) {
-  if (!out_need || (!d_out && out_cap)) return CJS_E_INVALID_ARG;
-  *out_need = 0;
-  clear_detail();
-  CJS_GUARD_BEGIN
-  CJS_TRY(range_check_args(d_in, n, idx, off, len, count, out_off, out_len, status));
-  RangePlan P;
-  CJS_TRY(range_plan(idx, off, len, count, P));
-  *out_need = (size_t)P.total;
-  for (size_t k = 0; k < count; k++) { out_off[k] = (size_t)P.lay_off[k]; out_len[k] = (size_t)P.lay_len[k]; status[k] = 0; }
-  if (P.total > out_cap) return CJS_E_OUTPUT_TOO_SMALL;           // (known from the index alone: nothing is launched, d_out untouched)
-  if (P.touched.empty()) return 0;
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if (!on_device(d_in, dev) || !on_device(d_out, dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
-  std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD), fail; std::vector<uint32_t> crc_got(idx->e.size(), 0);
-  RangeStats st;
-  CJS_TRY(range_run(nullptr, d_in, idx, P, nullptr, d_out, verdict, crc_got, dev, st));
-  range_verdicts(idx, P, off, count, verdict, crc_got, status, fail);
-  for (size_t k = 0; k < count; k++) if (fail[k]) out_len[k] = 0;      // (the region keeps its place)
-  range_debug("device", idx, P, count, st);
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-// ---------------------------------------------------------------- batch (Bzip2.decompressFiles)
-// The groups above with the inputs and the result in host memory: a group's inputs are staged into one host buffer and uploaded
-// as phase A uploads a single stream; phase C copies the bytes back into a result buffer of the group.  See DESIGN.md §6c.
-namespace {
-
-struct BatchPiece { uint8_t* buf; size_t size; };       // a HostPool result buffer and the bytes used in it
-
-// one group: inputs [k0, k1); every status / off (inside the group's piece) / len and detail is set
-int dec_batch_group(const uint8_t* const* in, const size_t* n, size_t k0, size_t k1, int multistream, int dev, size_t* off, size_t* len,
-                    int32_t* status, std::vector<std::string>& detail, BatchPiece* piece) {
-  piece->buf = nullptr; piece->size = 0;
-  DecJob J; DecShare S; BatchGroup G;
-  S.device = dev;
-  for (size_t k = k0; k < k1; k++) off[k] = len[k] = 0;
-  group_layout(J, S, G, k0, k1, n, status, detail, [&](size_t k) { return in[k]; },
-               [&](size_t k, int level) { return bz_max_level(in[k], n[k], level, multistream != 0); }, [](size_t, size_t) {});
-  uint8_t* host_in = (uint8_t*)HostPool::take(J.n ? J.n : 1);
-  if (!host_in) return CJS_E_OUT_OF_MEMORY;
-  struct GiveBack { uint8_t* p; ~GiveBack() { HostPool::give(p); } } give_in{host_in};
-  for (size_t k = k0; k < k1; k++) if (G.ok[k - k0]) memcpy(host_in + S.bst[k - k0], in[k], n[k]);
-  J.in = host_in;
-  uint64_t total = 0;
-  CJS_TRY(group_prepare(J, S, G, status, detail, [&](size_t k, const WalkCands& C) { return walk_chain(J, C, in[k], n[k], multistream, 0, met_nothing); }, &total));
-  const size_t nb = J.chain.size();
-  J.host = (uint8_t*)HostPool::take(total ? (size_t)total : 1);
-  if (!J.host) return CJS_E_OUT_OF_MEMORY;
-  J.crc_got.assign(nb, 0);
-  if (nb) guarded(S.rc, [&] { dec_phase_c(&J, &S); });
-  S.release();                                                 // (the stream has drained before J.host is read or given back)
-  if (S.rc) { HostPool::give(J.host); return S.rc; }
-  group_verdicts(J, G, 0, off, len, status, detail);
-  if (J.timing)
-    fprintf(stderr, "[cjs dec batch] group: %zu inputs, %zu candidates, %u row batches (phase A), %u inverse-BWT batches (phase B), %zu chain blocks, %llu bytes out\n",
-            k1 - k0, S.cands.size(), S.a_batches, S.b_batches, nb, (unsigned long long)total);
-  piece->buf = J.host; piece->size = (size_t)total;
-  return 0;
-}
-
-}  // namespace
-
-extern "C" int cjs_bzip2_decompress_batch(const uint8_t* const* in, const size_t* n, size_t count, int multistream, uint8_t** out, size_t* off,
-                                          size_t* len, int32_t* status, const cjs_opts* opts) {
-  if (!out) return CJS_E_INVALID_ARG;
-  *out = nullptr;
-  clear_detail();
-  if (count == 0) return 0;
-  if (!in || !n || !off || !len || !status) return CJS_E_INVALID_ARG;
-  for (size_t k = 0; k < count; k++) if (n[k] && !in[k]) return CJS_E_INVALID_ARG;
-  CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  int dev = 0, ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  cjs_opts one; memset(&one, 0, sizeof one);                   // (the large inputs: this device, n_devices and stats ignored)
-  one.struct_size = sizeof one; one.device = dev;
-  const size_t G = dec_group_bytes();
-  std::vector<std::string> detail(count);
-  std::vector<BatchPiece> pieces;
-  std::vector<size_t> piece_of(count);
-  struct Pieces { std::vector<BatchPiece>& v; ~Pieces() { for (auto& p : v) HostPool::give(p.buf); } } keep{pieces};
-  int rc = 0;
-  for (size_t k0 = 0; k0 < count && !rc;) {
-    if (n[k0] > G) {                                           // an input of its own: the single-stream path
-      uint8_t* o = nullptr; size_t on = 0;
-      const int r = cjs_bzip2_decompress(in[k0], n[k0], multistream, &o, &on, &one);
-      if (r == CJS_E_OUT_OF_MEMORY || r == CJS_E_NO_DEVICE || r == CJS_E_HIP || r == CJS_E_INVALID_ARG) { rc = r; break; }
-      status[k0] = r; off[k0] = 0; len[k0] = r ? 0 : on;
-      if (r) detail[k0] = cjs_last_error_detail();
-      else { pieces.push_back(BatchPiece{o, on}); piece_of[k0] = pieces.size() - 1; }
-      if (r) { piece_of[k0] = pieces.size(); pieces.push_back(BatchPiece{nullptr, 0}); }
-      k0++;
-      continue;
-    }
-    const size_t k1 = dec_group_end(n, count, k0, G);
-    BatchPiece p{nullptr, 0};
-    if ((rc = dec_batch_group(in, n, k0, k1, multistream, dev, off, len, status, detail, &p)) != 0) break;
-    pieces.push_back(p);
-    for (size_t k = k0; k < k1; k++) piece_of[k] = pieces.size() - 1;
-    k0 = k1;
-  }
-  clear_detail();
-  if (rc) return rc;
-  uint8_t* res = nullptr;
-  if (pieces.size() == 1 && pieces[0].buf) { res = pieces[0].buf; pieces[0].buf = nullptr; }      // (one group: its buffer is the result)
-  else {
-    std::vector<size_t> base(pieces.size() + 1, 0);
-    for (size_t i = 0; i < pieces.size(); i++) base[i + 1] = base[i] + pieces[i].size;
-    if (!(res = (uint8_t*)HostPool::take(base.back() ? base.back() : 1))) return CJS_E_OUT_OF_MEMORY;
-    for (size_t i = 0; i < pieces.size(); i++) if (pieces[i].size) memcpy(res + base[i], pieces[i].buf, pieces[i].size);
-    for (size_t k = 0; k < count; k++) off[k] += base[piece_of[k]];
-  }
-  *out = res;
-  for (size_t k = 0; k < count; k++) if (status[k]) { set_detail("%s", detail[k].c_str()); break; }      // the lowest-index failing input's
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-// ---------------------------------------------------------------- device-resident batch (cjs_bzip2_decompress_batch_device)
-// cjs_bzip2_decompress_batch with the inputs and the result in GPU memory: the same groups (dec_group_bytes), verdicts and layout.
-// Every group and every input above the group size (the single device path) is prepared up to phase B first -- the single
-// ones also through a CRC-only phase C, as a failed one takes no bytes -- so the layout and its size are known before anything
-// is written; then each emits into its region of d_out.  See DESIGN.md §6d.
-extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size_t* in_off, size_t count, int multistream, uint8_t* d_out, size_t out_cap,
-                                                 size_t* out_off, size_t* out_len, int32_t* status, size_t* out_need, const cjs_opts* opts) {
-  clear_detail();
-  if (count == 0) { if (out_need) *out_need = 0; return 0; }
-  if (!in_off || !out_off || !out_len || !status || !out_need || count >= 0xFFFFFFFFu) return CJS_E_INVALID_ARG;
-  for (size_t k = 0; k < count; k++) if (in_off[k + 1] < in_off[k]) return CJS_E_INVALID_ARG;
-  if ((!d_in && in_off[count] > in_off[0]) || (!d_out && out_cap)) return CJS_E_INVALID_ARG;
-  *out_need = 0;
-  CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if ((in_off[count] > in_off[0] && !on_device(d_in + in_off[0], dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;
-  DecShare H;                                                   // the header pass: its stream, pool and copy tally
-  H.device = dev;
-  std::vector<DevHdr> hd;
-  CJS_TRY(dev_headers(H, d_in, std::vector<uint64_t>(in_off, in_off + count + 1), multistream != 0, hd));
-  H.release();
-  const size_t G = dec_group_bytes();
-  std::vector<size_t> n(count);
-  for (size_t k = 0; k < count; k++) n[k] = in_off[k + 1] - in_off[k];
-  std::vector<std::string> detail(count);
-  std::vector<std::unique_ptr<DevUnit>> units;
-  std::vector<size_t> unit_base;
-  uint64_t need = 0;
-  for (size_t k0 = 0; k0 < count;) {
-    units.emplace_back(new DevUnit);
-    DevUnit& U = *units.back();
-    U.S.device = dev;
-    if (n[k0] > G) {                                            // an input of its own: the single device path
-      U.G.k0 = k0; U.G.k1 = k0 + 1;
-      clear_detail();
-      int r = dev_single_prepare(U, d_in + in_off[k0], n[k0], multistream, hd[k0]);
-      if (!r) r = dev_single_emit(U, nullptr);                  // (the verdict: a failed input takes no bytes)
-      if (r == CJS_E_OUT_OF_MEMORY || r == CJS_E_NO_DEVICE || r == CJS_E_HIP || r == CJS_E_INVALID_ARG) return r;
-      status[k0] = r;
-      if (r) { detail[k0] = cjs_last_error_detail(); U.S.release(); }
-      unit_base.push_back((size_t)need);
-      out_off[k0] = (size_t)need; out_len[k0] = r ? 0 : (size_t)U.total;
-      need += r ? 0 : U.total;
-      k0++;
-      continue;
-    }
-    const size_t k1 = dec_group_end(n.data(), count, k0, G);
-    CJS_TRY(dev_group_prepare(U, d_in, in_off, n.data(), k0, k1, multistream, hd, status, detail));
-    unit_base.push_back((size_t)need);
-    need += U.total;
-    k0 = k1;
-  }
-  clear_detail();
-  *out_need = (size_t)need;
-  uint64_t h2d = H.h2d, d2h = H.d2h, cands = 0, blocks = 0;
-  auto tally = [&]() {
-    for (auto& u : units) { h2d += u->S.h2d; d2h += u->S.d2h; cands += u->S.cands.size(); blocks += u->J.chain.size(); }
-    if (env_debug())
-      fprintf(stderr, "[cjs dec dev] batch: %zu inputs, %zu units, %llu bytes out, H2D %llu D2H %llu candidates %llu blocks %llu\n", count, units.size(),
-              (unsigned long long)need, (unsigned long long)h2d, (unsigned long long)d2h, (unsigned long long)cands, (unsigned long long)blocks);
-  };
-  if (need > out_cap) { tally(); return CJS_E_OUTPUT_TOO_SMALL; }      // (d_out untouched)
-  for (size_t u = 0; u < units.size(); u++) {
-    DevUnit& U = *units[u];
-    if (U.J.batch) CJS_TRY(dev_group_emit(U, d_out + unit_base[u], unit_base[u], out_off, out_len, status, detail));
-    else if (!status[U.G.k0] && dev_single_emit(U, d_out + unit_base[u]) != 0) return CJS_E_HIP;      // (its verdict was 0 a moment ago)
-    U.S.release();
-  }
-  tally();
-  clear_detail();
-  for (size_t k = 0; k < count; k++) if (status[k]) { set_detail("%s", detail[k].c_str()); break; }      // the lowest-index failing input's
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-// ---------------------------------------------------------------- streaming decode (cjs_bzip2_dec_*)
-// The phases above over a sliding window of the stream.  The decoder keeps the stream bytes from the carry point on (host copy;
-// uploaded per step at their absolute byte offset, so the dword phase holds), the walk state (WalkState: bit position, folded
-// stream CRC, the member's block size) and one output buffer of out_bytes.  A step: phase A over the window with rows for the
-// first R block candidates at the walk position; bz_walk resumed from the kept state, stopping in front of whatever the bytes
-// still to come could change; phase B over the chain; the chain cut to the output budget (the walk state rolled back to the first
-// block not emitted); phase C into the device output buffer and one D2H.  All device scratch comes from the decoder's DecArena.
-// Synchronous: no worker thread.  See DESIGN.md §6f.
-namespace {
-constexpr size_t DEC_DEFAULT_CHUNK = (size_t)64 << 20, DEC_DEFAULT_OUT = (size_t)256 << 20;      // DESIGN.md §6f (placeholders, UNMEASURED)
-constexpr size_t DEC_MIN_CHUNK = (size_t)64 << 10, DEC_MAX_CHUNK = (size_t)1 << 30;
-const char* const WALK_WHY[] = {"runs", "end of stream", "block magic not all here", "stream crc not all here", "member header not all here", "candidate without a row",
-                                "block not all here", "error too near the end", "output budget"};
-struct WinBytes {                        // the window by absolute stream byte
-  const uint8_t* p; uint64_t off;
-  uint8_t operator[](uint64_t i) const { return p[i - off]; }
-};
-}  // namespace
-
-struct cjs_bz_dec {
-  int multistream = 0, device = -1;
-  size_t chunk = 0, out_req = 0;
-  bool eager = false, debug = false;
-  int rc = 0; char detail[192] = {0};      // first failure: every later call returns it
-  // input window: stream bytes [win_off, win_off + win_len); the first `seen` of them have been through a step
-  uint8_t* win = nullptr; size_t win_cap = 0, win_len = 0, seen = 0; uint64_t win_off = 0, written = 0;
-  bool win_pinned = false, finished = false, header_ok = false, ended = false, dev_ready = false;
-  int level = 0;                           // of the header; rows and blocks are sized for L = 9 with multistream
-  uint32_t tt_stride = 0, rows = 0;
-  WalkState W;
-  // output of the last step: held - held_pos bytes still to be read; then the pending verdict
-  size_t out_cap = 0, held = 0, held_pos = 0;
-  Pinned<uint8_t> h_out; DevMem<uint8_t> d_out;
-  int pend_rc = 0; char pend_detail[192] = {0};
-  DecArena arena; Stream s;
-  uint32_t steps = 0;
-  int fail(int code, const char* text) {
-    if (!rc) { rc = code; snprintf(detail, sizeof detail, "%s", text ? text : ""); }
-    clear_detail();
-    if (detail[0]) set_detail("%s", detail);
-    return rc;
-  }
-  ~cjs_bz_dec() {
-    int cur = 0;
-    if (dev_ready && hipGetDevice(&cur) == hipSuccess) {
-      RestoreDevice restore{cur};          // the caller's device stays current
-      if (hipSetDevice(device) == hipSuccess) {
-        if (s) (void)hipStreamSynchronize(s);
-        if (win_pinned) (void)hipHostUnregister(win);
-        s.reset(); h_out.reset(); d_out.reset(); arena.release();
-      }
-    }
-    free(win);
-  }
-};
-
-namespace {
-
-// _start_bunzip (:1408-1427) on the first four bytes: no device
-int dec_header(cjs_bz_dec* d) {
-  const char* why = nullptr;
-  if (bz_header_check(d->win, d->written, &d->level, &why)) return d->fail(CJS_E_NOT_BZIP_DATA, why);
-  const uint32_t L = d->multistream ? 9u : (uint32_t)d->level;      // later members cannot be seen ahead
-  d->tt_stride = 100000u * L;
-  d->out_cap = std::max<size_t>(d->out_req ? d->out_req : DEC_DEFAULT_OUT, (size_t)52 * d->tt_stride);
-  d->rows = (uint32_t)std::min<size_t>(65535, std::max<size_t>(1, d->out_cap / d->tt_stride));
-  d->W = WalkState{};
-  d->W.dbuf_size = 100000u * (uint32_t)d->level;
-  d->header_ok = true;
-  return 0;
-}
-
-int dec_device_init(cjs_bz_dec* d) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CJS_E_NO_DEVICE; }
-  if (d->device >= ndev) return CJS_E_INVALID_ARG;
-  if (d->device < 0 && hipGetDevice(&d->device) != hipSuccess) return CJS_E_NO_DEVICE;
-  CJS_HIP_TRY(hipSetDevice(d->device));
-  d->dev_ready = true;
-  CJS_HIP_TRY(hipStreamCreate(d->s.put()));
-  if (hipHostRegister(d->win, d->win_cap, hipHostRegisterDefault) == hipSuccess) d->win_pinned = true; else (void)hipGetLastError();
-  CJS_HIP_TRY(hipHostMalloc((void**)d->h_out.put(), d->out_cap));
-  CJS_TRY(d->d_out.alloc(d->out_cap + 256));
-  // rows ~10 B and inverse BWT ~24 B per byte of rows x block size, the window twice (upload + candidates)
-  return d->arena.init((size_t)28 * d->rows * ((size_t)d->tt_stride + 4096) + 2 * d->win_cap + ((size_t)16 << 20));
-}
-
-int dec_step(cjs_bz_dec* d) {
-  int cur = 0;
-  if (!d->dev_ready) {
-    const bool had = hipGetDevice(&cur) == hipSuccess;
-    const int rc = dec_device_init(d);
-    if (rc) { if (had) (void)hipSetDevice(cur); return rc; }
-    if (had) (void)hipSetDevice(cur);
-  }
-  if (hipGetDevice(&cur) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{cur};
-  CJS_HIP_TRY(hipSetDevice(d->device));
-  const bool final = d->finished, was_full = d->win_len == d->win_cap;
-  const uint32_t spills0 = d->arena.spills;
-  const uint64_t n = d->win_off + d->win_len, pos0 = d->W.pos;
-  const size_t len0 = d->win_len;
-  DecJob J; J.n = (size_t)n; J.mode = 0; J.timing = env_debug(); J.tt_stride = d->tt_stride; J.batch = true;
-  DecShare S; S.device = d->device; S.arena = &d->arena; S.s = std::move(d->s);
-  struct Back { cjs_bz_dec* d; DecShare& S; ~Back() { S.release_keep_stream(d->s); } } back{d, S};      // on every path out
-  S.lo = S.up_lo = d->win_off; S.hi = S.up_hi = n; S.row_limit = d->rows; S.row_from = d->W.pos;
-  J.upload = [d](DecShare* sh, uint8_t* dst) {
-    if (d->win_len && hipMemcpyAsync(dst, d->win, d->win_len, hipMemcpyHostToDevice, sh->s) != hipSuccess) return (int)CJS_E_HIP;
-    sh->h2d += d->win_len;
-    return 0;
-  };
-  guarded(S.rc, [&] { dec_phase_a(&J, &S); });
-  if (S.rc) return S.rc;
-  // ---- the walk, resumed
-  WalkState& W = d->W;
-  W.partial = !final; W.cut_bit = S.cut_bit; W.extent = dec_extent(d->tt_stride); W.stop = WALK_RUNS;
-  std::vector<WalkState> before;           // the state in front of each chain block
-  clear_detail();
-  int wrc = walk_chain(J, WalkCands(&S, 1), WinBytes{d->win, d->win_off}, (size_t)n, d->multistream, 0,
-                       [&](long ci, uint64_t) { if (S.cands[(size_t)ci].kind == 0) before.push_back(W); }, &W);
-  char wdetail[192];
-  snprintf(wdetail, sizeof wdetail, "%s", cjs_last_error_detail());
-  clear_detail();
-  // ---- phase B over the chain, then the cut to the output budget
-  size_t nb = J.chain.size();
-  const size_t walked = nb;
-  if (nb) {
-    S.c0 = 0; S.c1 = nb;
-    guarded(S.rc, [&] { dec_phase_b(&J, &S); });
-    if (S.rc) return S.rc;
-  }
-  chain_out_offsets(J);
-  if (nb) {
-    if (J.out_off[1] > d->out_cap) return CJS_E_UNSUPPORTED;      // cannot happen: out_cap >= a block's largest expansion
-    size_t k = 1;
-    while (k < nb && J.out_off[k + 1] <= d->out_cap) k++;
-    if (k < nb) {                          // block k and what the walk met behind it: the next step's
-      const WalkState& b = before[k];
-      W.pos = b.pos; W.crc = b.crc; W.dbuf_size = b.dbuf_size; W.stop = WALK_OUT_BUDGET;
-      wrc = 0;
-      J.chain.resize(k); J.out_off.resize(k + 1); S.c1 = nb = k;
-    }
-    // ---- phase C: a CRC verdict per block; the first bad block in chain order comes before the walk's error
-    J.dev_out = d->d_out; J.host = nullptr; J.crc_got.assign(nb, 0);
-    S.rc = 0;
-    guarded(S.rc, [&] { dec_phase_c(&J, &S); });
-    if (S.rc) return S.rc;
-  }
-  size_t bad = 0;
-  while (bad < nb && J.crc_got[bad] == J.chain[bad].crc) bad++;
-  const size_t deliver = (size_t)J.out_off[bad];
-  if (deliver) { CJS_HIP_TRY(hipMemcpyAsync(d->h_out, d->d_out, deliver, hipMemcpyDeviceToHost, S.s)); CJS_HIP_TRY(hipStreamSynchronize(S.s)); S.d2h += deliver; }
-  d->held = deliver; d->held_pos = 0;
-  if (bad < nb) {                          // Bad block CRC (:1756-1761): nothing of the block is delivered
-    d->pend_rc = CJS_E_DATA_ERROR;
-    bad_crc_detail(d->pend_detail, sizeof d->pend_detail, J.crc_got[bad], J.chain[bad].crc);
-  } else if (wrc) {
-    d->pend_rc = wrc;
-    snprintf(d->pend_detail, sizeof d->pend_detail, "%s", wdetail);
-  } else if (W.stop == WALK_ENDED) d->ended = true;
-  // ---- the carry: the window from the walk position's byte on
-  if (!d->pend_rc) {
-    const uint64_t keep_from = d->ended ? n : std::min<uint64_t>(W.pos >> 3, n);
-    const size_t gone = (size_t)(keep_from - d->win_off);
-    if (gone) memmove(d->win, d->win + gone, d->win_len - gone);
-    d->win_off = keep_from; d->win_len -= gone;
-  }
-  d->seen = d->win_len;
-  if (d->debug)
-    fprintf(stderr, "[cjs dec step] %u: window %zu B at byte %llu, carry %zu B, candidates %u rows %u, blocks walked %zu emitted %zu, %zu B out, walk stopped: %s%s%s\n",
-            d->steps, len0, (unsigned long long)(n - len0), d->win_len, S.ncand_seen, S.nrows_given(), walked, std::min(bad, nb), deliver,
-            d->pend_rc ? "error" : WALK_WHY[W.stop], final ? " (final)" : "", d->arena.spills != spills0 ? " [arena spilled]" : "");
-  d->steps++;
-  // (cannot happen: a full window holds a whole block behind the walk position, and the final steps end or emit)
-  if (!d->pend_rc && !d->ended && (final ? W.pos == pos0 : was_full && d->win_len == d->win_cap)) return CJS_E_UNSUPPORTED;
-  return 0;
-}
-
-// A full window always has fresh bytes: the step that last ran on a full window either moved the walk position, and with it the
-// carry point (a block, an end-of-stream record or a member header: whole bytes each), so the window was no longer full and only
-// a _write can have filled it again; or it failed the decoder (CJS_E_UNSUPPORTED in dec_step).  So a _write that took nothing is
-// always followed by a step.
-bool dec_step_due(const cjs_bz_dec* d) {
-  if (d->ended || d->pend_rc) return false;
-  if (d->finished) return true;
-  const size_t fresh = d->win_len - d->seen;
-  return d->eager ? fresh > 0 : (fresh >= d->chunk || (d->win_len == d->win_cap && fresh > 0));
-}
-
-}  // namespace
-
-extern "C" int cjs_bzip2_dec_create(cjs_bz_dec** out, int multistream, size_t chunk_bytes, size_t out_bytes, const cjs_opts* opts) {
-  if (!out) return CJS_E_INVALID_ARG;
-  *out = nullptr;
-  CJS_GUARD_BEGIN
-  cjs_bz_dec* d = new cjs_bz_dec();
-  d->multistream = multistream ? 1 : 0;
-  if (!chunk_bytes) {                      // the default; CJS_DEC_CHUNK_BYTES replaces it (callers without a chunk argument: the JS fronts, cli.js)
-    const char* env = getenv("CJS_DEC_CHUNK_BYTES");
-    chunk_bytes = env ? (size_t)strtoull(env, nullptr, 10) : 0;
-    if (!chunk_bytes) chunk_bytes = DEC_DEFAULT_CHUNK;
-  }
-  d->chunk = std::min(std::max(chunk_bytes, DEC_MIN_CHUNK), DEC_MAX_CHUNK);
-  d->out_req = out_bytes;
-  d->device = Opts(opts).device;
-  const char* eager = getenv("CJS_DEC_STREAM_EAGER");
-  d->eager = eager && eager[0] == '1';
-  d->debug = getenv("CJS_DEBUG") != nullptr;
-  d->win_cap = d->chunk + (size_t)dec_extent(900000u);
-  *out = d;
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-extern "C" int cjs_bzip2_dec_write(cjs_bz_dec* d, const uint8_t* in, size_t n, size_t* taken) {
-  if (taken) *taken = 0;
-  if (!d) return CJS_E_INVALID_ARG;
-  if (d->rc) return d->fail(d->rc, nullptr);
-  if (!taken || (!in && n) || d->finished) return d->fail(CJS_E_INVALID_ARG, nullptr);
-  if (d->ended || d->pend_rc) { *taken = n; return 0; }      // the end has been decided: the reference never reads these bytes
-  if (!n) return 0;
-  if (!d->win && !(d->win = (uint8_t*)malloc(d->win_cap))) return d->fail(CJS_E_OUT_OF_MEMORY, nullptr);
-  const size_t take = std::min(n, d->win_cap - d->win_len);
-  memcpy(d->win + d->win_len, in, take);
-  d->win_len += take; d->written += take;
-  *taken = take;
-  return 0;
-}
-
-extern "C" int cjs_bzip2_dec_finish(cjs_bz_dec* d) {
-  if (!d) return CJS_E_INVALID_ARG;
-  if (d->rc) return d->fail(d->rc, nullptr);
-  d->finished = true;
-  return 0;
-}
-
-extern "C" int cjs_bzip2_dec_read(cjs_bz_dec* d, uint8_t* out, size_t cap, size_t* got) {
-  if (got) *got = 0;
-  if (!d) return CJS_E_INVALID_ARG;
-  if (d->rc) return d->fail(d->rc, nullptr);
-  if (!got || (!out && cap)) return d->fail(CJS_E_INVALID_ARG, nullptr);
-  CJS_GUARD_BEGIN
-  for (;;) {
-    if (d->held_pos < d->held) {
-      const size_t take = std::min(cap, d->held - d->held_pos);
-      if (take) memcpy(out, d->h_out.p + d->held_pos, take);
-      d->held_pos += take;
-      *got = take;
-      return 0;
-    }
-    if (d->pend_rc) return d->fail(d->pend_rc, d->pend_detail);      // every byte in front of it has been read
-    if (d->ended) return 0;
-    if (!d->header_ok) {
-      if (d->written < 4 && !d->finished) return 0;
-      CJS_TRY(dec_header(d));
-    }
-    if (!dec_step_due(d)) return 0;
-    if (!d->win && !(d->win = (uint8_t*)malloc(d->win_cap))) return d->fail(CJS_E_OUT_OF_MEMORY, nullptr);
-    const int rc = dec_step(d);
-    if (rc) return d->fail(rc, cjs_last_error_detail());
-  }
-  CJS_GUARD_END(d->fail(CJS_E_OUT_OF_MEMORY, nullptr), d->fail(CJS_E_HIP, nullptr))
-}
-
-extern "C" int cjs_bzip2_dec_done(const cjs_bz_dec* d) { return d && !d->rc && d->ended && d->held_pos == d->held ? 1 : 0; }
-
-extern "C" void cjs_bzip2_dec_destroy(cjs_bz_dec* d) { delete d; }

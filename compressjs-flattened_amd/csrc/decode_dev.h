@@ -1,5 +1,6 @@
-// decode_dev.h -- device-side pieces of Bzip2 decode shared by decode.hip (cjs_bzip2_decompress) and batch_dec.hip
-// (cjs_bzip2_decompress_batch): candidate and block records, the bit readers, the code tables and the chain helpers of stage 2.
+// decode_dev.h -- device-side pieces of Bzip2 decode shared by decode.hip (the single-stream kernels) and batch_dec.hip (their
+// batch forms): candidate and block records, the bit readers, the code tables and the chain helpers of stage 2; and the launch
+// functions of batch_dec.hip and dec_device.hip.  The host side of the engine is dec_engine.h.
 #pragma once
 #include "cjs_internal.h"
 #include "prims.hpp"
@@ -292,13 +293,5 @@ void launch_dev_eos_bytes(hipStream_t s, const uint8_t* d_in, const uint64_t* d_
 struct GatherPiece { uint64_t src; uint32_t dst, len; };
 constexpr size_t GATHER_PIECE = 65536;                 // bytes per piece of an input (a multiple of 4)
 void launch_dev_gather(hipStream_t s, const uint8_t* d_in, const GatherPiece* d_pc, uint32_t npieces, uint8_t* dst);
-
-// range.hip: the indexed range reads.  A slice = len bytes (1 .. SLICE_TASK) from device address src to device address dst, any
-// alignment; n slices in launches of SLICE_SLAB.  launch_cand_magic: ok[c] = the block magic stands at bit bits[c] of d_in (n bytes).
-struct Slice { uint64_t src, dst, len; };
-constexpr uint64_t SLICE_TASK = 65536;                 // (a multiple of 16)
-constexpr size_t SLICE_SLAB = 65535;
-void launch_slices(hipStream_t s, const Slice* d_sl, size_t n);
-void launch_cand_magic(hipStream_t s, const uint8_t* d_in, uint64_t n, const uint64_t* d_bits, uint32_t nc, uint32_t* d_ok);
 
 }  // namespace cjs

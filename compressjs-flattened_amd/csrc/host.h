@@ -72,6 +72,15 @@ struct DevBuf : Owner<void*, PoolGive> {
   explicit DevBuf(size_t bytes) { p = DevPool::take(bytes); }
 };
 
+// One HostPool buffer (or malloc'd memory: reset(p) adopts it), given back when its owner goes; release() hands it to the caller.
+// Where a share's stream copies into or out of it, it is declared in front of the share: given back once that stream has drained.
+struct HostGive { void operator()(void* p) const { HostPool::give(p); } };
+struct HostBuf : Owner<uint8_t*, HostGive> {
+  HostBuf() = default;
+  explicit HostBuf(size_t bytes) { p = (uint8_t*)HostPool::take(bytes); }
+  uint8_t* release() { uint8_t* q = p; p = nullptr; return q; }
+};
+
 // Device d made current at scope exit (the caller's device, restored on every path out).
 struct RestoreDevice {
   int d;

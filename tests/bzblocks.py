@@ -9,7 +9,7 @@ stream with the oracle's encoder stages (its cyclic BWT, MTF/RLE2 and block pack
 """
 import numpy as np
 
-SPL = 64                      # the decoder's splitter spacing (csrc/decode.hip)
+SPL = 64                      # the decoder's splitter spacing (csrc/decode_dev.h)
 TILE = 16384                  # bytes of w per RLE1 tile (UR_TILE)
 
 

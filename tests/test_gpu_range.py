@@ -287,6 +287,89 @@ def test_several_passes_give_the_single_pass_result(L, fx):
             assert got[name + "/" + cap] == [_digest(host), _digest(dev)], (name, cap)
 
 
+def _flipped_bit_case(f):
+    """F1 with a bit of block 5 flipped (test_a_flipped_bit...): -> (stream, ranges)"""
+    e = f["entries"]
+    off = np.concatenate([[0], np.cumsum([x[2] for x in e])])
+    ranges = [(10, 100), (int(off[4]) + 5, 99981 - 5), (int(off[6]) - 1, 2), (int(off[5]), 1), (int(off[4]) + 99000, 2000), (int(off[6]), 50), (0, f["plain"].size),
+              (int(off[5]) + 500, 0), (int(off[9]), 10 ** 6)]
+    damaged = f["stream"].copy()
+    damaged[(e[5][0] + e[5][1]) // 16] ^= 0x04
+    return damaged, ranges
+
+
+def _wrong_crc_case(L, f):
+    """F1 with the stored CRC of block 5 overwritten in the stream and in the index (test_a_wrong_stored_crc...):
+    -> (stream, handle, ranges, the detail)"""
+    e = [list(x) for x in f["entries"]]
+    off = np.concatenate([[0], np.cumsum([x[2] for x in e])])
+    real = e[5][3]
+    e[5][3] = real ^ 0x00010000
+    stream = f["stream"].copy()
+    rg.set_bits(stream, e[5][0] + 48, 32, e[5][3])
+    rc, h = rg.create(L, [tuple(x) for x in e], stream.size, 0)
+    assert rc == 0, rg.detail(L)
+    ranges = [(10, 100), (int(off[4]) + 5, int(off[6] - off[4])), (int(off[6]), 50), (0, f["plain"].size), (int(off[2]) + 9, 1), (int(off[5]), 1)]
+    return stream, h, ranges, "Bad block CRC (got %x expected %x)" % (real, e[5][3])
+
+
+def _batch_runs(L, name, f):
+    """The calls of test_several_batches on fixture `name`: the full range list; F1: block 5 -- the second block of the third
+    inverse-BWT batch when a batch holds two -- with a flipped bit and with a wrong stored CRC.  -> case -> [host, device]"""
+    ranges = rg.range_list([x[2] for x in f["entries"]])
+    res = {"all": rg.both_forms(L, f["stream"], f["h"], ranges)}
+    if name == "F1":
+        damaged, ranges = _flipped_bit_case(f)
+        res["bit"] = rg.both_forms(L, damaged, f["h"], ranges)
+        stream, h, ranges, detail = _wrong_crc_case(L, f)
+        res["crc"] = rg.both_forms(L, stream, h, ranges)
+        L.cjs_bzip2_index_destroy(h)
+        assert res["crc"][0][4] == res["crc"][1][4] == detail
+    return res
+
+
+def child_batches(name, elems):
+    """(the child of test_several_batches) fixture `name` with at most `elems` BWT bytes to an inverse-BWT batch: the digests of
+    _batch_runs; the [cjs range] lines go to stderr"""
+    os.environ["CJS_DEC_BATCH_ELEMS"] = elems               # (read once, at the first batch of the process)
+    os.environ["CJS_DEBUG"] = "1"
+    import torch  # noqa: F401  (one HIP runtime per process: torch's copy is loaded before the library)
+    import support
+    L, oracle = rg.bind(), support.Oracle()
+    stream, plain, multi, members = rg.fixture(name, oracle)
+    rc, h = rg.build(L, stream, multi)
+    assert rc == 0
+    f = dict(stream=stream, plain=plain, h=h, entries=rg.entries(L, h))
+    print(json.dumps({k: [_digest(v[0]), _digest(v[1])] for k, v in _batch_runs(L, name, f).items()}))
+
+
+@pytest.mark.parametrize("name,elems", [("F1", "250000"), ("F2", "1000")])
+def test_several_batches_in_a_pass_give_the_same(L, fx, name, elems):
+    """Several inverse-BWT batches inside one pass (CJS_DEC_BATCH_ELEMS shrunk; F1: 10 blocks of <= 100,000 BWT bytes, two to a
+    batch): bytes, offsets, statuses and detail of both forms as in this process, also with a bad block in a later batch."""
+    import re
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join(sys.path))
+    code = "import test_gpu_range as t; t.child_batches(%r, %r)" % (name, elems)
+    run = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-c", code], capture_output=True, text=True, env=env,
+                         cwd=os.path.dirname(os.path.abspath(__file__)))
+    assert run.returncode == 0, run.stderr[-3000:]
+    got = json.loads(run.stdout.strip().splitlines()[-1])
+    f = fx[name]
+    here = _batch_runs(L, name, f)
+    _check(here["all"][0], rg.range_list([x[2] for x in f["entries"]]), f["plain"], name)
+    assert sorted(got) == sorted(here)
+    for case, (host, dev) in here.items():
+        assert got[case] == [_digest(host), _digest(dev)], (name, case)
+    if name == "F1":                                        # not vacuous: the full list went through >= 4 batches in one pass, in both forms
+        nranges = len(rg.range_list([x[2] for x in f["entries"]]))
+        lines = re.findall(r"\[cjs range\] (host|device): (\d+) ranges, .*? (\d+) passes \((\d+) row batches, (\d+) inverse-BWT batches\)", run.stderr)
+        full = [(form, int(p), int(b)) for form, n, p, a, b in lines if int(n) == nranges]
+        assert sorted(x[0] for x in full) == ["device", "host"], lines
+        for form, passes, batches in full:
+            assert passes == 1 and batches >= 4, (form, passes, batches)
+        assert len(lines) == 6 and all(int(b) > int(p) for form, n, p, a, b in lines), lines
+
+
 def test_python_front(fx):
     import importlib
     import torch
