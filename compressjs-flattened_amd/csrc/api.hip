@@ -1,8 +1,8 @@
-// api.hip — C ABI of libcjs_hip.so (include/cjs_hip.h): contexts, host-buffer entry points,
-// stage-level entry points.  No CPU fallback: without a HIP device every call fails loudly.
+// api.hip — what every entry point of libcjs_hip.so (include/cjs_hip.h) shares: the error detail, the device and pinned-host
+// buffer pools, the per-device cache table and what a call reads of cjs_opts.  No CPU fallback: without a HIP device every call
+// fails loudly.
 #include "cjs_internal.h"
 #include "host.h"
-#include "rle1.h"
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -194,69 +194,3 @@ static DevCache g_cache[MAX_DEVICES][CACHE_SLOTS];      // per-device context ca
 DevCache& dev_cache(int device, int slot) { return g_cache[device][slot]; }
 
 }  // namespace cjs
-
-extern "C" int cjs_stage_bwt(const uint8_t* in, size_t n, int block_len, int cyclic, uint8_t* out, int32_t* pidx, const cjs_opts* opts) {
-  CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  if (n == 0) return 0;
-  if (block_len <= 0) return CJS_E_INVALID_ARG;
-  const uint32_t stride = (uint32_t)block_len;
-  const uint32_t nb = (uint32_t)((n + stride - 1) / stride);
-  const uint32_t n_last = (uint32_t)(n - (size_t)(nb - 1) * stride);
-  Arena arena;
-  CJS_TRY(arena.init(BwtWork::bytes_needed(n) + 2 * ((n + 511) & ~(size_t)255) + 4 * (size_t)nb + 8192));
-  BwtWork w;
-  CJS_TRY(w.carve(arena, n));
-  uint8_t* d_T = arena.take<uint8_t>(n);
-  uint8_t* d_U = arena.take<uint8_t>(n);
-  uint32_t* d_p = arena.take<uint32_t>(nb);
-  if (!d_T || !d_U || !d_p) return CJS_E_OUT_OF_MEMORY;
-  Stream s;
-  CJS_HIP_TRY(hipStreamCreate(s.put()));
-  CJS_HIP_TRY(hipMemcpyAsync(d_T, in, n, hipMemcpyHostToDevice, s));
-  CJS_TRY(bwt_run(s, w, d_T, nb, stride, n_last, cyclic != 0, d_U, d_p, Opts(opts).stats));
-  CJS_HIP_TRY(hipMemcpyAsync(out, d_U, n, hipMemcpyDeviceToHost, s));
-  CJS_HIP_TRY(hipMemcpyAsync(pidx, d_p, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
-  CJS_HIP_TRY(hipStreamSynchronize(s));
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}
-
-extern "C" int cjs_stage_rle1(const uint8_t* in, size_t n, int level, uint8_t* blocks, size_t blocks_cap,
-                              uint32_t* block_len, uint32_t* block_crc, uint64_t* block_start, long cap_blocks, long* nblocks,
-                              const cjs_opts* opts) {
-  CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;
-  const uint32_t cap = (uint32_t)level * 100000u - 19u;
-  *nblocks = 0;
-  if (n == 0) return 0;
-  Arena arena;
-  const size_t maxb = Rle1Work::max_blocks_for(n, cap);
-  CJS_TRY(arena.init(Rle1Work::bytes_needed(n, cap) + n + maxb * cap + 65536));
-  Rle1Work w;
-  CJS_TRY(w.carve(arena, n, cap));
-  uint8_t* d_in = arena.take<uint8_t>(n);
-  uint8_t* d_blocks = arena.take<uint8_t>(maxb * cap);
-  if (!d_in || !d_blocks) return CJS_E_OUT_OF_MEMORY;
-  Stream s;
-  CJS_HIP_TRY(hipStreamCreate(s.put()));
-  CJS_HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s));
-  uint32_t nb = 0;
-  const int rc = rle1_run(s, w, d_in, n, &nb);
-  *nblocks = (long)nb;
-  CJS_TRY(rc);
-  CJS_TRY(rle1_finish(s, w, d_in, n, 0, nb, d_blocks));
-  CJS_HIP_TRY(hipStreamSynchronize(s));
-  if ((long)nb > cap_blocks || (size_t)nb * cap > blocks_cap) return CJS_E_OUTPUT_TOO_SMALL;
-  if (nb) {
-    std::vector<RleBlock> hb(nb);
-    CJS_HIP_TRY(hipMemcpy(hb.data(), w.blocks, sizeof(RleBlock) * nb, hipMemcpyDeviceToHost));
-    CJS_HIP_TRY(hipMemcpy(block_len, w.block_len, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    CJS_HIP_TRY(hipMemcpy(block_crc, w.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    CJS_HIP_TRY(hipMemcpy(blocks, d_blocks, (size_t)nb * cap, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < nb; k++) block_start[k] = hb[k].s;
-  }
-  return 0;
-  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
-}

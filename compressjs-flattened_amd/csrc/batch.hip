@@ -90,25 +90,18 @@ __global__ __launch_bounds__(256) void batch_asm_frame(const AsmStream* __restri
   if (i >= n) return;
   const AsmStream t = tab[i];
   atomicOr(&out32[t.off >> 2], __builtin_bswap32(0x425a6830u + (uint32_t)level));
-  uint64_t bit = t.end_bit;
-  const uint64_t vals[2] = {0x177245385090ull, (uint64_t)t.crc};
-  const uint32_t nbs[2] = {48, 32};
-  for (int q = 0; q < 2; q++) {
-    uint32_t left = nbs[q];
-    while (left) {
-      const uint32_t o = (uint32_t)(bit & 31), room = 32 - o, take = left < room ? left : room;
-      const uint32_t chunk = (uint32_t)((vals[q] >> (left - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
-      atomicOr(&out32[bit >> 5], __builtin_bswap32(chunk << (room - take)));
-      left -= take; bit += take;
-    }
-  }
+  put_trailer_words(out32, t.end_bit, t.crc);
 }
 
 // One sub-batch: blocks it[0..nb) in slots of `stride`, through every stage in one pass.  framed: every block is a stream of its
-// own (into the staging buffer), else a bare bit string (into the scratch buffer), both from byte `base` on.  Per block: byte
-// offset, byte length, bit length, CRC.
+// own (into the staging buffer), else a bare bit string (into the scratch buffer), both from byte `base` on.  res[at + j]: block j.
+struct BlockOuts {                   // per block: byte offset, byte length, bit length, CRC
+  std::vector<uint64_t> so;
+  std::vector<uint32_t> sl, bits, crc;
+  void resize(size_t n) { so.resize(n); sl.resize(n); bits.resize(n); crc.resize(n); }
+};
 int run_sub(cjs_ctx* c, const uint8_t* d_in, const BItem* it, uint32_t nb, uint32_t stride, size_t segs, int level, bool framed, uint64_t base,
-            std::vector<uint64_t>& so, std::vector<uint32_t>& sl, std::vector<uint32_t>& bits, std::vector<uint32_t>& crc, uint64_t* bytes) {
+            BlockOuts& res, size_t at, uint64_t* bytes) {
   BatchWork& b = *c->batch;
   hipStream_t s = c->stream;
   Arena& a = b.arena;
@@ -139,7 +132,7 @@ int run_sub(cjs_ctx* c, const uint8_t* d_in, const BItem* it, uint32_t nb, uint3
   CJS_TRY(crc_ranges(s, d_in, d_rb, d_nb, nb, (uint32_t)segs, d_seg, d_crc));
   CJS_TRY(bwt_run_var(s, b.bwt, d_blocks, nb, stride, d_blen, d_U, d_pidx));
   CJS_TRY(mtf_run(s, b.mtf, d_U, nb, d_blen));
-  CJS_TRY(huff_tables_run(s, b.huff, nb, b.mtf.b.A, b.mtf.b.a_stride, b.mtf.b.npos, b.mtf.b.asz, b.mtf.b.freq, b.mtf.b.alist));
+  CJS_TRY(huff_tables_run(s, b.huff, nb, b.mtf.rows()));
   CJS_TRY(huff_batch_offsets_run(s, b.huff, nb, base, framed ? 1 : 0, d_soff, d_slen));
   CJS_HIP_TRY(hipMemcpyAsync(b.h_sc, b.huff.scalars, 8, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipStreamSynchronize(s));                  // (the output buffer may have to grow before the streams are written)
@@ -148,13 +141,12 @@ int run_sub(cjs_ctx* c, const uint8_t* d_in, const BItem* it, uint32_t nb, uint3
   size_t& cap = framed ? b.stage_cap : b.scratch_cap;
   CJS_TRY(DevCache::grow(buf, cap, base + total + 16, true, s));
   CJS_HIP_TRY(hipMemsetAsync(buf + base, 0, total + 16, s));
-  CJS_TRY(huff_batch_pack_run(s, b.huff, nb, level, framed ? 1 : 0, b.mtf.b.A, b.mtf.b.a_stride, b.mtf.b.npos, b.mtf.b.asz, b.mtf.b.alist,
-                              d_crc, d_pidx, d_soff, (uint32_t*)buf.p));
-  so.resize(nb); sl.resize(nb); bits.resize(nb); crc.resize(nb);
-  CJS_HIP_TRY(hipMemcpyAsync(so.data(), d_soff, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
-  CJS_HIP_TRY(hipMemcpyAsync(sl.data(), d_slen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
-  CJS_HIP_TRY(hipMemcpyAsync(bits.data(), b.huff.b.bitlen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
-  CJS_HIP_TRY(hipMemcpyAsync(crc.data(), d_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  PackJob job{nb, 0, nb, 0, level, framed, framed, d_crc, d_pidx, (uint32_t*)buf.p, 0};
+  CJS_TRY(huff_batch_pack_run(s, b.huff, b.mtf.rows(), job, d_soff));
+  CJS_HIP_TRY(hipMemcpyAsync(res.so.data() + at, d_soff, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(res.sl.data() + at, d_slen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(res.bits.data() + at, b.huff.b.bitlen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(res.crc.data() + at, d_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipStreamSynchronize(s));
   *bytes = total;
   return 0;
@@ -163,11 +155,9 @@ int run_sub(cjs_ctx* c, const uint8_t* d_in, const BItem* it, uint32_t nb, uint3
 // Runs of a list of blocks sorted by descending length through run_sub.  A run ends where the workspace (or 65535 blocks) is
 // full, or, for slots wider than SMALL_SLOT, where a block is shorter than half the run's first one (bounds the slots left empty
 // behind the shorter blocks; narrow slots cost little, so tiny inputs all share one pass).
-int run_list(cjs_ctx* c, const uint8_t* d_in, const std::vector<BItem>& L, int level, bool framed, uint64_t& used, uint32_t& passes,
-             std::vector<uint64_t>& so_all, std::vector<uint32_t>& sl_all, std::vector<uint32_t>& bits_all, std::vector<uint32_t>& crc_all) {
+int run_list(cjs_ctx* c, const uint8_t* d_in, const std::vector<BItem>& L, int level, bool framed, uint64_t& used, uint32_t& passes, BlockOuts& res) {
   BatchWork& b = *c->batch;
-  so_all.resize(L.size()); sl_all.resize(L.size()); bits_all.resize(L.size()); crc_all.resize(L.size());
-  std::vector<uint64_t> so; std::vector<uint32_t> sl, bits, crc;
+  res.resize(L.size());
   for (size_t i0 = 0; i0 < L.size();) {
     const uint32_t stride = (L[i0].len + 15u) & ~15u;
     size_t segs = 0, i1 = i0;
@@ -179,9 +169,7 @@ int run_list(cjs_ctx* c, const uint8_t* d_in, const std::vector<BItem>& L, int l
     }
     if (sub_bytes(i1 - i0, stride, segs) > b.arena.cap) return CJS_E_OUT_OF_MEMORY;     // the workspace cannot take even one block
     uint64_t bytes = 0;
-    CJS_TRY(run_sub(c, d_in, L.data() + i0, (uint32_t)(i1 - i0), stride, segs, level, framed, used, so, sl, bits, crc, &bytes));
-    std::copy(so.begin(), so.end(), so_all.begin() + i0); std::copy(sl.begin(), sl.end(), sl_all.begin() + i0);
-    std::copy(bits.begin(), bits.end(), bits_all.begin() + i0); std::copy(crc.begin(), crc.end(), crc_all.begin() + i0);
+    CJS_TRY(run_sub(c, d_in, L.data() + i0, (uint32_t)(i1 - i0), stride, segs, level, framed, used, res, i0, &bytes));
     used += bytes;
     passes++;
     i0 = i1;
@@ -252,12 +240,12 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
   std::stable_sort(parts.begin(), parts.end(), by_len);
   uint64_t used = 0, sused = 0;
   uint32_t passes = 0;
-  std::vector<uint64_t> so; std::vector<uint32_t> sl, bits, crc;
-  CJS_TRY(run_list(c, d_in, one, level, true, used, passes, so, sl, bits, crc));
-  for (size_t i = 0; i < one.size(); i++) { out_off[one[i].input] = (size_t)so[i]; out_len[one[i].input] = sl[i]; }
+  BlockOuts r;
+  CJS_TRY(run_list(c, d_in, one, level, true, used, passes, r));
+  for (size_t i = 0; i < one.size(); i++) { out_off[one[i].input] = (size_t)r.so[i]; out_len[one[i].input] = r.sl[i]; }
   // inputs of several blocks: their blocks' bit strings (scratch), then assembled into streams behind the others
   if (!parts.empty()) {
-    CJS_TRY(run_list(c, d_in, parts, level, false, sused, passes, so, sl, bits, crc));
+    CJS_TRY(run_list(c, d_in, parts, level, false, sused, passes, r));
     std::vector<size_t> at(multi.size() + 1, 0), pos(count, 0);
     for (size_t j = 0; j < multi.size(); j++) pos[multi[j]] = j;
     std::vector<size_t> cnt(multi.size(), 0);
@@ -273,9 +261,9 @@ static int batch_core(cjs_ctx* c, const uint8_t* d_in, const std::vector<uint64_
       uint32_t scrc = 0;
       for (size_t q = 0; q < cnt[j]; q++) {
         const size_t i = order[at[j] + q];
-        ab[at[j] + q] = AsmBlock{so[i], bit, bits[i]};
-        bit += bits[i];
-        scrc = ((scrc << 1) | (scrc >> 31)) ^ crc[i];          // J/Bzip2_joined_.js:2237
+        ab[at[j] + q] = AsmBlock{r.so[i], bit, r.bits[i]};
+        bit += r.bits[i];
+        scrc = crc_fold(scrc, r.crc[i]);
       }
       as[j] = AsmStream{used, bit, scrc, 0};
       out_off[multi[j]] = (size_t)used; out_len[multi[j]] = (size_t)((bit + 80 - used * 8 + 7) / 8);

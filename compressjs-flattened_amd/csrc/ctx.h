@@ -1,6 +1,8 @@
-// ctx.h — the per-GPU context behind the opaque cjs_ctx of the C ABI (pipeline.hip: single streams; batch.hip: batches).
+// ctx.h — the per-GPU context behind the opaque cjs_ctx of the C ABI (pipeline.hip: single streams and the shard phases;
+// enc_host.hip: the host-buffer driver; enc_stream.hip: the streaming encoder; batch.hip: batches).
 #pragma once
 #include "cjs_internal.h"
+#include "bz_frame.h"
 #include "rle1.h"
 #include "mtf.h"
 #include "huff.h"
@@ -39,7 +41,21 @@ struct cjs_ctx {
 };
 
 namespace cjs {
-// pipeline.hip: blocks [f, f + cnt) of the stream whose boundaries c->rle holds (rle1_run: nb blocks, the last of last_len bytes)
-// through RLE1 bytes / CRCs, suffix sort, MTF / RLE2 and the Huffman tables; the caller packs (huff_pack_run)
+// All of these: pipeline.hip.
+// blocks [f, f + cnt) of the stream whose boundaries c->rle holds (rle1_run: nb blocks, the last of last_len bytes)
+// through RLE1 bytes / CRCs, suffix sort, MTF / RLE2 and the Huffman tables; the caller packs (pack_enqueue)
 int blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32_t nb, uint32_t last_len, uint32_t f, uint32_t cnt, cjs_stats* st, bool stage_times);
+// The packing of those blocks on the context's stream, in two halves (a caller may enqueue more between them):
+// pack_enqueue: huff_pack_run over the context's symbol rows, then the copy of the run's scalars to the host;
+// pack_finish: waits for the stream; CJS_E_OUTPUT_TOO_SMALL if the stream did not fit, else *end_bit = the bit behind what was written
+int pack_enqueue(cjs_ctx* c, const PackJob& j);
+int pack_finish(cjs_ctx* c, uint64_t* end_bit);
+// rc; after an error (rc != 0) the context's three streams have drained first: an early return may leave kernels in flight (block
+// CRCs on the side stream, MTF / Huffman tables of earlier pieces on the tail stream) against a context the caller reuses
+int drain_on_error(cjs_ctx* c, int rc);
+// The bodies of cjs_bzip2_shard_blocks (without drain_on_error: the caller's) and of cjs_bzip2_shard_pack behind shard_layout,
+// which the worker threads of the host-buffer driver (enc_host.hip) run on byte ranges that are streams of their own.
+int shard_blocks_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, int rank, int world, const void* d_shares, cjs_shard_meta* meta, cjs_stats* st);
+int shard_pack_core(cjs_ctx* c, int level, bool header, bool trailer, uint64_t start, uint64_t bits, uint32_t scrc, uint8_t* d_out, size_t out_cap,
+                    size_t* frag_off, size_t* frag_len, uint64_t* stream_off);
 }  // namespace cjs

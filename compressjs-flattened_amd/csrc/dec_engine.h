@@ -7,6 +7,7 @@
 // A driver holds what is particular to it: where the bytes come from and where they go.
 #pragma once
 #include "cjs_internal.h"
+#include "bz_frame.h"
 #include "decode_dev.h"
 #include "host.h"
 #include <algorithm>
@@ -239,7 +240,7 @@ int bz_walk(const Bytes& in, size_t n, int multistream, int mode, uint32_t tt_st
       if (rc) return rc;
       if (partial && bo.end_bit >= (uint64_t)n * 8) return stop(WALK_BLOCK_OPEN);
       take(bo, pos);
-      stream_crc = bo.crc ^ ((stream_crc << 1) | (stream_crc >> 31));
+      stream_crc = crc_fold(stream_crc, bo.crc);
       pos = bo.end_bit;
     } else {
       if (partial && (pos + 80 > (uint64_t)n * 8 || (multistream && (pos + 80 + 7) / 8 + 4 > n))) return stop(pos + 80 > (uint64_t)n * 8 ? WALK_NEED_CRC : WALK_NEED_HEADER);

@@ -119,7 +119,7 @@ int recover_core(const uint8_t* in, const uint8_t* d_src, size_t n, bool as_stre
       if (as_stream) {
         runs.push_back(BitRun{src_addr, src_words, p, sbit, e - p});
         sbit += e - p;
-        fold = ((fold << 1) | (fold >> 31)) ^ J.chain[k].crc;
+        fold = crc_fold(fold, J.chain[k].crc);
       } else if (len) {
         if (!pieces.empty() && pieces.back().from + pieces.back().len == J.out_off[k]) pieces.back().len += len;
         else pieces.push_back(Piece{J.out_off[k], total, len});

@@ -197,7 +197,7 @@ struct EncWork {
       CJS_HIP_TRY(hipMemcpyAsync(h_crc, ctx->rle.block_crc, 4 * (size_t)cnt, hipMemcpyDeviceToHost, s));
       if (!final) CJS_HIP_TRY(hipMemcpyAsync(h_blk, ctx->rle.blocks + cnt, sizeof(RleBlock), hipMemcpyDeviceToHost, s));
       CJS_HIP_TRY(hipStreamSynchronize(s));
-      for (uint32_t k = 0; k < cnt; k++) scrc = ((scrc << 1) | (scrc >> 31)) ^ h_crc[k];
+      for (uint32_t k = 0; k < cnt; k++) scrc = crc_fold(scrc, h_crc[k]);
       if (!final) {
         const uint64_t from = h_blk->s;
         if (from == 0 || from > N) return CJS_E_HIP;
@@ -206,13 +206,10 @@ struct EncWork {
       const bool header = !header_done;
       const PackShard ps{scrc, 0};
       uint8_t* o = d_out[packs & 1];
-      CJS_TRY(huff_pack_run(s, ctx->huff, nb, 0, cnt, header ? 32 : phase, e->level, header ? 1 : 0, final ? 1 : 0, ctx->mtf.b.A, ctx->mtf.b.a_stride,
-                            ctx->mtf.b.npos, ctx->mtf.b.asz, ctx->mtf.b.alist, ctx->rle.block_crc, ctx->d_pidx, (uint32_t*)o, out_cap, &ps));
-      CJS_HIP_TRY(hipMemcpyAsync(ctx->h_scalars, ctx->huff.scalars, 24, hipMemcpyDeviceToHost, s));
-      if (!final) CJS_TRY(move_carry(s, N - next_carry, N));
-      CJS_HIP_TRY(hipStreamSynchronize(s));
-      if (ctx->h_scalars[2]) return CJS_E_OUTPUT_TOO_SMALL;
-      const uint64_t end_bit = ctx->h_scalars[0];
+      CJS_TRY(pack_enqueue(ctx, PackJob{nb, 0, cnt, header ? 32u : phase, e->level, header, final, ctx->rle.block_crc, ctx->d_pidx, (uint32_t*)o, out_cap, &ps}));
+      if (!final) CJS_TRY(move_carry(s, N - next_carry, N));       // (between the two halves: the carry moves beside the wait)
+      uint64_t end_bit = 0;
+      CJS_TRY(pack_finish(ctx, &end_bit));
       out_bytes = (size_t)((end_bit + 7) / 8);
       dl = (uint8_t*)HostPool::take(out_bytes);
       if (!dl) return CJS_E_OUT_OF_MEMORY;

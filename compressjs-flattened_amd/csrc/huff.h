@@ -1,6 +1,7 @@
 // huff.h — Huffman table construction + bit packing stage buffers and entry points.
 #pragma once
 #include "cjs_internal.h"
+#include "mtf.h"
 
 namespace cjs {
 
@@ -43,25 +44,46 @@ struct HuffWork {
 // which implementation builds the tables: HUFF_AUTO = by the shape of the call (what every production caller uses), or forced
 // (the stage-level tests run both on the same blocks)
 enum HuffPath { HUFF_AUTO = 0, HUFF_PER_BLOCK = 1, HUFF_CHAIN = 2 };
-int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                    const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist, int path = HUFF_AUTO);
+int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const SymRows& r, int path = HUFF_AUTO);
 // a rank of a multi-GPU job: the stream CRC folded over ALL ranks' blocks (the trailer writer needs it), and whether the next
 // rank's blocks follow this fragment (pack_frame then completes the fragment's last word with the leading bits of the block magic)
 struct PackShard { uint32_t stream_crc; int follow_magic; };
-// Packs blocks [first, first+count) starting at absolute bit `start_bit` of d_out32 (the part the stream occupies is
-// zeroed here, the bits in front of start_bit included).
-int huff_pack_run(hipStream_t s, HuffWork& w, uint32_t nb_total, uint32_t first, uint32_t count, uint64_t start_bit, int level,
-                  int write_header, int write_trailer, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                  const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
-                  uint32_t* d_out32, size_t out_cap_bytes, const PackShard* ps = nullptr);    // scalars[2] = 1 and nothing written if the stream does not fit
+// What a pack run is told besides the symbol rows: blocks [first, first + count) of a stream of nb_total, from absolute bit
+// start_bit of out32 on (the part the stream occupies is zeroed by the run, the bits in front of start_bit included).
+struct PackJob {
+  uint32_t nb_total, first, count;
+  uint64_t start_bit;
+  int level;
+  bool header, trailer;              // 'BZh<level>' in front / end-of-stream magic and stream CRC behind
+  const uint32_t *block_crc, *pidx;  // per block: block_crc indexed from block 0 of the stream, pidx from `first`
+  uint32_t* out32;
+  size_t out_cap_bytes;
+  const PackShard* shard = nullptr;
+};
+int huff_pack_run(hipStream_t s, HuffWork& w, const SymRows& r, const PackJob& j);    // scalars[2] = 1 and nothing written if the stream does not fit
 
 // Batches of independent streams (cjs_bzip2_compress_batch*), one per block: framed = header, block j, trailer; else block j's
 // bare bit string from bit 0.  Item j lands at byte d_soff[j] (4-byte aligned, from `base` on, in block order); d_slen[j] = its
-// length in bytes, w.scalars[0] = bytes of all of them (aligned).  The pack run writes them into d_out32, whose range
-// [base, base + scalars[0]) the caller has zeroed.
+// length in bytes, w.scalars[0] = bytes of all of them (aligned).  The pack run writes them into j.out32, whose range
+// [base, base + scalars[0]) the caller has zeroed; of the job it reads count, level, header (= framed), block_crc, pidx, out32.
 int huff_batch_offsets_run(hipStream_t s, HuffWork& w, uint32_t nb, uint64_t base, int framed, uint64_t* d_soff, uint32_t* d_slen);
-int huff_batch_pack_run(hipStream_t s, HuffWork& w, uint32_t nb, int level, int framed, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                        const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
-                        const uint64_t* d_soff, uint32_t* d_out32);
+int huff_batch_pack_run(hipStream_t s, HuffWork& w, const SymRows& r, const PackJob& j, const uint64_t* d_soff);
+
+// end-of-stream magic and stream CRC (48 + 32 bits) OR-ed into the big-endian words of out32 from stream bit `bit` on; returns
+// the bit behind them.  One lane per stream (pack_frame, huff_batch_frame, batch_asm_frame).
+__device__ __forceinline__ uint64_t put_trailer_words(uint32_t* out32, uint64_t bit, uint32_t crc) {
+  const uint64_t vals[2] = {0x177245385090ull, (uint64_t)crc};
+  const uint32_t nbs[2] = {48, 32};
+  for (int q = 0; q < 2; q++) {
+    uint32_t left = nbs[q];
+    while (left) {
+      const uint32_t o = (uint32_t)(bit & 31), room = 32 - o, take = left < room ? left : room;
+      const uint32_t chunk = (uint32_t)((vals[q] >> (left - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
+      atomicOr(&out32[bit >> 5], __builtin_bswap32(chunk << (room - take)));
+      left -= take; bit += take;
+    }
+  }
+  return bit;
+}
 
 }  // namespace cjs

@@ -739,19 +739,7 @@ __global__ void pack_frame(HuffBufs hb, uint32_t nb_range_end, int level, int wr
     const uint32_t room = 32 - (uint32_t)(bit & 31);
     atomicOr(&out32[bit >> 5], __builtin_bswap32((uint32_t)(0x314159265359ull >> (48 - room))));
   }
-  if (write_trailer) {
-    const uint64_t vals[2] = {0x177245385090ull, (uint64_t)*stream_crc};
-    const uint32_t nbs[2] = {48, 32};
-    for (int q = 0; q < 2; q++) {
-      uint32_t left = nbs[q];
-      while (left) {
-        const uint32_t o = (uint32_t)(bit & 31), room = 32 - o, take = left < room ? left : room;
-        const uint32_t chunk = (uint32_t)((vals[q] >> (left - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
-        atomicOr(&out32[bit >> 5], __builtin_bswap32(chunk << (room - take)));
-        left -= take; bit += take;
-      }
-    }
-  }
+  if (write_trailer) bit = put_trailer_words(out32, bit, *stream_crc);
   *total_bits = bit;
 }
 
@@ -780,18 +768,7 @@ __global__ __launch_bounds__(256) void huff_batch_frame(HuffBufs hb, uint32_t nb
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= nb) return;
   out32[soff[j] >> 2] = __builtin_bswap32(0x425a6830u + (uint32_t)level);      // 'B''Z''h''0'+level (a word of its own)
-  uint64_t bit = hb.bitoff[j] + hb.bitlen[j];
-  const uint64_t vals[2] = {0x177245385090ull, (uint64_t)block_crc[j]};
-  const uint32_t nbs[2] = {48, 32};
-  for (int q = 0; q < 2; q++) {
-    uint32_t left = nbs[q];
-    while (left) {
-      const uint32_t o = (uint32_t)(bit & 31), room = 32 - o, take = left < room ? left : room;
-      const uint32_t chunk = (uint32_t)((vals[q] >> (left - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
-      atomicOr(&out32[bit >> 5], __builtin_bswap32(chunk << (room - take)));
-      left -= take; bit += take;
-    }
-  }
+  put_trailer_words(out32, hb.bitoff[j] + hb.bitlen[j], block_crc[j]);
 }
 
 int huff_batch_offsets_run(hipStream_t s, HuffWork& w, uint32_t nb, uint64_t base, int framed, uint64_t* d_soff, uint32_t* d_slen) {
@@ -800,13 +777,12 @@ int huff_batch_offsets_run(hipStream_t s, HuffWork& w, uint32_t nb, uint64_t bas
   CJS_HIP_TRY(hipGetLastError());
   return 0;
 }
-int huff_batch_pack_run(hipStream_t s, HuffWork& w, uint32_t nb, int level, int framed, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                        const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
-                        const uint64_t* d_soff, uint32_t* d_out32) {
+int huff_batch_pack_run(hipStream_t s, HuffWork& w, const SymRows& r, const PackJob& j, const uint64_t* d_soff) {
+  const uint32_t nb = j.count;
   if (!nb) return 0;
-  hipLaunchKernelGGL(pack_block, dim3(nb), dim3(1024), 0, s, w.b, 0u, d_A, a_stride, d_npos, d_asz, d_alist, d_block_crc, d_pidx, d_out32, w.scalars + 2);
-  hipLaunchKernelGGL(pack_data, dim3((unsigned)(w.b.tile_stride - 1), nb), dim3(1024), 0, s, w.b, d_A, a_stride, d_npos, d_out32, w.scalars + 2);
-  if (framed) hipLaunchKernelGGL(huff_batch_frame, dim3((nb + 255) / 256), dim3(256), 0, s, w.b, nb, level, d_block_crc, d_soff, d_out32);
+  hipLaunchKernelGGL(pack_block, dim3(nb), dim3(1024), 0, s, w.b, 0u, r.A, r.a_stride, r.npos, r.asz, r.alist, j.block_crc, j.pidx, j.out32, w.scalars + 2);
+  hipLaunchKernelGGL(pack_data, dim3((unsigned)(w.b.tile_stride - 1), nb), dim3(1024), 0, s, w.b, r.A, r.a_stride, r.npos, j.out32, w.scalars + 2);
+  if (j.header) hipLaunchKernelGGL(huff_batch_frame, dim3((nb + 255) / 256), dim3(256), 0, s, w.b, nb, j.level, j.block_crc, d_soff, j.out32);
   CJS_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -838,8 +814,7 @@ int HuffWork::carve(Arena& a, size_t max_blocks_, uint32_t stride) {
   return (scalars && b.tileoff && b.wl && b.wfreq) ? 0 : CJS_E_OUT_OF_MEMORY;
 }
 
-int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                    const uint32_t* d_asz, const uint32_t* d_freq, const uint8_t* d_alist, int path) {
+int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const SymRows& r, int path) {
   if (nb == 0) return 0;
   if (path != HUFF_AUTO && path != HUFF_PER_BLOCK && path != HUFF_CHAIN) return CJS_E_INVALID_ARG;
   const bool dbg = env_debug();
@@ -849,15 +824,15 @@ int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A
   if (split) {
     const uint32_t max_sel = (uint32_t)(((size_t)w.max_stride + 1 + GSZ - 1) / GSZ);
     const uint32_t ga = (max_sel + HS_STEPS * AS_GROUPS - 1) / (HS_STEPS * AS_GROUPS), gc = (w.max_stride + 1 + HS_CNT - 1) / HS_CNT;
-    hipLaunchKernelGGL(hs_init, dim3(nb), dim3(128), 0, s, w.b, d_asz, d_freq);
+    hipLaunchKernelGGL(hs_init, dim3(nb), dim3(128), 0, s, w.b, r.asz, r.freq);
     for (int ng = 2; ng <= 6; ng++) {
-      hipLaunchKernelGGL(hs_assign, dim3(ga, nb), dim3(1024), 0, s, w.b, d_A, a_stride, d_npos, ng);
+      hipLaunchKernelGGL(hs_assign, dim3(ga, nb), dim3(1024), 0, s, w.b, r.A, r.a_stride, r.npos, ng);
       if (ng == 6) break;
-      hipLaunchKernelGGL(hs_split, dim3(nb), dim3(1024), 0, s, w.b, d_npos, ng);
-      hipLaunchKernelGGL(hs_count, dim3(gc, nb), dim3(1024), 0, s, w.b, d_A, a_stride, d_npos, ng);
-      hipLaunchKernelGGL(hs_build, dim3(nb), dim3(384), 0, s, w.b, d_npos, d_asz, ng);
+      hipLaunchKernelGGL(hs_split, dim3(nb), dim3(1024), 0, s, w.b, r.npos, ng);
+      hipLaunchKernelGGL(hs_count, dim3(gc, nb), dim3(1024), 0, s, w.b, r.A, r.a_stride, r.npos, ng);
+      hipLaunchKernelGGL(hs_build, dim3(nb), dim3(384), 0, s, w.b, r.npos, r.asz, ng);
     }
-    hipLaunchKernelGGL(hs_finish, dim3(nb), dim3(1024), 0, s, w.b, d_npos, d_asz, d_alist);
+    hipLaunchKernelGGL(hs_finish, dim3(nb), dim3(1024), 0, s, w.b, r.npos, r.asz, r.alist);
     CJS_HIP_TRY(hipGetLastError());
     if (dbg) {
       uint64_t clk[8];
@@ -868,7 +843,7 @@ int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A
     }
     return 0;
   }
-  hipLaunchKernelGGL(huff_block, dim3(nb), dim3(1024), 0, s, w.b, d_A, a_stride, d_npos, d_asz, d_freq, d_alist, dbg ? 1 : 0);
+  hipLaunchKernelGGL(huff_block, dim3(nb), dim3(1024), 0, s, w.b, r.A, r.a_stride, r.npos, r.asz, r.freq, r.alist, dbg ? 1 : 0);
   CJS_HIP_TRY(hipGetLastError());
   if (dbg) {
     uint64_t clk[32];
@@ -881,19 +856,18 @@ int huff_tables_run(hipStream_t s, HuffWork& w, uint32_t nb, const uint16_t* d_A
   return 0;
 }
 
-int huff_pack_run(hipStream_t s, HuffWork& w, uint32_t nb_total, uint32_t first, uint32_t count, uint64_t start_bit, int level,
-                  int write_header, int write_trailer, const uint16_t* d_A, size_t a_stride, const uint32_t* d_npos,
-                  const uint32_t* d_asz, const uint8_t* d_alist, const uint32_t* d_block_crc, const uint32_t* d_pidx,
-                  uint32_t* d_out32, size_t out_cap_bytes, const PackShard* ps) {
+int huff_pack_run(hipStream_t s, HuffWork& w, const SymRows& r, const PackJob& j) {
   uint32_t* stream_crc = (uint32_t*)(w.scalars + 1);
-  hipLaunchKernelGGL(huff_offsets, dim3(1), dim3(1), 0, s, w.b, d_block_crc, nb_total, first, count, start_bit, stream_crc,
-                     (uint64_t)(write_trailer ? 80 : 0), (uint64_t)out_cap_bytes, w.scalars + 2, ps ? 1 : 0, ps ? ps->stream_crc : 0u);
-  hipLaunchKernelGGL(pack_zero_output, dim3(4096), dim3(256), 0, s, w.b, count, (uint64_t)(write_trailer ? 80 : 0), d_out32, (uint64_t)out_cap_bytes, w.scalars + 2);
-  if (count) {
-    hipLaunchKernelGGL(pack_block, dim3(count), dim3(1024), 0, s, w.b, first, d_A, a_stride, d_npos, d_asz, d_alist, d_block_crc, d_pidx, d_out32, w.scalars + 2);
-    hipLaunchKernelGGL(pack_data, dim3((unsigned)(w.b.tile_stride - 1), count), dim3(1024), 0, s, w.b, d_A, a_stride, d_npos, d_out32, w.scalars + 2);
+  const PackShard* ps = j.shard;
+  const uint64_t trailer_bits = j.trailer ? 80 : 0;
+  hipLaunchKernelGGL(huff_offsets, dim3(1), dim3(1), 0, s, w.b, j.block_crc, j.nb_total, j.first, j.count, j.start_bit, stream_crc,
+                     trailer_bits, (uint64_t)j.out_cap_bytes, w.scalars + 2, ps ? 1 : 0, ps ? ps->stream_crc : 0u);
+  hipLaunchKernelGGL(pack_zero_output, dim3(4096), dim3(256), 0, s, w.b, j.count, trailer_bits, j.out32, (uint64_t)j.out_cap_bytes, w.scalars + 2);
+  if (j.count) {
+    hipLaunchKernelGGL(pack_block, dim3(j.count), dim3(1024), 0, s, w.b, j.first, r.A, r.a_stride, r.npos, r.asz, r.alist, j.block_crc, j.pidx, j.out32, w.scalars + 2);
+    hipLaunchKernelGGL(pack_data, dim3((unsigned)(w.b.tile_stride - 1), j.count), dim3(1024), 0, s, w.b, r.A, r.a_stride, r.npos, j.out32, w.scalars + 2);
   }
-  hipLaunchKernelGGL(pack_frame, dim3(1), dim3(1), 0, s, w.b, count, level, write_header, write_trailer, ps ? ps->follow_magic : 0, stream_crc, d_out32, w.scalars);
+  hipLaunchKernelGGL(pack_frame, dim3(1), dim3(1), 0, s, w.b, j.count, j.level, j.header ? 1 : 0, j.trailer ? 1 : 0, ps ? ps->follow_magic : 0, stream_crc, j.out32, w.scalars);
   CJS_HIP_TRY(hipGetLastError());
   return 0;
 }

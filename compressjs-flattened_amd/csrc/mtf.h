@@ -18,10 +18,20 @@ struct MtfBufs {
   size_t list_stride, a_stride, hstride;   // hstride: per-block stride of hpos/hsym/hrank (multiple of 16)
 };
 
+// What the Huffman stage reads of the MTF stage's output: per block the symbol row, its length, the alphabet size, the symbol
+// counts and the used byte values (freq: only the table construction reads it)
+struct SymRows {
+  const uint16_t* A;
+  size_t a_stride;
+  const uint32_t *npos, *asz, *freq;
+  const uint8_t* alist;
+};
+
 struct MtfWork {
   size_t max_blocks = 0;
   uint32_t stride = 0;
   MtfBufs b{};
+  SymRows rows() const { return SymRows{b.A, b.a_stride, b.npos, b.asz, b.freq, b.alist}; }
   static size_t list_stride_for(uint32_t stride) { return ((size_t)(stride + 255) / 256 + 1) * 256; }
   static size_t seg_stride_for(uint32_t stride) { return ((size_t)stride + 8191) / 8192 + 1; }
   static size_t hstride_for(uint32_t stride) { return ((size_t)stride + 15) & ~(size_t)15; }

@@ -1,0 +1,229 @@
+// stages.hip — stage-level entry points of the compress pipeline (host buffers; the parity tests use them to localise a
+// mismatch): every call carves a workspace of its own, runs one stage on a stream of its own and copies the stage's output back.
+#include "cjs_internal.h"
+#include "host.h"
+#include "rle1.h"
+#include "mtf.h"
+#include "huff.h"
+#include <algorithm>
+#include <vector>
+
+using namespace cjs;
+
+extern "C" int cjs_stage_bwt(const uint8_t* in, size_t n, int block_len, int cyclic, uint8_t* out, int32_t* pidx, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (n == 0) return 0;
+  if (block_len <= 0) return CJS_E_INVALID_ARG;
+  const uint32_t stride = (uint32_t)block_len;
+  const uint32_t nb = (uint32_t)((n + stride - 1) / stride);
+  const uint32_t n_last = (uint32_t)(n - (size_t)(nb - 1) * stride);
+  Arena arena;
+  CJS_TRY(arena.init(BwtWork::bytes_needed(n) + 2 * ((n + 511) & ~(size_t)255) + 4 * (size_t)nb + 8192));
+  BwtWork w;
+  CJS_TRY(w.carve(arena, n));
+  uint8_t* d_T = arena.take<uint8_t>(n);
+  uint8_t* d_U = arena.take<uint8_t>(n);
+  uint32_t* d_p = arena.take<uint32_t>(nb);
+  if (!d_T || !d_U || !d_p) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpyAsync(d_T, in, n, hipMemcpyHostToDevice, s));
+  CJS_TRY(bwt_run(s, w, d_T, nb, stride, n_last, cyclic != 0, d_U, d_p, Opts(opts).stats));
+  CJS_HIP_TRY(hipMemcpyAsync(out, d_U, n, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(pidx, d_p, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_stage_rle1(const uint8_t* in, size_t n, int level, uint8_t* blocks, size_t blocks_cap,
+                              uint32_t* block_len, uint32_t* block_crc, uint64_t* block_start, long cap_blocks, long* nblocks,
+                              const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;
+  const uint32_t cap = (uint32_t)level * 100000u - 19u;
+  *nblocks = 0;
+  if (n == 0) return 0;
+  Arena arena;
+  const size_t maxb = Rle1Work::max_blocks_for(n, cap);
+  CJS_TRY(arena.init(Rle1Work::bytes_needed(n, cap) + n + maxb * cap + 65536));
+  Rle1Work w;
+  CJS_TRY(w.carve(arena, n, cap));
+  uint8_t* d_in = arena.take<uint8_t>(n);
+  uint8_t* d_blocks = arena.take<uint8_t>(maxb * cap);
+  if (!d_in || !d_blocks) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s));
+  uint32_t nb = 0;
+  const int rc = rle1_run(s, w, d_in, n, &nb);
+  *nblocks = (long)nb;
+  CJS_TRY(rc);
+  CJS_TRY(rle1_finish(s, w, d_in, n, 0, nb, d_blocks));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  if ((long)nb > cap_blocks || (size_t)nb * cap > blocks_cap) return CJS_E_OUTPUT_TOO_SMALL;
+  if (nb) {
+    std::vector<RleBlock> hb(nb);
+    CJS_HIP_TRY(hipMemcpy(hb.data(), w.blocks, sizeof(RleBlock) * nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(block_len, w.block_len, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(block_crc, w.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(blocks, d_blocks, (size_t)nb * cap, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < nb; k++) block_start[k] = hb[k].s;
+  }
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_stage_mtf(const uint8_t* U, const uint8_t* blocks, size_t n, int block_len, uint16_t* A, uint32_t* npos,
+                             uint32_t* freq, uint32_t* alphabet, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  (void)blocks;   // the used-symbol set of a block equals that of its BWT (a permutation of it)
+  CJS_TRY(select_device(opts));
+  if (n == 0) return 0;
+  if (block_len <= 0) return CJS_E_INVALID_ARG;
+  const uint32_t stride = (uint32_t)block_len, nb = (uint32_t)((n + stride - 1) / stride);
+  Arena arena;
+  CJS_TRY(arena.init(MtfWork::bytes_needed(nb, stride) + (size_t)nb * stride + 4 * (size_t)nb + 65536));
+  MtfWork w;
+  CJS_TRY(w.carve(arena, nb, stride));
+  uint8_t* d_U = arena.take<uint8_t>((size_t)nb * stride);
+  uint32_t* d_len = arena.take<uint32_t>(nb);
+  if (!d_U || !d_len) return CJS_E_OUT_OF_MEMORY;
+  std::vector<uint32_t> lens(nb, stride);
+  lens[nb - 1] = (uint32_t)(n - (size_t)(nb - 1) * stride);
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpy(d_U, U, n, hipMemcpyHostToDevice));
+  CJS_HIP_TRY(hipMemcpy(d_len, lens.data(), 4 * (size_t)nb, hipMemcpyHostToDevice));
+  CJS_TRY(mtf_run(s, w, d_U, nb, d_len));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  std::vector<uint32_t> hnpos(nb);
+  CJS_HIP_TRY(hipMemcpy(hnpos.data(), w.b.npos, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(freq, w.b.freq, 4 * 258 * (size_t)nb, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(alphabet, w.b.asz, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < nb; k++) {
+    npos[k] = hnpos[k];
+    CJS_HIP_TRY(hipMemcpy(A + (size_t)k * (stride + 1), w.b.A + (size_t)k * w.b.a_stride, 2 * (size_t)hnpos[k], hipMemcpyDeviceToHost));
+  }
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_stage_huff(const uint16_t* A, uint32_t npos, uint32_t alphabet, uint8_t* selectors, uint8_t* lengths,
+                              uint32_t* ngroups, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (npos == 0 || alphabet == 0 || alphabet > 256) return CJS_E_INVALID_ARG;
+  const uint32_t stride = npos;    // any stride >= npos-1 works for the selector buffers
+  Arena arena;
+  CJS_TRY(arena.init(HuffWork::bytes_needed(1, stride) + 2 * (size_t)npos + 4096 * 4 + 65536));
+  HuffWork w;
+  const int rc = w.carve(arena, 1, stride);
+  uint16_t* d_A = arena.take<uint16_t>(npos);
+  uint32_t* d_misc = arena.take<uint32_t>(2 + 258);
+  uint8_t* d_alist = arena.take<uint8_t>(256);
+  std::vector<uint32_t> misc(2 + 258, 0);
+  misc[0] = npos; misc[1] = alphabet;
+  for (uint32_t i = 0; i < npos; i++) { if (A[i] > alphabet + 1) return CJS_E_INVALID_ARG; misc[2 + A[i]]++; }
+  CJS_TRY(rc);
+  if (!d_A || !d_misc || !d_alist) return CJS_E_OUT_OF_MEMORY;
+  uint8_t al[256]; for (int i = 0; i < 256; i++) al[i] = (uint8_t)i;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpy(d_A, A, 2 * (size_t)npos, hipMemcpyHostToDevice));
+  CJS_HIP_TRY(hipMemcpy(d_misc, misc.data(), 4 * misc.size(), hipMemcpyHostToDevice));
+  CJS_HIP_TRY(hipMemcpy(d_alist, al, 256, hipMemcpyHostToDevice));
+  CJS_TRY(huff_tables_run(s, w, 1, SymRows{d_A, npos, d_misc, d_misc + 1, d_misc + 2, d_alist}));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  const uint32_t nsel = (npos + 49) / 50;
+  CJS_HIP_TRY(hipMemcpy(selectors, w.b.sel, nsel, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(lengths, w.b.lens, 6 * 258, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(ngroups, w.b.ngroups, 4, hipMemcpyDeviceToHost));
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_stage_huff_blocks(const uint16_t* A, size_t a_stride, uint32_t nb, const uint32_t* npos, const uint32_t* alphabet,
+                                     const uint8_t* used, const uint32_t* block_crc, const uint32_t* pidx, int path,
+                                     uint32_t* ngroups, uint8_t* selectors, uint8_t* lengths, uint8_t* bits, size_t bits_stride,
+                                     uint64_t* nbits, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (nb == 0 || nb > 65535 || a_stride == 0 || (path != HUFF_AUTO && path != HUFF_PER_BLOCK && path != HUFF_CHAIN)) return CJS_E_INVALID_ARG;
+  // the blocks' symbol counts (the MTF stage's freq[]) and the checks the kernels rely on: symbols index tables of asz + 2 entries
+  std::vector<uint32_t> freq((size_t)nb * 258, 0);
+  std::vector<uint8_t> alist((size_t)nb * 256, 0);
+  uint32_t max_npos = 0;
+  for (uint32_t k = 0; k < nb; k++) {
+    const uint32_t n = npos[k], asz = alphabet[k];
+    if (n == 0 || n > a_stride || n > 50u * 32767u || asz == 0 || asz > 256) return CJS_E_INVALID_ARG;     // (15-bit selector count)
+    for (uint32_t i = 0; i < asz; i++) {
+      if (i && used[(size_t)k * 256 + i] <= used[(size_t)k * 256 + i - 1]) return CJS_E_INVALID_ARG;     // ascending, distinct
+      alist[(size_t)k * 256 + i] = used[(size_t)k * 256 + i];
+    }
+    const uint16_t* a = A + (size_t)k * a_stride;
+    for (uint32_t i = 0; i < n; i++) { if (a[i] > asz + 1) return CJS_E_INVALID_ARG; freq[(size_t)k * 258 + a[i]]++; }
+    max_npos = std::max(max_npos, n);
+  }
+  // device rows as the pipeline carves them: a block of up to `stride` bytes yields up to stride + 1 symbols
+  const uint32_t stride = max_npos > 1 ? max_npos - 1 : 1;
+  const size_t das = MtfWork::a_stride_for(stride);
+  Arena arena;
+  CJS_TRY(arena.init(HuffWork::bytes_needed(nb, stride) + 2 * das * nb + (size_t)nb * (258 * 4 + 256 + 5 * 4 + 8) + 16 * 256 + 65536));
+  HuffWork w;
+  CJS_TRY(w.carve(arena, nb, stride));
+  uint16_t* d_A = arena.take<uint16_t>(das * nb);
+  uint32_t* d_npos = arena.take<uint32_t>(nb);
+  uint32_t* d_asz = arena.take<uint32_t>(nb);
+  uint32_t* d_freq = arena.take<uint32_t>((size_t)nb * 258);
+  uint8_t* d_alist = arena.take<uint8_t>((size_t)nb * 256);
+  uint32_t* d_crc = arena.take<uint32_t>(nb);
+  uint32_t* d_pidx = arena.take<uint32_t>(nb);
+  uint64_t* d_soff = arena.take<uint64_t>(nb);
+  uint32_t* d_slen = arena.take<uint32_t>(nb);
+  if (!d_A || !d_npos || !d_asz || !d_freq || !d_alist || !d_crc || !d_pidx || !d_soff || !d_slen) return CJS_E_OUT_OF_MEMORY;
+  const SymRows rows{d_A, das, d_npos, d_asz, d_freq, d_alist};
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemsetAsync(d_A, 0, 2 * das * nb, s));
+  CJS_HIP_TRY(hipMemsetAsync(w.b.lens, 0, (size_t)nb * 6 * 258, s));
+  CJS_HIP_TRY(hipMemcpy2DAsync(d_A, 2 * das, A, 2 * a_stride, 2 * (size_t)max_npos, nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_npos, npos, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_asz, alphabet, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_freq, freq.data(), 4 * freq.size(), hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_alist, alist.data(), alist.size(), hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_crc, block_crc, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_pidx, pidx, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_TRY(huff_tables_run(s, w, nb, rows, path));
+  // the blocks' bare bit strings (no stream header / trailer), each from bit 0 at a 4-byte aligned offset
+  CJS_TRY(huff_batch_offsets_run(s, w, nb, 0, 0, d_soff, d_slen));
+  uint64_t total = 0;
+  CJS_HIP_TRY(hipMemcpyAsync(&total, w.scalars, 8, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  Arena oarena;
+  CJS_TRY(oarena.init(total + 4096));
+  uint32_t* d_out = oarena.take<uint32_t>((total + 16 + 3) / 4);
+  if (!d_out) return CJS_E_OUT_OF_MEMORY;
+  CJS_HIP_TRY(hipMemsetAsync(d_out, 0, total + 16, s));
+  CJS_TRY(huff_batch_pack_run(s, w, rows, PackJob{nb, 0, nb, 0, 9, false, false, d_crc, d_pidx, d_out, 0}, d_soff));
+  std::vector<uint64_t> soff(nb);
+  std::vector<uint32_t> slen(nb), blen(nb);
+  CJS_HIP_TRY(hipMemcpyAsync(soff.data(), d_soff, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(slen.data(), d_slen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(blen.data(), w.b.bitlen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(ngroups, w.b.ngroups, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(lengths, w.b.lens, (size_t)nb * 6 * 258, hipMemcpyDeviceToHost, s));
+  const size_t hsel = (a_stride + 49) / 50;
+  CJS_HIP_TRY(hipMemcpy2DAsync(selectors, hsel, w.b.sel, w.b.sel_stride, ((size_t)max_npos + 49) / 50, nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  for (uint32_t k = 0; k < nb; k++) if (slen[k] > bits_stride) return CJS_E_INVALID_ARG;      // (nothing of the bits written yet)
+  for (uint32_t k = 0; k < nb; k++) {
+    CJS_HIP_TRY(hipMemcpyAsync(bits + (size_t)k * bits_stride, (const uint8_t*)d_out + soff[k], slen[k], hipMemcpyDeviceToHost, s));
+    nbits[k] = blen[k];
+  }
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}

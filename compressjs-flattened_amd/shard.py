@@ -1,8 +1,8 @@
 """shard.py — host-side logic of the multi-GPU bzip2 path, mirrored in Python for the launcher side of a
 one-process-per-GPU job and for the CPU tests: deal contiguous block ranges to ranks, chain the ranks' CRC folds into the
 stream CRC (J/Bzip2_joined_.js:2237), and the layout of the ranks' fragments -- each rank packs its blocks at their FINAL bit
-offset, so the fragments are disjoint runs of whole 32-bit words of the one .bz2 stream (pipeline.hip: shard_layout /
-shard_pack_core).  No collective on the data path: ranks exchange only (bit length, block count, CRC fold)."""
+offset, so the fragments are disjoint runs of whole 32-bit words of the one .bz2 stream (bz_frame.h: shard_layout;
+pipeline.hip: shard_pack_core).  No collective on the data path: ranks exchange only (bit length, block count, CRC fold)."""
 import numpy as np
 
 BLOCK_MAGIC = 0x314159265359

@@ -321,6 +321,35 @@ def test_chunked_large_input_path_is_bit_exact(oracle):
     assert rc == 0 and rc_s == "0" and sha == support.sha256(want)
 
 
+@pytest.mark.parametrize("expr,level", [("recipes.textgen(1200000, 14)", 1), ("recipes.textgen(1200000, 14)", 9),
+                                        ("np.full(1200000, 0x61, dtype=np.uint8)", 1)], ids=["text-1", "text-9", "one-byte-1"])
+def test_waves_of_two_ranges_and_empty_ranges_are_bit_exact(oracle, expr, level):
+    # CJS_CHUNK_BYTES=500000 cuts 1,200,000 bytes into five ranges, CJS_DEVICES=2 runs them two at a time (waves of 2, 2, 1), the
+    # host stitches their bit strings.  Level 1: ~12 blocks over the five ranges; level 9: 2 blocks, so three ranges have no block
+    # and add 0 bits to the stitch; one repeated byte: blocks of a few hundred bits, the stitch is mostly shared edge bytes.
+    data = eval(expr)
+    rc, want = oracle.bzip2_compress(data, level)
+    code = ("import sys; sys.path.insert(0, 'tests'); import torch, support, recipes, numpy as np; "
+            "d = %s; rc, out = support.HipLib().bzip2_compress(d, %d); print(rc, support.sha256(out))" % (expr, level))
+    env = dict(os.environ, CJS_CHUNK_BYTES="500000", CJS_DEVICES="2")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+    assert out.returncode == 0, out.stderr[-1500:]
+    rc_s, sha = out.stdout.split()
+    assert rc == 0 and rc_s == "0" and sha == support.sha256(want)
+
+
+@pytest.mark.parametrize("n", [50000, 250000])
+def test_more_shards_than_blocks_all_at_once(hip, oracle, monkeypatch, n):
+    # CJS_DEVICES=5 on one block and on three: the shards without blocks publish empty metas and write nothing, the last shard
+    # WITH blocks ends the stream (trailer and combined CRC)
+    data = recipes.textgen(n, 15)
+    rc, want = oracle.bzip2_compress(data, 1)
+    monkeypatch.setenv("CJS_DEVICES", "5")
+    rc2, out = hip.bzip2_compress(data, 1)
+    monkeypatch.delenv("CJS_DEVICES")
+    assert rc == 0 and rc2 == 0 and np.array_equal(out, want)
+
+
 def _run_variant(env, n, seed, level):
     """HipLib().bzip2_compress in a fresh process under `env` (the toggles are read once per process) -> (rc, sha256)"""
     import subprocess, sys as _sys

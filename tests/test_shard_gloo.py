@@ -1,6 +1,6 @@
 """The N>1 path without GPUs: gloo ranks each produce the bare bit string of their contiguous block range (here with
 the oracle standing in for the per-rank HIP pipeline), all-gather one (bit length, block count, CRC fold) per rank, place
-their blocks at the FINAL bit offset (shard.fragment: the Python mirror of pipeline.hip's shard_layout / shard_pack_core) and
+their blocks at the FINAL bit offset (shard.fragment: the Python mirror of bz_frame.h's shard_layout and pipeline.hip's shard_pack_core) and
 rank 0's concatenation of the word-aligned fragments must equal the single-rank stream bit for bit."""
 import importlib
 import os
