@@ -55,6 +55,19 @@ class IndexEntry(ctypes.Structure):
                 ("level", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class Match(ctypes.Structure):
+    """cjs_bz_match: one match of a search (16 bytes)."""
+    _fields_ = [("off", ctypes.c_uint64), ("pattern", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SearchInfo(ctypes.Structure):
+    """cjs_bz_search_info (32 bytes)."""
+    _fields_ = [("n_matches", ctypes.c_uint64), ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64),
+                ("blocks_decoded", ctypes.c_uint64)]
+
+
+SEARCH_NOCASE = 1     # CJS_SEARCH_NOCASE
+
 _lib = None
 
 
@@ -121,6 +134,9 @@ def load_library():
     L.cjs_bzip2_index_destroy.restype = None
     L.cjs_bzip2_read_ranges.argtypes = [u8p, S, V, PU, PU, S, PP, PS, PS, ctypes.POINTER(ctypes.c_int32), V]
     L.cjs_bzip2_read_ranges_device.argtypes = [V, S, V, PU, PU, S, V, S, PS, PS, ctypes.POINTER(ctypes.c_int32), PS, V]
+    U32, U64 = ctypes.c_uint32, ctypes.c_uint64
+    L.cjs_bzip2_search.argtypes = [u8p, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
+    L.cjs_bzip2_search_device.argtypes = [V, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
     L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
     L.cjs_bzip2_enc_write.argtypes = [V, V, S]
     L.cjs_bzip2_enc_finish.argtypes = [V]
@@ -723,6 +739,71 @@ class Bzip2Index:
         if isinstance(r, CjsError):
             raise r
         return r
+
+    def search(self, data, patterns, off=0, length=None, nocase=False, limit=None):
+        """Where `patterns` (bytes-likes or str) occur in [off, off + length) of the decoded bytes, found on the GPU
+        (cjs_bzip2_search): -> SearchResult.  limit=None counts first and then fetches every match."""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        return _search(lambda *a: L.cjs_bzip2_search(keep.ctypes.data_as(u8p), data.size, self._h, *a, None), patterns, off, length, nocase, limit)
+
+    def grep(self, data, patterns, before=0, after=0, **kw):
+        """search, then one read_ranges of [o - before, o + len(pattern) + after) per match: -> [(off, pattern, bytes)] (a
+        CjsError in place of the bytes of a context that touches a bad block)"""
+        pats = _pattern_arrays(patterns)[0]
+        res = self.search(data, patterns, **kw)
+        ranges = [(max(o - before, 0), min(o, before) + len(pats[j]) + after) for o, j in res.matches]
+        ctx = self.read_ranges(data, ranges) if ranges else []
+        return [(o, j, c) for (o, j), c in zip(res.matches, ctx)]
+
+
+class SearchResult:
+    """What a search found: matches = [(off, pattern)] sorted by (off, pattern), at most `limit` of them; total = all matches of
+    the window; bad_blocks / first_bad_block (None if none) / detail = the touched blocks that were not good."""
+
+    def __init__(self, matches, info, detail):
+        self.matches, self.total = matches, int(info.n_matches)
+        self.bad_blocks = int(info.n_bad_blocks)
+        self.first_bad_block = int(info.first_bad_block) if info.n_bad_blocks else None
+        self.blocks_decoded = int(info.blocks_decoded)
+        self.detail = detail
+
+
+def _pattern_arrays(patterns):
+    pats = [bytes(_coerce_input(p.encode() if isinstance(p, str) else p)) for p in patterns]
+    blob = np.frombuffer(b"".join(pats) or b"\0", dtype=np.uint8).copy()
+    return pats, blob, np.cumsum([0] + [len(p) for p in pats]).astype(np.uint32)
+
+
+def _search(call, patterns, off, length, nocase, limit):
+    """call(pat, pat_off, npat, flags, off, len, found, cap, info) -> rc; limit=None: the count query, then all"""
+    L = load_library()
+    pats, blob, p_off = _pattern_arrays(patterns)
+    ln = 2 ** 64 - 1 if length is None else int(length)
+
+    def once(cap):
+        found = (Match * max(cap, 1))()
+        info = SearchInfo()
+        _check(call(blob.ctypes.data_as(u8p), p_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(pats), SEARCH_NOCASE if nocase else 0,
+                    int(off), ln, found if cap else None, cap, ctypes.byref(info)))
+        detail = L.cjs_last_error_detail().decode() if info.n_bad_blocks else ""
+        got = min(cap, info.n_matches)
+        raw = np.frombuffer(found, dtype=[("off", "<u8"), ("pattern", "<u4"), ("reserved", "<u4")], count=got)
+        return SearchResult(list(zip(raw["off"].tolist(), raw["pattern"].tolist())), info, detail)
+
+    if limit is not None:
+        return once(int(limit))
+    res = once(0)
+    return once(res.total) if res.total else res
+
+
+def search_device(d_in_ptr, n, index, patterns, off=0, length=None, nocase=False, limit=None, device=-1):
+    """Bzip2Index.search with the stream in GPU memory (cjs_bzip2_search_device; the memory rules of decompress_device).  The
+    result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _search(lambda *a: L.cjs_bzip2_search_device(d_in_ptr, n, index._h, *a, ctypes.byref(opts)), patterns, off, length, nocase, limit)
 
 
 def read_ranges_device(d_in_ptr, n, index, ranges, d_out_ptr, out_cap, device=-1):

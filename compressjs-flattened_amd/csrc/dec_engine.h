@@ -1,6 +1,7 @@
 // dec_engine.h -- the Bzip2 decode engine as its drivers see it.  decode.hip defines it (the kernels, phases A / B / C, the header,
 // level and verdict helpers, the single-stream driver bunzip_core); the drivers in dec_batch.hip (host and device batch, device
-// single), dec_recover.hip (recovery), range.hip (indexed range reads) and dec_stream.hip (streaming) sit on what is declared here.
+// single), dec_recover.hip (recovery), range.hip (indexed range reads; search.hip runs on its pass engine) and dec_stream.hip
+// (streaming) sit on what is declared here.
 // The glue between the phases is written once: bz_header_check (_start_bunzip), WalkCands + walk_chain (candidate lookup, bz_walk,
 // chain append), chain_out_offsets (the prefix sum), group_layout / group_prepare / group_verdicts (a batch group, both forms),
 // dec_scratch_batches (phases B and C batch by batch into scratch: recovery and range reads), ShareScratch (a phase's own scratch).

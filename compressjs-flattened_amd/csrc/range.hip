@@ -1,12 +1,12 @@
 // range.hip -- the indexed range reads (cjs_bzip2_index_build, cjs_bzip2_read_ranges[_device]): their two kernels
-// and, on the decode engine (dec_engine.h, decode.hip), their driver.
+// and, on the decode engine (dec_engine.h, decode.hip), their driver: the pass engine (range_engine.h), which the pattern search
+// (search.hip) runs on as well, and the range reads' consumer of it.
 //   rg_slices       the slice gather: every piece (source address, destination address, length) of a pass in one launch per slab.
 //                   It moves the ranges' bytes out of a pass's expanded blocks (to the packed device buffer of the host form, or
 //                   straight into the caller's d_out), and it is the device form's upload: the byte runs of the touched blocks,
 //                   out of the caller's d_in into the pass's upload buffer.
 //   rg_cand_magic   the 48-bit block magic at every candidate the index names (there is no magic scan on this path)
-#include "dec_engine.h"
-#include "bz_index.h"
+#include "range_engine.h"
 #include <algorithm>
 #include <stdlib.h>
 #include <string.h>
@@ -20,16 +20,6 @@ namespace cjs {
 struct Slice { uint64_t src, dst, len; };
 constexpr uint64_t SLICE_TASK = 65536;                 // (a multiple of 16)
 constexpr size_t SLICE_SLAB = 65535;
-
-// The aligned 16 bytes at address p of a source that is bytes [lo, hi): a vector load when they all belong to it; at the two ends
-// of a source the bytes that do, one by one, zeros for the others (nothing outside the source is read).
-__device__ __forceinline__ uint4 rg_ld16(uint64_t p, uint64_t lo, uint64_t hi) {
-  if (p >= lo && p + 16 <= hi) return *reinterpret_cast<const uint4*>(p);
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int i = 0; i < 16; i++) if (p + i >= lo && p + i < hi) w[i >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(p + i) << (8 * (i & 3));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // The interior of a piece: nvec 16-byte vectors, the destination da aligned, the source sa = 16 * q + 4 * K + m behind an aligned
 // address.  Lane i stores vector i (consecutive lanes, consecutive 16 bytes) from the two aligned source vectors it straddles:
@@ -92,11 +82,10 @@ __global__ __launch_bounds__(256) void rg_cand_magic(const uint8_t* __restrict__
 // ---------------------------------------------------------------- the driver
 // recover_core's shape (dec_recover.hip) with the candidates given by an index instead of found by the scan: the blocks that the
 // ranges touch go through phases A, B and C in ascending passes, a pass being what one upload of the batch decoder's group size
-// holds.  Only the
-// byte runs of a pass's blocks are uploaded, packed (RangeUpload), and phase A is told its candidates (DecJob::given): no
-// magic scan, no stream header, no chain walk -- a block stands or falls by its own index entry.  Phase C expands a batch of
-// blocks into scratch (dec_scratch_batches), where their CRCs are computed, and the slice gather takes every piece of every range
-// from there to its place.
+// holds.  Only the byte runs of a pass's blocks are uploaded, packed (RangeUpload), and phase A is told its candidates
+// (DecJob::given): no magic scan, no stream header, no chain walk -- a block stands or falls by its own index entry.  Phase C expands a batch of
+// blocks into scratch (dec_scratch_batches), where their CRCs are computed; the engine hands the batch to its consumer there: the
+// slice gather takes every piece of every range from there to its place (range_run), the scan looks for patterns (search.hip).
 namespace {
 
 void launch_slices(hipStream_t s, const Slice* d_sl, size_t n) {
@@ -107,7 +96,6 @@ void launch_cand_magic(hipStream_t s, const uint8_t* d_in, uint64_t n, const uin
   if (nc) hipLaunchKernelGGL(rg_cand_magic, dim3((nc + 255) / 256), dim3(256), 0, s, d_in, n, d_bits, nc, d_ok);
 }
 
-enum { RG_GOOD = 0, RG_MISMATCH = 1, RG_BAD_CRC = 2 };
 struct RangePiece { uint32_t block, in_off, len, pad; uint64_t out; };      // len bytes from byte in_off of the block to byte `out` of the layout
 
 // What the index alone says about a call: the layout (lay_off / lay_len: range k clipped, packed in range order), the pieces
@@ -177,21 +165,19 @@ void range_slices(std::vector<Slice>& sl, uint64_t src, uint64_t dst, uint64_t l
   for (uint64_t o = 0; o < len; cut = std::min<uint64_t>(len - o, SLICE_TASK)) { sl.push_back(Slice{src + o, dst + o, cut}); o += cut; }
 }
 
-struct RangeStats { uint64_t h2d = 0, d2h = 0, up = 0; uint32_t passes = 0, a_batches = 0, b_batches = 0; size_t slices = 0; };
+}  // namespace
 
-// in: the stream on the host, or nullptr with d_src: the stream on device `dev`.  host_out: the host form's buffer in the plan's
-// layout; else d_out.  verdict / crc_got: per block of the index (RG_*; the computed CRC of an RG_BAD_CRC block).
-int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const RangePlan& P, uint8_t* host_out, uint8_t* d_out,
-              std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st) {
-  const size_t nt = P.touched.size(), cap_blocks = range_pass_blocks(), G = dec_group_bytes();
+// The pass engine (range_engine.h): the passes over `touched`, each block's verdict, every decoded batch handed to `consume`.
+int cjs::range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const std::vector<uint32_t>& touched,
+                      std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st, const RangeConsumer& consume) {
+  const size_t nt = touched.size(), cap_blocks = range_pass_blocks(), G = dec_group_bytes();
   Stream keep;                                                     // one stream for all passes
-  size_t piece_at = 0;                                             // pieces in front of it belong to earlier blocks
   for (size_t t0 = 0; t0 < nt;) {
     // ---- the pass: touched blocks [t0, t1)
     RangeUpload U;
     size_t t1 = t0; uint32_t max_level = 1; uint64_t decoded = 0;
     while (t1 < nt && t1 - t0 < cap_blocks && t1 - t0 < DEC_BATCH_BLOCKS) {
-      const cjs_bz_index_entry& e = ix->e[P.touched[t1]];
+      const cjs_bz_index_entry& e = ix->e[touched[t1]];
       if (t1 > t0 && (U.bytes_with(e, (uint64_t)(uintptr_t)d_src) > G || decoded + e.size > RANGE_PASS_DECODED)) break;
       U.add(e, (uint64_t)(uintptr_t)d_src);
       max_level = std::max(max_level, e.level); decoded += e.size; t1++;
@@ -211,7 +197,7 @@ int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, c
       for (const RangeRun& r : U.runs) memcpy(staged.p + r.at, in + r.lo, (size_t)(r.hi - r.lo));
       J.in = staged.p;
       for (size_t i = 0; i < t1 - t0; i++) {
-        const uint64_t bp = ix->e[P.touched[t0 + i]].bitpos;
+        const uint64_t bp = ix->e[touched[t0 + i]].bitpos;
         uint64_t w = 0;
         for (int q = 0; q < 7; q++) w = (w << 8) | in[(bp >> 3) + q];      // (end_bit > bitpos + 80 and end_bit <= 8 n: inside the stream)
         if (((w >> (8 - (bp & 7))) & 0xFFFFFFFFFFFFull) != MAGIC_BLOCK) continue;
@@ -262,7 +248,7 @@ int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, c
     // ---- the blocks that agree with their entries so far become the chain of phases B and C
     std::vector<uint32_t> chain_blk;
     for (size_t i = 0; i < t1 - t0; i++) {
-      const uint32_t b = P.touched[t0 + i], c = cand_of[i];
+      const uint32_t b = touched[t0 + i], c = cand_of[i];
       const cjs_bz_index_entry& e = ix->e[b];
       verdict[b] = RG_MISMATCH;
       if (c == ~0u || S.cands[c].kind != 0) continue;
@@ -272,66 +258,89 @@ int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, c
       if (v || !bo.count || bo.end_bit - (U.bit[i] - e.bitpos) != e.end_bit || bo.crc != e.crc) continue;
       J.chain.push_back(ib_block(bo, S.tt_ptr[c])); chain_blk.push_back(b);
     }
-    // ---- a decoded batch: the verdicts, and the good blocks' pieces as runs of the scratch (neighbours in both the scratch and the
-    // layout merged)
-    auto deliver = [&](size_t g0, size_t g1, uint8_t* d_exp, ShareScratch& q) {
-      struct Run { uint64_t src, to, len; };                        // len bytes from byte src of d_exp to byte `to` of the layout
-      std::vector<Run> runs;
-      uint64_t packed = 0;
+    // ---- a decoded batch: the verdicts of its blocks, then the consumer
+    auto use = [&](size_t g0, size_t g1, uint8_t* d_exp, ShareScratch& q) {
       for (size_t k = g0; k < g1; k++) {
         const uint32_t b = chain_blk[k];
-        while (piece_at < P.pieces.size() && P.pieces[piece_at].block < b) piece_at++;
         if (J.chain[k].out_len != ix->e[b].size) continue;
         if (J.crc_got[k] != J.chain[k].crc) { verdict[b] = RG_BAD_CRC; crc_got[b] = J.crc_got[k]; continue; }
         verdict[b] = RG_GOOD;
-        for (; piece_at < P.pieces.size() && P.pieces[piece_at].block == b; piece_at++) {
-          const RangePiece& p = P.pieces[piece_at];
-          const uint64_t src = J.out_off[k] + p.in_off;
-          if (!runs.empty() && runs.back().src + runs.back().len == src && runs.back().to + runs.back().len == p.out) runs.back().len += p.len;
-          else runs.push_back(Run{src, p.out, p.len});
-          packed += p.len;
-        }
       }
-      // Host form, a few long runs (one long range, the whole stream): each goes from the scratch straight to its place, no
-      // gather.  Else the slice gather: into d_out, or into a packed buffer that goes to the host in one copy.
-      const bool direct = host_out && runs.size() <= 16;
-      std::vector<Slice> sl;
-      uint8_t* d_pack = nullptr; Slice* d_sl = nullptr;
-      HostBuf bounce;
-      int rc = 0;
-      if (!direct && packed) {
-        if (host_out) CJS_TRY(q.take((void**)&d_pack, (size_t)packed + 64));
-        if (host_out && !(bounce = HostBuf((size_t)packed))) return (int)CJS_E_OUT_OF_MEMORY;
-        uint64_t at = 0;
-        for (const Run& r : runs) {
-          range_slices(sl, (uint64_t)(uintptr_t)(d_exp + r.src), (uint64_t)(uintptr_t)(host_out ? d_pack + at : d_out + r.to), r.len);
-          at += r.len;
-        }
-        CJS_TRY(q.take((void**)&d_sl, sizeof(Slice) * sl.size()));
-        // from here on no way out without the synchronize below: the copy may still be reading `sl`
-        if (hipMemcpyAsync(d_sl, sl.data(), sizeof(Slice) * sl.size(), hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-        else {
-          S.h2d += sizeof(Slice) * sl.size(); st.slices += sl.size();
-          launch_slices(s, d_sl, sl.size());
-          if (hipGetLastError() != hipSuccess) rc = CJS_E_HIP;
-        }
-      }
-      if (!rc && host_out && packed) {
-        if (direct) { for (const Run& r : runs) if (hipMemcpyAsync(host_out + r.to, d_exp + r.src, (size_t)r.len, hipMemcpyDeviceToHost, s) != hipSuccess) { rc = CJS_E_HIP; break; } }
-        else if (hipMemcpyAsync(bounce.p, d_pack, (size_t)packed, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
-        S.d2h += packed;
-      }
-      if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = CJS_E_HIP;
-      if (rc) return rc;
-      if (bounce) { uint64_t at = 0; for (const Run& r : runs) { memcpy(host_out + r.to, bounce.p + at, (size_t)r.len); at += r.len; } }
-      return 0;
+      return consume(RangeBatch{J, S, chain_blk, g0, g1, d_exp, q, s});
     };
-    CJS_TRY(dec_scratch_batches(J, S, deliver));
+    CJS_TRY(dec_scratch_batches(J, S, use));
     st.h2d += S.h2d; st.d2h += S.d2h; st.a_batches += S.a_batches; st.b_batches += S.b_batches;
     S.release_keep_stream(keep);
     t0 = t1;
   }
   return 0;
+}
+
+void cjs::range_bad_detail(const cjs_bz_index* ix, size_t bad, const std::vector<uint8_t>& verdict, const std::vector<uint32_t>& crc_got) {
+  char d[96];
+  if (verdict[bad] == RG_BAD_CRC) { bad_crc_detail(d, sizeof d, crc_got[bad], ix->e[bad].crc); set_detail("%s", d); }
+  else set_detail("index does not match the stream at block %zu", bad);
+}
+
+namespace {
+
+// The range reads' consumer of the engine: the good blocks' pieces as runs of the scratch (neighbours in both the scratch and the
+// layout merged), gathered to their place.  host_out: the host form's buffer in the plan's layout; else d_out.
+int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const RangePlan& P, uint8_t* host_out, uint8_t* d_out,
+              std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st) {
+  size_t piece_at = 0;                                             // pieces in front of it belong to earlier blocks
+  auto deliver = [&](const RangeBatch& B) {
+    uint8_t* const d_exp = B.d_exp; hipStream_t s = B.s; ShareScratch& q = B.q;
+    struct Run { uint64_t src, to, len; };                        // len bytes from byte src of d_exp to byte `to` of the layout
+    std::vector<Run> runs;
+    uint64_t packed = 0;
+    for (size_t k = B.g0; k < B.g1; k++) {
+      const uint32_t b = B.blk[k];
+      while (piece_at < P.pieces.size() && P.pieces[piece_at].block < b) piece_at++;
+      if (verdict[b] != RG_GOOD) continue;
+      for (; piece_at < P.pieces.size() && P.pieces[piece_at].block == b; piece_at++) {
+        const RangePiece& p = P.pieces[piece_at];
+        const uint64_t src = B.J.out_off[k] + p.in_off;
+        if (!runs.empty() && runs.back().src + runs.back().len == src && runs.back().to + runs.back().len == p.out) runs.back().len += p.len;
+        else runs.push_back(Run{src, p.out, p.len});
+        packed += p.len;
+      }
+    }
+    // Host form, a few long runs (one long range, the whole stream): each goes from the scratch straight to its place, no
+    // gather.  Else the slice gather: into d_out, or into a packed buffer that goes to the host in one copy.
+    const bool direct = host_out && runs.size() <= 16;
+    std::vector<Slice> sl;
+    uint8_t* d_pack = nullptr; Slice* d_sl = nullptr;
+    HostBuf bounce;
+    int rc = 0;
+    if (!direct && packed) {
+      if (host_out) CJS_TRY(q.take((void**)&d_pack, (size_t)packed + 64));
+      if (host_out && !(bounce = HostBuf((size_t)packed))) return (int)CJS_E_OUT_OF_MEMORY;
+      uint64_t at = 0;
+      for (const Run& r : runs) {
+        range_slices(sl, (uint64_t)(uintptr_t)(d_exp + r.src), (uint64_t)(uintptr_t)(host_out ? d_pack + at : d_out + r.to), r.len);
+        at += r.len;
+      }
+      CJS_TRY(q.take((void**)&d_sl, sizeof(Slice) * sl.size()));
+      // from here on no way out without the synchronize below: the copy may still be reading `sl`
+      if (hipMemcpyAsync(d_sl, sl.data(), sizeof(Slice) * sl.size(), hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
+      else {
+        B.S.h2d += sizeof(Slice) * sl.size(); st.slices += sl.size();
+        launch_slices(s, d_sl, sl.size());
+        if (hipGetLastError() != hipSuccess) rc = CJS_E_HIP;
+      }
+    }
+    if (!rc && host_out && packed) {
+      if (direct) { for (const Run& r : runs) if (hipMemcpyAsync(host_out + r.to, d_exp + r.src, (size_t)r.len, hipMemcpyDeviceToHost, s) != hipSuccess) { rc = CJS_E_HIP; break; } }
+      else if (hipMemcpyAsync(bounce.p, d_pack, (size_t)packed, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
+      B.S.d2h += packed;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = CJS_E_HIP;
+    if (rc) return rc;
+    if (bounce) { uint64_t at = 0; for (const Run& r : runs) { memcpy(host_out + r.to, bounce.p + at, (size_t)r.len); at += r.len; } }
+    return 0;
+  };
+  return range_engine(in, d_src, ix, P.touched, verdict, crc_got, dev, st, deliver);
 }
 
 // The verdict of every range from the verdicts of the blocks: status, and the detail of the lowest-index failing range's first bad
@@ -350,9 +359,7 @@ void range_verdicts(const cjs_bz_index* ix, const RangePlan& P, const uint64_t* 
     if (bad > b1) continue;
     status[k] = CJS_E_DATA_ERROR; fail[k] = 1;
     if (first) {
-      char d[96];
-      if (verdict[bad] == RG_BAD_CRC) { bad_crc_detail(d, sizeof d, crc_got[bad], ix->e[bad].crc); set_detail("%s", d); }
-      else set_detail("index does not match the stream at block %zu", bad);
+      range_bad_detail(ix, bad, verdict, crc_got);
       first = false;
     }
   }

@@ -214,6 +214,25 @@ Bzip2.readRange = function (inStream, index, offset, length) {
   if (r instanceof Error) { throw r; }
   return r;
 };
+// Pattern search (cjs_bzip2_search): where `patterns` (strings, Buffers or Uint8Arrays; 1..64 of 1..256 bytes) occur in bytes
+// [offset, offset + length) of the decoded data, found on the GPU; only the matches come back.  opts: {offset = 0, length = to the
+// end, nocase = false (ASCII letters only), limit = every match}.  Returns {matches: [[offset, pattern], ...] sorted by (offset,
+// pattern), total: all matches of the window, badBlocks, firstBadBlock (null if none), detail}: a damaged block does not fail
+// the search, nothing matches across it.
+Bzip2.search = function (inStream, index, patterns, opts) {
+  var input = common.coerceInput(inStream), o = opts || {}, parts = [], lens = new Float64Array(patterns.length), r;
+  for (var i = 0; i < patterns.length; i++) {
+    var b = typeof patterns[i] === 'string' ? Buffer.from(patterns[i], 'utf8') : Buffer.from(common.coerceInput(patterns[i]).bytes);
+    parts.push(b); lens[i] = b.length;
+  }
+  try {
+    r = common.addon().bzip2Search(input.bytes, index, new Uint8Array(Buffer.concat(parts)), lens, o.nocase ? 1 : 0, o.offset === undefined ? 0 : o.offset,
+                                   o.length === undefined || o.length === null ? -1 : o.length, o.limit === undefined || o.limit === null ? -1 : o.limit);
+  } catch (e) { rethrow(e); }
+  var matches = [];
+  for (var k = 0; k < r.matches.length; k += 2) { matches.push([r.matches[k], r.matches[k + 1]]); }
+  return { matches: matches, total: r.total, badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, detail: r.detail };
+};
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

@@ -31,6 +31,8 @@ struct Api {
   void (*index_destroy)(cjs_bz_index*) = nullptr;
   int (*read_ranges)(const uint8_t*, size_t, const cjs_bz_index*, const uint64_t*, const uint64_t*, size_t, uint8_t**, size_t*, size_t*, int32_t*,
                      const cjs_opts*) = nullptr;
+  int (*search)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint64_t, uint64_t, cjs_bz_match*, size_t,
+                cjs_bz_search_info*, const cjs_opts*) = nullptr;
   int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
   int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
   int (*enc_finish)(cjs_bz_enc*) = nullptr;
@@ -72,7 +74,7 @@ bool load_api() {
   SYM(bzip2_compress_batch, "cjs_bzip2_compress_batch") SYM(bzip2_decompress_batch, "cjs_bzip2_decompress_batch")
   SYM(bzip2_recover, "cjs_bzip2_recover")
   SYM(index_build, "cjs_bzip2_index_build") SYM(index_save, "cjs_bzip2_index_save") SYM(index_load, "cjs_bzip2_index_load")
-  SYM(index_destroy, "cjs_bzip2_index_destroy") SYM(read_ranges, "cjs_bzip2_read_ranges")
+  SYM(index_destroy, "cjs_bzip2_index_destroy") SYM(read_ranges, "cjs_bzip2_read_ranges") SYM(search, "cjs_bzip2_search")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(dec_create, "cjs_bzip2_dec_create") SYM(dec_write, "cjs_bzip2_dec_write") SYM(dec_finish, "cjs_bzip2_dec_finish")
@@ -266,6 +268,69 @@ napi_value bzip2_read_ranges(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, res, "layout", lta);
   napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &dstr);
   napi_set_named_property(env, res, "detail", dstr);
+  return res;
+}
+
+// bzip2Search(input, index, patterns, lengths, flags, offset, length, limit) -> { matches: Float64Array, total, badBlocks,
+// firstBadBlock, detail }   (Bzip2.search).  patterns: the patterns' bytes back to back; lengths: Float64Array, one per pattern;
+// length < 0: to the end; limit < 0: every match (a count query first).  matches holds (offset, pattern) pairs.
+napi_value bzip2_search(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 8; napi_value argv[8];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *pp = nullptr; size_t n = 0, in = 0, pn = 0;
+  bool is_ta = false;
+  if (argc >= 4) napi_is_typedarray(env, argv[3], &is_ta);
+  napi_typedarray_type t = napi_int8_array; size_t npat = 0; void* ld = nullptr; napi_value lab; size_t loff = 0;
+  if (is_ta) napi_get_typedarray_info(env, argv[3], &t, &npat, &ld, &lab, &loff);
+  if (argc < 8 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &pp, &pn) || !is_ta || t != napi_float64_array) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array patterns, Float64Array lengths, flags, offset, length, limit)"); return nullptr;
+  }
+  double flags = 0, off = 0, len = 0, limit = 0;
+  napi_get_value_double(env, argv[4], &flags); napi_get_value_double(env, argv[5], &off); napi_get_value_double(env, argv[6], &len); napi_get_value_double(env, argv[7], &limit);
+  if (!(off >= 0 && off <= 9007199254740992.0 && off == (double)(uint64_t)off) || !(len <= 9007199254740992.0 && len == (double)(int64_t)len) ||
+      !(limit <= 9007199254740992.0 && limit == (double)(int64_t)limit)) {
+    napi_throw_type_error(env, nullptr, "offsets and lengths are integers from 0 to 2^53"); return nullptr;
+  }
+  std::vector<uint32_t> p_off(npat + 1, 0);
+  uint64_t sum = 0;
+  for (size_t j = 0; j < npat; j++) {
+    const double l = ((const double*)ld)[j];
+    sum += l >= 0 && l <= 65536.0 ? (uint64_t)l : 65536u;      // (an absurd length stays one: the library refuses it)
+    p_off[j + 1] = (uint32_t)std::min<uint64_t>(sum, 0xFFFFFFFFull);
+  }
+  if (sum != pn || npat > 1000000) { napi_throw_type_error(env, nullptr, "the pattern lengths do not add up to the pattern bytes"); return nullptr; }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_search_info si;
+  memset(&si, 0, sizeof si);
+  std::vector<cjs_bz_match> found;
+  const uint64_t ulen = len < 0 ? ~0ull : (uint64_t)len;
+  size_t cap = limit < 0 ? 0 : (size_t)limit;
+  if (limit < 0) {                                                 // the count query
+    rc = api.search(p ? p : &dummy, n, ix, pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, (uint64_t)off, ulen, nullptr, 0, &si, nullptr);
+    cap = (size_t)si.n_matches;
+  }
+  if (rc == 0 && (limit >= 0 || cap)) {
+    try { found.resize(cap); } catch (...) { api.index_destroy(ix); napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
+    rc = api.search(p ? p : &dummy, n, ix, pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, (uint64_t)off, ulen, cap ? found.data() : nullptr, cap, &si, nullptr);
+  }
+  std::string detail = rc == 0 && !si.n_bad_blocks ? "" : api.detail_();      // (before the next call of the library on this thread)
+  api.index_destroy(ix);
+  if (rc != 0) return throw_code(env, rc);
+  const size_t got = (size_t)std::min<uint64_t>(cap, si.n_matches);
+  napi_value res, mab, mta, v; void* mdst;
+  napi_create_object(env, &res);
+  napi_create_arraybuffer(env, sizeof(double) * 2 * got, &mdst, &mab);
+  for (size_t k = 0; k < got; k++) { ((double*)mdst)[2 * k] = (double)found[k].off; ((double*)mdst)[2 * k + 1] = (double)found[k].pattern; }
+  napi_create_typedarray(env, napi_float64_array, 2 * got, mab, 0, &mta);
+  napi_set_named_property(env, res, "matches", mta);
+  napi_create_double(env, (double)si.n_matches, &v); napi_set_named_property(env, res, "total", v);
+  napi_create_double(env, (double)si.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
+  napi_create_double(env, si.n_bad_blocks ? (double)si.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
+  napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
   return res;
 }
 
@@ -605,6 +670,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2Recover", nullptr, bzip2_recover, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2BuildIndex", nullptr, bzip2_build_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2ReadRanges", nullptr, bzip2_read_ranges, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2Search", nullptr, bzip2_search, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncWrite", nullptr, enc_write, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncFinish", nullptr, enc_finish, nullptr, nullptr, nullptr, napi_default, nullptr},

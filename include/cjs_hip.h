@@ -226,6 +226,52 @@ int cjs_bzip2_read_ranges(const uint8_t *in, size_t n, const cjs_bz_index *idx, 
 int cjs_bzip2_read_ranges_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint64_t *off, const uint64_t *len,
                                  size_t count, uint8_t *d_out, size_t out_cap, size_t *out_off, size_t *out_len, int32_t *status,
                                  size_t *out_need, const cjs_opts *opts);
+/* cjs_bzip2_search: where `npat` byte patterns occur in a window of the address space of cjs_bzip2_read_ranges ([0, total_bytes)
+ * of the index), found on the GPU: the decoded bytes never leave it, 16 bytes per match do.  Pattern j is pat[pat_off[j] ..
+ * pat_off[j+1]) (pat_off: npat + 1 ascending offsets, pat_off[0] == 0; 1..CJS_SEARCH_MAX_PATTERNS patterns of
+ * 1..CJS_SEARCH_MAX_PATTERN_BYTES bytes).  The window is [off, min(off + len, total_bytes)); the add saturates, so len =
+ * UINT64_MAX means "to the end".  A match (o, j) exists iff pattern j's bytes stand at decoded offset o, o >= off and o + its
+ * length <= the window's end.  Every start position counts: overlapping matches, matches of several patterns at one offset and
+ * the matches of equal patterns are all reported.  With CJS_SEARCH_NOCASE the ASCII letters 'A'..'Z' equal 'a'..'z', in the
+ * patterns and in the text; no other byte is folded.  The matches are sorted by (off, pattern); `found` gets the first
+ * min(cap, n_matches) of them and nothing past those is written, info->n_matches counts them all (cap = 0, found = NULL: the count
+ * query).  The list does not depend on how the blocks fall into passes and batches.
+ * The TOUCHED blocks are those of non-zero size that overlap the window; each is decoded once and judged as cjs_bzip2_read_ranges
+ * judges it, by the same passes (CJS_RANGE_PASS_BLOCKS, CJS_DEC_GROUP_BYTES, CJS_DEC_BATCH_ELEMS and CJS_DEC_ROW_BYTES act as
+ * there).  A bad block does not fail the call: it returns 0, info->n_bad_blocks / first_bad_block say what was bad,
+ * cjs_last_error_detail() is the first bad block's detail (read_ranges' two texts), and the matches are those that lie wholly
+ * inside runs of consecutive GOOD blocks (blocks of size zero are transparent): nothing matches across a bad block.
+ * Per decoded inverse-BWT batch two kernels run over 16 KiB tiles of the good runs -- one counts the matches of every tile, the
+ * other, behind a scan of the counts, writes them at their rank -- so there is no atomic on the list and no sort.  The last
+ * (longest pattern - 1) bytes of a batch's last run wait in a small buffer of the call until the next batch shows whether the run
+ * goes on.  Device memory held: a pass's (as for cjs_bzip2_read_ranges), 8 bytes per tile, and 16 bytes per match delivered from
+ * one batch.  A batch's matches reach `found` in one copy.
+ * CJS_E_INVALID_ARG before the device is touched: NULL idx, info, pat or pat_off; NULL in with n > 0; NULL found with cap > 0;
+ * n != the index's stream_bytes; npat outside 1..64; a pattern length outside 1..256; pat_off[0] != 0; undefined flag bits.
+ * A window without a touched block: success without touching the device.  Device form: d_in is memory of the GPU (the memory
+ * rules of cjs_bzip2_decompress_device; CJS_E_INVALID_ARG before any launch otherwise); found and info are HOST memory.
+ * opts->device is honoured, n_devices and stats are ignored.  CJS_DEBUG: one "[cjs search]" line per call on stderr (blocks,
+ * passes, upload, H2D and D2H bytes, matches). */
+#define CJS_SEARCH_NOCASE 1u
+#define CJS_SEARCH_MAX_PATTERNS 64
+#define CJS_SEARCH_MAX_PATTERN_BYTES 256
+typedef struct cjs_bz_match {
+  uint64_t off;        /* decoded offset of the match's first byte */
+  uint32_t pattern;    /* which pattern */
+  uint32_t reserved;   /* 0 */
+} cjs_bz_match;
+typedef struct cjs_bz_search_info {
+  uint64_t n_matches;       /* all matches of the window, also when more than cap */
+  uint64_t n_bad_blocks;    /* touched blocks that were not GOOD */
+  uint64_t first_bad_block; /* index of the first of them; ~0 if none */
+  uint64_t blocks_decoded;  /* touched blocks */
+} cjs_bz_search_info;
+int cjs_bzip2_search(const uint8_t *in, size_t n, const cjs_bz_index *idx, const uint8_t *pat, const uint32_t *pat_off, uint32_t npat,
+                     uint32_t flags, uint64_t off, uint64_t len, cjs_bz_match *found, size_t cap, cjs_bz_search_info *info,
+                     const cjs_opts *opts);
+int cjs_bzip2_search_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint8_t *pat, const uint32_t *pat_off,
+                            uint32_t npat, uint32_t flags, uint64_t off, uint64_t len, cjs_bz_match *found, size_t cap,
+                            cjs_bz_search_info *info, const cjs_opts *opts);
 /* Streaming form of cjs_bzip2_compress: the input is written in pieces of any size (zero included), the .bz2 stream is read in
  * pieces of any size, and the bytes read, in order, once cjs_bzip2_enc_finish has returned, are exactly what
  * cjs_bzip2_compress(all written bytes, level) returns -- for every level, every split of the input, every chunk_bytes and every
