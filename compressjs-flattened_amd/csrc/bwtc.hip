@@ -873,7 +873,7 @@ extern "C" int cjs_stage_bwtc_code(const uint64_t* steps, size_t n, int first_by
 // ---------------------------------------------------------------- BWTC.decompressFile (J/BWTC_joined_.js:1827-1920)
 // Range decoding and the adaptive model are one serial chain over the whole file (every decoded symbol feeds the
 // model that decodes the next one), so that part runs on one host thread; the inverse BWT of all blocks
-// (BWT.unbwtransform, n dependent gathers per block in the reference) runs on the GPU (decode.hip).
+// (BWT.unbwtransform, n dependent gathers per block in the reference) runs on the GPU (dec_ibwt.hip).
 //
 // The host side keeps the stream format's arithmetic (it IS the format) but not the reference's data structures: the
 // adaptive models are flat per-symbol counters laid out in CODING ORDER with 16-entry bucket sums, searched linearly

@@ -182,7 +182,7 @@ template <typename K>
 int radix_passes(hipStream_t s, RadixWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit,
                  LaunchTimes* lt = nullptr, const SegGeom* seg = nullptr, const GenSrc* gen = nullptr, bool noval = false,
                  bool first_hist_ready = false, uint8_t* dig = nullptr);
-// ... over nseg segments of `stride` 32-bit keys each (decode.hip: one segment per block)
+// ... over nseg segments of `stride` 32-bit keys each (dec_ibwt.hip: one segment per block)
 int radix_pass_segments(hipStream_t s, RadixWork& w, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride,
                         int lo_bit, int hi_bit, bool noval, bool first_hist_ready);
 
@@ -215,7 +215,7 @@ int bwt_run(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t
 // 1 <= d_len[k] <= stride (device array); BWT bytes to d_U with the same layout.  The slots past a block's length are ignored.
 int bwt_run_var(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint32_t stride, const uint32_t* d_len,
                 uint8_t* d_U, uint32_t* d_pidx);
-// Inverse sentinel BWT of nb blocks back to back in d_T (lengths lens[], primary indices pidx[], host arrays) into d_out (decode.hip)
+// Inverse sentinel BWT of nb blocks back to back in d_T (lengths lens[], primary indices pidx[], host arrays) into d_out (dec_ibwt.hip)
 int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint32_t nb, const uint32_t* lens, const uint32_t* pidx, uint8_t* d_out);
 
 }  // namespace cjs

@@ -1,7 +1,8 @@
-// dec_engine.h -- the Bzip2 decode engine as its drivers see it.  decode.hip defines it (the kernels, phases A / B / C, the header,
-// level and verdict helpers, the single-stream driver bunzip_core); the drivers in dec_batch.hip (host and device batch, device
-// single), dec_recover.hip (recovery), range.hip (indexed range reads; search.hip runs on its pass engine) and dec_stream.hip
-// (streaming) sit on what is declared here.
+// dec_engine.h -- the Bzip2 decode engine as its drivers see it.  Each phase is a file of its own, kernels and host steps together:
+// dec_blocks.hip (phase A), dec_ibwt.hip (phase B), dec_unrle1.hip (phase C); decode.hip holds the header, level and verdict helpers
+// and the single-stream driver bunzip_core.  The drivers in dec_batch.hip (host and device batch, device single), dec_recover.hip
+// (recovery), range.hip (indexed range reads; search.hip runs on its pass engine) and dec_stream.hip (streaming) sit on what is
+// declared here.
 // The glue between the phases is written once: bz_header_check (_start_bunzip), WalkCands + walk_chain (candidate lookup, bz_walk,
 // chain append), chain_out_offsets (the prefix sum), group_layout / group_prepare / group_verdicts (a batch group, both forms),
 // dec_scratch_batches (phases B and C batch by batch into scratch: recovery and range reads), ShareScratch (a phase's own scratch).
@@ -34,7 +35,6 @@ inline IbBlock ib_block(const BlockOut& bo, uint64_t tt) {
   IbBlock ib; ib.tt = tt; ib.count = bo.count; ib.orig = bo.orig; ib.off = 0; ib.woff = 0; ib.out_off = 0; ib.out_len = 0; ib.crc = bo.crc;
   return ib;
 }
-struct RleCarry;            // decode.hip: the RLE1 expansion state at a tile start (written by phase B, read by phase C)
 
 constexpr uint32_t DEC_BATCH_BLOCKS = 65535;          // blocks of an inverse-BWT batch: grid.y of the per-block kernels
 
@@ -161,17 +161,24 @@ struct DecJob {
   std::function<int(DecShare* S)> vet;
 };
 
+// A HIP call inside a phase: any failure is CJS_E_HIP, without a word (the phases' contract; not CJS_HIP_TRY, which prints and
+// tells out-of-memory apart)
+#define DEC_HIP(expr) do { if ((expr) != hipSuccess) return (int)CJS_E_HIP; } while (0)
+
+// ---- the phases.  dec_phase_x(J, S) sets the share's device and stream, runs its steps, leaves their code in S->rc and the time in ms_x
+void dec_phase_a(DecJob* J, DecShare* S);      // dec_blocks.hip: upload, magic scan, speculative decode of every candidate of the share
+void dec_phase_b(DecJob* J, DecShare* S);      // dec_ibwt.hip: inverse BWT + RLE1 length pass of chain blocks [S->c0, S->c1), in batches
+void dec_phase_c(DecJob* J, DecShare* S);      // dec_unrle1.hip: RLE1 expansion to the final offsets, block CRCs, D2H
+size_t dec_next_batch(const DecJob* J, size_t b0, size_t c1);      // dec_ibwt.hip: the inverse-BWT batch [b0, return) of chain blocks [b0, c1)
+// dec_unrle1.hip, for phase B: the RLE1 length pass over the walk's output d_w of nb blocks -> every tile's RleCarry, every block's out_len
+void launch_unrle1_lengths(hipStream_t s, const uint8_t* d_w, IbBlock* d_blocks, uint32_t nb, RleCarry* d_carry, uint32_t carry_tiles);
+void bad_crc_detail(char* d, size_t cap, uint32_t got, uint32_t expected);
 // ---- decode.hip
 double ms_since(std::chrono::steady_clock::time_point a);
-void dec_phase_a(DecJob* J, DecShare* S);      // upload, magic scan, speculative decode of every candidate of the share
-void dec_phase_b(DecJob* J, DecShare* S);      // inverse BWT + RLE1 length pass of chain blocks [S->c0, S->c1), in batches
-void dec_phase_c(DecJob* J, DecShare* S);      // RLE1 expansion to the final offsets, block CRCs, D2H
-size_t dec_next_batch(const DecJob* J, size_t b0, size_t c1);      // the inverse-BWT batch [b0, return) of chain blocks [b0, c1)
 int bz_header_check(const uint8_t* h, size_t n, int* level, const char** why);
 int bz_max_level(const uint8_t* in, size_t n, int level, bool multistream);
 int bz_block_verdict(const BlockOut& bo, uint32_t dbuf_size, uint64_t bitpos, bool timing);
 uint64_t chain_out_offsets(DecJob& J);
-void bad_crc_detail(char* d, size_t cap, uint32_t got, uint32_t expected);
 int bunzip_core(const uint8_t* in, size_t n, int multistream, int mode, uint64_t at_bit, uint8_t** out, size_t* out_n, uint64_t* tab_pos, uint32_t* tab_size,
                 long tab_cap, long* tab_n, const cjs_opts* opts, std::vector<cjs_bz_index_entry>* tab_ix = nullptr);
 // ---- dec_batch.hip

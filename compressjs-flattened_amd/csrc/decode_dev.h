@@ -1,18 +1,16 @@
-// decode_dev.h -- device-side pieces of Bzip2 decode shared by decode.hip (the single-stream kernels) and batch_dec.hip (their
-// batch forms): candidate and block records, the bit readers, the code tables and the chain helpers of stage 2; and the launch
-// functions of batch_dec.hip and dec_device.hip.  The host side of the engine is dec_engine.h.
+// decode_dev.h -- device-side pieces of Bzip2 decode shared by dec_blocks.hip (the single-stream kernels) and batch_dec.hip (their
+// batch forms): candidate and block records, the bit readers, the code tables and the chain helpers of stage 2; the RLE1 tile
+// state that dec_ibwt.hip sizes and dec_unrle1.hip fills; and the launch functions of batch_dec.hip and dec_device.hip.  The host
+// side of the engine is dec_engine.h.
 #pragma once
 #include "cjs_internal.h"
+#include "dec_plan.h"
 #include "prims.hpp"
 
 namespace cjs {
 
 constexpr uint64_t MAGIC_BLOCK = 0x314159265359ull, MAGIC_END = 0x177245385090ull;
-// One splitter every SPL slots of the LF vector.  A walk ends where it lands on a splitter slot -- a 1-in-SPL chance per step --,
-// so the segments are geometric and the walk kernels last as long as the LONGEST of a block's segments, ~SPL x ln(n / SPL) steps
-// of dependent loads (1,100 at 128, 610 at 64): halving SPL halves them; the splitter chain of a block (14,064 nodes at level 9)
-// still fits the ranking kernel's LDS.
-constexpr int SPL = 64;
+// (SPL, the splitter spacing of the inverse BWT; GROUP_SYMS, MAX_SELECTORS: dec_plan.h)
 
 struct Cand { uint64_t bit; uint32_t kind; uint32_t pad; };      // kind 0 = block, 1 = end of stream; pad = row of the block candidate in the decode buffer (set by the host)
 struct BlockOut {
@@ -150,8 +148,6 @@ constexpr uint32_t CH_WIN = CH_T - 64;          // positions of a table in a ste
 constexpr uint32_t CH_ARR2 = CH_T + 64;         // the later groups' tables: CH_WIN positions, and 64 + 64 that map to themselves
 constexpr uint32_t CH_NONE2 = CH_ARR2 - 1;
 constexpr uint32_t CH_WORDS = 2048;             // 32-bit words of the stream kept in LDS (65536 bits: ~180 groups of text)
-constexpr uint32_t GROUP_SYMS = 50;
-constexpr uint32_t MAX_SELECTORS = 32768;
 
 
 // bz_chain's tables: level lv (next^(2^lv)) of table t by byte offset.  A level is read by the round behind it only (the hops aside: 1, 4
@@ -275,6 +271,13 @@ __device__ __forceinline__ uint32_t chain_table_full(const DecShared& S, const u
 //   rank symbols (>= 2) emit one byte each and leave as op (rank - 1, output offset); the bytes must fit the block (:1647, :1663).
 constexpr int SO_PT = 8;                       // symbols per thread (a tile is a dozen barriers whatever it holds: 0.58 / 0.47 / 0.87 ms per 100 MB with 4 / 8 / 16)
 constexpr uint32_t SO_TILE = 1024 * SO_PT, SO_KG = SO_TILE / GROUP_SYMS + 2;      // a tile's symbols lie in SO_KG groups at most
+
+// ---------------------------------------------------------------- 5. RLE1 expansion (dec_unrle1.hip)
+// A block is expanded in tiles of UR_TILE bytes, one workgroup of 1024 threads each.  RleCarry: the state at a tile's start (start of
+// the current stretch, its carried bit, output bytes so far), one per chain block and tile: written by phase B, read by phase C.
+constexpr int UR_BPT = 16;                          // bytes per thread: the ten-step function scan over the 1024 threads is most of a tile, whatever the bytes per thread (4 bytes: 1.05 ms per 100 MB for the length pass)
+constexpr uint32_t UR_TILE = 1024 * UR_BPT;
+struct RleCarry { uint32_t cur_start, cur_c0, out_base, pad; };
 
 // batch_dec.hip: the batch forms, launched on stream s (input k of the group: bytes [st[k], en[k]); per candidate: cend = the end
 // of its input, cdsz = 100000 x that input's largest level; rlim: one word per row of the row batch)

@@ -2,7 +2,7 @@
 //
 // Sorts n keys of type K (uint64_t / uint32_t), with or without a 32-bit value each, on bits [lo_bit, hi_bit) between two
 // buffers.  Used by the suffix sort (bwt.hip: round 1, the groups too large for the tile sorters, the whole-array fallbacks) and
-// by the inverse BWT (decode.hip: stable partition of the BWT bytes).  Integer sort/scan only (no MFMA); HBM-bound on the
+// by the inverse BWT (dec_ibwt.hip: stable partition of the BWT bytes).  Integer sort/scan only (no MFMA); HBM-bound on the
 // scatter passes.
 #include "radix.hpp"
 

@@ -1,5 +1,5 @@
-"""-m gpu: the second half of the Bzip2 decoder -- the inverse BWT (ib_*) and the RLE1 expansion (unrle1_*, ur_load) of
-csrc/decode.hip -- on blocks built byte by byte (bzblocks.py), against the Python restatement of the reference's two loops.
+"""-m gpu: the second half of the Bzip2 decoder -- the inverse BWT (ib_*, csrc/dec_ibwt.hip) and the RLE1 expansion (unrle1_*,
+ur_load, csrc/dec_unrle1.hip) -- on blocks built byte by byte (bzblocks.py), against the Python restatement of the reference's two loops.
 
 Family R gives the expansion its borders: count bytes on either side of a thread's 16 bytes, a wave's 1024 and a tile's 16384,
 count bytes equal to their run's byte, single-value stretches over one and two tile borders, block ends in the middle of a run,
