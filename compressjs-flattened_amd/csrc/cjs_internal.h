@@ -217,5 +217,9 @@ int bwt_run_var(hipStream_t s, BwtWork& w, const uint8_t* d_T, uint32_t nb, uint
                 uint8_t* d_U, uint32_t* d_pidx);
 // Inverse sentinel BWT of nb blocks back to back in d_T (lengths lens[], primary indices pidx[], host arrays) into d_out (dec_ibwt.hip)
 int ibwt_sentinel_run(hipStream_t s, const uint8_t* d_T, uint32_t max_len, uint32_t nb, const uint32_t* lens, const uint32_t* pidx, uint8_t* d_out);
+// BWTC model evaluation of nb blocks (bwtc_model.hip): one workgroup per block, DefSumModel (fast, levels 1-5) or FenwickModel
+// (levels 6-9); reads mb.A / a_stride / asz / npos (mtf.h), leaves block k's coder steps at d_steps + k * step_stride, their count in d_nsteps[k]
+struct MtfBufs;
+int bwtc_model_launch(hipStream_t s, bool fast, const MtfBufs& mb, uint32_t nb, uint64_t* d_steps, size_t step_stride, uint32_t* d_nsteps);
 
 }  // namespace cjs

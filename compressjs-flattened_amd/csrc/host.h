@@ -2,6 +2,8 @@
 // context caches, scoped DevPool buffers and worker threads.
 #pragma once
 #include "cjs_internal.h"
+#include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <mutex>
 #include <thread>
@@ -80,6 +82,15 @@ struct HostBuf : Owner<uint8_t*, HostGive> {
   explicit HostBuf(size_t bytes) { p = (uint8_t*)HostPool::take(bytes); }
   uint8_t* release() { uint8_t* q = p; p = nullptr; return q; }
 };
+
+// v's bytes as a result of the C ABI: malloc'd (the caller frees it with cjs_free), *out / *out_n set; on failure both are left alone
+inline int malloc_result(const std::vector<uint8_t>& v, uint8_t** out, size_t* out_n) {
+  uint8_t* host = (uint8_t*)malloc(v.size() ? v.size() : 1);
+  if (!host) return CJS_E_OUT_OF_MEMORY;
+  if (!v.empty()) memcpy(host, v.data(), v.size());
+  *out = host; *out_n = v.size();
+  return 0;
+}
 
 // Device d made current at scope exit (the caller's device, restored on every path out).
 struct RestoreDevice {

@@ -9,7 +9,7 @@
  *   - the reference's own known answers (cyclic-BWT KATs NPM/test/bwtest.js:39-79, allocator
  *     KATs NPM/test/huffman.js:15-76, decoder goldens sample0-4.bz2, .bzt tables, block dumps)
  *   - outputs of the reference JS itself run under Node in the build container, committed as
- *     tests/golden/*.json by tests/golden/make_golden.js (length + sha256 of every stream).
+ *     the .json files of tests/golden/ by tests/golden/make_golden.js (length + sha256 of every stream).
  *
  * Citations: J/ = /root/reference/ (Bzip2_joined_.js, BWTC_joined_.js).
  */

@@ -1,4 +1,4 @@
-"""The host range coder of BWTC compression (HostCoder in csrc/bwtc.hip: division, reciprocal and two-thread forms of one
+"""The host range coder of BWTC compression (HostCoder in csrc/bwtc_host.h: division, reciprocal and two-thread forms of one
 arithmetic) against the oracle's coder, byte for byte, on the crafted step lists of tests/bwtc_cases.py, through
 cjs_stage_bwtc_code in both modes.  Host logic only: runs without a GPU."""
 import numpy as np

@@ -1,5 +1,7 @@
 """Host logic of the product that needs no GPU: the serial entropy stage of BWTC.decompressFile
-(cjs_stage_bwtc_entropy_decode: range decoder + adaptive model + RLE2 + MTF inverse, J/BWTC_joined_.js:1827-1913).
+(cjs_stage_bwtc_entropy_decode over csrc/bwtc_decode.h: range decoder + adaptive model + RLE2 + MTF inverse,
+J/BWTC_joined_.js:1827-1913).  These tests see return codes only; the same decoder on thousands of damaged streams under the host
+compiler's sanitizers is tests/test_bwtc_host_check.py.
 
 The streams come from the oracle's BWTC encoder (pinned by the reference-cut goldens in test_oracle.py); the decoded BWT
 columns / primary indices are compared with the oracle's sentinel BWT of every block.  Negative cases: truncated and
