@@ -137,6 +137,21 @@ def load_library():
     U32, U64 = ctypes.c_uint32, ctypes.c_uint64
     L.cjs_bzip2_search.argtypes = [u8p, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
     L.cjs_bzip2_search_device.argtypes = [V, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
+    PU32, PI32 = ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_int32)
+    L.cjs_bzip2_lines_build.argtypes = [u8p, S, V, ctypes.POINTER(V), V]
+    L.cjs_bzip2_lines_build_device.argtypes = [V, S, V, ctypes.POINTER(V), V]
+    L.cjs_bzip2_lines_create.argtypes = [V, PU32, S, ctypes.POINTER(V)]
+    L.cjs_bzip2_lines_save.argtypes = [V, PP, PS]
+    L.cjs_bzip2_lines_load.argtypes = [u8p, S, V, ctypes.POINTER(V)]
+    L.cjs_bzip2_lines_info.argtypes = [V, PU, PU, PU]
+    L.cjs_bzip2_lines_counts.argtypes = [V, PU32, ctypes.c_long]
+    L.cjs_bzip2_lines_counts.restype = ctypes.c_long
+    L.cjs_bzip2_lines_destroy.argtypes = [V]
+    L.cjs_bzip2_lines_destroy.restype = None
+    L.cjs_bzip2_lines_locate.argtypes = [u8p, S, V, V, PU, S, PU, PI32, V]
+    L.cjs_bzip2_lines_locate_device.argtypes = [V, S, V, V, PU, S, PU, PI32, V]
+    L.cjs_bzip2_lines_number.argtypes = [u8p, S, V, V, PU, S, PU, PI32, V]
+    L.cjs_bzip2_lines_number_device.argtypes = [V, S, V, V, PU, S, PU, PI32, V]
     L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
     L.cjs_bzip2_enc_write.argtypes = [V, V, S]
     L.cjs_bzip2_enc_finish.argtypes = [V]
@@ -756,6 +771,156 @@ class Bzip2Index:
         ranges = [(max(o - before, 0), min(o, before) + len(pats[j]) + after) for o, j in res.matches]
         ctx = self.read_ranges(data, ranges) if ranges else []
         return [(o, j, c) for (o, j), c in zip(res.matches, ctx)]
+
+    def line_starts(self, data, lines, line_numbers):
+        """start(k) of every line number (cjs_bzip2_lines_locate): -> (starts, status, detail), uint64 / int32 arrays"""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        return _lines_ask(lambda *a: L.cjs_bzip2_lines_locate(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a, None), line_numbers)
+
+    def line_numbers(self, data, lines, offsets):
+        """number(o) of every decoded offset (cjs_bzip2_lines_number): -> (numbers, status, detail)"""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        return _lines_ask(lambda *a: L.cjs_bzip2_lines_number(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a, None), offsets)
+
+    def read_lines(self, data, lines, spans):
+        """spans = [(first, count)]: lines first .. first + count - 1, newlines included -- one locate of 2 * len(spans)
+        questions, then one read_ranges.  -> per span its bytes, or a CjsError for a span that touches a bad block"""
+        L = load_library()
+        spans = [(int(a), int(c)) for a, c in spans]
+        if not spans:
+            return []
+        ask = [min(x, 2 ** 64 - 1) for a, c in spans for x in (a, a + c)]
+        at, st, detail = self.line_starts(data, lines, ask)
+        res = [None] * len(spans)
+        ranges, where = [], []
+        for k in range(len(spans)):
+            bad = int(st[2 * k]) or int(st[2 * k + 1])
+            if bad:
+                res[k] = CjsError(bad, L.cjs_strerror(bad).decode() + (": " + detail if detail else ""))
+                detail = ""
+            else:
+                ranges.append((int(at[2 * k]), int(at[2 * k + 1]) - int(at[2 * k])))
+                where.append(k)
+        for k, r in zip(where, self.read_ranges(data, ranges) if ranges else []):
+            res[k] = r
+        return res
+
+    def grep_lines(self, data, lines, patterns, **search_kw):
+        """bzgrep -n: search, then number of the match offsets, then locate of each distinct line and its successor, then one
+        read_ranges.  -> [(line_no, line_bytes, [(off, pattern), ...])] ascending, each line once (a match that spans lines
+        belongs to the line its first byte is in; a CjsError in place of the bytes of a line that touches a bad block)"""
+        res = self.search(data, patterns, **search_kw)
+        if not res.matches:
+            return []
+        numbers, st, _ = self.line_numbers(data, lines, [o for o, j in res.matches])
+        by_line = {}
+        for (o, j), no, s in zip(res.matches, numbers.tolist(), st.tolist()):
+            if not s:
+                by_line.setdefault(no, []).append((o, j))
+        order = sorted(by_line)
+        text = self.read_lines(data, lines, [(no, 1) for no in order])
+        return [(no, t, by_line[no]) for no, t in zip(order, text)]
+
+
+class Bzip2Lines:
+    """The line table of an indexed .bz2 stream (cjs_bz_lines): the newlines of every block of one Bzip2Index.  Made by build()
+    (one counting pass on the GPU), load() (the serialised form save() returns) or create() (a caller's counts)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self._fin = weakref.finalize(self, load_library().cjs_bzip2_lines_destroy, handle)
+
+    @staticmethod
+    def build(data, index):
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        _check(L.cjs_bzip2_lines_build(keep.ctypes.data_as(u8p), data.size, index._h, ctypes.byref(h), None))
+        return Bzip2Lines(h)
+
+    @staticmethod
+    def load(raw, index):
+        L = load_library()
+        raw = _coerce_input(raw)
+        keep = raw if raw.size else np.zeros(1, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        _check(L.cjs_bzip2_lines_load(keep.ctypes.data_as(u8p), raw.size, index._h, ctypes.byref(h)))
+        return Bzip2Lines(h)
+
+    @staticmethod
+    def create(index, counts):
+        L = load_library()
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        keep = c if c.size else np.zeros(1, dtype=np.uint32)
+        h = ctypes.c_void_p()
+        _check(L.cjs_bzip2_lines_create(index._h, keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), c.size, ctypes.byref(h)))
+        return Bzip2Lines(h)
+
+    def save(self):
+        L = load_library()
+        out, out_n = u8p(), ctypes.c_size_t(0)
+        _check(L.cjs_bzip2_lines_save(self._h, ctypes.byref(out), ctypes.byref(out_n)))
+        raw = ctypes.string_at(out, out_n.value)
+        L.cjs_free(out)
+        return raw
+
+    def _info(self):
+        b, nl, t = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(load_library().cjs_bzip2_lines_info(self._h, ctypes.byref(b), ctypes.byref(nl), ctypes.byref(t)))
+        return b.value, nl.value, t.value
+
+    blocks = property(lambda self: self._info()[0])
+    newlines = property(lambda self: self._info()[1])
+    total = property(lambda self: self._info()[2])
+
+    def counts(self):
+        """the newlines of every block, a uint32 array"""
+        c = np.zeros(max(self.blocks, 1), dtype=np.uint32)
+        nb = load_library().cjs_bzip2_lines_counts(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), c.size)
+        return c[:nb]
+
+    def close(self):
+        self._fin()
+
+
+def _lines_ask(call, questions):
+    """call(q, count, out, status) -> rc: the answers, the statuses and the lowest-index failing question's detail"""
+    q = np.ascontiguousarray(np.asarray(list(questions), dtype=np.uint64).reshape(-1))
+    count = q.size
+    keep = q if count else np.zeros(1, dtype=np.uint64)
+    out, st = np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.int32)
+    PU = ctypes.POINTER(ctypes.c_uint64)
+    _check(call(keep.ctypes.data_as(PU), count, out.ctypes.data_as(PU), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    detail = load_library().cjs_last_error_detail().decode() if st[:count].any() else ""
+    return out[:count], st[:count], detail
+
+
+def lines_build_device(d_in_ptr, n, index, device=-1):
+    """Bzip2Lines.build with the stream in GPU memory (cjs_bzip2_lines_build_device; the memory rules of decompress_device)"""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    h = ctypes.c_void_p()
+    _check(L.cjs_bzip2_lines_build_device(d_in_ptr, n, index._h, ctypes.byref(h), ctypes.byref(opts)))
+    return Bzip2Lines(h)
+
+
+def line_starts_device(d_in_ptr, n, index, lines, line_numbers, device=-1):
+    """Bzip2Index.line_starts with the stream in GPU memory (cjs_bzip2_lines_locate_device).  The result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _lines_ask(lambda *a: L.cjs_bzip2_lines_locate_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), line_numbers)
+
+
+def line_numbers_device(d_in_ptr, n, index, lines, offsets, device=-1):
+    """Bzip2Index.line_numbers with the stream in GPU memory (cjs_bzip2_lines_number_device).  The result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _lines_ask(lambda *a: L.cjs_bzip2_lines_number_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), offsets)
 
 
 class SearchResult:

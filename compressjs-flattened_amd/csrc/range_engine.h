@@ -1,7 +1,7 @@
 // range_engine.h -- the pass engine of the indexed entry points (range.hip defines it): the blocks an index names go through phases
 // A, B and C in bounded passes, each judged against its entry, and every decoded inverse-BWT batch is handed to a consumer while it
-// stands expanded in device scratch.  Two consumers: the slice gather of the range reads (range.hip) and the pattern scan
-// (search.hip).
+// stands expanded in device scratch.  Three consumers: the slice gather of the range reads (range.hip), the pattern scan
+// (search.hip) and the newline count, select and rank of the line table (lines.hip).
 #pragma once
 #include "dec_engine.h"
 #include "bz_index.h"

@@ -233,6 +233,34 @@ Bzip2.search = function (inStream, index, patterns, opts) {
   for (var k = 0; k < r.matches.length; k += 2) { matches.push([r.matches[k], r.matches[k + 1]]); }
   return { matches: matches, total: r.total, badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, detail: r.detail };
 };
+// The line table (cjs_bzip2_lines_*): lines are numbered from 0 and end with their '\n' (0x0A, nothing else); line N, behind the
+// last newline, is the unterminated tail.  buildLineIndex counts the newlines of every block on the GPU and returns the table in
+// its serialised form (a Uint8Array to keep beside the index).  lineStarts gives the decoded offset where each line starts (the
+// end of the data for a line past the last), lineNumbers the line each decoded offset belongs to; both decode at most one block
+// per question and return {values: [...], status: [...], detail}: status is 0 or the code of a question whose block is damaged
+// (its value is 0 then).  readLines returns lines first .. first + count - 1 as bytes, by one lineStarts and one readRange.
+Bzip2.buildLineIndex = function (inStream, index) {
+  var input = common.coerceInput(inStream);
+  try { return common.addon().bzip2BuildLineIndex(input.bytes, index); } catch (e) { rethrow(e); }
+};
+function linesAsk(inStream, index, lineIndex, questions, kind) {
+  var input = common.coerceInput(inStream), r;
+  try { r = common.addon().bzip2LinesAsk(input.bytes, index, lineIndex, Float64Array.from(questions), kind); } catch (e) { rethrow(e); }
+  return { values: Array.from(r.answers), status: Array.from(r.status), detail: r.detail };
+}
+Bzip2.lineStarts = function (inStream, index, lineIndex, lines) { return linesAsk(inStream, index, lineIndex, lines, 0); };
+Bzip2.lineNumbers = function (inStream, index, lineIndex, offsets) { return linesAsk(inStream, index, lineIndex, offsets, 1); };
+Bzip2.readLines = function (inStream, index, lineIndex, first, count) {
+  var at = Bzip2.lineStarts(inStream, index, lineIndex, [first, first + count]);
+  for (var k = 0; k < 2; k++) {
+    if (at.status[k] !== 0) {
+      var t = new TypeError((Messages[at.status[k]] || 'Data error') + (at.detail ? ': ' + at.detail : ''));
+      t.errorCode = at.status[k];
+      throw t;
+    }
+  }
+  return Bzip2.readRange(inStream, index, at.values[0], at.values[1] - at.values[0]);
+};
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

@@ -33,6 +33,12 @@ struct Api {
                      const cjs_opts*) = nullptr;
   int (*search)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint64_t, uint64_t, cjs_bz_match*, size_t,
                 cjs_bz_search_info*, const cjs_opts*) = nullptr;
+  int (*lines_build)(const uint8_t*, size_t, const cjs_bz_index*, cjs_bz_lines**, const cjs_opts*) = nullptr;
+  int (*lines_save)(const cjs_bz_lines*, uint8_t**, size_t*) = nullptr;
+  int (*lines_load)(const uint8_t*, size_t, const cjs_bz_index*, cjs_bz_lines**) = nullptr;
+  void (*lines_destroy)(cjs_bz_lines*) = nullptr;
+  int (*lines_locate)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, const uint64_t*, size_t, uint64_t*, int32_t*, const cjs_opts*) = nullptr;
+  int (*lines_number)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, const uint64_t*, size_t, uint64_t*, int32_t*, const cjs_opts*) = nullptr;
   int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
   int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
   int (*enc_finish)(cjs_bz_enc*) = nullptr;
@@ -75,6 +81,8 @@ bool load_api() {
   SYM(bzip2_recover, "cjs_bzip2_recover")
   SYM(index_build, "cjs_bzip2_index_build") SYM(index_save, "cjs_bzip2_index_save") SYM(index_load, "cjs_bzip2_index_load")
   SYM(index_destroy, "cjs_bzip2_index_destroy") SYM(read_ranges, "cjs_bzip2_read_ranges") SYM(search, "cjs_bzip2_search")
+  SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
+  SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(dec_create, "cjs_bzip2_dec_create") SYM(dec_write, "cjs_bzip2_dec_write") SYM(dec_finish, "cjs_bzip2_dec_finish")
@@ -331,6 +339,84 @@ napi_value bzip2_search(napi_env env, napi_callback_info info) {
   napi_create_double(env, (double)si.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
   napi_create_double(env, si.n_bad_blocks ? (double)si.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
   napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
+  return res;
+}
+
+// bzip2BuildLineIndex(input, index) -> Uint8Array: the serialised line table of the stream under its serialised block index
+// (Bzip2.buildLineIndex)
+napi_value bzip2_build_line_index(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr; size_t n = 0, in = 0;
+  if (argc < 2 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in)) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index)"); return nullptr;
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_lines* lt = nullptr;
+  rc = api.lines_build(p ? p : &dummy, n, ix, &lt, nullptr);
+  api.index_destroy(ix);
+  if (rc != 0) return throw_code(env, rc);
+  uint8_t* raw = nullptr; size_t raw_n = 0;
+  rc = api.lines_save(lt, &raw, &raw_n);
+  api.lines_destroy(lt);
+  if (rc != 0) return throw_code(env, rc);
+  return wrap_result(env, raw, raw_n);
+}
+
+// bzip2LinesAsk(input, index, lineIndex, questions, kind) -> { answers: Float64Array, status: Float64Array, detail: string }
+// (Bzip2.lineStarts: kind 0, questions = line numbers; Bzip2.lineNumbers: kind 1, questions = decoded offsets).  questions:
+// Float64Array of integers from 0 to 2^53; detail is the lowest-index failing question's ("" when none failed).
+napi_value bzip2_lines_ask(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 5; napi_value argv[5];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *lp = nullptr; size_t n = 0, in = 0, ln = 0;
+  bool is_ta = false;
+  if (argc >= 4) napi_is_typedarray(env, argv[3], &is_ta);
+  napi_typedarray_type t = napi_int8_array; size_t count = 0; void* qd = nullptr; napi_value qab; size_t qoff = 0;
+  if (is_ta) napi_get_typedarray_info(env, argv[3], &t, &count, &qd, &qab, &qoff);
+  if (argc < 5 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &lp, &ln) || !is_ta || t != napi_float64_array) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array line index, Float64Array questions, kind)"); return nullptr;
+  }
+  int32_t kind = 0;
+  napi_get_value_int32(env, argv[4], &kind);
+  std::vector<uint64_t> q(count + 1), a(count + 1); std::vector<int32_t> status(count + 1);
+  for (size_t k = 0; k < count; k++) {
+    const double v = ((const double*)qd)[k];
+    if (!(v >= 0 && v <= 9007199254740992.0 && v == (double)(uint64_t)v)) {      // (negative, NaN, above 2^53 or with a fraction)
+      napi_throw_type_error(env, nullptr, "line numbers and offsets are integers from 0 to 2^53"); return nullptr;
+    }
+    q[k] = (uint64_t)v;
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_lines* lt = nullptr;
+  rc = api.lines_load(lp ? lp : &dummy, ln, ix, &lt);
+  if (rc != 0) { api.index_destroy(ix); return throw_code(env, rc); }
+  rc = (kind ? api.lines_number : api.lines_locate)(p ? p : &dummy, n, ix, lt, q.data(), count, a.data(), status.data(), nullptr);
+  std::string detail = api.detail_();                            // (before the next call of the library on this thread)
+  api.lines_destroy(lt);
+  api.index_destroy(ix);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value res, ab, ta, dstr; void* dst;
+  napi_create_object(env, &res);
+  napi_create_arraybuffer(env, sizeof(double) * count, &dst, &ab);
+  for (size_t k = 0; k < count; k++) ((double*)dst)[k] = (double)a[k];
+  napi_create_typedarray(env, napi_float64_array, count, ab, 0, &ta);
+  napi_set_named_property(env, res, "answers", ta);
+  napi_create_arraybuffer(env, sizeof(double) * count, &dst, &ab);
+  bool failed = false;
+  for (size_t k = 0; k < count; k++) { ((double*)dst)[k] = (double)status[k]; failed = failed || status[k]; }
+  napi_create_typedarray(env, napi_float64_array, count, ab, 0, &ta);
+  napi_set_named_property(env, res, "status", ta);
+  napi_create_string_utf8(env, failed ? detail.c_str() : "", NAPI_AUTO_LENGTH, &dstr);
+  napi_set_named_property(env, res, "detail", dstr);
   return res;
 }
 
@@ -671,6 +757,8 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2BuildIndex", nullptr, bzip2_build_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2ReadRanges", nullptr, bzip2_read_ranges, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Search", nullptr, bzip2_search, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2BuildLineIndex", nullptr, bzip2_build_line_index, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncWrite", nullptr, enc_write, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncFinish", nullptr, enc_finish, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -272,6 +272,62 @@ int cjs_bzip2_search(const uint8_t *in, size_t n, const cjs_bz_index *idx, const
 int cjs_bzip2_search_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint8_t *pat, const uint32_t *pat_off,
                             uint32_t npat, uint32_t flags, uint64_t off, uint64_t len, cjs_bz_match *found, size_t cap,
                             cjs_bz_search_info *info, const cjs_opts *opts);
+/* The line table of an indexed stream: seek by line, number offsets (`wc -l`, `sed -n 'a,bp'`, `bzgrep -n` over a .bz2 stream).
+ * A NEWLINE is the byte 0x0A and no other (CR does not count).  With off[b] the decoded offset of block b of `idx`, total =
+ * total_bytes, nl[b] the newlines among block b's decoded bytes, cum[b] the sum of nl[0..b) and N their total:
+ *   lines are numbered from 0; start(0) = 0; for 1 <= k <= N start(k) = the decoded offset of the k-th newline (1-based) + 1;
+ *   for k > N start(k) = total.  Line k is the bytes [start(k), start(k+1)), its newline included; line N is the unterminated
+ *   tail and may be empty.  number(o) = the newlines in decoded bytes [0, min(o, total)): the line that byte o belongs to.
+ * A cjs_bz_lines holds nl[] for one index; it is immutable once made and shared between threads like an index.
+ * _build (and _build_device: d_in under the memory rules of cjs_bzip2_decompress_device) counts the newlines on the GPU in one
+ * pass of the range engine over every block of non-zero size; four bytes per block come back.  A touched block that is not GOOD
+ * by cjs_bzip2_read_ranges' rules fails the call: CJS_E_DATA_ERROR with that block's detail (the lowest such block), no table.
+ * An index without a block of non-zero size: success without touching the device.  _create takes a caller's counts[count];
+ * _save gives the serialised form (*bytes: malloc'd, cjs_free), _load reads it:
+ *   40-byte header: the 8 bytes "CJSBZLN1", u32 version = 1, u32 flags = 0, u64 blocks, u64 total_bytes, u32 crc_fold (the
+ *   index entries' stored CRCs folded from 0 as c = rol1(c) ^ crc, the stream-CRC rule), u32 reserved = 0; then `blocks` u32
+ *   counts; everything little-endian.
+ * _create and _load refuse with CJS_E_INVALID_ARG and a detail text, before any device is touched: wrong magic, version or
+ * length; flag or reserved bits set; blocks, total_bytes or crc_fold not those of idx; counts[b] > size[b].  NULL arguments:
+ * CJS_E_INVALID_ARG.  _info: any out pointer may be NULL.  _counts copies the first min(cap, blocks) counts and returns the
+ * number of blocks.  A table belongs to one index: every call that takes both compares blocks, total_bytes and crc_fold again
+ * and refuses with CJS_E_INVALID_ARG, "the line table is of another index".
+ * _locate: start[k] = start(line[k]).  _number: line[k] = number(off[k]).  Queries may repeat and come in any order; count == 0
+ * is a success.  The table alone answers line[k] == 0, line[k] > N, off[k] at a block's first byte and off[k] >= total: such a
+ * query touches no block, and a call in which no query needs a block does not touch the device.  Else the TOUCHED block of a
+ * locate query is the one block b with cum[b] < line[k] <= cum[b+1], of a number query the block that holds off[k].  Each is
+ * decoded once, however many queries want it, judged as cjs_bzip2_read_ranges judges it and by the same passes
+ * (CJS_RANGE_PASS_BLOCKS, CJS_DEC_GROUP_BYTES, CJS_DEC_BATCH_ELEMS and CJS_DEC_ROW_BYTES act as there).  A query whose block is
+ * bad gets status[k] = CJS_E_DATA_ERROR and start / line 0; other queries are unaffected and the call returns 0;
+ * cjs_last_error_detail() is then the detail of the lowest-index failing query's block.  Every tile of a touched block is
+ * counted anyway, so a GOOD block whose newline count is not the table's fails its queries the same way, with the detail
+ * "line table does not match the stream at block <b>".
+ * Per decoded inverse-BWT batch, over 16 KiB tiles of the blocks (a tile never spans two blocks): one kernel counts the newlines
+ * of every tile, one scans the counts per block, and one wave per query finds the r-th newline of its block (locate) or counts
+ * those in front of its offset (number).  No atomics; the answers do not depend on how the blocks fall into passes and batches.
+ * Eight bytes per query and four per touched block leave the GPU.  Device memory held: a pass's (as for cjs_bzip2_read_ranges),
+ * 4 bytes per tile of the batch, and 16 bytes per query of the batch: never proportional to the stream.
+ * CJS_E_INVALID_ARG before the device is touched: NULL idx or lines; NULL arrays with count > 0; NULL in with n > 0; n != the
+ * index's stream_bytes; a foreign table.  All arrays are HOST memory in both forms.  opts->device is honoured, n_devices and
+ * stats are ignored.  CJS_DEBUG: one "[cjs lines]" line per call on stderr (form, build / locate / number, queries, blocks
+ * touched, passes, inverse-BWT batches, H2D and D2H bytes). */
+typedef struct cjs_bz_lines cjs_bz_lines;
+int cjs_bzip2_lines_build(const uint8_t *in, size_t n, const cjs_bz_index *idx, cjs_bz_lines **lines, const cjs_opts *opts);
+int cjs_bzip2_lines_build_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, cjs_bz_lines **lines, const cjs_opts *opts);
+int cjs_bzip2_lines_create(const cjs_bz_index *idx, const uint32_t *counts, size_t count, cjs_bz_lines **lines);
+int cjs_bzip2_lines_save(const cjs_bz_lines *lines, uint8_t **bytes, size_t *nbytes);
+int cjs_bzip2_lines_load(const uint8_t *bytes, size_t nbytes, const cjs_bz_index *idx, cjs_bz_lines **lines);
+int cjs_bzip2_lines_info(const cjs_bz_lines *lines, uint64_t *blocks, uint64_t *newlines, uint64_t *total_bytes);
+long cjs_bzip2_lines_counts(const cjs_bz_lines *lines, uint32_t *counts, long cap);
+void cjs_bzip2_lines_destroy(cjs_bz_lines *lines);
+int cjs_bzip2_lines_locate(const uint8_t *in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, const uint64_t *line,
+                           size_t count, uint64_t *start, int32_t *status, const cjs_opts *opts);
+int cjs_bzip2_lines_locate_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines,
+                                  const uint64_t *line, size_t count, uint64_t *start, int32_t *status, const cjs_opts *opts);
+int cjs_bzip2_lines_number(const uint8_t *in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, const uint64_t *off,
+                           size_t count, uint64_t *line, int32_t *status, const cjs_opts *opts);
+int cjs_bzip2_lines_number_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines,
+                                  const uint64_t *off, size_t count, uint64_t *line, int32_t *status, const cjs_opts *opts);
 /* Streaming form of cjs_bzip2_compress: the input is written in pieces of any size (zero included), the .bz2 stream is read in
  * pieces of any size, and the bytes read, in order, once cjs_bzip2_enc_finish has returned, are exactly what
  * cjs_bzip2_compress(all written bytes, level) returns -- for every level, every split of the input, every chunk_bytes and every
