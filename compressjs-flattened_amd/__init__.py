@@ -68,6 +68,19 @@ class SearchInfo(ctypes.Structure):
 
 SEARCH_NOCASE = 1     # CJS_SEARCH_NOCASE
 
+
+class Diff(ctypes.Structure):
+    """cjs_bz_diff: one differing byte of a compare (16 bytes)."""
+    _fields_ = [("off", ctypes.c_uint64), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+
+
+class CompareInfo(ctypes.Structure):
+    """cjs_bz_cmp_info (64 bytes)."""
+    _fields_ = [("n_diffs", ctypes.c_uint64), ("first_diff", ctypes.c_uint64), ("compared", ctypes.c_uint64), ("n_bad_blocks", ctypes.c_uint64),
+                ("first_bad_block", ctypes.c_uint64), ("blocks_decoded", ctypes.c_uint64), ("n_bad_blocks_b", ctypes.c_uint64),
+                ("first_bad_block_b", ctypes.c_uint64)]
+
+
 _lib = None
 
 
@@ -137,6 +150,11 @@ def load_library():
     U32, U64 = ctypes.c_uint32, ctypes.c_uint64
     L.cjs_bzip2_search.argtypes = [u8p, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
     L.cjs_bzip2_search_device.argtypes = [V, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
+    cmp_tail = [U64, U64, ctypes.POINTER(Diff), S, ctypes.POINTER(CompareInfo), V]
+    L.cjs_bzip2_compare.argtypes = [u8p, S, V, u8p, S, U64] + cmp_tail
+    L.cjs_bzip2_compare_device.argtypes = [V, S, V, V, S, U64] + cmp_tail
+    L.cjs_bzip2_compare_streams.argtypes = [u8p, S, V, u8p, S, V] + cmp_tail
+    L.cjs_bzip2_compare_streams_device.argtypes = [V, S, V, V, S, V] + cmp_tail
     PU32, PI32 = ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_int32)
     L.cjs_bzip2_lines_build.argtypes = [u8p, S, V, ctypes.POINTER(V), V]
     L.cjs_bzip2_lines_build_device.argtypes = [V, S, V, ctypes.POINTER(V), V]
@@ -772,6 +790,25 @@ class Bzip2Index:
         ctx = self.read_ranges(data, ranges) if ranges else []
         return [(o, j, c) for (o, j), c in zip(res.matches, ctx)]
 
+    def compare(self, data, other, off=0, length=None, other_off=0, limit=64):
+        """cmp on the GPU (cjs_bzip2_compare): other[k] against decoded byte other_off + k, inside [off, off + length): ->
+        CompareResult with at most `limit` differences.  limit=None counts first and then fetches every difference."""
+        L = load_library()
+        data, other = _coerce_input(data), _coerce_input(other)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        keep2 = other if other.size else np.zeros(1, dtype=np.uint8)
+        return _compare(lambda *a: L.cjs_bzip2_compare(keep.ctypes.data_as(u8p), data.size, self._h, keep2.ctypes.data_as(u8p), other.size, int(other_off), *a, None),
+                        off, length, limit, self.total, int(other_off) + other.size)
+
+    def compare_stream(self, data, other_data, other_index, off=0, length=None, limit=64):
+        """bzcmp on the GPU (cjs_bzip2_compare_streams): this stream against the stream `other_data` of `other_index`"""
+        L = load_library()
+        data, other = _coerce_input(data), _coerce_input(other_data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        keep2 = other if other.size else np.zeros(1, dtype=np.uint8)
+        return _compare(lambda *a: L.cjs_bzip2_compare_streams(keep.ctypes.data_as(u8p), data.size, self._h, keep2.ctypes.data_as(u8p), other.size, other_index._h, *a, None),
+                        off, length, limit, self.total, other_index.total)
+
     def line_starts(self, data, lines, line_numbers):
         """start(k) of every line number (cjs_bzip2_lines_locate): -> (starts, status, detail), uint64 / int32 arrays"""
         L = load_library()
@@ -969,6 +1006,87 @@ def search_device(d_in_ptr, n, index, patterns, off=0, length=None, nocase=False
     L = load_library()
     opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
     return _search(lambda *a: L.cjs_bzip2_search_device(d_in_ptr, n, index._h, *a, ctypes.byref(opts)), patterns, off, length, nocase, limit)
+
+
+class CompareResult:
+    """What a compare found: diffs = [(off, a, b)] ascending, at most `limit` of them (a: the stream's byte, b: the other side's);
+    total = all differences of the span; first_diff (None if none); compared = the bytes actually
+    compared; len_a / len_b = the decoded bytes of the stream / where the other side ends; bad_blocks / first_bad_block /
+    bad_blocks_b / first_bad_block_b / detail = the touched blocks that were not good."""
+
+    def __init__(self, diffs, info, detail, len_a, len_b):
+        self.diffs, self.total = diffs, int(info.n_diffs)
+        self.first_diff = int(info.first_diff) if info.n_diffs else None
+        self.compared = int(info.compared)
+        self.len_a, self.len_b = int(len_a), int(len_b)
+        self.bad_blocks, self.bad_blocks_b = int(info.n_bad_blocks), int(info.n_bad_blocks_b)
+        self.first_bad_block = int(info.first_bad_block) if info.n_bad_blocks else None
+        self.first_bad_block_b = int(info.first_bad_block_b) if info.n_bad_blocks_b else None
+        self.blocks_decoded = int(info.blocks_decoded)
+        self.detail = detail
+
+    @property
+    def whole(self):
+        """the whole of both sides was compared"""
+        return self.len_a == self.len_b and self.compared == self.len_a
+
+    @property
+    def equal(self):
+        return self.total == 0 and self.bad_blocks == 0 and self.bad_blocks_b == 0 and self.whole
+
+    def cmp_text(self, index=None, data=None, lines=None):
+        """What `cmp` prints: "" when equal, "differ: byte N[, line M]" (both 1-based; the line needs the stream's index, its
+        bytes and its Bzip2Lines: one line_numbers question), "EOF on a" / "EOF on b" when one side is a proper prefix of the
+        other.  The common prefix must have been compared whole (CjsError otherwise: bad blocks, or a narrower window)."""
+        if self.total:
+            text = "differ: byte %d" % (self.first_diff + 1)
+            if lines is not None:
+                numbers, st, detail = index.line_numbers(data, lines, [self.first_diff])
+                _check(int(st[0]))
+                text += ", line %d" % (int(numbers[0]) + 1)
+            return text
+        if self.bad_blocks or self.bad_blocks_b or self.compared != min(self.len_a, self.len_b):
+            raise CjsError(-5, "compare: not every byte of the common prefix was compared" + (": " + self.detail if self.detail else ""))
+        if self.len_a == self.len_b:
+            return ""
+        return "EOF on a" if self.len_a < self.len_b else "EOF on b"
+
+
+def _compare(call, off, length, limit, len_a, len_b):
+    """call(off, len, diffs, cap, info) -> rc; limit=None: the count query, then all"""
+    L = load_library()
+    ln = 2 ** 64 - 1 if length is None else int(length)
+
+    def once(cap):
+        diffs = (Diff * max(cap, 1))()
+        info = CompareInfo()
+        _check(call(int(off), ln, diffs if cap else None, cap, ctypes.byref(info)))
+        detail = L.cjs_last_error_detail().decode() if info.n_bad_blocks or info.n_bad_blocks_b else ""
+        got = min(cap, info.n_diffs)
+        raw = np.frombuffer(diffs, dtype=[("off", "<u8"), ("a", "u1"), ("b", "u1"), ("reserved", "u1", (6,))], count=got)
+        return CompareResult(list(zip(raw["off"].tolist(), raw["a"].tolist(), raw["b"].tolist())), info, detail, len_a, len_b)
+
+    if limit is not None:
+        return once(int(limit))
+    res = once(0)
+    return once(res.total) if res.total else res
+
+
+def compare_device(d_in_ptr, n, index, d_other_ptr, other_n, off=0, length=None, other_off=0, limit=64, device=-1):
+    """Bzip2Index.compare with the stream and the other side in GPU memory (cjs_bzip2_compare_device; the memory rules of
+    decompress_device).  The result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _compare(lambda *a: L.cjs_bzip2_compare_device(d_in_ptr, n, index._h, d_other_ptr, other_n, int(other_off), *a, ctypes.byref(opts)),
+                    off, length, limit, index.total, int(other_off) + int(other_n))
+
+
+def compare_streams_device(d_a_ptr, na, index_a, d_b_ptr, nb, index_b, off=0, length=None, limit=64, device=-1):
+    """Bzip2Index.compare_stream with both streams in GPU memory (cjs_bzip2_compare_streams_device)."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _compare(lambda *a: L.cjs_bzip2_compare_streams_device(d_a_ptr, na, index_a._h, d_b_ptr, nb, index_b._h, *a, ctypes.byref(opts)),
+                    off, length, limit, index_a.total, index_b.total)
 
 
 def read_ranges_device(d_in_ptr, n, index, ranges, d_out_ptr, out_cap, device=-1):

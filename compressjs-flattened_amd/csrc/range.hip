@@ -365,6 +365,19 @@ void range_verdicts(const cjs_bz_index* ix, const RangePlan& P, const uint64_t* 
   }
 }
 
+}  // namespace
+
+// The range reads' core with the result on the device (range_engine.h), for a caller that has checked its arguments.
+int cjs::range_read_to_device(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const uint64_t* off, const uint64_t* len, size_t count,
+                              uint8_t* d_out, std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st) {
+  RangePlan P;
+  CJS_TRY(range_plan(ix, off, len, count, P));
+  if (P.touched.empty()) return 0;
+  return range_run(in, d_src, ix, P, nullptr, d_out, verdict, crc_got, dev, st);
+}
+
+namespace {
+
 int range_check_args(const void* in, size_t n, const cjs_bz_index* idx, const uint64_t* off, const uint64_t* len, size_t count, const size_t* out_off,
                      const size_t* out_len, const int32_t* status) {
   if (!idx || (!in && n)) return CJS_E_INVALID_ARG;

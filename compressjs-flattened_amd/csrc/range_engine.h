@@ -1,7 +1,7 @@
 // range_engine.h -- the pass engine of the indexed entry points (range.hip defines it): the blocks an index names go through phases
 // A, B and C in bounded passes, each judged against its entry, and every decoded inverse-BWT batch is handed to a consumer while it
-// stands expanded in device scratch.  Three consumers: the slice gather of the range reads (range.hip), the pattern scan
-// (search.hip) and the newline count, select and rank of the line table (lines.hip).
+// stands expanded in device scratch.  Four consumers: the slice gather of the range reads (range.hip), the pattern scan
+// (search.hip), the newline count, select and rank of the line table (lines.hip) and the compare (compare.hip).
 #pragma once
 #include "dec_engine.h"
 #include "bz_index.h"
@@ -38,6 +38,11 @@ using RangeConsumer = std::function<int(const RangeBatch&)>;
 // verdict / crc_got: per block of the index (RG_*; the computed CRC of an RG_BAD_CRC block), written for the touched blocks.
 int range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const std::vector<uint32_t>& touched,
                  std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st, const RangeConsumer& consume);
+// The range reads on the engine, the result in device memory: range k ([off[k], off[k] + len[k]) clipped to total_bytes) at d_out +
+// the sum of the clipped lengths in front of it, from the stream on the host (`in`) or on device `dev` (d_src).  The region of a
+// range that touches a bad block holds unspecified bytes; the verdicts say which blocks were bad.
+int range_read_to_device(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const uint64_t* off, const uint64_t* len, size_t count,
+                         uint8_t* d_out, std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st);
 // the detail text of bad block `bad`: one of read_ranges' two
 void range_bad_detail(const cjs_bz_index* ix, size_t bad, const std::vector<uint8_t>& verdict, const std::vector<uint32_t>& crc_got);
 // the block that holds decoded offset o < total_bytes (of non-zero size)

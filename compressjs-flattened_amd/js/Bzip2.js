@@ -233,6 +233,35 @@ Bzip2.search = function (inStream, index, patterns, opts) {
   for (var k = 0; k < r.matches.length; k += 2) { matches.push([r.matches[k], r.matches[k + 1]]); }
   return { matches: matches, total: r.total, badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, detail: r.detail };
 };
+// Compare (cjs_bzip2_compare, cjs_bzip2_compare_streams): `cmp` / `bzcmp` on the GPU; only the differing bytes come back.
+// compare: byte k of `other` (plain bytes) against decoded byte otherOffset + k, inside [offset, offset + length).  compareStreams:
+// the decoded bytes of stream A against those of stream B.  opts: {offset = 0, length = to the end, otherOffset = 0, limit = 64
+// (null: every difference)}.  Returns {equal, diffs: [{offset, a, b}, ...] ascending (a: the stream's byte, b: the other side's),
+// total: all differences of the span, firstDiff (null if none), compared: the bytes actually compared, lenA, lenB: where the two
+// sides end, badBlocks, firstBadBlock, badBlocksB, firstBadBlockB (null if none), detail}: a damaged block does not fail the
+// compare, its bytes are not compared.  equal: no difference, no bad block, both sides of one length and compared whole.
+function compareResult(r) {
+  var diffs = [];
+  for (var k = 0; k < r.diffs.length; k += 3) { diffs.push({ offset: r.diffs[k], a: r.diffs[k + 1], b: r.diffs[k + 2] }); }
+  return { equal: r.total === 0 && r.badBlocks === 0 && r.badBlocksB === 0 && r.lenA === r.lenB && r.compared === r.lenA,
+           diffs: diffs, total: r.total, firstDiff: r.firstDiff < 0 ? null : r.firstDiff, compared: r.compared, lenA: r.lenA, lenB: r.lenB,
+           badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, badBlocksB: r.badBlocksB,
+           firstBadBlockB: r.firstBadBlockB < 0 ? null : r.firstBadBlockB, detail: r.detail };
+}
+function compareCall(input, index, other, otherIndex, o) {
+  try {
+    return compareResult(common.addon().bzip2Compare(input.bytes, index, other.bytes, otherIndex, o.otherOffset === undefined ? 0 : o.otherOffset,
+                                                     o.offset === undefined ? 0 : o.offset, o.length === undefined || o.length === null ? -1 : o.length,
+                                                     o.limit === undefined ? 64 : o.limit === null ? -1 : o.limit));
+  } catch (e) { rethrow(e); }
+}
+Bzip2.compare = function (inStream, index, other, opts) {
+  return compareCall(common.coerceInput(inStream), index, common.coerceInput(other), null, opts || {});
+};
+Bzip2.compareStreams = function (inStreamA, indexA, inStreamB, indexB, opts) {
+  var o = opts || {};
+  return compareCall(common.coerceInput(inStreamA), indexA, common.coerceInput(inStreamB), indexB, { offset: o.offset, length: o.length, limit: o.limit });
+};
 // The line table (cjs_bzip2_lines_*): lines are numbered from 0 and end with their '\n' (0x0A, nothing else); line N, behind the
 // last newline, is the unterminated tail.  buildLineIndex counts the newlines of every block on the GPU and returns the table in
 // its serialised form (a Uint8Array to keep beside the index).  lineStarts gives the decoded offset where each line starts (the

@@ -33,6 +33,11 @@ struct Api {
                      const cjs_opts*) = nullptr;
   int (*search)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint64_t, uint64_t, cjs_bz_match*, size_t,
                 cjs_bz_search_info*, const cjs_opts*) = nullptr;
+  int (*index_info)(const cjs_bz_index*, uint64_t*, uint64_t*, uint64_t*, int*) = nullptr;
+  int (*compare)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, size_t, uint64_t, uint64_t, uint64_t, cjs_bz_diff*, size_t, cjs_bz_cmp_info*,
+                 const cjs_opts*) = nullptr;
+  int (*compare_streams)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, size_t, const cjs_bz_index*, uint64_t, uint64_t, cjs_bz_diff*, size_t,
+                         cjs_bz_cmp_info*, const cjs_opts*) = nullptr;
   int (*lines_build)(const uint8_t*, size_t, const cjs_bz_index*, cjs_bz_lines**, const cjs_opts*) = nullptr;
   int (*lines_save)(const cjs_bz_lines*, uint8_t**, size_t*) = nullptr;
   int (*lines_load)(const uint8_t*, size_t, const cjs_bz_index*, cjs_bz_lines**) = nullptr;
@@ -81,6 +86,7 @@ bool load_api() {
   SYM(bzip2_recover, "cjs_bzip2_recover")
   SYM(index_build, "cjs_bzip2_index_build") SYM(index_save, "cjs_bzip2_index_save") SYM(index_load, "cjs_bzip2_index_load")
   SYM(index_destroy, "cjs_bzip2_index_destroy") SYM(read_ranges, "cjs_bzip2_read_ranges") SYM(search, "cjs_bzip2_search")
+  SYM(index_info, "cjs_bzip2_index_info") SYM(compare, "cjs_bzip2_compare") SYM(compare_streams, "cjs_bzip2_compare_streams")
   SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
@@ -338,6 +344,76 @@ napi_value bzip2_search(napi_env env, napi_callback_info info) {
   napi_create_double(env, (double)si.n_matches, &v); napi_set_named_property(env, res, "total", v);
   napi_create_double(env, (double)si.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
   napi_create_double(env, si.n_bad_blocks ? (double)si.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
+  napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
+  return res;
+}
+
+// bzip2Compare(input, index, other, otherIndex, otherOffset, offset, length, limit) -> { diffs: Float64Array, total, firstDiff,
+// compared, lenA, lenB, badBlocks, firstBadBlock, badBlocksB, firstBadBlockB, detail }   (Bzip2.compare, Bzip2.compareStreams).
+// otherIndex: null = `other` is plain bytes, byte k of it decoded byte otherOffset + k; a serialised index = `other` is the stream
+// of that index.  length < 0: to the end; limit < 0: every difference (a count query first).  diffs holds (offset, a, b) triples.
+napi_value bzip2_compare(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 8; napi_value argv[8];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *op = nullptr, *oip = nullptr; size_t n = 0, in = 0, on = 0, oin = 0;
+  napi_valuetype oit = napi_undefined;
+  if (argc >= 4) napi_typeof(env, argv[3], &oit);
+  const bool two = oit != napi_null && oit != napi_undefined;
+  if (argc < 8 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &op, &on) ||
+      (two && !get_bytes(env, argv[3], &oip, &oin))) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array other, Uint8Array index or null, otherOffset, offset, length, limit)"); return nullptr;
+  }
+  double ooff = 0, off = 0, len = 0, limit = 0;
+  napi_get_value_double(env, argv[4], &ooff); napi_get_value_double(env, argv[5], &off); napi_get_value_double(env, argv[6], &len); napi_get_value_double(env, argv[7], &limit);
+  if (!(off >= 0 && off <= 9007199254740992.0 && off == (double)(uint64_t)off) || !(ooff >= 0 && ooff <= 9007199254740992.0 && ooff == (double)(uint64_t)ooff) ||
+      !(len <= 9007199254740992.0 && len == (double)(int64_t)len) || !(limit <= 9007199254740992.0 && limit == (double)(int64_t)limit)) {
+    napi_throw_type_error(env, nullptr, "offsets and lengths are integers from 0 to 2^53"); return nullptr;
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index *ix = nullptr, *oix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  if (two && (rc = api.index_load(oip ? oip : &dummy, oin, &oix)) != 0) { api.index_destroy(ix); return throw_code(env, rc); }
+  uint64_t blocks = 0, len_a = 0, len_b = (uint64_t)ooff + on, sb = 0; int multi = 0;
+  api.index_info(ix, &blocks, &len_a, &sb, &multi);
+  if (two) api.index_info(oix, &blocks, &len_b, &sb, &multi);
+  cjs_bz_cmp_info ci;
+  memset(&ci, 0, sizeof ci);
+  std::vector<cjs_bz_diff> diffs;
+  const uint64_t ulen = len < 0 ? ~0ull : (uint64_t)len;
+  auto call = [&](cjs_bz_diff* d, size_t cap) {
+    return two ? api.compare_streams(p ? p : &dummy, n, ix, op ? op : &dummy, on, oix, (uint64_t)off, ulen, d, cap, &ci, nullptr)
+               : api.compare(p ? p : &dummy, n, ix, op ? op : &dummy, on, (uint64_t)ooff, (uint64_t)off, ulen, d, cap, &ci, nullptr);
+  };
+  size_t cap = limit < 0 ? 0 : (size_t)limit;
+  if (limit < 0) {                                                 // the count query
+    rc = call(nullptr, 0);
+    cap = (size_t)ci.n_diffs;
+  }
+  if (rc == 0 && (limit >= 0 || cap)) {
+    try { diffs.resize(cap); } catch (...) { api.index_destroy(ix); api.index_destroy(oix); napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
+    rc = call(cap ? diffs.data() : nullptr, cap);
+  }
+  std::string detail = rc == 0 && !ci.n_bad_blocks && !ci.n_bad_blocks_b ? "" : api.detail_();      // (before the next call of the library on this thread)
+  api.index_destroy(ix); api.index_destroy(oix);
+  if (rc != 0) return throw_code(env, rc);
+  const size_t got = (size_t)std::min<uint64_t>(cap, ci.n_diffs);
+  napi_value res, dab, dta, v; void* ddst;
+  napi_create_object(env, &res);
+  napi_create_arraybuffer(env, sizeof(double) * 3 * got, &ddst, &dab);
+  for (size_t k = 0; k < got; k++) { ((double*)ddst)[3 * k] = (double)diffs[k].off; ((double*)ddst)[3 * k + 1] = (double)diffs[k].a; ((double*)ddst)[3 * k + 2] = (double)diffs[k].b; }
+  napi_create_typedarray(env, napi_float64_array, 3 * got, dab, 0, &dta);
+  napi_set_named_property(env, res, "diffs", dta);
+  napi_create_double(env, (double)ci.n_diffs, &v); napi_set_named_property(env, res, "total", v);
+  napi_create_double(env, ci.n_diffs ? (double)ci.first_diff : -1.0, &v); napi_set_named_property(env, res, "firstDiff", v);
+  napi_create_double(env, (double)ci.compared, &v); napi_set_named_property(env, res, "compared", v);
+  napi_create_double(env, (double)len_a, &v); napi_set_named_property(env, res, "lenA", v);
+  napi_create_double(env, (double)len_b, &v); napi_set_named_property(env, res, "lenB", v);
+  napi_create_double(env, (double)ci.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
+  napi_create_double(env, ci.n_bad_blocks ? (double)ci.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
+  napi_create_double(env, (double)ci.n_bad_blocks_b, &v); napi_set_named_property(env, res, "badBlocksB", v);
+  napi_create_double(env, ci.n_bad_blocks_b ? (double)ci.first_bad_block_b : -1.0, &v); napi_set_named_property(env, res, "firstBadBlockB", v);
   napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
   return res;
 }
@@ -757,6 +833,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2BuildIndex", nullptr, bzip2_build_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2ReadRanges", nullptr, bzip2_read_ranges, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Search", nullptr, bzip2_search, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2Compare", nullptr, bzip2_compare, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2BuildLineIndex", nullptr, bzip2_build_line_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},

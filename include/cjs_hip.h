@@ -328,6 +328,65 @@ int cjs_bzip2_lines_number(const uint8_t *in, size_t n, const cjs_bz_index *idx,
                            size_t count, uint64_t *line, int32_t *status, const cjs_opts *opts);
 int cjs_bzip2_lines_number_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines,
                                   const uint64_t *off, size_t count, uint64_t *line, int32_t *status, const cjs_opts *opts);
+/* cjs_bzip2_compare: `cmp` over the address space of cjs_bzip2_read_ranges ([0, total_bytes) of the index), done on the GPU: is
+ * the decoded stream equal to `other`, and if not, where and with which bytes?  The decoded bytes never leave the GPU, 16 bytes
+ * per reported difference do.  other[k] is compared with decoded byte other_off + k.  The COMPARED SPAN is
+ * [max(off, other_off), min(off + len, total_bytes, other_off + other_n)) minus the bad blocks; off + len saturates, so len =
+ * UINT64_MAX means "to the end".  A difference is one byte position of the span where the two sides differ: `a` is the stream's
+ * byte, `b` the other side's.  `diffs` gets the first min(cap, n_diffs) differences in ascending offset and nothing past those is
+ * written; info->n_diffs counts them all, info->first_diff is the lowest offset (~0: none), info->compared the bytes actually
+ * compared (cap = 0, diffs = NULL: the count query).  The list does not depend on how the blocks fall into passes, batches and
+ * tiles.  Lengths are not judged: total_bytes is in the index and other_n is the caller's, who turns the two into "equal" or
+ * "EOF on ..".
+ * The TOUCHED blocks are those of non-zero size that overlap the span without the bad blocks taken out; each is decoded once and
+ * judged as cjs_bzip2_read_ranges judges it, by the same passes (CJS_RANGE_PASS_BLOCKS, CJS_DEC_GROUP_BYTES, CJS_DEC_BATCH_ELEMS
+ * and CJS_DEC_ROW_BYTES act as there).  A bad block does not fail the call: it returns 0, info->n_bad_blocks / first_bad_block
+ * say what was bad, cjs_last_error_detail() is the first bad block's detail (read_ranges' two texts), and its bytes are neither
+ * compared nor counted in `compared`.
+ * Per decoded inverse-BWT batch two kernels run over 16 KiB tiles of the good runs -- one counts the differing bytes of every
+ * tile in one pass over its bytes (16 bytes per lane and step, aligned vector loads of both sides bounded to their sources, the
+ * other side brought into phase by a byte funnel shift), the other, behind a scan of the counts and only when there is something
+ * to deliver, writes the differences at their rank -- so there is no atomic on the list and no sort.  Device memory held: a
+ * pass's (as for cjs_bzip2_read_ranges), 16 bytes per tile, 16 bytes per difference delivered from one batch; host form: the
+ * bytes of `other` under the batch's good blocks (the only part of `other` that is uploaded).
+ * cjs_bzip2_compare_streams: the other side is a second indexed stream B.  The span is [off, min(off + len, total_bytes of A,
+ * total_bytes of B)); it is walked in windows of CJS_COMPARE_WINDOW_BYTES decoded bytes (read at every call; default 64 MiB):
+ * B's window is read into one device buffer by the range reads' core, one range per touched block of B, so that a bad block of
+ * B costs only its own bytes (reported in n_bad_blocks_b / first_bad_block_b, not compared); then A's blocks of the window are
+ * compared against it.  A block that straddles a window edge is decoded once per window it touches.  Device memory: one window
+ * plus a pass's, whatever the streams' sizes.  The detail is that of A's first bad block, or of B's if A has none.
+ * CJS_E_INVALID_ARG before the device is touched: NULL idx or info; NULL in with n > 0; NULL other with other_n > 0; NULL diffs
+ * with cap > 0; n != the index's stream_bytes (for either stream).  An empty span: success with zeros without touching the device.
+ * Device forms: d_in and d_other (d_a and d_b) are memory of the GPU (the memory rules of cjs_bzip2_decompress_device;
+ * CJS_E_INVALID_ARG before any launch otherwise); diffs and info are HOST memory.  opts->device is honoured, n_devices and stats
+ * are ignored.  CJS_DEBUG: one "[cjs compare]" line per call on stderr (form, window, blocks touched and bad, passes and batches,
+ * windows, tiles, H2D and D2H bytes, n_diffs, compared). */
+typedef struct cjs_bz_diff {
+  uint64_t off;        /* decoded offset of the differing byte */
+  uint8_t a, b;        /* the stream's byte, the other side's */
+  uint8_t reserved[6]; /* 0 */
+} cjs_bz_diff;
+typedef struct cjs_bz_cmp_info {
+  uint64_t n_diffs;           /* all differences of the span, also when more than cap */
+  uint64_t first_diff;        /* the lowest differing offset; ~0 if none */
+  uint64_t compared;          /* bytes actually compared */
+  uint64_t n_bad_blocks;      /* touched blocks (of the stream `idx` / `idx_a` is of) that were not GOOD */
+  uint64_t first_bad_block;   /* index of the first of them; ~0 if none */
+  uint64_t blocks_decoded;    /* touched blocks of that stream */
+  uint64_t n_bad_blocks_b;    /* two-stream forms: the same for stream B; else 0 */
+  uint64_t first_bad_block_b; /* ~0 if none */
+} cjs_bz_cmp_info;
+int cjs_bzip2_compare(const uint8_t *in, size_t n, const cjs_bz_index *idx, const uint8_t *other, size_t other_n, uint64_t other_off,
+                      uint64_t off, uint64_t len, cjs_bz_diff *diffs, size_t cap, cjs_bz_cmp_info *info, const cjs_opts *opts);
+int cjs_bzip2_compare_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint8_t *d_other, size_t other_n,
+                             uint64_t other_off, uint64_t off, uint64_t len, cjs_bz_diff *diffs, size_t cap, cjs_bz_cmp_info *info,
+                             const cjs_opts *opts);
+int cjs_bzip2_compare_streams(const uint8_t *a, size_t na, const cjs_bz_index *idx_a, const uint8_t *b, size_t nb,
+                              const cjs_bz_index *idx_b, uint64_t off, uint64_t len, cjs_bz_diff *diffs, size_t cap,
+                              cjs_bz_cmp_info *info, const cjs_opts *opts);
+int cjs_bzip2_compare_streams_device(const uint8_t *d_a, size_t na, const cjs_bz_index *idx_a, const uint8_t *d_b, size_t nb,
+                                     const cjs_bz_index *idx_b, uint64_t off, uint64_t len, cjs_bz_diff *diffs, size_t cap,
+                                     cjs_bz_cmp_info *info, const cjs_opts *opts);
 /* Streaming form of cjs_bzip2_compress: the input is written in pieces of any size (zero included), the .bz2 stream is read in
  * pieces of any size, and the bytes read, in order, once cjs_bzip2_enc_finish has returned, are exactly what
  * cjs_bzip2_compress(all written bytes, level) returns -- for every level, every split of the input, every chunk_bytes and every
