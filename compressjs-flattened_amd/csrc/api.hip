@@ -190,6 +190,14 @@ int select_device(const cjs_opts* opts) {
   return 0;
 }
 
+int current_device(const cjs_opts* opts, int& dev) {
+  CJS_TRY(select_device(opts));
+  int ndev = 0, cur = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&cur) != hipSuccess) return CJS_E_NO_DEVICE;
+  dev = cur;
+  return 0;
+}
+
 static DevCache g_cache[MAX_DEVICES][CACHE_SLOTS];      // per-device context caches (host.h)
 DevCache& dev_cache(int device, int slot) { return g_cache[device][slot]; }
 

@@ -219,9 +219,8 @@ extern "C" int cjs_bzip2_decompress_device(const uint8_t* d_in, size_t n, int mu
   *out_n = 0;
   clear_detail();
   CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  int dev = 0;
+  CJS_TRY(current_device(opts, dev));
   RestoreDevice restore{dev};
   if ((n && !on_device(d_in, dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
   DevUnit U;
@@ -288,9 +287,8 @@ extern "C" int cjs_bzip2_decompress_batch(const uint8_t* const* in, const size_t
   if (!in || !n || !off || !len || !status) return CJS_E_INVALID_ARG;
   for (size_t k = 0; k < count; k++) if (n[k] && !in[k]) return CJS_E_INVALID_ARG;
   CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  int dev = 0, ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  int dev = 0;
+  CJS_TRY(current_device(opts, dev));
   RestoreDevice restore{dev};
   cjs_opts one; memset(&one, 0, sizeof one);                   // (the large inputs: this device, n_devices and stats ignored)
   one.struct_size = sizeof one; one.device = dev;
@@ -349,9 +347,8 @@ extern "C" int cjs_bzip2_decompress_batch_device(const uint8_t* d_in, const size
   if ((!d_in && in_off[count] > in_off[0]) || (!d_out && out_cap)) return CJS_E_INVALID_ARG;
   *out_need = 0;
   CJS_GUARD_BEGIN
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  int dev = 0;
+  CJS_TRY(current_device(opts, dev));
   RestoreDevice restore{dev};
   if ((in_off[count] > in_off[0] && !on_device(d_in + in_off[0], dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;
   DecShare H;                                                   // the header pass: its stream, pool and copy tally

@@ -202,9 +202,8 @@ extern "C" int cjs_bzip2_recover(const uint8_t* in, size_t n, int as_stream, uin
     *out_n = sz;
     return 0;
   }
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  int dev = 0;
+  CJS_TRY(current_device(opts, dev));
   RestoreDevice restore{dev};
   const int rc = recover_core(in, nullptr, n, as_stream != 0, out, nullptr, 0, out_n, found, cap, n_found, dev);
   if (rc) { *out_n = 0; *n_found = 0; }
@@ -219,9 +218,8 @@ extern "C" int cjs_bzip2_recover_device(const uint8_t* d_in, size_t n, int as_st
   clear_detail();
   CJS_GUARD_BEGIN
   if (n < 6 && !as_stream) return 0;
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
+  int dev = 0;
+  CJS_TRY(current_device(opts, dev));
   RestoreDevice restore{dev};
   if ((n && !on_device(d_in, dev)) || (out_cap && !on_device(d_out, dev))) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
   if (n < 6) {                                                    // the empty stream

@@ -20,6 +20,7 @@ struct Opts {
   explicit Opts(const cjs_opts* o);
 };
 int select_device(const cjs_opts* opts);      // makes opts' device current; CJS_E_NO_DEVICE without any
+int current_device(const cjs_opts* opts, int& dev);      // select_device, then dev = the device that is current now
 
 // Per-device cache of a context and its device staging buffers, kept between host-buffer calls.  Slots of a device:
 //   0 .. SHARD_SLOTS-1  cjs_bzip2_compress: slot 0 the one-GPU call and the first shard of a multi-GPU call on the device, the
@@ -96,6 +97,12 @@ inline int malloc_result(const std::vector<uint8_t>& v, uint8_t** out, size_t* o
 struct RestoreDevice {
   int d;
   ~RestoreDevice() { (void)hipSetDevice(d); }
+};
+// The device of a call: select() makes opts' device current (current_device); from then on it is made current again at scope exit.
+struct CallDevice {
+  int dev = -1;
+  int select(const cjs_opts* opts) { return current_device(opts, dev); }
+  ~CallDevice() { if (dev >= 0) (void)hipSetDevice(dev); }
 };
 
 // f(), an exception that leaves it turned into rc (std::bad_alloc: CJS_E_OUT_OF_MEMORY, else CJS_E_HIP); rc untouched otherwise

@@ -8,7 +8,6 @@
 // A tile is 16 KiB of one block, counted from the block's first byte (wherever that stands in the scratch): it never spans two.
 #include "range_engine.h"
 #include "bz_lines.h"
-#include "prims.hpp"
 #include <algorithm>
 #include <stdlib.h>
 #include <string.h>
@@ -31,29 +30,21 @@ __device__ __forceinline__ uint32_t ln_nl4(uint32_t w) {
   const uint32_t v = w ^ 0x0A0A0A0Au, t = (v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
   return ~(t | v | 0x7F7F7F7Fu);
 }
-__device__ __forceinline__ uint32_t ln_count16(uint4 x) { return __popc(ln_nl4(x.x)) + __popc(ln_nl4(x.y)) + __popc(ln_nl4(x.z)) + __popc(ln_nl4(x.w)); }
-// bit i = byte i of the 16 is a newline
-__device__ __forceinline__ uint32_t ln_mask16(uint4 x) {
-  auto nib = [](uint32_t z) { return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u); };
-  return nib(ln_nl4(x.x)) | (nib(ln_nl4(x.y)) << 4) | (nib(ln_nl4(x.z)) << 8) | (nib(ln_nl4(x.w)) << 12);
-}
+// the newlines of 16 bytes: their number, and bit i = byte i is one
+__device__ __forceinline__ uint32_t ln_count16(uint4 x) { return rg_count16<ln_nl4>(x); }
+__device__ __forceinline__ uint32_t ln_mask16(uint4 x) { return rg_mask16<ln_nl4>(x); }
 
-// The bytes [a0, a0 + n) of a tile as aligned 16-byte vectors: vector v is the 16 bytes at base + 16 v, those outside the tile
-// read as zeros (rg_ld16: nothing outside the tile, so nothing outside the block, is read).
-struct LnSpan { uint64_t a0, base; uint32_t n, nvec; };
-__device__ __forceinline__ LnSpan ln_span(uint64_t a0, uint32_t n) { return LnSpan{a0, a0 & ~15ull, n, ((uint32_t)(a0 & 15u) + n + 15u) / 16u}; }
-__device__ __forceinline__ uint4 ln_vec(const LnSpan& S, uint32_t v) { return rg_ld16(S.base + 16ull * v, S.a0, S.a0 + S.n); }
+// a tile's bytes as bounded aligned vectors (nothing outside the tile, so nothing outside the block, is read)
+using LnSpan = RgSpan;
 
 __global__ __launch_bounds__(256) void ln_count(const LnBlk* __restrict__ blks, uint32_t nblk, uint32_t* __restrict__ cnt) {
   __shared__ uint32_t sm[4];
   const uint32_t t = blockIdx.x;
-  uint32_t lo = 0, hi = nblk;                                                // the last block with tile0 <= t
-  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (blks[mid].tile0 <= t) lo = mid; else hi = mid; }
-  const LnBlk g = blks[lo];
+  const LnBlk g = rg_seg_of(blks, nblk, t);
   const uint32_t p0 = (t - g.tile0) * LN_TILE;
-  const LnSpan S = ln_span(g.src + p0, min(LN_TILE, g.len - p0));
+  const LnSpan S = rg_span(g.src + p0, min(LN_TILE, g.len - p0));
   uint32_t c = 0;
-  for (uint32_t v = threadIdx.x; v < S.nvec; v += 256) c += ln_count16(ln_vec(S, v));
+  for (uint32_t v = threadIdx.x; v < S.nvec; v += 256) c += ln_count16(rg_vec(S, v));
   const uint32_t total = block_sum<256, uint32_t>(c, sm);
   if (threadIdx.x == 0) cnt[t] = total;
 }
@@ -91,10 +82,10 @@ __global__ __launch_bounds__(256) void ln_select(const LnBlk* __restrict__ blks,
   while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (ex[mid] < r) lo = mid; else hi = mid; }
   uint32_t rem = r - ex[lo];
   const uint32_t p0 = lo * LN_TILE;
-  const LnSpan S = ln_span(g.src + p0, min(LN_TILE, g.len - p0));
+  const LnSpan S = rg_span(g.src + p0, min(LN_TILE, g.len - p0));
   for (uint32_t row = 0; row * 64 < S.nvec; row++) {
     const uint32_t v = row * 64 + lane_id();
-    uint32_t m = v < S.nvec ? ln_mask16(ln_vec(S, v)) : 0u;
+    uint32_t m = v < S.nvec ? ln_mask16(rg_vec(S, v)) : 0u;
     const uint32_t c = __popc(m), inc = wave_incl_sum(c);
     const uint32_t in_row = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
     if (rem > in_row) { rem -= in_row; continue; }
@@ -116,9 +107,9 @@ __global__ __launch_bounds__(256) void ln_rank(const LnBlk* __restrict__ blks, c
   const LnAsk A = asks[q];
   const LnBlk g = blks[A.blk];
   const uint32_t p = min(A.arg, g.len), tile = min(p / LN_TILE, ln_tiles(g.len) - 1), within = p - tile * LN_TILE;
-  const LnSpan S = ln_span(g.src + (uint64_t)tile * LN_TILE, within);
+  const LnSpan S = rg_span(g.src + (uint64_t)tile * LN_TILE, within);
   uint32_t c = 0;
-  for (uint32_t v = lane_id(); v < S.nvec; v += 64) c += ln_count16(ln_vec(S, v));
+  for (uint32_t v = lane_id(); v < S.nvec; v += 64) c += ln_count16(rg_vec(S, v));
   const uint32_t s = wave_sum(c);
   if (lane_id() == 0) ans[q] = (uint64_t)cnt[g.tile0 + tile] + s;
 }
@@ -167,18 +158,18 @@ struct LinesCall {
   std::vector<uint64_t> ans;                                       // per question
   uint64_t h2d = 0, d2h = 0, tiles = 0;
 
-  int batch(const RangeBatch& B, const std::vector<uint8_t>& verdict) {
+  int batch(const RangeBatch& B) {
     std::vector<LnBlk> blks; std::vector<uint32_t> which; std::vector<LnAsk> asks; std::vector<size_t> ask_k;
     uint64_t nt = 0;
     for (size_t k = B.g0; k < B.g1; k++) {
       const uint32_t b = B.blk[k];
       while (want_at < wants.size() && wants[want_at].block < b) want_at++;
       const uint32_t len = ix->e[b].size;
-      if (verdict[b] != RG_GOOD || !len) continue;
+      if (!B.V.good(b) || !len) continue;
       for (; want_at < wants.size() && wants[want_at].block == b; want_at++) {
         asks.push_back(LnAsk{(uint32_t)blks.size(), wants[want_at].arg}); ask_k.push_back(wants[want_at].k);
       }
-      blks.push_back(LnBlk{(uint64_t)(uintptr_t)(B.d_exp + B.J.out_off[k]), ix->off[b], len, (uint32_t)nt});
+      blks.push_back(LnBlk{B.addr(k), ix->off[b], len, (uint32_t)nt});
       which.push_back(b);
       nt += ln_tiles(len);
     }
@@ -223,15 +214,13 @@ struct LinesCall {
 struct LinesRun { RangeStats st; uint64_t h2d = 0, d2h = 0, tiles = 0; };
 
 // The touched blocks through the engine with the call as its consumer: verdicts, counts and answers.
-int lines_run(const uint8_t* in, const uint8_t* d_in, const cjs_bz_index* idx, const std::vector<uint32_t>& touched, LinesCall& C,
-              std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, const cjs_opts* opts, LinesRun& R) {
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if (d_in && !on_device(d_in, dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
+int lines_run(const uint8_t* in, const uint8_t* d_in, const cjs_bz_index* idx, const std::vector<uint32_t>& touched, LinesCall& C, RangeVerdicts& V,
+              const cjs_opts* opts, LinesRun& R) {
+  CallDevice cd;
+  CJS_TRY(cd.select(opts));
+  if (d_in && !on_device(d_in, cd.dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
   C.ix = idx; C.got.assign(idx->e.size(), 0);
-  CJS_TRY(range_engine(in, d_in, idx, touched, verdict, crc_got, dev, R.st, [&](const RangeBatch& B) { return C.batch(B, verdict); }));
+  CJS_TRY(range_engine(in, d_in, idx, touched, V, cd.dev, R.st, [&](const RangeBatch& B) { return C.batch(B); }));
   R.h2d = R.st.h2d + C.h2d; R.d2h = R.st.d2h + C.d2h; R.tiles = C.tiles;
   return 0;
 }
@@ -247,16 +236,16 @@ int lines_build_core(const uint8_t* in, const uint8_t* d_in, size_t n, const cjs
   if (!lines) return CJS_E_INVALID_ARG;
   *lines = nullptr;
   clear_detail();
-  if (!idx || (!in && !d_in && n)) return CJS_E_INVALID_ARG;
-  if (idx->stream_bytes != n) { set_detail("the index is of a stream of %llu bytes", (unsigned long long)idx->stream_bytes); return CJS_E_INVALID_ARG; }
-  std::vector<uint32_t> touched;
-  for (size_t b = 0; b < idx->e.size(); b++) if (idx->e[b].size) touched.push_back((uint32_t)b);
+  if (!idx) return CJS_E_INVALID_ARG;
+  CJS_TRY(check_index_stream(in ? in : d_in, n, idx));
+  const std::vector<uint32_t> touched = blocks_under(idx->off, 0, idx->off.back());
   LinesCall C; LinesRun R;
   C.mode = LN_BUILD; C.got.assign(idx->e.size(), 0);
   if (!touched.empty()) {
-    std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD); std::vector<uint32_t> crc_got(idx->e.size(), 0);
-    CJS_TRY(lines_run(in, d_in, idx, touched, C, verdict, crc_got, opts, R));
-    for (uint32_t b : touched) if (verdict[b] != RG_GOOD) { range_bad_detail(idx, b, verdict, crc_got); return CJS_E_DATA_ERROR; }
+    RangeVerdicts V(idx);
+    CJS_TRY(lines_run(in, d_in, idx, touched, C, V, opts, R));
+    const BadBlocks bad = V.bad_among(touched);
+    if (bad.n) { V.set_bad_detail(idx, (size_t)bad.first); return CJS_E_DATA_ERROR; }
   }
   lines_debug(d_in != nullptr, LN_BUILD, 0, touched.size(), idx, R);
   return bz_lines_make(idx, C.got.data(), C.got.size(), lines);
@@ -265,45 +254,34 @@ int lines_build_core(const uint8_t* in, const uint8_t* d_in, size_t n, const cjs
 int lines_ask_core(int mode, const uint8_t* in, const uint8_t* d_in, size_t n, const cjs_bz_index* idx, const cjs_bz_lines* t, const uint64_t* q, size_t count,
                    uint64_t* out, int32_t* status, const cjs_opts* opts) {
   clear_detail();
-  if (!idx || !t || (!in && !d_in && n)) return CJS_E_INVALID_ARG;
-  if (count && (!q || !out || !status)) return CJS_E_INVALID_ARG;
-  if (idx->stream_bytes != n) { set_detail("the index is of a stream of %llu bytes", (unsigned long long)idx->stream_bytes); return CJS_E_INVALID_ARG; }
+  if (!idx || !t || (count && (!q || !out || !status))) return CJS_E_INVALID_ARG;
+  CJS_TRY(check_index_stream(in ? in : d_in, n, idx));
   if (!lines_belong(idx, t)) return CJS_E_INVALID_ARG;
-  const uint64_t total = t->total_bytes, N = t->cum.back();
   LinesCall C; LinesRun R;
   C.mode = mode; C.ans.assign(count, 0);
   std::vector<uint64_t> res(count, 0); std::vector<int32_t> st(count, 0);      // (the caller's arrays are written on success only)
   std::vector<uint32_t> block_of(count, ~0u);                      // ~0: the table alone answers
   for (size_t k = 0; k < count; k++) {
-    if (mode == LN_LOCATE) {
-      if (q[k] == 0 || q[k] > N) { res[k] = q[k] ? total : 0; continue; }
-      const size_t b = (size_t)(std::lower_bound(t->cum.begin(), t->cum.end(), q[k]) - t->cum.begin()) - 1;      // cum[b] < line <= cum[b+1]
-      block_of[k] = (uint32_t)b;
-      C.wants.push_back(LnWant{(uint32_t)b, (uint32_t)(q[k] - t->cum[b]), k});
-    } else {
-      if (q[k] >= total) { res[k] = N; continue; }
-      const size_t b = range_block_of(idx, q[k]);
-      if (q[k] == idx->off[b]) { res[k] = t->cum[b]; continue; }
-      block_of[k] = (uint32_t)b;
-      C.wants.push_back(LnWant{(uint32_t)b, (uint32_t)(q[k] - idx->off[b]), k});
-    }
+    const LineRoute r = mode == LN_LOCATE ? route_locate(t->cum, t->total_bytes, q[k]) : route_number(t->cum, idx->off, q[k]);
+    block_of[k] = r.block; res[k] = r.value;
+    if (r.block != ~0u) C.wants.push_back(LnWant{r.block, r.arg, k});
   }
   std::stable_sort(C.wants.begin(), C.wants.end(), [](const LnWant& a, const LnWant& b) { return a.block < b.block; });
   std::vector<uint32_t> touched;
   for (const LnWant& w : C.wants) if (touched.empty() || touched.back() != w.block) touched.push_back(w.block);
   if (!touched.empty()) {
-    std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD); std::vector<uint32_t> crc_got(idx->e.size(), 0);
-    CJS_TRY(lines_run(in, d_in, idx, touched, C, verdict, crc_got, opts, R));
+    RangeVerdicts V(idx);
+    CJS_TRY(lines_run(in, d_in, idx, touched, C, V, opts, R));
     bool first = true;
     for (size_t k = 0; k < count; k++) {
       const uint32_t b = block_of[k];
       if (b == ~0u) continue;
-      const bool bad = verdict[b] != RG_GOOD;
+      const bool bad = !V.good(b);
       if (!bad && C.got[b] == t->nl[b] && C.ans[k] != ~0ull) { res[k] = mode == LN_LOCATE ? C.ans[k] : t->cum[b] + C.ans[k]; continue; }
       st[k] = CJS_E_DATA_ERROR;
       if (!first) continue;
       first = false;
-      if (bad) range_bad_detail(idx, b, verdict, crc_got);
+      if (bad) V.set_bad_detail(idx, b);
       else set_detail("line table does not match the stream at block %u", b);
     }
   }

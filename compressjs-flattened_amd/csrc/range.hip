@@ -1,6 +1,6 @@
 // range.hip -- the indexed range reads (cjs_bzip2_index_build, cjs_bzip2_read_ranges[_device]): their two kernels
-// and, on the decode engine (dec_engine.h, decode.hip), their driver: the pass engine (range_engine.h), which the pattern search
-// (search.hip) runs on as well, and the range reads' consumer of it.
+// and, on the decode engine (dec_engine.h, decode.hip), the pass engine with what its consumers share on the host
+// (range_engine.h lists the four and the shared pieces), and the range reads' own consumer of it.
 //   rg_slices       the slice gather: every piece (source address, destination address, length) of a pass in one launch per slab.
 //                   It moves the ranges' bytes out of a pass's expanded blocks (to the packed device buffer of the host form, or
 //                   straight into the caller's d_out), and it is the device form's upload: the byte runs of the touched blocks,
@@ -22,23 +22,11 @@ constexpr uint64_t SLICE_TASK = 65536;                 // (a multiple of 16)
 constexpr size_t SLICE_SLAB = 65535;
 
 // The interior of a piece: nvec 16-byte vectors, the destination da aligned, the source sa = 16 * q + 4 * K + m behind an aligned
-// address.  Lane i stores vector i (consecutive lanes, consecutive 16 bytes) from the two aligned source vectors it straddles:
-// dword j of the result is dwords K + j and K + j + 1 of the eight, funnelled by m bytes.  K and m are the same for every vector
-// of the piece, so the choice is made once per workgroup.
+// address.  Lane i stores vector i (consecutive lanes, consecutive 16 bytes) from the two aligned source vectors it straddles
+// (rg_funnel16).  K and m are the same for every vector of the piece, so the choice is made once per workgroup.
 template <int K>
 __device__ __forceinline__ void rg_interior(uint64_t sa, uint64_t da, uint64_t nvec, uint32_t m, uint64_t lo, uint64_t hi) {
-  for (uint64_t v = threadIdx.x; v < nvec; v += 256) {
-    const uint64_t base = (sa + 16 * v) & ~15ull;
-    const uint4 a = rg_ld16(base, lo, hi);
-    const uint4 b = (K || m) ? rg_ld16(base + 16, lo, hi) : make_uint4(0u, 0u, 0u, 0u);
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    uint4 o;
-    o.x = __builtin_amdgcn_alignbyte(w[K + 1], w[K], m);
-    o.y = __builtin_amdgcn_alignbyte(w[K + 2], w[K + 1], m);
-    o.z = __builtin_amdgcn_alignbyte(w[K + 3], w[K + 2], m);
-    o.w = __builtin_amdgcn_alignbyte(w[K + 4], w[K + 3], m);
-    *reinterpret_cast<uint4*>(da + 16 * v) = o;
-  }
+  for (uint64_t v = threadIdx.x; v < nvec; v += 256) *reinterpret_cast<uint4*>(da + 16 * v) = rg_funnel16<K>(sa + 16 * v, m, lo, hi);
 }
 
 // One workgroup per piece (at most SLICE_TASK bytes: the host cuts longer ones).  Source and destination are at any byte
@@ -105,7 +93,6 @@ struct RangePlan {
   std::vector<RangePiece> pieces;
   std::vector<uint32_t> touched;
   uint64_t total = 0;
-  size_t first_block(const cjs_bz_index* ix, uint64_t o) const { return (size_t)(std::upper_bound(ix->off.begin(), ix->off.end(), o) - ix->off.begin()) - 1; }
 };
 
 int range_plan(const cjs_bz_index* ix, const uint64_t* off, const uint64_t* len, size_t count, RangePlan& P) {
@@ -117,7 +104,7 @@ int range_plan(const cjs_bz_index* ix, const uint64_t* off, const uint64_t* len,
     if (off[k] >= end || !len[k]) continue;
     P.lay_len[k] = std::min<uint64_t>(len[k], end - off[k]);
     uint64_t pos = off[k], left = P.lay_len[k];
-    for (size_t b = P.first_block(ix, pos); left; b++) {
+    for (size_t b = range_block_of(ix, pos); left; b++) {
       const uint64_t take = std::min<uint64_t>(left, ix->off[b + 1] - pos);
       if (take) P.pieces.push_back(RangePiece{(uint32_t)b, (uint32_t)(pos - ix->off[b]), (uint32_t)take, 0u, P.total + (pos - off[k])});
       pos += take; left -= take;
@@ -168,8 +155,8 @@ void range_slices(std::vector<Slice>& sl, uint64_t src, uint64_t dst, uint64_t l
 }  // namespace
 
 // The pass engine (range_engine.h): the passes over `touched`, each block's verdict, every decoded batch handed to `consume`.
-int cjs::range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const std::vector<uint32_t>& touched,
-                      std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st, const RangeConsumer& consume) {
+int cjs::range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const std::vector<uint32_t>& touched, RangeVerdicts& V, int dev,
+                      RangeStats& st, const RangeConsumer& consume) {
   const size_t nt = touched.size(), cap_blocks = range_pass_blocks(), G = dec_group_bytes();
   Stream keep;                                                     // one stream for all passes
   for (size_t t0 = 0; t0 < nt;) {
@@ -250,7 +237,7 @@ int cjs::range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_inde
     for (size_t i = 0; i < t1 - t0; i++) {
       const uint32_t b = touched[t0 + i], c = cand_of[i];
       const cjs_bz_index_entry& e = ix->e[b];
-      verdict[b] = RG_MISMATCH;
+      V.verdict[b] = RG_MISMATCH;
       if (c == ~0u || S.cands[c].kind != 0) continue;
       const BlockOut& bo = S.bos[c];
       const int v = bz_block_verdict(bo, 100000u * e.level, e.bitpos, false);
@@ -263,10 +250,10 @@ int cjs::range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_inde
       for (size_t k = g0; k < g1; k++) {
         const uint32_t b = chain_blk[k];
         if (J.chain[k].out_len != ix->e[b].size) continue;
-        if (J.crc_got[k] != J.chain[k].crc) { verdict[b] = RG_BAD_CRC; crc_got[b] = J.crc_got[k]; continue; }
-        verdict[b] = RG_GOOD;
+        if (J.crc_got[k] != J.chain[k].crc) { V.verdict[b] = RG_BAD_CRC; V.crc_got[b] = J.crc_got[k]; continue; }
+        V.verdict[b] = RG_GOOD;
       }
-      return consume(RangeBatch{J, S, chain_blk, g0, g1, d_exp, q, s});
+      return consume(RangeBatch{J, S, chain_blk, V, g0, g1, d_exp, q, s});
     };
     CJS_TRY(dec_scratch_batches(J, S, use));
     st.h2d += S.h2d; st.d2h += S.d2h; st.a_batches += S.a_batches; st.b_batches += S.b_batches;
@@ -276,18 +263,47 @@ int cjs::range_engine(const uint8_t* in, const uint8_t* d_src, const cjs_bz_inde
   return 0;
 }
 
-void cjs::range_bad_detail(const cjs_bz_index* ix, size_t bad, const std::vector<uint8_t>& verdict, const std::vector<uint32_t>& crc_got) {
+void cjs::RangeVerdicts::set_bad_detail(const cjs_bz_index* ix, size_t bad) const {
   char d[96];
   if (verdict[bad] == RG_BAD_CRC) { bad_crc_detail(d, sizeof d, crc_got[bad], ix->e[bad].crc); set_detail("%s", d); }
   else set_detail("index does not match the stream at block %zu", bad);
+}
+
+int cjs::check_index_stream(const void* in, size_t n, const cjs_bz_index* idx) {
+  if (!in && n) return CJS_E_INVALID_ARG;
+  if (idx->stream_bytes != n) { set_detail("the index is of a stream of %llu bytes", (unsigned long long)idx->stream_bytes); return CJS_E_INVALID_ARG; }
+  return 0;
+}
+
+int cjs::count_then_emit(hipStream_t s, uint64_t nt, uint32_t trail, const std::function<int(uint64_t* cnt)>& count_scan,
+                         const std::function<void(const uint64_t* cnt, uint4* out, uint64_t keep)>& emit, void* host_out, uint64_t room, ScanStats& st, uint64_t* res) {
+  if (!nt) return drained(s, 0);
+  if (nt > 0x7FFFFFFFull) return drained(s, CJS_E_UNSUPPORTED);
+  DevBuf d_cnt(8 * (size_t)(nt + trail));
+  if (!d_cnt.p) return drained(s, CJS_E_OUT_OF_MEMORY);
+  uint64_t* cnt = (uint64_t*)d_cnt.p;
+  // from here on no way out without a synchronize: the copies may still be reading the caller's vectors or writing `res`
+  int rc = count_scan(cnt);
+  if (!rc && (hipGetLastError() != hipSuccess || hipMemcpyAsync(res, cnt + nt, 8 * (size_t)trail, hipMemcpyDeviceToHost, s) != hipSuccess)) rc = CJS_E_HIP;
+  if ((rc = drained(s, rc))) return rc;
+  st.d2h += 8 * (uint64_t)trail; st.tiles += nt;
+  const uint64_t keep = std::min(res[0], room);
+  if (!keep) return 0;                                             // (a count query and a batch without a hit: one kernel pass less)
+  DevBuf d_out(16 * (size_t)keep);
+  if (!d_out.p) return CJS_E_OUT_OF_MEMORY;
+  emit(cnt, (uint4*)d_out.p, keep);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(host_out, d_out.p, 16 * (size_t)keep, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
+  if ((rc = drained(s, rc))) return rc;
+  st.d2h += 16 * keep;
+  return 0;
 }
 
 namespace {
 
 // The range reads' consumer of the engine: the good blocks' pieces as runs of the scratch (neighbours in both the scratch and the
 // layout merged), gathered to their place.  host_out: the host form's buffer in the plan's layout; else d_out.
-int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const RangePlan& P, uint8_t* host_out, uint8_t* d_out,
-              std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st) {
+int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const RangePlan& P, uint8_t* host_out, uint8_t* d_out, RangeVerdicts& V, int dev,
+              RangeStats& st) {
   size_t piece_at = 0;                                             // pieces in front of it belong to earlier blocks
   auto deliver = [&](const RangeBatch& B) {
     uint8_t* const d_exp = B.d_exp; hipStream_t s = B.s; ShareScratch& q = B.q;
@@ -297,7 +313,7 @@ int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, c
     for (size_t k = B.g0; k < B.g1; k++) {
       const uint32_t b = B.blk[k];
       while (piece_at < P.pieces.size() && P.pieces[piece_at].block < b) piece_at++;
-      if (verdict[b] != RG_GOOD) continue;
+      if (!V.good(b)) continue;
       for (; piece_at < P.pieces.size() && P.pieces[piece_at].block == b; piece_at++) {
         const RangePiece& p = P.pieces[piece_at];
         const uint64_t src = B.J.out_off[k] + p.in_off;
@@ -340,28 +356,25 @@ int range_run(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, c
     if (bounce) { uint64_t at = 0; for (const Run& r : runs) { memcpy(host_out + r.to, bounce.p + at, (size_t)r.len); at += r.len; } }
     return 0;
   };
-  return range_engine(in, d_src, ix, P.touched, verdict, crc_got, dev, st, deliver);
+  return range_engine(in, d_src, ix, P.touched, V, dev, st, deliver);
 }
 
 // The verdict of every range from the verdicts of the blocks: status, and the detail of the lowest-index failing range's first bad
 // block.  `fail` gets 1 for a failing range.
-void range_verdicts(const cjs_bz_index* ix, const RangePlan& P, const uint64_t* off, size_t count, const std::vector<uint8_t>& verdict,
-                    const std::vector<uint32_t>& crc_got, int32_t* status, std::vector<uint8_t>& fail) {
+void range_verdicts(const cjs_bz_index* ix, const RangePlan& P, const uint64_t* off, size_t count, const RangeVerdicts& V, int32_t* status, std::vector<uint8_t>& fail) {
   const size_t nblk = ix->e.size();
   std::vector<size_t> next_bad(nblk + 1, nblk);                    // the first bad block at or behind b
-  for (size_t b = nblk; b-- > 0;) next_bad[b] = verdict[b] != RG_GOOD ? b : next_bad[b + 1];
+  for (size_t b = nblk; b-- > 0;) next_bad[b] = !V.good(b) ? b : next_bad[b + 1];
   fail.assign(count, 0);
   bool first = true;
   for (size_t k = 0; k < count; k++) {
     status[k] = 0;
     if (!P.lay_len[k]) continue;
-    const size_t b0 = P.first_block(ix, off[k]), b1 = P.first_block(ix, off[k] + P.lay_len[k] - 1), bad = next_bad[b0];
+    const size_t b0 = range_block_of(ix, off[k]), b1 = range_block_of(ix, off[k] + P.lay_len[k] - 1), bad = next_bad[b0];
     if (bad > b1) continue;
     status[k] = CJS_E_DATA_ERROR; fail[k] = 1;
-    if (first) {
-      range_bad_detail(ix, bad, verdict, crc_got);
-      first = false;
-    }
+    if (first) V.set_bad_detail(ix, bad);
+    first = false;
   }
 }
 
@@ -369,21 +382,19 @@ void range_verdicts(const cjs_bz_index* ix, const RangePlan& P, const uint64_t* 
 
 // The range reads' core with the result on the device (range_engine.h), for a caller that has checked its arguments.
 int cjs::range_read_to_device(const uint8_t* in, const uint8_t* d_src, const cjs_bz_index* ix, const uint64_t* off, const uint64_t* len, size_t count,
-                              uint8_t* d_out, std::vector<uint8_t>& verdict, std::vector<uint32_t>& crc_got, int dev, RangeStats& st) {
+                              uint8_t* d_out, RangeVerdicts& V, int dev, RangeStats& st) {
   RangePlan P;
   CJS_TRY(range_plan(ix, off, len, count, P));
   if (P.touched.empty()) return 0;
-  return range_run(in, d_src, ix, P, nullptr, d_out, verdict, crc_got, dev, st);
+  return range_run(in, d_src, ix, P, nullptr, d_out, V, dev, st);
 }
 
 namespace {
 
 int range_check_args(const void* in, size_t n, const cjs_bz_index* idx, const uint64_t* off, const uint64_t* len, size_t count, const size_t* out_off,
                      const size_t* out_len, const int32_t* status) {
-  if (!idx || (!in && n)) return CJS_E_INVALID_ARG;
-  if (count && (!off || !len || !out_off || !out_len || !status)) return CJS_E_INVALID_ARG;
-  if (idx->stream_bytes != n) { set_detail("the index is of a stream of %llu bytes", (unsigned long long)idx->stream_bytes); return CJS_E_INVALID_ARG; }
-  return 0;
+  if (!idx || (count && (!off || !len || !out_off || !out_len || !status))) return CJS_E_INVALID_ARG;
+  return check_index_stream(in, n, idx);
 }
 
 void range_debug(const char* form, const cjs_bz_index* ix, const RangePlan& P, size_t count, const RangeStats& st) {
@@ -418,16 +429,14 @@ extern "C" int cjs_bzip2_read_ranges(const uint8_t* in, size_t n, const cjs_bz_i
   CJS_TRY(range_plan(idx, off, len, count, P));
   HostBuf host((size_t)std::max<uint64_t>(P.total, 1));          // (given back on every failing path)
   if (!host) return CJS_E_OUT_OF_MEMORY;
-  std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD), fail; std::vector<uint32_t> crc_got(idx->e.size(), 0);
+  RangeVerdicts V(idx); std::vector<uint8_t> fail;
   RangeStats st;
   if (!P.touched.empty()) {
-    CJS_TRY(select_device(opts));
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-    RestoreDevice restore{dev};
-    CJS_TRY(range_run(in, nullptr, idx, P, host.p, nullptr, verdict, crc_got, dev, st));
+    CallDevice cd;
+    CJS_TRY(cd.select(opts));
+    CJS_TRY(range_run(in, nullptr, idx, P, host.p, nullptr, V, cd.dev, st));
   }
-  range_verdicts(idx, P, off, count, verdict, crc_got, status, fail);
+  range_verdicts(idx, P, off, count, V, status, fail);
   size_t at = 0;                                                   // the layout behind the verdicts: a failed range takes no room
   for (size_t k = 0; k < count; k++) {
     out_off[k] = at; out_len[k] = fail[k] ? 0 : (size_t)P.lay_len[k];
@@ -454,15 +463,13 @@ extern "C" int cjs_bzip2_read_ranges_device(const uint8_t* d_in, size_t n, const
   for (size_t k = 0; k < count; k++) { out_off[k] = (size_t)P.lay_off[k]; out_len[k] = (size_t)P.lay_len[k]; status[k] = 0; }
   if (P.total > out_cap) return CJS_E_OUTPUT_TOO_SMALL;           // (known from the index alone: nothing is launched, d_out untouched)
   if (P.touched.empty()) return 0;
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if (!on_device(d_in, dev) || !on_device(d_out, dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
-  std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD), fail; std::vector<uint32_t> crc_got(idx->e.size(), 0);
+  CallDevice cd;
+  CJS_TRY(cd.select(opts));
+  if (!on_device(d_in, cd.dev) || !on_device(d_out, cd.dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
+  RangeVerdicts V(idx); std::vector<uint8_t> fail;
   RangeStats st;
-  CJS_TRY(range_run(nullptr, d_in, idx, P, nullptr, d_out, verdict, crc_got, dev, st));
-  range_verdicts(idx, P, off, count, verdict, crc_got, status, fail);
+  CJS_TRY(range_run(nullptr, d_in, idx, P, nullptr, d_out, V, cd.dev, st));
+  range_verdicts(idx, P, off, count, V, status, fail);
   for (size_t k = 0; k < count; k++) if (fail[k]) out_len[k] = 0;      // (the region keeps its place)
   range_debug("device", idx, P, count, st);
   return 0;

@@ -5,9 +5,8 @@
 //   sr_scan    the exclusive scan of the tile counts (one workgroup), the batch's total behind them
 //   sr_emit    the matches of a tile again, written at base + rank
 // A segment is a run of GOOD, index-consecutive blocks of a batch, possibly with a prefix from the call's carry buffer: the last
-// (longest pattern - 1) bytes of the batch before, where a match that ends in this batch may start.
+// (longest pattern - 1) bytes of the batch before, where a match that ends in this batch may start (search_plan of scan_plan.h).
 #include "range_engine.h"
-#include "prims.hpp"
 #include <string.h>
 
 using namespace cjs;
@@ -20,13 +19,7 @@ constexpr uint32_t SR_MAXP = CJS_SEARCH_MAX_PATTERNS, SR_MAXL = CJS_SEARCH_MAX_P
 constexpr uint32_t SR_TEXT = (15 + SR_TILE + SR_MAXL - 1 + 15) / 16 * 16 + 16;      // staged bytes at any alignment, + the word behind the last
 static_assert(SR_ROWS == 256 && SR_MAXP == 64, "one row per thread of the block scan, one mask bit per pattern");
 
-struct SrSeg {
-  uint64_t src, len;       // len bytes at device address src ...
-  uint64_t off;            // ... behind `pre` bytes of the carry buffer; decoded offset of the first of all these bytes
-  uint64_t npos;           // start positions tested: [0, npos) of the pre + len bytes
-  uint64_t tile0;          // the segment's first tile
-  uint32_t pre, pad;
-};
+struct SrSeg : SearchSeg {};      // (scan_plan.h; the kernels' own name for it: the host hands them an array of SearchSeg)
 struct SrPatTab {          // the patterns as the kernels read them (folded under NOCASE)
   uint32_t npat, maxlen, nbytes, pad;
   uint32_t word[SR_MAXP], mask[SR_MAXP];      // the first up-to-4 bytes, little-endian, and the mask of those that exist
@@ -54,9 +47,7 @@ __device__ __forceinline__ uint32_t sr_fold4(uint32_t w) {
 __device__ __forceinline__ SrTile sr_stage(SrLds& L, const SrSeg* __restrict__ segs, uint32_t nseg, const SrPatTab* __restrict__ tab,
                                            const uint8_t* __restrict__ carry, uint32_t fold) {
   const uint64_t t = blockIdx.x;
-  uint32_t lo = 0, hi = nseg;                                                // the last segment with tile0 <= t
-  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (segs[mid].tile0 <= t) lo = mid; else hi = mid; }
-  const SrSeg g = segs[lo];
+  const SrSeg g = rg_seg_of(segs, nseg, t);
   const uint32_t npat = tab->npat, maxlen = tab->maxlen;
   const uint64_t p0 = (t - g.tile0) * SR_TILE, n = g.pre + g.len;
   SrTile T;
@@ -127,14 +118,7 @@ __global__ __launch_bounds__(256) void sr_count(const SrSeg* __restrict__ segs, 
 // cnt[0 .. nt) -> their exclusive prefix sums, cnt[nt] = the total
 __global__ __launch_bounds__(256) void sr_scan(uint64_t* __restrict__ cnt, uint64_t nt) {
   __shared__ uint64_t sm[4];
-  uint64_t run = 0;
-  for (uint64_t b = 0; b < nt; b += 256) {
-    const uint64_t i = b + threadIdx.x, v = i < nt ? cnt[i] : 0;
-    uint64_t tot;
-    const uint64_t ex = block_excl_sum<256, uint64_t>(v, sm, tot);
-    if (i < nt) cnt[i] = run + ex;
-    run += tot;
-  }
+  const uint64_t run = rg_scan_counts(cnt, nt, sm, [](uint64_t) {});
   if (threadIdx.x == 0) cnt[nt] = run;
 }
 
@@ -181,8 +165,8 @@ struct SearchCall {
   uint64_t win_lo = 0, win_hi = 0;
   cjs_bz_match* found = nullptr; uint64_t cap = 0, n_matches = 0;
   Owner<void*, PoolGive> mem;                                                 // SrPatTab, then the two carry buffers of SR_MAXL bytes
-  int cur = 0; uint32_t carry_len = 0; uint64_t carry_off = 0;     // carry_len bytes of decoded offset carry_off in buffer `cur`
-  uint64_t h2d = 0, d2h = 0, tiles = 0;
+  int cur = 0; SearchCarry held;                                   // the carry's bytes stand in buffer `cur`
+  ScanStats st;
   uint8_t* carry(int k) const { return (uint8_t*)mem.p + sizeof(SrPatTab) + SR_MAXL * (size_t)k; }
 
   int device_state() {                                             // (at the first batch: the device is current then)
@@ -190,99 +174,60 @@ struct SearchCall {
     mem = DevBuf(sizeof(SrPatTab) + 2 * SR_MAXL);
     if (!mem.p) return CJS_E_OUT_OF_MEMORY;
     if (hipMemcpy(mem.p, &tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) return CJS_E_HIP;
-    h2d += sizeof tab;
+    st.h2d += sizeof tab;
     return 0;
   }
 
   // The matches of `segs` (npos set, in order), appended to the list.  Returns with the stream drained.
-  int scan_segments(hipStream_t s, std::vector<SrSeg>& all) {
-    std::vector<SrSeg> segs;
-    uint64_t nt = 0;
-    for (SrSeg g : all) if (g.npos) { g.tile0 = nt; nt += (g.npos + SR_TILE - 1) / SR_TILE; segs.push_back(g); }
-    int rc = 0;
-    if (nt) {
-      if (nt > 0x7FFFFFFFull) return CJS_E_UNSUPPORTED;
-      DevBuf d_segs(sizeof(SrSeg) * segs.size()), d_cnt(8 * (size_t)(nt + 1));
-      if (!d_segs.p || !d_cnt.p) return CJS_E_OUT_OF_MEMORY;
-      const SrPatTab* d_tab = (const SrPatTab*)mem.p;
-      const uint32_t nseg = (uint32_t)segs.size();
-      uint64_t total = 0;
-      // from here on no way out without a synchronize: the copies may still be reading `segs` / writing `total`
-      if (hipMemcpyAsync(d_segs.p, segs.data(), sizeof(SrSeg) * segs.size(), hipMemcpyHostToDevice, s) != hipSuccess) rc = CJS_E_HIP;
-      else {
-        hipLaunchKernelGGL(sr_count, dim3((unsigned)nt), dim3(256), 0, s, (const SrSeg*)d_segs.p, nseg, d_tab, (const uint8_t*)carry(cur), fold, win_lo, win_hi, (uint64_t*)d_cnt.p);
-        hipLaunchKernelGGL(sr_scan, dim3(1), dim3(256), 0, s, (uint64_t*)d_cnt.p, nt);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, (uint64_t*)d_cnt.p + nt, 8, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
-      }
-      if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = CJS_E_HIP;
-      if (rc) return rc;
-      h2d += sizeof(SrSeg) * segs.size(); d2h += 8; tiles += nt;
-      const uint64_t keep = n_matches < cap ? std::min<uint64_t>(total, cap - n_matches) : 0;
-      if (keep) {                                                    // (a count query never gets here: one kernel pass less)
-        DevBuf d_found(16 * (size_t)keep);
-        if (!d_found.p) return CJS_E_OUT_OF_MEMORY;
-        hipLaunchKernelGGL(sr_emit, dim3((unsigned)nt), dim3(256), 0, s, (const SrSeg*)d_segs.p, nseg, d_tab, (const uint8_t*)carry(cur), fold, win_lo, win_hi,
-                           (const uint64_t*)d_cnt.p, (uint4*)d_found.p, keep);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(found + n_matches, d_found.p, 16 * (size_t)keep, hipMemcpyDeviceToHost, s) != hipSuccess) rc = CJS_E_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = CJS_E_HIP;
-        if (rc) return rc;
-        d2h += 16 * keep;
-      }
-      n_matches += total;
+  int scan_segments(hipStream_t s, std::vector<SearchSeg>& segs) {
+    const uint64_t nt = tile_segments(segs, SR_TILE);
+    const SrPatTab* d_tab = (const SrPatTab*)mem.p;
+    const uint32_t nseg = (uint32_t)segs.size();
+    Owner<void*, PoolGive> d_segs;
+    auto count_scan = [&](uint64_t* cnt) {
+      d_segs = DevBuf(sizeof(SearchSeg) * segs.size());
+      if (!d_segs.p) return (int)CJS_E_OUT_OF_MEMORY;
+      if (hipMemcpyAsync(d_segs.p, segs.data(), sizeof(SearchSeg) * segs.size(), hipMemcpyHostToDevice, s) != hipSuccess) return (int)CJS_E_HIP;
+      st.h2d += sizeof(SearchSeg) * segs.size();
+      hipLaunchKernelGGL(sr_count, dim3((unsigned)nt), dim3(256), 0, s, (const SrSeg*)d_segs.p, nseg, d_tab, (const uint8_t*)carry(cur), fold, win_lo, win_hi, cnt);
+      hipLaunchKernelGGL(sr_scan, dim3(1), dim3(256), 0, s, cnt, nt);
       return 0;
-    }
-    return hipStreamSynchronize(s) != hipSuccess ? (int)CJS_E_HIP : 0;
+    };
+    auto emit = [&](const uint64_t* cnt, uint4* out, uint64_t keep) {
+      hipLaunchKernelGGL(sr_emit, dim3((unsigned)nt), dim3(256), 0, s, (const SrSeg*)d_segs.p, nseg, d_tab, (const uint8_t*)carry(cur), fold, win_lo, win_hi, cnt, out, keep);
+    };
+    uint64_t total = 0;
+    CJS_TRY(count_then_emit(s, nt, 1, count_scan, emit, found + std::min(n_matches, cap), n_matches < cap ? cap - n_matches : 0, st, &total));
+    n_matches += total;
+    return 0;
   }
 
-  SrSeg carry_segment() const { return SrSeg{0, 0, carry_off, carry_len, 0, carry_len, 0}; }      // the carry alone: nothing follows it
-
-  // A decoded batch: its segments, the carry in front of the first if that goes on where the carry ends, else the carry on its
-  // own; the last segment's tail becomes the new carry and is tested with the next batch (or by finish()).
-  int batch(const RangeBatch& B, const std::vector<uint8_t>& verdict) {
-    CJS_TRY(device_state());
-    std::vector<SrSeg> segs;
-    bool open = false, first = true;
-    uint64_t end = 0;
-    for (size_t k = B.g0; k < B.g1; k++) {
-      const uint32_t b = B.blk[k];
-      if (verdict[b] != RG_GOOD) { open = false; continue; }
-      const uint64_t o = ix->off[b], len = ix->e[b].size;
-      if (open && o == end) { segs.back().len += len; end += len; continue; }
-      SrSeg g{(uint64_t)(uintptr_t)(B.d_exp + B.J.out_off[k]), len, o, 0, 0, 0, 0};
-      if (first && carry_len) {
-        if (carry_off + carry_len == o) { g.pre = carry_len; g.off = carry_off; }
-        else segs.push_back(carry_segment());
-      }
-      first = false;
-      segs.push_back(g); open = true; end = o + len;
-    }
-    if (first) return 0;                                             // no good block: the carry waits on
-    for (SrSeg& g : segs) g.npos = g.pre + g.len;
-    SrSeg& last = segs.back();
-    const uint64_t n = last.pre + last.len, hold = std::min<uint64_t>(tab.maxlen - 1, n);
-    last.npos = n - hold;
+  // A decoded batch: its segments and the new carry (search_plan); the last segment's tail is tested with the next batch (or by
+  // finish()).
+  int batch(const RangeBatch& B) {
+    if (const int rc = device_state()) return drained(B.s, rc);
+    SearchPlan P = search_plan(B.good_runs(ix->off, 0, ~0ull), held, tab.maxlen);
+    if (P.segs.empty()) return 0;                                    // no good block: the carry waits on
+    const SearchSeg& last = P.segs.back();
+    uint8_t* to = carry(cur ^ 1);                                    // the last P.hold bytes of the prefix and the segment
     int rc = 0;
-    if (hold) {                                                      // bytes [n - hold, n) of the prefix and the segment
-      uint8_t* to = carry(cur ^ 1);
-      const uint64_t from_pre = n - hold < last.pre ? last.pre - (n - hold) : 0;
-      if (from_pre && hipMemcpyAsync(to, carry(cur) + (last.pre - from_pre), (size_t)from_pre, hipMemcpyDeviceToDevice, B.s) != hipSuccess) rc = CJS_E_HIP;
-      if (!rc && hold > from_pre &&
-          hipMemcpyAsync(to + from_pre, (const uint8_t*)(uintptr_t)last.src + (last.len - (hold - from_pre)), (size_t)(hold - from_pre), hipMemcpyDeviceToDevice, B.s) != hipSuccess) rc = CJS_E_HIP;
-    }
-    const uint64_t new_off = last.off + n - hold;
-    const int rc2 = scan_segments(B.s, segs);
-    if (rc || rc2) { (void)hipStreamSynchronize(B.s); return rc ? rc : rc2; }
-    cur ^= hold ? 1 : 0; carry_len = (uint32_t)hold; carry_off = new_off;
+    if (P.from_pre && hipMemcpyAsync(to, carry(cur) + (last.pre - P.from_pre), (size_t)P.from_pre, hipMemcpyDeviceToDevice, B.s) != hipSuccess) rc = CJS_E_HIP;
+    const uint64_t from_seg = P.hold - P.from_pre;
+    if (!rc && from_seg && hipMemcpyAsync(to + P.from_pre, (const uint8_t*)(uintptr_t)last.src + (last.len - from_seg), (size_t)from_seg, hipMemcpyDeviceToDevice, B.s) != hipSuccess)
+      rc = CJS_E_HIP;
+    const int rc2 = scan_segments(B.s, P.segs);
+    if (rc || rc2) return rc ? rc : rc2;
+    cur ^= P.hold ? 1 : 0; held = P.next;
     return 0;
   }
 
   int finish() {                                                     // what still waits in the carry
-    if (!carry_len) return 0;
+    if (!held.len) return 0;
     Stream s;
     if (hipStreamCreate(s.put()) != hipSuccess) return CJS_E_HIP;
-    std::vector<SrSeg> segs(1, carry_segment());
+    std::vector<SearchSeg> segs(1, carry_segment(held));
     const int rc = scan_segments(s, segs);
-    carry_len = 0;
+    held.len = 0;
     return rc;
   }
 };
@@ -290,7 +235,7 @@ struct SearchCall {
 int search_check_args(const void* in, size_t n, const cjs_bz_index* idx, const uint8_t* pat, const uint32_t* pat_off, uint32_t npat, uint32_t flags,
                       const cjs_bz_match* found, size_t cap, const cjs_bz_search_info* info, SrPatTab& tab) {
   if (!idx || !info || !pat || !pat_off || (!in && n) || (!found && cap)) return CJS_E_INVALID_ARG;
-  if (idx->stream_bytes != n) { set_detail("the index is of a stream of %llu bytes", (unsigned long long)idx->stream_bytes); return CJS_E_INVALID_ARG; }
+  CJS_TRY(check_index_stream(in, n, idx));
   if (npat < 1 || npat > SR_MAXP) { set_detail("1 to %u patterns", SR_MAXP); return CJS_E_INVALID_ARG; }
   if (flags & ~(uint32_t)CJS_SEARCH_NOCASE) { set_detail("undefined flag bits"); return CJS_E_INVALID_ARG; }
   if (pat_off[0] != 0) { set_detail("pat_off[0] is not 0"); return CJS_E_INVALID_ARG; }
@@ -318,29 +263,26 @@ int search_core(const uint8_t* in, const uint8_t* d_in, size_t n, const cjs_bz_i
   SearchCall C;
   CJS_TRY(search_check_args(in ? (const void*)in : (const void*)d_in, n, idx, pat, pat_off, npat, flags, found, cap, info, C.tab));
   info->n_matches = info->n_bad_blocks = info->blocks_decoded = 0; info->first_bad_block = ~0ull;
-  const uint64_t total = idx->off.back(), win_hi = off + len < off ? total : std::min<uint64_t>(off + len, total);
-  std::vector<uint32_t> touched;                                   // the blocks of non-zero size that overlap [off, win_hi)
-  if (off < win_hi)
-    for (size_t b = range_block_of(idx, off); b < idx->e.size() && idx->off[b] < win_hi; b++) if (idx->e[b].size) touched.push_back((uint32_t)b);
+  const uint64_t win_hi = window_end(off, len, idx->off.back());
+  const std::vector<uint32_t> touched = blocks_under(idx->off, off, win_hi);
   if (touched.empty()) return 0;
-  CJS_TRY(select_device(opts));
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CJS_E_NO_DEVICE;
-  RestoreDevice restore{dev};
-  if (d_in && !on_device(d_in, dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
+  CallDevice cd;
+  CJS_TRY(cd.select(opts));
+  if (d_in && !on_device(d_in, cd.dev)) return CJS_E_INVALID_ARG;      // (no host pointer reaches a kernel)
   C.ix = idx; C.fold = flags & CJS_SEARCH_NOCASE; C.win_lo = off; C.win_hi = win_hi; C.found = found; C.cap = cap;
-  std::vector<uint8_t> verdict(idx->e.size(), RG_GOOD); std::vector<uint32_t> crc_got(idx->e.size(), 0);
+  RangeVerdicts V(idx);
   RangeStats st;
-  CJS_TRY(range_engine(in, d_in, idx, touched, verdict, crc_got, dev, st, [&](const RangeBatch& B) { return C.batch(B, verdict); }));
+  CJS_TRY(range_engine(in, d_in, idx, touched, V, cd.dev, st, [&](const RangeBatch& B) { return C.batch(B); }));
   CJS_TRY(C.finish());
   info->n_matches = C.n_matches; info->blocks_decoded = touched.size();
-  for (uint32_t b : touched) if (verdict[b] != RG_GOOD) { if (!info->n_bad_blocks++) info->first_bad_block = b; }
-  if (info->n_bad_blocks) range_bad_detail(idx, (size_t)info->first_bad_block, verdict, crc_got);
+  const BadBlocks bad = V.bad_among(touched);
+  info->n_bad_blocks = bad.n; info->first_bad_block = bad.first;
+  if (bad.n) V.set_bad_detail(idx, (size_t)bad.first);
   if (env_debug())
     fprintf(stderr, "[cjs search] %s: %u patterns (longest %u), window [%llu, %llu), %zu of %zu blocks touched, %llu bad, %u passes (%u row batches, %u inverse-BWT batches), "
             "upload %llu B, %llu tiles, H2D %llu D2H %llu, %llu matches\n", d_in ? "device" : "host", npat, C.tab.maxlen, (unsigned long long)off, (unsigned long long)win_hi,
             touched.size(), idx->e.size(), (unsigned long long)info->n_bad_blocks, st.passes, st.a_batches, st.b_batches, (unsigned long long)st.up,
-            (unsigned long long)C.tiles, (unsigned long long)(st.h2d + C.h2d), (unsigned long long)(st.d2h + C.d2h), (unsigned long long)C.n_matches);
+            (unsigned long long)C.st.tiles, (unsigned long long)(st.h2d + C.st.h2d), (unsigned long long)(st.d2h + C.st.d2h), (unsigned long long)C.n_matches);
   return 0;
 }
 

@@ -265,6 +265,40 @@ def test_several_batches_in_a_pass_give_the_same(L, fx):
     assert len(lines) == 4 and all(x["passes"] == 1 and x["batches"] >= 4 for x in lines), lines
 
 
+def _cap_cases(f):
+    """S4 against: a flip at both ends of every block (differences in every batch), and flips in its first three bytes only"""
+    everywhere, front = cc.flipped(f["plain"], _tiny_flips(f), seed=6), cc.flipped(f["plain"], [0, 1, 2], seed=8)
+    n = len(cc.expected(f["plain"], everywhere)[0])
+    return [(everywhere, n // 2), (everywhere, 1), (front, 2), (front, 3)]
+
+
+def child_caps(elems):
+    """(a child as well) S4 with at most `elems` BWT bytes to an inverse-BWT batch: [result of both_forms(other, cap=cap)] for
+    every case of _cap_cases; the [cjs compare] lines go to stderr"""
+    os.environ["CJS_DEBUG"] = "1"
+    os.environ["CJS_DEC_BATCH_ELEMS"] = elems
+    import torch  # noqa: F401
+    import support
+    L = cc.bind()
+    f = _fixture(L, "S4", support.Oracle())
+    print(json.dumps([list(cc.both_forms(L, f["stream"], f["h"], other, cap=cap)) for other, cap in _cap_cases(f)]))
+
+
+def test_cap_runs_out_in_a_later_batch(L, fx):
+    """S4 in inverse-BWT batches of at most 40 bytes (its 234 bytes, at least 195 after RLE1: five batches or more in one pass).
+    The list gets full in the middle of a later batch, in the first batch with differences in every later one, and in the first
+    batch with none behind it: the first cap differences, and n_diffs, first_diff and compared count on."""
+    f = fx["S4"]
+    cases = _cap_cases(f)
+    want = cc.expected(f["plain"], cases[0][0])[0]
+    assert len(want) > 100 and want[len(want) // 2][0] > 80 and want[-1][0] == f["total"] - 1
+    got, lines = _run_child("child_caps('40')")
+    for (other, cap), res in zip(cases, got):
+        want, compared = cc.expected(f["plain"], other)
+        assert res == _as_json((want[:cap], _info(want, compared, _blocks_of(f, 0, f["total"])), "")), cap
+    assert len(lines) == 4 * len(cases) and all(x["passes"] == 1 and x["batches"] >= 5 for x in lines), lines
+
+
 def test_device_form_moves_no_bulk(L, fx):
     """From the [cjs compare] lines of a default run of F1 (938,848 decoded bytes, 10 blocks).  The compare's own traffic per
     batch is 16 bytes to the host (the batch's count and first offset) and one 40-byte segment per run of good blocks to the

@@ -223,6 +223,40 @@ def test_cap(L, fx):
         assert got == want[:cap] and info[0] == total, cap
 
 
+def child_caps(elems, calls):
+    """(a child as well) S4 with at most `elems` BWT bytes to an inverse-BWT batch: [result of both_forms(pats, cap=cap)] for every
+    (pats, cap) of `calls`; the [cjs search] lines go to stderr"""
+    os.environ["CJS_DEBUG"] = "1"
+    os.environ["CJS_DEC_BATCH_ELEMS"] = elems
+    import torch  # noqa: F401
+    import support
+    L = sc.bind()
+    f = _fixture(L, "S4", support.Oracle())
+    print(json.dumps([list(sc.both_forms(L, f["stream"], f["h"], pats, cap=cap)) for pats, cap in calls]))
+
+
+def test_cap_runs_out_in_a_later_batch(L, fx):
+    """S4 in inverse-BWT batches of at most 40 bytes (its 234 bytes, at least 195 after RLE1: five batches or more in one pass).  The list gets full in the
+    middle of a later batch, in the first batch with matches in every later one, and in the first batch with none behind it: the
+    first cap matches, and n_matches counts on."""
+    f = fx["S4"]
+    many, head = [b"a", b"ab", b"aba"], [bytes(f["plain"][:12])]
+    want = sc.expected(f["plain"], many)
+    assert len(want) > 100 and sc.expected(f["plain"], head) == [(0, 0)]
+    assert want[len(want) // 2][0] > 80 and want[-1][0] > 200      # (half of the list lies behind the second batch; the last batch has matches)
+    calls = [(many, len(want) // 2), (many, 1), (head, 1), (head + many, 3)]
+    run = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-c", "import test_gpu_search as t; t.child_caps('40', %r)" % (calls,)], capture_output=True,
+                         text=True, env=dict(os.environ, PYTHONPATH=os.pathsep.join(sys.path)), cwd=os.path.dirname(os.path.abspath(__file__)))
+    assert run.returncode == 0, run.stderr[-3000:]
+    got = json.loads(run.stdout.strip().splitlines()[-1])
+    blocks = sum(1 for e in f["entries"] if e[2])
+    for (pats, cap), (m, info, d) in zip(calls, got):
+        full = sc.expected(f["plain"], pats)
+        assert [tuple(x) for x in m] == full[:cap] and tuple(info) == (len(full), 0, 2 ** 64 - 1, blocks) and d == "", (pats, cap)
+    lines = re.findall(r"\[cjs search\] (?:host|device): .*? (\d+) passes \(\d+ row batches, (\d+) inverse-BWT batches\)", run.stderr)
+    assert len(lines) == 4 * len(calls) and all(int(p) == 1 and int(b) >= 5 for p, b in lines), lines
+
+
 def test_nocase(L, oracle):
     """mixed-case text with bytes >= 0x80 (0xC1 / 0xE1 differ by 0x20 like A / a) and @ [ ` { next to letters: only A..Z fold"""
     rng = np.random.RandomState(8)
