@@ -178,6 +178,9 @@ def load_library():
     L.cjs_bzip2_enc_read.argtypes = [V, V, S, PS]
     L.cjs_bzip2_enc_destroy.argtypes = [V]
     L.cjs_bzip2_enc_destroy.restype = None
+    L.cjs_bzip2_enc_index.argtypes = [V, ctypes.POINTER(V), ctypes.POINTER(V)]
+    L.cjs_bzip2_compress_indexed.argtypes = [u8p, S, I, PP, PS, ctypes.POINTER(V), ctypes.POINTER(V), V]
+    L.cjs_bzip2_compress_device_indexed.argtypes = [V, V, S, I, V, S, PS, ctypes.POINTER(V), ctypes.POINTER(V), ctypes.POINTER(Stats)]
     L.cjs_bzip2_dec_create.argtypes = [ctypes.POINTER(V), I, S, S, V]
     L.cjs_bzip2_dec_write.argtypes = [V, V, S, PS]
     L.cjs_bzip2_dec_finish.argtypes = [V]
@@ -241,6 +244,22 @@ class Bzip2:
     def compressFile(input, output=None, props=None):
         res = _stream_call(load_library().cjs_bzip2_compress, input, _bzip2_level(props))
         return _deliver(res, output)
+
+    @staticmethod
+    def compressIndexed(input, props=None, lines=True, n_devices=0):
+        """compressFile that also hands out the tables of its stream (cjs_bzip2_compress_indexed): (stream, Bzip2Index,
+        Bzip2Lines or None).  The stream is compressFile's; the tables are what Bzip2Index.build / Bzip2Lines.build give on it,
+        without their table pass and full decode.  n_devices: cjs_opts.n_devices (0: one GPU, or CJS_DEVICES)."""
+        L = load_library()
+        level = _bzip2_level(props)
+        data = _coerce_input(input)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        out, out_n = u8p(), ctypes.c_size_t(0)
+        hi, hl = ctypes.c_void_p(), ctypes.c_void_p()
+        opts = _Opts(ctypes.sizeof(_Opts), -1, n_devices, 0, None)
+        _check(L.cjs_bzip2_compress_indexed(keep.ctypes.data_as(u8p), data.size, level, ctypes.byref(out), ctypes.byref(out_n), ctypes.byref(hi),
+                                            ctypes.byref(hl) if lines else None, ctypes.byref(opts)))
+        return _adopt(out, out_n.value), Bzip2Index(hi), Bzip2Lines(hl) if lines else None
 
     @staticmethod
     def compressFiles(inputs, props=None):
@@ -359,13 +378,25 @@ class Bzip2:
 class Bzip2Encoder:
     """Streaming Bzip2.compressFile (cjs_bzip2_enc_*): write() input in pieces of any size, read() the stream in pieces; after
     finish() the bytes read are those of compressFile over everything written.  The device and pinned memory it holds depend
-    on chunk_bytes (0: the library's default) and level, not on the bytes written.  One worker thread runs the GPU steps."""
+    on chunk_bytes (0: the library's default) and level, not on the bytes written.  One worker thread runs the GPU steps.
+    index / lines: the encoder keeps the block index (and the line table) of the stream it writes, 36 bytes of host memory per
+    block; index() hands them out after finish()."""
 
-    def __init__(self, level=9, chunk_bytes=0, device=-1):
+    ENC_INDEX, ENC_LINES = 4, 8          # CJS_FLAG_ENC_INDEX, CJS_FLAG_ENC_LINES
+
+    def __init__(self, level=9, chunk_bytes=0, device=-1, index=False, lines=False):
         self.L = load_library()
         self.h = ctypes.c_void_p()
-        opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+        self._lines = bool(lines)
+        flags = (self.ENC_INDEX if index or lines else 0) | (self.ENC_LINES if lines else 0)
+        opts = _Opts(ctypes.sizeof(_Opts), device, 0, flags, None)
         _check(self.L.cjs_bzip2_enc_create(ctypes.byref(self.h), level, chunk_bytes, ctypes.byref(opts)))
+
+    def index(self):
+        """(Bzip2Index, Bzip2Lines or None) of the finished stream (cjs_bzip2_enc_index)"""
+        hi, hl = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(self.L.cjs_bzip2_enc_index(self.h, ctypes.byref(hi), ctypes.byref(hl) if self._lines else None))
+        return Bzip2Index(hi), Bzip2Lines(hl) if self._lines else None
 
     def write(self, data):
         a = _coerce_input(data)
@@ -545,6 +576,15 @@ class DeviceContext:
         _check(self.L.cjs_bzip2_compress_device(self.h, d_in_ptr, n, self.level, d_out_ptr, out_cap, ctypes.byref(out_n),
                                                 ctypes.byref(stats) if stats is not None else None))
         return out_n.value
+
+    def compress_indexed(self, d_in_ptr, n, d_out_ptr, out_cap, lines=True, stats=None):
+        """compress, and the tables of the stream it left at d_out (cjs_bzip2_compress_device_indexed): (out_n, Bzip2Index,
+        Bzip2Lines or None)"""
+        out_n = ctypes.c_size_t(0)
+        hi, hl = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(self.L.cjs_bzip2_compress_device_indexed(self.h, d_in_ptr, n, self.level, d_out_ptr, out_cap, ctypes.byref(out_n), ctypes.byref(hi),
+                                                        ctypes.byref(hl) if lines else None, ctypes.byref(stats) if stats is not None else None))
+        return out_n.value, Bzip2Index(hi), Bzip2Lines(hl) if lines else None
 
     def compress_range(self, d_in_ptr, n, first, count, d_out_ptr, out_cap, stats=None, crc_cap=1 << 16):
         bits = ctypes.c_uint64(0)

@@ -1,6 +1,7 @@
 // enc_host.hip — cjs_bzip2_compress: the host-buffer driver of the compress pipeline (pipeline.hip).  One GPU and an input below
 // CJS_CHUNK_BYTES: the cached context of the device, upload, cjs_bzip2_compress_device, download.  Several GPUs and / or a very
-// large input: contiguous block ranges on per-GPU worker threads (compress_multi).  Also cjs_trim.
+// large input: contiguous block ranges on per-GPU worker threads (compress_multi).  cjs_bzip2_compress_indexed is the same call with
+// the rows of every block handed up to the calling thread (enc_index.h).  Also cjs_trim.
 #include "ctx.h"
 #include "host.h"
 #include <stdlib.h>
@@ -58,6 +59,17 @@ struct Shard {
   uint64_t bits = 0;
   std::vector<uint8_t> bytes;            // wave mode: the shard's bit string from bit 0
   uint32_t crc_fold = 0;
+  bool want_rows = false;                // an indexed call: the rows of the shard's blocks (its bytes are a stream of their own, so
+  EncRowsWant rows;                      // they are complete), set at the shard's bit offset by the calling thread
+  EncRowsWant* want() { return want_rows ? &rows : nullptr; }
+};
+// What an indexed call collects on the calling thread: the entries and counts of the whole stream, its last block's end.
+struct HostTables {
+  bool lines = false;
+  std::vector<cjs_bz_index_entry> entries;
+  std::vector<uint32_t> newlines;
+  uint64_t end_bit = ENC_FIRST_BIT;
+  void append(const EncRowsWant& w, uint64_t start_bit, int level) { end_bit = enc_rows_append(entries, newlines, w.rows.data(), w.rows.size(), start_bit, level); }
 };
 static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* sync, bool& published) {
   if (hipSetDevice(sh->device) != hipSuccess) { sh->rc = CJS_E_HIP; return; }
@@ -76,7 +88,7 @@ static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* s
   if (!sync) {                                                           // wave mode: bare bit string from bit 0
     long total = 0;
     std::vector<uint32_t> crcs((size_t)sh->count + 1, 0u);
-    sh->rc = cjs_bzip2_compress_device_range(c, d_in, n, level, 0, -1, hc.c.d_out, out_cap, &sh->bits, crcs.data(), (long)crcs.size(), &total, nullptr);
+    sh->rc = compress_core(c, d_in, n, level, 0, -1, false, hc.c.d_out, out_cap, &sh->bits, crcs.data(), (long)crcs.size(), &total, nullptr, sh->want());
     if (!sh->rc && total != sh->count) sh->rc = CJS_E_HIP;          // cannot happen: the range was cut at block starts
     if (!sh->rc) {
       for (long k = 0; k < sh->count; k++) sh->crc_fold = crc_fold(sh->crc_fold, crcs[(size_t)k]);
@@ -87,7 +99,7 @@ static void run_shard_body(Shard* sh, const uint8_t* in, int level, MultiSync* s
     return;
   }
   cjs_shard_meta meta{};
-  sh->rc = shard_blocks_impl(c, d_in, n, level, 0, 1, nullptr, &meta, nullptr);      // the byte range is a stream of its own
+  sh->rc = shard_blocks_impl(c, d_in, n, level, 0, 1, nullptr, &meta, nullptr, sh->want());      // the byte range is a stream of its own
   if (!sh->rc && (long)meta.total_blocks != sh->count) sh->rc = CJS_E_HIP;           // cannot happen: the range was cut at block starts
   sync->publish(sh->index, meta, sh->rc);
   published = true;
@@ -151,7 +163,7 @@ static std::vector<Shard> deal_ranges(const std::vector<uint64_t>& starts, uint3
   return sh;
 }
 // all ranges at once: they meet at `sync`, where this thread allocates the result once its length is known
-static int run_all_at_once(std::vector<Shard>& sh, const uint8_t* in, int level, uint8_t** out, size_t* out_n) {
+static int run_all_at_once(std::vector<Shard>& sh, const uint8_t* in, int level, uint8_t** out, size_t* out_n, HostTables* tables) {
   const uint32_t nshards = (uint32_t)sh.size();
   MultiSync sync;
   sync.nshards = nshards; sync.metas.assign(nshards, cjs_shard_meta{});
@@ -174,12 +186,19 @@ static int run_all_at_once(std::vector<Shard>& sh, const uint8_t* in, int level,
   int rc = sync.rc;
   for (auto& x : sh) if (x.rc && !rc) rc = x.rc;
   if (rc) return rc;
+  if (tables) {                                               // every shard's rows at the bit its first block stands at
+    std::vector<uint64_t> at(nshards);
+    uint64_t start, tbits; uint32_t scrc; int writer;
+    shard_layout(sync.metas.data(), (int)nshards, 0, start, tbits, scrc, writer, at.data());
+    for (uint32_t i = 0; i < nshards; i++) if (!sh[i].rows.rows.empty()) tables->append(sh[i].rows, at[i], level);
+    if (tables->end_bit != tbits) return CJS_E_HIP;
+  }
   *out = result.release(); *out_n = len;
   return 0;
 }
 // max_parallel ranges at a time, each a bare bit string from bit 0; then the stitch: header, the strings shifted to their place
 // (interiors by a few threads: disjoint whole bytes; then the shared end bytes one range after the other), trailer
-static int run_in_waves(std::vector<Shard>& sh, const uint8_t* in, int level, uint32_t max_parallel, uint8_t** out, size_t* out_n) {
+static int run_in_waves(std::vector<Shard>& sh, const uint8_t* in, int level, uint32_t max_parallel, uint8_t** out, size_t* out_n, HostTables* tables) {
   const uint32_t nshards = (uint32_t)sh.size();
   for (uint32_t i0 = 0; i0 < nshards; i0 += max_parallel) {
     Workers workers;
@@ -194,6 +213,10 @@ static int run_in_waves(std::vector<Shard>& sh, const uint8_t* in, int level, ui
   uint64_t start, total; uint32_t scrc; int writer;
   shard_layout(metas.data(), (int)nshards, 0, start, total, scrc, writer, at.data());
   const size_t len = (size_t)((total + 80 + 7) / 8);
+  if (tables) {
+    for (uint32_t i = 0; i < nshards; i++) if (!sh[i].rows.rows.empty()) tables->append(sh[i].rows, at[i], level);
+    if (tables->end_bit != total) return CJS_E_HIP;
+  }
   HostBuf o;
   o.reset((uint8_t*)calloc(len + 16, 1));                      // (plain malloc'd memory: what cjs_free gives back to free())
   if (!o) return CJS_E_OUT_OF_MEMORY;
@@ -212,7 +235,7 @@ static int run_in_waves(std::vector<Shard>& sh, const uint8_t* in, int level, ui
 }
 // max_parallel = shards in flight at a time (0 = all): one at a time bounds the workspace when the ranges are only there to
 // cut a very large input into pieces (each piece's workspace is ~70 B per byte of its blocks)
-static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshards, uint8_t** out, size_t* out_n, uint32_t max_parallel = 0) {
+static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshards, uint8_t** out, size_t* out_n, uint32_t max_parallel, HostTables* tables) {
   int ndev = 0, dev0 = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev0) != hipSuccess) return CJS_E_NO_DEVICE;
   if (ndev > MAX_DEVICES) ndev = MAX_DEVICES;
@@ -222,15 +245,12 @@ static int compress_multi(const uint8_t* in, size_t n, int level, uint32_t nshar
   CJS_TRY(block_starts(bc, in, n, level, starts));
   const bool waves = max_parallel && max_parallel < nshards;
   std::vector<Shard> sh = deal_ranges(starts, nshards, ndev, waves, bc.c.d_in);
-  return waves ? run_in_waves(sh, in, level, max_parallel, out, out_n) : run_all_at_once(sh, in, level, out, out_n);
+  if (tables) for (Shard& x : sh) { x.want_rows = true; x.rows.lines = tables->lines; }
+  return waves ? run_in_waves(sh, in, level, max_parallel, out, out_n, tables) : run_all_at_once(sh, in, level, out, out_n, tables);
 }
 
-extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_t** out, size_t* out_n, const cjs_opts* opts) {
-  if (!out || !out_n) return CJS_E_INVALID_ARG;
-  *out = nullptr; *out_n = 0;
-  clear_detail();
-  if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;                 // J/Bzip2_joined_.js:2208
-  CJS_GUARD_BEGIN
+// the body of cjs_bzip2_compress; tables (null: the plain call) collects the rows of an indexed call
+static int compress_host(const uint8_t* in, size_t n, int level, uint8_t** out, size_t* out_n, const cjs_opts* opts, HostTables* tables) {
   CJS_TRY(select_device(opts));
   const Opts o(opts);
   uint32_t nshards = o.n_devices;
@@ -243,7 +263,7 @@ extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_
     if (n > 0 && (nshards > 1 || pieces > 1)) {
       const uint32_t par = nshards > 1 ? nshards : 1;
       const uint32_t ranges = (uint32_t)std::max<size_t>(par, std::min<size_t>(pieces, 4096));
-      return compress_multi(in, n, level, ranges, out, out_n, ranges > par ? par : 0);
+      return compress_multi(in, n, level, ranges, out, out_n, ranges > par ? par : 0, tables);
     }
   }
   // The workspace (~70 B per input byte), the staging buffers and the streams are kept per device between calls
@@ -265,7 +285,12 @@ extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_
   const auto t2 = now();
   size_t len = 0;
   c->stage_times = !(o.flags & CJS_FLAG_NO_STAGE_TIMES);
-  if (!rc) rc = cjs_bzip2_compress_device(c, hc.c.d_in, n, level, hc.c.d_out, out_cap, &len, o.stats);
+  EncRowsWant want;
+  if (tables) want.lines = tables->lines;
+  uint64_t bits = 0;
+  if (!rc) rc = compress_core(c, hc.c.d_in, n, level, 0, -1, true, hc.c.d_out, out_cap, &bits, nullptr, 0, nullptr, o.stats, tables ? &want : nullptr);
+  len = (size_t)((bits + 7) / 8);
+  if (!rc && tables) { tables->append(want, ENC_FIRST_BIT, level); if (tables->end_bit + 80 != bits) rc = CJS_E_HIP; }
   const auto t3 = now();
   uint8_t* host = nullptr;
   if (!rc) { host = (uint8_t*)HostPool::take(len ? len : 1); if (!host) rc = CJS_E_OUT_OF_MEMORY; }
@@ -274,6 +299,39 @@ extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_
   if (dbg) fprintf(stderr, "[cjs] host compress: workspace %.2f ms, H2D %.2f ms, pipeline %.2f ms, malloc + D2H %.2f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
   if (hc.check(rc)) { HostPool::give(host); return rc; }
   *out = host; *out_n = len;
+  return 0;
+}
+
+extern "C" int cjs_bzip2_compress(const uint8_t* in, size_t n, int level, uint8_t** out, size_t* out_n, const cjs_opts* opts) {
+  if (!out || !out_n) return CJS_E_INVALID_ARG;
+  *out = nullptr; *out_n = 0;
+  clear_detail();
+  if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;                 // J/Bzip2_joined_.js:2208
+  CJS_GUARD_BEGIN
+  return compress_host(in, n, level, out, out_n, opts, nullptr);
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_bzip2_compress_indexed(const uint8_t* in, size_t n, int level, uint8_t** out, size_t* out_n, cjs_bz_index** idx, cjs_bz_lines** lines,
+                                          const cjs_opts* opts) {
+  if (out) *out = nullptr;
+  if (out_n) *out_n = 0;
+  if (idx) *idx = nullptr;
+  if (lines) *lines = nullptr;
+  if (!out || !out_n || !idx) return CJS_E_INVALID_ARG;
+  clear_detail();
+  if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;
+  CJS_GUARD_BEGIN
+  HostTables tables;
+  tables.lines = lines != nullptr;
+  HostBuf stream; size_t len = 0;
+  {
+    uint8_t* p = nullptr;
+    CJS_TRY(compress_host(in, n, level, &p, &len, opts, &tables));
+    stream.reset(p);
+  }
+  CJS_TRY(enc_tables_make(tables.entries, tables.newlines, tables.end_bit, idx, lines));
+  *out = stream.release(); *out_n = len;
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }

@@ -21,6 +21,10 @@
 // that found both staging chunks full, or in finish) and so cannot read.  Until then they stay in the worker's one download
 // buffer and the worker waits.  A caller that drains after each write of at most chunk_bytes therefore never finds more than one
 // step's output; finish adds at most the steps still under way: the one coming down, the one in work, the one staged, the final one.
+//
+// Index (CJS_FLAG_ENC_INDEX / _LINES): a step's blocks hand their rows (enc_index.h) down with the block CRCs, and the
+// worker appends them as entries at the stream's absolute bit, a 64-bit count kept beside the 0..7 phase.  The held-back last block
+// is not among a step's cnt blocks, so it is counted once: by the step that packs it.  36 bytes of host memory per block.
 #include "cjs_internal.h"
 #include "ctx.h"
 #include "host.h"
@@ -64,6 +68,11 @@ struct cjs_bz_enc {
   std::deque<Piece> outq;
   size_t pending = 0;
   std::thread worker;
+  // the tables of the stream being written (flags): the worker's until worker_done, read by cjs_bzip2_enc_index after it
+  uint32_t flags = 0;
+  std::vector<cjs_bz_index_entry> ix_entries;
+  std::vector<uint32_t> ix_newlines;
+  uint64_t ix_end_bit = ENC_FIRST_BIT;
   int fail(int code) { if (!rc) rc = code; return rc; }      // (mu held)
   // the caller waits for the worker and cannot read meanwhile (mu held)
   bool caller_waits() const { return finishing || (writing && slot[wslot].full); }
@@ -84,6 +93,7 @@ struct EncWork {
   Pinned<RleBlock> h_blk;
   size_t carry = 0;
   uint32_t scrc = 0, phase = 0, steps = 0, packs = 0;
+  uint64_t bit_at = ENC_FIRST_BIT;       // the stream's absolute bit behind the blocks packed so far (an indexing encoder)
   bool header_done = false;
   uint8_t hold = 0;                      // the stream's partial last byte (phase bits), not yet handed out
   // download in flight
@@ -196,7 +206,14 @@ struct EncWork {
       if (ctx->side) CJS_HIP_TRY(hipStreamWaitEvent(s, ctx->ev_join, 0));
       CJS_HIP_TRY(hipMemcpyAsync(h_crc, ctx->rle.block_crc, 4 * (size_t)cnt, hipMemcpyDeviceToHost, s));
       if (!final) CJS_HIP_TRY(hipMemcpyAsync(h_blk, ctx->rle.blocks + cnt, sizeof(RleBlock), hipMemcpyDeviceToHost, s));
+      const bool index = (e->flags & (CJS_FLAG_ENC_INDEX | CJS_FLAG_ENC_LINES)) != 0;
+      if (index) CJS_TRY(enc_rows_enqueue(ctx, d_in, N, 0, cnt, (e->flags & CJS_FLAG_ENC_LINES) != 0));
       CJS_HIP_TRY(hipStreamSynchronize(s));
+      if (index) {
+        EncRowsWant w;
+        enc_rows_collect(ctx, cnt, w);
+        bit_at = enc_rows_append(e->ix_entries, e->ix_newlines, w.rows.data(), w.rows.size(), bit_at, e->level);
+      }
       for (uint32_t k = 0; k < cnt; k++) scrc = crc_fold(scrc, h_crc[k]);
       if (!final) {
         const uint64_t from = h_blk->s;
@@ -211,6 +228,9 @@ struct EncWork {
       uint64_t end_bit = 0;
       CJS_TRY(pack_finish(ctx, &end_bit));
       out_bytes = (size_t)((end_bit + 7) / 8);
+      // (the packer's end, counted from this step's first byte, against the rows' bits)
+      if (index && ((bit_at + (final ? 80 : 0)) & 7) != (end_bit & 7)) return CJS_E_HIP;
+      e->ix_end_bit = bit_at;
       dl = (uint8_t*)HostPool::take(out_bytes);
       if (!dl) return CJS_E_OUT_OF_MEMORY;
       dl_len = out_bytes; dl_end_phase = (uint32_t)(end_bit & 7); dl_final = final;
@@ -294,7 +314,9 @@ extern "C" int cjs_bzip2_enc_create(cjs_bz_enc** out, int level, size_t chunk_by
     if (!chunk_bytes) chunk_bytes = ENC_DEFAULT_CHUNK;
   }
   e->chunk = std::min(std::max(chunk_bytes, ENC_MIN_CHUNK), ENC_MAX_CHUNK);
-  e->device = Opts(opts).device;
+  const Opts o(opts);
+  e->device = o.device;
+  e->flags = o.flags & (CJS_FLAG_ENC_INDEX | CJS_FLAG_ENC_LINES);
   if (e->device < 0 && hipGetDevice(&e->device) != hipSuccess) { (void)hipGetLastError(); e->device = -1; }      // (no device: the first write says so)
   *out = e;
   return 0;
@@ -345,6 +367,19 @@ extern "C" int cjs_bzip2_enc_finish(cjs_bz_enc* e) {
   if (!e->rc) { sl.final = true; sl.full = true; e->cv.notify_all(); }
   e->cv.wait(lk, [&] { return e->worker_done; });
   return e->rc;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+extern "C" int cjs_bzip2_enc_index(cjs_bz_enc* e, cjs_bz_index** idx, cjs_bz_lines** lines) {
+  if (idx) *idx = nullptr;
+  if (lines) *lines = nullptr;
+  if (!e || !idx) return CJS_E_INVALID_ARG;
+  CJS_GUARD_BEGIN
+  std::lock_guard<std::mutex> lock(e->mu);
+  if (e->rc) return e->rc;
+  if (!e->flags || (lines && !(e->flags & CJS_FLAG_ENC_LINES))) return CJS_E_INVALID_ARG;
+  if (!e->finished || (e->started && !e->worker_done)) return CJS_E_INVALID_ARG;      // finish() has not returned 0
+  return enc_tables_make(e->ix_entries, e->ix_newlines, e->ix_end_bit, idx, lines);
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 

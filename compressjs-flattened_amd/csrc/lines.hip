@@ -25,15 +25,6 @@ struct LnAsk { uint32_t blk, arg; };                       // blk: which LnBlk; 
 
 __host__ __device__ __forceinline__ uint32_t ln_tiles(uint32_t len) { return (len + LN_TILE - 1) / LN_TILE; }
 
-// bit 7 of every byte of w that is 0x0A, nothing else: the exact zero-byte test (the borrow form flags a 0x0B behind a 0x0A too)
-__device__ __forceinline__ uint32_t ln_nl4(uint32_t w) {
-  const uint32_t v = w ^ 0x0A0A0A0Au, t = (v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
-  return ~(t | v | 0x7F7F7F7Fu);
-}
-// the newlines of 16 bytes: their number, and bit i = byte i is one
-__device__ __forceinline__ uint32_t ln_count16(uint4 x) { return rg_count16<ln_nl4>(x); }
-__device__ __forceinline__ uint32_t ln_mask16(uint4 x) { return rg_mask16<ln_nl4>(x); }
-
 // a tile's bytes as bounded aligned vectors (nothing outside the tile, so nothing outside the block, is read)
 using LnSpan = RgSpan;
 

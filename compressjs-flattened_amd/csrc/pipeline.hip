@@ -164,7 +164,7 @@ int cjs::pack_finish(cjs_ctx* c, uint64_t* end_bit) {
 // Shared body: stage 0..tables for the whole stream, then pack blocks [first, first+count).
 static int compress_core_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, long first, long count, bool framed,
                               uint8_t* d_out, size_t out_cap, uint64_t* out_bits, uint32_t* block_crcs, long crc_cap,
-                              long* total_blocks, cjs_stats* st) {
+                              long* total_blocks, cjs_stats* st, EncRowsWant* want) {
   if (!c || level != c->level) return CJS_E_INVALID_ARG;
   if (n > c->max_input) return CJS_E_INVALID_ARG;
   if (((uintptr_t)d_out & 3) != 0) return CJS_E_INVALID_ARG;
@@ -187,16 +187,18 @@ static int compress_core_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int lev
     if ((long)nb > crc_cap) return CJS_E_OUTPUT_TOO_SMALL;
     CJS_HIP_TRY(hipMemcpyAsync(block_crcs, c->rle.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
   }
+  if (want) CJS_TRY(enc_rows_enqueue(c, d_in, n, f, cnt, want->lines));      // (behind the packing: the rows come down with its scalars)
   CJS_TRY(pack_finish(c, out_bits));
+  if (want) enc_rows_collect(c, cnt, *want);
   if (t.stages) st->ms_pack = c->timer.stop();
   t.end(cnt, n, *out_bits);
   return 0;
 }
-static int compress_core(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, long first, long count, bool framed,
-                         uint8_t* d_out, size_t out_cap, uint64_t* out_bits, uint32_t* block_crcs, long crc_cap,
-                         long* total_blocks, cjs_stats* st) {
+int cjs::compress_core(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, long first, long count, bool framed,
+                       uint8_t* d_out, size_t out_cap, uint64_t* out_bits, uint32_t* block_crcs, long crc_cap,
+                       long* total_blocks, cjs_stats* st, EncRowsWant* want) {
   CJS_GUARD_BEGIN
-  return drain_on_error(c, compress_core_impl(c, d_in, n, level, first, count, framed, d_out, out_cap, out_bits, block_crcs, crc_cap, total_blocks, st));
+  return drain_on_error(c, compress_core_impl(c, d_in, n, level, first, count, framed, d_out, out_cap, out_bits, block_crcs, crc_cap, total_blocks, st, want));
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
@@ -206,6 +208,25 @@ extern "C" int cjs_bzip2_compress_device(cjs_ctx* c, const uint8_t* d_in, size_t
   CJS_TRY(compress_core(c, d_in, n, level, 0, -1, true, d_out, out_cap, &bits, nullptr, 0, nullptr, stats));
   *out_n = (size_t)((bits + 7) / 8);
   return 0;
+}
+
+extern "C" int cjs_bzip2_compress_device_indexed(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, uint8_t* d_out, size_t out_cap,
+                                                 size_t* out_n, cjs_bz_index** idx, cjs_bz_lines** lines, cjs_stats* stats) {
+  if (idx) *idx = nullptr;
+  if (lines) *lines = nullptr;
+  if (!idx || !out_n) return CJS_E_INVALID_ARG;
+  CJS_GUARD_BEGIN
+  uint64_t bits = 0;
+  EncRowsWant want;
+  want.lines = lines != nullptr;
+  CJS_TRY(compress_core(c, d_in, n, level, 0, -1, true, d_out, out_cap, &bits, nullptr, 0, nullptr, stats, &want));
+  std::vector<cjs_bz_index_entry> entries; std::vector<uint32_t> newlines;
+  const uint64_t end_bit = enc_rows_append(entries, newlines, want.rows.data(), want.rows.size(), ENC_FIRST_BIT, level);
+  if (end_bit + 80 != bits) return CJS_E_HIP;            // (the packer's own count of the stream's bits)
+  CJS_TRY(enc_tables_make(entries, newlines, end_bit, idx, lines));
+  *out_n = (size_t)((bits + 7) / 8);
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
 extern "C" int cjs_bzip2_compress_device_range(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, long first_block, long count,
@@ -249,7 +270,8 @@ static void shard_range(uint32_t total, int rank, int world, uint32_t& first, ui
   first = std::min<uint64_t>((uint64_t)rank * share, total);
   count = std::min<uint32_t>(share, total - first);
 }
-int cjs::shard_blocks_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, int rank, int world, const void* d_shares, cjs_shard_meta* meta, cjs_stats* st) {
+int cjs::shard_blocks_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level, int rank, int world, const void* d_shares, cjs_shard_meta* meta, cjs_stats* st,
+                           EncRowsWant* want) {
   if (!c || !meta || level != c->level || world < 1 || rank < 0 || rank >= world || n > c->max_input || (world > 1 && !d_shares)) return CJS_E_INVALID_ARG;
   if (c->sh_state != 1 && d_shares) return CJS_E_INVALID_ARG;          // phase order
   CJS_HIP_TRY(hipSetDevice(c->device));
@@ -267,7 +289,9 @@ int cjs::shard_blocks_impl(cjs_ctx* c, const uint8_t* d_in, size_t n, int level,
   if (cnt && n && c->side) CJS_HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
   hipLaunchKernelGGL(shard_meta_kernel, dim3(1), dim3(1), 0, s, c->huff.b.bitlen, c->rle.block_crc, f, cnt, c->huff.scalars + 4);
   CJS_HIP_TRY(hipMemcpyAsync(c->h_scalars + 4, c->huff.scalars + 4, 16, hipMemcpyDeviceToHost, s));
+  if (want) CJS_TRY(enc_rows_enqueue(c, d_in, n, f, cnt, want->lines));
   CJS_HIP_TRY(hipStreamSynchronize(s));
+  if (want) enc_rows_collect(c, cnt, *want);
   meta->bits = c->h_scalars[4]; meta->crc_fold = (uint32_t)c->h_scalars[5];
   meta->total_blocks = nb; meta->first_block = f; meta->blocks = cnt;
   c->sh_nb = nb; c->sh_first = f; c->sh_cnt = cnt; c->sh_state = 2;

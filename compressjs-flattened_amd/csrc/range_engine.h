@@ -4,6 +4,7 @@
 //   range.hip     the slice gather of the range reads
 //   search.hip    the pattern scan: count, scan and emit over the tiles of a batch's segments, a carry between batches
 //   lines.hip     the newline count per block, select and rank for the line table's questions
+//                 (its newline test, ln_nl4, stands here: the compressor's block rows, enc_index.hip, count with it too)
 //   compare.hip   count, scan and emit over the tiles of the batch's runs intersected with the other side's
 // What they share stands here: the device helpers of a tile (its segment, its span of bounded aligned vectors, the 16-byte funnel,
 // the byte tests over 16 bytes, the scan of the tile counts) and, on the host, the verdicts of a call, the check of a stream
@@ -70,6 +71,15 @@ __device__ __forceinline__ uint32_t rg_mask16(uint4 x) {
   auto nib = [](uint32_t z) { return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u); };
   return nib(test4(x.x)) | (nib(test4(x.y)) << 4) | (nib(test4(x.z)) << 8) | (nib(test4(x.w)) << 12);
 }
+
+// bit 7 of every byte of w that is 0x0A, nothing else: the exact zero-byte test (the borrow form flags a 0x0B behind a 0x0A too)
+__device__ __forceinline__ uint32_t ln_nl4(uint32_t w) {
+  const uint32_t v = w ^ 0x0A0A0A0Au, t = (v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+  return ~(t | v | 0x7F7F7F7Fu);
+}
+// the newlines of 16 bytes: their number, and bit i = byte i is one
+__device__ __forceinline__ uint32_t ln_count16(uint4 x) { return rg_count16<ln_nl4>(x); }
+__device__ __forceinline__ uint32_t ln_mask16(uint4 x) { return rg_mask16<ln_nl4>(x); }
 
 // One workgroup of 256: cnt[0 .. nt) -> their exclusive prefix sums; returns the total.  also(i) runs for every i < nt in front of
 // its element's step.  sm: four words of LDS.

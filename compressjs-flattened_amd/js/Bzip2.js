@@ -48,8 +48,9 @@ function writeTo(outStream, piece) {
   for (var i = 0; i < piece.length; i++) { outStream.writeByte(piece[i]); }
 }
 // compressFile with a stream object on either side: the input is fed to the streaming encoder piece by piece and the output is
-// drained as it appears; neither the whole input nor (with an output stream) the whole result is ever held.
-function compressPiecewise(inStream, inIsStream, outStream, outIsStream, level) {
+// drained as it appears; neither the whole input nor (with an output stream) the whole result is ever held.  tables (optional,
+// compressFileIndexed): {lines}; the encoder keeps the stream's block index (and line table), left in tables.index / .lineIndex.
+function compressPiecewise(inStream, inIsStream, outStream, outIsStream, level, tables) {
   var a = common.addon(), enc = null, pieces = [], total = 0;
   function drain() {
     while (a.bzip2EncPending(enc) > 0) {
@@ -58,7 +59,7 @@ function compressPiecewise(inStream, inIsStream, outStream, outIsStream, level) 
     }
   }
   try {
-    enc = a.bzip2EncCreate(level, 0);
+    enc = tables ? a.bzip2EncCreate(level, 0, tables.lines ? 12 : 4) : a.bzip2EncCreate(level, 0);      // CJS_FLAG_ENC_INDEX | _LINES
     if (inIsStream) {
       var buf = new Uint8Array(IN_PIECE), n;
       while ((n = fillFrom(inStream, buf)) > 0) { a.bzip2EncWrite(enc, buf.subarray(0, n)); drain(); }
@@ -68,6 +69,7 @@ function compressPiecewise(inStream, inIsStream, outStream, outIsStream, level) 
     }
     a.bzip2EncFinish(enc);
     drain();
+    if (tables) { var t = a.bzip2EncIndex(enc, !!tables.lines); tables.index = t.index; tables.lineIndex = t.lineIndex; }
   } catch (e) { rethrow(e); } finally { if (enc) { a.bzip2EncDestroy(enc); } }
   if (outIsStream) {
     if (outStream.flush) { outStream.flush(); }
@@ -131,6 +133,25 @@ Bzip2.compressFile = function (inStream, outStream, props) {
   var result;
   try { result = common.addon().bzip2Compress(input.bytes, level); } catch (e) { rethrow(e); }
   return common.deliver(result, outStream);
+};
+// compressFile that also hands out the tables of its stream (cjs_bzip2_compress_indexed, cjs_bzip2_enc_index): returns {output:
+// what compressFile returns, index: what buildIndex(output) returns, lineIndex: what buildLineIndex(output, index) returns, or
+// null with opts.lines === false}, without the table pass and the full decode those two take.  With a stream object on either
+// side the streaming encoder keeps the tables (36 bytes per block) while the stream passes through.  opts: {lines = true}.
+Bzip2.compressFileIndexed = function (inStream, outStream, props, opts) {
+  var level = 9, lines = !(opts && opts.lines === false);
+  if (typeof props === 'number') { level = props; }
+  if (level < 1 || level > 9) { throw new Error('Invalid block size multiplier'); }
+  var inIsStream = isStream(inStream, 'readByte'), outIsStream = isStream(outStream, 'writeByte');
+  if (inIsStream || outIsStream) {
+    var tables = { lines: lines, index: null, lineIndex: null };
+    var output = compressPiecewise(inStream, inIsStream, outStream, outIsStream, level, tables);
+    return { output: output, index: tables.index, lineIndex: tables.lineIndex };
+  }
+  var input = common.coerceInput(inStream);
+  var r;
+  try { r = common.addon().bzip2CompressIndexed(input.bytes, level, lines); } catch (e) { rethrow(e); }
+  return { output: common.deliver(r.data, outStream), index: r.index, lineIndex: r.lineIndex };
 };
 // Bzip2.compressFile over a batch: one stream per input, in input order, all inputs in one pass per stage on the GPU
 Bzip2.compressFiles = function (inStreams, props) {

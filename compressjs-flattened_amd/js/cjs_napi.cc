@@ -50,6 +50,8 @@ struct Api {
   size_t (*enc_pending)(const cjs_bz_enc*) = nullptr;
   int (*enc_read)(cjs_bz_enc*, uint8_t*, size_t, size_t*) = nullptr;
   void (*enc_destroy)(cjs_bz_enc*) = nullptr;
+  int (*enc_index)(cjs_bz_enc*, cjs_bz_index**, cjs_bz_lines**) = nullptr;
+  int (*compress_indexed)(const uint8_t*, size_t, int, uint8_t**, size_t*, cjs_bz_index**, cjs_bz_lines**, const cjs_opts*) = nullptr;
   int (*dec_create)(cjs_bz_dec**, int, size_t, size_t, const cjs_opts*) = nullptr;
   int (*dec_write)(cjs_bz_dec*, const uint8_t*, size_t, size_t*) = nullptr;
   int (*dec_finish)(cjs_bz_dec*) = nullptr;
@@ -91,6 +93,7 @@ bool load_api() {
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
+  SYM(enc_index, "cjs_bzip2_enc_index") SYM(compress_indexed, "cjs_bzip2_compress_indexed")
   SYM(dec_create, "cjs_bzip2_dec_create") SYM(dec_write, "cjs_bzip2_dec_write") SYM(dec_finish, "cjs_bzip2_dec_finish")
   SYM(dec_read, "cjs_bzip2_dec_read") SYM(dec_done, "cjs_bzip2_dec_done") SYM(dec_destroy, "cjs_bzip2_dec_destroy")
   SYM(free_, "cjs_free") SYM(strerror_, "cjs_strerror") SYM(detail_, "cjs_last_error_detail") SYM(device_count, "cjs_device_count") SYM(version, "cjs_version") SYM(trim, "cjs_trim")
@@ -635,7 +638,49 @@ napi_value bzip2_decompress_batch(napi_env env, napi_callback_info info) {
   return res;
 }
 
-// ---- streaming encoder (cjs_bzip2_enc_*): bzip2EncCreate(level, chunkBytes) -> handle; bzip2EncWrite(handle, bytes);
+// The tables an indexed compress call made, in the serialised forms bzip2BuildIndex / bzip2BuildLineIndex return, set as `index`
+// and `lineIndex` (null without a line table) of obj; both objects are destroyed here.  False: an exception is pending.
+bool set_tables(napi_env env, napi_value obj, cjs_bz_index* ix, cjs_bz_lines* lt) {
+  uint8_t *raw = nullptr, *lraw = nullptr; size_t raw_n = 0, lraw_n = 0;
+  int rc = api.index_save(ix, &raw, &raw_n);
+  if (!rc && lt) rc = api.lines_save(lt, &lraw, &lraw_n);
+  api.index_destroy(ix);
+  if (lt) api.lines_destroy(lt);
+  if (rc != 0) { api.free_(raw); api.free_(lraw); throw_code(env, rc); return false; }
+  napi_value nul;
+  napi_get_null(env, &nul);
+  napi_set_named_property(env, obj, "index", wrap_result(env, raw, raw_n));
+  napi_set_named_property(env, obj, "lineIndex", lt ? wrap_result(env, lraw, lraw_n) : nul);
+  return true;
+}
+
+// bzip2CompressIndexed(input, level, wantLines) -> { data, index, lineIndex }: the stream of bzip2Compress and the tables of
+// exactly that stream (Bzip2.compressFileIndexed)
+napi_value bzip2_compress_indexed(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* p = nullptr; size_t n = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &p, &n)) { napi_throw_type_error(env, nullptr, "expected a Uint8Array or Buffer"); return nullptr; }
+  int32_t level = 9;
+  if (argc >= 2) napi_get_value_int32(env, argv[1], &level);
+  bool want_lines = true;
+  if (argc >= 3) napi_get_value_bool(env, argv[2], &want_lines);
+  static const uint8_t dummy = 0;
+  uint8_t* out = nullptr; size_t out_n = 0;
+  cjs_bz_index* ix = nullptr; cjs_bz_lines* lt = nullptr;
+  const int rc = api.compress_indexed(p ? p : &dummy, n, level, &out, &out_n, &ix, want_lines ? &lt : nullptr, nullptr);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value res;
+  napi_create_object(env, &res);
+  napi_set_named_property(env, res, "data", wrap_result(env, out, out_n));
+  if (!set_tables(env, res, ix, lt)) return nullptr;
+  return res;
+}
+
+// ---- streaming encoder (cjs_bzip2_enc_*): bzip2EncCreate(level, chunkBytes[, flags]) -> handle (flags: cjs_opts.flags, 4 = keep
+// the index of the stream, 8 = and its line table); bzip2EncIndex(handle, wantLines) -> { index, lineIndex } once finished;
+// bzip2EncWrite(handle, bytes);
 // bzip2EncFinish(handle); bzip2EncPending(handle) -> number; bzip2EncRead(handle, maxBytes) -> Uint8Array (at most maxBytes of
 // what is pending, never blocks); bzip2EncDestroy(handle).  The handle is an external whose finalizer destroys the encoder if
 // bzip2EncDestroy has not.
@@ -657,13 +702,16 @@ EncHandle* enc_arg(napi_env env, napi_callback_info info, size_t want, napi_valu
 }
 napi_value enc_create(napi_env env, napi_callback_info info) {
   if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
-  size_t argc = 2; napi_value argv[2];
+  size_t argc = 3; napi_value argv[3];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  int32_t level = 9; double chunk = 0;
+  int32_t level = 9; double chunk = 0; uint32_t flags = 0;
   if (argc >= 1) napi_get_value_int32(env, argv[0], &level);
   if (argc >= 2) napi_get_value_double(env, argv[1], &chunk);
+  if (argc >= 3) napi_get_value_uint32(env, argv[2], &flags);
+  cjs_opts opts; memset(&opts, 0, sizeof opts);
+  opts.struct_size = sizeof opts; opts.device = -1; opts.flags = flags;
   EncHandle* h = new EncHandle();
-  const int rc = api.enc_create(&h->e, level, chunk > 0 ? (size_t)chunk : 0, nullptr);
+  const int rc = api.enc_create(&h->e, level, chunk > 0 ? (size_t)chunk : 0, flags ? &opts : nullptr);
   if (rc != 0) { delete h; return throw_code(env, rc); }
   napi_value v;
   if (napi_create_external(env, h, finalize_enc, nullptr, &v) != napi_ok) { api.enc_destroy(h->e); delete h; napi_throw_error(env, nullptr, "cannot create the encoder handle"); return nullptr; }
@@ -686,6 +734,20 @@ napi_value enc_finish(napi_env env, napi_callback_info info) {
   const int rc = api.enc_finish(h->e);
   if (rc != 0) return throw_code(env, rc);
   napi_value v; napi_get_undefined(env, &v); return v;
+}
+napi_value enc_index(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  EncHandle* h = enc_arg(env, info, 2, argv);
+  if (!h) return nullptr;
+  bool want_lines = false;
+  napi_get_value_bool(env, argv[1], &want_lines);
+  cjs_bz_index* ix = nullptr; cjs_bz_lines* lt = nullptr;
+  const int rc = api.enc_index(h->e, &ix, want_lines ? &lt : nullptr);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value res;
+  napi_create_object(env, &res);
+  if (!set_tables(env, res, ix, lt)) return nullptr;
+  return res;
 }
 napi_value enc_pending(napi_env env, napi_callback_info info) {
   napi_value argv[1];
@@ -836,6 +898,8 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2Compare", nullptr, bzip2_compare, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2BuildLineIndex", nullptr, bzip2_build_line_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2CompressIndexed", nullptr, bzip2_compress_indexed, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2EncIndex", nullptr, enc_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncWrite", nullptr, enc_write, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncFinish", nullptr, enc_finish, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -4,6 +4,8 @@
  * (NPM/bin/compressjs:7-25 options, :31-58 checks and messages, :60-120 fd streams, :143-175 dispatch):
  *   cli.js -d|-z [-t bzip2|bwtc] [-1..-9] [-b <bits>] [infile] [outfile]
  *   cli.js --recover|--repair -t bzip2 [infile] [outfile]
+ *   cli.js -z -t bzip2 --index FILE [--line-index FILE] ...: once the stream is complete, FILE gets its block index (and its line
+ *   table) in the serialised forms of Bzip2.buildIndex / buildLineIndex, kept by the encoder while the stream passed through.
  * --recover writes the decoded bytes of the intact blocks of damaged .bz2 data, --repair a .bz2 stream made of those blocks (what
  * bzip2recover is for; Bzip2.recoverFile), each with one line "recovered K of M blocks (N bytes)" on stderr.
  * infile omitted: stdin; outfile omitted: stdout; neither -d nor -z: compress; default level 7 (:57).
@@ -24,6 +26,8 @@ for (var i = 0; i < argv.length; i++) {
   else if (a === '-z' || a === '--compress') { opt.compress = true; }
   else if (a === '-b' || a === '--block') { opt.block = +argv[++i]; }
   else if (a === '-t') { opt.type = argv[++i]; }
+  else if (a === '--index') { opt.index = argv[++i]; if (!opt.index) { fail('--index needs a file name'); } }
+  else if (a === '--line-index') { opt.lineIndex = argv[++i]; if (!opt.lineIndex) { fail('--line-index needs a file name'); } }
   else if (a === '--recover' || a === '--repair') {
     if (opt.recover && opt.recover !== a) { fail("Can't specify both " + opt.recover + ' and ' + a); }
     opt.recover = a;
@@ -32,7 +36,7 @@ for (var i = 0; i < argv.length; i++) {
     if (level) { fail("Can't specify both -" + level + ' and ' + a); }
     level = +a.slice(1);
   } else if (a === '-h' || a === '--help') {
-    console.log('Usage: cli.js -d|-z [-t bzip2|bwtc] [-1..-9] [-b <bits>] [infile] [outfile]\n' +
+    console.log('Usage: cli.js -d|-z [-t bzip2|bwtc] [-1..-9] [-b <bits>] [--index <file> [--line-index <file>]] [infile] [outfile]\n' +
                 '       cli.js --recover|--repair -t bzip2 [infile] [outfile]\n' +
                 '  If <infile> is omitted, reads from stdin.\n  If <outfile> is omitted, writes to stdout.');
     process.exit(0);
@@ -51,6 +55,12 @@ var type = String(opt.type || '').toLowerCase();
 if (type === 'bzip') { type = 'bzip2'; }
 if (!fronts[type]) {
   fail(opt.type ? 'Unknown compressor: ' + opt.type + ' (this build has bzip2 and bwtc)' : 'Select the compressor with -t bzip2 or -t bwtc');
+}
+if (opt.index || opt.lineIndex) {
+  if (opt.recover) { fail('--index and --line-index cannot be used with ' + opt.recover); }
+  if (opt.decompress) { fail('--index and --line-index can only be used with compression'); }
+  if (type !== 'bzip2') { fail('--index and --line-index need -t bzip2'); }
+  if (!opt.index) { fail('--line-index needs --index'); }
 }
 
 function readAll(fd) {
@@ -101,7 +111,13 @@ var inFd = opt.files.length > 0 ? fs.openSync(opt.files[0], 'r') : 0;
 var outFd = opt.files.length > 1 ? fs.openSync(opt.files[1], 'w') : 1;
 if (opt.compress && type === 'bzip2') {
   // streaming: the input is read in pieces and the output written as it appears, file and pipe alike -- no buffer of the whole file
-  try { fronts.bzip2.compressFile(fdInput(inFd), fdOutput(outFd), level); } catch (e) { fail(String(e && e.message ? e.message : e)); }
+  try {
+    if (opt.index) {
+      var made = fronts.bzip2.compressFileIndexed(fdInput(inFd), fdOutput(outFd), level, { lines: !!opt.lineIndex });
+      fs.writeFileSync(opt.index, made.index);
+      if (opt.lineIndex) { fs.writeFileSync(opt.lineIndex, made.lineIndex); }
+    } else { fronts.bzip2.compressFile(fdInput(inFd), fdOutput(outFd), level); }
+  } catch (e) { fail(String(e && e.message ? e.message : e)); }
   if (inFd !== 0) { fs.closeSync(inFd); }
   if (outFd !== 1) { fs.closeSync(outFd); }
   process.exit(0);

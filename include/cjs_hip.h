@@ -415,6 +415,29 @@ int cjs_bzip2_enc_finish(cjs_bz_enc *e);
 size_t cjs_bzip2_enc_pending(const cjs_bz_enc *e);
 int cjs_bzip2_enc_read(cjs_bz_enc *e, uint8_t *out, size_t cap, size_t *got);
 void cjs_bzip2_enc_destroy(cjs_bz_enc *e);
+/* Compress and hand out the tables of the stream: the indexed forms return, beside the stream, the cjs_bz_index of exactly that
+ * stream and, if asked, its cjs_bz_lines -- what cjs_bzip2_index_build and cjs_bzip2_lines_build give on the result, entry for
+ * entry, without the table pass and the full decode those two take: the compressor holds every field when it packs (a block's
+ * bits, CRC and input span; the newlines are one more read of the input, which is in device memory then).  The stream is
+ * byte-identical to the plain call's; the plain calls are untouched.  The index is multistream = 0.  *idx / *lines are new objects
+ * (cjs_bzip2_index_destroy / cjs_bzip2_lines_destroy).  lines == NULL: no line table is made (and the input is not read again).
+ * idx == NULL: CJS_E_INVALID_ARG.  On any failure *idx and *lines are NULL (and *out of the host form), nothing leaks.
+ * cjs_bzip2_compress_indexed: cjs_bzip2_compress' arguments, rules and modes (one device; opts->n_devices > 1; inputs above
+ * CJS_CHUNK_BYTES in waves): every shard hands its blocks' rows to the calling thread, which sets them at the shard's bit offset.
+ * cjs_bzip2_compress_device_indexed: cjs_bzip2_compress_device's arguments and rules; 16 bytes per block come down with the
+ * packer's scalars, in front of the one synchronisation the plain call makes.  The context keeps 16 bytes per block of device and
+ * pinned memory from its first indexed call on.
+ * Streaming: an encoder made with CJS_FLAG_ENC_INDEX (and CJS_FLAG_ENC_LINES) in opts->flags keeps 36 bytes of host memory per
+ * block written -- the only thing that grows with the stream -- and cjs_bzip2_enc_index hands the tables out once _finish has
+ * returned 0, any number of times, whether or not the output has been read.  Before that, for an encoder made without the flag,
+ * for lines != NULL without CJS_FLAG_ENC_LINES, and for NULL e or idx: CJS_E_INVALID_ARG (the encoder does not stay failed for
+ * it); a failed encoder returns its code.  No input at all: an index of no entries, stream_bytes 14.
+ * Not covered: cjs_bzip2_compress_batch[_device], the cjs_bzip2_shard_* phases, the decoder, BWTC. */
+#define CJS_FLAG_ENC_INDEX 4u   /* cjs_bzip2_enc_create: keep the index of the stream being written */
+#define CJS_FLAG_ENC_LINES 8u   /* ... and its line table (implies CJS_FLAG_ENC_INDEX) */
+int cjs_bzip2_compress_indexed(const uint8_t *in, size_t n, int level, uint8_t **out, size_t *out_n, cjs_bz_index **idx,
+                               cjs_bz_lines **lines, const cjs_opts *opts);
+int cjs_bzip2_enc_index(cjs_bz_enc *e, cjs_bz_index **idx, cjs_bz_lines **lines);
 /* Streaming form of cjs_bzip2_decompress: the .bz2 stream is written in pieces of any size, the decoded bytes are read in pieces
  * of any size, and the bytes read, in order, are exactly what cjs_bzip2_decompress(all written bytes, multistream) returns; a
  * stream that fails fails with the same code and the same cjs_last_error_detail().  The device and host memory a decoder holds
@@ -486,7 +509,10 @@ void cjs_ctx_set_stage_times(cjs_ctx *ctx, int on);
  * Synchronous on return (the context stream has drained). */
 int cjs_bzip2_compress_device(cjs_ctx *ctx, const uint8_t *d_in, size_t n, int level,
                               uint8_t *d_out, size_t out_cap, size_t *out_n, cjs_stats *stats);
-/* Batch form of the above on a cjs_ctx_create_batch context: input k is d_in[in_off[k] .. in_off[k+1]) (in_off: HOST array of
+/* ... and the block index (and, lines != NULL, the line table) of that stream: see cjs_bzip2_compress_indexed. */
+int cjs_bzip2_compress_device_indexed(cjs_ctx *ctx, const uint8_t *d_in, size_t n, int level, uint8_t *d_out, size_t out_cap,
+                                      size_t *out_n, cjs_bz_index **idx, cjs_bz_lines **lines, cjs_stats *stats);
+/* Batch form of cjs_bzip2_compress_device on a cjs_ctx_create_batch context: input k is d_in[in_off[k] .. in_off[k+1]) (in_off: HOST array of
  * count + 1 ascending offsets).  Stream k is left at d_out + out_off[k], out_len[k] bytes (4-byte-aligned offsets, out_off /
  * out_len host arrays of `count` entries).  The streams are assembled in the context's staging buffer and reach d_out in one copy
  * once all sizes are known: when the last stream ends past out_cap (max of out_off[k] + out_len[k]) the call returns
