@@ -11,6 +11,7 @@
 //     header and trailer with the stream CRC folded over the input's blocks
 //   empty inputs: the 14-byte empty stream
 // The streams are assembled in a staging buffer of the context; they reach the caller's buffer only once every size is known.
+#include "crc.h"
 #include "ctx.h"
 #include "host.h"
 #include "prims.hpp"

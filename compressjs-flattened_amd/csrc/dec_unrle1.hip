@@ -2,7 +2,7 @@
 // for phase B, and phase C of the engine (dec_engine.h): expansion to the final offsets, block CRCs, D2H.
 #include "dec_engine.h"
 #include "prims.hpp"
-#include "rle1.h"
+#include "crc.h"
 
 using namespace cjs;
 
@@ -329,7 +329,7 @@ static CBatch c_batch(const DecJob& J, const DecShare& S, size_t b0, size_t b1) 
   for (uint32_t k = 0; k < B.nb; k++) {
     B.blk[k].off = B.blk[k].woff = (uint32_t)(S.ebase[b0 + k - S.c0] - B.e0);
     B.blk[k].out_off = J.out_off[b0 + k] - B.o0;                  // inside the batch's output buffer
-    B.need_segs = std::max(B.need_segs, (uint32_t)((B.blk[k].out_len + 16383) / 16384 + 1));
+    B.need_segs = std::max(B.need_segs, (uint32_t)crc_segs_for(B.blk[k].out_len));
   }
   return B;
 }

@@ -21,7 +21,7 @@
 //   5. RLE1 expansion    (:1738-1753) parsed in parallel: a count byte follows 4 equal literals; inside a
 //                        stretch of equal bytes the literal/count phase has period 5 and the only carried
 //                        state (does the stretch start with a count byte?) is a 2-state function scan;
-//   6. CRC check         per block over the output bytes (rle1.hip's slice + GF(2) combine), :1756-1761.
+//   6. CRC check         per block over the output bytes (crc.hip's slice + GF(2) combine), :1756-1761.
 // Recovery of damaged data (dec_recover.hip: cjs_bzip2_recover, no reference equivalent: the job of bzip2recover) is 1, 2 and 4-6
 // over EVERY decodable candidate, with step 3 replaced by a selection of the intact, non-overlapping ones; an indexed range read
 // (range.hip) is 2 and 4-6 over the blocks its index names.

@@ -1,6 +1,9 @@
-// rle1.h — stage 0 (RLE1 + block boundaries + CRC) workspace and entry point.
+// rle1.h — stage 0 (RLE1 + block boundaries + CRC) workspace and entry points: rle1.hip (boundaries), rle1_bytes.hip (bytes, CRCs),
+// rle1_batch.hip (batches of inputs).  The rules of the arithmetic: rle1_rules.h; the CRC of byte ranges: crc.h.
 #pragma once
 #include "cjs_internal.h"
+#include "crc32_bz.h"
+#include "rle1_rules.h"
 
 namespace cjs {
 
@@ -22,13 +25,13 @@ struct Rle1Work {
   uint8_t* dmod = nullptr;       // [tiles][16] chunk phase of each subtile's first byte
   RleBlock* blocks = nullptr;
   uint32_t *block_len = nullptr, *block_crc = nullptr, *nblocks = nullptr, *seg_crc = nullptr;
-  static size_t max_blocks_for(size_t max_in, uint32_t cap) { return max_in / ((size_t)cap * 4 / 5) + 2; }
-  static size_t max_segs_for(uint32_t cap) { return ((size_t)cap * 51 + 16383) / 16384 + 1; }
-  // multi-GPU jobs: every rank makes the tile tables of `tiles_per_rank` consecutive 4 KiB tiles and the ranks exchange them.
-  // Layout of one share (tpr tiles): lb u64[tpr] | fb u64[tpr] | gt u64[tpr] | subpre u16[tpr][16] | dmod u8[tpr][16]
-  static uint32_t tiles_for(uint64_t n) { return (uint32_t)((n + 4095) / 4096); }
-  static uint32_t tiles_per_rank(uint64_t n, uint32_t world) { const uint32_t t = (tiles_for(n) + world - 1) / (world ? world : 1); return (t + 3u) & ~3u; }
-  __host__ __device__ static size_t share_bytes(uint32_t tpr) { return (size_t)72 * tpr; }
+  static size_t max_blocks_for(size_t max_in, uint32_t cap) { return cjs::max_blocks_for(max_in, cap); }
+  static size_t max_segs_for(uint32_t cap) { return crc_segs_for((size_t)cap * 51); }     // a block takes at most 51 input bytes per output byte (255 for 5)
+  // multi-GPU jobs: every rank makes the tile tables of `tiles_per_rank` consecutive 4 KiB tiles and the ranks exchange them
+  // (the layout of one share: tile_share() of rle1_rules.h)
+  static uint32_t tiles_for(uint64_t n) { return cjs::tiles_for(n); }
+  static uint32_t tiles_per_rank(uint64_t n, uint32_t world) { return cjs::tiles_per_rank(n, world); }
+  static size_t share_bytes(uint32_t tpr) { return tile_share(tpr).bytes; }
   // range_blocks = max number of blocks materialised / CRC'd per call (0 = all blocks of the stream)
   static size_t bytes_needed(size_t max_in, uint32_t cap, size_t range_blocks = 0);
   int carve(Arena& a, size_t max_in, uint32_t cap, size_t range_blocks = 0);
@@ -48,10 +51,6 @@ int rle1_batch_len(hipStream_t s, const uint8_t* d_in, const uint64_t* d_se, uin
 int rle1_batch_walk(hipStream_t s, const uint8_t* d_in, const uint64_t* d_se, const uint32_t* d_item, const uint32_t* d_tbase, uint32_t count,
                     uint32_t cap, RleBlock* d_blocks, uint32_t* d_nblk);
 int rle1_batch_materialize(hipStream_t s, const uint8_t* d_in, const RleBlock* d_blk, uint32_t nb, uint32_t stride, uint8_t* d_blocks);
-// CRC-32 (bzip2 form) of byte ranges [d_blocks[k].s, d_blocks[k].e) of d_data, k < min(count, *d_nblocks); d_seg_crc holds
-// count * max_segs words, max_segs >= (longest range) / 16 KiB + 2
-int crc_ranges(hipStream_t s, const uint8_t* d_data, const RleBlock* d_blocks, const uint32_t* d_nblocks, uint32_t count, uint32_t max_segs,
-               uint32_t* d_seg_crc, uint32_t* d_crc_out);
 int rle1_finish(hipStream_t s, Rle1Work& w, const uint8_t* d_in, uint64_t N, uint32_t first, uint32_t count, uint8_t* d_blocks,
                 hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr);
 

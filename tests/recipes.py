@@ -37,6 +37,25 @@ def xorshift_bytes(n, seed, mask=255, add=0):
     return out
 
 
+_rle_seams = None
+
+
+def rle_seam_inputs():
+    """{(L, E): input}: one run of L equal bytes that ends exactly at offset E, in xorshift noise (mask 63, add 32: the run's byte
+    0x7a differs from every neighbour), 300 bytes of noise behind it.  The run lengths sit around the chunk rule's steps (the
+    fourth byte, 255, 255 + 4, 2 * 255), the end offsets around the borders of a lane's 16 bytes, a 4 KiB tile and two tiles, so
+    every chunk phase that matters crosses a lane, subtile and tile border of the stage-0 kernels.  Built once, shared."""
+    global _rle_seams
+    if _rle_seams is None:
+        _rle_seams = {}
+        for E in (16, 4095, 4096, 4097, 8192):
+            for L in (3, 4, 5, 254, 255, 256, 258, 259, 510, 511):
+                if L <= E:
+                    _rle_seams[(L, E)] = np.concatenate([xorshift_bytes(E - L, 1000 * L + E, 63, 32), np.full(L, 0x7a, np.uint8),
+                                                         xorshift_bytes(300, 7 * L + E, 63, 32)])
+    return _rle_seams
+
+
 def build(recipe):
     kind = recipe["kind"]
     if kind == "file":

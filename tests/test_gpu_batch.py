@@ -108,6 +108,18 @@ def test_oracle_mixture(level, oracle, hip):
         assert rc == 0 and np.array_equal(o, single), "input %d differs from cjs_bzip2_compress" % k
 
 
+def test_run_seams_one_batch():
+    """The stage-0 seam inputs (recipes.rle_seam_inputs: one run of 3..511 bytes ending at a lane, tile or two-tile border) as ONE
+    batch: stream k is compressFile of input k -- the batch kernels' tile carry and their share of the chunk rule."""
+    pkg = _pkg()
+    cases = sorted(recipes.rle_seam_inputs().items())
+    assert len(cases) == 43
+    outs = pkg.Bzip2.compressFiles([d for _, d in cases], 1)
+    assert len(outs) == len(cases)
+    for ((L, E), d), o in zip(cases, outs):
+        assert np.array_equal(o, pkg.Bzip2.compressFile(d, None, 1)), "run of %d ending at %d" % (L, E)
+
+
 def test_scale_many_tiny_and_one_large(oracle, hip):
     pkg = _pkg()
     rng = np.random.default_rng(3)

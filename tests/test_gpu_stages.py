@@ -93,22 +93,40 @@ RLE_INPUTS = {
 }
 
 
+def _check_rle1(hip, oracle, data, level):
+    want = oracle.rle1_blocks(data, level)
+    rc, got = hip.stage_rle1(data, level)
+    assert rc == 0
+    assert len(got) == len(want), "level %d: %d blocks, want %d" % (level, len(got), len(want))
+    for k, ((gb, gcrc, gs), (wb, wcrc, ws, we)) in enumerate(zip(got, want)):
+        assert gs == ws, "level %d block %d start %d want %d" % (level, k, gs, ws)
+        assert gb.size == wb.size, "level %d block %d len %d want %d" % (level, k, gb.size, wb.size)
+        if not np.array_equal(gb, wb):
+            bad = np.nonzero(gb != wb)[0]
+            raise AssertionError("level %d block %d: %d bytes differ, first at %d" % (level, k, bad.size, bad[0]))
+        assert gcrc == wcrc, "level %d block %d crc %08x want %08x" % (level, k, gcrc, wcrc)
+
+
 @pytest.mark.parametrize("name", sorted(RLE_INPUTS))
 def test_rle1_stage(hip, oracle, name):
     recipe, levels = RLE_INPUTS[name]
     data = recipes.build(recipe)
     for level in levels:
-        want = oracle.rle1_blocks(data, level)
-        rc, got = hip.stage_rle1(data, level)
-        assert rc == 0
-        assert len(got) == len(want), "level %d: %d blocks, want %d" % (level, len(got), len(want))
-        for k, ((gb, gcrc, gs), (wb, wcrc, ws, we)) in enumerate(zip(got, want)):
-            assert gs == ws, "level %d block %d start %d want %d" % (level, k, gs, ws)
-            assert gb.size == wb.size, "level %d block %d len %d want %d" % (level, k, gb.size, wb.size)
-            if not np.array_equal(gb, wb):
-                bad = np.nonzero(gb != wb)[0]
-                raise AssertionError("level %d block %d: %d bytes differ, first at %d" % (level, k, bad.size, bad[0]))
-            assert gcrc == wcrc, "level %d block %d crc %08x want %08x" % (level, k, gcrc, wcrc)
+        _check_rle1(hip, oracle, data, level)
+
+
+@pytest.mark.parametrize("end", [16, 4095, 4096, 4097, 8192])
+def test_rle1_stage_run_seams(hip, oracle, end):
+    """One run of 3..511 bytes that ends at a lane, tile or two-tile border (recipes.rle_seam_inputs): the chunk rule, the
+    16-bytes-per-lane emission and the count byte whose run end comes from the next tile's table, in rle_tile_count and in both
+    paths of rle_materialize (tiles 0 and 1 are assembled in LDS, the last tile goes byte by byte)."""
+    cases = {L: d for (L, E), d in recipes.rle_seam_inputs().items() if E == end}
+    assert len(cases) == (3 if end == 16 else 10)
+    for L, data in sorted(cases.items()):
+        try:
+            _check_rle1(hip, oracle, data, 1)
+        except AssertionError as e:
+            raise AssertionError("run of %d ending at %d: %s" % (L, end, e))
 
 
 MTF_INPUTS = ["banana", "aaaa", "mary", "zeros_5000", "ab_10000", "range256", "random_multi", "random4sym", "textgen_multi", "textgen_900k", "sample3", "sample1"]
