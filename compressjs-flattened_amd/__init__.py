@@ -150,6 +150,9 @@ def load_library():
     U32, U64 = ctypes.c_uint32, ctypes.c_uint64
     L.cjs_bzip2_search.argtypes = [u8p, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
     L.cjs_bzip2_search_device.argtypes = [V, S, V, u8p, ctypes.POINTER(U32), U32, U32, U64, U64, ctypes.POINTER(Match), S, ctypes.POINTER(SearchInfo), V]
+    L.cjs_bzip2_search_regex.argtypes = L.cjs_bzip2_search.argtypes
+    L.cjs_bzip2_search_regex_device.argtypes = L.cjs_bzip2_search_device.argtypes
+    L.cjs_regex_check.argtypes = [u8p, ctypes.POINTER(U32), U32, U32, ctypes.POINTER(U32), ctypes.POINTER(U32)]
     cmp_tail = [U64, U64, ctypes.POINTER(Diff), S, ctypes.POINTER(CompareInfo), V]
     L.cjs_bzip2_compare.argtypes = [u8p, S, V, u8p, S, U64] + cmp_tail
     L.cjs_bzip2_compare_device.argtypes = [V, S, V, V, S, U64] + cmp_tail
@@ -821,9 +824,23 @@ class Bzip2Index:
         keep = data if data.size else np.zeros(1, dtype=np.uint8)
         return _search(lambda *a: L.cjs_bzip2_search(keep.ctypes.data_as(u8p), data.size, self._h, *a, None), patterns, off, length, nocase, limit)
 
-    def grep(self, data, patterns, before=0, after=0, **kw):
+    def search_regex(self, data, patterns, off=0, length=None, nocase=False, limit=None):
+        """search with patterns that are bounded regular expressions (cjs_bzip2_search_regex: the dialect and the 256-byte clamp
+        are described there): -> SearchResult whose matches are (off, pattern, length) triples, length the longest match there."""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        return _search(lambda *a: L.cjs_bzip2_search_regex(keep.ctypes.data_as(u8p), data.size, self._h, *a, None), patterns, off, length, nocase, limit, lengths=True)
+
+    def grep(self, data, patterns, before=0, after=0, regex=False, **kw):
         """search, then one read_ranges of [o - before, o + len(pattern) + after) per match: -> [(off, pattern, bytes)] (a
-        CjsError in place of the bytes of a context that touches a bad block)"""
+        CjsError in place of the bytes of a context that touches a bad block).  regex=True: search_regex, and the match's own
+        length in the pattern's place."""
+        if regex:
+            res = self.search_regex(data, patterns, **kw)
+            ranges = [(max(o - before, 0), min(o, before) + n + after) for o, j, n in res.matches]
+            ctx = self.read_ranges(data, ranges) if ranges else []
+            return [(o, j, c) for (o, j, n), c in zip(res.matches, ctx)]
         pats = _pattern_arrays(patterns)[0]
         res = self.search(data, patterns, **kw)
         ranges = [(max(o - before, 0), min(o, before) + len(pats[j]) + after) for o, j in res.matches]
@@ -886,18 +903,19 @@ class Bzip2Index:
             res[k] = r
         return res
 
-    def grep_lines(self, data, lines, patterns, **search_kw):
+    def grep_lines(self, data, lines, patterns, regex=False, **search_kw):
         """bzgrep -n: search, then number of the match offsets, then locate of each distinct line and its successor, then one
         read_ranges.  -> [(line_no, line_bytes, [(off, pattern), ...])] ascending, each line once (a match that spans lines
-        belongs to the line its first byte is in; a CjsError in place of the bytes of a line that touches a bad block)"""
-        res = self.search(data, patterns, **search_kw)
+        belongs to the line its first byte is in; a CjsError in place of the bytes of a line that touches a bad block).
+        regex=True is bzgrep -n -E: search_regex, the matches (off, pattern, length) triples."""
+        res = self.search_regex(data, patterns, **search_kw) if regex else self.search(data, patterns, **search_kw)
         if not res.matches:
             return []
-        numbers, st, _ = self.line_numbers(data, lines, [o for o, j in res.matches])
+        numbers, st, _ = self.line_numbers(data, lines, [m[0] for m in res.matches])
         by_line = {}
-        for (o, j), no, s in zip(res.matches, numbers.tolist(), st.tolist()):
+        for m, no, s in zip(res.matches, numbers.tolist(), st.tolist()):
             if not s:
-                by_line.setdefault(no, []).append((o, j))
+                by_line.setdefault(no, []).append(m)
         order = sorted(by_line)
         text = self.read_lines(data, lines, [(no, 1) for no in order])
         return [(no, t, by_line[no]) for no, t in zip(order, text)]
@@ -1018,8 +1036,9 @@ def _pattern_arrays(patterns):
     return pats, blob, np.cumsum([0] + [len(p) for p in pats]).astype(np.uint32)
 
 
-def _search(call, patterns, off, length, nocase, limit):
-    """call(pat, pat_off, npat, flags, off, len, found, cap, info) -> rc; limit=None: the count query, then all"""
+def _search(call, patterns, off, length, nocase, limit, lengths=False):
+    """call(pat, pat_off, npat, flags, off, len, found, cap, info) -> rc; limit=None: the count query, then all; lengths: the
+    matches are (off, pattern, length) triples (the regex search)"""
     L = load_library()
     pats, blob, p_off = _pattern_arrays(patterns)
     ln = 2 ** 64 - 1 if length is None else int(length)
@@ -1032,7 +1051,8 @@ def _search(call, patterns, off, length, nocase, limit):
         detail = L.cjs_last_error_detail().decode() if info.n_bad_blocks else ""
         got = min(cap, info.n_matches)
         raw = np.frombuffer(found, dtype=[("off", "<u8"), ("pattern", "<u4"), ("reserved", "<u4")], count=got)
-        return SearchResult(list(zip(raw["off"].tolist(), raw["pattern"].tolist())), info, detail)
+        cols = (raw["off"].tolist(), raw["pattern"].tolist()) + ((raw["reserved"].tolist(),) if lengths else ())
+        return SearchResult(list(zip(*cols)), info, detail)
 
     if limit is not None:
         return once(int(limit))
@@ -1046,6 +1066,23 @@ def search_device(d_in_ptr, n, index, patterns, off=0, length=None, nocase=False
     L = load_library()
     opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
     return _search(lambda *a: L.cjs_bzip2_search_device(d_in_ptr, n, index._h, *a, ctypes.byref(opts)), patterns, off, length, nocase, limit)
+
+
+def search_regex_device(d_in_ptr, n, index, patterns, off=0, length=None, nocase=False, limit=None, device=-1):
+    """Bzip2Index.search_regex with the stream in GPU memory (cjs_bzip2_search_regex_device).  The result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _search(lambda *a: L.cjs_bzip2_search_regex_device(d_in_ptr, n, index._h, *a, ctypes.byref(opts)), patterns, off, length, nocase, limit, lengths=True)
+
+
+def regex_check(patterns, nocase=False):
+    """Compile `patterns` as Bzip2Index.search_regex would, without a device (cjs_regex_check): -> [(states, max_len)] per pattern;
+    a CjsError with the detail text ("pattern J, byte P: ...") for a pattern the dialect refuses."""
+    L = load_library()
+    pats, blob, p_off = _pattern_arrays(patterns)
+    states, max_len = (ctypes.c_uint32 * max(len(pats), 1))(), (ctypes.c_uint32 * max(len(pats), 1))()
+    _check(L.cjs_regex_check(blob.ctypes.data_as(u8p), p_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(pats), SEARCH_NOCASE if nocase else 0, states, max_len))
+    return list(zip(list(states), list(max_len)))[:len(pats)]
 
 
 class CompareResult:

@@ -254,6 +254,41 @@ Bzip2.search = function (inStream, index, patterns, opts) {
   for (var k = 0; k < r.matches.length; k += 2) { matches.push([r.matches[k], r.matches[k + 1]]); }
   return { matches: matches, total: r.total, badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, detail: r.detail };
 };
+// Regex search (cjs_bzip2_search_regex): Bzip2.search with patterns that are bounded regular expressions (strings, Buffers or
+// Uint8Arrays of 1..1024 bytes; the dialect and the clamp at 256 bytes are described in cjs_hip.h).  Same opts and result, the
+// matches [[offset, pattern, length], ...], length the longest match at that offset.  A pattern the dialect refuses throws an Error
+// whose message ends in the library's detail ("pattern J, byte P: ...") and whose errorCode is the library's code.
+function patternBytes(patterns) {
+  var parts = [], lens = new Float64Array(patterns.length);
+  for (var i = 0; i < patterns.length; i++) {
+    var b = typeof patterns[i] === 'string' ? Buffer.from(patterns[i], 'utf8') : Buffer.from(common.coerceInput(patterns[i]).bytes);
+    parts.push(b); lens[i] = b.length;
+  }
+  return { bytes: new Uint8Array(Buffer.concat(parts)), lens: lens };
+}
+function rethrowWithDetail(e) {
+  if (e && typeof e.cjsCode === 'number' && !Messages[e.cjsCode] && e.cjsDetail) {
+    var g = new Error(e.message + ': ' + e.cjsDetail); g.errorCode = e.cjsCode; throw g;
+  }
+  rethrow(e);
+}
+Bzip2.searchRegex = function (inStream, index, patterns, opts) {
+  var input = common.coerceInput(inStream), o = opts || {}, p = patternBytes(patterns), r;
+  try {
+    r = common.addon().bzip2SearchRegex(input.bytes, index, p.bytes, p.lens, o.nocase ? 1 : 0, o.offset === undefined ? 0 : o.offset,
+                                        o.length === undefined || o.length === null ? -1 : o.length, o.limit === undefined || o.limit === null ? -1 : o.limit);
+  } catch (e) { rethrowWithDetail(e); }
+  var matches = [];
+  for (var k = 0; k < r.matches.length; k += 3) { matches.push([r.matches[k], r.matches[k + 1], r.matches[k + 2]]); }
+  return { matches: matches, total: r.total, badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, detail: r.detail };
+};
+// Compile only, without a device (cjs_regex_check): [{states, maxLen}, ...] per pattern; opts: {nocase = false}.
+Bzip2.regexCheck = function (patterns, opts) {
+  var p = patternBytes(patterns), r, out = [];
+  try { r = common.addon().regexCheck(p.bytes, p.lens, opts && opts.nocase ? 1 : 0); } catch (e) { rethrowWithDetail(e); }
+  for (var k = 0; k < r.length; k += 2) { out.push({ states: r[k], maxLen: r[k + 1] }); }
+  return out;
+};
 // Compare (cjs_bzip2_compare, cjs_bzip2_compare_streams): `cmp` / `bzcmp` on the GPU; only the differing bytes come back.
 // compare: byte k of `other` (plain bytes) against decoded byte otherOffset + k, inside [offset, offset + length).  compareStreams:
 // the decoded bytes of stream A against those of stream B.  opts: {offset = 0, length = to the end, otherOffset = 0, limit = 64

@@ -33,6 +33,9 @@ struct Api {
                      const cjs_opts*) = nullptr;
   int (*search)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint64_t, uint64_t, cjs_bz_match*, size_t,
                 cjs_bz_search_info*, const cjs_opts*) = nullptr;
+  int (*search_regex)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint64_t, uint64_t, cjs_bz_match*, size_t,
+                      cjs_bz_search_info*, const cjs_opts*) = nullptr;
+  int (*regex_check)(const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t*) = nullptr;
   int (*index_info)(const cjs_bz_index*, uint64_t*, uint64_t*, uint64_t*, int*) = nullptr;
   int (*compare)(const uint8_t*, size_t, const cjs_bz_index*, const uint8_t*, size_t, uint64_t, uint64_t, uint64_t, cjs_bz_diff*, size_t, cjs_bz_cmp_info*,
                  const cjs_opts*) = nullptr;
@@ -88,6 +91,7 @@ bool load_api() {
   SYM(bzip2_recover, "cjs_bzip2_recover")
   SYM(index_build, "cjs_bzip2_index_build") SYM(index_save, "cjs_bzip2_index_save") SYM(index_load, "cjs_bzip2_index_load")
   SYM(index_destroy, "cjs_bzip2_index_destroy") SYM(read_ranges, "cjs_bzip2_read_ranges") SYM(search, "cjs_bzip2_search")
+  SYM(search_regex, "cjs_bzip2_search_regex") SYM(regex_check, "cjs_regex_check")
   SYM(index_info, "cjs_bzip2_index_info") SYM(compare, "cjs_bzip2_compare") SYM(compare_streams, "cjs_bzip2_compare_streams")
   SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
@@ -291,7 +295,8 @@ napi_value bzip2_read_ranges(napi_env env, napi_callback_info info) {
 // bzip2Search(input, index, patterns, lengths, flags, offset, length, limit) -> { matches: Float64Array, total, badBlocks,
 // firstBadBlock, detail }   (Bzip2.search).  patterns: the patterns' bytes back to back; lengths: Float64Array, one per pattern;
 // length < 0: to the end; limit < 0: every match (a count query first).  matches holds (offset, pattern) pairs.
-napi_value bzip2_search(napi_env env, napi_callback_info info) {
+// bzip2SearchRegex: the same arguments with pattern texts (Bzip2.searchRegex); matches holds (offset, pattern, length) triples.
+napi_value search_call(napi_env env, napi_callback_info info, bool regex) {
   if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
   size_t argc = 8; napi_value argv[8];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
@@ -326,29 +331,72 @@ napi_value bzip2_search(napi_env env, napi_callback_info info) {
   std::vector<cjs_bz_match> found;
   const uint64_t ulen = len < 0 ? ~0ull : (uint64_t)len;
   size_t cap = limit < 0 ? 0 : (size_t)limit;
+  const auto search = regex ? api.search_regex : api.search;
+  const size_t per = regex ? 3 : 2;
   if (limit < 0) {                                                 // the count query
-    rc = api.search(p ? p : &dummy, n, ix, pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, (uint64_t)off, ulen, nullptr, 0, &si, nullptr);
+    rc = search(p ? p : &dummy, n, ix, pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, (uint64_t)off, ulen, nullptr, 0, &si, nullptr);
     cap = (size_t)si.n_matches;
   }
   if (rc == 0 && (limit >= 0 || cap)) {
     try { found.resize(cap); } catch (...) { api.index_destroy(ix); napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
-    rc = api.search(p ? p : &dummy, n, ix, pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, (uint64_t)off, ulen, cap ? found.data() : nullptr, cap, &si, nullptr);
+    rc = search(p ? p : &dummy, n, ix, pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, (uint64_t)off, ulen, cap ? found.data() : nullptr, cap, &si, nullptr);
   }
   std::string detail = rc == 0 && !si.n_bad_blocks ? "" : api.detail_();      // (before the next call of the library on this thread)
+  if (rc != 0) { napi_value e = throw_code(env, rc); api.index_destroy(ix); return e; }      // (the detail goes into the error first)
   api.index_destroy(ix);
-  if (rc != 0) return throw_code(env, rc);
   const size_t got = (size_t)std::min<uint64_t>(cap, si.n_matches);
   napi_value res, mab, mta, v; void* mdst;
   napi_create_object(env, &res);
-  napi_create_arraybuffer(env, sizeof(double) * 2 * got, &mdst, &mab);
-  for (size_t k = 0; k < got; k++) { ((double*)mdst)[2 * k] = (double)found[k].off; ((double*)mdst)[2 * k + 1] = (double)found[k].pattern; }
-  napi_create_typedarray(env, napi_float64_array, 2 * got, mab, 0, &mta);
+  napi_create_arraybuffer(env, sizeof(double) * per * got, &mdst, &mab);
+  for (size_t k = 0; k < got; k++) {
+    double* m = (double*)mdst + per * k;
+    m[0] = (double)found[k].off; m[1] = (double)found[k].pattern;
+    if (regex) m[2] = (double)found[k].reserved;
+  }
+  napi_create_typedarray(env, napi_float64_array, per * got, mab, 0, &mta);
   napi_set_named_property(env, res, "matches", mta);
   napi_create_double(env, (double)si.n_matches, &v); napi_set_named_property(env, res, "total", v);
   napi_create_double(env, (double)si.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
   napi_create_double(env, si.n_bad_blocks ? (double)si.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
   napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
   return res;
+}
+
+napi_value bzip2_search(napi_env env, napi_callback_info info) { return search_call(env, info, false); }
+napi_value bzip2_search_regex(napi_env env, napi_callback_info info) { return search_call(env, info, true); }
+
+// regexCheck(patterns, lengths, flags) -> Float64Array of (states, maxLen) pairs, one per pattern   (Bzip2.regexCheck; no device)
+napi_value regex_check(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* pp = nullptr; size_t pn = 0;
+  bool is_ta = false;
+  if (argc >= 2) napi_is_typedarray(env, argv[1], &is_ta);
+  napi_typedarray_type t = napi_int8_array; size_t npat = 0; void* ld = nullptr; napi_value lab; size_t loff = 0;
+  if (is_ta) napi_get_typedarray_info(env, argv[1], &t, &npat, &ld, &lab, &loff);
+  if (argc < 3 || !get_bytes(env, argv[0], &pp, &pn) || !is_ta || t != napi_float64_array) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array patterns, Float64Array lengths, flags)"); return nullptr;
+  }
+  double flags = 0;
+  napi_get_value_double(env, argv[2], &flags);
+  std::vector<uint32_t> p_off(npat + 1, 0);
+  uint64_t sum = 0;
+  for (size_t j = 0; j < npat; j++) {
+    const double l = ((const double*)ld)[j];
+    sum += l >= 0 && l <= 65536.0 ? (uint64_t)l : 65536u;
+    p_off[j + 1] = (uint32_t)std::min<uint64_t>(sum, 0xFFFFFFFFull);
+  }
+  if (sum != pn || npat > 1000000) { napi_throw_type_error(env, nullptr, "the pattern lengths do not add up to the pattern bytes"); return nullptr; }
+  static const uint8_t dummy = 0;
+  std::vector<uint32_t> states(npat + 1), max_len(npat + 1);
+  const int rc = api.regex_check(pp ? pp : &dummy, p_off.data(), (uint32_t)npat, (uint32_t)flags, states.data(), max_len.data());
+  if (rc != 0) return throw_code(env, rc);
+  napi_value ab, ta; void* dst;
+  napi_create_arraybuffer(env, sizeof(double) * 2 * npat, &dst, &ab);
+  for (size_t j = 0; j < npat; j++) { ((double*)dst)[2 * j] = states[j]; ((double*)dst)[2 * j + 1] = max_len[j]; }
+  napi_create_typedarray(env, napi_float64_array, 2 * npat, ab, 0, &ta);
+  return ta;
 }
 
 // bzip2Compare(input, index, other, otherIndex, otherOffset, offset, length, limit) -> { diffs: Float64Array, total, firstDiff,
@@ -895,6 +943,8 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2BuildIndex", nullptr, bzip2_build_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2ReadRanges", nullptr, bzip2_read_ranges, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Search", nullptr, bzip2_search, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2SearchRegex", nullptr, bzip2_search_regex, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"regexCheck", nullptr, regex_check, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Compare", nullptr, bzip2_compare, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2BuildLineIndex", nullptr, bzip2_build_line_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -258,7 +258,7 @@ int cjs_bzip2_read_ranges_device(const uint8_t *d_in, size_t n, const cjs_bz_ind
 typedef struct cjs_bz_match {
   uint64_t off;        /* decoded offset of the match's first byte */
   uint32_t pattern;    /* which pattern */
-  uint32_t reserved;   /* 0 */
+  uint32_t reserved;   /* 0 from cjs_bzip2_search; the match's length from cjs_bzip2_search_regex */
 } cjs_bz_match;
 typedef struct cjs_bz_search_info {
   uint64_t n_matches;       /* all matches of the window, also when more than cap */
@@ -272,6 +272,51 @@ int cjs_bzip2_search(const uint8_t *in, size_t n, const cjs_bz_index *idx, const
 int cjs_bzip2_search_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint8_t *pat, const uint32_t *pat_off,
                             uint32_t npat, uint32_t flags, uint64_t off, uint64_t len, cjs_bz_match *found, size_t cap,
                             cjs_bz_search_info *info, const cjs_opts *opts);
+/* cjs_bzip2_search_regex: cjs_bzip2_search with patterns that are bounded regular expressions.  The arguments are those of
+ * cjs_bzip2_search; pattern j is the TEXT pat[pat_off[j] .. pat_off[j+1]) of 1..1024 bytes, flags are CJS_SEARCH_NOCASE or 0.
+ * A match (o, j, L) exists iff some string of 1..256 bytes matched by pattern j stands at decoded offset o, with o >= off, the
+ * string inside the window, and the string inside one run of consecutive GOOD blocks (blocks of size zero are transparent).
+ * L is the LONGEST such length, bounded by 256, by the window's end and by the run's end.  Matches longer than 256 bytes are not
+ * seen.  A start position is still reported if a shorter match starts there.  `a.*b` finds every `a` with a `b` within the next
+ * 255 bytes of its line, with L reaching to the last such `b`.  A record's `reserved` holds L.
+ * No state is carried from byte to byte across tiles, batches or passes: every start position is judged on its own, by walking an
+ * anchored automaton over at most 256 bytes in front of it, so segments, carry, tiles, the count-then-emit round and the bad-block
+ * rules are those of cjs_bzip2_search, and so are these: every start position counts (overlapping matches, several patterns at
+ * one offset); the list is sorted by (off, pattern); `found` gets the first min(cap, n_matches) and nothing past them is written;
+ * cap = 0 with found = NULL is the count query; a bad block is reported in info and the detail text, the call returns 0 and
+ * nothing matches across it; a window without a touched block succeeds without touching the device; the list does not depend on
+ * CJS_RANGE_PASS_BLOCKS, CJS_DEC_GROUP_BYTES, CJS_DEC_BATCH_ELEMS or CJS_DEC_ROW_BYTES.
+ * The dialect: patterns are byte strings, and where both Python's `re` on a bytes pattern (no flags, or re.IGNORECASE) and this
+ * dialect accept a pattern they mean the same.  Accepted: literal bytes (bytes >= 0x80 are literals); \ before punctuation;
+ * \n \r \t \f \v \xHH; \d \w \s \D \W \S (ASCII); `.` = any byte but 0x0A; bracket classes with ranges, negation and the
+ * escapes above ([^a] matches 0x0A); ( ) and (?: ), both plain grouping; |; ? * + {m} {m,} {,n} {m,n} with bounds <= 256.  With
+ * CJS_SEARCH_NOCASE 'A'..'Z' equal 'a'..'z' in pattern and text, classes included ([Z-a] matches z Z [ ` a A, [^A-C] neither b nor
+ * B); no other byte folds.
+ * Refusals, all before the device is touched, each with a detail text "pattern J, byte P: ...".  CJS_E_INVALID_ARG: the argument
+ * errors of cjs_bzip2_search; npat outside 1..64; a pattern text outside 1..1024 bytes; a syntax error (unbalanced ( or [, a
+ * quantifier with nothing to repeat or behind another, {m,n} with n < m or a bound above 256, a bad \x, an unescaped { that is no
+ * quantifier); a pattern that matches the empty string.  CJS_E_UNSUPPORTED: what `re` has and this dialect does not (^ $ \b \B
+ * \A \Z, backreferences, lookaround, lazy or possessive quantifiers, named groups, inline flags, any other escaped letter or
+ * digit); a pattern whose minimised automaton has more than 255 states that a transition enters (the start state takes none of the
+ * 255 when nothing leads back to it: x{256} is accepted); patterns whose tables together exceed CJS_REGEX_MAX_TABLE_BYTES.
+ * Anchors are left out on purpose: a start position does not know the byte in front of it; lines are the line table's business.
+ * CJS_DEBUG: one "[cjs regex]" line per call on stderr.
+ * cjs_regex_check compiles only, without a device: per pattern the number of states of its automaton (the dead one not counted)
+ * and the longest possible match, clamped to 256 (the largest of these sizes the halo and the carry); either array may be NULL.
+ * cjs_stage_regex_scan EXISTS FOR TESTS; no product path calls it: it runs the compiled tables over the plain host buffer
+ * text[0 .. n) with the per-position walk of the kernels; found gets the first min(cap, *n_found) of every (o, j, L) of the buffer
+ * in (off, pattern) order, *n_found counts them all. */
+#define CJS_REGEX_MAX_PATTERN_TEXT 1024
+#define CJS_REGEX_MAX_TABLE_BYTES 32768
+int cjs_bzip2_search_regex(const uint8_t *in, size_t n, const cjs_bz_index *idx, const uint8_t *pat, const uint32_t *pat_off,
+                           uint32_t npat, uint32_t flags, uint64_t off, uint64_t len, cjs_bz_match *found, size_t cap,
+                           cjs_bz_search_info *info, const cjs_opts *opts);
+int cjs_bzip2_search_regex_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const uint8_t *pat, const uint32_t *pat_off,
+                                  uint32_t npat, uint32_t flags, uint64_t off, uint64_t len, cjs_bz_match *found, size_t cap,
+                                  cjs_bz_search_info *info, const cjs_opts *opts);
+int cjs_regex_check(const uint8_t *pat, const uint32_t *pat_off, uint32_t npat, uint32_t flags, uint32_t *states, uint32_t *max_len);
+int cjs_stage_regex_scan(const uint8_t *pat, const uint32_t *pat_off, uint32_t npat, uint32_t flags, const uint8_t *text, size_t n,
+                         cjs_bz_match *found, size_t cap, size_t *n_found);
 /* The line table of an indexed stream: seek by line, number offsets (`wc -l`, `sed -n 'a,bp'`, `bzgrep -n` over a .bz2 stream).
  * A NEWLINE is the byte 0x0A and no other (CR does not count).  With off[b] the decoded offset of block b of `idx`, total =
  * total_bytes, nl[b] the newlines among block b's decoded bytes, cum[b] the sum of nl[0..b) and N their total:
