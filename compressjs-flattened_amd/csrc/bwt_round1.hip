@@ -1,0 +1,143 @@
+// bwt_round1.hip — round 1 of the suffix sort (the map: bwt.hip): the keys of its unsegmented form, and the record rebuild between
+// the two phases of the packed form.  The radix passes themselves are radix.hip; the key and record layouts are bwt_rules.h.
+#include "bwt_dev.hpp"
+
+namespace cjs {
+
+// keys of the unsegmented round 1: (block id, first nsym symbols).  cyclic: bytes wrap; sentinel: 9-bit symbols, 0 = past the end
+// VarGeom: one more bit between the block id and the symbols flags a hole; a hole's symbols are its position (unique)
+template <typename G>
+__global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__ T, G g, int cyclic, int nsym, uint32_t M,
+                                                     uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+  for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < M; a += (uint64_t)gridDim.x * 256) {
+    const uint32_t blk = (uint32_t)(a / g.stride), i = (uint32_t)(a - (uint64_t)blk * g.stride), n = blk_len(g, blk);
+    const uint8_t* t = T + (size_t)blk * g.stride;
+    uint64_t k = 0;
+    if constexpr (std::is_same_v<G, VarGeom>) {
+      uint32_t x = i;
+      if (i >= n) k = (1ull << r1_hole_bit(nsym)) | i;
+      else for (int j = 0; j < nsym; j++) { k = (k << 8) | t[x]; if (++x == n) x = 0; }
+      k |= (uint64_t)blk << (r1_hole_bit(nsym) + 1);
+    } else if (cyclic) {
+      uint32_t x = i;
+      for (int j = 0; j < nsym; j++) { k = (k << 8) | t[x]; if (++x == n) x = 0; }
+      k |= (uint64_t)blk << r1_block_shift(true, nsym);
+    } else {
+      for (int j = 0; j < nsym; j++) { const uint32_t x = i + j; k = (k << 9) | (x < n ? (uint32_t)t[x] + 1u : 0u); }
+      k |= (uint64_t)blk << r1_block_shift(false, nsym);
+    }
+    key[a] = k; val[a] = i;                // slot a of round 1 is sorted position a: no pos[] yet
+  }
+}
+
+// Two-phase round 1 (cyclic, packed records): seven bytes of depth at 8 bytes per record.  Phase 1 sorted every block by
+// bytes 2..6; here every sorted slot learns r1 = block-local slot of the head of its (bytes 2..6) class and becomes the
+// phase-2 record  byte0 . byte1 (bits 63..48) | r1 (47..28) | parity (20) | position (19..0); two more stable passes on the
+// top 16 bits then order by (byte0, byte1, class of bytes 2..6), and key >> 20 is the 7-byte group key.
+// Tiles are the tiles of the segmented radix passes (one segment per block), so this kernel also leaves the per-tile
+// histogram of byte1 -- the digit of the first phase-2 pass -- in hist[], and that pass needs no rs_hist of its own.
+// No flag / scan passes in front either: the only class head a tile cannot see is the one of the class that runs into it,
+// and the block is sorted, so wave 0 finds it by looking at the 64 slots in front of the tile (nearly always enough) and
+// otherwise by a 64-way search for the lower bound of the tile's first key in the block.
+__global__ __launch_bounds__(256) void bwt_phase2_records(const uint64_t* __restrict__ key, SegGeom sg, const uint8_t* __restrict__ T,
+                                                          uint32_t* __restrict__ hist, uint64_t* __restrict__ out) {
+  __shared__ uint64_t sk[RS_TILE + 1];
+  __shared__ uint64_t m_nh[64];
+  __shared__ uint32_t wp_head[64];
+  constexpr int PH = 2;                          // histogram copies per wave (the 32 KB of sk[] limit the residency already)
+  __shared__ uint32_t h[4 * 256 * PH];
+  __shared__ uint32_t carry_s;
+  const uint32_t tile = blockIdx.x;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const TileRef t = tile_ref(sg, tile);
+  if (!t.nvalid) { hist[(size_t)tile * 256 + tid] = 0; return; }
+  const uint64_t base = t.base, seg0 = (uint64_t)t.seg * sg.stride;
+  const uint32_t nvalid = t.nvalid, n = t.seg + 1 == sg.nseg ? sg.n_last : sg.stride;
+  uint64_t k16[16];                              // all loads first (see bwt_apply)
+#pragma unroll
+  for (int it = 0; it < 16; it++) {
+    const uint32_t e = (uint32_t)it * 256u + tid;
+    k16[it] = __builtin_nontemporal_load(key + base + (e < nvalid ? e : nvalid - 1u));
+  }
+  if (tid == 64) sk[0] = t.off ? key[base - 1] : ~0ull;
+  if (w == 0) {
+    // head of the class of the tile's first slot (global index + 1, as bwt_scan_tiles would have carried it)
+    const uint32_t carry = (uint32_t)class_head_before(key, seg0, base, PK_SHIFT, lane) + 1u;
+    if (lane == 0) carry_s = carry;
+  }
+  // the two leading bytes of every record's suffix: gathers from the block text (L2), independent of everything below
+  uint32_t b01[16];
+  {
+    const uint8_t* tx = T + seg0;
+#pragma unroll
+    for (int it = 0; it < 16; it++) {
+      const uint32_t p = pk_pos(k16[it]);
+      b01[it] = ((uint32_t)tx[p] << 8) | tx[p + 1 < n ? p + 1 : 0];          // (one unaligned 16-bit load instead: 720 -> 900 us)
+      b01[it] |= (uint32_t)tx[p ? p - 1 : n - 1] << 16;                     // the byte in front (nearly always the line of tx[p]): carried from here on
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4 * PH; i++) h[i * 256 + tid] = 0;
+#pragma unroll
+  for (int it = 0; it < 16; it++) {
+    const uint32_t e = (uint32_t)it * 256u + tid;
+    sk[e + 1] = e < nvalid ? k16[it] : ~0ull;
+  }
+  __syncthreads();
+  uint32_t* hw = h + w * 256 * PH + (tid & (PH - 1));      // (bank-interleaved copies as in rs_hist)
+#pragma unroll
+  for (int it = 0; it < 16; it++) {
+    const uint32_t e = (uint32_t)it * 256u + tid;
+    const bool nh = e < nvalid && (t.off + e == 0 || (sk[e] >> PK_SHIFT) != (sk[e + 1] >> PK_SHIFT));
+    const uint64_t mnh = __ballot(nh);
+    if (lane == 0) m_nh[it * 4 + w] = mnh;
+    if (e < nvalid) atomicAdd(&hw[(b01[it] & 255u) * PH], 1u);
+  }
+  __syncthreads();
+  if (w == 0) {
+    const uint64_t mh = m_nh[lane];
+    uint32_t im;
+    wp_head[lane] = last_head_before_word(mh, lane, im);
+  }
+  {
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int r = 0; r < PH; r++) sum += h[i * 256 * PH + tid * PH + r];
+    hist[(size_t)tile * 256 + tid] = sum;
+  }
+  __syncthreads();
+  const uint32_t carry = carry_s;
+  const uint64_t le = mask_le(lane);
+#pragma unroll
+  for (int it = 0; it < 16; it++) {
+    const uint32_t e = (uint32_t)it * 256u + tid;
+    if (e < nvalid) {
+      const int wi = it * 4 + w;
+      const uint64_t hm = m_nh[wi] & le;
+      const uint32_t head_a = hm ? (uint32_t)base + (uint32_t)wi * 64u + 63u - (uint32_t)__builtin_clzll(hm) : wp_head[wi] ? (uint32_t)base + wp_head[wi] - 1u : carry - 1u;
+      const uint32_t r1 = head_a - (uint32_t)seg0;
+      __builtin_nontemporal_store(pk2_record(b01[it], r1, b01[it] >> 16, pk_pos(k16[it])), out + base + e);
+    }
+  }
+}
+
+// The sort of round 1 by the plan: unsegmented | segmented | segmented and packed (two phases)
+template <typename G>
+int sort_round1(hipStream_t s, BwtWork& w, const G& g, const Plan& p, Round& r, LaunchTimes* lt) {
+  if (!p.segmented) {
+    const int grid_lin = (int)((r.A + 255) / 256 < 65535u * 16u ? (r.A + 255) / 256 : 65535u * 16u);
+    hipLaunchKernelGGL(bwt_init_keys<G>, dim3(grid_lin), dim3(256), 0, s, p.gen.T, g, p.gen.cyclic, p.nsym, r.A, w.key[0], w.val[0]);
+    return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt);
+  }
+  if (!p.packed) return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt, &p.sg, &p.gen);
+  CJS_TRY((radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, PK_KEY_LO, 64, lt, &p.sg, &p.gen, true, false, w.dflag)));
+  hipLaunchKernelGGL(bwt_phase2_records, dim3(p.sg.nseg * p.sg.tps), dim3(256), 0, s, w.key[r.c], p.sg, p.gen.T, w.rs.hist, w.key[1 - r.c]);
+  r.c = 1 - r.c;
+  return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 48, 64, lt, &p.sg, nullptr, true, true, w.dflag);
+}
+template int sort_round1<Geom>(hipStream_t, BwtWork&, const Geom&, const Plan&, Round&, LaunchTimes*);
+template int sort_round1<VarGeom>(hipStream_t, BwtWork&, const VarGeom&, const Plan&, Round&, LaunchTimes*);
+
+}  // namespace cjs

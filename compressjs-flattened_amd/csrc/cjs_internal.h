@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <new>
 #include "cjs_hip.h"
+#include "bwt_rules.h"      // bits_for, enum Counter
 
 #define CJS_HIP_TRY(expr)                                                                   \
   do {                                                                                      \
@@ -124,7 +125,6 @@ inline void Arena::destroy() {
 }
 
 constexpr uint32_t RS_TILE = 4096;   // radix-sort tile (256 threads x 16 keys)
-inline int bits_for(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }      // bits needed to write x
 
 // Workspace of the radix sorter (radix.hip): room for sorts of up to hist_tiles tiles in up to bintot_segs segments.  The rest of
 // the code relies on two things: hist is free between sorts (sort_round of bwt.hip borrows it as hcount), and the chunk sums of
@@ -199,7 +199,7 @@ struct BwtWork {
   uint8_t* hflag = nullptr;      // per slot of a round >= 2, behind the sort: bit 0 = head of the new grouping, bit 1 = head of the previous one
   RadixWork rs;                  // of the radix passes
   uint32_t* tile_cnt = nullptr;  // 3 * tiles (+ scanned copies)
-  uint32_t* counters = nullptr;  // 16, of which five are in use: see enum Counter in bwt.hip
+  uint32_t* counters = nullptr;  // 16, of which five are in use: see enum Counter in bwt_rules.h
   Pinned<uint32_t> h_counters;     // host mirror
   Event ev_scan;                   // recorded behind the tile scan of a round (the host waits for the counters, not for the round)
   LaunchTimes lt;                  // dominant-kernel events of the last bwt_run that was given a stats struct

@@ -1,9 +1,10 @@
-// radix.hpp — device-side pieces that the radix sorter (radix.hip) and the suffix-sort kernels (bwt.hip) share: the XCD tile
-// order, the tile geometry of a segmented sort, the key source and record layout of round 1 (rs_hist and rs_scatter are
-// instantiated on them) and the wave ranking step of a scatter.
+// radix.hpp — device-side pieces that the radix sorter (radix.hip) and the suffix-sort kernels (bwt_*.hip) share: the XCD tile
+// order, the tile geometry of a segmented sort, the key source of round 1 (rs_hist and rs_scatter are instantiated on it; the
+// record layouts are bwt_rules.h) and the wave ranking step of a scatter.
 #pragma once
 #include "cjs_internal.h"
 #include "prims.hpp"
+#include "bwt_rules.h"
 
 namespace cjs {
 
@@ -34,17 +35,8 @@ __device__ __forceinline__ TileRef tile_ref(const SegGeom& sg, uint32_t tile) {
 // Key source of the first pass of round 1: keys are made on the fly from the block bytes (no key array is ever
 // written for them).  key = leading nsym symbols | block parity above them (adjacent blocks must not compare equal);
 // cyclic: bytes, wrapping; sentinel: 9-bit symbols byte+1, 0 = past the end.  value = position in the block.
+// (the packed records of the cyclic round 1, packed == 2: pk_record of bwt_rules.h)
 struct GenSrc { const uint8_t* T; int cyclic, nsym, packed; };
-// packed records (cyclic round 1): ONE u64 per suffix = 5 bytes (bits 63..24) | block parity (bit 20) | position in the block
-// (bits 19..0): a radix pass moves 8 B per suffix each way instead of 12, and there is no value array.  The first phase sorts by
-// bytes 2..6 of the suffix (packed == 2, the only packed form)
-constexpr int PK_SHIFT = 20, PK_KEY_LO = 24;
-constexpr uint32_t PK_POS_MASK = (1u << PK_SHIFT) - 1u;
-// records of the two-phase sort after bwt_phase2_records: byte0 . byte1 (63..48) | rank of the class of bytes 2..6 (47..28) | the byte IN
-// FRONT of the suffix (27..20) | position (19..0).  The group key is key >> PK2_GSHIFT; block boundaries are taken from the slot
-// number (no parity bit).  The byte in front is what the BWT emits for the suffix: it rides along (later in the top byte of val[])
-// so that the regroup kernels write BWT bytes without gathering them from the text.
-constexpr int PK2_GSHIFT = 28, PK2_PREV_SHIFT = 20, VAL_PREV_SHIFT = 24;
 constexpr uint32_t GEN_PAD = 8;
 // stages the tile's bytes (+GEN_PAD lookahead) in LDS; returns the byte offset of the tile's first byte inside tb (< 4):
 // tiles that do not touch the end of their block are copied as aligned 32-bit words from the aligned-down address
@@ -73,7 +65,7 @@ __device__ __forceinline__ uint64_t gen_key(const GenSrc& gs, const SegGeom& sg,
   uint64_t k = 0;
   if (gs.cyclic) {
     k = ((uint64_t)__builtin_bswap32(lo) << 24) | (uint64_t)(__builtin_bswap32(hi) >> 8);     // 7 bytes, first byte on top
-    if (gs.packed) return ((k & 0xFFFFFFFFFFull) << PK_KEY_LO) | ((uint64_t)(t.seg & 1u) << PK_SHIFT) | (uint64_t)(t.off + loc);  // bytes 2..6 (two-phase sort)
+    if (gs.packed) return ((k & 0xFFFFFFFFFFull) << PK_KEY_LO) | ((uint64_t)(t.seg & 1u) << PK_SHIFT) | (uint64_t)(t.off + loc);  // bytes 2..6 (two-phase sort): pk_record
     k >>= 8 * (7 - gs.nsym);
     k |= (uint64_t)(t.seg & 1u) << (8 * gs.nsym);
   } else {

@@ -1,4 +1,4 @@
-"""Suffix sort rounds >= 2 with head flags as bytes (bwt.hip: hflag[]): inputs aimed at the seams of that form.
+"""Suffix sort rounds >= 2 with head flags as bytes (bwt_tile_sort.hip, bwt_defer.hip, bwt_regroup.hip: hflag[]): inputs aimed at the seams of that form.
 
 Rounds >= 2 no longer pass a sorted 64-bit key per slot from the sorters to the regroup kernels but one flag byte (bit 0 = head
 of the new grouping, bit 1 = head of the previous round's grouping).  Every slot has one writer: the tile-sorter window that
@@ -19,7 +19,7 @@ import recipes
 import support
 
 ROOT = support.ROOT
-WIN = 3072          # nominal range of a tile-sorter window (TS_NOM in bwt.hip): a window owns the groups that start in it
+WIN = 3072          # nominal range of a tile-sorter window (TS_NOM in bwt_rules.h): a window owns the groups that start in it
 
 
 def _check_bwt(hip, oracle, data, block_len, cyclic):
@@ -46,7 +46,11 @@ def _check_bwt(hip, oracle, data, block_len, cyclic):
 # byte into a unit repeat six of its bytes, and the few that also agree in the byte behind form small groups of their own:
 # those start with a byte >= 0x40 and sort behind all planted groups.)  A size of 1 cannot be planted: a suffix alone in its
 # group is resolved and leaves the array; every case makes thousands of them as NEW groups.
-def _planted(sizes_and_offsets, unit_len, sep_len, seed):
+# The filler groups between the targets decide which tile sorter round 2 takes (radix_tile_sorter in bwt_rules.h: the LDS radix
+# sorter from 5 suffixes per group on, the counting / bitonic sorter below): fillers of 450 put the targets through
+# bwt_tile_sort_radix, fillers of 2 and 3 through bwt_tile_sort.  Those take more units than two id bytes number (64 * 128): a
+# third id byte, again at or above 0x80, keeps "first byte below 0x40, in id order".
+def _planted(sizes_and_offsets, unit_len, sep_len, seed, tiny_fillers=False):
     """sizes_and_offsets: [(group size, offset of its first slot from a multiple of WIN)] -> (bytes, [(start slot, size)])"""
     rng = np.random.default_rng(seed)
     plan = []                      # sizes of all planted groups in array order
@@ -55,6 +59,14 @@ def _planted(sizes_and_offsets, unit_len, sep_len, seed):
 
     def fill(gap):
         nonlocal at
+        if tiny_fillers and gap:
+            assert gap >= 2
+            while gap > 4:         # 2, 3, 2, 3, ... and a rest of 2, 3 or 2 + 2
+                m = 2 + (len(plan) & 1)
+                plan.append(m); gap -= m; at += m
+            for m in ((2, 2) if gap == 4 else (gap,)):
+                plan.append(m); at += m
+            return
         while gap > 900:
             plan.append(450); gap -= 450; at += 450
         if gap:
@@ -72,8 +84,12 @@ def _planted(sizes_and_offsets, unit_len, sep_len, seed):
     parts = []
     for uid, m in enumerate(plan):
         unit = rng.integers(0x40, 0x80, unit_len, dtype=np.uint8)
-        unit[0] = uid >> 7; unit[1] = 0x80 | (uid & 127)
-        assert uid < 64 * 128
+        if tiny_fillers:
+            unit[0] = uid >> 14; unit[1] = 0x80 | ((uid >> 7) & 127); unit[2] = 0x80 | (uid & 127)
+            assert uid < 64 * 128 * 128
+        else:
+            unit[0] = uid >> 7; unit[1] = 0x80 | (uid & 127)
+            assert uid < 64 * 128
         occ = rng.integers(0x40, 0x80, (m, unit_len + sep_len), dtype=np.uint8)
         occ[:, :unit_len] = unit
         parts.append(occ.reshape(-1))
@@ -87,6 +103,11 @@ def _planted(sizes_and_offsets, unit_len, sep_len, seed):
 _SIZES = (2, 64, 65, 1023, 1024, 1025)
 _SHALLOW = [(s, o) for s in _SIZES for o in (-1, 0, 1)]        # unit of 7 bytes: the groups split into singletons in round 2
 _DEEP = [(s, o) for s in (65, 1024, 1025) for o in (-1, 0, 1)]  # unit of 15 bytes: they pass round 2 whole (1025: deferred twice) and split in round 3
+_PLANTED = {
+    "shallow": lambda: _planted(_SHALLOW, 7, 5, 101),
+    "deep": lambda: _planted(_DEEP, 15, 4, 102),
+    "tiny": lambda: _planted(_SHALLOW, 7, 5, 103, tiny_fillers=True),      # the shallow targets among fillers of 2 and 3
+}
 
 
 def _groups_after_round1(data):
@@ -103,23 +124,30 @@ def _groups_after_round1(data):
     return list(zip((np.cumsum(sizes) - sizes).tolist(), sizes.tolist()))
 
 
-@pytest.mark.parametrize("which", ["shallow", "deep"])
+@pytest.mark.parametrize("which", ["shallow", "deep", "tiny"])
 def test_planted_inputs_put_the_groups_where_they_say(which):
     """no GPU: the construction above really puts groups of the listed sizes on the slots just before, on and just behind
-    multiples of the window's nominal range"""
-    data, targets = _planted(_SHALLOW, 7, 5, 101) if which == "shallow" else _planted(_DEEP, 15, 4, 102)
+    multiples of the window's nominal range, and round 2 takes the tile sorter that the fillers are meant to choose: A
+    (unresolved suffixes) and ngroups as the host reads them behind round 1 of the cyclic form"""
+    data, targets = _PLANTED[which]()
     assert data.size <= 1000000
-    have = set(_groups_after_round1(data))
+    groups = _groups_after_round1(data)
+    have = set(groups)
     for start, size in targets:
         assert (start, size) in have, (start, size)
     assert {(s % WIN if s % WIN < WIN // 2 else s % WIN - WIN) for s, _ in targets} == {-1, 0, 1}
+    assert sorted({size for _, size in targets}) == sorted({s for s, _ in (_DEEP if which == "deep" else _SHALLOW)})
+    A, ngroups = sum(size for _, size in groups), len(groups)
+    assert A >= 2 * 4096                                        # the tile sorters take the round (tile_sorted_round in bwt_rules.h)
+    assert (A // ngroups < 5) == (which == "tiny"), (A, ngroups)      # radix_tile_sorter: counting / bitonic below 5, LDS radix from 5 on
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cyclic", [True, False], ids=["cyclic", "sentinel"])
-@pytest.mark.parametrize("which", ["shallow", "deep"])
+@pytest.mark.parametrize("which", ["shallow", "deep", "tiny"])
 def test_groups_on_window_borders(hip, oracle, which, cyclic):
-    data, _ = _planted(_SHALLOW, 7, 5, 101) if which == "shallow" else _planted(_DEEP, 15, 4, 102)
+    """shallow, deep: round 2 through bwt_tile_sort_radix; tiny: through bwt_tile_sort, whose window prologue is the same code"""
+    data, _ = _PLANTED[which]()
     _check_bwt(hip, oracle, data, data.size, cyclic)
 
 
