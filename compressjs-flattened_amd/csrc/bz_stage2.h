@@ -410,7 +410,9 @@ __global__ __launch_bounds__(256) void BZ_NAME(bz_group_syms)(const uint8_t* __r
   sym_stride = rlim[row] + 4096u;                // (the input's own symbol cap: dec_phase_a's sym_stride rule)
 #endif
   const int g = sel_all[(size_t)row * MAX_SELECTORS + k];
-  const uint32_t sym_total = T.sym_total;
+  // (symbols 0 and 1 are RUNA and RUNB whatever the used map says: with no used byte there is NO end-of-block symbol, :1621 comes
+  // before :1654, and the block is rejected when its selectors run out)
+  const uint32_t last_rank = max(T.sym_total, 1u);
   const uint64_t data_bit = T.data_bit;
   uint64_t pos = data_bit + gstart_all[(size_t)row * (MAX_SELECTORS + 1) + k];
   // symbol j of group k is stored at [j][k]: the lanes of a wave (64 groups) write one line, not 64
@@ -434,7 +436,7 @@ __global__ __launch_bounds__(256) void BZ_NAME(bz_group_syms)(const uint8_t* __r
     }
     if (!len || idx >= sym_stride) { atomicMin(&T.err_key, (unsigned long long)idx << 32); break; }      // no code starts here (or more symbols than any block has room for)
     pos += len;
-    if (sym > sym_total) { atomicMin(&T.eob_key, ((unsigned long long)idx << 32) | (unsigned long long)(uint32_t)(pos - data_bit)); break; }      // end of block (:1640)
+    if (sym > last_rank) { atomicMin(&T.eob_key, ((unsigned long long)idx << 32) | (unsigned long long)(uint32_t)(pos - data_bit)); break; }      // end of block (:1640)
     syms[(size_t)j * sym_groups] = (uint16_t)sym;
   }
 }
