@@ -18,8 +18,9 @@
 //             rebuilds the records as bytes 0..1 | rank of the class of bytes 2..6 | the byte in front | position, and two more
 //             passes finish depth 7
 //   sentinel  (u64 key, u32 value) records, 9-bit symbols
-//   fallback  more blocks or tiles than the workspace has segments for, blocks of different lengths (bwt_run_var), or
-//             CJS_NO_SEGMENTED_SORT: bwt_init_keys writes keys with the block id on top, sorted as one array
+//   fallback  more blocks or tiles than the workspace has segments for, several blocks shorter than a 4096-slot tile, blocks of
+//             different lengths (bwt_run_var), or CJS_NO_SEGMENTED_SORT: bwt_init_keys writes keys with the block id on top,
+//             sorted as one array
 // Rounds >= 2 sort only the suffixes of unresolved groups, by (group ordinal, rank of suffix + h), h = 7, 14, 28, ...  The array
 // is already ordered by group, so the tile sorters order every group of <= 1024 suffixes in LDS and fetch the ranks themselves;
 // larger groups are deferred: compacted, radix-sorted apart, scattered back.  Whole-array fallbacks (radix passes over keys that
@@ -77,7 +78,11 @@ static Plan plan_round1(const BwtWork& w, const G& g, bool cyclic, const uint8_t
   constexpr bool VAR = std::is_same_v<G, VarGeom>;
   Plan p;
   const uint32_t tps = ((g.nb > 1 ? g.stride : g.n_last) + RS_TILE - 1) / RS_TILE;
-  p.segmented = !VAR && (uint64_t)g.nb * tps <= w.rs.hist_tiles && g.nb <= w.rs.bintot_segs && getenv("CJS_NO_SEGMENTED_SORT") == nullptr;
+  // Segmented keys carry no block id, and the regroup of round 1 (bwt_flags, bwt_apply) takes ONE block start per 4096-slot tile
+  // as a head: blocks shorter than a tile, several to a tile, keep the block id in the key (equal blocks would merge otherwise)
+  const bool blocks_share_tiles = g.nb > 1 && g.stride < RS_TILE;
+  p.segmented = !VAR && !blocks_share_tiles && (uint64_t)g.nb * tps <= w.rs.hist_tiles && g.nb <= w.rs.bintot_segs &&
+                getenv("CJS_NO_SEGMENTED_SORT") == nullptr;
   p.packed = p.segmented && cyclic;
   p.sweeps = g.nb >= 8 && p.packed;
   const Round1Keys k = round1_keys(g.nb, cyclic, p.segmented, VAR);

@@ -37,6 +37,37 @@ extern "C" int cjs_stage_bwt(const uint8_t* in, size_t n, int block_len, int cyc
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
+// Blocks of different lengths, one per slot of `stride` bytes: the geometry of the batched compressor (batch.hip, run_sub), which
+// instantiates every templated kernel of the sort a second time and sorts round 1 unsegmented, with a depth that follows nb.
+extern "C" int cjs_stage_bwt_var(const uint8_t* blocks, uint32_t nb, uint32_t stride, const uint32_t* len, uint8_t* out, int32_t* pidx,
+                                 const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (nb == 0 || nb > 65535 || stride == 0 || stride % 16 != 0) return CJS_E_INVALID_ARG;      // (run_list only makes such strides)
+  for (uint32_t k = 0; k < nb; k++) if (len[k] == 0 || len[k] > stride) return CJS_E_INVALID_ARG;      // the kernels read len - 1
+  const size_t e = (size_t)nb * stride;
+  if (!bwt_admits(e, stride)) return CJS_E_INVALID_ARG;
+  Arena arena;
+  CJS_TRY(arena.init(BwtWork::bytes_needed(e) + 2 * ((e + 16 + 511) & ~(size_t)255) + 8 * (size_t)nb + 8192));
+  BwtWork w;
+  CJS_TRY(w.carve(arena, e));
+  uint8_t* d_T = arena.take<uint8_t>(e + 16);             // 16 bytes of slack behind the text and the output, as run_sub carves them
+  uint8_t* d_U = arena.take<uint8_t>(e + 16);
+  uint32_t* d_p = arena.take<uint32_t>(nb);
+  uint32_t* d_len = arena.take<uint32_t>(nb);
+  if (!d_T || !d_U || !d_p || !d_len) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemcpyAsync(d_T, blocks, e, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_len, len, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_TRY(bwt_run_var(s, w, d_T, nb, stride, d_len, d_U, d_p));
+  CJS_HIP_TRY(hipMemcpyAsync(out, d_U, e, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(pidx, d_p, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
 extern "C" int cjs_stage_rle1(const uint8_t* in, size_t n, int level, uint8_t* blocks, size_t blocks_cap,
                               uint32_t* block_len, uint32_t* block_crc, uint64_t* block_start, long cap_blocks, long* nblocks,
                               const cjs_opts* opts) {

@@ -610,6 +610,12 @@ int cjs_bzip2_shard_pack(cjs_ctx *ctx, int level, int rank, int world, const cjs
  * cjs_stage_bwt: cyclic!=0 -> BWT.bwtransform2 semantics (J/Bzip2_joined_.js:928-971, Q4),
  *                cyclic==0 -> BWT.bwtransform semantics (J/BWTC_joined_.js:1125-1145). */
 int cjs_stage_bwt(const uint8_t *in, size_t n, int block_len, int cyclic, uint8_t *out, int32_t *pidx, const cjs_opts *opts);
+/* The cyclic form over blocks of different lengths, the geometry of the batched compressor (one block per slot): blocks = nb slots
+ * of stride bytes, block k = the first len[k] bytes of slot k (what lies behind them in the slot is never looked at as text); out
+ * has the same layout and only out[k*stride .. k*stride + len[k]) is defined.  CJS_E_INVALID_ARG, before anything is launched,
+ * for nb == 0 or nb > 65535, a stride that is 0 or no multiple of 16, and any len[k] that is 0 or exceeds stride. */
+int cjs_stage_bwt_var(const uint8_t *blocks, uint32_t nb, uint32_t stride, const uint32_t *len, uint8_t *out, int32_t *pidx,
+                      const cjs_opts *opts);
 /* readBlock (J/Bzip2_joined_.js:1954-1985) for the whole stream: RLE1 bytes of all blocks,
  * concatenated with stride = level*100000-19; per block length / crc / input start */
 int cjs_stage_rle1(const uint8_t *in, size_t n, int level, uint8_t *blocks, size_t blocks_cap,

@@ -223,6 +223,10 @@ static void check_round_arithmetic() {
     if (!seg && k.nsym < 7) CHECK((k.nsym + 1) * (cyclic ? 8 : 9) + var + id_bits > 64, "nb %u: room for another symbol", nb);
     if (var) CHECK(var_geom_admits(k.nsym) == ((uint64_t)(BWT_MAX_STRIDE - 1) < (1ull << r1_hole_bit(k.nsym))), "nb %u: VarGeom admitted = %d with %d symbols", nb, (int)var_geom_admits(k.nsym), k.nsym);
   }
+  // the block counts at which the depth of round 1 over blocks of different lengths changes (tests/test_gpu_bwt_var.py runs a call
+  // on either side of both): 7 symbols up to 128 blocks, 6 up to 32768, 5 beyond
+  CHECK(round1_keys(128, true, false, true).nsym == 7 && round1_keys(129, true, false, true).nsym == 6, "VarGeom depth at 128 / 129 blocks");
+  CHECK(round1_keys(32768, true, false, true).nsym == 6 && round1_keys(32769, true, false, true).nsym == 5, "VarGeom depth at 32768 / 32769 blocks");
   // (no block count up to 70,000 leaves fewer than five symbols, so the refusal itself, symbol count by symbol count:)
   for (int nsym = 0; nsym <= 7; nsym++) CHECK(var_geom_admits(nsym) == ((uint64_t)(BWT_MAX_STRIDE - 1) < (1ull << r1_hole_bit(nsym))), "VarGeom with %d symbols", nsym);
   for (int b = 0; b <= 64; b++) for (int d = -1; d <= 1; d++) {

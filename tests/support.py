@@ -277,6 +277,7 @@ class HipLib(_StreamLib):
             "cjs_bzip2_decompress_block": [u8p, S, ctypes.c_uint64, PP, PS, V],
             "cjs_bzip2_table": [u8p, S, I, V, V, ctypes.c_long, V],
             "cjs_stage_bwt": [V, S, I, I, V, V, V],
+            "cjs_stage_bwt_var": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
             "cjs_stage_rle1": [V, S, I, V, S, V, V, V, ctypes.c_long, ctypes.POINTER(ctypes.c_long), V],
             "cjs_stage_mtf": [V, V, S, I, V, V, V, V, V],
             "cjs_stage_huff": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
@@ -394,6 +395,23 @@ class HipLib(_StreamLib):
         pidx = np.zeros(nb, dtype=np.int32)
         rc = self.L.cjs_stage_bwt(data.ctypes.data, data.size, block_len, 1 if cyclic else 0, U.ctypes.data, pidx.ctypes.data, None)
         return rc, U[: data.size], pidx
+
+    def stage_bwt_var(self, blocks, stride, hole_fill=0):
+        """the cyclic BWT of blocks of different lengths, block k in slot k of `stride` bytes (cjs_stage_bwt_var); the holes
+        behind the blocks are filled with `hole_fill`.  Returns (rc, [U_k, len(blocks[k]) bytes each], pidx)"""
+        blocks = [as_u8(b) for b in blocks]
+        nb = len(blocks)
+        lens = np.array([b.size for b in blocks], dtype=np.uint32)
+        slots = np.full((max(nb, 1), stride), hole_fill, dtype=np.uint8)
+        for k, b in enumerate(blocks):
+            slots[k, : min(b.size, stride)] = b[:stride]        # (a block longer than its slot: the entry point refuses the call)
+        U = np.zeros((max(nb, 1), stride), dtype=np.uint8)
+        pidx = np.zeros(max(nb, 1), dtype=np.int32)
+        keep = lens if nb else np.zeros(1, dtype=np.uint32)
+        rc = self.L.cjs_stage_bwt_var(slots.ctypes.data, nb, stride, keep.ctypes.data, U.ctypes.data, pidx.ctypes.data, None)
+        if rc:
+            return rc, None, None
+        return 0, [U[k, : blocks[k].size] for k in range(nb)], pidx[:nb]
 
     def stage_rle1(self, data, level):
         data = as_u8(data)

@@ -169,6 +169,28 @@ def test_tiny_inputs_share_one_pass():
     assert " 1 passes (10000 one-block inputs, 0 blocks of 0 inputs" in line, line
 
 
+# (the text inputs are slices of ONE generated text: the generator's start-up would cost 20,000 calls a quarter of a minute)
+_TINY_40000 = ("text = recipes.textgen(1 << 20, 5); "
+               "ins = [text[21 * k: 21 * k + int(n)].copy() if k % 2 else (rng.integers(0, 2, int(n)) + 48).astype(np.uint8) "
+               "for k, n in enumerate(rng.integers(1, 41, 40000))]")
+
+
+def test_more_than_32768_tiny_inputs_share_one_pass(oracle):
+    # 40,000 inputs of 1-40 bytes, text and 2-symbol bytes: one pass of 40,000 blocks, so the block id and the hole bit leave the
+    # suffix sort's round 1 five symbols of depth (more than 32768 blocks; tests/test_gpu_bwt_var.py has the stage on its own)
+    line = _passes(_PASS_SCRIPT % (_TINY_40000, 9))
+    assert " 1 passes (40000 one-block inputs, 0 blocks of 0 inputs" in line, line
+    scope = {"np": np, "recipes": recipes, "rng": np.random.default_rng(9)}
+    exec(_TINY_40000, scope)
+    ins = scope["ins"]
+    assert len(ins) == 40000 and min(d.size for d in ins) == 1 and max(d.size for d in ins) == 40
+    outs = _pkg().Bzip2.compressFiles(ins, 9)
+    assert len(outs) == len(ins)
+    for k, (d, o) in enumerate(zip(ins, outs)):
+        rc, want = oracle.bzip2_compress(d, 9)
+        assert rc == 0 and np.array_equal(o, want), "input %d (%d bytes)" % (k, d.size)
+
+
 def test_multi_block_inputs_are_batched():
     # 24 inputs of 150-400 kB at level 1 (100 kB blocks): their blocks share a few passes (length classes), not one pipeline per input
     line = _passes(_PASS_SCRIPT % ("ins = [recipes.textgen(int(n), k) for k, n in enumerate(rng.integers(150000, 400001, 24))]", 1))

@@ -17,9 +17,9 @@ import pytest
 
 import recipes
 import support
+from bwt_cases import DEEP as _DEEP, EQUAL_KEY_INPUTS, FALLBACK_INPUTS, PLANTED as _PLANTED, SHALLOW as _SHALLOW, WIN, groups_after_round1
 
 ROOT = support.ROOT
-WIN = 3072          # nominal range of a tile-sorter window (TS_NOM in bwt_rules.h): a window owns the groups that start in it
 
 
 def _check_bwt(hip, oracle, data, block_len, cyclic):
@@ -37,101 +37,15 @@ def _check_bwt(hip, oracle, data, block_len, cyclic):
             raise AssertionError("BWT bytes differ in block %d at %d positions, first %d (n=%d cyclic=%s)" % (k, bad.size, bad[0], blk.size, cyclic))
 
 
-# ---- planted groups at chosen places of the compacted array ---------------------------------------------------------------
-# Background and filling bytes are random in [0x40, 0x80): with 64^7 possible 7-grams next to nothing of it repeats, so round 1
-# (depth 7) resolves it.  A planted unit starts with a two-byte id (first byte below 0x40, second at or above 0x80) and occurs
-# m times: its occurrences are a group of m suffixes after round 1, the groups of all units come FIRST in the compacted array
-# (their first byte sorts below everything else) and in id order.  So the array that round 2 sorts starts with groups of exactly
-# the sizes planted, in the order planted, and a group's start slot is the sum of the sizes in front of it.  (The suffixes one
-# byte into a unit repeat six of its bytes, and the few that also agree in the byte behind form small groups of their own:
-# those start with a byte >= 0x40 and sort behind all planted groups.)  A size of 1 cannot be planted: a suffix alone in its
-# group is resolved and leaves the array; every case makes thousands of them as NEW groups.
-# The filler groups between the targets decide which tile sorter round 2 takes (radix_tile_sorter in bwt_rules.h: the LDS radix
-# sorter from 5 suffixes per group on, the counting / bitonic sorter below): fillers of 450 put the targets through
-# bwt_tile_sort_radix, fillers of 2 and 3 through bwt_tile_sort.  Those take more units than two id bytes number (64 * 128): a
-# third id byte, again at or above 0x80, keeps "first byte below 0x40, in id order".
-def _planted(sizes_and_offsets, unit_len, sep_len, seed, tiny_fillers=False):
-    """sizes_and_offsets: [(group size, offset of its first slot from a multiple of WIN)] -> (bytes, [(start slot, size)])"""
-    rng = np.random.default_rng(seed)
-    plan = []                      # sizes of all planted groups in array order
-    targets = []
-    at = 0
-
-    def fill(gap):
-        nonlocal at
-        if tiny_fillers and gap:
-            assert gap >= 2
-            while gap > 4:         # 2, 3, 2, 3, ... and a rest of 2, 3 or 2 + 2
-                m = 2 + (len(plan) & 1)
-                plan.append(m); gap -= m; at += m
-            for m in ((2, 2) if gap == 4 else (gap,)):
-                plan.append(m); at += m
-            return
-        while gap > 900:
-            plan.append(450); gap -= 450; at += 450
-        if gap:
-            assert gap >= 2
-            plan.append(gap); at += gap
-
-    for size, off in sizes_and_offsets:
-        want = (at // WIN + 1) * WIN + off
-        while want - at < 2 and want != at:
-            want += WIN
-        fill(want - at)
-        targets.append((at, size))
-        plan.append(size); at += size
-    fill(5)                        # the last target is not the end of the planted part
-    parts = []
-    for uid, m in enumerate(plan):
-        unit = rng.integers(0x40, 0x80, unit_len, dtype=np.uint8)
-        if tiny_fillers:
-            unit[0] = uid >> 14; unit[1] = 0x80 | ((uid >> 7) & 127); unit[2] = 0x80 | (uid & 127)
-            assert uid < 64 * 128 * 128
-        else:
-            unit[0] = uid >> 7; unit[1] = 0x80 | (uid & 127)
-            assert uid < 64 * 128
-        occ = rng.integers(0x40, 0x80, (m, unit_len + sep_len), dtype=np.uint8)
-        occ[:, :unit_len] = unit
-        parts.append(occ.reshape(-1))
-    data = np.concatenate(parts)
-    # occurrences of one unit stand apart: shuffle all occurrences (same length each) so that no unit is periodic in the text
-    occs = data.reshape(-1, unit_len + sep_len)
-    data = occs[rng.permutation(occs.shape[0])].reshape(-1)
-    return np.ascontiguousarray(data), targets
-
-
-_SIZES = (2, 64, 65, 1023, 1024, 1025)
-_SHALLOW = [(s, o) for s in _SIZES for o in (-1, 0, 1)]        # unit of 7 bytes: the groups split into singletons in round 2
-_DEEP = [(s, o) for s in (65, 1024, 1025) for o in (-1, 0, 1)]  # unit of 15 bytes: they pass round 2 whole (1025: deferred twice) and split in round 3
-_PLANTED = {
-    "shallow": lambda: _planted(_SHALLOW, 7, 5, 101),
-    "deep": lambda: _planted(_DEEP, 15, 4, 102),
-    "tiny": lambda: _planted(_SHALLOW, 7, 5, 103, tiny_fillers=True),      # the shallow targets among fillers of 2 and 3
-}
-
-
-def _groups_after_round1(data):
-    """(start slot, size) of the groups of the compacted array after a depth-7 cyclic round, in array order"""
-    n = data.size
-    ext = np.concatenate([data, data[:7]]).astype(np.uint64)
-    key = np.zeros(n, dtype=np.uint64)
-    for j in range(7):
-        key = (key << np.uint64(8)) | ext[j:j + n]
-    key.sort()
-    starts = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
-    sizes = np.diff(np.concatenate([starts, [n]]))
-    sizes = sizes[sizes > 1]
-    return list(zip((np.cumsum(sizes) - sizes).tolist(), sizes.tolist()))
-
-
+# ---- planted groups at chosen places of the compacted array: the construction is bwt_cases.planted -------------------------
 @pytest.mark.parametrize("which", ["shallow", "deep", "tiny"])
 def test_planted_inputs_put_the_groups_where_they_say(which):
-    """no GPU: the construction above really puts groups of the listed sizes on the slots just before, on and just behind
+    """no GPU: the construction (bwt_cases.planted) really puts groups of the listed sizes on the slots just before, on and just behind
     multiples of the window's nominal range, and round 2 takes the tile sorter that the fillers are meant to choose: A
     (unresolved suffixes) and ngroups as the host reads them behind round 1 of the cyclic form"""
     data, targets = _PLANTED[which]()
     assert data.size <= 1000000
-    groups = _groups_after_round1(data)
+    groups = groups_after_round1([data], 7)
     have = set(groups)
     for start, size in targets:
         assert (start, size) in have, (start, size)
@@ -151,22 +65,7 @@ def test_groups_on_window_borders(hip, oracle, which, cyclic):
     _check_bwt(hip, oracle, data, data.size, cyclic)
 
 
-# ---- equal rank keys inside a group ----------------------------------------------------------------------------------------
-def _pages(page_len, copies, seed):
-    """a page repeated `copies` times, each copy followed by one byte of its own: the suffixes at one page offset form a group
-    whose members carry EQUAL rank keys round after round (the next difference is up to page_len bytes away), so they must stay
-    one group with one new head; 40 copies take the counting path of the tile sorter, 70 and 300 the bitonic / radix paths"""
-    page = recipes.textgen(page_len, seed)
-    return np.concatenate([np.concatenate([page, np.array([48 + i % 200], dtype=np.uint8)]) for i in range(copies)])
-
-
-EQUAL_KEY_INPUTS = {
-    "pages_40x5000": lambda: _pages(5000, 40, 21),
-    "pages_70x5000": lambda: _pages(5000, 70, 22),
-    "pages_300x1500": lambda: _pages(1500, 300, 23),
-}
-
-
+# ---- equal rank keys inside a group (bwt_cases.pages) ----------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("cyclic", [True, False], ids=["cyclic", "sentinel"])
 @pytest.mark.parametrize("name", sorted(EQUAL_KEY_INPUTS))
@@ -175,27 +74,7 @@ def test_equal_rank_keys_stay_one_group(hip, oracle, name, cyclic):
     _check_bwt(hip, oracle, data, data.size, cyclic)
 
 
-# ---- groups of more than 1024 suffixes in rounds > 2, and the whole-array fallbacks -------------------------------------------
-FALLBACK_INPUTS = {
-    # periodic stretches inside text with periods that are no powers of two: groups of ~16,000 and ~28,000 suffixes that go
-    # through compact -> radix passes -> bwt_defer_scatter for a dozen rounds, with text groups in the tile sorters beside them
-    "text_plus_period12": lambda: (recipes.build({"kind": "concat", "parts": [
-        {"kind": "textgen", "n": 500000, "seed": 31}, {"kind": "repeat", "unit_hex": "6162636465666768696a6b6c", "n": 200000},
-        {"kind": "textgen", "n": 99981, "seed": 32}]}), 799981),
-    "text_plus_period7": lambda: (recipes.build({"kind": "concat", "parts": [
-        {"kind": "textgen", "n": 300000, "seed": 33}, {"kind": "repeat", "unit_hex": "71727374757677", "n": 200003},
-        {"kind": "textgen", "n": 50000, "seed": 34}]}), 550003),
-    # more than half of the workspace deferred: the whole array is sorted by keys that are gathered again (bwt_key_flags)
-    "zeros_900k": lambda: (np.zeros(900000, dtype=np.uint8), 900000),
-    "period2_900k": lambda: (recipes.build({"kind": "repeat", "unit_hex": "6162", "n": 900000}), 900000),
-    # fewer than 8192 unresolved suffixes from the start, or falling below that on the way: whole-array radix passes
-    "repeats_5k": lambda: (np.tile(recipes.textgen(1700, 41), 3)[:5000].copy(), 5000),
-    "repeats_7k": lambda: (np.tile(recipes.textgen(900, 42), 8)[:7000].copy(), 7000),
-    "repeats_9k": lambda: (np.tile(recipes.textgen(2900, 43), 4)[:9000].copy(), 9000),
-    "repeats_9k_two_blocks": lambda: (np.tile(recipes.textgen(2100, 44), 9)[:18000].copy(), 9000),
-}
-
-
+# ---- groups of more than 1024 suffixes in rounds > 2, and the whole-array fallbacks (bwt_cases.FALLBACK_INPUTS) -----------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("cyclic", [True, False], ids=["cyclic", "sentinel"])
 @pytest.mark.parametrize("name", sorted(FALLBACK_INPUTS))

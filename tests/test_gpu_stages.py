@@ -32,6 +32,10 @@ BWT_INPUTS = {
     "abab": (np.frombuffer(b"abababababab", dtype=np.uint8), 12),
     "mary": (np.frombuffer(b"Mary had a little lamb, its fleece was white as snow" * 8 + b"Nary had a little lamb, its fleece was white as snow", dtype=np.uint8), 1000),
     "zeros_5000": (np.zeros(5000, dtype=np.uint8), 5000),
+    # several EQUAL blocks inside one 4096-slot tile of the regroup kernels: only the slot number tells their rotations apart
+    "zeros_8_by_4": (np.zeros(8, dtype=np.uint8), 4),
+    "zeros_3000_by_1000": (np.zeros(3000, dtype=np.uint8), 1000),
+    "abab_3_by_4": (np.frombuffer(b"abababababab", dtype=np.uint8), 4),
     "zeros_3blocks": (np.zeros(10000, dtype=np.uint8), 4096),
     "ab_10000": (recipes.build({"kind": "repeat", "unit_hex": "6162", "n": 10000}), 10000),
     "abc_period3": (recipes.build({"kind": "repeat", "unit_hex": "616263", "n": 30000}), 30000),
