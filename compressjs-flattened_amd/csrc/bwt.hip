@@ -26,8 +26,11 @@
 // larger groups are deferred: compacted, radix-sorted apart, scattered back.  Whole-array fallbacks (radix passes over keys that
 // bwt_gather_keys writes): fewer than 8192 unresolved suffixes, or more than half of the workspace deferred.
 // Every round ends in a regroup: new ranks into R, resolved suffixes out (cyclic: their BWT byte straight into the output;
-// sentinel: into SA), survivors compacted.  The host reads the survivor and group counts behind the tile scan and queues the
-// next round.  Cyclic blocks with h >= the block length hold only equal rotations: bwt_flush_active emits them as they stand.
+// sentinel: into SA), survivors compacted, each with one head byte (ghead[]: 1 = starts a group of the new grouping).  That byte is
+// all the next sort is told about the groups: the tile sorters lay the bytes over their mask words, the deferral kernels number the
+// groups they get from the head bit that the sorters leave in the keys, and bwt_gather_keys counts group ordinals out of the bytes.
+// The host reads the survivor and group counts behind the tile scan and queues the next round.  Cyclic blocks with h >= the block
+// length hold only equal rotations: bwt_flush_active emits them as they stand.
 //
 // Launches of one round, in order ([..]: only when the condition holds):
 //   sort, round 1    [fallback: bwt_init_keys]  radix passes (rs_hist | rs_hist_bytes, rs_scan_*, rs_scatter per digit)
@@ -35,7 +38,7 @@
 //   sort, round >= 2 [large groups possible: dev_fill dflag]  bwt_tile_sort | bwt_tile_sort_radix
 //                    [large groups possible: bwt_defer_count, scan_u32_single x 2, HOST WAIT; if any:
 //                     bwt_defer_gather, radix passes, bwt_defer_scatter | over half deferred: bwt_gather_keys, whole-array sort]
-//     whole array:   radix passes, bwt_key_flags
+//     whole array:   radix passes, bwt_key_flags   (keys: [more than two tiles: bwt_head_counts, bwt_head_scan] bwt_gather_keys)
 //   regroup          bwt_flags (round 1) | bwt_flags_bytes -> bwt_scan_tiles -> event -> bwt_apply
 //                    round 1, packed, >= 8 blocks: bwt_apply sweep 1 -> bwt_scan_tiles -> event -> bwt_apply sweep 2
 //   HOST WAIT on the event; then [equal rotations only: bwt_flush_active, done]  [next round whole-array: bwt_gather_keys]
@@ -52,8 +55,8 @@ size_t BwtWork::bytes_needed(size_t cap) {
   const size_t T = RadixWork::hist_tiles_for(cap);
   size_t b = 0;
   auto add = [&](size_t n) { b += (n + 255) & ~(size_t)255; };
-  add(cap * 8); add(cap * 8); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4);  // key x2, val x2, pos x2, gord
-  add(cap * 4); add(cap * 4); add(cap); add(cap);  // R, SA, dflag, hflag
+  add(cap * 8); add(cap * 8); add(cap * 4); add(cap * 4); add(cap * 4); add(cap * 4);  // key x2, val x2, pos x2
+  add(cap * 4); add(cap * 4); add(cap); add(cap); add(cap);  // R, SA, dflag, hflag, ghead
   add(RadixWork::hist_words(T) * 4); add(256 * RadixWork::segs_for(cap) * 4); add(3 * T * 4); add(64);
   return b + 4096;
 }
@@ -63,8 +66,7 @@ int BwtWork::carve(Arena& a, size_t cap_) {
   key[0] = a.take<uint64_t>(cap); key[1] = a.take<uint64_t>(cap);
   val[0] = a.take<uint32_t>(cap); val[1] = a.take<uint32_t>(cap);
   pos[0] = a.take<uint32_t>(cap); pos[1] = a.take<uint32_t>(cap);
-  gord = a.take<uint32_t>(cap);
-  R = a.take<uint32_t>(cap); SA = a.take<uint32_t>(cap); dflag = a.take<uint8_t>(cap); hflag = a.take<uint8_t>(cap);
+  R = a.take<uint32_t>(cap); SA = a.take<uint32_t>(cap); dflag = a.take<uint8_t>(cap); hflag = a.take<uint8_t>(cap); ghead = a.take<uint8_t>(cap);
   CJS_TRY(rs.carve(a, T, RadixWork::segs_for(cap)));
   tile_cnt = a.take<uint32_t>(3 * T); counters = a.take<uint32_t>(16);
   if (!counters) return CJS_E_OUT_OF_MEMORY;
@@ -125,7 +127,7 @@ static int sort_round(hipStream_t s, BwtWork& w, Round& r, LaunchTimes* lt, cons
   if (env_debug()) fprintf(stderr, "[cjs bwt]   tile sort: %u of %u suffixes in groups > %u\n", D, A, TS_MAXGRP);
   if (D == 0) { r.no_large_groups = true; return 0; }
   if (deferred_overflow(D, w.cap)) {       // no room to sort them apart: the whole array by its keys (the sorted slots hold none: gathered again)
-    launch_gather_keys(s, tg, A, w.val[c], w.key[c]);
+    launch_gather_keys(s, tg, A, w.val[c], w.key[c], w.tile_cnt);      // (tcount is dead behind the host wait)
     return sort_round_whole(s, w, r, lt);
   }
   CJS_TRY(sort_deferred(s, w, r, D, w.h_counters[CN_DEFERRED_GROUPS], tcount, hcount, lt));
@@ -136,8 +138,8 @@ static int sort_round(hipStream_t s, BwtWork& w, Round& r, LaunchTimes* lt, cons
 // Behind a regroup: the keys of the next sort, its depth and its key bits
 template <typename G>
 static void prepare_next(hipStream_t s, BwtWork& w, const G& g, bool cyclic, Round& r, TsGatherT<G>& tg) {
-  tg = TsGatherT<G>{w.R, w.pos[r.pc], w.gord, r.h, (int)cyclic, g};
-  if (!tile_sorted_round(r.A)) launch_gather_keys(s, tg, r.A, w.val[r.c], w.key[r.c]);      // (else the tile sorters fetch the ranks themselves)
+  tg = TsGatherT<G>{w.R, w.pos[r.pc], w.ghead, r.h, (int)cyclic, g};
+  if (!tile_sorted_round(r.A)) launch_gather_keys(s, tg, r.A, w.val[r.c], w.key[r.c], w.tile_cnt);      // (else the tile sorters fetch the ranks themselves)
   r.h = next_depth(r.h);
   r.bits = round_key_bits(r.ngroups);
 }

@@ -18,9 +18,9 @@ __global__ __launch_bounds__(1024) void scan_u32_single(uint32_t* __restrict__ a
   if (threadIdx.x == 0) { *total = carry; *host_total = carry; }
 }
 // Groups too large for the tile sorters (dflag = 1 on all their slots) are compacted, sorted by the global radix passes and
-// put back.  Their group ordinals take ~23 bits of the sort key; numbered densely among themselves (there are at most
-// A / 1025 of them) they take ~11, which saves two of the six passes: a slot starts a deferred group when the slot in front of
-// it is not deferred or carries another ordinal.  Per 2048-slot tile: deferred slots -> tcount, deferred group heads -> hcount.
+// put back.  Numbered densely among themselves (there are at most A / 1025 of them) their ordinals take ~11 bits of the sort
+// key: a deferred slot starts a deferred group when its key carries the head bit (the tile sorters store head bit | rank key for
+// the slots they do not own; a group is deferred whole).  Per 2048-slot tile: deferred slots -> tcount, deferred heads -> hcount.
 __device__ __forceinline__ void defer_flags(uint32_t A, const uint8_t* __restrict__ dflag, const uint64_t* __restrict__ key, uint64_t a0,
                                             uint32_t& f, uint32_t& heads, uint64_t (&k8)[8]) {
   f = 0; heads = 0;
@@ -33,15 +33,9 @@ __device__ __forceinline__ void defer_flags(uint32_t A, const uint8_t* __restric
   if (!f) return;
 #pragma unroll
   for (int j = 0; j < 8; j++) k8[j] = a0 + j < A ? key[a0 + j] : 0ull;
-  const bool pf = a0 && dflag[a0 - 1];
-  uint64_t prev = pf ? round_key_ordinal(key[a0 - 1]) : ~0ull;
-  bool prev_def = pf;
 #pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const bool d = (f >> j) & 1u;
-    if (d && (!prev_def || prev != round_key_ordinal(k8[j]))) heads |= 1u << j;
-    prev_def = d; prev = round_key_ordinal(k8[j]);
-  }
+  for (int j = 0; j < 8; j++) heads |= (uint32_t)(round_key_ordinal(k8[j]) & 1ull) << j;      // (slots that are not deferred hold stale keys)
+  heads &= f;
 }
 __global__ __launch_bounds__(256) void bwt_defer_count(uint32_t A, const uint8_t* __restrict__ dflag, const uint64_t* __restrict__ key,
                                                        uint32_t* __restrict__ tcount, uint32_t* __restrict__ hcount) {

@@ -1,6 +1,6 @@
 // bwt_dev.hpp — device-side pieces that more than one of the suffix sort's kernel files share (bwt_round1.hip, bwt_tile_sort.hip,
-// bwt_defer.hip, bwt_regroup.hip; the map is in bwt.hip): the block geometries, the arguments of the fused rank gather, the flag
-// bytes as 16-slot masks, and two wave-wide searches for a group head.  The rules themselves are in bwt_rules.h.
+// bwt_defer.hip, bwt_regroup.hip; the map is in bwt.hip): the block geometries, the block of a sorted position without a division,
+// the flag and head bytes as 16-slot masks, and two wave-wide searches for a group head.  The rules themselves are in bwt_rules.h.
 #pragma once
 #include "bwt_parts.h"      // (and radix.hpp, prims.hpp, bwt_rules.h through it)
 #include <type_traits>
@@ -9,6 +9,13 @@ namespace cjs {
 
 __device__ __forceinline__ uint32_t blk_len(const Geom& g, uint32_t blk) { return blk == g.nb - 1 ? g.n_last : g.stride; }
 __device__ __forceinline__ uint32_t blk_len(const VarGeom& g, uint32_t blk) { return g.len[blk]; }
+
+// Block of sorted position p without a division: pos[] ascends along the array, so a thread divides once, for its first slot, and
+// steps from the block `prev` of a position at or below p (the same block or the next one; a tail round's window may span more)
+__device__ __forceinline__ uint32_t blk_step(uint32_t p, uint32_t stride, uint32_t prev) {
+  const uint32_t off = p - prev * stride;
+  return off < stride ? prev : off - stride < stride ? prev + 1u : p / stride;
+}
 
 // bit `bit` of each of the 16 flag bytes in v -> 16-bit mask (byte j -> bit j)
 __device__ __forceinline__ uint32_t hf_bits16(const uint4& v, int bit) {

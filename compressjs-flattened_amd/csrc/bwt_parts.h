@@ -36,7 +36,7 @@ struct Round {
 };
 
 // Arguments of the fused rank gather of the tile sorters (bwt_tile_sort.hip)
-template <typename G> struct TsGatherT { const uint32_t* R; const uint32_t* pos; const uint32_t* gord; uint32_t h; int cyclic; G g; };
+template <typename G> struct TsGatherT { const uint32_t* R; const uint32_t* pos; const uint8_t* ghead; uint32_t h; int cyclic; G g; };
 
 // Every function below is instantiated for G = Geom and VarGeom (TG = TsGatherT of them) and queues its launches on s.
 // bwt_round1.hip: the sort of round 1 ([bwt_init_keys] radix passes [bwt_phase2_records, radix passes]); flips r.c as the passes do
@@ -50,7 +50,8 @@ void launch_defer_count(hipStream_t s, uint32_t A, const uint8_t* dflag, const u
 int sort_deferred(hipStream_t s, BwtWork& w, const Round& r, uint32_t D, uint32_t ndg, const uint32_t* tcount, const uint32_t* hcount, LaunchTimes* lt);
 // bwt_regroup.hip.  regroup: per-tile counts, their scan (w.ev_scan behind it is what the host waits for), then bwt_apply
 template <typename G> int regroup(hipStream_t s, BwtWork& w, const G& g, const Plan& p, const Round& r);
-template <typename G> void launch_gather_keys(hipStream_t s, const TsGatherT<G>& tg, uint32_t A, const uint32_t* val, uint64_t* key);
+// (the keys' group ordinals are counted from the head bytes: tile_cnt takes the per-tile sums when A spans more than two tiles)
+template <typename G> void launch_gather_keys(hipStream_t s, const TsGatherT<G>& tg, uint32_t A, const uint32_t* val, uint64_t* key, uint32_t* tile_cnt);
 void launch_key_flags(hipStream_t s, const uint64_t* key, uint32_t A, uint8_t* hflag);
 template <typename G> void launch_flush_active(hipStream_t s, const BwtWork& w, const G& g, const Plan& p, const Round& r);
 template <typename G> void launch_finish(hipStream_t s, const BwtWork& w, const G& g, bool cyclic, bool leftover, uint32_t M, const uint8_t* d_T, uint8_t* d_U, uint32_t* d_pidx);      // bwt_pidx, [sentinel: bwt_emit_sentinel]

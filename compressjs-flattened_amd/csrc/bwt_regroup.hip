@@ -14,27 +14,69 @@ namespace cjs {
 // in round 2) and is not kept.
 struct HalfMap { uint32_t halves, stride; };      // halves 2: the two sweeps are the launches SWEEP 1 and SWEEP 2 of bwt_apply
 
-// keys of a round >= 2 for the whole-array sorts: (group ordinal, rank of suffix i+h)
+// Heads per 4096-slot tile of the head bytes, and their exclusive sums in place: the group ordinals of bwt_gather_keys when the
+// array spans more than two tiles (the overflow fallback; rare, not tuned)
+__global__ __launch_bounds__(256) void bwt_head_counts(const uint8_t* __restrict__ ghead, uint32_t A, uint32_t* __restrict__ tsum) {
+  __shared__ uint32_t sm[4];
+  const uint64_t base = (uint64_t)blockIdx.x * RS_TILE;
+  const uint32_t nvalid = (uint32_t)((uint64_t)A - base < RS_TILE ? (uint64_t)A - base : RS_TILE);
+  uint32_t valid;
+  const uint4 v = hf_load16(ghead, base, nvalid, threadIdx.x, valid);
+  const uint32_t n = block_sum<256>((uint32_t)__popc(hf_bits16(v, 0) & valid), sm);
+  if (threadIdx.x == 0) tsum[blockIdx.x] = n;
+}
+__global__ __launch_bounds__(1024) void bwt_head_scan(uint32_t* __restrict__ tsum, uint32_t T) {
+  __shared__ uint32_t sm[16];
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < T; base += 1024) {
+    const uint32_t i = base + threadIdx.x;
+    uint32_t tot;
+    const uint32_t ex = block_excl_sum<1024>(i < T ? tsum[i] : 0u, sm, tot);
+    if (i < T) tsum[i] = carry + ex;
+    carry += tot;
+  }
+}
+// keys of a round >= 2 for the whole-array sorts: (group ordinal, rank of suffix i+h).  The ordinal of a slot is the number of
+// heads up to and including it, less one: heads in front of the tile from tsum, or (tsum null, at most two tiles: the small
+// rounds) counted by the workgroup itself; inside the tile from the head bytes as 64 mask words.
 template <typename G>
 __global__ __launch_bounds__(256) void bwt_gather_keys(G g, int cyclic, uint32_t A, uint32_t h, const uint32_t* __restrict__ R,
                                                        const uint32_t* __restrict__ val, const uint32_t* __restrict__ pos,
-                                                       const uint32_t* __restrict__ gord, uint64_t* __restrict__ key, uint32_t T) {
+                                                       const uint8_t* __restrict__ ghead, const uint32_t* __restrict__ tsum, uint64_t* __restrict__ key, uint32_t T) {
+  __shared__ uint64_t m_h[64];
+  __shared__ uint32_t wp_h[64];
+  __shared__ uint32_t sm[4];
   const uint32_t tile = xcd_tile(blockIdx.x, T);
   if (tile >= T) return;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const uint64_t base = (uint64_t)tile * RS_TILE;
   const uint32_t nvalid = (uint32_t)((uint64_t)A - base < RS_TILE ? (uint64_t)A - base : RS_TILE);
   // three batches of sixteen independent loads each (streams, then the rank gathers, then the stores): as one loop the
   // compiler waits for every gather before it issues the next
-  uint32_t p16[16], v16[16], g16[16], kk[16];
+  uint32_t p16[16], v16[16], kk[16];
+  uint32_t hvalid;
+  const uint4 hv = hf_load16(ghead, base, nvalid, tid, hvalid);
 #pragma unroll
   for (int it = 0; it < 16; it++) {
     const uint32_t e = (uint32_t)it * 256 + threadIdx.x;
     const uint64_t a = base + (e < nvalid ? e : nvalid - 1u);
-    p16[it] = __builtin_nontemporal_load(pos + a); v16[it] = __builtin_nontemporal_load(val + a); g16[it] = __builtin_nontemporal_load(gord + a);
+    p16[it] = __builtin_nontemporal_load(pos + a); v16[it] = __builtin_nontemporal_load(val + a);
   }
+  uint32_t obase = tsum ? tsum[tile] : 0u;      // heads in front of the tile
+  if (!tsum) for (uint32_t t = 0; t < tile; t++) {
+    uint32_t pvalid;
+    const uint4 pvv = hf_load16(ghead, (uint64_t)t * RS_TILE, RS_TILE, tid, pvalid);
+    obase += block_sum<256>((uint32_t)__popc(hf_bits16(pvv, 0)), sm);
+  }
+  reinterpret_cast<uint16_t*>(m_h)[tid] = (uint16_t)(hf_bits16(hv, 0) & hvalid);
+  __syncthreads();
+  if (w == 0) { const uint32_t n = (uint32_t)__popcll(m_h[lane]); wp_h[lane] = wave_incl_sum(n) - n; }
+  __syncthreads();
+  uint32_t blk = p16[0] / g.stride;             // (pos[] ascends along the array: blk_step)
 #pragma unroll
   for (int it = 0; it < 16; it++) {
-    const uint32_t blk = p16[it] / g.stride, n = blk_len(g, blk);
+    blk = blk_step(p16[it], g.stride, blk);
+    const uint32_t n = blk_len(g, blk);
     uint32_t j = pk_pos(v16[it]) + h;// (both below 2^31; the top byte of val[] may carry the byte in front of the suffix)
     if (cyclic) { if (j >= n) j %= n; }
     const bool past = !cyclic && j >= n;
@@ -44,7 +86,9 @@ __global__ __launch_bounds__(256) void bwt_gather_keys(G g, int cyclic, uint32_t
 #pragma unroll
   for (int it = 0; it < 16; it++) {
     const uint32_t e = (uint32_t)it * 256 + threadIdx.x;
-    if (e < nvalid) __builtin_nontemporal_store(round_key(g16[it], kk[it]), key + base + e);
+    const int wi = it * 4 + w;                  // slot e = 64 * wi + lane
+    const uint32_t ord = obase + wp_h[wi] + (uint32_t)__popcll(m_h[wi] & mask_le(lane)) - 1u;      // (slot 0 of the array is a head)
+    if (e < nvalid) __builtin_nontemporal_store(round_key(ord, kk[it]), key + base + e);
   }
 }
 
@@ -192,12 +236,12 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
                                                  const uint32_t* __restrict__ pos, uint32_t A, G g,
                                                  uint32_t* tile_cnt, uint32_t T,
                                                  uint32_t* __restrict__ R, uint32_t* __restrict__ SA,
-                                                 uint32_t* __restrict__ nval, uint32_t* __restrict__ npos, uint32_t* __restrict__ ngord, HalfMap hm_,
+                                                 uint32_t* __restrict__ nval, uint32_t* __restrict__ npos, uint8_t* __restrict__ nhead /* per survivor: 1 = starts a group */, HalfMap hm_,
                                                  const uint8_t* __restrict__ Tx, uint8_t* __restrict__ U, uint32_t* __restrict__ big_flag,
                                                  int gs1 /* FIRST: group key = key >> gs1 */, int carried /* the byte in front of a suffix rides in its record / val */) {
   __shared__ uint64_t sk[FIRST ? RS_TILE + 2 : 1];        // rounds >= 2 stage no keys: 4 KB of LDS instead of 36
   __shared__ uint64_t m_nh[64], m_sg[64], m_oh[64];
-  __shared__ uint32_t wp_s[64], wp_h[64], wp_head[64];
+  __shared__ uint32_t wp_s[64], wp_head[64];
   __shared__ uint32_t carry_s, nx_s;
   const uint32_t tile = xcd_tile(blockIdx.x, T), half = SWEEP == 2 ? 1u : 0u;
   if (tile >= T) return;
@@ -206,8 +250,8 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
   const uint64_t base = (uint64_t)tile * RS_TILE;
   const uint32_t nvalid = (uint32_t)((uint64_t)A - base < RS_TILE ? (uint64_t)A - base : RS_TILE);
   // every streaming load of the tile is issued up front (one loop of load + LDS store makes the compiler wait per load)
-  uint32_t sbase = 0, hbase = 0, carry = 0;
-  if (SWEEP != 1) { sbase = tile_cnt[tile]; hbase = tile_cnt[T + tile]; carry = tile_cnt[2 * (size_t)T + tile]; }
+  uint32_t sbase = 0, carry = 0;
+  if (SWEEP != 1) { sbase = tile_cnt[tile]; carry = tile_cnt[2 * (size_t)T + tile]; }
   else if (w == 0) {
     const uint64_t seg0 = (uint64_t)((uint32_t)base / g.stride) * g.stride;     // (round 1: slot = sorted position)
     const uint32_t c = (uint32_t)class_head_before(key, seg0, base, gs1, lane) + 1u;
@@ -283,7 +327,7 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
     const uint32_t is = wave_incl_sum(sv), ih = wave_incl_sum(hd);
     uint32_t im;
     const uint32_t em = last_head_before_word(mh, lane, im);
-    wp_s[lane] = is - sv; wp_h[lane] = ih - hd; wp_head[lane] = em;
+    wp_s[lane] = is - sv; wp_head[lane] = em;
     if (SWEEP == 1 && lane == 63) store_tile_counts(tile_cnt, T, tile, is, ih, im ? (uint32_t)base + im : 0u);      // what bwt_flags counts
     if (SWEEP == 1) {                        // (and its large-group test: eight words to a run)
       const uint64_t nz = __ballot(mh != 0);
@@ -298,17 +342,20 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
 #pragma unroll
   for (int it = 0; it < 16; it++) ub[it] = 0u;
   const bool emits = U != nullptr && SWEEP != 1;
+  const uint32_t blk0 = (FIRST ? (uint32_t)base + (uint32_t)tid : p16[0]) / g.stride;      // the thread's sorted positions ascend with `it`: blk_step
   if (emits && !carried) {
+    uint32_t blk = blk0;
 #pragma unroll
     for (int it = 0; it < 16; it++) {
       const uint32_t e = (uint32_t)it * 256u + tid;
       const bool sing = e < nvalid && ((m_sg[it * 4 + w] >> lane) & 1ull);
       const uint32_t p = FIRST ? (uint32_t)(base + e) : p16[FIRST ? 0 : it];
       const uint32_t vv = pk_pos(PACKED ? (uint32_t)sk[e + 1] : v16[PACKED ? 0 : it]);
-      const uint32_t blk = p / g.stride;
+      blk = blk_step(p, g.stride, blk);
       ub[it] = sing ? (uint32_t)Tx[(size_t)blk * g.stride + (vv ? vv - 1u : blk_len(g, blk) - 1u)] : 0u;
     }
   }
+  uint32_t blk = blk0;
 #pragma unroll
   for (int it = 0; it < 16; it++) {
     const uint32_t e = (uint32_t)it * 256u + tid;
@@ -331,7 +378,7 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
       const uint32_t vraw = PACKED ? (uint32_t)sk[e + 1] : v16[PACKED ? 0 : it];
       const uint32_t vv = pk_pos(vraw);                          // the suffix (positions are below 2^20)
       const uint32_t pb = PACKED ? pk2_prev(vraw) : val_prev(vraw);      // its carried byte, if any
-      const uint32_t blk = p / g.stride;
+      blk = blk_step(p, g.stride, blk);
       const uint32_t head_pos = p - ((uint32_t)a - head_a);
       if (!keeps_rank && (SWEEP == 0 || (uint32_t)(vv >= hsplit) == half)) R[(size_t)blk * g.stride + vv] = head_pos - blk * g.stride;
       if (SWEEP == 1) continue;
@@ -343,8 +390,8 @@ __global__ __launch_bounds__(256) void bwt_apply(const uint64_t* __restrict__ ke
         else __builtin_nontemporal_store(vv, SA + p);
       } else {
         const uint32_t so = sbase + wp_s[wi] + (uint32_t)__popcll(~ms & lt);
-        const uint32_t ho = hbase + wp_h[wi] + (uint32_t)__popcll(mh & ~ms & le);
-        __builtin_nontemporal_store(carried ? val_carrying(vv, pb) : vv, nval + so); __builtin_nontemporal_store(p, npos + so); __builtin_nontemporal_store(ho - 1u, ngord + so);
+        __builtin_nontemporal_store(carried ? val_carrying(vv, pb) : vv, nval + so); __builtin_nontemporal_store(p, npos + so);
+        nhead[so] = (uint8_t)((mh >> lane) & 1ull);      // a surviving head starts a group among the survivors (its group survives whole)
       }
     }
   }
@@ -403,7 +450,7 @@ __global__ __launch_bounds__(256) void bwt_emit_sentinel(const uint8_t* __restri
 template <bool FIRST, bool PACKED, int SWEEP, typename G>
 static void launch_apply(hipStream_t s, BwtWork& w, const G& g, const Plan& p, const Round& r, uint32_t T) {
   hipLaunchKernelGGL((bwt_apply<FIRST, PACKED, SWEEP, G>), dim3(xcd_grid(T)), dim3(256), 0, s, FIRST ? w.key[r.c] : nullptr, FIRST ? nullptr : w.hflag,
-                     w.val[r.c], w.pos[r.pc], r.A, g, w.tile_cnt, T, w.R, w.SA, w.val[1 - r.c], w.pos[1 - r.pc], w.gord, HalfMap{SWEEP ? 2u : 1u, g.stride},
+                     w.val[r.c], w.pos[r.pc], r.A, g, w.tile_cnt, T, w.R, w.SA, w.val[1 - r.c], w.pos[1 - r.pc], w.ghead, HalfMap{SWEEP ? 2u : 1u, g.stride},
                      p.Tx, p.U, w.counters + CN_LARGE_GROUP, p.gs1, p.carried);
 }
 template <typename G>
@@ -425,12 +472,17 @@ template int regroup<Geom>(hipStream_t, BwtWork&, const Geom&, const Plan&, cons
 template int regroup<VarGeom>(hipStream_t, BwtWork&, const VarGeom&, const Plan&, const Round&);
 
 template <typename G>
-void launch_gather_keys(hipStream_t s, const TsGatherT<G>& tg, uint32_t A, const uint32_t* val, uint64_t* key) {
+void launch_gather_keys(hipStream_t s, const TsGatherT<G>& tg, uint32_t A, const uint32_t* val, uint64_t* key, uint32_t* tile_cnt) {
   const uint32_t T = (A + RS_TILE - 1) / RS_TILE;
-  hipLaunchKernelGGL(bwt_gather_keys<G>, dim3(xcd_grid(T)), dim3(256), 0, s, tg.g, tg.cyclic, A, tg.h, tg.R, val, tg.pos, tg.gord, key, T);
+  uint32_t* tsum = T > 2 ? tile_cnt : nullptr;      // up to two tiles (every round below tile_sorted_round): the workgroups count for themselves
+  if (tsum) {
+    hipLaunchKernelGGL(bwt_head_counts, dim3(T), dim3(256), 0, s, tg.ghead, A, tsum);
+    hipLaunchKernelGGL(bwt_head_scan, dim3(1), dim3(1024), 0, s, tsum, T);
+  }
+  hipLaunchKernelGGL(bwt_gather_keys<G>, dim3(xcd_grid(T)), dim3(256), 0, s, tg.g, tg.cyclic, A, tg.h, tg.R, val, tg.pos, tg.ghead, tsum, key, T);
 }
-template void launch_gather_keys<Geom>(hipStream_t, const TsGatherT<Geom>&, uint32_t, const uint32_t*, uint64_t*);
-template void launch_gather_keys<VarGeom>(hipStream_t, const TsGatherT<VarGeom>&, uint32_t, const uint32_t*, uint64_t*);
+template void launch_gather_keys<Geom>(hipStream_t, const TsGatherT<Geom>&, uint32_t, const uint32_t*, uint64_t*, uint32_t*);
+template void launch_gather_keys<VarGeom>(hipStream_t, const TsGatherT<VarGeom>&, uint32_t, const uint32_t*, uint64_t*, uint32_t*);
 void launch_key_flags(hipStream_t s, const uint64_t* key, uint32_t A, uint8_t* hflag) {
   hipLaunchKernelGGL(bwt_key_flags, dim3((A + 255) / 256 < 8192u ? (A + 255) / 256 : 8192u), dim3(256), 0, s, key, A, hflag);
 }

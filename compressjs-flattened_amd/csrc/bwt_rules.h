@@ -41,7 +41,8 @@ constexpr uint32_t pk2_prev(uint32_t rec_lo) { return (rec_lo >> PK2_PREV_SHIFT)
 // val[] of the rounds >= 2: the position, and (cyclic, packed round 1) the byte in front of the suffix on top
 constexpr uint32_t val_carrying(uint32_t pos, uint32_t prev) { return pos | (prev << VAL_PREV_SHIFT); }
 constexpr uint32_t val_prev(uint32_t v) { return v >> VAL_PREV_SHIFT; }
-// key of a round >= 2: group ordinal | rank key of the suffix h further on
+// key of a round >= 2: group ordinal | rank key of the suffix h further on.  The keys that the tile sorters leave for the deferral
+// kernels carry the slot's head bit (1 = starts a group) as the ordinal: bwt_defer_gather numbers the deferred groups from them
 constexpr uint64_t round_key(uint32_t ordinal, uint32_t rank_key) { return ((uint64_t)ordinal << RANK_BITS) | rank_key; }
 constexpr uint64_t round_key_ordinal(uint64_t k) { return k >> RANK_BITS; }
 constexpr uint32_t round_key_rank(uint64_t k) { return (uint32_t)k & RANK_MASK; }
@@ -120,9 +121,15 @@ constexpr TsOwn ts_classify(int hx, int nx, uint32_t L, bool at_end) {
   const bool owned = small && (uint32_t)hx < TS_NOM;
   return {small, owned, owned && (e - hx) > (int)TS_TINY};
 }
-// The group that runs into a window from the left.  Thread t looks at ordinals [4t, 4t + 4) of the TS_MAXGRP in front of the
-// window: index + 1 of the last of its four that differs from the window's first ordinal g0, 0 = none does.  The maximum over
-// the threads leaves TS_MAXGRP - li_max members of that group in front of the window (TS_MAXGRP: or more).
+// The group that runs into a window from the left, when the window's first slot is no head.  Thread t looks at the head bits of
+// slots [4t, 4t + 4) of the TS_MAXGRP in front of the window (heads4: bit j = slot 4t + j starts a group): the index of the last
+// head among its four, 0 = none.  The maximum over the threads is where that group starts, which leaves TS_MAXGRP - li_max of its
+// members in front of the window (TS_MAXGRP: or more -- a head on index 0 and no head at all read the same, and both are too many
+// for ts_prev_end).
+constexpr uint32_t ts_li4(uint32_t t, uint32_t heads4) { return (heads4 & 15u) ? t * 4u + 31u - (uint32_t)__builtin_clz(heads4 & 15u) : 0u; }
+// The same on group ordinals (the serial model of the host check numbers its groups): index + 1 of the last of the four ordinals
+// that differs from the window's first ordinal g0.  With g0 the ordinal of a group that starts in front of the window, the two
+// forms agree.
 constexpr uint32_t ts_li4(uint32_t t, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3, uint32_t g0) {
   return q3 != g0 ? t * 4u + 4u : q2 != g0 ? t * 4u + 3u : q1 != g0 ? t * 4u + 2u : q0 != g0 ? t * 4u + 1u : 0u;
 }

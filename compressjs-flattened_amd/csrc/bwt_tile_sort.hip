@@ -9,8 +9,9 @@
 
 namespace cjs {
 
-// Fused rank gather: the tile sorters of rounds >= 2 make the round's keys themselves -- group
-// ordinal from gord[], rank of suffix val + h out of R -- instead of reading back a key array that bwt_gather_keys wrote: the
+// Fused rank gather: the tile sorters of rounds >= 2 make the round's keys themselves -- the groups from the head bytes that
+// the regroup before left (ghead[]: one byte per slot, 1 = starts a group; a group ordinal is never needed, only where a group
+// starts), rank of suffix val + h out of R -- instead of reading back a key array that bwt_gather_keys wrote: the
 // random rank fetches (bound by the number of 64-byte transactions) then overlap the VALU-bound sorting of the other
 // workgroups of the CU, and 16 B per suffix of key traffic are gone.  Every slot has ONE window that fetches its rank
 // (ts_fetches): the window that owns its group stores the flag bytes of the group's slots at their sorted places, no keys; the
@@ -19,37 +20,32 @@ namespace cjs {
 template <bool WMAP> __device__ __forceinline__ uint32_t ts_slot(int s, int tid) {
   return WMAP ? (uint32_t)(tid >> 6) * 1024u + (uint32_t)s * 64u + (uint32_t)(tid & 63) : (uint32_t)s * 256u + (uint32_t)tid;
 }
-// Loads of the fused form (all issued before the first use): ordinals, suffixes and sorted positions of the window, and the
-// position (+1) of the last ordinal in front of the window that differs from the window's first one (this thread's four).
+// Loads of the fused form (all issued before the first use): suffixes and sorted positions of the window in the thread's slot
+// layout; the head bytes of slots [16 * tid, +16) of the window as a 16-bit mask (the same slots in both layouts: the mask words
+// do not depend on WMAP); and where the last head among this thread's four of the TS_MAXGRP slots in front of the window lies.
 template <bool WMAP, typename TG>
 __device__ __forceinline__ uint32_t ts_fused_load(const TG& tg, const uint32_t* __restrict__ val, uint64_t wb, uint32_t L,
-                                                  uint32_t (&go)[16], uint32_t (&pv)[16], uint32_t (&pp)[16], uint32_t& gprev) {
+                                                  uint32_t& heads16, uint32_t (&pv)[16], uint32_t (&pp)[16]) {
   const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 16; s++) { const uint32_t x = ts_slot<WMAP>(s, tid); go[s] = tg.gord[wb + (x < L ? x : L - 1u)]; }
+  uint32_t hvalid;
+  const uint4 hv = hf_load16(tg.ghead, wb, L, tid, hvalid);      // (window bases are multiples of 16)
 #pragma unroll
   for (int s = 0; s < 16; s++) { const uint32_t x = ts_slot<WMAP>(s, tid); pv[s] = val[wb + (x < L ? x : L - 1u)]; }
 #pragma unroll
   for (int s = 0; s < 16; s++) { const uint32_t x = ts_slot<WMAP>(s, tid); pp[s] = tg.pos[wb + (x < L ? x : L - 1u)]; }
   uint32_t li = 0;
-  gprev = 0xFFFFFFFFu;
-  if (wb) {                                       // wb is a multiple of TS_NOM >= TS_MAXGRP
-    const uint32_t* q = tg.gord + wb - TS_MAXGRP + (uint32_t)tid * 4u;
-    const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], g0 = tg.gord[wb];
-    gprev = tg.gord[wb - 1];
-    li = ts_li4((uint32_t)tid, q0, q1, q2, q3, g0);
-  }
-#pragma unroll
-  for (int s = 0; s < 16; s++) if (ts_slot<WMAP>(s, tid) >= L) go[s] = 0xFFFFFFFFu;
+  if (wb) li = ts_li4((uint32_t)tid, hf_bits4(*reinterpret_cast<const uint32_t*>(tg.ghead + wb - TS_MAXGRP + (uint32_t)tid * 4u), 0));      // wb is a multiple of TS_NOM >= TS_MAXGRP
+  heads16 = hf_bits16(hv, 0) & hvalid;
   return li;
 }
 // rank keys of the slots in `need` (bit s = step s): R[suffix + h] + 1 of the suffix's block, 0 past the end (sentinel form)
 template <typename TG>
 __device__ __forceinline__ void ts_fused_gather(const TG& tg, uint32_t need, const uint32_t (&pv)[16], uint32_t (&pp)[16], uint32_t (&rk20)[16]) {
-  uint32_t past = 0;
+  uint32_t past = 0, blk = pp[0] / tg.g.stride;      // the thread's slots ascend with s in both layouts, and pos[] with the slot
 #pragma unroll
   for (int s = 0; s < 16; s++) {
-    const uint32_t blk = pp[s] / tg.g.stride, n = blk_len(tg.g, blk);
+    blk = blk_step(pp[s], tg.g.stride, blk);
+    const uint32_t n = blk_len(tg.g, blk);
     uint32_t j = pk_pos(pv[s]) + tg.h;      // (the top byte of val[] may carry the byte in front of the suffix)
     if (tg.cyclic) { if (j >= n) j %= n; }
     else if (j >= n) { j = 0; past |= 1u << s; }
@@ -65,30 +61,21 @@ __device__ __forceinline__ void ts_fused_gather(const TG& tg, uint32_t need, con
 // among the window's L slots, classifies every slot by the window rule (bwt_rules.h), clears the defer flags of the owned
 // ones, fetches the rank keys of the slots that this window answers for and stores, for those it does not own, the key as
 // gathered.  each(s, x, hx, nx, owned, medium) runs once per step s, for all threads together: slot x, its group [hx, nx) in
-// window slots (nx closed by ts_close) and how this window holds it.  gk: TS_WIN words of LDS, dead behind the caller's next
-// barrier.  Leaves pv = the suffixes and rk20 = the rank keys of the fetched slots; returns the mask of the owned steps.
+// window slots (nx closed by ts_close) and how this window holds it.  Leaves pv = the suffixes and rk20 = the rank keys of the
+// fetched slots; returns the mask of the owned steps.
 template <bool WMAP, typename TG, typename Each>
 __device__ __forceinline__ uint32_t ts_window(uint64_t* __restrict__ key, const uint32_t* __restrict__ val, uint8_t* __restrict__ dflag, const TG& tg,
-                                              uint64_t wb, uint32_t L, bool at_end, uint32_t* gk, uint32_t (&pv)[16], uint32_t (&rk20)[16], Each&& each) {
+                                              uint64_t wb, uint32_t L, bool at_end, uint32_t (&pv)[16], uint32_t (&rk20)[16], Each&& each) {
   __shared__ uint64_t hm[64];                    // head mask of the window
   __shared__ int32_t wlast[64], wnext[64];       // last head before word / first head after word (window slot, TS_NO_HEAD / TS_NO_NEXT = none)
   __shared__ uint32_t lired[4];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  uint32_t go[16], pp[16], gprev;   // go: group ordinal of slot ts_slot(s, tid)
-  // every global load of the window (ordinals, suffixes, positions) is issued before the first LDS store: written as one loop
+  uint32_t pp[16], heads16;
+  // every global load of the window (head bytes, suffixes, positions) is issued before the first LDS store: written as one loop
   // the compiler waits for each load in turn, sixteen memory round trips instead of one
-  const uint32_t li = wave_max(ts_fused_load<WMAP>(tg, val, wb, L, go, pv, pp, gprev));
+  const uint32_t li = wave_max(ts_fused_load<WMAP>(tg, val, wb, L, heads16, pv, pp));
   if (lane == 0) lired[w] = li;
-#pragma unroll
-  for (int s = 0; s < 16; s++) gk[ts_slot<WMAP>(s, tid)] = go[s];
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 16; s++) {
-    const uint32_t x = ts_slot<WMAP>(s, tid);
-    const bool head = x < L && (wb + x == 0 || gk[x] != (x ? gk[x - 1] : gprev));
-    const uint64_t m = __ballot(head);
-    if (lane == 0) hm[x >> 6] = m;
-  }
+  reinterpret_cast<uint16_t*>(hm)[tid] = (uint16_t)heads16;      // the head mask is the head bytes themselves: 16 bits per thread, laid over the 64 words
   __syncthreads();
   if (w == 0) {      // per mask word: last head strictly before the word, first head strictly after it
     const uint64_t m = hm[lane];
@@ -103,12 +90,13 @@ __device__ __forceinline__ uint32_t ts_window(uint64_t* __restrict__ key, const 
   __syncthreads();
   const uint32_t a01 = lired[0] > lired[1] ? lired[0] : lired[1], a23 = lired[2] > lired[3] ? lired[2] : lired[3];
   const uint32_t prev_end = ts_prev_end(wb, L, at_end, a01 > a23 ? a01 : a23, hm[0], wnext[0]);
-  uint32_t ownm = 0, needm = 0;
+  uint32_t ownm = 0, needm = 0, headm = 0;
 #pragma unroll
   for (int s = 0; s < 16; s++) {
     const uint32_t x = ts_slot<WMAP>(s, tid);
     const int wi = (int)(x >> 6);
     const uint64_t m = hm[wi];
+    headm |= (uint32_t)((m >> lane) & 1ull) << s;      // (lane = x & 63 in both layouts)
     const int hx = ts_head_of(m, wi, lane, wlast[wi]), nx = ts_next_of(m, wi, lane, wnext[wi]);
     const TsOwn own = ts_classify(hx, nx, L, at_end);
     const bool owned = x < L && own.owned;
@@ -120,7 +108,7 @@ __device__ __forceinline__ uint32_t ts_window(uint64_t* __restrict__ key, const 
   ts_fused_gather(tg, needm, pv, pp, rk20);
 #pragma unroll
   for (int s = 0; s < 16; s++)
-    if (((needm >> s) & 1u) && !((ownm >> s) & 1u)) key[wb + ts_slot<WMAP>(s, tid)] = round_key(go[s], rk20[s]);      // not sorted here: the key as gathered
+    if (((needm >> s) & 1u) && !((ownm >> s) & 1u)) key[wb + ts_slot<WMAP>(s, tid)] = round_key((headm >> s) & 1u, rk20[s]);      // not sorted here: head bit | rank key, for the deferral
   return ownm;
 }
 
@@ -132,8 +120,8 @@ __device__ __forceinline__ void ts_ce(uint64_t& a, uint64_t& b, bool up) {
 template <typename TG>
 __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint8_t* __restrict__ hflag, uint32_t A,
                                                      uint8_t* __restrict__ dflag, TG tg, uint32_t Tt) {
-  __shared__ uint64_t sk[TS_WIN];                // first the group ordinals of the window slots (ts_window), then the sort
-  __shared__ uint64_t mm[64];                    // mask of the owned slots in groups of > TS_TINY members
+  __shared__ uint64_t sk[TS_WIN];                // the sort: 32-bit counting words, then the compacted members of the larger groups
+  __shared__ uint64_t mm[64];                   // mask of the owned slots in groups of > TS_TINY members
   __shared__ uint32_t mpre[65];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const uint32_t win = xcd_tile(blockIdx.x, Tt);            // windows of one block on one XCD: its ranks stay in that L2
@@ -145,7 +133,7 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
   int any_medium = 0;
   uint32_t hx16[16];          // head slot (low 16 bits) | group size (high 16 bits) of owned slots, 0xFFFFFFFF otherwise
   uint32_t rk20[16];
-  ts_window<false>(key, val, dflag, tg, wb, L, wb + L == A, reinterpret_cast<uint32_t*>(sk), pv, rk20,
+  ts_window<false>(key, val, dflag, tg, wb, L, wb + L == A, pv, rk20,
                    [&](int it, uint32_t x, int hx, int nx, bool owned, bool medium) {
     hx16[it] = owned ? ((uint32_t)hx | ((uint32_t)(nx - hx) << 16)) : 0xFFFFFFFFu;
     const uint64_t mb = __ballot(medium);
@@ -154,7 +142,6 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
   });
 #pragma unroll
   for (int it = 0; it < 16; it++) r[it] = hx16[it] != 0xFFFFFFFFu ? ts64_owned(hx16[it] & 0xFFFFu, rk20[it], pv[it]) : ts64_other((uint32_t)it * 256u + tid);
-  __syncthreads();           // the ordinals in sk are dead from here
   // groups of <= TS_TINY members: every member counts the smaller members of its group.  Inside a group only the
   // 20-bit rank key matters (equal keys stay one group, any order): 32-bit words (key << 12 | slot) are compared
   uint32_t* sk32 = reinterpret_cast<uint32_t*>(sk);
@@ -249,7 +236,7 @@ __global__ __launch_bounds__(256) void bwt_tile_sort(uint64_t* __restrict__ key,
 template <typename TG>
 __global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint8_t* __restrict__ hflag, uint32_t A,
                                                            uint8_t* __restrict__ dflag, TG tg, uint32_t Tt) {
-  __shared__ uint64_t se[TS_WIN];                // first the group ordinals of the window slots (ts_window); then (composite << 32) | suffix: staging of a pass
+  __shared__ uint64_t se[TS_WIN];                // (composite << 32) | suffix: staging of a pass
   __shared__ uint32_t wcnt[4][256];
   __shared__ uint32_t sm[4];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -259,7 +246,7 @@ __global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict_
   const uint32_t L = ts_win_len(wb, A);
   // slot of (wave w, step s, lane): w * 1024 + s * 64 + lane -- array order = (w, s, lane) order, which the stable ranking needs
   uint32_t rk20[16], pv[16], comp[16];
-  const uint32_t ownm = ts_window<true>(key, val, dflag, tg, wb, L, wb + L == A, reinterpret_cast<uint32_t*>(se), pv, rk20,
+  const uint32_t ownm = ts_window<true>(key, val, dflag, tg, wb, L, wb + L == A, pv, rk20,
                                         [&](int s, uint32_t, int hx, int, bool, bool) { comp[s] = (uint32_t)hx; });
 #pragma unroll
   for (int s = 0; s < 16; s++) {
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(256) void bwt_tile_sort_radix(uint64_t* __restrict_
     comp[s] = owned ? ts32_owned(comp[s], rk20[s]) : ts32_other(ts_slot<true>(s, tid));
     if (!owned) pv[s] = 0u;
   }
-  if (!__syncthreads_or((int)ownm)) return;      // also: the ordinals in se are dead from here
+  if (!__syncthreads_or((int)ownm)) return;
 #pragma unroll 1
   for (int shift = 0; shift < 32; shift += 8) {
     for (int i = tid; i < 1024; i += 256) (&wcnt[0][0])[i] = 0;

@@ -192,7 +192,7 @@ struct BwtWork {
   uint64_t* key[2] = {nullptr, nullptr};
   uint32_t* val[2] = {nullptr, nullptr};
   uint32_t* pos[2] = {nullptr, nullptr};
-  uint32_t* gord = nullptr;
+  uint8_t* ghead = nullptr;      // per slot of a round >= 2, in front of the sort: 1 = the slot starts a group (the regroup before wrote it)
   uint32_t* R = nullptr;
   uint32_t* SA = nullptr;
   uint8_t* dflag = nullptr;      // per slot of a round >= 2: 1 = its group is too large for the tile sorters
