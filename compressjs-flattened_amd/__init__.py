@@ -81,6 +81,30 @@ class CompareInfo(ctypes.Structure):
                 ("first_bad_block_b", ctypes.c_uint64)]
 
 
+class LineKey(ctypes.Structure):
+    """cjs_bz_linekey: the key of one line (16 bytes); all three fields all-ones: the line touches a bad block."""
+    _fields_ = [("hash", ctypes.c_uint64), ("len", ctypes.c_uint32), ("check", ctypes.c_uint32)]
+
+
+class LineKeysInfo(ctypes.Structure):
+    """cjs_bz_linekeys_info (32 bytes)."""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64),
+                ("blocks_decoded", ctypes.c_uint64)]
+
+
+class Hunk(ctypes.Structure):
+    """cjs_bz_hunk: lines [a_first, +a_count) of A replaced by [b_first, +b_count) of B (32 bytes)."""
+    _fields_ = [("a_first", ctypes.c_uint64), ("a_count", ctypes.c_uint64), ("b_first", ctypes.c_uint64), ("b_count", ctypes.c_uint64)]
+
+
+class LineDiffInfo(ctypes.Structure):
+    """cjs_bz_ldiff_info (32 bytes)."""
+    _fields_ = [("n_hunks", ctypes.c_uint64), ("edits", ctypes.c_uint64), ("common", ctypes.c_uint64), ("minimal", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+LINE_KEY_DTYPE = np.dtype([("hash", "<u8"), ("len", "<u4"), ("check", "<u4")])
+
 _lib = None
 
 
@@ -173,6 +197,10 @@ def load_library():
     L.cjs_bzip2_lines_locate_device.argtypes = [V, S, V, V, PU, S, PU, PI32, V]
     L.cjs_bzip2_lines_number.argtypes = [u8p, S, V, V, PU, S, PU, PI32, V]
     L.cjs_bzip2_lines_number_device.argtypes = [V, S, V, V, PU, S, PU, PI32, V]
+    keys_tail = [V, V, U64, U64, U64, V, S, ctypes.POINTER(LineKeysInfo), V]
+    L.cjs_bzip2_line_keys.argtypes = [u8p, S] + keys_tail
+    L.cjs_bzip2_line_keys_device.argtypes = [V, S] + keys_tail
+    L.cjs_line_keys_diff.argtypes = [V, S, V, S, U64, ctypes.POINTER(Hunk), S, ctypes.POINTER(LineDiffInfo)]
     L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
     L.cjs_bzip2_enc_write.argtypes = [V, V, S]
     L.cjs_bzip2_enc_finish.argtypes = [V]
@@ -903,6 +931,32 @@ class Bzip2Index:
             res[k] = r
         return res
 
+    def line_keys(self, data, lines, first=0, count=None, seed=0):
+        """The keys of lines [first, first + count) (count=None: to the last), hashed on the GPU (cjs_bzip2_line_keys): ->
+        (keys, info): a structured array of (hash, len, check) per line, all-ones for a line that touches a bad block, and a
+        LineKeysResult.  The bases follow from `seed` alone: against crafted input pass a seed of your own."""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        return _line_keys(lambda *a: L.cjs_bzip2_line_keys(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a, None), first, count, seed)
+
+    def diff_stream(self, data, lines, other_data, other_index, other_lines, max_edits=0, seed=0):
+        """bzdiff on the GPU: the line diff of this stream (A) against the stream `other_data` of `other_index` (B) -> LineDiff.
+        Both streams' lines are hashed where they stand decoded (line_keys); the diff runs on the host over 16 bytes per line
+        (diff_keys).  An empty final line (the text ends in a newline) is dropped from either side first, as `diff` does.  A bad
+        block on either side: CjsError(CJS_E_DATA_ERROR) with its detail."""
+        sides = []
+        for ix, d, ln in ((self, data, lines), (other_index, other_data, other_lines)):
+            keys, info = ix.line_keys(d, ln, seed=seed)
+            if info.bad_blocks:
+                raise CjsError(-5, load_library().cjs_strerror(-5).decode() + (": " + info.detail if info.detail else ""))
+            ends_in_newline = keys.size > 0 and keys[-1].tolist() == (0, 0, 0)
+            sides.append((keys[:-1] if ends_in_newline else keys, ends_in_newline or ix.total == 0))
+        (ka, a_nl), (kb, b_nl) = sides
+        res = diff_keys(ka, kb, max_edits)
+        res.a_lines, res.b_lines, res.a_final_newline, res.b_final_newline = int(ka.size), int(kb.size), a_nl, b_nl
+        return res
+
     def grep_lines(self, data, lines, patterns, regex=False, **search_kw):
         """bzgrep -n: search, then number of the match offsets, then locate of each distinct line and its successor, then one
         read_ranges.  -> [(line_no, line_bytes, [(off, pattern), ...])] ascending, each line once (a match that spans lines
@@ -1016,6 +1070,100 @@ def line_numbers_device(d_in_ptr, n, index, lines, offsets, device=-1):
     L = load_library()
     opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
     return _lines_ask(lambda *a: L.cjs_bzip2_lines_number_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), offsets)
+
+
+class LineKeysResult:
+    """What came with the keys: n_lines = the lines of the window; bad_blocks / first_bad_block (None if none) / detail = the
+    touched blocks that were not good."""
+
+    def __init__(self, info, detail):
+        self.n_lines = int(info.n_lines)
+        self.bad_blocks = int(info.n_bad_blocks)
+        self.first_bad_block = int(info.first_bad_block) if info.n_bad_blocks else None
+        self.blocks_decoded = int(info.blocks_decoded)
+        self.detail = detail
+
+
+def _line_keys(call, first, count, seed):
+    """call(first, count, seed, keys, cap, info) -> rc: the count query (the table alone), then every key of the window"""
+    L = load_library()
+    first, cnt = int(first), 2 ** 64 - 1 if count is None else int(count)
+    info = LineKeysInfo()
+    _check(call(first, cnt, int(seed), None, 0, ctypes.byref(info)))
+    keys = np.zeros(int(info.n_lines), dtype=LINE_KEY_DTYPE)
+    if keys.size:
+        _check(call(first, cnt, int(seed), keys.ctypes.data, keys.size, ctypes.byref(info)))
+    detail = L.cjs_last_error_detail().decode() if info.n_bad_blocks else ""
+    return keys, LineKeysResult(info, detail)
+
+
+def line_keys_device(d_in_ptr, n, index, lines, first=0, count=None, seed=0, device=-1):
+    """Bzip2Index.line_keys with the stream in GPU memory (cjs_bzip2_line_keys_device; the memory rules of decompress_device).
+    The result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _line_keys(lambda *a: L.cjs_bzip2_line_keys_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), first, count, seed)
+
+
+class LineDiff:
+    """A line diff: hunks = [(a_first, a_count, b_first, b_count)] ascending, each replacing lines [a_first, +a_count) of A by
+    [b_first, +b_count) of B; edits = the lines deleted plus the lines inserted; common = the lines kept; minimal = the script is
+    a shortest one (False: max_edits was below the minimum and everything between the common ends is one hunk)."""
+
+    def __init__(self, hunks, info):
+        self.hunks = hunks
+        self.edits, self.common, self.minimal = int(info.edits), int(info.common), bool(info.minimal)
+        self.a_lines = self.b_lines = None                           # (diff_stream: the lines of either side ...
+        self.a_final_newline = self.b_final_newline = True           # ... and whether its last one ends in a newline)
+
+    @property
+    def equal(self):
+        return not self.hunks      # (a last line with and without its newline are two keys)
+
+    def normal_text(self, index, data, lines, other_index, other_data, other_lines):
+        """What `diff` prints in its normal format: NaM, N,MdK and N,McK,L commands, "< " and "> " lines, "---" between the two
+        sides of a change and "\\ No newline at end of file" behind a side's last line when that has none.  Only the hunks' lines
+        are read, through read_lines (one call per side); a hunk that touches a bad block raises its CjsError."""
+        def side(ix, d, ln, spans):
+            got = ix.read_lines(d, ln, spans) if spans else []
+            for g in got:
+                if isinstance(g, CjsError):
+                    raise g
+            return [g.split(b"\n") for g in got]
+
+        def numbers(first, count):
+            return "%d" % (first + (1 if count else 0)) if count <= 1 else "%d,%d" % (first + 1, first + count)
+
+        a_text = side(index, data, lines, [(h[0], h[1]) for h in self.hunks])
+        b_text = side(other_index, other_data, other_lines, [(h[2], h[3]) for h in self.hunks])
+        out = []
+        for (a0, an, b0, bn), ta, tb in zip(self.hunks, a_text, b_text):
+            out.append((numbers(a0, an) + ("a" if not an else "d" if not bn else "c") + numbers(b0, bn)).encode() + b"\n")
+            for mark, parts, n, last, final in ((b"< ", ta, an, a0 + an == self.a_lines, self.a_final_newline),
+                                                (b"> ", tb, bn, b0 + bn == self.b_lines, self.b_final_newline)):
+                if mark == b"> " and an and bn:
+                    out.append(b"---\n")
+                for k in range(n):
+                    out.append(mark + parts[k] + b"\n")
+                    if k == n - 1 and last and not final:
+                        out.append(b"\\ No newline at end of file\n")
+        return b"".join(out)
+
+
+def diff_keys(a, b, max_edits=0):
+    """The line diff of two key arrays (Bzip2Index.line_keys) on the host (cjs_line_keys_diff; no device) -> LineDiff.  With at
+    most max_edits edits (0: 16,384) in the shortest script the result is one; else everything between the common ends is one
+    hunk.  All-ones keys equal nothing."""
+    L = load_library()
+    a = np.ascontiguousarray(a, dtype=LINE_KEY_DTYPE)
+    b = np.ascontiguousarray(b, dtype=LINE_KEY_DTYPE)
+    pa, pb = (a.ctypes.data if a.size else None), (b.ctypes.data if b.size else None)
+    info = LineDiffInfo()
+    _check(L.cjs_line_keys_diff(pa, a.size, pb, b.size, int(max_edits), None, 0, ctypes.byref(info)))
+    hunks = (Hunk * max(int(info.n_hunks), 1))()
+    if info.n_hunks:
+        _check(L.cjs_line_keys_diff(pa, a.size, pb, b.size, int(max_edits), hunks, int(info.n_hunks), ctypes.byref(info)))
+    return LineDiff([(h.a_first, h.a_count, h.b_first, h.b_count) for h in hunks[:int(info.n_hunks)]], info)
 
 
 class SearchResult:

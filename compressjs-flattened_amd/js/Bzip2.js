@@ -346,6 +346,38 @@ Bzip2.readLines = function (inStream, index, lineIndex, first, count) {
   }
   return Bzip2.readRange(inStream, index, at.values[0], at.values[1] - at.values[0]);
 };
+// The line keys (cjs_bzip2_line_keys): a 16-byte record per line, hashed on the GPU while the blocks stand decoded there.  lineKeys
+// returns {keys: Uint8Array (16 bytes per line, little-endian: u64 hash, u32 len, u32 check; all ones: the line touches a damaged
+// block), lines, badBlocks, firstBadBlock (null if none), detail} for lines first .. first + count - 1 (count undefined: to the
+// last).  Equal records mean equal lines up to a hash collision; the hash's bases follow from seed alone, so against crafted
+// input pass a seed of your own.  diffLines is bzdiff: the keys of both streams, then the line diff on the host: {hunks: [{aFirst,
+// aCount, bFirst, bCount}] ascending, edits, common, minimal}; an empty final line is dropped from either side first, as diff does;
+// a damaged block on either side throws.  maxEdits (0: 16,384): above it the middle is one hunk and minimal is false.
+function lineKeysCall(inStream, index, lineIndex, o) {
+  var input = common.coerceInput(inStream), r;
+  try {
+    r = common.addon().bzip2LineKeys(input.bytes, index, lineIndex, o.first === undefined ? 0 : o.first, o.count === undefined || o.count === null ? -1 : o.count,
+                                     o.seed === undefined ? 0 : o.seed);
+  } catch (e) { rethrow(e); }
+  return { keys: r.keys, lines: r.lines, badBlocks: r.badBlocks, firstBadBlock: r.firstBadBlock < 0 ? null : r.firstBadBlock, detail: r.detail };
+}
+Bzip2.lineKeys = function (inStream, index, lineIndex, opts) { return lineKeysCall(inStream, index, lineIndex, opts || {}); };
+Bzip2.diffLines = function (inStreamA, indexA, lineIndexA, inStreamB, indexB, lineIndexB, opts) {
+  var o = opts || {}, sides = [[inStreamA, indexA, lineIndexA], [inStreamB, indexB, lineIndexB]].map(function (s) {
+    var r = lineKeysCall(s[0], s[1], s[2], { seed: o.seed });
+    if (r.badBlocks) {
+      var t = new TypeError(Messages[Err.DATA_ERROR] + (r.detail ? ': ' + r.detail : '')); t.errorCode = Err.DATA_ERROR; throw t;
+    }
+    var k = r.keys, last = k.length - 16, empty = true;
+    for (var i = last; i < k.length; i++) { empty = empty && k[i] === 0; }
+    return empty ? k.subarray(0, last) : k;
+  });
+  var d;
+  try { d = common.addon().lineKeysDiff(sides[0], sides[1], o.maxEdits === undefined ? 0 : o.maxEdits); } catch (e) { rethrow(e); }
+  var hunks = [];
+  for (var j = 0; j < d.hunks.length; j += 4) { hunks.push({ aFirst: d.hunks[j], aCount: d.hunks[j + 1], bFirst: d.hunks[j + 2], bCount: d.hunks[j + 3] }); }
+  return { hunks: hunks, edits: d.edits, common: d.common, minimal: d.minimal };
+};
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

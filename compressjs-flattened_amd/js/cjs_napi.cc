@@ -47,6 +47,9 @@ struct Api {
   void (*lines_destroy)(cjs_bz_lines*) = nullptr;
   int (*lines_locate)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, const uint64_t*, size_t, uint64_t*, int32_t*, const cjs_opts*) = nullptr;
   int (*lines_number)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, const uint64_t*, size_t, uint64_t*, int32_t*, const cjs_opts*) = nullptr;
+  int (*line_keys)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint64_t, cjs_bz_linekey*, size_t, cjs_bz_linekeys_info*,
+                   const cjs_opts*) = nullptr;
+  int (*line_keys_diff)(const cjs_bz_linekey*, size_t, const cjs_bz_linekey*, size_t, uint64_t, cjs_bz_hunk*, size_t, cjs_bz_ldiff_info*) = nullptr;
   int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
   int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
   int (*enc_finish)(cjs_bz_enc*) = nullptr;
@@ -95,6 +98,7 @@ bool load_api() {
   SYM(index_info, "cjs_bzip2_index_info") SYM(compare, "cjs_bzip2_compare") SYM(compare_streams, "cjs_bzip2_compare_streams")
   SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
+  SYM(line_keys, "cjs_bzip2_line_keys") SYM(line_keys_diff, "cjs_line_keys_diff")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(enc_index, "cjs_bzip2_enc_index") SYM(compress_indexed, "cjs_bzip2_compress_indexed")
@@ -547,6 +551,97 @@ napi_value bzip2_lines_ask(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// A whole number from 0 to 2^53 out of a JS number (false: negative, NaN, above 2^53 or with a fraction).
+bool get_whole(napi_env env, napi_value v, uint64_t* out) {
+  double d = 0;
+  if (napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0 && d <= 9007199254740992.0 && d == (double)(uint64_t)d)) return false;
+  *out = (uint64_t)d;
+  return true;
+}
+
+// bzip2LineKeys(input, index, lineIndex, first, count, seed) -> { keys: Uint8Array, lines, badBlocks, firstBadBlock, detail }
+// (Bzip2.lineKeys).  keys: the 16-byte records (cjs_bz_linekey, little-endian: u64 hash, u32 len, u32 check) of lines first ..
+// first + count - 1 (count < 0: to the last); lines: their number; first, count and seed are integers from 0 to 2^53.
+napi_value bzip2_line_keys(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 6; napi_value argv[6];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *lp = nullptr; size_t n = 0, in = 0, ln = 0;
+  if (argc < 6 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &lp, &ln)) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array line index, first, count, seed)"); return nullptr;
+  }
+  uint64_t first = 0, count = ~0ull, seed = 0;
+  double c = -1;
+  napi_get_value_double(env, argv[4], &c);
+  if (!get_whole(env, argv[3], &first) || (c >= 0 && !get_whole(env, argv[4], &count)) || !(c >= 0 || c == -1) || !get_whole(env, argv[5], &seed)) {
+    napi_throw_type_error(env, nullptr, "first, count and seed are integers from 0 to 2^53"); return nullptr;
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_lines* lt = nullptr;
+  rc = api.lines_load(lp ? lp : &dummy, ln, ix, &lt);
+  if (rc != 0) { api.index_destroy(ix); return throw_code(env, rc); }
+  cjs_bz_linekeys_info ki;
+  rc = api.line_keys(p ? p : &dummy, n, ix, lt, first, count, seed, nullptr, 0, &ki, nullptr);      // the count query: the table alone
+  napi_value res = nullptr, ab, ta, v; void* dst = nullptr;
+  std::string detail;
+  if (rc == 0) {
+    napi_create_arraybuffer(env, sizeof(cjs_bz_linekey) * (size_t)ki.n_lines, &dst, &ab);
+    if (ki.n_lines) rc = api.line_keys(p ? p : &dummy, n, ix, lt, first, count, seed, (cjs_bz_linekey*)dst, (size_t)ki.n_lines, &ki, nullptr);
+    if (rc == 0 && ki.n_bad_blocks) detail = api.detail_();      // (before the next call of the library on this thread)
+  }
+  api.lines_destroy(lt);
+  api.index_destroy(ix);
+  if (rc != 0) return throw_code(env, rc);
+  napi_create_object(env, &res);
+  napi_create_typedarray(env, napi_uint8_array, sizeof(cjs_bz_linekey) * (size_t)ki.n_lines, ab, 0, &ta);
+  napi_set_named_property(env, res, "keys", ta);
+  napi_create_double(env, (double)ki.n_lines, &v); napi_set_named_property(env, res, "lines", v);
+  napi_create_double(env, (double)ki.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
+  napi_create_double(env, ki.n_bad_blocks ? (double)ki.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
+  napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
+  return res;
+}
+
+// lineKeysDiff(keysA, keysB, maxEdits) -> { hunks: Float64Array, edits, common, minimal } (Bzip2.diffLines): the line diff of two
+// arrays of 16-byte records on the host (cjs_line_keys_diff); hunks holds four numbers per hunk: aFirst, aCount, bFirst, bCount.
+napi_value line_keys_diff(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *a = nullptr, *b = nullptr; size_t na = 0, nb = 0;
+  uint64_t max_edits = 0;
+  if (argc < 3 || !get_bytes(env, argv[0], &a, &na) || !get_bytes(env, argv[1], &b, &nb) || na % sizeof(cjs_bz_linekey) || nb % sizeof(cjs_bz_linekey) ||
+      !get_whole(env, argv[2], &max_edits)) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array keys, Uint8Array keys, maxEdits): 16 bytes per key"); return nullptr;
+  }
+  // (a typed array's bytes may stand at any address: the records are copied to where they are aligned)
+  std::vector<cjs_bz_linekey> ka(na / sizeof(cjs_bz_linekey) + 1), kb(nb / sizeof(cjs_bz_linekey) + 1);
+  if (na) memcpy(ka.data(), a, na);
+  if (nb) memcpy(kb.data(), b, nb);
+  cjs_bz_ldiff_info di;
+  int rc = api.line_keys_diff(ka.data(), na / sizeof(cjs_bz_linekey), kb.data(), nb / sizeof(cjs_bz_linekey), max_edits, nullptr, 0, &di);
+  if (rc != 0) return throw_code(env, rc);
+  std::vector<cjs_bz_hunk> h((size_t)di.n_hunks + 1);
+  rc = api.line_keys_diff(ka.data(), na / sizeof(cjs_bz_linekey), kb.data(), nb / sizeof(cjs_bz_linekey), max_edits, h.data(), (size_t)di.n_hunks, &di);
+  if (rc != 0) return throw_code(env, rc);
+  napi_value res, ab, ta, v; void* dst;
+  napi_create_object(env, &res);
+  napi_create_arraybuffer(env, sizeof(double) * 4 * (size_t)di.n_hunks, &dst, &ab);
+  for (size_t k = 0; k < (size_t)di.n_hunks; k++) {
+    double* d = (double*)dst + 4 * k;
+    d[0] = (double)h[k].a_first; d[1] = (double)h[k].a_count; d[2] = (double)h[k].b_first; d[3] = (double)h[k].b_count;
+  }
+  napi_create_typedarray(env, napi_float64_array, 4 * (size_t)di.n_hunks, ab, 0, &ta);
+  napi_set_named_property(env, res, "hunks", ta);
+  napi_create_double(env, (double)di.edits, &v); napi_set_named_property(env, res, "edits", v);
+  napi_create_double(env, (double)di.common, &v); napi_set_named_property(env, res, "common", v);
+  napi_get_boolean(env, di.minimal != 0, &v); napi_set_named_property(env, res, "minimal", v);
+  return res;
+}
+
 // bzip2Recover(input, asStream) -> { data: Uint8Array, found: Float64Array }   (Bzip2.recoverFile)
 // found holds six numbers per block candidate, ascending: bitpos, end_bit, out_off, size, status, crc (cjs_bz_found).
 napi_value bzip2_recover(napi_env env, napi_callback_info info) {
@@ -948,6 +1043,8 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2Compare", nullptr, bzip2_compare, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2BuildLineIndex", nullptr, bzip2_build_line_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2LineKeys", nullptr, bzip2_line_keys, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"lineKeysDiff", nullptr, line_keys_diff, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2CompressIndexed", nullptr, bzip2_compress_indexed, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncIndex", nullptr, enc_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},

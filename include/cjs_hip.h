@@ -373,6 +373,75 @@ int cjs_bzip2_lines_number(const uint8_t *in, size_t n, const cjs_bz_index *idx,
                            size_t count, uint64_t *line, int32_t *status, const cjs_opts *opts);
 int cjs_bzip2_lines_number_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines,
                                   const uint64_t *off, size_t count, uint64_t *line, int32_t *status, const cjs_opts *opts);
+/* cjs_bzip2_line_keys: a fixed-size key per line of an indexed stream, hashed on the GPU while the blocks stand decoded there
+ * (the primitive under `bzdiff`: a line diff of two streams is a host algorithm over 16 bytes per line instead of the text).
+ * Lines are the line table's: line k is the bytes [start(k), start(k+1)), its newline included; line N is the unterminated tail.
+ * With P = 2^61 - 1 and B1, B2 = 256 + (s mod (P - 256)), s the first and the second output of splitmix64 started at `seed`
+ * (constants 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB; shifts 30, 27, 31), and for bytes b_0 .. b_{m-1}
+ * H_B = sum (b_i + 1) * B^(m-1-i) mod P (the empty string: 0), a line's key is hash = H_B1 (always below 2^61), len = the low 32
+ * bits of m, check = the low 32 bits of H_B2.  Two lines are taken as equal iff their records are equal: equality of lines up to
+ * a collision (about 93 bits of hash, plus the length).  The bases are PUBLIC for a given seed, so a caller who faces crafted
+ * input passes a seed of its own.  All three fields all-ones: "this line touches a bad block"; no key has that value.
+ * The WINDOW is lines [first, min(first + count, N + 1)); the add saturates.  `keys` gets the first min(cap, lines in the window)
+ * records and nothing past them is written; info->n_lines counts the window's lines (cap = 0, keys = NULL: the count query, which
+ * the table alone answers without a device; so does every empty window).
+ * The TOUCHED blocks come from the table alone: from the block that holds newline number `first` (1-based; block 0 when first is
+ * 0) through the block that holds newline number first + count (the last block when there is no such newline), blocks of size
+ * zero left out.  Each is decoded once and judged as cjs_bzip2_read_ranges judges it, by the same passes; the records do not
+ * depend on CJS_RANGE_PASS_BLOCKS, CJS_DEC_GROUP_BYTES, CJS_DEC_BATCH_ELEMS or CJS_DEC_ROW_BYTES.
+ * Per decoded inverse-BWT batch, over 16 KiB tiles of the blocks (a tile never spans two blocks): one kernel counts the newlines
+ * of every tile and hashes the fragment behind its last newline, one per block scans the counts and chains those fragments
+ * into every tile's carry-in, and -- once the host has seen that every GOOD block has the newlines the table says -- one writes
+ * a record per newline at its rank (the fragment from the block's previous newline, or from its first byte) and, per block, the
+ * fragment behind its last newline.  No atomics.  16 bytes per newline and 32 per block leave the GPU; the fragments of a line
+ * that spans blocks, batches or passes are joined on the host (H is linear in the string), so no state stays on the device
+ * between batches.  Device memory held: a pass's, 32 bytes per tile and 16 bytes per newline of the batch.
+ * A GOOD block whose counted newlines differ from the table's fails the call: CJS_E_DATA_ERROR, "line table does not match the
+ * stream at block <b>"; nothing is written at the table's ranks for it.  A bad block does not fail the call: it returns 0, info
+ * and cjs_last_error_detail() follow cjs_bzip2_search's rules, and every line that by the table's account may have a byte in bad
+ * block b gets the all-ones record: lines cum[b] .. cum[b+1].  (The last of them is included although it has no byte there when
+ * the block's last byte is a newline: only the block's bytes could tell.)
+ * CJS_E_INVALID_ARG before the device is touched: the argument errors of cjs_bzip2_lines_locate (NULL idx or lines; NULL in with
+ * n > 0; n != the index's stream_bytes; a foreign table), NULL keys with cap > 0, NULL info.  keys and info are HOST memory in
+ * both forms (d_in: the memory rules of cjs_bzip2_decompress_device).  opts->device is honoured.  CJS_DEBUG: one "[cjs linekeys]"
+ * line per call on stderr (form, window, lines, blocks touched and bad, passes, batches, tiles, H2D and D2H bytes).
+ * cjs_stage_line_keys EXISTS FOR TESTS; no product path calls it: the keys of the lines of the plain host buffer text[0 .. n),
+ * by the same functions (csrc/line_key.h), without a device; *n_lines = newlines + 1.
+ * cjs_line_keys_diff: the line diff of two key lists, on the host (no device).  Hunks are ascending; each replaces lines
+ * [a_first, +a_count) of A by [b_first, +b_count) of B; at least one count is non-zero; neighbouring hunks are separated by at
+ * least one common line; b_first = a_first - (earlier a_counts) + (earlier b_counts).  info->edits = sum (a_count + b_count),
+ * common = (na + nb - edits) / 2.  The common prefix and suffix are trimmed, the rest goes through Myers' O(ND) search with the
+ * linear-space middle-snake recursion: memory O(na + nb + max_edits), no stored trace.  If the shortest script has at most
+ * max_edits edits (0: 16,384), edits is that minimum, na + nb - 2 LCS, and minimal = 1; otherwise everything between the common
+ * prefix and suffix is one hunk and minimal = 0: still a valid, deterministic script.  `hunks` gets the first min(cap, n_hunks)
+ * and nothing past them is written (cap = 0, hunks = NULL: the count query).  All-ones records never equal anything.
+ * CJS_E_INVALID_ARG: NULL info; NULL a / b / hunks with na / nb / cap > 0. */
+typedef struct cjs_bz_linekey {
+  uint64_t hash;   /* H_B1, below 2^61 */
+  uint32_t len;    /* the line's length in bytes, newline included (low 32 bits) */
+  uint32_t check;  /* the low 32 bits of H_B2 */
+} cjs_bz_linekey;
+typedef struct cjs_bz_linekeys_info {
+  uint64_t n_lines;         /* lines of the window, also when more than cap */
+  uint64_t n_bad_blocks;    /* touched blocks that were not GOOD */
+  uint64_t first_bad_block; /* index of the first of them; ~0 if none */
+  uint64_t blocks_decoded;  /* touched blocks */
+} cjs_bz_linekeys_info;
+typedef struct cjs_bz_hunk {
+  uint64_t a_first, a_count, b_first, b_count;
+} cjs_bz_hunk;
+typedef struct cjs_bz_ldiff_info {
+  uint64_t n_hunks, edits, common;
+  uint32_t minimal, reserved;
+} cjs_bz_ldiff_info;
+int cjs_bzip2_line_keys(const uint8_t *in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first, uint64_t count,
+                        uint64_t seed, cjs_bz_linekey *keys, size_t cap, cjs_bz_linekeys_info *info, const cjs_opts *opts);
+int cjs_bzip2_line_keys_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first,
+                               uint64_t count, uint64_t seed, cjs_bz_linekey *keys, size_t cap, cjs_bz_linekeys_info *info,
+                               const cjs_opts *opts);
+int cjs_stage_line_keys(const uint8_t *text, size_t n, uint64_t seed, cjs_bz_linekey *keys, size_t cap, size_t *n_lines);
+int cjs_line_keys_diff(const cjs_bz_linekey *a, size_t na, const cjs_bz_linekey *b, size_t nb, uint64_t max_edits, cjs_bz_hunk *hunks,
+                       size_t cap, cjs_bz_ldiff_info *info);
 /* cjs_bzip2_compare: `cmp` over the address space of cjs_bzip2_read_ranges ([0, total_bytes) of the index), done on the GPU: is
  * the decoded stream equal to `other`, and if not, where and with which bytes?  The decoded bytes never leave the GPU, 16 bytes
  * per reported difference do.  other[k] is compared with decoded byte other_off + k.  The COMPARED SPAN is
