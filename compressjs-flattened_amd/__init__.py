@@ -103,7 +103,15 @@ class LineDiffInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class CutInfo(ctypes.Structure):
+    """cjs_bz_cut_info (40 bytes)."""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("blocks_decoded", ctypes.c_uint64),
+                ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64)]
+
+
 LINE_KEY_DTYPE = np.dtype([("hash", "<u8"), ("len", "<u4"), ("check", "<u4")])
+CUT_RANGE_DTYPE = np.dtype([("lo", "<u4"), ("hi", "<u4")])
+CUT_FIELDS, CUT_BYTES, CUT_TO_END = 0, 1, 0xFFFFFFFF
 
 _lib = None
 
@@ -201,6 +209,11 @@ def load_library():
     L.cjs_bzip2_line_keys.argtypes = [u8p, S] + keys_tail
     L.cjs_bzip2_line_keys_device.argtypes = [V, S] + keys_tail
     L.cjs_line_keys_diff.argtypes = [V, S, V, S, U64, ctypes.POINTER(Hunk), S, ctypes.POINTER(LineDiffInfo)]
+    cut_head = [V, V, U64, U64, U32, U32, V, U32]
+    L.cjs_bzip2_cut.argtypes = [u8p, S] + cut_head + [PP, PS, ctypes.POINTER(CutInfo), V]
+    L.cjs_bzip2_cut_device.argtypes = [V, S] + cut_head + [V, S, PS, ctypes.POINTER(CutInfo), V]
+    L.cjs_stage_cut.argtypes = [V, S, U32, U32, V, U32, V, S, PS]
+    L.cjs_cut_list_parse.argtypes = [ctypes.c_char_p, V, U32, PU32]
     L.cjs_bzip2_enc_create.argtypes = [ctypes.POINTER(V), I, S, V]
     L.cjs_bzip2_enc_write.argtypes = [V, V, S]
     L.cjs_bzip2_enc_finish.argtypes = [V]
@@ -940,6 +953,20 @@ class Bzip2Index:
         keep = data if data.size else np.zeros(1, dtype=np.uint8)
         return _line_keys(lambda *a: L.cjs_bzip2_line_keys(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a, None), first, count, seed)
 
+    def cut_lines(self, data, lines, fields=None, bytes=None, delimiter=b"\t", first=0, count=None):
+        """`bzcat | cut -f LIST -d D` / `cut -b LIST` over lines [first, first + count) (count=None: to the last), selected and
+        packed on the GPU (cjs_bzip2_cut) -> bytes.  Exactly one of fields / bytes: a cut-style string ("1,3-5,7-"), or a list of
+        ints and (lo, hi) pairs (hi=None: to the end of the line).  A line without the delimiter is a line of one field (GNU cut
+        prints it whole).  A bad block inside the window: CjsError(CJS_E_DATA_ERROR)."""
+        L = load_library()
+        mode, d, sel = _cut_args(fields, bytes, delimiter)
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        out, out_n, info = u8p(), ctypes.c_size_t(0), CutInfo()
+        _check(L.cjs_bzip2_cut(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, int(first), 2 ** 64 - 1 if count is None else int(count), mode, d,
+                               sel.ctypes.data, sel.size, ctypes.byref(out), ctypes.byref(out_n), ctypes.byref(info), None))
+        return _adopt(out, out_n.value).tobytes()
+
     def diff_stream(self, data, lines, other_data, other_index, other_lines, max_edits=0, seed=0):
         """bzdiff on the GPU: the line diff of this stream (A) against the stream `other_data` of `other_index` (B) -> LineDiff.
         Both streams' lines are hashed where they stand decoded (line_keys); the diff runs on the host over 16 bytes per line
@@ -1103,6 +1130,68 @@ def line_keys_device(d_in_ptr, n, index, lines, first=0, count=None, seed=0, dev
     L = load_library()
     opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
     return _line_keys(lambda *a: L.cjs_bzip2_line_keys_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), first, count, seed)
+
+
+def cut_list(spec):
+    """A cut-style LIST ("1,3-5,7-", "-4") -> [(lo, hi)] as written (cjs_cut_list_parse; no device); hi = CUT_TO_END: to the end
+    of the line.  CjsError(CJS_E_INVALID_ARG) for what is no list."""
+    L = load_library()
+    sel = np.zeros(64, dtype=CUT_RANGE_DTYPE)
+    n = ctypes.c_uint32(0)
+    _check(L.cjs_cut_list_parse(spec.encode() if isinstance(spec, str) else bytes(spec), sel.ctypes.data, 64, ctypes.byref(n)))
+    return [(int(r["lo"]), int(r["hi"])) for r in sel[:n.value]]
+
+
+def _cut_args(fields, bytes_, delimiter):
+    """-> (mode, delimiter byte, the ranges as an array): exactly one of fields / bytes_, each a LIST string or ints and pairs"""
+    if (fields is None) == (bytes_ is None):
+        raise ValueError("exactly one of fields and bytes must be given")
+    spec = fields if bytes_ is None else bytes_
+    if isinstance(spec, (str, bytes)):
+        pairs = cut_list(spec)
+    else:
+        pairs = [(int(x), int(x)) if not isinstance(x, (tuple, list)) else (int(x[0]), CUT_TO_END if x[1] is None else int(x[1])) for x in spec]
+    if any(not 0 <= v <= CUT_TO_END for p in pairs for v in p):
+        raise ValueError("a unit number does not fit 32 bits")
+    raw = delimiter.encode("latin-1") if isinstance(delimiter, str) else bytes([delimiter]) if isinstance(delimiter, int) else bytes(delimiter)
+    if len(raw) != 1:
+        raise ValueError("the delimiter is one byte")
+    d = raw[0]
+    sel = np.zeros(max(len(pairs), 1), dtype=CUT_RANGE_DTYPE)
+    for k, p in enumerate(pairs):
+        sel[k] = p
+    return (CUT_FIELDS if bytes_ is None else CUT_BYTES), d, sel[:len(pairs)]
+
+
+def cut_text(text, fields=None, bytes=None, delimiter=b"\t"):
+    """The cut of a plain host buffer by the library's scalar walk (cjs_stage_cut; no device): what Bzip2Index.cut_lines gives for
+    the whole of a stream that decodes to `text`."""
+    L = load_library()
+    mode, d, sel = _cut_args(fields, bytes, delimiter)
+    text = _coerce_input(text)
+    keep = text if text.size else np.zeros(1, dtype=np.uint8)
+    out = np.zeros(text.size + 1, dtype=np.uint8)
+    n = ctypes.c_size_t(0)
+    _check(L.cjs_stage_cut(keep.ctypes.data, text.size, mode, d, sel.ctypes.data, sel.size, out.ctypes.data, out.size, ctypes.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def cut_lines_device(d_in_ptr, n, index, lines, fields=None, bytes=None, delimiter=b"\t", first=0, count=None, d_out_ptr=None, out_cap=0, device=-1):
+    """Bzip2Index.cut_lines with the stream and the result in GPU memory (cjs_bzip2_cut_device; the memory rules of
+    decompress_device) -> the bytes written at d_out_ptr.  Output above out_cap: CjsError(CJS_E_OUTPUT_TOO_SMALL) whose `need` is
+    the full size (d_out_ptr=None, out_cap=0: the size query); nothing at or past out_cap is written."""
+    L = load_library()
+    mode, d, sel = _cut_args(fields, bytes, delimiter)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    need, info = ctypes.c_size_t(0), CutInfo()
+    rc = L.cjs_bzip2_cut_device(d_in_ptr, n, index._h, lines._h, int(first), 2 ** 64 - 1 if count is None else int(count), mode, d, sel.ctypes.data,
+                                sel.size, d_out_ptr, out_cap, ctypes.byref(need), ctypes.byref(info), ctypes.byref(opts))
+    try:
+        _check(rc)
+    except CjsError as e:
+        e.need = need.value if rc == -33 else None
+        raise
+    return need.value
 
 
 class LineDiff:

@@ -1,6 +1,6 @@
 // range_engine.h -- the pass engine of the indexed entry points (range.hip defines it): the blocks an index names go through phases
 // A, B and C in bounded passes, each judged against its entry, and every decoded inverse-BWT batch is handed to a consumer while it
-// stands expanded in device scratch.  Six consumers:
+// stands expanded in device scratch.  Seven consumers:
 //   range.hip     the slice gather of the range reads
 //   search.hip    the pattern scan: count, scan and emit over the tiles of a batch's segments, a carry between batches
 //   regex.hip     the same scan with an automaton walk per start position as the match function (the tile's text: scan_text.h)
@@ -8,6 +8,8 @@
 //                 (its newline test, ln_nl4, stands here: the compressor's block rows, enc_index.hip, count with it too)
 //   compare.hip   count, scan and emit over the tiles of the batch's runs intersected with the other side's
 //   linekeys.hip  a key per line: count and hash per tile, a chain per block, a record per newline at its rank (line_key.h)
+//   cut.hip       fields or byte columns of the lines: a summary per tile, one chain over the batch from the state the batch in
+//                 front left, count, scan, and a byte-granular compaction through LDS (cut_plan.h)
 // What they share stands here: the device helpers of a tile (its segment, its span of bounded aligned vectors, the 16-byte funnel,
 // the byte tests over 16 bytes, the scan of the tile counts) and, on the host, the verdicts of a call, the check of a stream
 // against its index and the count-then-emit round of the search and the compare.  Their host arithmetic (windows, runs,

@@ -1,6 +1,7 @@
 // scan_plan.h -- host arithmetic of the consumers of the pass engine (range_engine.h): the window of a call and the blocks under
 // it, the good blocks of a decoded batch as runs, two sides' runs as tiled segments (compare.hip), a batch's segments with the carry
-// between batches (search.hip) and where a line question is answered (lines.hip).  Plain integers and vectors: offsets, sizes,
+// between batches (search.hip) and where a line question is answered (lines.hip; linekeys.hip and cut.hip route the two ends of
+// their window of lines by it; the cut's own arithmetic is cut_plan.h).  Plain integers and vectors: offsets, sizes,
 // verdict bytes, device addresses as uint64_t.  No HIP in here (tests/host/scan_plan_check.cc compiles it with the host compiler).
 #pragma once
 #include <stddef.h>

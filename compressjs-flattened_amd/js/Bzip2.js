@@ -378,6 +378,34 @@ Bzip2.diffLines = function (inStreamA, indexA, lineIndexA, inStreamB, indexB, li
   for (var j = 0; j < d.hunks.length; j += 4) { hunks.push({ aFirst: d.hunks[j], aCount: d.hunks[j + 1], bFirst: d.hunks[j + 2], bCount: d.hunks[j + 3] }); }
   return { hunks: hunks, edits: d.edits, common: d.common, minimal: d.minimal };
 };
+// The column cut (cjs_bzip2_cut): `bzcat | cut -f LIST -d D` / `cut -b LIST`, selected and packed on the GPU; only the selected bytes
+// come back, as a Buffer.  opts: {fields | bytes (exactly one): a cut-style string ("1,3-5,7-") or an array of numbers and [lo, hi]
+// pairs (hi null: to the end of the line); delimiter = '\t' (one byte: a string, a Buffer or a number); first = 0, count = to the
+// last line}.  A line without the delimiter is a line of one field (GNU cut prints it whole).  A damaged block inside the window
+// throws; every error carries errorCode and ends in the library's detail.
+function cutList(spec) {
+  if (typeof spec === 'string') { return spec; }
+  var flat = [];
+  for (var i = 0; i < spec.length; i++) {
+    if (Array.isArray(spec[i])) { flat.push(spec[i][0], spec[i][1] === null || spec[i][1] === undefined ? -1 : spec[i][1]); } else { flat.push(spec[i], spec[i]); }
+  }
+  return Float64Array.from(flat);
+}
+Bzip2.cutLines = function (inStream, index, lineIndex, opts) {
+  var input = common.coerceInput(inStream), o = opts || {}, r;
+  if ((o.fields === undefined || o.fields === null) === (o.bytes === undefined || o.bytes === null)) { throw new TypeError('exactly one of fields and bytes must be given'); }
+  var byBytes = o.fields === undefined || o.fields === null, d = o.delimiter === undefined ? '\t' : o.delimiter;
+  if (typeof d !== 'number') {
+    var raw = typeof d === 'string' ? Buffer.from(d, 'latin1') : Buffer.from(common.coerceInput(d).bytes);
+    if (raw.length !== 1) { throw new TypeError('the delimiter is one byte'); }
+    d = raw[0];
+  }
+  try {
+    r = common.addon().bzip2Cut(input.bytes, index, lineIndex, byBytes ? 1 : 0, d, cutList(byBytes ? o.bytes : o.fields), o.first === undefined ? 0 : o.first,
+                                o.count === undefined || o.count === null ? -1 : o.count);
+  } catch (e) { rethrowWithDetail(e); }
+  return Buffer.from(r.buffer, r.byteOffset, r.length);
+};
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

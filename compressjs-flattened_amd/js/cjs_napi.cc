@@ -50,6 +50,9 @@ struct Api {
   int (*line_keys)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint64_t, cjs_bz_linekey*, size_t, cjs_bz_linekeys_info*,
                    const cjs_opts*) = nullptr;
   int (*line_keys_diff)(const cjs_bz_linekey*, size_t, const cjs_bz_linekey*, size_t, uint64_t, cjs_bz_hunk*, size_t, cjs_bz_ldiff_info*) = nullptr;
+  int (*cut)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint32_t, uint32_t, const cjs_cut_range*, uint32_t, uint8_t**,
+             size_t*, cjs_bz_cut_info*, const cjs_opts*) = nullptr;
+  int (*cut_list_parse)(const char*, cjs_cut_range*, uint32_t, uint32_t*) = nullptr;
   int (*enc_create)(cjs_bz_enc**, int, size_t, const cjs_opts*) = nullptr;
   int (*enc_write)(cjs_bz_enc*, const uint8_t*, size_t) = nullptr;
   int (*enc_finish)(cjs_bz_enc*) = nullptr;
@@ -99,6 +102,7 @@ bool load_api() {
   SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
   SYM(line_keys, "cjs_bzip2_line_keys") SYM(line_keys_diff, "cjs_line_keys_diff")
+  SYM(cut, "cjs_bzip2_cut") SYM(cut_list_parse, "cjs_cut_list_parse")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
   SYM(enc_index, "cjs_bzip2_enc_index") SYM(compress_indexed, "cjs_bzip2_compress_indexed")
@@ -605,6 +609,70 @@ napi_value bzip2_line_keys(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// bzip2Cut(input, index, lineIndex, mode, delim, list, first, count) -> Uint8Array (Bzip2.cutLines): the fields (mode 0, delimiter
+// byte delim) or byte positions (mode 1) that `list` selects of lines first .. first + count - 1 (count < 0: to the last), each
+// line's output behind the other's (cjs_bzip2_cut).  list: a cut-style string ("1,3-5,7-"; cjs_cut_list_parse) or a Float64Array of
+// (lo, hi) pairs, hi < 0: to the end of the line.  The result is an external ArrayBuffer over the library's buffer.
+napi_value bzip2_cut(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 8; napi_value argv[8];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *lp = nullptr; size_t n = 0, in = 0, ln = 0;
+  uint32_t mode = 0, delim = 0;
+  if (argc < 8 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &lp, &ln) ||
+      napi_get_value_uint32(env, argv[3], &mode) != napi_ok || napi_get_value_uint32(env, argv[4], &delim) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array line index, mode, delimiter byte, list, first, count)"); return nullptr;
+  }
+  uint64_t first = 0, count = ~0ull;
+  double c = -1;
+  napi_get_value_double(env, argv[7], &c);
+  if (!get_whole(env, argv[6], &first) || (c >= 0 && !get_whole(env, argv[7], &count)) || !(c >= 0 || c == -1)) {
+    napi_throw_type_error(env, nullptr, "first and count are integers from 0 to 2^53"); return nullptr;
+  }
+  std::vector<cjs_cut_range> sel(64);
+  uint32_t nsel = 0;
+  napi_valuetype kind = napi_undefined;
+  napi_typeof(env, argv[5], &kind);
+  if (kind == napi_string) {
+    size_t len = 0;
+    napi_get_value_string_utf8(env, argv[5], nullptr, 0, &len);
+    std::string list(len + 1, 0);
+    napi_get_value_string_utf8(env, argv[5], &list[0], len + 1, &len);
+    const int rc = api.cut_list_parse(list.c_str(), sel.data(), 64, &nsel);
+    if (rc != 0) return throw_code(env, rc);
+  } else {
+    bool is_ta = false;
+    napi_is_typedarray(env, argv[5], &is_ta);
+    napi_typedarray_type t = napi_int8_array; size_t len = 0; void* d = nullptr; napi_value ab; size_t off = 0;
+    if (is_ta) napi_get_typedarray_info(env, argv[5], &t, &len, &d, &ab, &off);
+    if (!is_ta || t != napi_float64_array || (len & 1)) { napi_throw_type_error(env, nullptr, "list is a string or a Float64Array of (lo, hi) pairs"); return nullptr; }
+    const double* q = (const double*)d;
+    sel.resize(len / 2 ? len / 2 : 1);
+    for (size_t k = 0; k < len / 2; k++) {
+      const double lo = q[2 * k], hi = q[2 * k + 1] < 0 ? 4294967295.0 : q[2 * k + 1];
+      if (!(lo >= 0 && lo <= 4294967295.0 && hi <= 4294967295.0 && lo == (double)(uint32_t)lo && hi == (double)(uint32_t)hi)) {
+        napi_throw_type_error(env, nullptr, "a unit number is an integer that fits 32 bits"); return nullptr;
+      }
+      sel[k].lo = (uint32_t)lo; sel[k].hi = (uint32_t)hi;
+    }
+    nsel = len / 2 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(len / 2);      // (the library refuses none and more than 64)
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_lines* lt = nullptr;
+  rc = api.lines_load(lp ? lp : &dummy, ln, ix, &lt);
+  if (rc != 0) { api.index_destroy(ix); return throw_code(env, rc); }
+  uint8_t* out = nullptr; size_t out_n = 0;
+  cjs_bz_cut_info ci;
+  rc = api.cut(p ? p : &dummy, n, ix, lt, first, count, mode, delim, sel.data(), nsel, &out, &out_n, &ci, nullptr);
+  if (rc != 0) throw_code(env, rc);                           // (the detail is read before the next call of the library on this thread)
+  api.lines_destroy(lt);
+  api.index_destroy(ix);
+  return rc != 0 ? nullptr : wrap_result(env, out, out_n);
+}
+
 // lineKeysDiff(keysA, keysB, maxEdits) -> { hunks: Float64Array, edits, common, minimal } (Bzip2.diffLines): the line diff of two
 // arrays of 16-byte records on the host (cjs_line_keys_diff); hunks holds four numbers per hunk: aFirst, aCount, bFirst, bCount.
 napi_value line_keys_diff(napi_env env, napi_callback_info info) {
@@ -1045,6 +1113,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2LineKeys", nullptr, bzip2_line_keys, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"lineKeysDiff", nullptr, line_keys_diff, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2Cut", nullptr, bzip2_cut, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2CompressIndexed", nullptr, bzip2_compress_indexed, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncIndex", nullptr, enc_index, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncCreate", nullptr, enc_create, nullptr, nullptr, nullptr, napi_default, nullptr},

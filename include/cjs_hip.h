@@ -442,6 +442,56 @@ int cjs_bzip2_line_keys_device(const uint8_t *d_in, size_t n, const cjs_bz_index
 int cjs_stage_line_keys(const uint8_t *text, size_t n, uint64_t seed, cjs_bz_linekey *keys, size_t cap, size_t *n_lines);
 int cjs_line_keys_diff(const cjs_bz_linekey *a, size_t na, const cjs_bz_linekey *b, size_t nb, uint64_t max_edits, cjs_bz_hunk *hunks,
                        size_t cap, cjs_bz_ldiff_info *info);
+/* cjs_bzip2_cut: fields or byte columns of the lines of an indexed stream (`bzcat x.bz2 | cut -f LIST` / `cut -b LIST`), selected
+ * and packed on the GPU while the blocks stand decoded there: only the selected bytes leave it.
+ * The WINDOW is lines [first, min(first + count, N + 1)) as the line table numbers them, as in cjs_bzip2_line_keys: line N is the
+ * unterminated tail, the add saturates, info->n_lines is the clipped count.  A window starts at a line start.
+ * The OUTPUT of one line (its bytes without the newline):
+ *   CJS_CUT_FIELDS, delimiter d (any byte value but 0x0A): the fields are the line split at every d, numbered from 1; the
+ *     selected fields that are present, in input order, joined by d, then "\n".  Per byte: a field byte is written iff its field
+ *     is selected; the delimiter that opens field k iff k is selected and the selection holds a field below k; a newline always.
+ *   CJS_CUT_BYTES: the bytes at the selected 1-based positions of the line, then "\n" (delim is ignored).
+ *   The tail line, if it is inside the window and not empty, is written like any line with a "\n" appended; an empty tail line
+ *   writes nothing.
+ * The output of the call is the concatenation: what `cut -d d -f LIST` / `cut -b LIST` writes under LC_ALL=C, with ONE
+ * DIFFERENCE: a line WITHOUT the delimiter is a line of one field here (GNU cut prints such a line whole whatever the list says).
+ * -s, --complement and --output-delimiter are not offered.
+ * The SELECTION: 1 .. 64 ranges, 1-based and closed, 1 <= lo <= hi, hi == 0xFFFFFFFF: to the end of the line; they may overlap
+ * and come in any order (the library sorts and merges them).  The unit counter of a line (delimiters, or bytes) is 32 bits and
+ * saturates at 0xFFFFFFFE: every further unit of such a line keeps the last number, nothing wraps.
+ * The TOUCHED blocks are those of cjs_bzip2_line_keys, by the same passes.  The output has no place for a hole: a touched block
+ * that is not GOOD fails the call with CJS_E_DATA_ERROR, cjs_last_error_detail() being the text cjs_bzip2_read_ranges gives for
+ * that block, info->n_bad_blocks / first_bad_block filled (host form: no buffer; device form: unspecified bytes below out_cap).
+ * A block whose newlines differ from the table's: CJS_E_DATA_ERROR, "line table does not match the stream at block <k>".
+ * Per decoded inverse-BWT batch, over 16 KiB tiles of the blocks: a summary per tile (newlines, units behind the last newline), one
+ * workgroup chains the summaries across the tiles and blocks of the batch from the state the previous batch left (line number,
+ * unit counter, open line: carried ON THE DEVICE side of the call, a few words per batch come back), a count per tile, a scan, and
+ * an emit that packs the tile's selected bytes in LDS and stores them at the scanned offset.  No atomics decide an order.  The
+ * result does not depend on CJS_RANGE_PASS_BLOCKS, CJS_DEC_GROUP_BYTES, CJS_DEC_BATCH_ELEMS or CJS_DEC_ROW_BYTES.
+ * Host form: *out is allocated by the library (cjs_free) and grows batch by batch; a buffer is returned even for empty output.
+ * Device form: no byte of d_out at or past out_cap is ever written; output above out_cap: the remaining passes still run to count
+ * and the call returns CJS_E_OUTPUT_TOO_SMALL with *out_need = the full size (d_out = NULL, out_cap = 0: the size query, on the
+ * same path).  On success *out_need = the bytes written.  The window's bytes + 1 are always room enough.
+ * CJS_E_INVALID_ARG before the device is touched: nsel == 0 or > 64, NULL sel, lo == 0, lo > hi, delim > 255, delim == 0x0A in
+ * fields mode, an unknown mode, NULL idx / lines / info / out / out_n / out_need, NULL in with n > 0, NULL d_out with out_cap > 0,
+ * n != the index's stream_bytes, a foreign table.  CJS_DEBUG: one "[cjs cut]" line per call on stderr.
+ * cjs_stage_cut EXISTS FOR TESTS; no product path calls it: the same rule walked byte by byte over the plain host buffer
+ * text[0 .. n) (csrc/cut_plan.h), without a device.  *out_n = the full size; above cap: CJS_E_OUTPUT_TOO_SMALL, out[0 .. cap) written.
+ * cjs_cut_list_parse: a cut-style LIST ("1,3-5,7-", "-4") as ranges; CJS_E_INVALID_ARG for an empty list or item, a zero, a
+ * decreasing range, a "-" alone, any other character, a number above 0xFFFFFFFE, more than `cap` items. */
+typedef struct { uint32_t lo, hi; } cjs_cut_range;   /* 1-based, closed; hi == 0xFFFFFFFF: to the end of the line */
+typedef struct { uint64_t n_lines, out_bytes, blocks_decoded, n_bad_blocks, first_bad_block; } cjs_bz_cut_info;
+#define CJS_CUT_FIELDS 0u
+#define CJS_CUT_BYTES  1u
+int cjs_bzip2_cut(const uint8_t *in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first, uint64_t count,
+                  uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel, uint8_t **out, size_t *out_n,
+                  cjs_bz_cut_info *info, const cjs_opts *opts);
+int cjs_bzip2_cut_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first,
+                         uint64_t count, uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel, uint8_t *d_out,
+                         size_t out_cap, size_t *out_need, cjs_bz_cut_info *info, const cjs_opts *opts);
+int cjs_stage_cut(const uint8_t *text, size_t n, uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel,
+                  uint8_t *out, size_t cap, size_t *out_n);
+int cjs_cut_list_parse(const char *list, cjs_cut_range *sel, uint32_t cap, uint32_t *nsel);
 /* cjs_bzip2_compare: `cmp` over the address space of cjs_bzip2_read_ranges ([0, total_bytes) of the index), done on the GPU: is
  * the decoded stream equal to `other`, and if not, where and with which bytes?  The decoded bytes never leave the GPU, 16 bytes
  * per reported difference do.  other[k] is compared with decoded byte other_off + k.  The COMPARED SPAN is
