@@ -142,6 +142,56 @@ extern "C" int cjs_stage_mtf(const uint8_t* U, const uint8_t* blocks, size_t n, 
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
+// Blocks of different lengths, one per slot of `stride` bytes, as both callers of mtf_run hand them over: the pipeline's rows start
+// at odd addresses (stride = level * 100000 - 19), the batch compressor's at multiples of 16.  What the slots hold behind a block's
+// end is the caller's (hole bytes in `blocks`), and the whole workspace is filled with `work_fill` before the run: the product
+// reuses its workspace between calls, so every kernel meets stale heads, lists and segment keys there.
+// The head kernels read aligned 32-bit words around a thread's first byte p0 < len: al[-1] .. al[4], the last byte of which lies
+// at most 16 bytes behind p0, so at most 16 bytes behind a block's last byte.  Inside the array that is the next slot; behind the
+// last slot batch.hip has its 16 bytes of slack (and, with rows a multiple of 16, never reads past the row), and pipeline.hip's
+// d_U is followed in its arena by d_pidx and 64 KiB of slack (Arena::take rounds to 256): both cover the reach.  d_U is carved
+// here as batch.hip carves it.
+extern "C" int cjs_stage_mtf_var(const uint8_t* blocks, uint32_t nb, uint32_t stride, const uint32_t* len, int work_fill, uint16_t* A,
+                                 uint32_t* npos, uint32_t* freq, uint32_t* alphabet, uint8_t* alist, uint32_t* nheads, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (nb == 0 || nb > 65535 || stride == 0) return CJS_E_INVALID_ARG;
+  if (((size_t)stride + 4095) / 4096 > 1024) return CJS_E_INVALID_ARG;      // mtf_run scans a block's tile counts in one workgroup
+  for (uint32_t k = 0; k < nb; k++) if (len[k] == 0 || len[k] > stride) return CJS_E_INVALID_ARG;
+  const size_t e = (size_t)nb * stride;
+  Arena arena;
+  const size_t wbytes = MtfWork::bytes_needed(nb, stride);
+  CJS_TRY(arena.init(wbytes + e + 16 + 4 * (size_t)nb + 65536));
+  MtfWork w;
+  CJS_TRY(w.carve(arena, nb, stride));
+  const size_t wend = arena.used;                          // the workspace is arena.base[0 .. wend)
+  uint8_t* d_U = arena.take<uint8_t>(e + 16);
+  uint32_t* d_len = arena.take<uint32_t>(nb);
+  if (!d_U || !d_len) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  CJS_HIP_TRY(hipMemsetAsync(arena.base, work_fill & 0xFF, wend, s));
+  CJS_HIP_TRY(hipMemsetAsync(d_U + e, work_fill & 0xFF, 16, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_U, blocks, e, hipMemcpyHostToDevice, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_len, len, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
+  CJS_TRY(mtf_run(s, w, d_U, nb, d_len));                  // (refuses the strides whose tile counts it cannot scan)
+  std::vector<uint32_t> hnpos(nb);
+  CJS_HIP_TRY(hipMemcpyAsync(hnpos.data(), w.b.npos, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(freq, w.b.freq, 4 * 258 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(alphabet, w.b.asz, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(alist, w.b.alist, 256 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(nheads, w.b.nheads, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  for (uint32_t k = 0; k < nb; k++) {
+    if (hnpos[k] == 0 || hnpos[k] > stride + 1) return CJS_E_OUTPUT_TOO_SMALL;       // (a row of A holds stride + 1 symbols)
+    CJS_HIP_TRY(hipMemcpyAsync(A + (size_t)k * ((size_t)stride + 1), w.b.A + (size_t)k * w.b.a_stride, 2 * (size_t)hnpos[k], hipMemcpyDeviceToHost, s));
+  }
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  for (uint32_t k = 0; k < nb; k++) npos[k] = hnpos[k];
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
 extern "C" int cjs_stage_huff(const uint16_t* A, uint32_t npos, uint32_t alphabet, uint8_t* selectors, uint8_t* lengths,
                               uint32_t* ngroups, const cjs_opts* opts) {
   CJS_GUARD_BEGIN

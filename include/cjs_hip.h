@@ -743,6 +743,16 @@ int cjs_stage_rle1(const uint8_t *in, size_t n, int level, uint8_t *blocks, size
  * cjs_stage_bwt; A = u16 symbols with stride block_len+1 */
 int cjs_stage_mtf(const uint8_t *U, const uint8_t *blocks, size_t n, int block_len, uint16_t *A, uint32_t *npos,
                   uint32_t *freq /* nb*258 */, uint32_t *alphabet /* nb */, const cjs_opts *opts);
+/* The same over blocks of different lengths, as both compressors call the stage: blocks = nb slots of stride bytes (any stride
+ * >= 1, odd ones included: the pipeline's rows start at odd addresses, the batch compressor's at multiples of 16), block k = the
+ * first len[k] bytes of slot k; what the slots hold behind a block's end must not matter.  The whole workspace is filled with the
+ * byte work_fill before the run, as a workspace left behind by an earlier call would be.  Out, per block: A (row of stride + 1
+ * symbols, npos[k] of them defined), npos, freq[258], alphabet, alist[256] (the used byte values, ascending, alphabet[k] of them
+ * defined) and nheads (the number of runs).  CJS_E_INVALID_ARG, before anything is launched, for nb == 0 or nb > 65535,
+ * stride == 0, any len[k] that is 0 or exceeds stride, and a stride with more tiles than the stage scans (above 4 Mi). */
+int cjs_stage_mtf_var(const uint8_t *blocks, uint32_t nb, uint32_t stride, const uint32_t *len, int work_fill, uint16_t *A,
+                      uint32_t *npos, uint32_t *freq /* nb*258 */, uint32_t *alphabet /* nb */, uint8_t *alist /* nb*256 */,
+                      uint32_t *nheads /* nb */, const cjs_opts *opts);
 /* Huffman tables + selectors (J/Bzip2_joined_.js:1989-2054,2147-2163) for one symbol stream */
 int cjs_stage_huff(const uint16_t *A, uint32_t npos, uint32_t alphabet, uint8_t *selectors, uint8_t *lengths /* 6*258 */,
                    uint32_t *ngroups, const cjs_opts *opts);

@@ -280,6 +280,7 @@ class HipLib(_StreamLib):
             "cjs_stage_bwt_var": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
             "cjs_stage_rle1": [V, S, I, V, S, V, V, V, ctypes.c_long, ctypes.POINTER(ctypes.c_long), V],
             "cjs_stage_mtf": [V, V, S, I, V, V, V, V, V],
+            "cjs_stage_mtf_var": [V, ctypes.c_uint32, ctypes.c_uint32, V, I, V, V, V, V, V, V, V],
             "cjs_stage_huff": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
             "cjs_stage_huff_blocks": [V, S, ctypes.c_uint32, V, V, V, V, V, I, V, V, V, V, S, V, V],
             "cjs_stage_bwtc_entropy_decode": [u8p, S, PP, PS, V, V, ctypes.c_long, ctypes.POINTER(I)],
@@ -441,6 +442,29 @@ class HipLib(_StreamLib):
         rc = self.L.cjs_stage_mtf(U.ctypes.data, blocks.ctypes.data, U.size, block_len, A.ctypes.data, npos.ctypes.data,
                                   freq.ctypes.data, asz.ctypes.data, None)
         return rc, A.reshape(nb, block_len + 1), npos, freq.reshape(nb, 258), asz
+
+    def stage_mtf_var(self, blocks, stride, hole_fill=0, work_fill=0):
+        """MTF + RLE2 of blocks of different lengths, block k in slot k of `stride` bytes (cjs_stage_mtf_var).  hole_fill: one byte
+        for every hole, or one per block (the hole behind block k); the workspace is filled with `work_fill` before the run.
+        Returns (rc, A[nb][stride + 1], npos, freq[nb][258], asz, alist[nb][256], nheads)"""
+        blocks = [as_u8(b) for b in blocks]
+        nb = len(blocks)
+        lens = np.array([b.size for b in blocks], dtype=np.uint32)
+        slots = np.zeros((max(nb, 1), stride), dtype=np.uint8)
+        slots[:] = np.asarray(hole_fill, dtype=np.uint8).reshape(-1, 1)
+        for k, b in enumerate(blocks):
+            slots[k, : min(b.size, stride)] = b[:stride]        # (a block longer than its slot: the entry point refuses the call)
+        m = max(nb, 1)
+        A = np.zeros((m, stride + 1), dtype=np.uint16)
+        npos, asz, nheads = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+        freq = np.zeros((m, 258), dtype=np.uint32)
+        alist = np.zeros((m, 256), dtype=np.uint8)
+        keep = lens if nb else np.zeros(1, dtype=np.uint32)
+        rc = self.L.cjs_stage_mtf_var(slots.ctypes.data, nb, stride, keep.ctypes.data, work_fill, A.ctypes.data, npos.ctypes.data,
+                                      freq.ctypes.data, asz.ctypes.data, alist.ctypes.data, nheads.ctypes.data, None)
+        if rc:
+            return rc, None, None, None, None, None, None
+        return 0, A[:nb], npos[:nb], freq[:nb], asz[:nb], alist[:nb], nheads[:nb]
 
     def stage_huff(self, A, alphabet):
         A = np.ascontiguousarray(A, dtype=np.uint16)

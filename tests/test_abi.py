@@ -92,6 +92,20 @@ def test_stage_bwt_var_needs_a_device():
         assert rc == -30 and U is None and pidx is None          # CJS_E_NO_DEVICE before any argument is looked at
 
 
+def test_stage_mtf_var_needs_a_device():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import support
+    hip = support.HipLib()
+    assert "cjs_stage_mtf_var" not in hip.missing
+    for blocks, stride in (([b"nnbaaa", b"ba"], 16), ([b"nnbaaa"], 7), ([b"nnbaaa"], 5), ([b""], 16), ([], 16)):
+        res = hip.stage_mtf_var(blocks, stride, 0xFF, 0x61)
+        assert res[0] == -30 and all(x is None for x in res[1:])          # CJS_E_NO_DEVICE before any argument is looked at
+
+
 def test_free_and_trim_need_no_device():
     # cjs_free takes what the library handed out (plain malloc or a pinned result buffer) and, like free(), a null pointer;
     # memory it does not know is plain malloc'd memory.  cjs_trim with nothing cached is a no-op.  Neither needs a GPU.

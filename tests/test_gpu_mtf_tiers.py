@@ -11,44 +11,12 @@ target fails instead of passing vacuously.  All cases compare `A`, `npos` and `f
 import numpy as np
 import pytest
 
+from mtf_cases import heads_from_ranks
+
 CHUNK = 512        # heads per lane (MTF_CHUNK)
 WAVE = 64
 EXACT_RANKS = [3, 4, 7, 8, 15, 16, 31, 32, 63, 64, 65]      # + asz - 1; either side of a word, a tier and the register part
 ALPHABETS = [2, 5, 17, 65, 66, 256]
-
-
-def _alphabet(asz):
-    """asz byte values, ascending, 0 and 255 among them (when asz >= 2)"""
-    return [0] if asz == 1 else sorted(set(int(round(i * 255.0 / (asz - 1))) for i in range(asz)))
-
-
-def heads_from_ranks(asz, ranks):
-    """Bytes whose i-th run head has MTF rank ranks[i] (every rank in 1 .. asz-1; runs of length one).  Symbols of the alphabet
-    the ranks never reach are appended once each at the end, so that the block does have `asz` symbols; returns (bytes, the
-    ranks of ALL heads, the closing ones included)."""
-    syms = _alphabet(asz)
-    assert len(syms) == asz
-    lst = list(syms)
-    seen = set()
-    out = bytearray()
-    all_ranks = []
-    for r in ranks:
-        assert 1 <= r < asz
-        s = lst.pop(r)
-        lst.insert(0, s)
-        out.append(s)
-        seen.add(s)
-        all_ranks.append(r)
-    for s in syms:
-        if s not in seen:
-            r = lst.index(s)
-            if r == 0:          # only when no rank was asked for at all: the lone first head
-                assert not out
-            lst.pop(r)
-            lst.insert(0, s)
-            out.append(s)
-            all_ranks.append(r)
-    return np.frombuffer(bytes(out), dtype=np.uint8), np.asarray(all_ranks, dtype=np.int64)
 
 
 def oracle_side(oracle, U, ranks):
