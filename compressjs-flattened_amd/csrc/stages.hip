@@ -3,6 +3,7 @@
 #include "cjs_internal.h"
 #include "host.h"
 #include "rle1.h"
+#include "crc.h"
 #include "mtf.h"
 #include "huff.h"
 #include <algorithm>
@@ -68,41 +69,162 @@ extern "C" int cjs_stage_bwt_var(const uint8_t* blocks, uint32_t nb, uint32_t st
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }
 
+// Stage 0 over one stream with a block capacity of the caller's choice: `cap` is a run-time argument of every kernel of the stage,
+// and a small one puts thousands of block boundaries, each at another chunk phase and subtile offset, into an input of a few
+// tiles.  world > 1 makes the tile tables share by share, as the ranks of a sharded job do (pipeline.hip, cjs_bzip2_shard_tiles /
+// shard_blocks_impl), into one buffer laid out as their all-gather leaves it; range_blocks > 0 carves the workspace for that
+// many blocks per rle1_finish call and takes the blocks through it window by window, as the streaming compressor does.
+// work_fill >= 0: the workspace, the share buffer and d_blocks are filled with that byte first (the product reuses them).
+//
+// The floor of cap is 2.  Rle1Work::max_blocks_for divides by cap * 4 / 5, which is 0 for cap == 1.  Nothing else in the stage
+// asks for more: run_fill_input and emitted_fresh hold from cap 1 on (rem == 0 only from cap 5 on, where q >= 1);
+// max_segs_for(cap) covers the 51 input bytes per output byte of a block at every cap (a block of cap < 5 ends within its
+// first four bytes of a run); subpre counts the bytes of one tile (at most 5120) whatever the cap; and the walk's
+// speculation needs two targets never to fall on one input byte, which holds because a byte emits at most 2 <= cap bytes.
+// The ceiling is the product's largest capacity (level 9).  rle1_finish launches one row of CRC workgroups per block of a
+// window, so a window of more than 65535 blocks is refused as well.
+constexpr uint32_t RLE1_CAP_FLOOR = 2, RLE1_CAP_CEIL = 9 * 100000 - 19;
+extern "C" int cjs_stage_rle1_cap(const uint8_t* in, size_t n, uint32_t cap, uint32_t world, uint32_t range_blocks, int work_fill,
+                                  uint8_t* blocks, size_t blocks_cap, uint32_t* block_len, uint32_t* block_crc, uint64_t* block_start,
+                                  uint64_t* block_end, long cap_blocks, long* nblocks, uint32_t* last_len, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (cap < RLE1_CAP_FLOOR || cap > RLE1_CAP_CEIL || world == 0 || world > 65535 || !nblocks) return CJS_E_INVALID_ARG;
+  *nblocks = 0;
+  if (last_len) *last_len = 0;
+  if (n == 0) return 0;
+  const size_t maxb = Rle1Work::max_blocks_for(n, cap);
+  const size_t rows = range_blocks ? std::min<size_t>(range_blocks, maxb) : maxb;      // blocks per rle1_finish call
+  if (rows > 65535) return CJS_E_INVALID_ARG;
+  const uint32_t Tn = Rle1Work::tiles_for(n), tpr = Rle1Work::tiles_per_rank(n, world);
+  const size_t share = Rle1Work::share_bytes(tpr), shares = world > 1 ? share * world : 0;
+  Arena arena;
+  CJS_TRY(arena.init(Rle1Work::bytes_needed(n, cap, rows) + n + rows * cap + shares + 65536));
+  Rle1Work w;
+  CJS_TRY(w.carve(arena, n, cap, rows));
+  uint8_t* d_blocks = arena.take<uint8_t>(rows * cap);
+  uint8_t* d_shares = shares ? arena.take<uint8_t>(shares) : nullptr;
+  const size_t fill_end = arena.used;                      // workspace, block rows and shares are arena.base[0 .. fill_end)
+  uint8_t* d_in = arena.take<uint8_t>(n);
+  if (!d_in || !d_blocks || (shares && !d_shares)) return CJS_E_OUT_OF_MEMORY;
+  Stream s;
+  CJS_HIP_TRY(hipStreamCreate(s.put()));
+  if (work_fill >= 0) CJS_HIP_TRY(hipMemsetAsync(arena.base, work_fill & 0xFF, fill_end, s));
+  CJS_HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s));
+  uint32_t nb = 0, ll = 0;
+  if (world == 1) CJS_TRY(rle1_run(s, w, d_in, n, &nb, &ll));
+  else {
+    for (uint32_t r = 0; r < world; r++) {                 // every rank in turn; the ranks behind the last tile have no share to make
+      const uint64_t t0 = (uint64_t)r * tpr;
+      if (t0 < Tn) CJS_TRY(rle1_tiles(s, w, d_in, n, (uint32_t)t0, (uint32_t)std::min<uint64_t>(Tn, t0 + tpr), d_shares + (size_t)r * share, tpr));
+    }
+    CJS_TRY(rle1_tables_from_shares(s, w, n, d_shares, tpr));
+    CJS_TRY(rle1_walk_run(s, w, d_in, n, &nb, &ll));
+  }
+  *nblocks = (long)nb;
+  if (last_len) *last_len = ll;
+  if (nb > maxb) return CJS_E_HIP;                          // (the walk counted past its table: max_blocks_for is no bound)
+  if ((long)nb > cap_blocks || (size_t)nb * cap > blocks_cap) return CJS_E_OUTPUT_TOO_SMALL;
+  for (uint32_t first = 0; first < nb; first += (uint32_t)rows) {
+    const uint32_t cnt = (uint32_t)std::min<size_t>(rows, nb - first);
+    CJS_TRY(rle1_finish(s, w, d_in, n, first, cnt, d_blocks));
+    CJS_HIP_TRY(hipMemcpyAsync(blocks + (size_t)first * cap, d_blocks, (size_t)cnt * cap, hipMemcpyDeviceToHost, s));
+    CJS_HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (nb) {
+    std::vector<RleBlock> hb(nb);
+    CJS_HIP_TRY(hipMemcpy(hb.data(), w.blocks, sizeof(RleBlock) * nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(block_len, w.block_len, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    CJS_HIP_TRY(hipMemcpy(block_crc, w.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < nb; k++) { block_start[k] = hb[k].s; if (block_end) block_end[k] = hb[k].e; }
+  }
+  return 0;
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
 extern "C" int cjs_stage_rle1(const uint8_t* in, size_t n, int level, uint8_t* blocks, size_t blocks_cap,
                               uint32_t* block_len, uint32_t* block_crc, uint64_t* block_start, long cap_blocks, long* nblocks,
                               const cjs_opts* opts) {
   CJS_GUARD_BEGIN
   CJS_TRY(select_device(opts));
   if (level < 1 || level > 9) return CJS_E_BAD_LEVEL;
-  const uint32_t cap = (uint32_t)level * 100000u - 19u;
-  *nblocks = 0;
-  if (n == 0) return 0;
+  return cjs_stage_rle1_cap(in, n, (uint32_t)level * 100000u - 19u, 1u, 0u, -1, blocks, blocks_cap, block_len, block_crc, block_start, nullptr,
+                            cap_blocks, nblocks, nullptr, opts);
+  CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
+}
+
+// The three kernels of rle1_batch.hip, each on its own and each with exactly the arrays of the caller (none of batch.hip's host
+// logic between them): rle1_batch_len over all `count` inputs in[se[2k] .. se[2k+1]); rle1_batch_walk over the inputs item[0 ..
+// nitem) with the block slots tbase[] grants them, into a table of table_slots >= tbase[nitem] entries; rle1_batch_materialize
+// and, as run_sub calls it right behind, crc_ranges over the nmat blocks of the caller's table (s / e relative to `in`).  The
+// walk's table, nblk[] and the rows are filled with work_fill first, so that what a kernel left untouched can be told apart.
+extern "C" int cjs_stage_rle1_batch(const uint8_t* in, size_t in_n, const uint64_t* se, uint32_t count, uint32_t cap, int work_fill,
+                                    uint64_t* len2, const uint32_t* item, const uint32_t* tbase, uint32_t nitem, uint32_t table_slots,
+                                    uint64_t* walk_s, uint64_t* walk_e, uint32_t* walk_len, uint32_t* nblk, const uint64_t* mat_s,
+                                    const uint64_t* mat_e, const uint32_t* mat_len, uint32_t nmat, uint32_t stride, uint8_t* rows,
+                                    uint32_t* row_crc, const cjs_opts* opts) {
+  CJS_GUARD_BEGIN
+  CJS_TRY(select_device(opts));
+  if (cap < RLE1_CAP_FLOOR || cap > RLE1_CAP_CEIL || count > (1u << 20) || nitem > (1u << 20) || table_slots > (1u << 24) || nmat > 65535) return CJS_E_INVALID_ARG;
+  if (nitem && !count) return CJS_E_INVALID_ARG;
+  for (uint32_t k = 0; k < count; k++) if (se[2 * k] > se[2 * k + 1] || se[2 * k + 1] > in_n) return CJS_E_INVALID_ARG;
+  for (uint32_t j = 0; j < nitem; j++) if (item[j] >= count || tbase[j] > tbase[j + 1]) return CJS_E_INVALID_ARG;
+  if (nitem && tbase[nitem] > table_slots) return CJS_E_INVALID_ARG;
+  if (nmat && stride == 0) return CJS_E_INVALID_ARG;
+  size_t longest = 0;
+  for (uint32_t j = 0; j < nmat; j++) {
+    if (mat_s[j] > mat_e[j] || mat_e[j] > in_n || mat_len[j] > stride) return CJS_E_INVALID_ARG;
+    longest = std::max<size_t>(longest, mat_e[j] - mat_s[j]);
+  }
+  if (!count && !nmat) return 0;
+  const size_t segs = crc_segs_for(longest);
   Arena arena;
-  const size_t maxb = Rle1Work::max_blocks_for(n, cap);
-  CJS_TRY(arena.init(Rle1Work::bytes_needed(n, cap) + n + maxb * cap + 65536));
-  Rle1Work w;
-  CJS_TRY(w.carve(arena, n, cap));
-  uint8_t* d_in = arena.take<uint8_t>(n);
-  uint8_t* d_blocks = arena.take<uint8_t>(maxb * cap);
-  if (!d_in || !d_blocks) return CJS_E_OUT_OF_MEMORY;
+  CJS_TRY(arena.init(in_n + 16 + 24 * (size_t)count + 8 * ((size_t)nitem + 1) + sizeof(RleBlock) * ((size_t)table_slots + nmat) +
+                     (size_t)nmat * (stride + 4 * segs + 4) + 64 + 16 * 256 + 65536));
+  uint8_t* d_in = arena.take<uint8_t>(in_n + 16);          // (crc_ranges loads whole 16-byte words around a range)
+  uint64_t* d_se = arena.take<uint64_t>(2 * (size_t)count);
+  uint64_t* d_len2 = arena.take<uint64_t>(count);
+  uint32_t* d_item = arena.take<uint32_t>(nitem);
+  uint32_t* d_tbase = arena.take<uint32_t>((size_t)nitem + 1);
+  uint32_t* d_nblk = arena.take<uint32_t>(nitem);
+  RleBlock* d_tab = arena.take<RleBlock>(table_slots);
+  RleBlock* d_rb = arena.take<RleBlock>(nmat);
+  uint8_t* d_rows = arena.take<uint8_t>((size_t)nmat * stride);
+  uint32_t* d_seg = arena.take<uint32_t>((size_t)nmat * segs);
+  uint32_t* d_crc = arena.take<uint32_t>(nmat);
+  uint32_t* d_nb = arena.take<uint32_t>(16);
+  if (!d_in || !d_se || !d_len2 || !d_item || !d_tbase || !d_nblk || !d_tab || !d_rb || !d_rows || !d_seg || !d_crc || !d_nb) return CJS_E_OUT_OF_MEMORY;
   Stream s;
   CJS_HIP_TRY(hipStreamCreate(s.put()));
-  CJS_HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s));
-  uint32_t nb = 0;
-  const int rc = rle1_run(s, w, d_in, n, &nb);
-  *nblocks = (long)nb;
-  CJS_TRY(rc);
-  CJS_TRY(rle1_finish(s, w, d_in, n, 0, nb, d_blocks));
-  CJS_HIP_TRY(hipStreamSynchronize(s));
-  if ((long)nb > cap_blocks || (size_t)nb * cap > blocks_cap) return CJS_E_OUTPUT_TOO_SMALL;
-  if (nb) {
-    std::vector<RleBlock> hb(nb);
-    CJS_HIP_TRY(hipMemcpy(hb.data(), w.blocks, sizeof(RleBlock) * nb, hipMemcpyDeviceToHost));
-    CJS_HIP_TRY(hipMemcpy(block_len, w.block_len, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    CJS_HIP_TRY(hipMemcpy(block_crc, w.block_crc, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    CJS_HIP_TRY(hipMemcpy(blocks, d_blocks, (size_t)nb * cap, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < nb; k++) block_start[k] = hb[k].s;
+  CJS_HIP_TRY(hipMemsetAsync(arena.base, work_fill & 0xFF, arena.used, s));
+  if (in_n) CJS_HIP_TRY(hipMemcpyAsync(d_in, in, in_n, hipMemcpyHostToDevice, s));
+  if (count) {
+    CJS_HIP_TRY(hipMemcpyAsync(d_se, se, 16 * (size_t)count, hipMemcpyHostToDevice, s));
+    CJS_TRY(rle1_batch_len(s, d_in, d_se, count, cap, d_len2));
+    CJS_HIP_TRY(hipMemcpyAsync(len2, d_len2, 8 * (size_t)count, hipMemcpyDeviceToHost, s));
   }
+  std::vector<RleBlock> tab(table_slots);
+  if (nitem) {
+    CJS_HIP_TRY(hipMemcpyAsync(d_item, item, 4 * (size_t)nitem, hipMemcpyHostToDevice, s));
+    CJS_HIP_TRY(hipMemcpyAsync(d_tbase, tbase, 4 * ((size_t)nitem + 1), hipMemcpyHostToDevice, s));
+    CJS_TRY(rle1_batch_walk(s, d_in, d_se, d_item, d_tbase, nitem, cap, d_tab, d_nblk));
+    CJS_HIP_TRY(hipMemcpyAsync(nblk, d_nblk, 4 * (size_t)nitem, hipMemcpyDeviceToHost, s));
+  }
+  if (table_slots) CJS_HIP_TRY(hipMemcpyAsync(tab.data(), d_tab, sizeof(RleBlock) * table_slots, hipMemcpyDeviceToHost, s));
+  if (nmat) {
+    std::vector<RleBlock> rb(nmat);
+    for (uint32_t j = 0; j < nmat; j++) { rb[j] = RleBlock{}; rb[j].s = mat_s[j]; rb[j].e = mat_e[j]; rb[j].len = mat_len[j]; }
+    const uint32_t nbv = nmat;
+    CJS_HIP_TRY(hipMemcpyAsync(d_rb, rb.data(), sizeof(RleBlock) * nmat, hipMemcpyHostToDevice, s));
+    CJS_HIP_TRY(hipMemcpyAsync(d_nb, &nbv, 4, hipMemcpyHostToDevice, s));
+    CJS_HIP_TRY(hipStreamSynchronize(s));                  // (rb and nbv are this scope's)
+    CJS_TRY(rle1_batch_materialize(s, d_in, d_rb, nmat, stride, d_rows));
+    CJS_TRY(crc_ranges(s, d_in, d_rb, d_nb, nmat, (uint32_t)segs, d_seg, d_crc));
+    CJS_HIP_TRY(hipMemcpyAsync(rows, d_rows, (size_t)nmat * stride, hipMemcpyDeviceToHost, s));
+    if (row_crc) CJS_HIP_TRY(hipMemcpyAsync(row_crc, d_crc, 4 * (size_t)nmat, hipMemcpyDeviceToHost, s));
+  }
+  CJS_HIP_TRY(hipStreamSynchronize(s));
+  for (uint32_t q = 0; q < table_slots; q++) { walk_s[q] = tab[q].s; walk_e[q] = tab[q].e; walk_len[q] = tab[q].len; }
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
 }

@@ -739,6 +739,30 @@ int cjs_stage_bwt_var(const uint8_t *blocks, uint32_t nb, uint32_t stride, const
  * concatenated with stride = level*100000-19; per block length / crc / input start */
 int cjs_stage_rle1(const uint8_t *in, size_t n, int level, uint8_t *blocks, size_t blocks_cap,
                    uint32_t *block_len, uint32_t *block_crc, uint64_t *block_start, long cap, long *nblocks, const cjs_opts *opts);
+/* The same with a block capacity of the caller's choice (cjs_stage_rle1 is this with cap = level*100000-19, world 1,
+ * range_blocks 0, work_fill -1): blocks with stride cap; per block length, crc, input start and input end (block_end and last_len
+ * may be null); *last_len = length of the last block as the boundary walk hands it to the host.  world > 1: the tile tables are
+ * made share by share as the ranks of a sharded job make them (ranks without tiles included) and unpacked from one gathered
+ * buffer.  range_blocks > 0: the workspace is carved for that many blocks per pass and the blocks' bytes and CRCs are made window
+ * by window, [0, range_blocks), [range_blocks, 2*range_blocks), ...  work_fill 0..255: workspace, share buffer and device rows
+ * are filled with that byte first; < 0: left as allocated.  CJS_E_INVALID_ARG, before anything is launched, for cap < 2 (the
+ * block-count bound divides by cap*4/5), cap > 899981, world == 0 or > 65535, and more than 65535 blocks per pass. */
+int cjs_stage_rle1_cap(const uint8_t *in, size_t n, uint32_t cap, uint32_t world, uint32_t range_blocks, int work_fill,
+                       uint8_t *blocks, size_t blocks_cap, uint32_t *block_len, uint32_t *block_crc, uint64_t *block_start,
+                       uint64_t *block_end, long cap_blocks, long *nblocks, uint32_t *last_len, const cjs_opts *opts);
+/* The three stage-0 kernels of the batched compressor, each with exactly the caller's arrays.  Inputs k < count: in[se[2k] ..
+ * se[2k+1]).  (1) len2[k] = min(RLE1 length, cap + 1) << 1 | (last byte absorbed into a count byte; defined where the length is
+ * <= cap).  (2) the block walk over inputs item[0 .. nitem): blocks of item j into table slots tbase[j] .. tbase[j+1] (s / e
+ * relative to the input, len), their true number to nblk[j]; all table_slots >= tbase[nitem] slots come back in walk_s / walk_e /
+ * walk_len, filled with work_fill where the kernel wrote nothing.  (3) the RLE1 bytes of nmat blocks in[mat_s[j] .. mat_e[j]), the
+ * first mat_len[j] of them into rows + j*stride (rows pre-filled with work_fill), and the blocks' CRCs (row_crc may be null).
+ * CJS_E_INVALID_ARG, before anything is launched, for cap outside 2 .. 899981, ranges outside in or reversed, item[j] >= count,
+ * tbase not ascending or beyond table_slots, mat_len[j] > stride, nmat > 65535. */
+int cjs_stage_rle1_batch(const uint8_t *in, size_t in_n, const uint64_t *se, uint32_t count, uint32_t cap, int work_fill,
+                         uint64_t *len2, const uint32_t *item, const uint32_t *tbase, uint32_t nitem, uint32_t table_slots,
+                         uint64_t *walk_s, uint64_t *walk_e, uint32_t *walk_len, uint32_t *nblk, const uint64_t *mat_s,
+                         const uint64_t *mat_e, const uint32_t *mat_len, uint32_t nmat, uint32_t stride, uint8_t *rows,
+                         uint32_t *row_crc, const cjs_opts *opts);
 /* MTF + RLE2 (J/Bzip2_joined_.js:2064-2139) for nb blocks: U and block bytes with the same layout as
  * cjs_stage_bwt; A = u16 symbols with stride block_len+1 */
 int cjs_stage_mtf(const uint8_t *U, const uint8_t *blocks, size_t n, int block_len, uint16_t *A, uint32_t *npos,

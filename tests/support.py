@@ -205,16 +205,27 @@ class Oracle(_StreamLib):
 
     def rle1_blocks(self, data, level):
         """all RLE1 blocks of a stream: list of (block bytes, crc, consumed_start, consumed_end)"""
+        return self.rle1_blocks_cap(data, level * 100000 - 19)
+
+    def rle1_len(self, data):
+        """RLE1 length of the whole input as ONE block (no capacity in the way)"""
         data = as_u8(data)
-        cap = level * 100000 - 19
+        res = self.rle1_blocks_cap(data, 2 * data.size + 16)
+        assert len(res) <= 1
+        return res[0][0].size if res else 0
+
+    def rle1_blocks_cap(self, data, cap):
+        """the same with any block capacity cap >= 1"""
+        data = as_u8(data)
         cur = ctypes.c_size_t(0)
         res = []
         keep = data if data.size else np.zeros(1, np.uint8)
+        blk = np.empty(cap, dtype=np.uint8)                   # (a small cap makes thousands of blocks: one buffer, addresses taken once)
+        crc = ctypes.c_uint32(0)
+        p_in, p_blk, p_cur, p_crc, fn = keep.ctypes.data, blk.ctypes.data, ctypes.byref(cur), ctypes.byref(crc), self.L.cjs_oracle_rle1_block
         while True:
-            blk = np.empty(cap, dtype=np.uint8)
-            crc = ctypes.c_uint32(0)
             start = cur.value
-            n = self.L.cjs_oracle_rle1_block(keep.ctypes.data, data.size, ctypes.byref(cur), blk.ctypes.data, cap, ctypes.byref(crc))
+            n = fn(p_in, data.size, p_cur, p_blk, cap, p_crc)
             if n > 0:
                 res.append((blk[:n].copy(), crc.value, start, cur.value))
             if n != cap:
@@ -279,6 +290,10 @@ class HipLib(_StreamLib):
             "cjs_stage_bwt": [V, S, I, I, V, V, V],
             "cjs_stage_bwt_var": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
             "cjs_stage_rle1": [V, S, I, V, S, V, V, V, ctypes.c_long, ctypes.POINTER(ctypes.c_long), V],
+            "cjs_stage_rle1_cap": [V, S, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, I, V, S, V, V, V, V, ctypes.c_long,
+                                   ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_uint32), V],
+            "cjs_stage_rle1_batch": [V, S, V, ctypes.c_uint32, ctypes.c_uint32, I, V, V, V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V,
+                                     V, V, V, ctypes.c_uint32, ctypes.c_uint32, V, V, V],
             "cjs_stage_mtf": [V, V, S, I, V, V, V, V, V],
             "cjs_stage_mtf_var": [V, ctypes.c_uint32, ctypes.c_uint32, V, I, V, V, V, V, V, V, V],
             "cjs_stage_huff": [V, ctypes.c_uint32, ctypes.c_uint32, V, V, V, V],
@@ -430,6 +445,55 @@ class HipLib(_StreamLib):
             return rc, None
         n = nb.value
         return 0, [(blocks[k * cap: k * cap + int(blen[k])].copy(), int(bcrc[k]), int(bstart[k])) for k in range(n)]
+
+    def stage_rle1_cap(self, data, cap, world=1, range_blocks=0, work_fill=0):
+        """stage 0 with a block capacity of the caller's choice (cjs_stage_rle1_cap): (rc, [(block bytes, crc, input start, input
+        end)], last_len).  The host rows are pre-filled with 0xA5, so bytes the stage never wrote do not pass for zeros."""
+        data = as_u8(data)
+        maxb = data.size // max(cap * 4 // 5, 1) + 2
+        blocks = np.full(maxb * max(cap, 1), 0xA5, dtype=np.uint8)
+        blen = np.zeros(maxb, dtype=np.uint32)
+        bcrc = np.zeros(maxb, dtype=np.uint32)
+        bstart = np.zeros(maxb, dtype=np.uint64)
+        bend = np.zeros(maxb, dtype=np.uint64)
+        nb, last = ctypes.c_long(0), ctypes.c_uint32(0)
+        keep = data if data.size else np.zeros(1, np.uint8)
+        rc = self.L.cjs_stage_rle1_cap(keep.ctypes.data, data.size, cap, world, range_blocks, work_fill, blocks.ctypes.data, blocks.size,
+                                       blen.ctypes.data, bcrc.ctypes.data, bstart.ctypes.data, bend.ctypes.data, maxb, ctypes.byref(nb),
+                                       ctypes.byref(last), None)
+        if rc:
+            return rc, None, None
+        return 0, [(blocks[k * cap: k * cap + int(blen[k])], int(bcrc[k]), int(bstart[k]), int(bend[k])) for k in range(nb.value)], last.value
+
+    def stage_rle1_batch(self, buf, se, cap, item=(), tbase=(0,), table_slots=None, mat=(), stride=16, work_fill=0):
+        """the three batch kernels of stage 0, each with the caller's arrays (cjs_stage_rle1_batch).  se: [(start, end)] in buf;
+        item / tbase: the walk's inputs and slot grants; mat: [(s, e, len)] of the blocks to materialise into rows of `stride`.
+        Returns (rc, len2[count], (walk_s, walk_e, walk_len)[table_slots], nblk[nitem], rows[nmat][stride], crc[nmat])"""
+        buf = as_u8(buf)
+        keep = buf if buf.size else np.zeros(1, np.uint8)
+        count, nitem, nmat = len(se), len(item), len(mat)
+        se_a = np.array([x for p in se for x in p], dtype=np.uint64).reshape(-1)
+        item_a = np.array(list(item) + [0], dtype=np.uint32)
+        tbase_a = np.array(list(tbase), dtype=np.uint32)
+        assert tbase_a.size == nitem + 1
+        slots = int(tbase_a[-1]) if table_slots is None else table_slots
+        len2 = np.zeros(max(count, 1), dtype=np.uint64)
+        ws, we = np.zeros(max(slots, 1), dtype=np.uint64), np.zeros(max(slots, 1), dtype=np.uint64)
+        wl = np.zeros(max(slots, 1), dtype=np.uint32)
+        nblk = np.zeros(max(nitem, 1), dtype=np.uint32)
+        ms = np.array([m[0] for m in mat] + [0], dtype=np.uint64)
+        me = np.array([m[1] for m in mat] + [0], dtype=np.uint64)
+        ml = np.array([m[2] for m in mat] + [0], dtype=np.uint32)
+        rows = np.zeros((max(nmat, 1), stride), dtype=np.uint8)
+        crc = np.zeros(max(nmat, 1), dtype=np.uint32)
+        keep_se = se_a if se_a.size else np.zeros(2, dtype=np.uint64)
+        rc = self.L.cjs_stage_rle1_batch(keep.ctypes.data, buf.size, keep_se.ctypes.data, count, cap, work_fill, len2.ctypes.data,
+                                         item_a.ctypes.data, tbase_a.ctypes.data, nitem, slots, ws.ctypes.data, we.ctypes.data,
+                                         wl.ctypes.data, nblk.ctypes.data, ms.ctypes.data, me.ctypes.data, ml.ctypes.data, nmat, stride,
+                                         rows.ctypes.data, crc.ctypes.data, None)
+        if rc:
+            return rc, None, None, None, None, None
+        return 0, len2[:count], (ws[:slots], we[:slots], wl[:slots]), nblk[:nitem], rows[:nmat], crc[:nmat]
 
     def stage_mtf(self, U, blocks, block_len):
         U = as_u8(U)

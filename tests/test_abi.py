@@ -106,6 +106,24 @@ def test_stage_mtf_var_needs_a_device():
         assert res[0] == -30 and all(x is None for x in res[1:])          # CJS_E_NO_DEVICE before any argument is looked at
 
 
+def test_stage_rle1_cap_and_batch_need_a_device():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import support
+    hip = support.HipLib()
+    assert "cjs_stage_rle1_cap" not in hip.missing and "cjs_stage_rle1_batch" not in hip.missing
+    data = np.arange(300, dtype=np.uint8)
+    for cap, world in ((50, 1), (1, 1), (50, 0), (50, 3)):
+        res = hip.stage_rle1_cap(data, cap, world, 2, 0xFF)
+        assert res[0] == -30 and res[1] is None          # CJS_E_NO_DEVICE before any argument is looked at
+    for item in ([0, 1], [0, 7]):
+        res = hip.stage_rle1_batch(data, [(1, 100), (100, 300)], 50, item=item, tbase=[0, 2, 4], mat=[(1, 50, 49)], stride=64)
+        assert res[0] == -30 and all(x is None for x in res[1:])
+
+
 def test_free_and_trim_need_no_device():
     # cjs_free takes what the library handed out (plain malloc or a pinned result buffer) and, like free(), a null pointer;
     # memory it does not know is plain malloc'd memory.  cjs_trim with nothing cached is a no-op.  Neither needs a GPU.
