@@ -14,9 +14,9 @@
 //
 // Round 1 sorts every suffix by its leading 7 symbols (fewer when the block id has to share the key) with the segmented radix
 // sorter of radix.hip, one segment per block:
-//   cyclic    packed two-phase records, one u64 per suffix and no value array: bytes 2..6 first, then bwt_phase2_records
-//             rebuilds the records as bytes 0..1 | rank of the class of bytes 2..6 | the byte in front | position, and two more
-//             passes finish depth 7
+//   cyclic    packed two-phase records and no value array: bytes 2..6 first (one u64 per suffix for two passes, one u32 = byte 2 |
+//             position for the last three), then bwt_phase2_records rebuilds the records as bytes 0..1 | rank of the class of
+//             bytes 2..6 | the byte in front | position, and two more passes finish depth 7
 //   sentinel  (u64 key, u32 value) records, 9-bit symbols
 //   fallback  more blocks or tiles than the workspace has segments for, several blocks shorter than a 4096-slot tile, blocks of
 //             different lengths (bwt_run_var), or CJS_NO_SEGMENTED_SORT: bwt_init_keys writes keys with the block id on top,

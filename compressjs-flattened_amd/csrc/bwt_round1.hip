@@ -1,5 +1,6 @@
 // bwt_round1.hip — round 1 of the suffix sort (the map: bwt.hip): the keys of its unsegmented form, and the record rebuild between
-// the two phases of the packed form.  The radix passes themselves are radix.hip; the key and record layouts are bwt_rules.h.
+// the two phases of the packed form, which reads the 4-byte records that phase 1 ends on and takes every slot's class key back
+// from the block text.  The radix passes themselves are radix.hip; the key and record layouts are bwt_rules.h.
 #include "bwt_dev.hpp"
 
 namespace cjs {
@@ -30,16 +31,20 @@ __global__ __launch_bounds__(256) void bwt_init_keys(const uint8_t* __restrict__
   }
 }
 
-// Two-phase round 1 (cyclic, packed records): seven bytes of depth at 8 bytes per record.  Phase 1 sorted every block by
-// bytes 2..6; here every sorted slot learns r1 = block-local slot of the head of its (bytes 2..6) class and becomes the
-// phase-2 record  byte0 . byte1 (bits 63..48) | r1 (47..28) | parity (20) | position (19..0); two more stable passes on the
-// top 16 bits then order by (byte0, byte1, class of bytes 2..6), and key >> 20 is the 7-byte group key.
+// Two-phase round 1 (cyclic, packed records): seven bytes of depth.  Phase 1 sorted every block by bytes 2..6 and ends on the
+// narrow records of its last passes (byte 2 | position, 4 bytes: bwt_rules.h); here every sorted slot learns r1 = block-local slot
+// of the head of its (bytes 2..6) class and becomes the phase-2 record  byte0 . byte1 (bits 63..48) | r1 (47..28) | the byte in
+// front (27..20) | position (19..0); two more stable passes on the top 16 bits then order by (byte0, byte1, class of bytes 2..6),
+// and key >> 28 is the 7-byte group key.
+// The class key of a slot is no longer in its record: it comes back from the block text, with the bytes in front and at the
+// suffix that this kernel gathers anyway -- text[p - 1 .. p + 6] as three aligned words (text8 of bwt_dev.hpp), which lie in one
+// 64-byte line about nine times out of ten.  So do the keys of the slot in front of the tile and of the class search's probes.
 // Tiles are the tiles of the segmented radix passes (one segment per block), so this kernel also leaves the per-tile
 // histogram of byte1 -- the digit of the first phase-2 pass -- in hist[], and that pass needs no rs_hist of its own.
 // No flag / scan passes in front either: the only class head a tile cannot see is the one of the class that runs into it,
 // and the block is sorted, so wave 0 finds it by looking at the 64 slots in front of the tile (nearly always enough) and
 // otherwise by a 64-way search for the lower bound of the tile's first key in the block.
-__global__ __launch_bounds__(256) void bwt_phase2_records(const uint64_t* __restrict__ key, SegGeom sg, const uint8_t* __restrict__ T,
+__global__ __launch_bounds__(256) void bwt_phase2_records(const uint32_t* __restrict__ rec, SegGeom sg, const uint8_t* __restrict__ T,
                                                           uint32_t* __restrict__ hist, uint64_t* __restrict__ out) {
   __shared__ uint64_t sk[RS_TILE + 1];
   __shared__ uint64_t m_nh[64];
@@ -53,42 +58,43 @@ __global__ __launch_bounds__(256) void bwt_phase2_records(const uint64_t* __rest
   if (!t.nvalid) { hist[(size_t)tile * 256 + tid] = 0; return; }
   const uint64_t base = t.base, seg0 = (uint64_t)t.seg * sg.stride;
   const uint32_t nvalid = t.nvalid, n = t.seg + 1 == sg.nseg ? sg.n_last : sg.stride;
-  uint64_t k16[16];                              // all loads first (see bwt_apply)
+  const uint8_t* tx = T + seg0;
+  uint32_t p16[16];                              // all loads first (see bwt_apply)
 #pragma unroll
   for (int it = 0; it < 16; it++) {
     const uint32_t e = (uint32_t)it * 256u + tid;
-    k16[it] = __builtin_nontemporal_load(key + base + (e < nvalid ? e : nvalid - 1u));
+    p16[it] = pk_pos(__builtin_nontemporal_load(rec + base + (e < nvalid ? e : nvalid - 1u)));
   }
-  if (tid == 64) sk[0] = t.off ? key[base - 1] : ~0ull;
+  const auto class_at = [&](uint64_t i) { return pk_key_of_text(text8(tx, pk_pos(rec[i]), n)); };
+  if (tid == 64) sk[0] = t.off ? class_at(base - 1) : ~0ull;
   if (w == 0) {
     // head of the class of the tile's first slot (global index + 1, as bwt_scan_tiles would have carried it)
-    const uint32_t carry = (uint32_t)class_head_before(key, seg0, base, PK_SHIFT, lane) + 1u;
+    const uint32_t carry = (uint32_t)class_head_before_by(class_at, seg0, base, lane) + 1u;
     if (lane == 0) carry_s = carry;
   }
-  // the two leading bytes of every record's suffix: gathers from the block text (L2), independent of everything below
-  uint32_t b01[16];
-  {
-    const uint8_t* tx = T + seg0;
+  // the eight text bytes around every record's suffix: gathers from the block text (L2), all issued before the first is used
+  uint64_t t16[16];
 #pragma unroll
-    for (int it = 0; it < 16; it++) {
-      const uint32_t p = pk_pos(k16[it]);
-      b01[it] = ((uint32_t)tx[p] << 8) | tx[p + 1 < n ? p + 1 : 0];          // (one unaligned 16-bit load instead: 720 -> 900 us)
-      b01[it] |= (uint32_t)tx[p ? p - 1 : n - 1] << 16;                     // the byte in front (nearly always the line of tx[p]): carried from here on
-    }
-  }
+  for (int it = 0; it < 16; it++) t16[it] = text8_words(tx, p16[it], n);
+#pragma unroll
+  for (int it = 0; it < 16; it++)
+    if (text8_wraps(p16[it], n)) t16[it] = text8_wrapping(tx, p16[it], n);      // (seven positions of a block)
+  uint32_t b01[16];                              // byte 0 . byte 1 | the byte in front << 16: carried from here on
+#pragma unroll
+  for (int it = 0; it < 16; it++) b01[it] = pk_bytes01_of_text(t16[it]) | (pk_prev_of_text(t16[it]) << 16);
 #pragma unroll
   for (int i = 0; i < 4 * PH; i++) h[i * 256 + tid] = 0;
 #pragma unroll
   for (int it = 0; it < 16; it++) {
     const uint32_t e = (uint32_t)it * 256u + tid;
-    sk[e + 1] = e < nvalid ? k16[it] : ~0ull;
+    sk[e + 1] = e < nvalid ? pk_key_of_text(t16[it]) : ~0ull;
   }
   __syncthreads();
   uint32_t* hw = h + w * 256 * PH + (tid & (PH - 1));      // (bank-interleaved copies as in rs_hist)
 #pragma unroll
   for (int it = 0; it < 16; it++) {
     const uint32_t e = (uint32_t)it * 256u + tid;
-    const bool nh = e < nvalid && (t.off + e == 0 || (sk[e] >> PK_SHIFT) != (sk[e + 1] >> PK_SHIFT));
+    const bool nh = e < nvalid && (t.off + e == 0 || sk[e] != sk[e + 1]);
     const uint64_t mnh = __ballot(nh);
     if (lane == 0) m_nh[it * 4 + w] = mnh;
     if (e < nvalid) atomicAdd(&hw[(b01[it] & 255u) * PH], 1u);
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(256) void bwt_phase2_records(const uint64_t* __rest
       const uint64_t hm = m_nh[wi] & le;
       const uint32_t head_a = hm ? (uint32_t)base + (uint32_t)wi * 64u + 63u - (uint32_t)__builtin_clzll(hm) : wp_head[wi] ? (uint32_t)base + wp_head[wi] - 1u : carry - 1u;
       const uint32_t r1 = head_a - (uint32_t)seg0;
-      __builtin_nontemporal_store(pk2_record(b01[it], r1, b01[it] >> 16, pk_pos(k16[it])), out + base + e);
+      __builtin_nontemporal_store(pk2_record(b01[it], r1, b01[it] >> 16, p16[it]), out + base + e);
     }
   }
 }
@@ -132,9 +138,11 @@ int sort_round1(hipStream_t s, BwtWork& w, const G& g, const Plan& p, Round& r, 
     return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt);
   }
   if (!p.packed) return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt, &p.sg, &p.gen);
-  CJS_TRY((radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, PK_KEY_LO, 64, lt, &p.sg, &p.gen, true, false, w.dflag)));
-  hipLaunchKernelGGL(bwt_phase2_records, dim3(p.sg.nseg * p.sg.tps), dim3(256), 0, s, w.key[r.c], p.sg, p.gen.T, w.rs.hist, w.key[1 - r.c]);
-  r.c = 1 - r.c;
+  // phase 1: its narrow records go through val[], which the packed round 1 does not use before the regroup writes the next
+  // round's values (behind the rebuild that consumes them).  The 8-byte records of the first passes in key[] are dead by then:
+  // the rebuild writes key[r.c]
+  CJS_TRY(radix_passes_pk1(s, w.rs, w.key[0], w.key[1], w.val[0], w.val[1], r.A, lt, p.sg, p.gen, w.dflag));
+  hipLaunchKernelGGL(bwt_phase2_records, dim3(p.sg.nseg * p.sg.tps), dim3(256), 0, s, w.val[0], p.sg, p.gen.T, w.rs.hist, w.key[r.c]);
   return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 48, 64, lt, &p.sg, nullptr, true, true, w.dflag);
 }
 template int sort_round1<Geom>(hipStream_t, BwtWork&, const Geom&, const Plan&, Round&, LaunchTimes*);

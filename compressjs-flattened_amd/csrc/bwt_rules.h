@@ -28,7 +28,19 @@ constexpr uint32_t PK_POS_MASK = (1u << PK_SHIFT) - 1u;
 constexpr uint64_t pk_record(uint64_t bytes2to6, uint32_t parity, uint32_t pos) {
   return ((bytes2to6 & 0xFFFFFFFFFFull) << PK_KEY_LO) | ((uint64_t)(parity & 1u) << PK_SHIFT) | (uint64_t)pos;
 }
-constexpr uint32_t pk_pos(uint64_t rec) { return (uint32_t)rec & PK_POS_MASK; }      // of both packed layouts, and of val[]
+constexpr uint32_t pk_pos(uint64_t rec) { return (uint32_t)rec & PK_POS_MASK; }      // of every packed layout, and of val[]
+// narrow records of the last phase-1 passes: ONE u32 per suffix = byte 2 (bits 27..20) | position (19..0).  An LSD pass only needs
+// the digits that are still to come: behind the pass on byte 4 that is byte 3 (it rides in dig[]) and byte 2.  No parity bit:
+// tiles never straddle a block, and whoever compares neighbours (bwt_phase2_records) stops at the block start by the slot number
+constexpr int PK1_B2_SHIFT = PK_SHIFT;
+constexpr uint32_t pk1_record(uint32_t b2, uint32_t pos) { return ((b2 & 0xFFu) << PK1_B2_SHIFT) | (pos & PK_POS_MASK); }
+constexpr uint32_t pk1_of(uint64_t rec) { return pk1_record((uint32_t)(rec >> 56), pk_pos(rec)); }      // of a pk_record
+constexpr uint32_t pk1_b2(uint32_t rec) { return rec >> PK1_B2_SHIFT; }
+// the 40-bit class key of phase 1 (bytes 2..6, byte 2 on top) and the fields of the phase-2 record out of the eight text bytes
+// around a suffix, byte j of `t` = text[position - 1 + j] (cyclic)
+constexpr uint64_t pk_key_of_text(uint64_t t) { return ((t >> 24 & 0xFFu) << 32) | __builtin_bswap32((uint32_t)(t >> 32)); }
+constexpr uint32_t pk_bytes01_of_text(uint64_t t) { return (uint32_t)((t >> 8 & 0xFFu) << 8 | (t >> 16 & 0xFFu)); }
+constexpr uint32_t pk_prev_of_text(uint64_t t) { return (uint32_t)t & 0xFFu; }
 // records of the two-phase sort after bwt_phase2_records: byte0 . byte1 (63..48) | rank of the class of bytes 2..6 (47..28) | the byte IN
 // FRONT of the suffix (27..20) | position (19..0).  The group key is key >> PK2_GSHIFT; block boundaries are taken from the slot
 // number (no parity bit).  The byte in front is what the BWT emits for the suffix: it rides along (later in the top byte of val[])

@@ -182,6 +182,11 @@ template <typename K>
 int radix_passes(hipStream_t s, RadixWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit,
                  LaunchTimes* lt = nullptr, const SegGeom* seg = nullptr, const GenSrc* gen = nullptr, bool noval = false,
                  bool first_hist_ready = false, uint8_t* dig = nullptr);
+// The five phase-1 passes of the packed cyclic round 1 (bytes 6..2 of every suffix, keys made from the block bytes gen.T): 8-byte
+// records through k0 / k1 for two passes, then the narrow records of bwt_rules.h through n0 / n1; sorted, they end in n0.
+// dig: a byte per key
+int radix_passes_pk1(hipStream_t s, RadixWork& w, uint64_t* k0, uint64_t* k1, uint32_t* n0, uint32_t* n1, uint32_t n, LaunchTimes* lt,
+                     const SegGeom& sg, const GenSrc& gen, uint8_t* dig);
 // ... over nseg segments of `stride` 32-bit keys each (dec_ibwt.hip: one segment per block)
 int radix_pass_segments(hipStream_t s, RadixWork& w, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, int& cur, uint32_t nseg, uint32_t stride,
                         int lo_bit, int hi_bit, bool noval, bool first_hist_ready);

@@ -4,7 +4,10 @@
 // buffers.  Used by the suffix sort (bwt.hip: round 1, the groups too large for the tile sorters, the whole-array fallbacks) and
 // by the inverse BWT (dec_ibwt.hip: stable partition of the BWT bytes).  Integer sort/scan only (no MFMA); HBM-bound on the
 // scatter passes.
+// radix_passes_pk1 is the phase-1 sort of the packed cyclic round 1, five passes on records that shrink as their digits are
+// used up: 8 bytes for two passes, then 4 (rs_scatter with a narrower output type, then with its digit from a byte array).
 #include "radix.hpp"
+#include <type_traits>
 
 namespace cjs {
 
@@ -142,13 +145,19 @@ __global__ __launch_bounds__(256) void rs_scan_chunk_apply(uint32_t* __restrict_
   for (uint32_t t = t0; t < t1; t++) { const uint32_t v = hist[(size_t)t * 256 + threadIdx.x]; hist[(size_t)t * 256 + threadIdx.x] = carry; carry += v; }
 }
 
-template <typename K, bool GEN, bool NOVAL>
-__global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, const uint32_t* __restrict__ vin,
-                                                  K* __restrict__ kout, uint32_t* __restrict__ vout, SegGeom sg, GenSrc gs, int shift,
+// KO: the records as they go out -- K, or the narrow phase-1 record (pk1_of, bwt_rules.h) of a packed one; they are staged in
+// LDS as they come in.  DIGIN (key-only passes): the records no longer hold this pass's digit: it is the byte that the pass in
+// front left at the record's index, handed in through vin and staged beside the records (a byte each); such a pass leaves no
+// digit for the next one -- other workgroups of the launch are still reading the array it would write to.  Otherwise the digit
+// is bits [shift, shift + 8) and the next one lies above it.
+template <typename K, bool GEN, bool NOVAL, typename KO = K, bool DIGIN = false>
+__global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, const std::conditional_t<DIGIN, uint8_t, uint32_t>* __restrict__ vin,
+                                                  KO* __restrict__ kout, uint32_t* __restrict__ vout, SegGeom sg, GenSrc gs, int shift,
                                                   const uint32_t* __restrict__ hist, uint32_t T, const uint32_t* __restrict__ bintot,
                                                   uint8_t* __restrict__ dig /* next digit of every key, at the key's new index (or null) */) {
   __shared__ __attribute__((aligned(16))) K skey[RS_TILE + 2];
   __shared__ uint32_t sval[NOVAL ? 1 : RS_TILE];
+  __shared__ uint8_t sdig[DIGIN ? RS_TILE : 1];
   __shared__ uint32_t wcnt[4][256];
   __shared__ uint32_t goff[256];
   __shared__ uint32_t sm[4];
@@ -158,6 +167,7 @@ __global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, con
   const uint64_t base = t.base;
   const uint32_t nvalid = t.nvalid;
   for (int i = tid; i < 1024; i += 256) (&wcnt[0][0])[i] = 0;
+  static_assert(!DIGIN || (NOVAL && !GEN), "the digit bytes come in where the values would");
   K k[16];
   uint32_t v[16];
   uint32_t rk[16];
@@ -178,12 +188,16 @@ __global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, con
       const uint32_t loc = (uint32_t)w * 1024u + (uint32_t)s * 64u + lane;
       const bool ok = loc < nvalid;
       k[s] = ok ? kin[base + loc] : (K)~(K)0;           // (non-temporal loads here: no change, 12.69 vs 12.69 ms per step)
-      v[s] = (ok && !NOVAL) ? vin[base + loc] : 0u;
+      if constexpr (DIGIN) v[s] = ok ? (uint32_t)vin[base + loc] : 255u;      // v[] = this pass's digit
+      else v[s] = (ok && !NOVAL) ? vin[base + loc] : 0u;
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int s = 0; s < 16; s++) rk[s] = rank_step((uint32_t)(k[s] >> shift) & 255u, wcnt[w]);
+  for (int s = 0; s < 16; s++) {
+    if constexpr (DIGIN) rk[s] = rank_step(v[s], wcnt[w]);
+    else rk[s] = rank_step((uint32_t)(k[s] >> shift) & 255u, wcnt[w]);
+  }
   __syncthreads();
   {
     const uint32_t c0 = wcnt[0][tid], c1 = wcnt[1][tid], c2 = wcnt[2][tid], c3 = wcnt[3][tid];
@@ -197,10 +211,12 @@ __global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, con
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < 16; s++) {
-    const uint32_t d = (uint32_t)(k[s] >> shift) & 255u;
+    uint32_t d;
+    if constexpr (DIGIN) d = v[s]; else d = (uint32_t)(k[s] >> shift) & 255u;
     const uint32_t p = wcnt[w][d] + rk[s];
     skey[p] = k[s];
     if (!NOVAL) sval[p] = v[s];
+    if constexpr (DIGIN) sdig[p] = (uint8_t)d;
   }
   __syncthreads();
 #pragma unroll 4
@@ -208,11 +224,25 @@ __global__ __launch_bounds__(256) void rs_scatter(const K* __restrict__ kin, con
     const uint32_t j = (uint32_t)it * 256u + tid;
     if (j < nvalid) {
       const K kk = skey[j];
-      const uint32_t dst = goff[(uint32_t)(kk >> shift) & 255u] + j;
-      kout[dst] = kk;
+      uint32_t dst;
+      if constexpr (DIGIN) dst = goff[sdig[j]] + j; else dst = goff[(uint32_t)(kk >> shift) & 255u] + j;
+      if constexpr (sizeof(KO) < sizeof(K)) kout[dst] = pk1_of(kk); else kout[dst] = kk;
       if (!NOVAL) vout[dst] = sval[j];
-      if (dig) dig[dst] = (uint8_t)((uint64_t)kk >> (shift + 8));
+      if constexpr (!DIGIN) if (dig) dig[dst] = (uint8_t)((uint64_t)kk >> (shift + 8));
     }
+  }
+}
+
+// the tile counts of a digit in w.hist -> every tile's offsets inside its segment, digit totals per segment in w.bintot
+static void scan_counts(hipStream_t s, RadixWork& w, const SegGeom& sg) {
+  if (sg.tps <= 4 * SB_CHUNK) { hipLaunchKernelGGL(rs_scan_bins, dim3(sg.nseg), dim3(256), 0, s, w.hist, sg.tps, w.bintot); return; }
+  for (uint32_t sgi = 0; sgi < sg.nseg; sgi++) {      // one long segment (nseg > 1 with long segments: still correct, one launch per segment)
+    uint32_t* hseg = w.hist + (size_t)sgi * sg.tps * 256;
+    const uint32_t nch = (sg.tps + SB_CHUNK - 1) / SB_CHUNK;
+    uint32_t* csum = w.hist + (size_t)w.hist_tiles * 256;          // behind the per-tile rows (RadixWork::hist_words)
+    hipLaunchKernelGGL(rs_scan_chunk_sum, dim3(nch), dim3(256), 0, s, hseg, sg.tps, csum);
+    hipLaunchKernelGGL(rs_scan_chunk_mid, dim3(1), dim3(256), 0, s, csum, nch, w.bintot + (size_t)sgi * 256);
+    hipLaunchKernelGGL(rs_scan_chunk_apply, dim3(nch), dim3(256), 0, s, hseg, sg.tps, csum);
   }
 }
 
@@ -236,17 +266,7 @@ int radix_passes(hipStream_t s, RadixWork& w, K* k0, uint32_t* v0, K* k1, uint32
       hipLaunchKernelGGL(rs_hist_bytes, dim3(T), dim3(256), 0, s, gen->T, sg, w.hist, 6u);
     else if (first_gen) hipLaunchKernelGGL((rs_hist<K, true>), dim3(T), dim3(256), 0, s, kk[cur], sg, *gen, shift, w.hist, T);
     else hipLaunchKernelGGL((rs_hist<K, false>), dim3(T), dim3(256), 0, s, kk[cur], sg, g0, shift, w.hist, T);
-    if (sg.tps <= 4 * SB_CHUNK) hipLaunchKernelGGL(rs_scan_bins, dim3(sg.nseg), dim3(256), 0, s, w.hist, sg.tps, w.bintot);
-    else {                                    // one long segment (nseg > 1 with long segments: still correct, one launch per segment)
-      for (uint32_t sgi = 0; sgi < sg.nseg; sgi++) {
-        uint32_t* hseg = w.hist + (size_t)sgi * sg.tps * 256;
-        const uint32_t nch = (sg.tps + SB_CHUNK - 1) / SB_CHUNK;
-        uint32_t* csum = w.hist + (size_t)w.hist_tiles * 256;          // behind the per-tile rows (RadixWork::hist_words)
-        hipLaunchKernelGGL(rs_scan_chunk_sum, dim3(nch), dim3(256), 0, s, hseg, sg.tps, csum);
-        hipLaunchKernelGGL(rs_scan_chunk_mid, dim3(1), dim3(256), 0, s, csum, nch, w.bintot + (size_t)sgi * 256);
-        hipLaunchKernelGGL(rs_scan_chunk_apply, dim3(nch), dim3(256), 0, s, hseg, sg.tps, csum);
-      }
-    }
+    scan_counts(s, w, sg);
     if (lt) lt->begin(s, n);
 #define RS_SCATTER(GEN_, NOVAL_, G_) hipLaunchKernelGGL((rs_scatter<K, GEN_, NOVAL_>), dim3(T), dim3(256), 0, s, kk[cur], vv[cur], kk[1 - cur], vv[1 - cur], sg, G_, shift, w.hist, T, w.bintot, dig_out ? dig : nullptr)
     if (noval) { if (first_gen) RS_SCATTER(true, true, *gen); else RS_SCATTER(false, true, g0); }
@@ -267,6 +287,42 @@ int radix_pass_segments(hipStream_t s, RadixWork& w, uint32_t* k0, uint32_t* v0,
                         int lo_bit, int hi_bit, bool noval, bool first_hist_ready) {
   const SegGeom sg{nseg, stride, stride, (stride + RS_TILE - 1) / RS_TILE};
   return radix_passes<uint32_t>(s, w, k0, v0, k1, v1, cur, nseg * stride, lo_bit, hi_bit, nullptr, &sg, nullptr, noval, first_hist_ready);
+}
+
+// (declared in cjs_internal.h)  Pass by pass, what a record still has to carry shrinks: passes 1 and 2 (bytes 6, 5) move the
+// 8-byte pk_record; pass 3 (byte 4) reads it and writes the 4-byte pk1 record, byte 3 beside it in dig[] as every pass leaves the
+// next digit; pass 4 takes its digit from dig[] at the record's own index and leaves none (see rs_scatter); pass 5 (byte 2, in
+// the record) is the plain 32-bit key-only pass and counts its digits from the records.
+int radix_passes_pk1(hipStream_t s, RadixWork& w, uint64_t* k0, uint64_t* k1, uint32_t* n0, uint32_t* n1, uint32_t n, LaunchTimes* lt,
+                     const SegGeom& sg, const GenSrc& gen, uint8_t* dig) {
+  const uint32_t T = sg.nseg * sg.tps;
+  if (T > w.hist_tiles || sg.nseg > w.bintot_segs) return CJS_E_INVALID_ARG;
+  const GenSrc g0{nullptr, 0, 0, 0};
+  // counts of the pass's digit from a byte per record (pass 1: the text byte at suffix + 6), then their scan; the scatter is timed
+  auto counts = [&](const uint8_t* bytes, uint32_t delta) {
+    hipLaunchKernelGGL(rs_hist_bytes, dim3(T), dim3(256), 0, s, bytes, sg, w.hist, delta);
+    scan_counts(s, w, sg);
+    if (lt) lt->begin(s, n);
+  };
+  counts(gen.T, 6u);
+  hipLaunchKernelGGL((rs_scatter<uint64_t, true, true>), dim3(T), dim3(256), 0, s, k0, nullptr, k0, nullptr, sg, gen, PK_KEY_LO, w.hist, T, w.bintot, dig);
+  if (lt) lt->end(s);
+  counts(dig, 0u);
+  hipLaunchKernelGGL((rs_scatter<uint64_t, false, true>), dim3(T), dim3(256), 0, s, k0, nullptr, k1, nullptr, sg, g0, PK_KEY_LO + 8, w.hist, T, w.bintot, dig);
+  if (lt) lt->end(s);
+  counts(dig, 0u);
+  hipLaunchKernelGGL((rs_scatter<uint64_t, false, true, uint32_t>), dim3(T), dim3(256), 0, s, k1, nullptr, n0, nullptr, sg, g0, PK_KEY_LO + 16, w.hist, T, w.bintot, dig);
+  if (lt) lt->end(s);
+  counts(dig, 0u);
+  hipLaunchKernelGGL((rs_scatter<uint32_t, false, true, uint32_t, true>), dim3(T), dim3(256), 0, s, n0, dig, n1, nullptr, sg, g0, 0, w.hist, T, w.bintot, nullptr);
+  if (lt) lt->end(s);
+  hipLaunchKernelGGL((rs_hist<uint32_t, false>), dim3(T), dim3(256), 0, s, n1, sg, g0, PK1_B2_SHIFT, w.hist, T);
+  scan_counts(s, w, sg);
+  if (lt) lt->begin(s, n);
+  hipLaunchKernelGGL((rs_scatter<uint32_t, false, true>), dim3(T), dim3(256), 0, s, n1, nullptr, n0, nullptr, sg, g0, PK1_B2_SHIFT, w.hist, T, w.bintot, nullptr);
+  if (lt) lt->end(s);
+  CJS_HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 int RadixWork::carve(Arena& a, size_t tiles, size_t segs) {
