@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void batch_empty_streams(const uint64_t* __res
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   uint32_t* o = out32 + (off[i] >> 2);
-  o[0] = __builtin_bswap32(0x425a6830u + (uint32_t)level);
+  o[0] = __builtin_bswap32(BZH0_WORD + (uint32_t)level);
   o[1] = __builtin_bswap32(0x17724538u);
   o[2] = __builtin_bswap32(0x50900000u);
   o[3] = 0;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void batch_asm_frame(const AsmStream* __restri
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const AsmStream t = tab[i];
-  atomicOr(&out32[t.off >> 2], __builtin_bswap32(0x425a6830u + (uint32_t)level));
+  atomicOr(&out32[t.off >> 2], __builtin_bswap32(BZH0_WORD + (uint32_t)level));
   put_trailer_words(out32, t.end_bit, t.crc);
 }
 

@@ -7,6 +7,10 @@
 
 namespace cjs {
 
+// block magic (pi), end-of-stream magic (sqrt pi), 48 bits each; the stream's first word is BZH0_WORD + level
+constexpr uint64_t MAGIC_BLOCK = 0x314159265359ull, MAGIC_END = 0x177245385090ull;
+constexpr uint32_t BZH0_WORD = 0x425a6830u;      // 'B' 'Z' 'h' '0'
+
 // stream CRC after one more block: c -> rol1(c) ^ crc (J/Bzip2_joined_.js:2237)
 inline uint32_t crc_fold(uint32_t c, uint32_t crc) { return ((c << 1) | (c >> 31)) ^ crc; }
 // ... after `blocks` more blocks whose CRCs folded from 0 give `fold`: c -> rol(c, blocks) ^ fold
@@ -64,7 +68,7 @@ inline void funnel_merge(uint8_t* dst, uint64_t pos, const uint8_t* src, uint64_
 
 // end-of-stream magic and stream CRC (48 + 32 bits) OR-ed into `bytes` (zero there) from bit `bit` on
 inline void put_trailer(uint8_t* bytes, uint64_t bit, uint32_t crc) {
-  const uint64_t vals[2] = {0x177245385090ull, crc}; const int nbs[2] = {48, 32};
+  const uint64_t vals[2] = {MAGIC_END, crc}; const int nbs[2] = {48, 32};
   for (int q = 0; q < 2; q++) for (int i = nbs[q] - 1; i >= 0; i--, bit++) if ((vals[q] >> i) & 1) bytes[bit >> 3] |= (uint8_t)(0x80 >> (bit & 7));
 }
 

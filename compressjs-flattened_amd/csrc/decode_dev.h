@@ -3,14 +3,14 @@
 // state that dec_ibwt.hip sizes and dec_unrle1.hip fills; and the launch functions of batch_dec.hip and dec_device.hip.  The host
 // side of the engine is dec_engine.h.
 #pragma once
+#include "bz_frame.h"
 #include "cjs_internal.h"
 #include "dec_plan.h"
 #include "prims.hpp"
 
 namespace cjs {
 
-constexpr uint64_t MAGIC_BLOCK = 0x314159265359ull, MAGIC_END = 0x177245385090ull;
-// (SPL, the splitter spacing of the inverse BWT; GROUP_SYMS, MAX_SELECTORS: dec_plan.h)
+// (MAGIC_BLOCK, MAGIC_END: bz_frame.h; SPL, the splitter spacing of the inverse BWT; GROUP_SYMS, MAX_SELECTORS: dec_plan.h)
 
 struct Cand { uint64_t bit; uint32_t kind; uint32_t pad; };      // kind 0 = block, 1 = end of stream; pad = row of the block candidate in the decode buffer (set by the host)
 struct BlockOut {

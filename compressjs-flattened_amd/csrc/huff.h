@@ -2,6 +2,7 @@
 #pragma once
 #include "cjs_internal.h"
 #include "mtf.h"
+#include "huff_rules.h"
 
 namespace cjs {
 
@@ -26,7 +27,7 @@ struct HuffWork {
   uint32_t max_stride = 0;
   HuffBufs b{};
   uint64_t* scalars = nullptr;   // [0] total bits, [1] (u32) stream crc, [2] output too small
-  static size_t sel_stride_for(uint32_t stride) { return (((size_t)stride + 1 + 49) / 50 + 63) & ~(size_t)63; }
+  static size_t sel_stride_for(uint32_t stride) { return cjs::sel_stride_for(stride); }
   static size_t bytes_needed(size_t max_blocks, uint32_t stride);
   int carve(Arena& a, size_t max_blocks, uint32_t stride);
   // the table-construction buffers seen from block `first` on (`count` blocks); bitoff / scalars belong to the packing of a whole call
@@ -34,9 +35,9 @@ struct HuffWork {
     HuffWork v = *this;
     v.max_blocks = count;
     v.b.sel += first * b.sel_stride; v.b.selj += first * b.sel_stride; v.b.bcost += first * b.sel_stride;
-    v.b.lens += first * 6 * 258; v.b.codes += first * 6 * 258;
+    v.b.lens += first * lens_row_bytes(); v.b.codes += first * codes_row_elems();
     v.b.ngroups += first; v.b.bitlen += first; v.b.databits += first; v.b.tileoff += first * b.tile_stride;
-    v.b.wl += first * 6 * 264; v.b.wfreq += first * 6 * 260;
+    v.b.wl += first * wl_row_bytes(); v.b.wfreq += first * wfreq_row_elems();
     return v;
   }
 };
@@ -72,16 +73,11 @@ int huff_batch_pack_run(hipStream_t s, HuffWork& w, const SymRows& r, const Pack
 // end-of-stream magic and stream CRC (48 + 32 bits) OR-ed into the big-endian words of out32 from stream bit `bit` on; returns
 // the bit behind them.  One lane per stream (pack_frame, huff_batch_frame, batch_asm_frame).
 __device__ __forceinline__ uint64_t put_trailer_words(uint32_t* out32, uint64_t bit, uint32_t crc) {
-  const uint64_t vals[2] = {0x177245385090ull, (uint64_t)crc};
+  const uint64_t vals[2] = {MAGIC_END, (uint64_t)crc};
   const uint32_t nbs[2] = {48, 32};
   for (int q = 0; q < 2; q++) {
-    uint32_t left = nbs[q];
-    while (left) {
-      const uint32_t o = (uint32_t)(bit & 31), room = 32 - o, take = left < room ? left : room;
-      const uint32_t chunk = (uint32_t)((vals[q] >> (left - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
-      atomicOr(&out32[bit >> 5], __builtin_bswap32(chunk << (room - take)));
-      left -= take; bit += take;
-    }
+    split_bits(bit, vals[q], nbs[q], [&](uint64_t w, uint32_t piece) { atomicOr(&out32[w], __builtin_bswap32(piece)); });
+    bit += nbs[q];
   }
   return bit;
 }

@@ -340,9 +340,9 @@ extern "C" int cjs_stage_huff(const uint16_t* A, uint32_t npos, uint32_t alphabe
   CJS_HIP_TRY(hipMemcpy(d_alist, al, 256, hipMemcpyHostToDevice));
   CJS_TRY(huff_tables_run(s, w, 1, SymRows{d_A, npos, d_misc, d_misc + 1, d_misc + 2, d_alist}));
   CJS_HIP_TRY(hipStreamSynchronize(s));
-  const uint32_t nsel = (npos + 49) / 50;
+  const uint32_t nsel = groups_for(npos);
   CJS_HIP_TRY(hipMemcpy(selectors, w.b.sel, nsel, hipMemcpyDeviceToHost));
-  CJS_HIP_TRY(hipMemcpy(lengths, w.b.lens, 6 * 258, hipMemcpyDeviceToHost));
+  CJS_HIP_TRY(hipMemcpy(lengths, w.b.lens, lens_row_bytes(), hipMemcpyDeviceToHost));
   CJS_HIP_TRY(hipMemcpy(ngroups, w.b.ngroups, 4, hipMemcpyDeviceToHost));
   return 0;
   CJS_GUARD_END(CJS_E_OUT_OF_MEMORY, CJS_E_HIP)
@@ -391,7 +391,7 @@ extern "C" int cjs_stage_huff_blocks(const uint16_t* A, size_t a_stride, uint32_
   Stream s;
   CJS_HIP_TRY(hipStreamCreate(s.put()));
   CJS_HIP_TRY(hipMemsetAsync(d_A, 0, 2 * das * nb, s));
-  CJS_HIP_TRY(hipMemsetAsync(w.b.lens, 0, (size_t)nb * 6 * 258, s));
+  CJS_HIP_TRY(hipMemsetAsync(w.b.lens, 0, (size_t)nb * lens_row_bytes(), s));
   CJS_HIP_TRY(hipMemcpy2DAsync(d_A, 2 * das, A, 2 * a_stride, 2 * (size_t)max_npos, nb, hipMemcpyHostToDevice, s));
   CJS_HIP_TRY(hipMemcpyAsync(d_npos, npos, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
   CJS_HIP_TRY(hipMemcpyAsync(d_asz, alphabet, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
@@ -417,9 +417,9 @@ extern "C" int cjs_stage_huff_blocks(const uint16_t* A, size_t a_stride, uint32_
   CJS_HIP_TRY(hipMemcpyAsync(slen.data(), d_slen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipMemcpyAsync(blen.data(), w.b.bitlen, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipMemcpyAsync(ngroups, w.b.ngroups, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
-  CJS_HIP_TRY(hipMemcpyAsync(lengths, w.b.lens, (size_t)nb * 6 * 258, hipMemcpyDeviceToHost, s));
-  const size_t hsel = (a_stride + 49) / 50;
-  CJS_HIP_TRY(hipMemcpy2DAsync(selectors, hsel, w.b.sel, w.b.sel_stride, ((size_t)max_npos + 49) / 50, nb, hipMemcpyDeviceToHost, s));
+  CJS_HIP_TRY(hipMemcpyAsync(lengths, w.b.lens, (size_t)nb * lens_row_bytes(), hipMemcpyDeviceToHost, s));
+  const size_t hsel = groups_for(a_stride);
+  CJS_HIP_TRY(hipMemcpy2DAsync(selectors, hsel, w.b.sel, w.b.sel_stride, groups_for((size_t)max_npos), nb, hipMemcpyDeviceToHost, s));
   CJS_HIP_TRY(hipStreamSynchronize(s));
   for (uint32_t k = 0; k < nb; k++) if (slen[k] > bits_stride) return CJS_E_INVALID_ARG;      // (nothing of the bits written yet)
   for (uint32_t k = 0; k < nb; k++) {
