@@ -109,7 +109,21 @@ class CutInfo(ctypes.Structure):
                 ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64)]
 
 
+class TallyInfo(ctypes.Structure):
+    """cjs_tally_info (40 bytes)."""
+    _fields_ = [("n_keys", ctypes.c_uint64), ("n_bad", ctypes.c_uint64), ("n_distinct", ctypes.c_uint64), ("n_groups", ctypes.c_uint64),
+                ("max_count", ctypes.c_uint64)]
+
+
+class StreamTallyInfo(ctypes.Structure):
+    """cjs_bz_tally_info (64 bytes)."""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_bad_lines", ctypes.c_uint64), ("n_distinct", ctypes.c_uint64), ("n_groups", ctypes.c_uint64),
+                ("max_count", ctypes.c_uint64), ("blocks_decoded", ctypes.c_uint64), ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64)]
+
+
 LINE_KEY_DTYPE = np.dtype([("hash", "<u8"), ("len", "<u4"), ("check", "<u4")])
+TALLY_DTYPE = np.dtype([("hash", "<u8"), ("len", "<u4"), ("check", "<u4"), ("first", "<u8"), ("count", "<u8")])      # cjs_bz_tally (32 bytes)
+TALLY_BY_FIRST, TALLY_BY_COUNT, TALLY_LINES = 0, 1, 2
 CUT_RANGE_DTYPE = np.dtype([("lo", "<u4"), ("hi", "<u4")])
 CUT_FIELDS, CUT_BYTES, CUT_TO_END = 0, 1, 0xFFFFFFFF
 
@@ -209,6 +223,13 @@ def load_library():
     L.cjs_bzip2_line_keys.argtypes = [u8p, S] + keys_tail
     L.cjs_bzip2_line_keys_device.argtypes = [V, S] + keys_tail
     L.cjs_line_keys_diff.argtypes = [V, S, V, S, U64, ctypes.POINTER(Hunk), S, ctypes.POINTER(LineDiffInfo)]
+    tally_tail = [S, U32, U64, U64, V, S, ctypes.POINTER(TallyInfo)]
+    L.cjs_keys_tally.argtypes = [V] + tally_tail + [V]
+    L.cjs_keys_tally_device.argtypes = [V] + tally_tail + [V]
+    L.cjs_stage_keys_tally.argtypes = [V] + tally_tail
+    stream_tally_tail = [V, V, U64, U64, U64, U32, U32, V, U32, U32, U64, U64, V, S, ctypes.POINTER(StreamTallyInfo), V]
+    L.cjs_bzip2_tally.argtypes = [u8p, S] + stream_tally_tail
+    L.cjs_bzip2_tally_device.argtypes = [V, S] + stream_tally_tail
     cut_head = [V, V, U64, U64, U32, U32, V, U32]
     L.cjs_bzip2_cut.argtypes = [u8p, S] + cut_head + [PP, PS, ctypes.POINTER(CutInfo), V]
     L.cjs_bzip2_cut_device.argtypes = [V, S] + cut_head + [V, S, PS, ctypes.POINTER(CutInfo), V]
@@ -967,6 +988,22 @@ class Bzip2Index:
                                sel.ctypes.data, sel.size, ctypes.byref(out), ctypes.byref(out_n), ctypes.byref(info), None))
         return _adopt(out, out_n.value).tobytes()
 
+    def tally_lines(self, data, lines, fields=None, bytes=None, delimiter=b"\t", first=0, count=None, seed=0, order="count", min_count=1, max_count=0,
+                    limit=None):
+        """`bzcat | sort | uniq -c | sort -rn | head` over lines [first, first + count) (count=None: to the last): the lines' keys
+        are made and grouped on the GPU (cjs_bzip2_tally), only the groups come down -> TallyResult.  order="count": descending
+        count, ties by first occurrence; "first": by first occurrence.  min_count=2 is `uniq -d`, max_count=1 is `uniq -u`;
+        limit: the first so many groups (None: all).  A group's `first` is the number of its first line.  A tail line without a
+        newline counts as if it had one; an empty tail is no line.  Lines that touch a bad block are counted in n_bad_lines and
+        grouped nowhere.  fields / bytes (one of them, with delimiter, as in cut_lines): the tally of that cut, "which values of
+        column 3 occur how often" -- the key of a line is that of its cut_lines output line; a bad block inside the window then
+        fails the call as it fails cut_lines."""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        return _tally_lines(lambda *a: L.cjs_bzip2_tally(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a, None), lines, fields, bytes, delimiter, first, count,
+                            seed, order, min_count, max_count, limit)
+
     def diff_stream(self, data, lines, other_data, other_index, other_lines, max_edits=0, seed=0):
         """bzdiff on the GPU: the line diff of this stream (A) against the stream `other_data` of `other_index` (B) -> LineDiff.
         Both streams' lines are hashed where they stand decoded (line_keys); the diff runs on the host over 16 bytes per line
@@ -1253,6 +1290,97 @@ def diff_keys(a, b, max_edits=0):
     if info.n_hunks:
         _check(L.cjs_line_keys_diff(pa, a.size, pb, b.size, int(max_edits), hunks, int(info.n_hunks), ctypes.byref(info)))
     return LineDiff([(h.a_first, h.a_count, h.b_first, h.b_count) for h in hunks[:int(info.n_hunks)]], info)
+
+
+class TallyResult:
+    """A frequency table: groups = a structured array of (hash, len, check, first, count) per returned group, in the order asked
+    for and at most `limit` of them; n_lines = the keys tallied; n_bad_lines = those that were all-ones (grouped nowhere);
+    n_distinct = all groups; n_groups = the groups that pass the filter; max_count = the size of the largest group."""
+
+    def __init__(self, groups, info, detail="", cut=None):
+        self.groups = groups
+        self.cut = cut          # of a tally of a cut: the fields / bytes / delimiter it was made with
+        if isinstance(info, TallyInfo):
+            self.n_lines, self.n_bad_lines = int(info.n_keys), int(info.n_bad)
+        else:      # of a stream: the touched blocks that were not good beside it, as in LineKeysResult
+            self.n_lines, self.n_bad_lines = int(info.n_lines), int(info.n_bad_lines)
+            self.bad_blocks, self.blocks_decoded = int(info.n_bad_blocks), int(info.blocks_decoded)
+            self.first_bad_block = int(info.first_bad_block) if info.n_bad_blocks else None
+            self.detail = detail
+        self.n_distinct, self.n_groups, self.max_count = int(info.n_distinct), int(info.n_groups), int(info.max_count)
+
+    def text(self, index, data, lines):
+        """`uniq -c` style lines ("%7d %s") of the returned groups of Bzip2Index.tally_lines (or of tally_keys over the keys of
+        the stream's lines from line 0 on): each group's representative line is read through read_lines, all in one call, and
+        for the tally of a cut passed through cut_text.  A line that touches a bad block raises its CjsError."""
+        got = index.read_lines(data, lines, [(int(f), 1) for f in self.groups["first"]])
+        out = []
+        for g, c in zip(got, self.groups["count"].tolist()):
+            if isinstance(g, CjsError):
+                raise g
+            if self.cut:
+                g = cut_text(g, **self.cut)          # the group's key is that of the cut line
+            out.append(b"%7d " % c + (g if g.endswith(b"\n") else g + b"\n"))
+        return b"".join(out)
+
+
+def _tally_args(order, min_count, max_count, limit):
+    orders = {"first": TALLY_BY_FIRST, "count": TALLY_BY_COUNT}
+    if order not in orders:
+        raise ValueError("order is 'count' or 'first'")
+    min_count, max_count = int(min_count), int(max_count)
+    if min_count < 0 or max_count < 0 or (max_count and max_count < min_count):
+        raise ValueError("0 <= min_count, and max_count is 0 (no bound) or at least min_count")
+    if limit is not None and int(limit) < 0:
+        raise ValueError("limit is None or a count")
+    return orders[order], min_count, max_count, None if limit is None else int(limit)
+
+
+def _tally(call, limit, most, info=None, cut=None):
+    """call(out, cap, info) -> rc, once: with room for `limit` groups, or without a limit for `most`, which bounds their number"""
+    info = TallyInfo() if info is None else info
+    cap = int(most) if limit is None else min(limit, int(most))
+    groups = np.zeros(cap, dtype=TALLY_DTYPE)
+    _check(call(groups.ctypes.data if cap else None, cap, ctypes.byref(info)))      # (no room: the count query)
+    detail = load_library().cjs_last_error_detail().decode() if getattr(info, "n_bad_blocks", 0) else ""
+    return TallyResult(groups[:min(cap, int(info.n_groups))].copy(), info, detail, cut)
+
+
+def tally_keys(keys, order="count", min_count=1, max_count=0, limit=None, device=-1):
+    """`sort | uniq -c` over a key array (Bzip2Index.line_keys), grouped on the GPU (cjs_keys_tally) -> TallyResult.  Two keys are
+    one group iff all three fields are equal; all-ones keys are grouped nowhere.  order="count": descending count, ties by first
+    occurrence; "first": by first occurrence.  min_count=2 is `uniq -d`, max_count=1 is `uniq -u`; limit: the first so many groups
+    (None: all).  A group's `first` is the index of its first key."""
+    L = load_library()
+    order, min_count, max_count, limit = _tally_args(order, min_count, max_count, limit)
+    keys = np.ascontiguousarray(keys, dtype=LINE_KEY_DTYPE)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    ptr = keys.ctypes.data if keys.size else None
+    return _tally(lambda *a: L.cjs_keys_tally(ptr, keys.size, order, min_count, max_count, *a, ctypes.byref(opts)), limit, keys.size)
+
+
+def _tally_lines(call, lines, fields, bytes_, delimiter, first, count, seed, order, min_count, max_count, limit):
+    """call(first, count, seed, mode, delim, sel, nsel, order, min_count, max_count, out, cap, info) -> rc"""
+    order, min_count, max_count, limit = _tally_args(order, min_count, max_count, limit)
+    if fields is None and bytes_ is None:
+        mode, d, sel, cut = TALLY_LINES, 0, np.zeros(0, dtype=CUT_RANGE_DTYPE), None
+    else:
+        mode, d, sel = _cut_args(fields, bytes_, delimiter)
+        cut = dict(fields=fields, bytes=bytes_, delimiter=delimiter)
+    first, cnt = int(first), 2 ** 64 - 1 if count is None else int(count)
+    window = max(min(first + cnt, lines.newlines + 1) - first, 0)          # the window's lines by the table: no more groups than that
+    head = (first, cnt, int(seed), mode, d, sel.ctypes.data if sel.size else None, sel.size, order, min_count, max_count)
+    return _tally(lambda *a: call(*head, *a), limit, window, StreamTallyInfo(), cut)
+
+
+def tally_lines_device(d_in_ptr, n, index, lines, fields=None, bytes=None, delimiter=b"\t", first=0, count=None, seed=0, order="count", min_count=1,
+                       max_count=0, limit=None, device=-1):
+    """Bzip2Index.tally_lines with the stream in GPU memory (cjs_bzip2_tally_device; the memory rules of decompress_device).  The
+    result is host memory."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    return _tally_lines(lambda *a: L.cjs_bzip2_tally_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), lines, fields, bytes, delimiter, first,
+                        count, seed, order, min_count, max_count, limit)
 
 
 class SearchResult:

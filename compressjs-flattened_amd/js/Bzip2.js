@@ -391,20 +391,46 @@ function cutList(spec) {
   }
   return Float64Array.from(flat);
 }
+function cutDelimiter(d) {
+  if (d === undefined) { d = '\t'; }
+  if (typeof d === 'number') { return d; }
+  var raw = typeof d === 'string' ? Buffer.from(d, 'latin1') : Buffer.from(common.coerceInput(d).bytes);
+  if (raw.length !== 1) { throw new TypeError('the delimiter is one byte'); }
+  return raw[0];
+}
 Bzip2.cutLines = function (inStream, index, lineIndex, opts) {
   var input = common.coerceInput(inStream), o = opts || {}, r;
   if ((o.fields === undefined || o.fields === null) === (o.bytes === undefined || o.bytes === null)) { throw new TypeError('exactly one of fields and bytes must be given'); }
-  var byBytes = o.fields === undefined || o.fields === null, d = o.delimiter === undefined ? '\t' : o.delimiter;
-  if (typeof d !== 'number') {
-    var raw = typeof d === 'string' ? Buffer.from(d, 'latin1') : Buffer.from(common.coerceInput(d).bytes);
-    if (raw.length !== 1) { throw new TypeError('the delimiter is one byte'); }
-    d = raw[0];
-  }
+  var byBytes = o.fields === undefined || o.fields === null, d = cutDelimiter(o.delimiter);
   try {
     r = common.addon().bzip2Cut(input.bytes, index, lineIndex, byBytes ? 1 : 0, d, cutList(byBytes ? o.bytes : o.fields), o.first === undefined ? 0 : o.first,
                                 o.count === undefined || o.count === null ? -1 : o.count);
   } catch (e) { rethrowWithDetail(e); }
   return Buffer.from(r.buffer, r.byteOffset, r.length);
+};
+// The line frequency table (cjs_bzip2_tally; `bzcat | sort | uniq -c | sort -rn | head`): the lines' keys are made and grouped on the
+// GPU and only the groups come down.  tallyLines returns {groups: Uint8Array (32 bytes per group, little-endian: u64 hash, u32 len,
+// u32 check, u64 first = the number of the group's first line, u64 count), nLines, nDistinct, nGroups, nBadLines, maxCount,
+// badBlocks, firstBadBlock (null if none), detail} for lines first .. first + count - 1 (count undefined: to the last).  order
+// 'count' (default): descending count, ties by first occurrence; 'first': by first occurrence.  minCount 2 is uniq -d, maxCount 1 is
+// uniq -u; limit: the first so many groups (undefined: all).  A tail without a newline counts as the line with one; lines that touch
+// a damaged block are counted in nBadLines and grouped nowhere.  fields | bytes (with delimiter, as cutLines takes them): the tally
+// of that cut -- which values of a column occur how often; a damaged block inside the window then throws as it does in cutLines.
+Bzip2.tallyLines = function (inStream, index, lineIndex, opts) {
+  var o = opts || {}, input = common.coerceInput(inStream), r;
+  var order = o.order === undefined || o.order === 'count' ? 1 : o.order === 'first' ? 0 : -1;
+  if (order < 0) throw new TypeError("order is 'count' or 'first'");
+  var noFields = o.fields === undefined || o.fields === null, noBytes = o.bytes === undefined || o.bytes === null;
+  if (!noFields && !noBytes) { throw new TypeError('at most one of fields and bytes may be given'); }
+  var mode = noFields && noBytes ? 2 : noFields ? 1 : 0;
+  try {
+    r = common.addon().bzip2Tally(input.bytes, index, lineIndex, o.first === undefined ? 0 : o.first, o.count === undefined || o.count === null ? -1 : o.count,
+                                  o.seed === undefined ? 0 : o.seed, order, o.minCount === undefined ? 1 : o.minCount, o.maxCount === undefined ? 0 : o.maxCount,
+                                  o.limit === undefined || o.limit === null ? -1 : o.limit, mode, mode === 2 ? 0 : cutDelimiter(o.delimiter),
+                                  mode === 2 ? '' : cutList(mode === 1 ? o.bytes : o.fields));
+  } catch (e) { rethrowWithDetail(e); }
+  r.firstBadBlock = r.firstBadBlock < 0 ? null : r.firstBadBlock;
+  return r;
 };
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;

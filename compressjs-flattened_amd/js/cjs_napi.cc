@@ -50,6 +50,8 @@ struct Api {
   int (*line_keys)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint64_t, cjs_bz_linekey*, size_t, cjs_bz_linekeys_info*,
                    const cjs_opts*) = nullptr;
   int (*line_keys_diff)(const cjs_bz_linekey*, size_t, const cjs_bz_linekey*, size_t, uint64_t, cjs_bz_hunk*, size_t, cjs_bz_ldiff_info*) = nullptr;
+  int (*tally)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint64_t, uint32_t, uint32_t, const cjs_cut_range*, uint32_t,
+               uint32_t, uint64_t, uint64_t, cjs_bz_tally*, size_t, cjs_bz_tally_info*, const cjs_opts*) = nullptr;
   int (*cut)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint32_t, uint32_t, const cjs_cut_range*, uint32_t, uint8_t**,
              size_t*, cjs_bz_cut_info*, const cjs_opts*) = nullptr;
   int (*cut_list_parse)(const char*, cjs_cut_range*, uint32_t, uint32_t*) = nullptr;
@@ -101,7 +103,7 @@ bool load_api() {
   SYM(index_info, "cjs_bzip2_index_info") SYM(compare, "cjs_bzip2_compare") SYM(compare_streams, "cjs_bzip2_compare_streams")
   SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
-  SYM(line_keys, "cjs_bzip2_line_keys") SYM(line_keys_diff, "cjs_line_keys_diff")
+  SYM(line_keys, "cjs_bzip2_line_keys") SYM(line_keys_diff, "cjs_line_keys_diff") SYM(tally, "cjs_bzip2_tally")
   SYM(cut, "cjs_bzip2_cut") SYM(cut_list_parse, "cjs_cut_list_parse")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
@@ -609,6 +611,111 @@ napi_value bzip2_line_keys(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// a cut LIST argument: a cut-style string (cjs_cut_list_parse) or a Float64Array of (lo, hi) pairs, hi < 0: to the end of the line.
+// false: an exception is pending
+static bool get_cut_list(napi_env env, napi_value v, std::vector<cjs_cut_range>& sel, uint32_t& nsel) {
+  sel.assign(64, cjs_cut_range{0, 0});
+  nsel = 0;
+  napi_valuetype kind = napi_undefined;
+  napi_typeof(env, v, &kind);
+  if (kind == napi_string) {
+    size_t len = 0;
+    napi_get_value_string_utf8(env, v, nullptr, 0, &len);
+    std::string list(len + 1, 0);
+    napi_get_value_string_utf8(env, v, &list[0], len + 1, &len);
+    const int rc = api.cut_list_parse(list.c_str(), sel.data(), 64, &nsel);
+    if (rc != 0) { throw_code(env, rc); return false; }
+  } else {
+    bool is_ta = false;
+    napi_is_typedarray(env, v, &is_ta);
+    napi_typedarray_type t = napi_int8_array; size_t len = 0; void* d = nullptr; napi_value ab; size_t off = 0;
+    if (is_ta) napi_get_typedarray_info(env, v, &t, &len, &d, &ab, &off);
+    if (!is_ta || t != napi_float64_array || (len & 1)) { napi_throw_type_error(env, nullptr, "list is a string or a Float64Array of (lo, hi) pairs"); return false; }
+    const double* q = (const double*)d;
+    sel.resize(len / 2 ? len / 2 : 1);
+    for (size_t k = 0; k < len / 2; k++) {
+      const double lo = q[2 * k], hi = q[2 * k + 1] < 0 ? 4294967295.0 : q[2 * k + 1];
+      if (!(lo >= 0 && lo <= 4294967295.0 && hi <= 4294967295.0 && lo == (double)(uint32_t)lo && hi == (double)(uint32_t)hi)) {
+        napi_throw_type_error(env, nullptr, "a unit number is an integer that fits 32 bits"); return false;
+      }
+      sel[k].lo = (uint32_t)lo; sel[k].hi = (uint32_t)hi;
+    }
+    nsel = len / 2 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(len / 2);      // (the library refuses none and more than 64)
+  }
+  return true;
+}
+
+// bzip2Tally(input, index, lineIndex, first, count, seed, order, minCount, maxCount, limit, mode, delim, list) -> { groups: Uint8Array, nLines, nDistinct,
+// nGroups, nBadLines, maxCount, badBlocks, firstBadBlock, detail } (Bzip2.tallyLines).  groups: the 32-byte records (cjs_bz_tally,
+// little-endian: u64 hash, u32 len, u32 check, u64 first, u64 count) of the first `limit` groups (limit < 0: all of them; the
+// window's lines by the table bound their number) of lines first .. first + count - 1 (count < 0: to the last); order 0: by first
+// occurrence, 1: by descending count.  The numbers are integers from 0 to 2^53.  mode 2: whole lines (delim and list are not looked
+// at); mode 0 / 1 with a delimiter byte and a list as bzip2Cut takes them: the tally of that cut.
+napi_value bzip2_tally(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 13; napi_value argv[13];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *lp = nullptr; size_t n = 0, in = 0, ln = 0;
+  uint32_t mode = 2, delim = 0;
+  if (argc < 13 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &lp, &ln) ||
+      napi_get_value_uint32(env, argv[10], &mode) != napi_ok || napi_get_value_uint32(env, argv[11], &delim) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array line index, first, count, seed, order, minCount, maxCount, limit, mode, "
+                          "delimiter byte, list)");
+    return nullptr;
+  }
+  std::vector<cjs_cut_range> sel;
+  uint32_t nsel = 0;
+  if (mode != 2 && !get_cut_list(env, argv[12], sel, nsel)) return nullptr;
+  uint64_t first = 0, count = ~0ull, seed = 0, order = 0, lo = 0, hi = 0, limit = 0;
+  double c = -1, lim = -1;
+  napi_get_value_double(env, argv[4], &c);
+  napi_get_value_double(env, argv[9], &lim);
+  if (!get_whole(env, argv[3], &first) || (c >= 0 && !get_whole(env, argv[4], &count)) || !(c >= 0 || c == -1) || !get_whole(env, argv[5], &seed) ||
+      !get_whole(env, argv[6], &order) || !get_whole(env, argv[7], &lo) || !get_whole(env, argv[8], &hi) || (lim >= 0 && !get_whole(env, argv[9], &limit)) ||
+      !(lim >= 0 || lim == -1)) {
+    napi_throw_type_error(env, nullptr, "first, count, seed, minCount, maxCount and limit are integers from 0 to 2^53"); return nullptr;
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_lines* lt = nullptr;
+  rc = api.lines_load(lp ? lp : &dummy, ln, ix, &lt);
+  if (rc != 0) { api.index_destroy(ix); return throw_code(env, rc); }
+  cjs_bz_linekeys_info ki;
+  rc = api.line_keys(p ? p : &dummy, n, ix, lt, first, count, seed, nullptr, 0, &ki, nullptr);      // the window's lines: the table alone
+  cjs_bz_tally_info ti;
+  std::vector<cjs_bz_tally> groups;
+  std::string detail;
+  if (rc == 0) {
+    const size_t cap = (size_t)(lim < 0 || limit > ki.n_lines ? ki.n_lines : limit);
+    groups.resize(cap ? cap : 1);
+    rc = api.tally(p ? p : &dummy, n, ix, lt, first, count, seed, mode, delim, nsel ? sel.data() : nullptr, nsel, order > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)order, lo, hi, cap ? groups.data() : nullptr, cap, &ti,
+                   nullptr);
+    if (rc == 0) groups.resize((size_t)(ti.n_groups < cap ? ti.n_groups : cap));
+    if (rc == 0 && ti.n_bad_blocks) detail = api.detail_();      // (before the next call of the library on this thread)
+  }
+  if (rc != 0) throw_code(env, rc);                           // (the detail is read before the next call of the library on this thread)
+  api.lines_destroy(lt);
+  api.index_destroy(ix);
+  if (rc != 0) return nullptr;
+  napi_value res = nullptr, ab, ta, v; void* dst = nullptr;
+  napi_create_arraybuffer(env, sizeof(cjs_bz_tally) * groups.size(), &dst, &ab);
+  if (!groups.empty()) memcpy(dst, groups.data(), sizeof(cjs_bz_tally) * groups.size());
+  napi_create_object(env, &res);
+  napi_create_typedarray(env, napi_uint8_array, sizeof(cjs_bz_tally) * groups.size(), ab, 0, &ta);
+  napi_set_named_property(env, res, "groups", ta);
+  napi_create_double(env, (double)ti.n_lines, &v); napi_set_named_property(env, res, "nLines", v);
+  napi_create_double(env, (double)ti.n_distinct, &v); napi_set_named_property(env, res, "nDistinct", v);
+  napi_create_double(env, (double)ti.n_groups, &v); napi_set_named_property(env, res, "nGroups", v);
+  napi_create_double(env, (double)ti.n_bad_lines, &v); napi_set_named_property(env, res, "nBadLines", v);
+  napi_create_double(env, (double)ti.max_count, &v); napi_set_named_property(env, res, "maxCount", v);
+  napi_create_double(env, (double)ti.n_bad_blocks, &v); napi_set_named_property(env, res, "badBlocks", v);
+  napi_create_double(env, ti.n_bad_blocks ? (double)ti.first_bad_block : -1.0, &v); napi_set_named_property(env, res, "firstBadBlock", v);
+  napi_create_string_utf8(env, detail.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, res, "detail", v);
+  return res;
+}
+
 // bzip2Cut(input, index, lineIndex, mode, delim, list, first, count) -> Uint8Array (Bzip2.cutLines): the fields (mode 0, delimiter
 // byte delim) or byte positions (mode 1) that `list` selects of lines first .. first + count - 1 (count < 0: to the last), each
 // line's output behind the other's (cjs_bzip2_cut).  list: a cut-style string ("1,3-5,7-"; cjs_cut_list_parse) or a Float64Array of
@@ -629,34 +736,9 @@ napi_value bzip2_cut(napi_env env, napi_callback_info info) {
   if (!get_whole(env, argv[6], &first) || (c >= 0 && !get_whole(env, argv[7], &count)) || !(c >= 0 || c == -1)) {
     napi_throw_type_error(env, nullptr, "first and count are integers from 0 to 2^53"); return nullptr;
   }
-  std::vector<cjs_cut_range> sel(64);
+  std::vector<cjs_cut_range> sel;
   uint32_t nsel = 0;
-  napi_valuetype kind = napi_undefined;
-  napi_typeof(env, argv[5], &kind);
-  if (kind == napi_string) {
-    size_t len = 0;
-    napi_get_value_string_utf8(env, argv[5], nullptr, 0, &len);
-    std::string list(len + 1, 0);
-    napi_get_value_string_utf8(env, argv[5], &list[0], len + 1, &len);
-    const int rc = api.cut_list_parse(list.c_str(), sel.data(), 64, &nsel);
-    if (rc != 0) return throw_code(env, rc);
-  } else {
-    bool is_ta = false;
-    napi_is_typedarray(env, argv[5], &is_ta);
-    napi_typedarray_type t = napi_int8_array; size_t len = 0; void* d = nullptr; napi_value ab; size_t off = 0;
-    if (is_ta) napi_get_typedarray_info(env, argv[5], &t, &len, &d, &ab, &off);
-    if (!is_ta || t != napi_float64_array || (len & 1)) { napi_throw_type_error(env, nullptr, "list is a string or a Float64Array of (lo, hi) pairs"); return nullptr; }
-    const double* q = (const double*)d;
-    sel.resize(len / 2 ? len / 2 : 1);
-    for (size_t k = 0; k < len / 2; k++) {
-      const double lo = q[2 * k], hi = q[2 * k + 1] < 0 ? 4294967295.0 : q[2 * k + 1];
-      if (!(lo >= 0 && lo <= 4294967295.0 && hi <= 4294967295.0 && lo == (double)(uint32_t)lo && hi == (double)(uint32_t)hi)) {
-        napi_throw_type_error(env, nullptr, "a unit number is an integer that fits 32 bits"); return nullptr;
-      }
-      sel[k].lo = (uint32_t)lo; sel[k].hi = (uint32_t)hi;
-    }
-    nsel = len / 2 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(len / 2);      // (the library refuses none and more than 64)
-  }
+  if (!get_cut_list(env, argv[5], sel, nsel)) return nullptr;
   static const uint8_t dummy = 0;
   cjs_bz_index* ix = nullptr;
   int rc = api.index_load(ip ? ip : &dummy, in, &ix);
@@ -1113,6 +1195,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2LinesAsk", nullptr, bzip2_lines_ask, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2LineKeys", nullptr, bzip2_line_keys, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"lineKeysDiff", nullptr, line_keys_diff, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2Tally", nullptr, bzip2_tally, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Cut", nullptr, bzip2_cut, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2CompressIndexed", nullptr, bzip2_compress_indexed, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncIndex", nullptr, enc_index, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -442,6 +442,41 @@ int cjs_bzip2_line_keys_device(const uint8_t *d_in, size_t n, const cjs_bz_index
 int cjs_stage_line_keys(const uint8_t *text, size_t n, uint64_t seed, cjs_bz_linekey *keys, size_t cap, size_t *n_lines);
 int cjs_line_keys_diff(const cjs_bz_linekey *a, size_t na, const cjs_bz_linekey *b, size_t nb, uint64_t max_edits, cjs_bz_hunk *hunks,
                        size_t cap, cjs_bz_ldiff_info *info);
+/* cjs_keys_tally: the frequency table of a list of line keys (`... | sort | uniq -c | sort -rn | head` over keys), grouped on the
+ * GPU: only the groups asked for leave it.
+ * GROUPS: two records are one group iff all three fields are equal, the equality cjs_line_keys_diff uses.  An all-ones record
+ * belongs to no group; info->n_bad counts them.  A group's `first` is the lowest index of a member in keys, `count` its size,
+ * `key` the record.  info->n_keys = n, n_distinct = all groups, max_count = the size of the largest of them, n_groups = the groups
+ * with min_count <= count and (max_count == 0 or count <= max_count): `uniq -d` is min_count = 2, `uniq -u` is max_count = 1.
+ * ORDER of those groups: CJS_TALLY_BY_FIRST, ascending first occurrence, or CJS_TALLY_BY_COUNT, descending count with ties by
+ * ascending first occurrence.  Both are total, so the output is fully determined: `out` gets the first min(cap, n_groups) groups
+ * and nothing past them is written (cap = 0, out = NULL: the count query, which runs everything and writes nothing).  The order
+ * of `sort` itself, by content, is NOT offered: keys do not order as lines do.
+ * n == 0 is answered without a device.  n > 2^32 - 2: CJS_E_UNSUPPORTED (the sorter's indices are 32 bits).
+ * On the device: a sort word len << 32 | check per record with its index as the value, a stable LSD radix sort over it, the hashes
+ * gathered through that permutation and a second stable sort over them -- together the sort by the whole record with ties in input
+ * order, the bad records last; a head flag per record from a compare of the whole record with its predecessor's, a scan, every
+ * group's head position (count = the distance to the next head, first = the index at the head), the filter as a compaction by
+ * scan, a sort of the kept groups by the order word and an emit of the first cap of them.  No atomic decides an order.  Besides
+ * the groups the host reads four scalars.  Device memory: 37 bytes per key, the sorter's histograms and, in the host form, the
+ * keys (16 bytes each) and the groups written.
+ * cjs_keys_tally: keys and out are host memory.  cjs_keys_tally_device: both are memory of the GPU; d_keys must be 8-byte aligned
+ * (a record array at an address that is no multiple of 16 is served) and d_out 16-byte aligned, anything else is refused.
+ * CJS_E_INVALID_ARG before the device is touched: NULL info, NULL keys with n > 0, NULL out with cap > 0, an unknown order,
+ * max_count != 0 below min_count, a misaligned pointer of the device form; before any launch: a pointer of the device form that is
+ * not memory of the GPU.  opts->device is honoured.  info is host memory.
+ * cjs_stage_keys_tally EXISTS FOR TESTS; no product path calls it: the same rule on the host with std::stable_sort
+ * (csrc/tally_plan.h), without a device. */
+typedef struct { cjs_bz_linekey key; uint64_t first; uint64_t count; } cjs_bz_tally;   /* 32 bytes */
+typedef struct { uint64_t n_keys, n_bad, n_distinct, n_groups, max_count; } cjs_tally_info;
+#define CJS_TALLY_BY_FIRST 0u   /* ascending first occurrence */
+#define CJS_TALLY_BY_COUNT 1u   /* descending count, ties by ascending first occurrence */
+int cjs_keys_tally(const cjs_bz_linekey *keys, size_t n, uint32_t order, uint64_t min_count, uint64_t max_count, cjs_bz_tally *out,
+                   size_t cap, cjs_tally_info *info, const cjs_opts *opts);
+int cjs_keys_tally_device(const cjs_bz_linekey *d_keys, size_t n, uint32_t order, uint64_t min_count, uint64_t max_count,
+                          cjs_bz_tally *d_out, size_t cap, cjs_tally_info *info, const cjs_opts *opts);
+int cjs_stage_keys_tally(const cjs_bz_linekey *keys, size_t n, uint32_t order, uint64_t min_count, uint64_t max_count,
+                         cjs_bz_tally *out, size_t cap, cjs_tally_info *info);
 /* cjs_bzip2_cut: fields or byte columns of the lines of an indexed stream (`bzcat x.bz2 | cut -f LIST` / `cut -b LIST`), selected
  * and packed on the GPU while the blocks stand decoded there: only the selected bytes leave it.
  * The WINDOW is lines [first, min(first + count, N + 1)) as the line table numbers them, as in cjs_bzip2_line_keys: line N is the
@@ -492,6 +527,55 @@ int cjs_bzip2_cut_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx,
 int cjs_stage_cut(const uint8_t *text, size_t n, uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel,
                   uint8_t *out, size_t cap, size_t *out_n);
 int cjs_cut_list_parse(const char *list, cjs_cut_range *sel, uint32_t cap, uint32_t *nsel);
+/* cjs_bzip2_tally: the frequency table of the lines of an indexed stream (`bzcat x.bz2 | sort | uniq -c | sort -rn | head`): the
+ * keys of cjs_bzip2_line_keys, made by the same passes over the same touched blocks of the same window, stay in GPU memory and are
+ * grouped there as by cjs_keys_tally; the first min(cap, n_groups) groups come down, `first` being an absolute line number of the
+ * table (the window's first + the index in the window).  out and info are HOST memory in both forms.
+ * mode CJS_TALLY_LINES: the key of a line is its cjs_bzip2_line_keys record, newline included, with one rule for the tail: a tail
+ * line that is not empty is keyed as if it ended in a newline (so it groups with the earlier lines of its content), an empty tail
+ * is no line (info->n_lines does not count it), as in cjs_bzip2_cut.  delim, sel and nsel are ignored.
+ * modes CJS_CUT_FIELDS / CJS_CUT_BYTES ("which values of column 3 occur how often"): the key of a line is the key of its
+ * cjs_bzip2_cut output line, the selected bytes plus "\n"; cut's stated difference from GNU cut holds here too.  A composition:
+ * cjs_bzip2_cut_device into a pooled device buffer of the touched blocks' bytes + 1 (the host form uploads the stream first), the
+ * keys of that text's lines by the kernels of cjs_bzip2_line_keys over pieces of at most 900,000 bytes, which they see as they
+ * see a block (a piece's record count comes down before its records are written at their ranks; the pieces are joined on the host
+ * as blocks are), then the grouping.  A bad block in the window fails the call exactly as cjs_bzip2_cut fails, with its code,
+ * detail and info->n_bad_blocks / first_bad_block; the selection's argument checks are cut's.  Device memory on top of the
+ * figures below: the stream (host form), the touched blocks' bytes + 1, and about 100 bytes per 16 KiB of them.
+ * The rest of this comment is the whole-line mode's.
+ * A line that may touch a bad block (an all-ones record of cjs_bzip2_line_keys) is grouped nowhere and counted in
+ * info->n_bad_lines; the call does not fail, info->n_bad_blocks / first_bad_block and cjs_last_error_detail() follow
+ * cjs_bzip2_line_keys.  The sum of the counts of all groups is n_lines - n_bad_lines.  A block whose newlines differ from the
+ * table's: CJS_E_DATA_ERROR as there.  cap = 0, out = NULL: the count query, which runs everything.  An empty window, and a
+ * stream without a block, are answered without a device.
+ * The records do not cross the bus: a block's whole-line records go to their ranks in a device array of the window's lines by
+ * device-to-device copies, 16 bytes per touched block come down beside its tail fragment, the host joins the lines that span
+ * blocks as cjs_bzip2_line_keys does, and those records (at most one per touched block, and the tail) go up as patches at the
+ * end, the lines of bad blocks as fills.  Device memory beyond a pass's: 53 bytes per line of the window (16 for its record, 37
+ * for the grouping), the sorter's histograms, 24 bytes per touched block and 32 bytes per group that can come down (min(cap,
+ * the window's lines)), all sized from the table and taken before the first pass (failure: CJS_E_OUT_OF_MEMORY).  A window of
+ * more than 2^32 - 2 lines: CJS_E_UNSUPPORTED, checked before the device is touched, in every mode.
+ * CJS_E_INVALID_ARG before the device is touched: the argument errors of cjs_bzip2_line_keys (out for keys), an unknown order,
+ * max_count != 0 below min_count, an unknown mode, the selection errors of cjs_bzip2_cut.  opts->device is honoured.  CJS_DEBUG:
+ * one "[cjs tally]" line per call (form, window, mode, ..., H2D and D2H bytes).
+ * cjs_stage_bzip2_tally_limit and cjs_stage_text_keys_device EXIST FOR TESTS; no product path calls them.  The first is the
+ * whole-line tally by count with the limit on the window's lines as an argument (exactly one of in / d_in).  The second is the
+ * middle step of the tally of a cut: the keys of the lines of plain text in GPU memory, one per newline and one for the tail
+ * whatever it is (what cjs_stage_line_keys gives), brought down to keys (host); piece_bytes 0: 900,000. */
+typedef struct { uint64_t n_lines, n_bad_lines, n_distinct, n_groups, max_count, blocks_decoded, n_bad_blocks, first_bad_block; } cjs_bz_tally_info;
+#define CJS_TALLY_LINES 2u   /* beside CJS_CUT_FIELDS 0u and CJS_CUT_BYTES 1u */
+int cjs_bzip2_tally(const uint8_t *in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first, uint64_t count,
+                    uint64_t seed, uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel, uint32_t order,
+                    uint64_t min_count, uint64_t max_count, cjs_bz_tally *out, size_t cap, cjs_bz_tally_info *info, const cjs_opts *opts);
+int cjs_bzip2_tally_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first,
+                           uint64_t count, uint64_t seed, uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel,
+                           uint32_t order, uint64_t min_count, uint64_t max_count, cjs_bz_tally *out, size_t cap,
+                           cjs_bz_tally_info *info, const cjs_opts *opts);
+int cjs_stage_bzip2_tally_limit(const uint8_t *in, const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines,
+                                uint64_t first, uint64_t count, uint64_t max_lines, cjs_bz_tally *out, size_t cap,
+                                cjs_bz_tally_info *info, const cjs_opts *opts);
+int cjs_stage_text_keys_device(const uint8_t *d_text, size_t n, uint64_t seed, cjs_bz_linekey *keys, size_t cap, size_t *n_lines,
+                               size_t piece_bytes, const cjs_opts *opts);
 /* cjs_bzip2_compare: `cmp` over the address space of cjs_bzip2_read_ranges ([0, total_bytes) of the index), done on the GPU: is
  * the decoded stream equal to `other`, and if not, where and with which bytes?  The decoded bytes never leave the GPU, 16 bytes
  * per reported difference do.  other[k] is compared with decoded byte other_off + k.  The COMPARED SPAN is
