@@ -121,9 +121,16 @@ class StreamTallyInfo(ctypes.Structure):
                 ("max_count", ctypes.c_uint64), ("blocks_decoded", ctypes.c_uint64), ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64)]
 
 
+class SortInfo(ctypes.Structure):
+    """cjs_bz_sort_info (64 bytes)."""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_out", ctypes.c_uint64), ("n_distinct", ctypes.c_uint64), ("text_bytes", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint64), ("blocks_decoded", ctypes.c_uint64), ("n_bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64)]
+
+
 LINE_KEY_DTYPE = np.dtype([("hash", "<u8"), ("len", "<u4"), ("check", "<u4")])
 TALLY_DTYPE = np.dtype([("hash", "<u8"), ("len", "<u4"), ("check", "<u4"), ("first", "<u8"), ("count", "<u8")])      # cjs_bz_tally (32 bytes)
 TALLY_BY_FIRST, TALLY_BY_COUNT, TALLY_LINES = 0, 1, 2
+SORT_REVERSE, SORT_UNIQUE, SORT_LINES = 1, 2, 2
 CUT_RANGE_DTYPE = np.dtype([("lo", "<u4"), ("hi", "<u4")])
 CUT_FIELDS, CUT_BYTES, CUT_TO_END = 0, 1, 0xFFFFFFFF
 
@@ -230,6 +237,14 @@ def load_library():
     stream_tally_tail = [V, V, U64, U64, U64, U32, U32, V, U32, U32, U64, U64, V, S, ctypes.POINTER(StreamTallyInfo), V]
     L.cjs_bzip2_tally.argtypes = [u8p, S] + stream_tally_tail
     L.cjs_bzip2_tally_device.argtypes = [V, S] + stream_tally_tail
+    PSI = ctypes.POINTER(SortInfo)
+    L.cjs_text_sort.argtypes = [V, S, U32, V, V, S, PP, PS, PSI, V]
+    L.cjs_text_sort_device.argtypes = [V, S, U32, V, V, S, V, S, PS, PSI, V]
+    L.cjs_stage_text_sort.argtypes = [V, S, U32, V, V, S, PSI]
+    sort_head = [V, V, U64, U64, U32, U32, V, U32, U32, V, V, S]
+    L.cjs_bzip2_sort.argtypes = [u8p, S] + sort_head + [PP, PS, PSI, V]
+    L.cjs_bzip2_sort_device.argtypes = [V, S] + sort_head + [V, S, PS, PSI, V]
+    L.cjs_stage_bzip2_sort_limit.argtypes = [u8p, V, S, V, V, U64, U64, U64, U64, U32, V, V, S, PSI, V]
     cut_head = [V, V, U64, U64, U32, U32, V, U32]
     L.cjs_bzip2_cut.argtypes = [u8p, S] + cut_head + [PP, PS, ctypes.POINTER(CutInfo), V]
     L.cjs_bzip2_cut_device.argtypes = [V, S] + cut_head + [V, S, PS, ctypes.POINTER(CutInfo), V]
@@ -1004,6 +1019,25 @@ class Bzip2Index:
         return _tally_lines(lambda *a: L.cjs_bzip2_tally(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a, None), lines, fields, bytes, delimiter, first, count,
                             seed, order, min_count, max_count, limit)
 
+    def sort_lines(self, data, lines, fields=None, bytes=None, delimiter=b"\t", first=0, count=None, reverse=False, unique=False, limit=None, want_text=False):
+        """`bzcat | sort` over lines [first, first + count) (count=None: to the last), ordered by content on the GPU
+        (cjs_bzip2_sort) -> SortResult: the absolute numbers of the lines in LC_ALL=C order (bytes as Python orders them; equal
+        lines by ascending number).  reverse: descending content (`sort -r`, equal lines still ascending); unique: one entry per
+        run of equal lines, its lowest number, with the run's size in .counts (`sort -u`, `sort | uniq -c`); limit: the first so
+        many entries (`sort | head`; None: all); want_text: the text of the returned entries, each with a newline, in .text.  A
+        tail without a newline is a line, an empty tail is none.  fields / bytes (one of them, with delimiter, as in cut_lines):
+        the cut of each line is what is compared and what .text holds; the numbers are still those of whole lines (`sort -s -k`).
+        A bad block inside the window fails the call as it fails cut_lines."""
+        L = load_library()
+        data = _coerce_input(data)
+        keep = data if data.size else np.zeros(1, dtype=np.uint8)
+        out, out_n = u8p(), ctypes.c_size_t(0)
+        text = (ctypes.byref(out), ctypes.byref(out_n)) if want_text else (None, None)
+        res = _sort_lines(lambda *a: L.cjs_bzip2_sort(keep.ctypes.data_as(u8p), data.size, self._h, lines._h, *a[:-1], *text, a[-1], None), lines, fields, bytes,
+                          delimiter, first, count, reverse, unique, limit)
+        res.text = _adopt(out, out_n.value).tobytes() if want_text else None
+        return res
+
     def diff_stream(self, data, lines, other_data, other_index, other_lines, max_edits=0, seed=0):
         """bzdiff on the GPU: the line diff of this stream (A) against the stream `other_data` of `other_index` (B) -> LineDiff.
         Both streams' lines are hashed where they stand decoded (line_keys); the diff runs on the host over 16 bytes per line
@@ -1381,6 +1415,124 @@ def tally_lines_device(d_in_ptr, n, index, lines, fields=None, bytes=None, delim
     opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
     return _tally_lines(lambda *a: L.cjs_bzip2_tally_device(d_in_ptr, n, index._h, lines._h, *a, ctypes.byref(opts)), lines, fields, bytes, delimiter, first,
                         count, seed, order, min_count, max_count, limit)
+
+
+class SortResult:
+    """A sort: lines = the line numbers (uint64) in the order asked for, at most `limit` of them; counts = the size of each
+    entry's run of equal lines (all ones without unique); text = the returned entries' lines, each with a newline (None unless
+    asked for; the device forms give its size in text_n instead); n_lines = the lines sorted; n_distinct = the runs of equal lines;
+    n_out = the entries the flags select; text_bytes = the size of the text of all n_out entries; rounds = the sort rounds run."""
+
+    def __init__(self, lines, counts, info, text=None, text_n=None):
+        self.lines, self.counts, self.text, self.text_n = lines, counts, text, text_n
+        self.n_lines, self.n_out, self.n_distinct = int(info.n_lines), int(info.n_out), int(info.n_distinct)
+        self.text_bytes, self.rounds = int(info.text_bytes), int(info.rounds)
+        self.blocks_decoded = int(info.blocks_decoded)
+
+
+def sort_text(text, reverse=False, unique=False):
+    """The rule of the line sort restated in Python (no library call) -> (lines, counts): the text's lines (a tail that is not
+    empty is one, an empty tail is none) ordered as Python orders bytes, equal lines by ascending number; reverse: descending
+    content, equal lines still ascending; unique: the first line of every run of equal lines, with the run's size."""
+    body = bytes(_coerce_input(text).tobytes())
+    parts = body.split(b"\n")
+    if parts[-1] == b"":
+        parts.pop()
+    runs = []                                                   # [[line numbers]] per distinct content, ascending content
+    for i in sorted(range(len(parts)), key=lambda i: (parts[i], i)):
+        if runs and parts[runs[-1][0]] == parts[i]:
+            runs[-1].append(i)
+        else:
+            runs.append([i])
+    if reverse:
+        runs.reverse()
+    if unique:
+        return [r[0] for r in runs], [len(r) for r in runs]
+    return [i for r in runs for i in r], [1] * len(parts)
+
+
+def _sort_flags(reverse, unique, limit):
+    if limit is not None and int(limit) < 0:
+        raise ValueError("limit is None or a count")
+    return (SORT_REVERSE if reverse else 0) | (SORT_UNIQUE if unique else 0), None if limit is None else int(limit)
+
+
+def _sort(call, limit, most, text_n=None):
+    """call(lines_out, counts_out, cap, info) -> rc, once: with room for `limit` entries, or without a limit for `most`"""
+    info = SortInfo()
+    cap = int(most) if limit is None else min(limit, int(most))
+    lines_out, counts = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    rc = call(lines_out.ctypes.data if cap else None, counts.ctypes.data if cap else None, cap, ctypes.byref(info))
+    try:
+        _check(rc)
+    except CjsError as e:
+        e.need = text_n.value if rc == -33 and text_n is not None else None
+        raise
+    m = min(cap, int(info.n_out))
+    return SortResult(lines_out[:m].copy(), counts[:m].copy(), info, None, None if text_n is None else text_n.value)
+
+
+def text_sort(text, reverse=False, unique=False, limit=None, want_text=False, device=-1):
+    """`sort` over the lines of a plain host buffer, ordered on the GPU (cjs_text_sort) -> SortResult; the arguments are those of
+    Bzip2Index.sort_lines, the line numbers count from 0."""
+    L = load_library()
+    flags, limit = _sort_flags(reverse, unique, limit)
+    text = _coerce_input(text)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    out, out_n = u8p(), ctypes.c_size_t(0)
+    tp = (ctypes.byref(out), ctypes.byref(out_n)) if want_text else (None, None)
+    ptr = text.ctypes.data if text.size else None
+    res = _sort(lambda lo, co, cap, info: L.cjs_text_sort(ptr, text.size, flags, lo, co, cap, *tp, info, ctypes.byref(opts)), limit,
+                int(np.count_nonzero(text == 10)) + 1)          # (the lines are the newlines and at most a tail)
+    res.text = _adopt(out, out_n.value).tobytes() if want_text else None
+    return res
+
+
+def _sort_lines(call, lines, fields, bytes_, delimiter, first, count, reverse, unique, limit, text_n=None):
+    """call(first, count, mode, delim, sel, nsel, flags, lines_out, counts_out, cap, info) -> rc"""
+    flags, limit = _sort_flags(reverse, unique, limit)
+    if fields is None and bytes_ is None:
+        mode, d, sel = SORT_LINES, 0, np.zeros(0, dtype=CUT_RANGE_DTYPE)
+    else:
+        mode, d, sel = _cut_args(fields, bytes_, delimiter)
+    first, cnt = int(first), 2 ** 64 - 1 if count is None else int(count)
+    window = max(min(first + cnt, lines.newlines + 1) - first, 0)          # the window's lines by the table: no more entries than that
+    head = (first, cnt, mode, d, sel.ctypes.data if sel.size else None, sel.size, flags)
+    return _sort(lambda *a: call(*head, *a), limit, window, text_n)
+
+
+def sort_lines_device(d_in_ptr, n, index, lines, fields=None, bytes=None, delimiter=b"\t", first=0, count=None, reverse=False, unique=False, limit=None,
+                      d_text_out_ptr=None, text_cap=0, want_text=None, device=-1):
+    """Bzip2Index.sort_lines with the stream in GPU memory and, when asked for, the text written to GPU memory
+    (cjs_bzip2_sort_device; the memory rules of decompress_device).  Line numbers and counts are host memory.  Text is wanted
+    when d_text_out_ptr is given or want_text is true (want_text alone: the size query); its size comes back as .text_n; a text
+    above text_cap: CjsError(CJS_E_OUTPUT_TOO_SMALL) whose `need` is the full size, and nothing is written."""
+    L = load_library()
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    wanted = d_text_out_ptr is not None or bool(want_text)
+    text_n = ctypes.c_size_t(0) if wanted else None
+    tn = ctypes.byref(text_n) if wanted else None
+    return _sort_lines(lambda *a: L.cjs_bzip2_sort_device(d_in_ptr, n, index._h, lines._h, *a[:-1], d_text_out_ptr, text_cap, tn, a[-1], ctypes.byref(opts)),
+                       lines, fields, bytes, delimiter, first, count, reverse, unique, limit, text_n)
+
+
+def text_sort_device(d_text_ptr, n, reverse=False, unique=False, d_lines_out_ptr=None, d_counts_out_ptr=None, cap=0, d_text_out_ptr=None, text_cap=0,
+                     want_text=None, device=-1):
+    """text_sort with everything in GPU memory (cjs_text_sort_device) -> SortResult without arrays: the first min(cap, n_out)
+    line numbers and counts stand at d_lines_out_ptr / d_counts_out_ptr (uint64), the text at d_text_out_ptr, .text_n its size."""
+    L = load_library()
+    flags, _ = _sort_flags(reverse, unique, None)
+    opts = _Opts(ctypes.sizeof(_Opts), device, 0, 0, None)
+    wanted = d_text_out_ptr is not None or bool(want_text)
+    text_n, info = ctypes.c_size_t(0), SortInfo()
+    rc = L.cjs_text_sort_device(d_text_ptr, n, flags, d_lines_out_ptr, d_counts_out_ptr, cap, d_text_out_ptr, text_cap, ctypes.byref(text_n) if wanted else None,
+                                ctypes.byref(info), ctypes.byref(opts))
+    try:
+        _check(rc)
+    except CjsError as e:
+        e.need = text_n.value if rc == -33 else None
+        raise
+    return SortResult(None, None, info, None, text_n.value if wanted else None)
 
 
 class SearchResult:

@@ -11,7 +11,7 @@
 //   The ORDER of the kept groups is ascending in a 64-bit word: `first` (CJS_TALLY_BY_FIRST), or (~count & 0xFFFFFFFF) << 32 | first
 //   (CJS_TALLY_BY_COUNT: descending count, ties by ascending first).  Both fit because n < 2^32, and both are total: no two groups
 //   share a first.
-// The order of `sort` itself, by content, is not here: keys do not order as lines do.
+// The order of `sort` itself, by content, is not here but in sort_plan.h: keys do not order as lines do.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

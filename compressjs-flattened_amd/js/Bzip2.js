@@ -432,6 +432,27 @@ Bzip2.tallyLines = function (inStream, index, lineIndex, opts) {
   r.firstBadBlock = r.firstBadBlock < 0 ? null : r.firstBadBlock;
   return r;
 };
+// The line sort (cjs_bzip2_sort; `bzcat | sort`, `| sort | head`, `| sort -u`, `| cut .. | sort`): the lines are ordered by content on
+// the GPU and only their numbers come down.  sortLines returns {lines: Float64Array of line numbers in LC_ALL=C order of their content
+// (equal lines by ascending number), counts: Float64Array (the size of each entry's run of equal lines; all ones without unique),
+// text: Buffer of the returned entries' lines, each with a newline (only with text: true), nLines, nOut, nDistinct, textBytes, rounds}
+// for lines first .. first + count - 1 (count undefined: to the last).  reverse: descending content, equal lines still ascending;
+// unique: one entry per run of equal lines, its lowest number; limit: the first so many entries (undefined: all).  fields | bytes
+// (with delimiter, as cutLines takes them): the cut of each line is what is compared and what text holds; the numbers stay those of
+// whole lines.  A damaged block inside the window throws as it does in cutLines.
+Bzip2.sortLines = function (inStream, index, lineIndex, opts) {
+  var o = opts || {}, input = common.coerceInput(inStream), r;
+  var noFields = o.fields === undefined || o.fields === null, noBytes = o.bytes === undefined || o.bytes === null;
+  if (!noFields && !noBytes) { throw new TypeError('at most one of fields and bytes may be given'); }
+  var mode = noFields && noBytes ? 2 : noFields ? 1 : 0;
+  try {
+    r = common.addon().bzip2Sort(input.bytes, index, lineIndex, o.first === undefined ? 0 : o.first, o.count === undefined || o.count === null ? -1 : o.count,
+                                 (o.reverse ? 1 : 0) | (o.unique ? 2 : 0), o.limit === undefined || o.limit === null ? -1 : o.limit, !!o.text, mode,
+                                 mode === 2 ? 0 : cutDelimiter(o.delimiter), mode === 2 ? '' : cutList(mode === 1 ? o.bytes : o.fields));
+  } catch (e) { rethrowWithDetail(e); }
+  if (r.text !== undefined) { r.text = Buffer.from(r.text.buffer, r.text.byteOffset, r.text.length); }
+  return r;
+};
 Bzip2.REC_SHADOWED = 1;
 Bzip2.Err = Err;
 module.exports = Bzip2;

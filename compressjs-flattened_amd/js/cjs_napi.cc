@@ -52,6 +52,8 @@ struct Api {
   int (*line_keys_diff)(const cjs_bz_linekey*, size_t, const cjs_bz_linekey*, size_t, uint64_t, cjs_bz_hunk*, size_t, cjs_bz_ldiff_info*) = nullptr;
   int (*tally)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint64_t, uint32_t, uint32_t, const cjs_cut_range*, uint32_t,
                uint32_t, uint64_t, uint64_t, cjs_bz_tally*, size_t, cjs_bz_tally_info*, const cjs_opts*) = nullptr;
+  int (*sort)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint32_t, uint32_t, const cjs_cut_range*, uint32_t, uint32_t,
+              uint64_t*, uint64_t*, size_t, uint8_t**, size_t*, cjs_bz_sort_info*, const cjs_opts*) = nullptr;
   int (*cut)(const uint8_t*, size_t, const cjs_bz_index*, const cjs_bz_lines*, uint64_t, uint64_t, uint32_t, uint32_t, const cjs_cut_range*, uint32_t, uint8_t**,
              size_t*, cjs_bz_cut_info*, const cjs_opts*) = nullptr;
   int (*cut_list_parse)(const char*, cjs_cut_range*, uint32_t, uint32_t*) = nullptr;
@@ -104,6 +106,7 @@ bool load_api() {
   SYM(lines_build, "cjs_bzip2_lines_build") SYM(lines_save, "cjs_bzip2_lines_save") SYM(lines_load, "cjs_bzip2_lines_load")
   SYM(lines_destroy, "cjs_bzip2_lines_destroy") SYM(lines_locate, "cjs_bzip2_lines_locate") SYM(lines_number, "cjs_bzip2_lines_number")
   SYM(line_keys, "cjs_bzip2_line_keys") SYM(line_keys_diff, "cjs_line_keys_diff") SYM(tally, "cjs_bzip2_tally")
+  SYM(sort, "cjs_bzip2_sort")
   SYM(cut, "cjs_bzip2_cut") SYM(cut_list_parse, "cjs_cut_list_parse")
   SYM(enc_create, "cjs_bzip2_enc_create") SYM(enc_write, "cjs_bzip2_enc_write") SYM(enc_finish, "cjs_bzip2_enc_finish")
   SYM(enc_pending, "cjs_bzip2_enc_pending") SYM(enc_read, "cjs_bzip2_enc_read") SYM(enc_destroy, "cjs_bzip2_enc_destroy")
@@ -716,6 +719,84 @@ napi_value bzip2_tally(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// bzip2Sort(input, index, lineIndex, first, count, flags, limit, wantText, mode, delim, list) -> { lines: Float64Array, counts: Float64Array, text: Uint8Array
+// or undefined, nLines, nOut, nDistinct, textBytes, rounds } (Bzip2.sortLines): the numbers of lines first .. first + count - 1 (count < 0:
+// to the last) in LC_ALL=C order of their content, equal lines by ascending number; flags 1: descending content, 2: one entry per
+// run of equal lines with the run's size as its count; the first `limit` entries (limit < 0: all); wantText: their lines, each with
+// a newline.  mode 2: whole lines; mode 0 / 1 with a delimiter byte and a list as bzip2Cut takes them: the sort of that cut.  The
+// numbers are integers from 0 to 2^53.
+napi_value bzip2_sort(napi_env env, napi_callback_info info) {
+  if (!load_api()) { napi_throw_error(env, nullptr, api.error.c_str()); return nullptr; }
+  size_t argc = 11; napi_value argv[11];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t *p = nullptr, *ip = nullptr, *lp = nullptr; size_t n = 0, in = 0, ln = 0;
+  uint32_t mode = 2, delim = 0, flags = 0;
+  bool want_text = false;
+  if (argc < 11 || !get_bytes(env, argv[0], &p, &n) || !get_bytes(env, argv[1], &ip, &in) || !get_bytes(env, argv[2], &lp, &ln) ||
+      napi_get_value_uint32(env, argv[5], &flags) != napi_ok || napi_get_value_bool(env, argv[7], &want_text) != napi_ok ||
+      napi_get_value_uint32(env, argv[8], &mode) != napi_ok || napi_get_value_uint32(env, argv[9], &delim) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (Uint8Array, Uint8Array index, Uint8Array line index, first, count, flags, limit, wantText, mode, delimiter byte, list)");
+    return nullptr;
+  }
+  std::vector<cjs_cut_range> sel;
+  uint32_t nsel = 0;
+  if (mode != 2 && !get_cut_list(env, argv[10], sel, nsel)) return nullptr;
+  uint64_t first = 0, count = ~0ull, limit = 0;
+  double c = -1, lim = -1;
+  napi_get_value_double(env, argv[4], &c);
+  napi_get_value_double(env, argv[6], &lim);
+  if (!get_whole(env, argv[3], &first) || (c >= 0 && !get_whole(env, argv[4], &count)) || !(c >= 0 || c == -1) || (lim >= 0 && !get_whole(env, argv[6], &limit)) ||
+      !(lim >= 0 || lim == -1)) {
+    napi_throw_type_error(env, nullptr, "first, count and limit are integers from 0 to 2^53"); return nullptr;
+  }
+  static const uint8_t dummy = 0;
+  cjs_bz_index* ix = nullptr;
+  int rc = api.index_load(ip ? ip : &dummy, in, &ix);
+  if (rc != 0) return throw_code(env, rc);
+  cjs_bz_lines* lt = nullptr;
+  rc = api.lines_load(lp ? lp : &dummy, ln, ix, &lt);
+  if (rc != 0) { api.index_destroy(ix); return throw_code(env, rc); }
+  cjs_bz_linekeys_info ki;
+  rc = api.line_keys(p ? p : &dummy, n, ix, lt, first, count, 0, nullptr, 0, &ki, nullptr);      // the window's lines: the table alone
+  cjs_bz_sort_info si;
+  std::vector<uint64_t> lines, counts;
+  uint8_t* text = nullptr; size_t text_n = 0;
+  if (rc == 0) {
+    const size_t cap = (size_t)(lim < 0 || limit > ki.n_lines ? ki.n_lines : limit);
+    lines.resize(cap ? cap : 1); counts.resize(cap ? cap : 1);
+    rc = api.sort(p ? p : &dummy, n, ix, lt, first, count, mode, delim, nsel ? sel.data() : nullptr, nsel, flags, cap ? lines.data() : nullptr,
+                  cap ? counts.data() : nullptr, cap, want_text ? &text : nullptr, want_text ? &text_n : nullptr, &si, nullptr);
+    if (rc == 0) { lines.resize((size_t)(si.n_out < cap ? si.n_out : cap)); counts.resize(lines.size()); }
+  }
+  if (rc != 0) throw_code(env, rc);                           // (the detail is read before the next call of the library on this thread)
+  api.lines_destroy(lt);
+  api.index_destroy(ix);
+  if (rc != 0) return nullptr;
+  napi_value res = nullptr, ab, ta, v; void* dst = nullptr;
+  napi_create_object(env, &res);
+  const char* names[2] = {"lines", "counts"};
+  const std::vector<uint64_t>* arrays[2] = {&lines, &counts};
+  for (int k = 0; k < 2; k++) {
+    napi_create_arraybuffer(env, sizeof(double) * lines.size(), &dst, &ab);
+    for (size_t i = 0; i < lines.size(); i++) ((double*)dst)[i] = (double)(*arrays[k])[i];
+    napi_create_typedarray(env, napi_float64_array, lines.size(), ab, 0, &ta);
+    napi_set_named_property(env, res, names[k], ta);
+  }
+  if (want_text) {
+    napi_create_arraybuffer(env, text_n, &dst, &ab);
+    if (text_n) memcpy(dst, text, text_n);
+    api.free_(text);
+    napi_create_typedarray(env, napi_uint8_array, text_n, ab, 0, &ta);
+    napi_set_named_property(env, res, "text", ta);
+  }
+  napi_create_double(env, (double)si.n_lines, &v); napi_set_named_property(env, res, "nLines", v);
+  napi_create_double(env, (double)si.n_out, &v); napi_set_named_property(env, res, "nOut", v);
+  napi_create_double(env, (double)si.n_distinct, &v); napi_set_named_property(env, res, "nDistinct", v);
+  napi_create_double(env, (double)si.text_bytes, &v); napi_set_named_property(env, res, "textBytes", v);
+  napi_create_double(env, (double)si.rounds, &v); napi_set_named_property(env, res, "rounds", v);
+  return res;
+}
+
 // bzip2Cut(input, index, lineIndex, mode, delim, list, first, count) -> Uint8Array (Bzip2.cutLines): the fields (mode 0, delimiter
 // byte delim) or byte positions (mode 1) that `list` selects of lines first .. first + count - 1 (count < 0: to the last), each
 // line's output behind the other's (cjs_bzip2_cut).  list: a cut-style string ("1,3-5,7-"; cjs_cut_list_parse) or a Float64Array of
@@ -1196,6 +1277,7 @@ napi_value init(napi_env env, napi_value exports) {
     {"bzip2LineKeys", nullptr, bzip2_line_keys, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"lineKeysDiff", nullptr, line_keys_diff, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Tally", nullptr, bzip2_tally, nullptr, nullptr, nullptr, napi_default, nullptr},
+    {"bzip2Sort", nullptr, bzip2_sort, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2Cut", nullptr, bzip2_cut, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2CompressIndexed", nullptr, bzip2_compress_indexed, nullptr, nullptr, nullptr, napi_default, nullptr},
     {"bzip2EncIndex", nullptr, enc_index, nullptr, nullptr, nullptr, napi_default, nullptr},

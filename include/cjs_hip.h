@@ -576,6 +576,70 @@ int cjs_stage_bzip2_tally_limit(const uint8_t *in, const uint8_t *d_in, size_t n
                                 cjs_bz_tally_info *info, const cjs_opts *opts);
 int cjs_stage_text_keys_device(const uint8_t *d_text, size_t n, uint64_t seed, cjs_bz_linekey *keys, size_t cap, size_t *n_lines,
                                size_t piece_bytes, const cjs_opts *opts);
+/* cjs_text_sort / cjs_bzip2_sort: the lines of a text, or of a window of an indexed stream (`bzcat x.bz2 | sort`, `| sort | head`,
+ * `| sort -u`, `| cut .. | sort`), ordered by content on the GPU: only line numbers, counts and, when asked for, the sorted text
+ * leave it (the rule is csrc/sort_plan.h).
+ * A LINE is the bytes between newlines without the newline; a tail that is not empty is a line, an empty tail is none (the tail rule
+ * of cjs_bzip2_cut).  Lines are numbered from 0.  The ORDER is bytewise as memcmp, a proper prefix before the longer line
+ * (LC_ALL=C sort); equal lines go by ascending line number.  CJS_SORT_REVERSE: descending content, equal lines still by ascending
+ * line number.  CJS_SORT_UNIQUE: one entry per run of equal lines, its lowest line number, the run's size as its count.  Both
+ * orders are total: the output is fully determined.
+ * lines_out gets the first min(cap, info->n_out) line numbers in that order, counts_out (may be NULL) their counts (without
+ * CJS_SORT_UNIQUE all ones); nothing past those is written.  info->n_lines = the lines, n_distinct = the runs of equal lines, n_out
+ * = what the flags select of them, rounds = the sort rounds run (at most (longest line + 8) / 7).  cap = 0 without text: the count
+ * query, which runs everything.
+ * TEXT is optional (text_out and text_n both NULL: none): the emitted lines, i.e. the first min(cap, n_out), each followed by
+ * "\n".  info->text_bytes is the size that text has for all n_out lines, whatever cap is.  Host forms: *text_out is allocated by
+ * the library (cjs_free), also for empty output.  Device forms: d_text_out of text_cap bytes; a text above text_cap returns
+ * CJS_E_OUTPUT_TOO_SMALL with *text_n = the need and writes no byte of d_text_out (d_text_out = NULL, text_cap = 0 with text_n
+ * given: the size query); lines_out and counts_out are complete then.
+ * cjs_text_sort: everything is host memory; n == 0 needs no device.  cjs_text_sort_device: d_text, d_lines_out, d_counts_out and
+ * d_text_out are memory of the GPU (host pointers: CJS_E_INVALID_ARG); d_text at any alignment, and no byte outside
+ * [d_text, d_text + n) is read; the two output arrays 8-byte aligned; info and text_n are host memory.  More than 2^32 - 2 bytes
+ * or lines: CJS_E_UNSUPPORTED.  CJS_E_INVALID_ARG: NULL text with n > 0, NULL lines_out with cap > 0, one of text_out / text_n
+ * without the other, NULL info, an unknown flag.
+ * How: newline counts per 4 KiB tile and a scan give every line's start; round r keys every line of an active group by its ROUND
+ * WORD at depth 7 r (bytes [7 r, 7 r + 7) big-endian, zero-padded, << 8 | min(7, max(0, len - 7 r)): padding sorts below 0x00),
+ * two stable runs of the radix sorter order the active lines by (group, word), head flags and a scan split the groups, and the
+ * host reads one scalar per round: the lines still active.  A group is done with one member or a word that has ended.  Two equal
+ * lines of L bytes cost L / 7 rounds.  No atomics.  What comes down beyond the entries and the text asked for is 48 bytes of
+ * scalars (56 with text) and 8 bytes PER ROUND: under 1 KiB for ten entries while the rounds stay below a hundred, about 46 KB
+ * where two equal lines of 40 KiB take 5,852 rounds.
+ * cjs_bzip2_sort / cjs_bzip2_sort_device: the window is lines [first, min(first + count, N + 1)) of the table as in cjs_bzip2_cut.
+ * mode CJS_SORT_LINES: whole lines (the cut with bytes 1-).  modes CJS_CUT_FIELDS / CJS_CUT_BYTES: the cut of each line is what
+ * is sorted and what the text holds (`bzcat | cut .. | sort`); the cut writes one line per input line, so the line numbers are
+ * those of whole lines, `sort -s -t D -k ..` over them.  Line numbers are absolute: window line k is first + k.  A composition:
+ * cjs_bzip2_cut_device into a pooled device buffer of the touched blocks' bytes + 1 (the host form uploads the stream first),
+ * then the primitive.  lines_out, counts_out, info and text_n are HOST memory in both forms; the device form takes the stream and
+ * gives the text in GPU memory.  The argument checks are those of cjs_bzip2_cut (out / out_n for lines_out / text) and of the
+ * primitive, before the device is touched.  A bad block in the window fails the call as it fails cjs_bzip2_cut: code, detail,
+ * info->n_bad_blocks / first_bad_block.  Touched blocks above 2^32 - 2 bytes or a window above 2^32 - 2 lines:
+ * CJS_E_UNSUPPORTED.  All device memory (the text, 90 bytes per line of the window, 8 bytes per 4 KiB of text, the sorter's
+ * histograms, the outputs) is sized from the tables and taken before the cut runs (failure: CJS_E_OUT_OF_MEMORY).  An empty
+ * window needs no device.  CJS_DEBUG: one "[cjs sort]" line per call (lines, rounds, H2D and D2H bytes beyond the cut).
+ * cjs_stage_text_sort and cjs_stage_bzip2_sort_limit EXIST FOR TESTS; no product path calls them.  The first is the same rounds
+ * on the host (csrc/sort_plan.h), without a device.  The second is the whole-line stream sort with the limits on the touched
+ * blocks' bytes and the window's lines as arguments (exactly one of in / d_in; no text). */
+typedef struct { uint64_t n_lines, n_out, n_distinct, text_bytes, rounds, blocks_decoded, n_bad_blocks, first_bad_block; } cjs_bz_sort_info;   /* 64 bytes */
+#define CJS_SORT_REVERSE 1u
+#define CJS_SORT_UNIQUE  2u
+#define CJS_SORT_LINES   2u   /* mode, beside CJS_CUT_FIELDS 0u and CJS_CUT_BYTES 1u, as CJS_TALLY_LINES */
+int cjs_text_sort(const uint8_t *text, size_t n, uint32_t flags, uint64_t *lines_out, uint64_t *counts_out, size_t cap,
+                  uint8_t **text_out, size_t *text_n, cjs_bz_sort_info *info, const cjs_opts *opts);
+int cjs_text_sort_device(const uint8_t *d_text, size_t n, uint32_t flags, uint64_t *d_lines_out, uint64_t *d_counts_out, size_t cap,
+                         uint8_t *d_text_out, size_t text_cap, size_t *text_n, cjs_bz_sort_info *info, const cjs_opts *opts);
+int cjs_bzip2_sort(const uint8_t *in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first, uint64_t count,
+                   uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel, uint32_t flags, uint64_t *lines_out,
+                   uint64_t *counts_out, size_t cap, uint8_t **text_out, size_t *text_n, cjs_bz_sort_info *info, const cjs_opts *opts);
+int cjs_bzip2_sort_device(const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines, uint64_t first,
+                          uint64_t count, uint32_t mode, uint32_t delim, const cjs_cut_range *sel, uint32_t nsel, uint32_t flags,
+                          uint64_t *lines_out, uint64_t *counts_out, size_t cap, uint8_t *d_text_out, size_t text_cap, size_t *text_n,
+                          cjs_bz_sort_info *info, const cjs_opts *opts);
+int cjs_stage_text_sort(const uint8_t *text, size_t n, uint32_t flags, uint64_t *lines_out, uint64_t *counts_out, size_t cap,
+                        cjs_bz_sort_info *info);
+int cjs_stage_bzip2_sort_limit(const uint8_t *in, const uint8_t *d_in, size_t n, const cjs_bz_index *idx, const cjs_bz_lines *lines,
+                               uint64_t first, uint64_t count, uint64_t max_bytes, uint64_t max_lines, uint32_t flags,
+                               uint64_t *lines_out, uint64_t *counts_out, size_t cap, cjs_bz_sort_info *info, const cjs_opts *opts);
 /* cjs_bzip2_compare: `cmp` over the address space of cjs_bzip2_read_ranges ([0, total_bytes) of the index), done on the GPU: is
  * the decoded stream equal to `other`, and if not, where and with which bytes?  The decoded bytes never leave the GPU, 16 bytes
  * per reported difference do.  other[k] is compared with decoded byte other_off + k.  The COMPARED SPAN is
