@@ -1,7 +1,7 @@
 // bz_index.h -- the block index of a .bz2 stream behind the C ABI's opaque cjs_bz_index (bz_index.hip: create / save / load / info;
 // range.hip: cjs_bzip2_index_build and the range reads that run over it).
 #pragma once
-#include "cjs_internal.h"
+#include "cjs_hip.h"
 #include <vector>
 
 struct cjs_bz_index {

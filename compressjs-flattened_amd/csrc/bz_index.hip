@@ -1,6 +1,7 @@
 // bz_index.hip -- cjs_bz_index: the host half of the indexed range reads (include/cjs_hip.h).  No device is touched here:
 // an index is made from a caller's entries or from its serialised form, checked entry by entry, and handed out again.
 // cjs_bzip2_index_build (one table pass on the GPU) and the range reads are in range.hip.
+#include "cjs_internal.h"
 #include "bz_index.h"
 #include <algorithm>
 #include <stdlib.h>

@@ -1,5 +1,5 @@
 // bz_lines.h -- the line table of an indexed .bz2 stream behind the C ABI's opaque cjs_bz_lines (lines.hip: create / save / load /
-// info, the build and the two questions that run over it).
+// info, the build and the two questions that run over it).  No HIP in here: line_join.h reads the table on the host.
 #pragma once
 #include "bz_index.h"
 #include <vector>
@@ -22,5 +22,7 @@ inline uint32_t bz_lines_fold(const cjs_bz_index* ix) {
 }
 // the table of `count` counts for index ix (CJS_E_INVALID_ARG and a detail text if they cannot be that index's)
 int bz_lines_make(const cjs_bz_index* ix, const uint32_t* counts, size_t count, cjs_bz_lines** lines);
+// whether t is the table of index ix (a detail text if it is not): what every entry point that takes both asks first
+bool lines_belong(const cjs_bz_index* ix, const cjs_bz_lines* t);
 
 }  // namespace cjs

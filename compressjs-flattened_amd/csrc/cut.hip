@@ -9,9 +9,10 @@
 //   ct_scan     the exclusive prefix sums of the counts and their total
 //   ct_emit     per tile again: every thread ranks its bytes by the workgroup's prefix sums, the tile's output is packed in LDS at
 //               the phase of its destination and stored with 16-byte vectors where a whole one is inside, bytes at the two ends
-// The arithmetic (selection, summary, monoid, emit rule) is cut_plan.h, without HIP.  Tile geometry is that of lines.hip and
-// linekeys.hip: a tile never spans two blocks; a thread takes a contiguous share of its tile's 16-byte vectors (4 or 5 of them)
-// and walks it byte by byte; the shares are joined by a scan of their summaries.  No atomics decide an order.
+// The arithmetic (selection, summary, monoid, emit rule) is cut_plan.h, without HIP; tally_stream.hip and sort_stream.hip take the cut
+// as device text (linekeys.h).  Tile geometry is that of lines.hip and linekeys.hip: a tile never spans two blocks; a thread takes a
+// contiguous share of its tile's 16-byte vectors (4 or 5) and walks it byte by byte; the shares are joined by a scan of their summaries.
+// No atomics decide an order.
 #include "range_engine.h"
 #include "bz_lines.h"
 #include "cut_plan.h"
@@ -188,12 +189,6 @@ __global__ __launch_bounds__(256) void ct_emit(const CtBlk* __restrict__ blks, u
 // ---------------------------------------------------------------- the driver
 namespace {
 
-bool cut_lines_belong(const cjs_bz_index* ix, const cjs_bz_lines* t) {
-  if (t->nl.size() == ix->e.size() && t->total_bytes == ix->off.back() && t->crc_fold == bz_lines_fold(ix)) return true;
-  set_detail("the line table is of another index");
-  return false;
-}
-
 struct CutCall {
   const cjs_bz_index* ix = nullptr;
   const cjs_bz_lines* t = nullptr;
@@ -293,20 +288,13 @@ int cut_core(const uint8_t* in, const uint8_t* d_in, size_t n, const cjs_bz_inde
   CtSel S;
   CJS_TRY(ct_normalise(mode, delim, sel, nsel, &S));
   CJS_TRY(check_index_stream(host ? in : d_in, n, idx));
-  if (!cut_lines_belong(idx, t)) return CJS_E_INVALID_ARG;
+  if (!lines_belong(idx, t)) return CJS_E_INVALID_ARG;
   info->n_lines = info->out_bytes = info->n_bad_blocks = info->blocks_decoded = 0; info->first_bad_block = ~0ull;
-  const uint64_t N = t->cum.back();
-  const uint64_t end = first + count < first ? N + 1 : std::min(first + count, N + 1);      // (the add saturates)
+  const uint64_t end = line_window_end(first, count, t->cum.back());
   CutCall C;
   C.ix = idx; C.t = t; C.host = host; C.mode = S.mode; C.delim = S.delim; C.W = CtWin{first, end}; C.d_out = d_out; C.cap = out_cap;
-  // from the block of newline number `first` through the block of newline number `end`, the line table's routing of a line's start
-  std::vector<uint32_t> touched;
+  const std::vector<uint32_t> touched = line_window_blocks(t->cum, t->total_bytes, idx->off, first, end);
   if (first < end) info->n_lines = end - first;
-  if (first < end && !idx->e.empty()) {
-    const LineRoute r0 = route_locate(t->cum, t->total_bytes, first), r1 = route_locate(t->cum, t->total_bytes, end);
-    const size_t b0 = first ? r0.block : 0, b1 = end <= N ? r1.block : idx->e.size() - 1;
-    for (size_t b = b0; b <= b1; b++) if (idx->e[b].size) touched.push_back((uint32_t)b);
-  }
   C.touched = &touched;
   RangeStats st;
   RangeVerdicts V(idx);

@@ -119,6 +119,12 @@ int bz_lines_make(const cjs_bz_index* ix, const uint32_t* counts, size_t count, 
   return 0;
 }
 
+bool lines_belong(const cjs_bz_index* ix, const cjs_bz_lines* t) {
+  if (t->nl.size() == ix->e.size() && t->total_bytes == ix->off.back() && t->crc_fold == bz_lines_fold(ix)) return true;
+  set_detail("the line table is of another index");
+  return false;
+}
+
 }  // namespace cjs
 
 // ---------------------------------------------------------------- the driver
@@ -131,12 +137,6 @@ enum { LN_BUILD = 0, LN_LOCATE = 1, LN_NUMBER = 2 };
 
 void put_le(uint8_t* p, uint64_t v, int bytes) { for (int i = 0; i < bytes; i++) p[i] = (uint8_t)(v >> (8 * i)); }
 uint64_t get_le(const uint8_t* p, int bytes) { uint64_t v = 0; for (int i = 0; i < bytes; i++) v |= (uint64_t)p[i] << (8 * i); return v; }
-
-bool lines_belong(const cjs_bz_index* ix, const cjs_bz_lines* t) {
-  if (t->nl.size() == ix->e.size() && t->total_bytes == ix->off.back() && t->crc_fold == bz_lines_fold(ix)) return true;
-  set_detail("the line table is of another index");
-  return false;
-}
 
 struct LnWant { uint32_t block, arg; size_t k; };          // question k wants `arg` of index block `block`
 

@@ -7,13 +7,14 @@
 //   lines.hip     the newline count per block, select and rank for the line table's questions
 //                 (its newline test, ln_nl4, stands here: the compressor's block rows, enc_index.hip, count with it too)
 //   compare.hip   count, scan and emit over the tiles of the batch's runs intersected with the other side's
-//   linekeys.hip  a key per line: count and hash per tile, a chain per block, a record per newline at its rank (line_key.h)
+//   linekeys.hip  a key per line: count and hash per tile, a chain per block, a record per newline at its rank (line_key.h, line_join.h;
+//                 tally_stream.hip runs it with the records kept on the device)
 //   cut.hip       fields or byte columns of the lines: a summary per tile, one chain over the batch from the state the batch in
 //                 front left, count, scan, and a byte-granular compaction through LDS (cut_plan.h)
 // What they share stands here: the device helpers of a tile (its segment, its span of bounded aligned vectors, the 16-byte funnel,
 // the byte tests over 16 bytes, the scan of the tile counts) and, on the host, the verdicts of a call, the check of a stream
 // against its index and the count-then-emit round of the search and the compare.  Their host arithmetic (windows, runs,
-// segments, the search's carry, the routing of a line question) is scan_plan.h, which includes no HIP.
+// segments, the search's carry, the routing of a line question, a window of lines) is scan_plan.h, which includes no HIP.
 #pragma once
 #include "dec_engine.h"
 #include "bz_index.h"

@@ -1,7 +1,7 @@
 // scan_plan.h -- host arithmetic of the consumers of the pass engine (range_engine.h): the window of a call and the blocks under
 // it, the good blocks of a decoded batch as runs, two sides' runs as tiled segments (compare.hip), a batch's segments with the carry
-// between batches (search.hip) and where a line question is answered (lines.hip; linekeys.hip and cut.hip route the two ends of
-// their window of lines by it; the cut's own arithmetic is cut_plan.h).  Plain integers and vectors: offsets, sizes,
+// between batches (search.hip), where a line question is answered (lines.hip) and a window of lines with its touched blocks (cut.hip,
+// linekeys.hip, tally_stream.hip, sort_stream.hip; the cut's own arithmetic is cut_plan.h).  Plain integers and vectors: offsets, sizes,
 // verdict bytes, device addresses as uint64_t.  No HIP in here (tests/host/scan_plan_check.cc compiles it with the host compiler).
 #pragma once
 #include <stddef.h>
@@ -128,6 +128,17 @@ inline LineRoute route_number(const std::vector<uint64_t>& cum, const std::vecto
   if (q == off[b]) { r.value = cum[b]; return r; }
   r.block = (uint32_t)b; r.arg = (uint32_t)(q - off[b]);
   return r;
+}
+// A window of lines [first, first + count) over N newlines (lines 0 .. N, the last the tail): its end (the add saturates) ...
+inline uint64_t line_window_end(uint64_t first, uint64_t count, uint64_t N) { return first + count < first ? N + 1 : std::min(first + count, N + 1); }
+// ... and the touched blocks of [first, end), end <= N + 1: the blocks of non-zero size from the block of newline number `first`
+// through the block of newline number `end`, route_locate's answer for a line's start.  off: the blocks' sizes, as their offsets.
+inline std::vector<uint32_t> line_window_blocks(const std::vector<uint64_t>& cum, uint64_t total_bytes, const std::vector<uint64_t>& off, uint64_t first, uint64_t end) {
+  std::vector<uint32_t> touched;
+  if (first >= end || cum.size() < 2) return touched;      // (an empty window; an empty index)
+  const size_t b0 = first ? route_locate(cum, total_bytes, first).block : 0, b1 = end <= cum.back() ? route_locate(cum, total_bytes, end).block : cum.size() - 2;
+  for (size_t b = b0; b <= b1; b++) if (off[b + 1] > off[b]) touched.push_back((uint32_t)b);
+  return touched;
 }
 
 }  // namespace cjs

@@ -1,5 +1,5 @@
 // sort.h -- what the line sort (sort.hip) offers the stream consumer that feeds it a cut in device memory
-// (cjs_bzip2_sort, linekeys.hip): its two workspaces, sized from the text's bytes and from the number of lines, and the two steps.
+// (cjs_bzip2_sort, sort_stream.hip): its two workspaces, sized from the text's bytes and from the number of lines, and the two steps.
 #pragma once
 #include <functional>
 #include "cjs_internal.h"

@@ -1,5 +1,5 @@
 // tally.h -- what the key tally (tally.hip) offers the stream consumer that feeds it keys in device memory
-// (cjs_bzip2_tally, linekeys.hip): its workspace, sized from the number of keys alone, and the run into a host array.
+// (cjs_bzip2_tally, tally_stream.hip): its workspace, sized from the number of keys alone, and the run into a host array.
 #pragma once
 #include "cjs_internal.h"
 #include "tally_plan.h"

@@ -1,8 +1,8 @@
 // scan_plan_check.cc — the host arithmetic of csrc/scan_plan.h (windows and the blocks under them, the good blocks of a batch as
-// runs, two sides' runs as tiled segments, the search's segments and carry, the routing of a line question) checked by property on
-// random cases against brute-force models, not by restating its formulas.  Stand-alone: built with the host compiler under the
-// address / undefined-behaviour sanitizers and run by tests/test_scan_plan_host.py.  Exit 0 = all checks passed; a failing check
-// prints itself and the program exits 1.
+// runs, two sides' runs as tiled segments, the search's segments and carry, the routing of a line question, a window of lines and its
+// touched blocks) checked by property on random cases against brute-force models, not by restating its formulas.  Stand-alone:
+// built with the host compiler under the address / undefined-behaviour sanitizers and run by tests/test_scan_plan_host.py.  Exit 0 =
+// all checks passed; a failing check prints itself and the program exits 1.
 #include "scan_plan.h"
 #include "cjs_hip.h"
 #include <stdio.h>
@@ -227,12 +227,73 @@ static void line_cases() {
   }
 }
 
+// The window of lines and its touched blocks, against a walk over the text itself: line q starts behind newline q, the blocks that
+// hold a byte of the window's lines are touched, and so is every block from the start of a line to its end.
+static void line_window_cases() {
+  const uint64_t M = ~0ull;
+  CHECK(line_window_end(0, M, 7) == 8 && line_window_end(3, M - 2, 7) == 8 && line_window_end(M, M, 7) == 8 && line_window_end(5, 0, 7) == 5, "the add saturates");
+  CHECK(line_window_end(2, 3, 7) == 5 && line_window_end(2, 6, 7) == 8 && line_window_end(2, 7, 7) == 8 && line_window_end(9, 1, 7) == 8 && line_window_end(0, 0, 0) == 0, "clamp to N + 1");
+  const std::vector<uint64_t> none_cum(1, 0), none_off(1, 0);
+  CHECK(line_window_blocks(none_cum, 0, none_off, 0, 1).empty(), "an empty index has no block to touch");
+  for (int it = 0; it < 4000; it++) {
+    // blocks with empty ones at either end now and then; a text over them with a newline about every fifth byte
+    std::vector<uint64_t> off = random_offsets(1 + rnd() % 9);
+    if (it % 3 == 0) off.insert(off.begin(), 1 + rnd() % 2, 0);
+    if (it % 3 == 1) off.insert(off.end(), 1 + rnd() % 2, off.back());
+    const size_t nb = off.size() - 1;
+    const uint64_t total = off.back();
+    std::vector<uint8_t> is_nl(total);
+    for (auto& x : is_nl) x = rnd() % 5 == 0;
+    if (it % 7 == 0) std::fill(is_nl.begin(), is_nl.end(), 0);
+    std::vector<uint64_t> cum(1, 0), start(1, 0);                     // start[q]: the offset line q starts at
+    for (size_t b = 0; b < nb; b++) {
+      uint64_t c = 0;
+      for (uint64_t o = off[b]; o < off[b + 1]; o++) if (is_nl[o]) { c++; start.push_back(o + 1); }
+      cum.push_back(cum.back() + c);
+    }
+    const uint64_t N = cum.back();
+    start.push_back(total);                                           // (where the line behind the tail would start)
+    for (int w = 0; w < 6; w++) {
+      const uint64_t first = w == 0 ? 0 : w == 1 ? N + 1 + rnd() % 3 : rnd() % (N + 2);
+      const uint64_t count = w == 2 ? 0 : w == 3 ? M : rnd() % (N + 3), end = line_window_end(first, count, N);
+      CHECK(end <= N + 1 && (first + count < first || end == std::min(first + count, N + 1)), "line_window_end(%llu, %llu, %llu) = %llu", (ull)first, (ull)count, (ull)N, (ull)end);
+      const std::vector<uint32_t> got = line_window_blocks(cum, total, off, first, end);
+      // per line of the window: the block its start lies in (an empty line at the very end starts in the last block with bytes),
+      // and every block up to the one its last byte lies in
+      std::vector<uint8_t> want(nb, 0);
+      for (uint64_t q = first; q < end; q++) {
+        const uint64_t lo = start[q], hi = start[q + 1];              // the line's bytes [lo, hi)
+        if (!total) break;
+        const size_t b0 = block_by_walk(off, std::min(lo, total - 1)), b1 = block_by_walk(off, hi > lo ? hi - 1 : std::min(lo, total - 1));
+        for (size_t b = b0; b <= b1; b++) if (off[b + 1] > off[b]) want[b] = 1;
+      }
+      std::vector<uint32_t> want_list;
+      for (size_t b = 0; b < nb; b++) if (want[b]) want_list.push_back((uint32_t)b);
+      // the routing reads a line's start from the block of the newline in front of it: that block may come in front of the brute
+      // force's first, never behind it, and nothing else differs
+      std::vector<uint32_t> extra;
+      for (uint32_t b : got) if (!want[b]) extra.push_back(b);
+      for (uint32_t b : want_list) CHECK(std::find(got.begin(), got.end(), b) != got.end(), "lines [%llu, %llu): block %u holds a byte of the window and is not touched", (ull)first, (ull)end, b);
+      CHECK(std::is_sorted(got.begin(), got.end()) && std::adjacent_find(got.begin(), got.end()) == got.end(), "touched blocks ascend without repeats");
+      for (uint32_t b : got) CHECK(off[b + 1] > off[b], "block %u of size zero is touched", b);
+      CHECK(extra.size() <= 1, "lines [%llu, %llu): %zu blocks touched beyond those that hold the window", (ull)first, (ull)end, extra.size());
+      if (extra.size() == 1) {
+        // the one block more: the newline in front of the window's first line is the last byte of a block and the line starts in the next
+        CHECK(first > 0 && first <= N && extra[0] == block_by_walk(off, start[first] - 1) && (want_list.empty() || extra[0] < want_list[0]),
+              "lines [%llu, %llu): block %u is touched and neither holds a byte of the window nor the newline in front of it", (ull)first, (ull)end, extra[0]);
+      }
+      if (first >= end) CHECK(got.empty(), "an empty window touches %zu blocks", got.size());
+    }
+  }
+}
+
 int main() {
   window_cases();
   good_run_cases();
   intersect_cases();
   search_cases(CJS_SEARCH_MAX_PATTERN_BYTES);
   line_cases();
+  line_window_cases();
   if (g_fail) { printf("scan_plan_check: %d checks failed\n", g_fail); return 1; }
   printf("scan_plan_check ok\n");
   return 0;

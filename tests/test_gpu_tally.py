@@ -352,6 +352,53 @@ def test_a_damaged_block_counts_its_lines_and_serves_the_rest(L, fx):
     assert info.n_bad_lines == 0 and info.n_bad_blocks == 0
 
 
+def _three_crafted_blocks():
+    """three blocks of a few hundred bytes (bzcraft: random ranks over newline and eight letters) -> (stream, the blocks' texts);
+    a line runs from block 0 into block 1 and another from block 1 into block 2, and blocks 1 and 2 hold newlines"""
+    import bzcraft
+    import bzcraft_cases as bc
+    used = (10,) + tuple(range(97, 105))
+    for seed in range(64):
+        rng = np.random.RandomState(7000 + seed)
+        blocks = [bc.plain(used, bc.ranks(rng, len(used), 300)) for _ in range(3)]
+        texts = [bzcraft.model(bzcraft.stream([b])) for b in blocks]
+        if all(isinstance(x, bytes) and 200 <= len(x) <= 1000 for x in texts) and not texts[0].endswith(b"\n") and not texts[1].endswith(b"\n") \
+                and b"\n" in texts[1] and b"\n" in texts[2]:
+            return bzcraft.stream(blocks), texts
+    raise AssertionError("no seed gives the three blocks")
+
+
+def test_the_fills_and_the_patches_of_one_join_go_up_together(L):
+    """the middle one of three small blocks is bad: its lines are filled with all-ones, the line that ends in block 2 is patched
+    with all-ones, line 0 and the tail are patched with their keys -- against cjs_stage_keys_tally over the keys of the lines"""
+    stream, texts = _three_crafted_blocks()
+    plain = b"".join(texts)
+    rc, h = rg.build(L, stream, 0)
+    assert rc == 0, rg.detail(L)
+    e = rg.entries(L, h)
+    assert [x[2] for x in e] == [len(x) for x in texts]
+    t = lc.build_both(L, stream, h, lc.on_device(stream))
+    cum = np.concatenate([[0], np.cumsum([x.count(b"\n") for x in texts])])
+    damaged = stream.copy()
+    bit = e[1][0] + 48 + 32 + 1 + 23          # the lowest bit of the block's BWT start
+    damaged[bit >> 3] ^= 1 << (7 - (bit & 7))
+    g = dict(stream=damaged, dev=lc.on_device(damaged), h=h, t=t)
+    seed = SEEDS[1]
+    # the tally's lines: every newline's, and the tail's as if it ended in one (an empty tail is no line)
+    rc, keys, n = lk.stage_keys(L, plain if plain.endswith(b"\n") else plain + b"\n", seed)
+    assert rc == 0 and n == keys.size == int(cum[3]) + 1 + (not plain.endswith(b"\n"))
+    keys = keys[:-1]
+    bad = range(int(cum[1]), int(cum[2]) + 1)          # the lines the table gives block 1, and the one that goes on behind it
+    for k in bad:
+        keys[k] = tc.ONES
+    for order in (tc.BY_COUNT, tc.BY_FIRST):
+        groups, info = tc.both_forms(L, g, seed=seed, order=order)
+        rc, ref, rinfo = tc.stage_tally(L, keys, order)
+        assert rc == 0 and rinfo.n_bad == len(bad) >= 2
+        assert tc.stream_info_tuple(info) == tc.info_tuple(rinfo) + (3, 1, 1)
+        assert groups.tobytes() == ref.tobytes()
+
+
 def test_a_window_above_the_line_limit_is_refused(L, fx):
     """the limit is 2^32 - 2 lines and no table of that many fits a test: cjs_stage_bzip2_tally_limit takes it as an argument"""
     f = fx["TL1"]
