@@ -99,6 +99,7 @@ static Plan plan_round1(const BwtWork& w, const G& g, bool cyclic, const uint8_t
 
 // whole-array fallback of a round >= 2: radix passes over the 64-bit keys in key[c], then the flag bytes from the sorted keys
 static int sort_round_whole(hipStream_t s, BwtWork& w, Round& r, LaunchTimes* lt) {
+  // (whole digits are sorted: the rest of the last one is zero, bwt_gather_keys' round_key(ord, rank) has ord < ngroups on top)
   CJS_TRY((radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt)));
   launch_key_flags(s, w.key[r.c], r.A, w.hflag);
   CJS_HIP_TRY(hipGetLastError());

@@ -85,6 +85,7 @@ int sort_deferred(hipStream_t s, BwtWork& w, const Round& r, uint32_t D, uint32_
   uint32_t* dpos = w.pos[1 - r.pc];
   hipLaunchKernelGGL(bwt_defer_gather, dim3((r.A + TS_GT - 1) / TS_GT), dim3(256), 0, s, w.key[c], w.val[c], r.A, w.dflag, tcount, hcount, dk0, dv0, dpos);
   int cur = 0;
+  // (whole digits are sorted: the rest of the last one is zero, bwt_defer_gather's round_key(hid - 1, rank) has nothing above the ordinal)
   CJS_TRY((radix_passes<uint64_t>(s, w.rs, dk0, dv0, dk1, dv1, cur, D, 0, round_key_bits(ndg), lt)));      // dense ordinals 0 .. ndg-1 above the 20-bit rank key
   hipLaunchKernelGGL(bwt_defer_scatter, dim3((D + 255) / 256 < 8192u ? (D + 255) / 256 : 8192u), dim3(256), 0, s, D, cur ? dk1 : dk0, cur ? dv1 : dv0, dpos,
                      w.hflag, w.val[c]);

@@ -135,8 +135,10 @@ int sort_round1(hipStream_t s, BwtWork& w, const G& g, const Plan& p, Round& r, 
   if (!p.segmented) {
     const int grid_lin = (int)((r.A + 255) / 256 < 65535u * 16u ? (r.A + 255) / 256 : 65535u * 16u);
     hipLaunchKernelGGL(bwt_init_keys<G>, dim3(grid_lin), dim3(256), 0, s, p.gen.T, g, p.gen.cyclic, p.nsym, r.A, w.key[0], w.val[0]);
+    // (whole digits are sorted: the rest of the last one is zero, bwt_init_keys puts nothing above the block id, r.bits = p.bits wide)
     return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt);
   }
+  // (r.bits = 63: the last digit takes in bit 63, the segment's parity in gen_key -- equal in all keys of a segment, so it moves nothing)
   if (!p.packed) return radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], r.c, r.A, 0, r.bits, lt, &p.sg, &p.gen);
   // phase 1: its narrow records go through val[], which the packed round 1 does not use before the regroup writes the next
   // round's values (behind the rebuild that consumes them).  The 8-byte records of the first passes in key[] are dead by then:

@@ -175,9 +175,12 @@ struct LaunchTimes {   // event pairs around the dominant kernel; resolved after
 };
 
 struct SegGeom; struct GenSrc;      // radix.hpp
-// LSD radix passes over bits [lo_bit, hi_bit) of n keys (with their values unless noval) between k0 / v0 and k1 / v1; cur says
-// which pair holds the keys, before and after.  seg: sorted as segments (else one); gen: the first pass makes its keys from the
-// block bytes.  Instantiated for K = uint64_t and uint32_t.
+// LSD radix passes over n keys (with their values unless noval) between k0 / v0 and k1 / v1, one per 8-bit digit from lo_bit up
+// while the digit starts below hi_bit: the word sorted on is bits [lo_bit, lo_bit + 8 * ceil((hi_bit - lo_bit) / 8)), clipped at
+// the key width -- WHOLE digits.  A caller whose hi_bit - lo_bit is no multiple of 8 gets the sort on [lo_bit, hi_bit) only if the
+// rest of the last digit is equal in all keys of a segment (every such caller says why at its call; tests/test_gpu_radix.py
+// holds the rule).  n > 0.  cur says which pair holds the keys, before and after.  seg: sorted as segments (else one); gen: the
+// first pass makes its keys from the block bytes.  Instantiated for K = uint64_t and uint32_t.
 template <typename K>
 int radix_passes(hipStream_t s, RadixWork& w, K* k0, uint32_t* v0, K* k1, uint32_t* v1, int& cur, uint32_t n, int lo_bit, int hi_bit,
                  LaunchTimes* lt = nullptr, const SegGeom* seg = nullptr, const GenSrc* gen = nullptr, bool noval = false,

@@ -325,6 +325,7 @@ static int sort_and_pack(hipStream_t s, IbScratch& q, const IbPlan& P, uint32_t*
   if (P.strided) hipLaunchKernelGGL(ib_make_keys_hist, dim3(P.tps, P.nb), dim3(256), 0, s, q.d_blocks, q.key0, P.seg_stride, P.tps, q.sw.hist);
   else hipLaunchKernelGGL(ib_make_keys, dim3(64, P.nb), dim3(256), 0, s, q.d_blocks, q.key0, q.val0, 0u);
   int cur = 0;
+  // (whole digits are sorted: the rest of the last one is zero, ib_make_keys' (block << 8) | byte has block < nb on top)
   if (P.strided) CJS_TRY(radix_pass_segments(s, q.sw, q.key0, q.val0, q.key1, q.val1, cur, P.nb, P.seg_stride, 0, 8, true, true));
   else CJS_TRY(radix_passes<uint32_t>(s, q.sw, q.key0, q.val0, q.key1, q.val1, cur, P.M, 0, 8 + bits_for(P.nb - 1)));
   const uint32_t* sval = P.strided ? (cur ? q.key1 : q.key0) : (cur ? q.val1 : q.val0);
@@ -432,6 +433,7 @@ static int ibwt_sentinel_slab(hipStream_t s, const uint8_t* d_T, uint32_t max_le
   if (hipMemcpyAsync(d_blocks, chain.data(), sizeof(IbBlock) * nb, hipMemcpyHostToDevice, s) != hipSuccess) return CJS_E_HIP;
   hipLaunchKernelGGL(ib_make_keys, dim3(64, nb), dim3(256), 0, s, d_blocks.p, d_key0.p, d_val0.p, 0u);
   int cur = 0;
+  // (whole digits are sorted: the rest of the last one is zero, ib_make_keys' (block << 8) | byte has block < nb on top)
   CJS_TRY(radix_passes<uint32_t>(s, sw, d_key0, d_val0, d_key1, d_val1, cur, M, 0, 8 + bits_for(nb - 1)));
   uint32_t* sval = cur ? d_val1 : d_val0;
   uint32_t* d_dbuf = cur ? d_key0 : d_key1;

@@ -1,9 +1,11 @@
 // radix.hip — segmented LSD radix sorter for gfx950 (8-bit digits, LDS-staged buckets, wave64 match-any ranking).
 //
-// Sorts n keys of type K (uint64_t / uint32_t), with or without a 32-bit value each, on bits [lo_bit, hi_bit) between two
-// buffers.  Used by the suffix sort (bwt.hip: round 1, the groups too large for the tile sorters, the whole-array fallbacks) and
-// by the inverse BWT (dec_ibwt.hip: stable partition of the BWT bytes).  Integer sort/scan only (no MFMA); HBM-bound on the
-// scatter passes.
+// Sorts n keys of type K (uint64_t / uint32_t), with or without a 32-bit value each, between two buffers, on the whole 8-bit
+// digits from lo_bit up that start below hi_bit: bits [lo_bit, lo_bit + 8 * ceil((hi_bit - lo_bit) / 8)), clipped at the key
+// width, not [lo_bit, hi_bit) (see radix_passes in cjs_internal.h).  Used by the suffix sort (bwt.hip: round 1, the groups too
+// large for the tile sorters, the whole-array fallbacks), by the inverse BWT (dec_ibwt.hip: stable partition of the BWT bytes),
+// by the tally (tally.hip) and by the line sort (sort.hip); stage_radix.hip runs it on its own for the tests.  Integer sort/scan
+// only (no MFMA); HBM-bound on the scatter passes.
 // radix_passes_pk1 is the phase-1 sort of the packed cyclic round 1, five passes on records that shrink as their digits are
 // used up: 8 bytes for two passes, then 4 (rs_scatter with a narrower output type, then with its digit from a byte array).
 #include "radix.hpp"

@@ -346,7 +346,7 @@ int sort_run(hipStream_t s, SortWork& w, const SortCount& c, const SortCall& q, 
     int rc = radix_passes<uint64_t>(s, w.rs, w.key[0], w.val[0], w.key[1], w.val[1], cur, na, 0, 64);
     const uint32_t* perm = w.val[cur];
     if (!rc && agrp) {
-      // the groups' ordinals are below na / 2 + 1 (an active group has two members at least)
+      // the groups' ordinals are below na / 2 + 1 (an active group has two members at least); whole digits, as the passes sort them
       const int bits = (bits_for(na / 2) + 7) & ~7;
       int c2 = 0;
       hipLaunchKernelGGL(sl_gkeys, dim3(per), dim3(256), 0, s, agrp, perm, na, w.gk[0]);

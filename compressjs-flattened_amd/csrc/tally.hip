@@ -213,6 +213,7 @@ int tally_stages(hipStream_t s, TallyWork& w, const cjs_bz_linekey* d_keys, uint
   hipLaunchKernelGGL(tl_compact, dim3(gt), dim3(256), 0, s, (const uint32_t*)gpos, perm, nd, n_good, min_count, max_count, order, (const uint64_t*)w.tcnt,
                      w.cfirst, w.ccount, ok[0], ovv[0]);
   int oc = 0;
+  // (tl_order_bits is a whole number of digits: the bits above it, ~count's ones, are never sorted on)
   CJS_TRY(radix_passes<uint64_t>(s, w.rs, ok[0], ovv[0], ok[1], ovv[1], oc, (uint32_t)ng, 0, tl_order_bits(order, info->max_count)));
   const uint32_t* sorted = ovv[oc];
   rc = sink(m, [&](cjs_bz_tally* d_out) {

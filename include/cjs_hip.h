@@ -942,6 +942,40 @@ int cjs_stage_huff_blocks(const uint16_t *A, size_t a_stride, uint32_t nb, const
                           uint32_t *ngroups, uint8_t *selectors, uint8_t *lengths, uint8_t *bits, size_t bits_stride,
                           uint64_t *nbits, const cjs_opts *opts);
 
+/* cjs_stage_radix EXISTS FOR TESTS; no product path calls it: the radix sorter (csrc/radix.hip: radix_passes, radix_pass_segments)
+ * with the template arguments, bit range, geometry and workspace of the caller's choice, host buffers in and out.
+ * The sort: stable, by 8-bit digits from lo_bit upwards while the digit's low bit lies below hi_bit, so the word sorted on is
+ * (key >> lo_bit) & (2^(8*P) - 1), P = ceil((hi_bit - lo_bit) / 8), clipped at the key width: whole digits, not [lo_bit, hi_bit).
+ * keys: n keys of key_bytes (4 or 8) each.  vals: n 32-bit values that move with them, or NULL (key-only passes).
+ * Geometry: nseg segments of stride keys, the last one n_last (1 <= n_last <= stride, n == (nseg-1)*stride + n_last), each sorted
+ * on its own in the same launches; nseg == 1 (then stride == n_last == n) is the plain sort, run without a geometry.
+ * work_cap >= n: the sorter's workspace is carved for work_cap keys (RadixWork::hist_tiles_for / segs_for), as the product's
+ * workspaces are, so radix_passes refuses geometries with more tiles or segments than that, with CJS_E_INVALID_ARG.
+ * flags: CJS_RADIX_DIG hands the passes a byte-per-key array (a pass leaves the next digit of every key there and the next pass
+ * counts from it); CJS_RADIX_SEGMENTS goes through radix_pass_segments (4-byte keys, n_last == stride, no DIG);
+ * CJS_RADIX_FIRST_HIST: first_hist[nseg * tps * 256], tps = ceil(stride / 4096), holds the counts of the first digit per tile
+ * (row (seg * tps + tile) * 256 + digit), is copied into the workspace and the first pass counts nothing itself;
+ * CJS_RADIX_GEN: text[0 .. n) holds the segments' bytes and no keys or vals are read: the first pass makes the sentinel keys of
+ * round 1 of the suffix sort from them (seven 9-bit symbols byte + 1, 0 past the segment's end, first symbol on top, the segment's
+ * parity in bit 63; value = position in the segment); key_bytes 8, lo_bit 0, hi_bit 63 and no other flag; the text is followed
+ * by 16 bytes of slack on the device, as the compressors carve it.
+ * work_fill: before the run this byte fills the whole workspace (tile counts, chunk sums, digit totals), the byte-per-key array,
+ * both buffer pairs (the input is copied in behind the fill) and 1 KiB of guard behind each key, value and byte array.
+ * Out: keys_out / vals_out (vals_out unless key-only) = the buffer pair the sort ended in, *cur_out = which one (0: the one the input
+ * was put into), *guard_bad = the guard bytes that no longer hold work_fill, counted on the host.  A call that radix_passes refuses
+ * still sets *guard_bad and leaves keys_out, vals_out and *cur_out alone; its code is returned unchanged.
+ * n == 0: 0, nothing is launched (every caller of the sorter guards n > 0: the kernels read key n_last - 1 of a short tile).
+ * CJS_E_INVALID_ARG, before anything is launched: key_bytes not 4 or 8, lo_bit < 0, lo_bit >= hi_bit, hi_bit above the key width,
+ * a geometry that breaks the rules above, work_cap < n or above 2^26, unknown flag bits or a combination ruled out above, a NULL
+ * array that the flags call for, NULL keys_out, cur_out or guard_bad, NULL vals_out where values move. */
+#define CJS_RADIX_DIG 1u
+#define CJS_RADIX_SEGMENTS 2u
+#define CJS_RADIX_FIRST_HIST 4u
+#define CJS_RADIX_GEN 8u
+int cjs_stage_radix(const void *keys, int key_bytes, const uint32_t *vals, const uint8_t *text, const uint32_t *first_hist, uint32_t n,
+                    int lo_bit, int hi_bit, uint32_t nseg, uint32_t stride, uint32_t n_last, size_t work_cap, uint32_t flags,
+                    int work_fill, void *keys_out, uint32_t *vals_out, int *cur_out, uint64_t *guard_bad, const cjs_opts *opts);
+
 /* Serial entropy stage of BWTC.decompressFile (J/BWTC_joined_.js:1827-1913): range decoder + adaptive model + RLE2 + MTF
  * inverse, i.e. everything before BWT.unbwtransform.  Host logic only (the one entry point that needs no device; the chain
  * is serial by the format).  *cols receives the BWT columns of all non-empty blocks back to back (malloc'd, cjs_free);

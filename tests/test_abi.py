@@ -124,6 +124,28 @@ def test_stage_rle1_cap_and_batch_need_a_device():
         assert res[0] == -30 and all(x is None for x in res[1:])
 
 
+def test_stage_radix_needs_a_device():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import radix_cases as rc
+    L = rc.bind()
+    assert hasattr(L, "cjs_stage_radix")
+    keys = np.arange(300, dtype=np.uint64)
+    calls = (dict(geom=rc.plain(300), lo=0, hi=16), dict(geom=rc.plain(300), lo=16, hi=8),          # a fine call, a reversed bit range,
+             dict(geom=rc.Geom(4, 100, 0), lo=0, hi=8), dict(geom=rc.Geom(3, 100, 100), lo=0, hi=8, flags=rc.DIG | 64),   # bad shapes, an unknown flag,
+             dict(geom=rc.Geom(3, 100, 100), lo=0, hi=8, work_cap=5))                                # a workspace too small
+    for kw in calls:
+        res = rc.run(L, keys, np.arange(300, dtype=np.uint32), **kw)
+        assert res.rc == rc.E_NO_DEVICE and rc.untouched(res)          # CJS_E_NO_DEVICE before any argument is looked at
+    res = rc.run(L, None, None, rc.plain(300), 0, 63, key_bytes=8, flags=rc.GEN, text=np.zeros(300, np.uint8))
+    assert res.rc == rc.E_NO_DEVICE and rc.untouched(res)
+    res = rc.run(L, np.zeros(0, np.uint32), None, rc.Geom(1, 0, 0), 0, 8)          # n == 0 as well: the device comes first
+    assert res.rc == rc.E_NO_DEVICE and rc.untouched(res)
+
+
 def test_free_and_trim_need_no_device():
     # cjs_free takes what the library handed out (plain malloc or a pinned result buffer) and, like free(), a null pointer;
     # memory it does not know is plain malloc'd memory.  cjs_trim with nothing cached is a no-op.  Neither needs a GPU.
