@@ -4,6 +4,8 @@
 // Mirrors the block loop of Bzip2.compressFile (J/Bzip2_joined_.js:2199-2249) for all blocks at once.
 // The host-buffer driver on top of it: enc_host.hip; the stage-level test entry points: stages.hip.
 #include "ctx.h"
+#include "enc_pieces.h"
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <memory>
@@ -96,6 +98,13 @@ struct CallTimes {
     st->blocks = cnt; st->bytes_in = n; st->bytes_out = (bits + 7) / 8;
   }
 };
+
+// bytes of blocks from which blocks_through_tables goes in pieces (read at every call: tests shrink it)
+uint64_t enc_piece_bytes() {
+  const char* v = getenv("CJS_ENC_PIECE_BYTES");
+  const unsigned long long x = v ? strtoull(v, nullptr, 10) : 0;
+  return x ? (uint64_t)x : ENC_PIECE_BYTES;
+}
 }  // namespace
 
 // blocks [f, f + cnt) of the stream whose boundaries the context's tables hold (nb blocks in all): RLE1 bytes + CRCs, suffix
@@ -115,18 +124,22 @@ int cjs::blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32
   // Every piece pays the sort's ~90 launches again (each followed by ~6 us in which its write-back drains, and the tail rounds are
   // launch-bound whatever the piece holds): 100 MB in 2 / 3 / 4 pieces 12.5 / 13.2 / 14.2 ms against 11.7 in one; 2^30 bytes
   // (1,194 blocks) in 1 / 2 / 4 / 8 pieces 117.4 / 111.4 / 109.4 / 111.6 ms.  So: four pieces from 400 MB of blocks on.
-  const uint32_t pieces = (stage_times || !c->tail || (uint64_t)cnt * c->cap < 400000000ull) ? 1u : 4u;
+  // (the rule: enc_pieces.h)
+  const TablePieces tp = table_pieces(cnt, c->cap, enc_piece_bytes(), stage_times, c->tail.p != nullptr);
+  const uint32_t runs = table_piece_count(cnt, tp);
   // One piece: its "tail" stream is the work stream itself, so no event orders the two and the sort's dominant-kernel events stay
   // where bwt_run left them.  The stage timers only ever run with one piece.
-  const bool split = pieces > 1;
+  const bool split = tp.pieces > 1;
   hipStream_t ts = split ? c->tail.p : s;
-  const uint32_t per = (cnt + pieces - 1) / pieces;
   LaunchTimes keep;                                        // the dominant-kernel events of all pieces are resolved together
-  for (uint32_t i = 0, k0 = 0; k0 < cnt; i++, k0 += per) {
-    const uint32_t kc = std::min(per, cnt - k0);
+  uint32_t rounds = 0;                                     // bwt_run reports the rounds of its own blocks: the call reports the most
+  for (uint32_t i = 0; i < runs; i++) {
+    uint32_t k0, kc;
+    table_piece(cnt, tp, i, k0, kc);
     const bool has_last = k0 + kc == cnt;
     if (stage_times) c->timer.start();
     CJS_TRY(bwt_run(s, c->bwt, c->d_blocks + (size_t)k0 * c->cap, kc, c->cap, has_last ? n_last : c->cap, true, c->d_U + (size_t)k0 * c->cap, c->d_pidx + k0, st, stage_times));
+    if (st) { rounds = std::max(rounds, st->bwt_rounds); st->bwt_rounds = rounds; }
     if (stage_times) { st->ms_bwt = c->timer.stop(); c->timer.start(); }
     if (split) {
       if (st) { c->bwt.lt.move_into(keep); }
@@ -145,6 +158,7 @@ int cjs::blocks_through_tables(cjs_ctx* c, const uint8_t* d_in, size_t n, uint32
     CJS_HIP_TRY(hipEventRecord(c->ev_tail, c->tail));
     CJS_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0));
   }
+  if (cnt && env_debug()) fprintf(stderr, "[cjs pieces] blocks [%u, %u) of %u: %u pieces of up to %u blocks\n", f, f + cnt, nb, runs, tp.per);
   return 0;
 }
 
